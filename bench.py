@@ -26,6 +26,31 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured copy)
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this many bytes in all
+DUMP_PIXELS = 1 << 20     # pixels sampled (seeded, repeats removed) when a whole frame would exceed DUMP_BYTES
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(path, fb, z):
+    """--dump-outputs: what a caller of the timed step receives, from its last frame, as <path>/<name>.npy — framebuffer
+    ([h, w, bpp] bytes as float32) and z-buffer ([h, w] float64; None on a multi-rank run, whose ranks hold only their own rows).
+    Frames too large for DUMP_BYTES are reduced to the same seeded sample of pixels on every run of that size: framebuffer
+    [n, bpp], zbuffer [n] and pixel_index [n] (row-major y * w + x, float64).  Returns {name: shape}."""
+    from tinyrenderder_amd import scenes
+    os.makedirs(path, exist_ok=True)
+    H, W, bpp = fb.shape
+    if H * W * (bpp * 4 + (0 if z is None else 8)) <= DUMP_BYTES:
+        out = {"framebuffer": fb.astype(np.float32), "zbuffer": z}
+    else:
+        idx = np.unique(scenes.SplitMix64(DUMP_SEED).u64(DUMP_PIXELS) % np.uint64(H * W))
+        out = {"framebuffer": fb.reshape(H * W, bpp)[idx].astype(np.float32), "zbuffer": None if z is None else z.reshape(H * W)[idx],
+               "pixel_index": idx.astype(np.float64)}
+    shapes = {}
+    for name, a in out.items():
+        if a is not None:
+            np.save(os.path.join(path, name + ".npy"), a)
+            shapes[name] = list(a.shape)
+    return shapes
 
 
 def cpu_baseline(clip, col, W, H, sample):
@@ -227,7 +252,12 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=5, help="steps of the second, profiled loop (phase times, k_raster launch duration)")
     ap.add_argument("--workload", default="c4", choices=["c4", "c2", "c3"],
                     help="c4 (default, the metric's config): 10 M random flat triangles; c2/c3: PHONG head stand-in at 2048/4096")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the framebuffer and z-buffer of the last timed frame to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: a fixed, seeded sample of pixels for large frames)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     exit_code = [0]
 
     import torch
@@ -326,6 +356,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # --dump-outputs: the last timed frame, copied on the device (same stream) before anything else renders on this context;
+    # reading it back and writing the files wait for the end of the run, so that the GPU does not idle before the loops below
+    snapshot = None
+    if args.dump_outputs and rank == 0:
+        snapshot = (shard.framebuffer_tensor(ctx).clone(),
+                    None if use_dist else torch.as_tensor(shard._DevBuf(ctx.zbuffer_ptr, W * H * 8), device="cuda").clone())
     # a second, short loop with profiling ON: HIP events on the context's stream around the phases and right around the k_raster launch
     ctx.set_profiling(True)
     ctx.reset_phase_ms()
@@ -468,7 +504,12 @@ def main():
         if cpu:
             out["cpu_baseline"] = cpu
         if world == 1 and args.workload == "c4" and args.secondary:
-            out["secondary"] = [secondary_workload(nm, dev, 40, 5, check=not args.no_parity and args.cpu_sample > 0) for nm in args.secondary.split(",") if nm]
+            out["secondary"] = [secondary_workload(nm, dev, args.steps, args.warmup, check=not args.no_parity and args.cpu_sample > 0) for nm in args.secondary.split(",") if nm]
+        if snapshot is not None:
+            fb_dev, z_dev = snapshot
+            out["dump_outputs"] = {"dir": args.dump_outputs,
+                                   "arrays": dump_outputs(args.dump_outputs, fb_dev.cpu().numpy().reshape(H, W, 3),
+                                                          None if z_dev is None else z_dev.cpu().numpy().view(np.float64).reshape(H, W))}
         print(json.dumps(out))
         if failed:
             print("PARITY FAILURE: the GPU frame differs from the reference's; no throughput is reported", file=sys.stderr)

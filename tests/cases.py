@@ -162,6 +162,17 @@ CASES = {f.__name__: f for f in (
 FULL_BUFFER_CASES = ("flat_small_64", "odd_dims_101x67", "gray_bpp1_96x64")
 
 
+def vecops_inputs(n=2000):
+    """Inputs of the value-op comparison (tests/golden/make_vecops_golden.py, test_oracle.py): per row v[3], n[3], M[16],
+    v0 v1 v2 b [3 each] and an intensity, plus a packed colour.  Returns (data [n,35] f64, packed [n] u32)."""
+    rng = scenes.SplitMix64(77)
+    data = rng.uniform(n * 35, -3.0, 3.0).reshape(n, 35)
+    data[0, 0:3] = 0.0                                    # normalized(0) returns v
+    data[:, 34] = rng.uniform(n, -0.5, 1.5)
+    packed = (rng.u64(n) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    return data, packed
+
+
 def run_oracle(case, strip=None):
     """Render a case with the CPU oracle; returns (fb, z, stats tuple)."""
     from oracle import orc

@@ -40,13 +40,14 @@ def test_tga_header_layout():
     assert api.tga_encode(img, vflip=False, rle=True)[17] == 0x20 and api.tga_encode(img[..., :1], rle=True)[2] == 11
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not orc.ref_available(), reason="oracle/_ref not built (reference tree absent)")
+# few-colour images of 1 / 3 / 4 bytes per pixel with the files the reference wrote and read (tests/golden/make_tga_random_golden.py)
+RANDOM_GOLD = np.load(os.path.join(HERE, "golden", "tga_random_golden.npz"))
+
+
 def test_tga_random_images_against_reference_binary():
-    rng = np.random.default_rng(5)
     for bpp in (1, 3, 4):
-        img = (rng.integers(0, 3, size=(37, 53, bpp)) * 120).astype(np.uint8)     # few colours: lots of runs
-        assert api.tga_encode(img) == orc.run_reference_tga(img)
+        img = RANDOM_GOLD[f"w{bpp}_img"]
+        assert api.tga_encode(img) == RANDOM_GOLD[f"w{bpp}_file"].tobytes()
 
 
 # ---- reader (tgaimage.cpp:76-160): fixtures decoded by the reference's own read_tga_file ------------------------------
@@ -82,14 +83,12 @@ def test_tga_write_read_round_trip_is_the_references():
         assert np.array_equal(api.tga_decode(api.tga_encode(img, vflip=True, rle=rle)), img[::-1])
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(not orc.ref_available(), reason="oracle/_ref not built (reference tree absent)")
 def test_tga_reader_random_files_against_reference_binary():
-    rng = np.random.default_rng(9)
     for bpp in (1, 3, 4):
-        img = (rng.integers(0, 3, size=(23, 31, bpp)) * 120).astype(np.uint8)
-        for vflip in (False, True):
-            f = bytearray(api.tga_encode(img, vflip, True))
+        for vflip in (0, 1):
+            key = f"r{bpp}_v{vflip}"
+            img, f = RANDOM_GOLD[key + "_img"], RANDOM_GOLD[key + "_file"].tobytes()
+            assert api.tga_encode(img, bool(vflip), True) == f
             for cut in (len(f), len(f) - 7, 60):
-                ref = orc.run_reference_tga_read(bytes(f[:cut]))
-                assert np.array_equal(api.tga_decode(bytes(f[:cut])), ref) and np.array_equal(orc.tga_decode(bytes(f[:cut])), ref)
+                ref = RANDOM_GOLD[f"{key}_cut{cut}"]
+                assert np.array_equal(api.tga_decode(f[:cut]), ref) and np.array_equal(orc.tga_decode(f[:cut]), ref)
