@@ -15,11 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ int x86_cvttsd2si(double d) {
-    // (int)double exactly as the reference's x86-64 build executes it: out of range -> INT_MIN
-    if (!(d > -2147483649.0 && d < 2147483648.0)) return INT_MIN;
-    return (int)d;
-}
 __device__ __forceinline__ double dmin3(double a, double b, double c) { double m = a; if (b < m) m = b; if (c < m) m = c; return m; }
 __device__ __forceinline__ double dmax3(double a, double b, double c) { double m = a; if (m < b) m = b; if (m < c) m = c; return m; }
 __device__ __forceinline__ double dot4(const double* m, const double* v) {
@@ -341,7 +336,8 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_chunk_spine(const uint32_t* _
     }
     if (threadIdx.x == 0) {
         *total64 = running;
-        // The host needs the pair count and the two triangle counts that k_setup left next to it (DevStats: literal_tris, large_tris)
+        // The host needs the pair count and the two triangle counts that k_setup left behind it (DevStats: literal_tris, large_tris at
+        // total64[1] and [2], pinned by the static_asserts under DevStats in trgl_device.h)
         // before it launches the raster: written straight into its pinned memory instead of a copy command on the stream (4.6 us).
         host_copy[0] = running; host_copy[1] = total64[1]; host_copy[2] = total64[2];
         __threadfence_system();
@@ -626,7 +622,7 @@ __global__ __launch_bounds__(256) void k_bounds(const K* __restrict__ keys, cons
     const uint32_t p0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4u;
     if (p0 >= P) return;
     uint32_t k[4];
-    load4<K>(keys, p0, k);                                              // the buffers hold a multiple of 4 entries (grow_pairs)
+    load4<K>(keys, p0, k);                                              // the buffers hold a multiple of 4 entries (pair_capacity)
     uint32_t prev = p0 ? (uint32_t)keys[p0 - 1] : 0u;
     const uint32_t after = (p0 + 4 < P) ? (uint32_t)keys[p0 + 4] : 0u;
 #pragma unroll

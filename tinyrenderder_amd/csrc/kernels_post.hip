@@ -20,16 +20,6 @@ __device__ __forceinline__ double dot4(const double* m, double x, double y, doub
     sum += m[0] * x; sum += m[1] * y; sum += m[2] * z; sum += m[3] * w;
     return sum;
 }
-__device__ __forceinline__ double dmax(double a, double b) { return (a < b) ? b : a; }
-__device__ __forceinline__ double dmin(double a, double b) { return (b < a) ? b : a; }
-__device__ __forceinline__ unsigned long long zkey(double d) {
-    unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double zkey_decode(unsigned long long k) {
-    unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
 
 struct VertexStageParams {
     double mv[16], proj[16];

@@ -16,8 +16,6 @@
 
 namespace {
 
-__device__ __forceinline__ double dmax(double a, double b) { return (a < b) ? b : a; }   // std::max
-__device__ __forceinline__ double dmin(double a, double b) { return (b < a) ? b : a; }   // std::min
 // v_max_f64 as one instruction (a NaN operand yields the other one): for the depth maxima, where a pixel holding NaN can
 // never be written again (z < NaN is false), so leaving it out of a maximum keeps the maximum a valid bound
 __device__ __forceinline__ double vmax(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
@@ -49,10 +47,6 @@ __device__ __forceinline__ float f32_down(double d) {
     return f;
 }
 __device__ __forceinline__ int iclamp(int v, int lo, int hi) { return (v < lo) ? lo : (hi < v) ? hi : v; }
-__device__ __forceinline__ int x86_cvttsd2si(double d) {
-    if (!(d > -2147483649.0 && d < 2147483648.0)) return INT_MIN;
-    return (int)d;
-}
 __device__ __forceinline__ double dot3(const double* a, const double* b) {
     double sum = 0; sum += a[0] * b[0]; sum += a[1] * b[1]; sum += a[2] * b[2]; return sum;   // geometry.h:122-127
 }
@@ -60,10 +54,6 @@ __device__ __forceinline__ void normalized3(const double* v, double* out) {     
     double length = sqrt(dot3(v, v));
     if (length == 0) { out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; return; }
     out[0] = v[0] / length; out[1] = v[1] / length; out[2] = v[2] / length;
-}
-__device__ __forceinline__ unsigned long long zkey(double d) {       // order-preserving u64 key of a double
-    unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 // ---- samplers: model.cpp:415-459 + TGAImage::get tgaimage.cpp:24-30 ----------------------------

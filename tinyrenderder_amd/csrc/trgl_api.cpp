@@ -27,6 +27,32 @@ using namespace trgl;
 static thread_local std::string g_create_error;
 
 struct StageChunk { char* base; size_t cap, used; };
+struct trgl_ctx;
+
+// the growth rule of most device buffers: 25 % + 1024 elements of headroom
+static size_t headroom(size_t need) { return need + need / 4 + 1024; }
+// Device memory owned by the context (or by a caller's scope) and freed with it; `cap` counts elements.
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    // (re)allocate `n` elements; the old contents are not kept (the stream is synchronised before they are freed)
+    int alloc(trgl_ctx* c, size_t n);
+    // at least `need` elements: `ncap` of them (by default headroom(need)) when the buffer has to grow
+    int grow(trgl_ctx* c, size_t need, size_t ncap) { return need <= cap ? TRGL_OK : alloc(c, ncap); }
+    int grow(trgl_ctx* c, size_t need) { return grow(c, need, headroom(need)); }
+};
+// ... and of the pair buffers: a multiple of 4 entries (k_bounds reads 16 bytes at a time), at most 0xffffe000 (grids are sized by
+// cap + 4095 in 32 bits; a flush of 2^32 - 16 pairs and more is refused)
+static size_t pair_capacity(size_t need) {
+    const size_t ncap = (headroom(need) + 3) & ~size_t(3);
+    return ncap > 0xffffe000ull ? 0xffffe000ull : ncap;
+}
+
+// a flush whose first half (setup + binning) has run and whose raster half is still to be launched (trgl_flush_begin)
+struct PendingRaster { bool active = false; FrameParams fp; int flush_kind = 0; uint32_t cap = 0; int cur = 0; uint64_t N = 0; };
 
 struct trgl_ctx {
     int device = 0;
@@ -34,8 +60,8 @@ struct trgl_ctx {
     int W = 0, H = 0, bpp = 0, tiles_x = 0, tiles_y = 0;
     hipStream_t stream = nullptr;       // the stream in use
     hipStream_t own_stream = nullptr;   // created with the context
-    uint8_t* fb = nullptr;
-    double* zb = nullptr;
+    DevBuf<uint8_t> fb;
+    DevBuf<double> zb;
     double vp[16];
     bool clear_pending = true;
     uint32_t clear_color = 0xff000000u;
@@ -44,32 +70,28 @@ struct trgl_ctx {
     int il_tiles = 0, il_world = 1, il_rank = 0;     // interleaved bands instead of one strip (trgl_set_interleave)
 
     DevTexture tex_host[TRGL_MAX_TEXTURES];
-    DevTexture* tex_dev = nullptr;
+    DevBuf<DevTexture> tex_dev;
 
     std::vector<DrawDesc> draws;
     uint64_t queued_tris = 0;
     std::vector<StageChunk> stage;
     int stage_hold = 0;                 // >0 while a draw call has staged data that no DrawDesc references yet
 
-    TriRec* recs = nullptr; TriW* recs_w = nullptr; uint32_t* cnt = nullptr; uint2* tilebox = nullptr;
-    // a flush whose first half (setup + binning) has run and whose raster half is still to be launched (trgl_flush_begin)
-    struct { bool active = false; FrameParams fp; int flush_kind = 0; uint32_t cap = 0; int cur = 0; uint64_t N = 0; bool binned = false; } rp;
+    // per triangle of the flush (grown together, for N + 1 triangles: the record behind the last one is read by k_make_items)
+    DevBuf<TriRec> recs; DevBuf<TriW> recs_w; DevBuf<uint32_t> cnt; DevBuf<uint2> tilebox;
+    PendingRaster rp;
     hipEvent_t ev_pairs = nullptr;      // recorded behind the copy of the flush's pair count into pinned memory
-    uint32_t* idbuf = nullptr; size_t cap_idbuf = 0;        // visibility buffer of PHONG / EYE flushes, [H][W]
-    uint8_t* pp_out = nullptr; size_t cap_pp = 0;           // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
-    uint32_t* blk_sums = nullptr; size_t cap_blk = 0;       // pairs per setup block of 256 triangles
-    uint32_t* chunk_off = nullptr; size_t cap_chunk = 0;    // pairs before every 16th setup block
-    size_t cap_tris = 0;
-    uint32_t* keys[2] = { nullptr, nullptr }; uint32_t* vals[2] = { nullptr, nullptr }; uint16_t* bmask[2] = { nullptr, nullptr };
-    size_t cap_pairs = 0;
-    uint32_t* hist = nullptr; size_t cap_hist = 0;
-    uint32_t* scan_tmp = nullptr; size_t cap_scan = 0;
-    uint32_t* tile_start = nullptr; uint32_t* tile_end = nullptr;
-    uint4* items = nullptr; size_t cap_items = 0; uint32_t* n_items = nullptr;
-    unsigned long long* item_stats = nullptr; size_t cap_item_stats = 0;
-    DrawDesc* draws_dev = nullptr;
-    DrawDesc* draws_pinned = nullptr;
-    DevStats* stats_dev = nullptr;
+    DevBuf<uint32_t> idbuf;             // visibility buffer of PHONG / EYE flushes, [H][W]
+    DevBuf<uint8_t> pp_out;             // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
+    DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
+    DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
+    DevBuf<uint32_t> keys[2], vals[2]; DevBuf<uint16_t> bmask[2];     // (tile, triangle, block mask) pairs, ping-pong; grown together
+    DevBuf<uint32_t> hist, scan_tmp;
+    DevBuf<uint32_t> tile_start;        // tile_start[ntiles] followed by tile_end[ntiles]: cleared together per flush (in 16-byte words)
+    DevBuf<uint4> items; DevBuf<uint32_t> n_items;
+    DevBuf<unsigned long long> item_stats;
+    DevBuf<DrawDesc> draws_dev;
+    DevBuf<DevStats> stats_dev;
     DevStats* stats_pinned = nullptr;
 
     uint64_t triangles_total = 0;       // our_gl.cpp:90 counts every call, host side
@@ -81,6 +103,8 @@ struct trgl_ctx {
     uint64_t flushes_timed = 0;
 
     std::string err;
+
+    uint32_t* tile_end() const { return tile_start.p + (size_t)tiles_x * tiles_y; }
 };
 
 #define HIPCHK(ctx, expr)                                                                      \
@@ -94,45 +118,63 @@ struct trgl_ctx {
 
 #define CHKCTX(ctx) do { if (!(ctx)) return TRGL_E_INVALID; if (hipSetDevice((ctx)->device) != hipSuccess) return TRGL_E_HIP; } while (0)
 
-static int fail(trgl_ctx* c, int code, const char* msg) { c->err = msg; return code; }
+template <class T> int DevBuf<T>::alloc(trgl_ctx* c, size_t n) {
+    if (p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p)); p = nullptr; cap = 0; }
+    HIPCHK(c, hipMalloc((void**)&p, n * sizeof(T)));
+    cap = n;
+    return TRGL_OK;
+}
 
-static unsigned long long zkey_host(double d) {
-    unsigned long long b; std::memcpy(&b, &d, 8);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-static double zkey_decode(unsigned long long k) {
-    unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double d; std::memcpy(&d, &b, 8); return d;
-}
+// pins the staged arrays of a draw call in progress: a flush it triggers does not recycle them
+struct StageHold { trgl_ctx* c; explicit StageHold(trgl_ctx* x) : c(x) { ++c->stage_hold; } ~StageHold() { --c->stage_hold; } };
+
+static int fail(trgl_ctx* c, int code, const char* msg) { c->err = msg; return code; }
 
 static int reset_dev_stats(trgl_ctx* c) {
     DevStats s;
     s.fragments = 0;
-    s.zmin_key = zkey_host(std::numeric_limits<double>::infinity());
-    s.zmax_key = zkey_host(-std::numeric_limits<double>::infinity());
+    s.zmin_key = zkey(std::numeric_limits<double>::infinity());
+    s.zmax_key = zkey(-std::numeric_limits<double>::infinity());
     s.min_x = INT32_MAX; s.min_y = INT32_MAX; s.max_x = INT32_MIN; s.max_y = INT32_MIN;
     s.pairs_total = 0; s.literal_tris = 0; s.large_tris = 0;
     s.zero_pos_key = s.zero_neg_key = TRGL_ZERO_KEY_EMPTY;
     s.zero_locked = 0; s.zero_sign = 0;
     for (int k = 0; k < 16; ++k) s.dbg[k] = 0;
     *c->stats_pinned = s;
-    HIPCHK(c, hipMemcpyAsync(c->stats_dev, c->stats_pinned, sizeof(DevStats), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->stats_dev.p, c->stats_pinned, sizeof(DevStats), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return TRGL_OK;
 }
 
-// (re)allocate a device buffer; the old contents are not kept
-static int realloc_dev(trgl_ctx* c, void** p, size_t bytes) {
-    if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(*p)); *p = nullptr; }
-    HIPCHK(c, hipMalloc(p, bytes));
+// The context's state is about to change: launch the raster half that trgl_flush_begin left pending ...
+static int end_pending_raster(trgl_ctx* c) { return c->rp.active ? trgl_flush_end(c) : TRGL_OK; }
+// ... and submit the queued draws, which were made under the old state
+static int flush_queued(trgl_ctx* c) { return c->draws.empty() ? TRGL_OK : trgl_flush(c); }
+// everything queued, done
+static int flush_sync(trgl_ctx* c) {
+    int r = trgl_flush(c); if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return TRGL_OK;
 }
-template <class T> static int grow(trgl_ctx* c, T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return TRGL_OK;
-    size_t ncap = need + need / 4 + 1024;
-    int r = realloc_dev(c, (void**)&p, ncap * sizeof(T)); if (r) return r;
-    cap = ncap;
-    return TRGL_OK;
+
+// the stream, the fixed-size buffers, the events and the initial state of a new context
+static int init_ctx(trgl_ctx* c) {
+    const size_t npx = (size_t)c->W * c->H, ntiles = (size_t)c->tiles_x * c->tiles_y;
+    HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    c->stream = c->own_stream;
+    int r;
+    if ((r = c->fb.alloc(c, npx * c->bpp)) || (r = c->zb.alloc(c, npx)) || (r = c->tex_dev.alloc(c, TRGL_MAX_TEXTURES))) return r;
+    HIPCHK(c, hipMemset(c->tex_dev.p, 0, sizeof(c->tex_host)));
+    if ((r = c->tile_start.alloc(c, ntiles * 2 + 4))) return r;
+    if ((r = c->n_items.alloc(c, 2))) return r;                    // work items of the flush
+    HIPCHK(c, hipMemset(c->n_items.p, 0, 8));                       // k_fold_stats leaves it at 0 for the next flush
+    if ((r = c->draws_dev.alloc(c, TRGL_MAX_DRAWS)) || (r = c->stats_dev.alloc(c, 1))) return r;
+    HIPCHK(c, hipHostMalloc((void**)&c->stats_pinned, sizeof(DevStats)));
+    for (int i = 0; i < 6; ++i) HIPCHK(c, hipEventCreate(&c->ev[i]));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_pairs, hipEventDisableTiming));
+    // init_viewport(0,0,W,H), our_gl.cpp:59-69
+    trgl_init_viewport(c, 0, 0, c->W, c->H);
+    return reset_dev_stats(c);
 }
 
 extern "C" {
@@ -153,28 +195,7 @@ int trgl_create(int device, int width, int height, int bpp, trgl_ctx** out) {
     c->strip_y0 = 0; c->strip_y1 = height;
     { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) c->num_cus = n; }
     std::memset(c->tex_host, 0, sizeof(c->tex_host));
-    size_t npx = (size_t)width * height, ntiles = (size_t)c->tiles_x * c->tiles_y;
-#define CRE(expr) do { hipError_t e2 = (expr); if (e2 != hipSuccess) { g_create_error = std::string(#expr) + ": " + hipGetErrorString(e2); trgl_destroy(c); return TRGL_E_HIP; } } while (0)
-    CRE(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
-    CRE(hipMalloc((void**)&c->fb, npx * bpp));
-    CRE(hipMalloc((void**)&c->zb, npx * sizeof(double)));
-    CRE(hipMalloc((void**)&c->tex_dev, sizeof(c->tex_host)));
-    CRE(hipMemset(c->tex_dev, 0, sizeof(c->tex_host)));
-    CRE(hipMalloc((void**)&c->tile_start, ntiles * 8 + 16));   // tile_start[ntiles] followed by tile_end[ntiles]: cleared together per flush (in 16-byte words)
-    c->tile_end = c->tile_start + ntiles;
-    CRE(hipMalloc((void**)&c->n_items, 8));                     // work items of the flush
-    CRE(hipMemset(c->n_items, 0, 8));                           // k_fold_stats leaves it at 0 for the next flush
-    CRE(hipMalloc((void**)&c->draws_dev, sizeof(DrawDesc) * TRGL_MAX_DRAWS));
-    CRE(hipHostMalloc((void**)&c->draws_pinned, sizeof(DrawDesc) * TRGL_MAX_DRAWS));
-    CRE(hipMalloc((void**)&c->stats_dev, sizeof(DevStats)));
-    CRE(hipHostMalloc((void**)&c->stats_pinned, sizeof(DevStats)));
-    for (int i = 0; i < 6; ++i) CRE(hipEventCreate(&c->ev[i]));
-    CRE(hipEventCreateWithFlags(&c->ev_pairs, hipEventDisableTiming));
-#undef CRE
-    // init_viewport(0,0,W,H), our_gl.cpp:59-69
-    trgl_init_viewport(c, 0, 0, width, height);
-    if (reset_dev_stats(c) != TRGL_OK) { g_create_error = c->err; trgl_destroy(c); return TRGL_E_HIP; }
+    if (int r = init_ctx(c)) { g_create_error = c->err; trgl_destroy(c); return r; }
     *out = c;
     return TRGL_OK;
 }
@@ -185,25 +206,19 @@ int trgl_destroy(trgl_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& s : c->stage) (void)hipFree(s.base);
     for (int i = 0; i < TRGL_MAX_TEXTURES; ++i) if (c->tex_host[i].data) (void)hipFree((void*)c->tex_host[i].data);
-    void* ptrs[] = { c->fb, c->zb, c->tex_dev, c->recs, c->recs_w, c->bmask[0], c->bmask[1], c->cnt, c->idbuf, c->pp_out, c->blk_sums, c->chunk_off, c->tilebox, c->keys[0], c->keys[1], c->vals[0],
-                     c->vals[1], c->hist, c->scan_tmp, c->tile_start, c->draws_dev, c->stats_dev, c->items, c->n_items, c->item_stats };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (c->draws_pinned) (void)hipHostFree(c->draws_pinned);
     if (c->stats_pinned) (void)hipHostFree(c->stats_pinned);
     for (int i = 0; i < 6; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_pairs) (void)hipEventDestroy(c->ev_pairs);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                   // (the device buffers free themselves)
     return TRGL_OK;
 }
 
 int trgl_set_viewport(trgl_ctx* c, const double m[16]) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
+    int r = end_pending_raster(c); if (r) return r;
     if (!m) return fail(c, TRGL_E_INVALID, "trgl_set_viewport: null matrix");
-    if (!c->draws.empty() && std::memcmp(c->vp, m, sizeof(c->vp)) != 0) {   // rasterize() reads Viewport at call time
-        int r = trgl_flush(c); if (r) return r;
-    }
+    if (std::memcmp(c->vp, m, sizeof(c->vp)) != 0 && (r = flush_queued(c))) return r;   // rasterize() reads Viewport at call time
     std::memcpy(c->vp, m, sizeof(c->vp));
     return TRGL_OK;
 }
@@ -219,8 +234,8 @@ int trgl_init_viewport(trgl_ctx* c, int x, int y, int w, int h) {          // ou
 
 int trgl_clear(trgl_ctx* c, const uint8_t bgra[4], double z_clear) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
-    if (!c->draws.empty()) { int r = trgl_flush(c); if (r) return r; }      // earlier draws come first
+    int r = end_pending_raster(c); if (r) return r;
+    if ((r = flush_queued(c))) return r;                                     // earlier draws come first
     static const uint8_t dflt[4] = { 0, 0, 0, 255 };                         // TGAColor(), tgaimage.h:33
     const uint8_t* p = bgra ? bgra : dflt;
     c->clear_color = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
@@ -231,9 +246,9 @@ int trgl_clear(trgl_ctx* c, const uint8_t bgra[4], double z_clear) {
 
 int trgl_upload_texture(trgl_ctx* c, int slot, const uint8_t* texels, int w, int h, int bpp) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
+    int r = end_pending_raster(c); if (r) return r;
     if (slot < 0 || slot >= TRGL_MAX_TEXTURES) return fail(c, TRGL_E_INVALID, "trgl_upload_texture: bad slot");
-    if (!c->draws.empty()) { int r = trgl_flush(c); if (r) return r; }
+    if ((r = flush_queued(c))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->tex_host[slot].data) { HIPCHK(c, hipFree((void*)c->tex_host[slot].data)); c->tex_host[slot] = DevTexture{ nullptr, 0, 0, 0, 0 }; }
     if (texels && w > 0 && h > 0) {
@@ -244,15 +259,15 @@ int trgl_upload_texture(trgl_ctx* c, int slot, const uint8_t* texels, int w, int
         HIPCHK(c, hipMemcpy(d, texels, bytes, hipMemcpyHostToDevice));
         c->tex_host[slot] = DevTexture{ d, w, h, bpp, 0 };
     }
-    HIPCHK(c, hipMemcpy(c->tex_dev, c->tex_host, sizeof(c->tex_host), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->tex_dev.p, c->tex_host, sizeof(c->tex_host), hipMemcpyHostToDevice));
     return TRGL_OK;
 }
 
 int trgl_set_strip(trgl_ctx* c, int y0, int y1) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
+    int r = end_pending_raster(c); if (r) return r;
     if (y0 < 0 || y1 > c->H || y0 > y1) return fail(c, TRGL_E_INVALID, "trgl_set_strip: need 0 <= y0 <= y1 <= H");
-    if (!c->draws.empty()) { int r = trgl_flush(c); if (r) return r; }
+    if ((r = flush_queued(c))) return r;
     c->strip_y0 = y0; c->strip_y1 = y1;
     c->il_tiles = 0; c->il_world = 1; c->il_rank = 0;
     return TRGL_OK;
@@ -260,10 +275,10 @@ int trgl_set_strip(trgl_ctx* c, int y0, int y1) {
 
 int trgl_set_interleave(trgl_ctx* c, int band_rows, int rank, int world) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
+    int r = end_pending_raster(c); if (r) return r;
     if (band_rows <= 0 || band_rows % TRGL_TILE || world < 1 || rank < 0 || rank >= world)
         return fail(c, TRGL_E_INVALID, "trgl_set_interleave: band_rows must be a positive multiple of 32, 0 <= rank < world");
-    if (!c->draws.empty()) { int r = trgl_flush(c); if (r) return r; }
+    if ((r = flush_queued(c))) return r;
     c->strip_y0 = 0; c->strip_y1 = c->H;
     c->il_tiles = world > 1 ? band_rows / TRGL_TILE : 0; c->il_world = world; c->il_rank = rank;
     return TRGL_OK;
@@ -302,7 +317,7 @@ static int stage_copy(trgl_ctx* c, const void* src, size_t bytes, void** dev) {
 int trgl_draw(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip, const double* vary,
               const uint32_t* colors, uint64_t n, int mem_kind) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
+    int r = end_pending_raster(c); if (r) return r;
     if (kind < 0 || kind >= TRGL_NUM_SHADERS) return fail(c, TRGL_E_INVALID, "trgl_draw: unknown shader kind");
     if (n == 0) return TRGL_OK;
     if (!clip) return fail(c, TRGL_E_INVALID, "trgl_draw: clip is null");
@@ -311,13 +326,13 @@ int trgl_draw(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip,
     if ((kind == TRGL_SHADER_PHONG || kind == TRGL_SHADER_EYE) && !u) return fail(c, TRGL_E_INVALID, "trgl_draw: PHONG/EYE need uniforms");
     if (kind == TRGL_SHADER_CHECKER && (!u || u->reserved < 1)) return fail(c, TRGL_E_INVALID, "trgl_draw: CHECKER needs uniforms with reserved = cells >= 1");
     if (mem_kind != TRGL_MEM_HOST && mem_kind != TRGL_MEM_DEVICE) return fail(c, TRGL_E_INVALID, "trgl_draw: bad mem_kind");
-    if (c->queued_tris + n > 0xffffffffull) { int r = trgl_flush(c); if (r) return r; }
+    if (c->queued_tris + n > 0xffffffffull && (r = trgl_flush(c))) return r;
     if (n > 0xffffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_draw: more than 2^32-1 triangles in one draw");
 
     const double* dclip = clip; const double* dvary = K ? vary : nullptr; const uint32_t* dcol = colors;
-    struct Hold { trgl_ctx* c; Hold(trgl_ctx* x) : c(x) { ++c->stage_hold; } ~Hold() { --c->stage_hold; } } hold(c);
+    StageHold hold(c);
     if (mem_kind == TRGL_MEM_HOST) {
-        void* p = nullptr; int r;
+        void* p = nullptr;
         if ((r = stage_copy(c, clip, n * 12 * sizeof(double), &p))) return r;
         dclip = (const double*)p;
         if (K) { if ((r = stage_copy(c, vary, n * K * sizeof(double), &p))) return r; dvary = (const double*)p; }
@@ -326,7 +341,7 @@ int trgl_draw(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip,
     // a record addresses its triangle as (draw index, 24-bit index): split larger submissions
     for (uint64_t done = 0; done < n;) {
         uint64_t m = n - done; if (m > TRGL_DRAW_MAX_TRIS) m = TRGL_DRAW_MAX_TRIS;
-        if (c->draws.size() >= TRGL_MAX_DRAWS || c->queued_tris + m > TRGL_FLUSH_MAX_TRIS) { int r = trgl_flush(c); if (r) return r; }
+        if ((c->draws.size() >= TRGL_MAX_DRAWS || c->queued_tris + m > TRGL_FLUSH_MAX_TRIS) && (r = trgl_flush(c))) return r;
         DrawDesc d; std::memset(&d, 0, sizeof(d));
         d.n = (uint32_t)m; d.first = (uint32_t)c->queued_tris; d.kind = kind; d.K = K;
         if (u) d.u = *u; else { d.u.tex_diffuse = d.u.tex_normal = d.u.tex_specular = -1; }
@@ -343,7 +358,7 @@ int trgl_draw(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip,
 int trgl_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
                       int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
+    int r = end_pending_raster(c); if (r) return r;
     if (kind != TRGL_SHADER_PHONG && kind != TRGL_SHADER_EYE) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: kind must be PHONG or EYE");
     if (!u || !projection || !vertices || !indices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: null argument");
     if (stride < 8) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: vertex stride must be >= 8 doubles (pos3, normal3, uv2)");
@@ -351,8 +366,8 @@ int trgl_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const doubl
     if (n_faces == 0) return TRGL_OK;
     if (n_faces > 0xffffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, "trgl_draw_indexed: too many faces in one call");
     const double* dv = vertices; const uint32_t* di = indices;
-    void* p = nullptr; int r;
-    struct Hold { trgl_ctx* c; Hold(trgl_ctx* x) : c(x) { ++c->stage_hold; } ~Hold() { --c->stage_hold; } } hold(c);
+    void* p = nullptr;
+    StageHold hold(c);
     if (mem_kind == TRGL_MEM_HOST) {
         for (uint64_t k = 0; k < 3 * n_faces; ++k)
             if (indices[k] >= n_vertices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: index out of range");
@@ -376,8 +391,6 @@ void trgl_ssao_defaults(trgl_ssao_params* p) {      // main.cpp:317-321
     p->num_directions = 8; p->steps_per_direction = 8; p->sample_radius = 16.0; p->occlusion_threshold = 1e-3; p->intensity = 0.35;
 }
 
-static int flush_sync(trgl_ctx* c);
-
 int trgl_postprocess(trgl_ctx* c, const trgl_ssao_params* params, uint8_t* zimg, uint8_t* ao, uint8_t* fin) {
     CHKCTX(c);
     trgl_ssao_params sp; trgl_ssao_defaults(&sp);
@@ -388,24 +401,24 @@ int trgl_postprocess(trgl_ctx* c, const trgl_ssao_params* params, uint8_t* zimg,
     const size_t npx = (size_t)c->W * c->H;
     // three [H][W][3] images, each at a 16-byte boundary (the kernels store dwords: W * H need not be a multiple of 4), then the keys
     const size_t img = (npx * 3 + 15) & ~size_t(15);
-    if ((r = grow(c, c->pp_out, c->cap_pp, img * 3 + 64))) return r;      // allocated once per context, not per call
-    uint8_t* d_out = c->pp_out;
+    if ((r = c->pp_out.grow(c, img * 3 + 64))) return r;      // allocated once per context, not per call
+    uint8_t* d_out = c->pp_out.p;
     unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(d_out + img * 3);
     uint8_t* d_z = d_out; uint8_t* d_ao = d_out + img; uint8_t* d_fin = d_out + img * 2;
     hipStream_t s = c->stream;
-    if (zimg) launch_zimage(s, c->zb, c->W, c->H, d_keys, d_z);
+    if (zimg) launch_zimage(s, c->zb.p, c->W, c->H, d_keys, d_z);
     if (ao || fin) {
         double dx[16], dy[16];
         for (int d = 0; d < sp.num_directions; ++d) {         // main.cpp:333-334, host libm as in the reference
             double angle = 2.0 * 3.14159265358979323846 * d / sp.num_directions;
             dx[d] = std::cos(angle); dy[d] = std::sin(angle);
         }
-        launch_ssao(s, c->zb, c->W, c->H, dx, dy, sp.num_directions, sp.steps_per_direction, sp.sample_radius,
+        launch_ssao(s, c->zb.p, c->W, c->H, dx, dy, sp.num_directions, sp.steps_per_direction, sp.sample_radius,
                     sp.occlusion_threshold, sp.intensity, d_ao);
     }
     if (fin) {
         if (c->bpp < 3) return fail(c, TRGL_E_UNSUPPORTED, "trgl_postprocess: composite needs an RGB(A) framebuffer");
-        launch_composite(s, c->fb, c->bpp, d_ao, c->W, c->H, d_fin);
+        launch_composite(s, c->fb.p, c->bpp, d_ao, c->W, c->H, d_fin);
     }
     HIPCHK(c, hipGetLastError());
     if (zimg) HIPCHK(c, hipMemcpyAsync(zimg, d_z, npx * 3, hipMemcpyDeviceToHost, s));
@@ -440,43 +453,56 @@ int trgl_flush(trgl_ctx* c) {
 static int queue_binning(trgl_ctx* c, const FrameParams& fp, uint32_t cap, int* cur_out) {
     hipStream_t s = c->stream;
     const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
-    const unsigned long long* pairs_dev = &c->stats_dev->pairs_total;
+    const unsigned long long* pairs_dev = &c->stats_dev.p->pairs_total;
     int r;
     uint32_t blk_base = 0;
     const bool key16 = ntiles <= 65536;        // tile indices as 16-bit keys: a third less traffic in every binning kernel
     for (auto& d : c->draws) {
-        launch_expand(s, fp, d.first, d.n, c->tiles_x, c->cnt, c->blk_sums, c->chunk_off, blk_base, c->tilebox, c->keys[0], key16, c->vals[0], c->bmask[0], pairs_dev, cap);
+        launch_expand(s, fp, d.first, d.n, c->tiles_x, c->cnt.p, c->blk_sums.p, c->chunk_off.p, blk_base, c->tilebox.p, c->keys[0].p, key16, c->vals[0].p,
+                      c->bmask[0].p, pairs_dev, cap);
         blk_base += setup_num_blocks(d.n);
     }
     int key_bits = 1; while ((size_t(1) << key_bits) < ntiles) ++key_bits;
     int passes = (key_bits + 7) / 8;
     int bits_per = (key_bits + passes - 1) / passes;
     size_t hist_need = ((size_t)radix_num_workers(cap) << bits_per) + 16;
-    if ((r = grow(c, c->hist, c->cap_hist, hist_need))) return r;
-    if ((r = grow(c, c->scan_tmp, c->cap_scan, 256 + 16))) return r;   // the digit totals of a pass (k_radix_scan_rows)
+    if ((r = c->hist.grow(c, hist_need))) return r;
+    if ((r = c->scan_tmp.grow(c, 256 + 16))) return r;   // the digit totals of a pass (k_radix_scan_rows)
     int cur = 0;
     for (int ps = 0; ps < passes; ++ps) {
-        launch_radix_pass(s, c->keys[cur], c->vals[cur], c->bmask[cur], c->keys[cur ^ 1], c->vals[cur ^ 1], c->bmask[cur ^ 1], key16, pairs_dev, cap, ps * bits_per, bits_per,
-                          c->hist, c->scan_tmp);
+        launch_radix_pass(s, c->keys[cur].p, c->vals[cur].p, c->bmask[cur].p, c->keys[cur ^ 1].p, c->vals[cur ^ 1].p, c->bmask[cur ^ 1].p, key16, pairs_dev, cap,
+                          ps * bits_per, bits_per, c->hist.p, c->scan_tmp.p);
         cur ^= 1;
     }
-    launch_bounds(s, c->keys[cur], key16, pairs_dev, cap, c->tile_start, c->tile_end);
+    launch_bounds(s, c->keys[cur].p, key16, pairs_dev, cap, c->tile_start.p, c->tile_end());
     *cur_out = cur;
     return TRGL_OK;
 }
 
+// the six pair buffers grow together, to pair_capacity(need)
 static int grow_pairs(trgl_ctx* c, size_t need) {
-    if (need <= c->cap_pairs) return TRGL_OK;
-    size_t ncap = (need + need / 4 + 1024 + 3) & ~size_t(3);     // a multiple of 4 entries: k_bounds reads 16 bytes at a time
-    if (ncap > 0xffffe000ull) ncap = 0xffffe000ull;        // (grids are sized by cap + 4095 in 32 bits; a flush of 2^32 - 16 pairs and more is refused)
+    const size_t ncap = pair_capacity(need);
     int r;
-    for (int k = 0; k < 2; ++k) {
-        if ((r = realloc_dev(c, (void**)&c->keys[k], ncap * 4))) return r;
-        if ((r = realloc_dev(c, (void**)&c->vals[k], ncap * 4))) return r;
-        if ((r = realloc_dev(c, (void**)&c->bmask[k], ncap * 2))) return r;
-    }
-    c->cap_pairs = ncap;
+    for (int k = 0; k < 2; ++k)
+        if ((r = c->keys[k].grow(c, need, ncap)) || (r = c->vals[k].grow(c, need, ncap)) || (r = c->bmask[k].grow(c, need, ncap))) return r;
     return TRGL_OK;
+}
+
+// what the kernels of the next flush need to know of the context's state
+static FrameParams frame_params(const trgl_ctx* c) {
+    FrameParams fp; std::memset(&fp, 0, sizeof(fp));
+    fp.fb = c->fb.p; fp.zb = c->zb.p; fp.W = c->W; fp.H = c->H; fp.bpp = c->bpp;
+    fp.tiles_x = c->tiles_x; fp.tiles_y = c->tiles_y;
+    fp.strip_y0 = c->strip_y0; fp.strip_y1 = c->strip_y1;
+    fp.strip_ty0 = c->strip_y0 / TRGL_TILE;
+    fp.strip_ty1 = (c->strip_y1 + TRGL_TILE - 1) / TRGL_TILE;
+    if (c->strip_y1 <= c->strip_y0) fp.strip_ty1 = fp.strip_ty0;
+    fp.il_tiles = c->il_tiles; fp.il_world = c->il_world; fp.il_rank = c->il_rank;
+    fp.init_from_clear = c->clear_pending ? 1 : 0;
+    fp.n_tris = (uint32_t)c->queued_tris;
+    fp.clear_color = c->clear_color; fp.clear_z = c->clear_z;
+    std::memcpy(fp.vp, c->vp, sizeof(fp.vp));
+    return fp;
 }
 
 // First half of a flush: per-triangle setup and the stable tile binning.  Touches neither the framebuffer nor the
@@ -494,64 +520,48 @@ int trgl_flush_begin(trgl_ctx* c) {
     const uint64_t N = c->queued_tris;
     const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
     hipStream_t s = c->stream;
-
-    FrameParams fp; std::memset(&fp, 0, sizeof(fp));
-    fp.fb = c->fb; fp.zb = c->zb; fp.W = c->W; fp.H = c->H; fp.bpp = c->bpp;
-    fp.tiles_x = c->tiles_x; fp.tiles_y = c->tiles_y;
-    fp.strip_y0 = c->strip_y0; fp.strip_y1 = c->strip_y1;
-    fp.strip_ty0 = c->strip_y0 / TRGL_TILE;
-    fp.strip_ty1 = (c->strip_y1 + TRGL_TILE - 1) / TRGL_TILE;
-    if (c->strip_y1 <= c->strip_y0) fp.strip_ty1 = fp.strip_ty0;
-    fp.il_tiles = c->il_tiles; fp.il_world = c->il_world; fp.il_rank = c->il_rank;
-    fp.init_from_clear = c->clear_pending ? 1 : 0;
-    fp.n_tris = (uint32_t)c->queued_tris;
-    fp.clear_color = c->clear_color; fp.clear_z = c->clear_z;
-    std::memcpy(fp.vp, c->vp, sizeof(fp.vp));
+    FrameParams fp = frame_params(c);
 
     int flush_kind = c->draws.empty() ? TRGL_SHADER_FLAT : c->draws[0].kind;     // one kind for the whole flush, or -1
     for (auto& d : c->draws) if (d.kind != flush_kind) flush_kind = -1;
     bool shade_later = false;
     for (auto& d : c->draws) if (d.kind == TRGL_SHADER_PHONG || d.kind == TRGL_SHADER_EYE) shade_later = true;
     if (shade_later) {                                                            // shaded once per visible pixel (k_shade)
-        if ((r = grow(c, c->idbuf, c->cap_idbuf, (size_t)c->W * c->H))) return r;
-        fp.idbuf = c->idbuf;
+        if ((r = c->idbuf.grow(c, (size_t)c->W * c->H))) return r;
+        fp.idbuf = c->idbuf.p;
     }
 
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], s));
     uint32_t cap = 0;
     int cur = 0;
     if (N) {
-        // grow per-triangle buffers together
-        if (N + 1 > c->cap_tris) {                     // (+ 1: the record behind the last one, k_make_items)
-            size_t ncap = N + N / 4 + 1024;
-            if ((r = realloc_dev(c, (void**)&c->recs, ncap * sizeof(TriRec)))) return r;
-            if ((r = realloc_dev(c, (void**)&c->recs_w, ncap * sizeof(TriW)))) return r;
-            if ((r = realloc_dev(c, (void**)&c->cnt, ncap * 4))) return r;
-            if ((r = realloc_dev(c, (void**)&c->tilebox, ncap * sizeof(uint2)))) return r;
-            c->cap_tris = ncap;
-        }
-        if (c->cap_pairs == 0 && (r = grow_pairs(c, (size_t)2 * N + 4096))) return r;      // first flush: a guess, checked in trgl_flush_end
+        // the per-triangle buffers grow together (+ 1: the record behind the last one, k_make_items)
+        const size_t tcap = headroom(N);
+        if ((r = c->recs.grow(c, N + 1, tcap)) || (r = c->recs_w.grow(c, N + 1, tcap)) || (r = c->cnt.grow(c, N + 1, tcap)) ||
+            (r = c->tilebox.grow(c, N + 1, tcap))) return r;
+        if (c->keys[0].cap == 0 && (r = grow_pairs(c, (size_t)2 * N + 4096))) return r;      // first flush: a guess, checked in trgl_flush_end
         uint32_t nblk = 0;
         for (auto& d : c->draws) nblk += setup_num_blocks(d.n);
-        if ((r = grow(c, c->blk_sums, c->cap_blk, (size_t)nblk + 16))) return r;
-        if ((r = grow(c, c->chunk_off, c->cap_chunk, (size_t)nblk / 16 + 16))) return r;
+        if ((r = c->blk_sums.grow(c, (size_t)nblk + 16))) return r;
+        if ((r = c->chunk_off.grow(c, (size_t)nblk / 16 + 16))) return r;
         {
             uint32_t blk_base = 0;
             for (size_t i = 0; i < c->draws.size(); ++i) {
-                launch_setup(s, fp, c->draws[i], c->draws_dev, (int)i, c->draws[i].n, c->recs, c->recs_w, c->cnt, c->tilebox, c->stats_dev, c->blk_sums, blk_base);
+                launch_setup(s, fp, c->draws[i], c->draws_dev.p, (int)i, c->draws[i].n, c->recs.p, c->recs_w.p, c->cnt.p, c->tilebox.p, c->stats_dev.p,
+                             c->blk_sums.p, blk_base);
                 blk_base += setup_num_blocks(c->draws[i].n);
             }
         }
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], s));
         // (+ literal_tris, large_tris into pinned memory; the kernel also clears tile_start and tile_end)
-        launch_chunk_spine(s, c->blk_sums, nblk, c->chunk_off, &c->stats_dev->pairs_total, &c->stats_pinned->pairs_total,
-                           c->tile_start, (ntiles * 8 + 15) & ~size_t(15));
+        launch_chunk_spine(s, c->blk_sums.p, nblk, c->chunk_off.p, &c->stats_dev.p->pairs_total, &c->stats_pinned->pairs_total,
+                           c->tile_start.p, (ntiles * 8 + 15) & ~size_t(15));
         HIPCHK(c, hipEventRecord(c->ev_pairs, s));
-        cap = (uint32_t)c->cap_pairs;
+        cap = (uint32_t)c->keys[0].cap;
         if ((r = queue_binning(c, fp, cap, &cur))) return r;
     } else {
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], s));
-        HIPCHK(c, hipMemsetAsync(c->tile_start, 0, ntiles * 8, s));
+        HIPCHK(c, hipMemsetAsync(c->tile_start.p, 0, ntiles * 8, s));
     }
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], s));
     c->rp.active = true; c->rp.fp = fp; c->rp.flush_kind = flush_kind; c->rp.cap = cap; c->rp.cur = cur; c->rp.N = N;
@@ -581,29 +591,24 @@ int trgl_flush_end(trgl_ctx* c) {
         P = (uint32_t)P64;
         if (P > c->rp.cap) {                               // the buffers were too small: the queued binning did nothing
             if ((r = grow_pairs(c, P))) return r;
-            if ((r = queue_binning(c, fp, (uint32_t)c->cap_pairs, &cur))) return r;
+            if ((r = queue_binning(c, fp, (uint32_t)c->keys[0].cap, &cur))) return r;
             if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], s));
         }
     }
     // with no pairs every tile list is empty; the kernel must not (and does not) dereference these, but give it
     // valid addresses anyway
-    const TriRec* recs_arg = c->recs ? c->recs : reinterpret_cast<const TriRec*>(c->tile_start);
-    const uint32_t* vals_arg = (P && c->vals[cur]) ? c->vals[cur] : c->tile_start;
-    const uint16_t* bmask_arg = (P && c->bmask[cur]) ? c->bmask[cur] : reinterpret_cast<const uint16_t*>(c->tile_start);
+    const TriRec* recs_arg = c->recs.p ? c->recs.p : reinterpret_cast<const TriRec*>(c->tile_start.p);
+    const uint32_t* vals_arg = (P && c->vals[cur].p) ? c->vals[cur].p : c->tile_start.p;
+    const uint16_t* bmask_arg = (P && c->bmask[cur].p) ? c->bmask[cur].p : reinterpret_cast<const uint16_t*>(c->tile_start.p);
     // one work item (a workgroup of four block waves) per row of blocks of every owned tile
     const uint32_t max_items = raster_max_items(fp);
-    if ((r = grow(c, c->items, c->cap_items, (size_t)max_items + 64))) return r;
-    if ((r = grow(c, c->item_stats, c->cap_item_stats, ((size_t)max_items + 64) * 4))) return r;
+    if ((r = c->items.grow(c, (size_t)max_items + 64))) return r;
+    if ((r = c->item_stats.grow(c, ((size_t)max_items + 64) * 4))) return r;
     // k_setup counted the triangles that are not well scaled (it came over with the pair count): without any, the kernel without the literal path
     const bool all_well_scaled = N == 0 || c->stats_pinned->literal_tris == 0;
     fp.zq_cull = (N != 0 && c->stats_pinned->large_tris != 0) ? 1 : 0;      // (k_setup counted them; the count came over with the pair count)
-    if (std::getenv("TRGL_DEBUG_PTRS")) {        // diagnostics: where the buffers of this flush live
-        std::fprintf(stderr, "trgl ptrs: fb %p +%zu  zb %p +%zu  recs %p +%zu  recs_w %p  vals %p bmask %p cap_pairs %zu P %u  items %p cap %zu  item_stats %p  tile_start %p  N %llu max_items %u\n",
-                     (void*)c->fb, (size_t)c->W * c->H * c->bpp, (void*)c->zb, (size_t)c->W * c->H * 8, (const void*)recs_arg, c->cap_tris * sizeof(TriRec), (void*)c->recs_w,
-                     (const void*)vals_arg, (const void*)bmask_arg, c->cap_pairs, P, (void*)c->items, c->cap_items, (void*)c->item_stats, (void*)c->tile_start, (unsigned long long)N, max_items);
-    }
-    launch_raster(s, fp, flush_kind, all_well_scaled, recs_arg, c->recs_w, vals_arg, bmask_arg, c->tile_start, c->tile_end, c->draws_dev, c->tex_dev, c->stats_dev,
-                  max_items, c->items, c->n_items, c->item_stats,
+    launch_raster(s, fp, flush_kind, all_well_scaled, recs_arg, c->recs_w.p, vals_arg, bmask_arg, c->tile_start.p, c->tile_end(), c->draws_dev.p, c->tex_dev.p,
+                  c->stats_dev.p, max_items, c->items.p, c->n_items.p, c->item_stats.p,
                   c->profiling ? c->ev[4] : nullptr, c->profiling ? c->ev[5] : nullptr);
     if (c->profiling) { HIPCHK(c, hipEventRecord(c->ev[3], s)); c->events_pending = true; }
     HIPCHK(c, hipGetLastError());
@@ -625,13 +630,7 @@ int trgl_flush_end(trgl_ctx* c) {
 
 int trgl_sync(trgl_ctx* c) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return TRGL_OK;
-}
-
-static int flush_sync(trgl_ctx* c) {
-    int r = trgl_flush(c); if (r) return r;
+    int r = end_pending_raster(c); if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return TRGL_OK;
 }
@@ -640,28 +639,28 @@ int trgl_read_framebuffer(trgl_ctx* c, uint8_t* dst) {
     CHKCTX(c);
     if (!dst) return fail(c, TRGL_E_INVALID, "null destination");
     int r = flush_sync(c); if (r) return r;
-    HIPCHK(c, hipMemcpy(dst, c->fb, (size_t)c->W * c->H * c->bpp, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->fb.p, (size_t)c->W * c->H * c->bpp, hipMemcpyDeviceToHost));
     return TRGL_OK;
 }
 int trgl_write_framebuffer(trgl_ctx* c, const uint8_t* src) {
     CHKCTX(c);
     if (!src) return fail(c, TRGL_E_INVALID, "null source");
     int r = flush_sync(c); if (r) return r;
-    HIPCHK(c, hipMemcpy(c->fb, src, (size_t)c->W * c->H * c->bpp, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->fb.p, src, (size_t)c->W * c->H * c->bpp, hipMemcpyHostToDevice));
     return TRGL_OK;
 }
 int trgl_read_zbuffer(trgl_ctx* c, double* dst) {
     CHKCTX(c);
     if (!dst) return fail(c, TRGL_E_INVALID, "null destination");
     int r = flush_sync(c); if (r) return r;
-    HIPCHK(c, hipMemcpy(dst, c->zb, (size_t)c->W * c->H * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(dst, c->zb.p, (size_t)c->W * c->H * sizeof(double), hipMemcpyDeviceToHost));
     return TRGL_OK;
 }
 int trgl_write_zbuffer(trgl_ctx* c, const double* src) {
     CHKCTX(c);
     if (!src) return fail(c, TRGL_E_INVALID, "null source");
     int r = flush_sync(c); if (r) return r;
-    HIPCHK(c, hipMemcpy(c->zb, src, (size_t)c->W * c->H * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->zb.p, src, (size_t)c->W * c->H * sizeof(double), hipMemcpyHostToDevice));
     return TRGL_OK;
 }
 
@@ -669,7 +668,7 @@ int trgl_get_stats(trgl_ctx* c, trgl_stats* out) {
     CHKCTX(c);
     if (!out) return fail(c, TRGL_E_INVALID, "null stats");
     int r = flush_sync(c); if (r) return r;
-    HIPCHK(c, hipMemcpy(c->stats_pinned, c->stats_dev, sizeof(DevStats), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(c->stats_pinned, c->stats_dev.p, sizeof(DevStats), hipMemcpyDeviceToHost));
     const DevStats& s = *c->stats_pinned;
     out->triangles_rasterized = c->triangles_total;
     out->fragments_drawn = s.fragments;
@@ -699,8 +698,8 @@ int trgl_format_stats(const trgl_stats* s, char* buf, size_t buflen) {   // our_
     return (n < 0 || (size_t)n >= buflen) ? TRGL_E_INVALID : TRGL_OK;
 }
 
-void* trgl_framebuffer_device_ptr(trgl_ctx* c) { return c ? c->fb : nullptr; }
-void* trgl_zbuffer_device_ptr(trgl_ctx* c) { return c ? c->zb : nullptr; }
+void* trgl_framebuffer_device_ptr(trgl_ctx* c) { return c ? c->fb.p : nullptr; }
+void* trgl_zbuffer_device_ptr(trgl_ctx* c) { return c ? c->zb.p : nullptr; }
 void* trgl_stream(trgl_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 int trgl_obj_load(const char* path, double** vertices, uint64_t* n_vertices, uint32_t** indices, uint64_t* n_faces) {
@@ -765,15 +764,14 @@ int trgl_selftest_division(trgl_ctx* c, uint64_t samples, uint64_t seed, uint64_
     CHKCTX(c);
     if (!mismatches) return fail(c, TRGL_E_INVALID, "null mismatches");
     int r = trgl_flush(c); if (r) return r;
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, 8));
-    HIPCHK(c, hipMemsetAsync(d, 0, 8, c->stream));
+    DevBuf<unsigned long long> d;
+    if ((r = d.alloc(c, 1))) return r;
+    HIPCHK(c, hipMemsetAsync(d.p, 0, 8, c->stream));
     unsigned long long per_thread = (samples + 1024ull * 256 - 1) / (1024ull * 256);
-    launch_selftest_division(c->stream, per_thread, seed, d);
+    launch_selftest_division(c->stream, per_thread, seed, d.p);
     unsigned long long h = 0;
-    HIPCHK(c, hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h, d.p, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(d));
     *mismatches = h;
     return TRGL_OK;
 }
@@ -784,23 +782,19 @@ int trgl_selftest_sampler(trgl_ctx* c, int slot, const double* uv, uint64_t n, u
     if (slot < 0 || slot >= TRGL_MAX_TEXTURES) return fail(c, TRGL_E_INVALID, "trgl_selftest_sampler: bad slot");
     int r = trgl_flush(c); if (r) return r;
     if (!n) return TRGL_OK;
-    double* d_uv = nullptr; uint8_t* d_out = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_uv, n * 16));
-    HIPCHK(c, hipMalloc((void**)&d_out, n * 5));
-    HIPCHK(c, hipMemcpyAsync(d_uv, uv, n * 16, hipMemcpyHostToDevice, c->stream));
-    launch_selftest_sampler(c->stream, c->tex_dev, slot, d_uv, n, d_out);
-    HIPCHK(c, hipMemcpyAsync(out, d_out, n * 5, hipMemcpyDeviceToHost, c->stream));
+    DevBuf<double> d_uv; DevBuf<uint8_t> d_out;
+    if ((r = d_uv.alloc(c, n * 2)) || (r = d_out.alloc(c, n * 5))) return r;
+    HIPCHK(c, hipMemcpyAsync(d_uv.p, uv, n * 16, hipMemcpyHostToDevice, c->stream));
+    launch_selftest_sampler(c->stream, c->tex_dev.p, slot, d_uv.p, n, d_out.p);
+    HIPCHK(c, hipMemcpyAsync(out, d_out.p, n * 5, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(d_uv)); HIPCHK(c, hipFree(d_out));
     return TRGL_OK;
 }
 
 int trgl_set_stream(trgl_ctx* c, void* hip_stream, int use_own) {
     CHKCTX(c);
-    if (c->rp.active) { int fr = trgl_flush_end(c); if (fr) return fr; }
-    int r = TRGL_OK;
-    if (!c->draws.empty()) r = trgl_flush(c);      // a pending clear alone needs no launch: it stays pending
-    if (r) return r;
+    int r = end_pending_raster(c); if (r) return r;
+    if ((r = flush_queued(c))) return r;           // a pending clear alone needs no launch: it stays pending
     if ((r = resolve_events(c))) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // a NULL hipStream_t is a real stream (the legacy default stream, which is what torch's current stream
@@ -833,7 +827,7 @@ int trgl_reset_phase_ms(trgl_ctx* c) {
 extern "C" int trgl_debug_counters(trgl_ctx* c, unsigned long long out[16]) {
     CHKCTX(c);
     int r = flush_sync(c); if (r) return r;
-    HIPCHK(c, hipMemcpy(c->stats_pinned, c->stats_dev, sizeof(DevStats), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(c->stats_pinned, c->stats_dev.p, sizeof(DevStats), hipMemcpyDeviceToHost));
     for (int k = 0; k < 16; ++k) out[k] = c->stats_pinned->dbg[k];
     return TRGL_OK;
 }
@@ -921,8 +915,8 @@ int trgl_gather(trgl_ctx* c, void* comm, int rank, int world, int with_z) {
         if (c->strip_y0 != rank * rows || c->strip_y1 != (rank + 1) * rows)
             return fail(c, TRGL_E_STATE, "trgl_gather: this context's strip is not rows [rank * H / world, (rank + 1) * H / world)");
         if ((rc = r.GroupStart())) { c->err = rccl_err("ncclGroupStart", rc); return TRGL_E_HIP; }
-        rc = r.AllGather(c->fb + (size_t)c->strip_y0 * row_fb, c->fb, (size_t)rows * row_fb, NCCL_UINT8, comm, c->stream);
-        if (!rc && with_z) rc = r.AllGather(reinterpret_cast<uint8_t*>(c->zb) + (size_t)c->strip_y0 * row_z, c->zb, (size_t)rows * row_z, NCCL_UINT8, comm, c->stream);
+        rc = r.AllGather(c->fb.p + (size_t)c->strip_y0 * row_fb, c->fb.p, (size_t)rows * row_fb, NCCL_UINT8, comm, c->stream);
+        if (!rc && with_z) rc = r.AllGather(reinterpret_cast<uint8_t*>(c->zb.p) + (size_t)c->strip_y0 * row_z, c->zb.p, (size_t)rows * row_z, NCCL_UINT8, comm, c->stream);
         const int rc2 = r.GroupEnd();
         if (!rc) rc = rc2;
     } else {
@@ -933,8 +927,8 @@ int trgl_gather(trgl_ctx* c, void* comm, int rank, int world, int with_z) {
         if ((rc = r.GroupStart())) { c->err = rccl_err("ncclGroupStart", rc); return TRGL_E_HIP; }
         for (int p0 = 0; p0 < c->H && !rc; p0 += period) {
             const int y0 = p0 + rank * band;
-            rc = r.AllGather(c->fb + (size_t)y0 * row_fb, c->fb + (size_t)p0 * row_fb, (size_t)band * row_fb, NCCL_UINT8, comm, c->stream);
-            if (!rc && with_z) rc = r.AllGather(reinterpret_cast<uint8_t*>(c->zb) + (size_t)y0 * row_z, reinterpret_cast<uint8_t*>(c->zb) + (size_t)p0 * row_z,
+            rc = r.AllGather(c->fb.p + (size_t)y0 * row_fb, c->fb.p + (size_t)p0 * row_fb, (size_t)band * row_fb, NCCL_UINT8, comm, c->stream);
+            if (!rc && with_z) rc = r.AllGather(reinterpret_cast<uint8_t*>(c->zb.p) + (size_t)y0 * row_z, reinterpret_cast<uint8_t*>(c->zb.p) + (size_t)p0 * row_z,
                                                 (size_t)band * row_z, NCCL_UINT8, comm, c->stream);
         }
         const int rc2 = r.GroupEnd();

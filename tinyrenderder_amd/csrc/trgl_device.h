@@ -10,6 +10,8 @@
 //                                   for the radix passes
 //   tile_start/tile_end uint32[T]   per-tile slice of the sorted pair list
 #pragma once
+#include <limits.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/trgl.h"
 
@@ -88,6 +90,9 @@ struct DevStats {
     uint32_t zero_locked, zero_sign;     // set by k_fold_stats once any zero has been written
     unsigned long long dbg[16];           // diagnostic builds only (-DTRGL_DEBUG_COUNTERS): work counters of k_raster
 };
+// k_chunk_spine hands the host pairs_total and the two counts behind it as three consecutive words (total64[0..2])
+static_assert(offsetof(DevStats, literal_tris) == offsetof(DevStats, pairs_total) + 8, "k_chunk_spine reads literal_tris at total64[1]");
+static_assert(offsetof(DevStats, large_tris) == offsetof(DevStats, pairs_total) + 16, "k_chunk_spine reads large_tris at total64[2]");
 #define TRGL_ZERO_KEY_EMPTY 0xffffffffffffffffull
 
 struct FrameParams;
@@ -95,6 +100,33 @@ struct FrameParams;
 #define TRGL_HD __host__ __device__ __forceinline__
 #else
 #define TRGL_HD inline
+#endif
+
+// ---- bit-exactness helpers: one copy for the host and every kernel file ---------------------------------------------
+// order-preserving u64 key of a double (the z range of DevStats, kept with atomicMin / atomicMax): the host's reset values
+// and the kernels' atomics must agree bit for bit
+TRGL_HD unsigned long long zkey(double d) {
+#ifdef __HIP_DEVICE_COMPILE__
+    // (through HIP's own bit cast: the kernels' code is then instruction for instruction what it was with per-file copies)
+    const unsigned long long b = (unsigned long long)__double_as_longlong(d);
+#else
+    unsigned long long b; __builtin_memcpy(&b, &d, sizeof(b));
+#endif
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+TRGL_HD double zkey_decode(unsigned long long k) {
+    unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double d; __builtin_memcpy(&d, &b, sizeof(d));
+    return d;
+}
+#ifdef __HIPCC__
+__device__ __forceinline__ double dmax(double a, double b) { return (a < b) ? b : a; }   // std::max
+__device__ __forceinline__ double dmin(double a, double b) { return (b < a) ? b : a; }   // std::min
+__device__ __forceinline__ int x86_cvttsd2si(double d) {
+    // (int)double exactly as the reference's x86-64 build executes it: out of range -> INT_MIN
+    if (!(d > -2147483649.0 && d < 2147483648.0)) return INT_MIN;
+    return (int)d;
+}
 #endif
 struct FrameParams {
     uint8_t* fb;
