@@ -153,10 +153,134 @@ def empty_scene_64():
     return _case(64, 64, [])
 
 
+# ---- z ranges that end in a signed zero.  std::min / std::max (our_gl.cpp:197-198) keep the first of two equal values and
+# +0.0 == -0.0, so the printed end is "-0.000000" or "0.000000" after the first zero fragment WRITTEN in the reference's order
+# (triangle, then x, then y: our_gl.cpp:147-148).  Ordinary depths are folded to one side of zero, so that the range ends there.
+UNIT_VIEWPORT = np.eye(4)          # screen = NDC: vertices can sit exactly on pixel centres (and edge deltas can be tiny)
+
+
+def fold_depths(clip, sign):
+    """Vertex depths folded to sign * |z| (the clip z is ndc z * w)."""
+    c = clip.copy()
+    for v in range(3):
+        c[:, 4 * v + 2] = sign * np.abs(c[:, 4 * v + 2])
+    return c
+
+
+def set_zero_depths(clip, rows, signs):
+    """Vertex depths of the triangles `rows` become zeros of the given signs (one +-1 per vertex, or one for all three)."""
+    for i in rows:
+        for v in range(3):
+            s = signs[v] if hasattr(signs, "__len__") else signs
+            clip[i, 4 * v + 2] = np.copysign(0.0, s)
+
+
+def to_screen_space(clip, w, h):
+    """Triangles made for the default viewport of a w x h frame, restated for UNIT_VIEWPORT (same pixels)."""
+    c = clip.copy()
+    for v in range(3):
+        cw = c[:, 4 * v + 3]
+        c[:, 4 * v + 0] = ((c[:, 4 * v + 0] / cw) * (w / 2.0) + w / 2.0) * cw
+        c[:, 4 * v + 1] = ((c[:, 4 * v + 1] / cw) * (h / 2.0) + h / 2.0) * cw
+    return c
+
+
+def screen_triangle(p0, p1, p2, z=(0.0, 0.0, 0.0)):
+    """One clip row for UNIT_VIEWPORT from pixel-space vertices (w = 1)."""
+    return np.array([p0[0], p0[1], z[0], 1.0, p1[0], p1[1], z[1], 1.0, p2[0], p2[1], z[2], 1.0])
+
+
+def zero_min_neg_first_96x64():
+    """min ends at -0: triangles 100-102 write -0 before triangles 250-252 write +0 (both stay in the z-buffer)."""
+    clip, col = scenes.random_triangles(400, 96, 64, seed=41, rmin=3, rmax=24)
+    clip = fold_depths(clip, 1.0)
+    set_zero_depths(clip, range(100, 103), -1.0)
+    set_zero_depths(clip, range(250, 253), 1.0)
+    return _case(96, 64, [(FLAT, None, clip, None, col)])
+
+
+def zero_min_pos_first_96x64():
+    """min ends at +0 although a later triangle writes -0; perspective w."""
+    clip, col = scenes.random_triangles(400, 96, 64, seed=42, rmin=3, rmax=24, perspective_w=True)
+    clip = fold_depths(clip, 1.0)
+    set_zero_depths(clip, range(120, 123), 1.0)
+    set_zero_depths(clip, range(200, 203), -1.0)
+    return _case(96, 64, [(FLAT, None, clip, None, col)])
+
+
+def zero_signs_in_one_triangle_96x64():
+    """One triangle with vertex depths (-0, -0, +0) writes both signs: z = b0 (-0) + b1 (-0) + b2 (+0) is -0 only where
+    b2 = u.x / u.z is -0, on its edge v0 v1 - a column of pixel centres (x = 20.5).  In the reference's x-major order the
+    first pixel visited is that column (-0); a y-major walk would meet an interior pixel (+0) of row 10 first."""
+    clip, col = scenes.random_triangles(300, 96, 64, seed=43, rmin=3, rmax=24)
+    clip = fold_depths(to_screen_space(clip, 96, 64), 1.0)
+    tri = screen_triangle((20.5, 52.5), (20.5, 18.5), (60.5, 10.2), z=(-0.0, -0.0, 0.0))
+    clip = np.concatenate([clip[:150], tri[None], clip[150:]])
+    col = np.concatenate([col[:150], np.array([0xFF10E0F0], np.uint32), col[150:]])
+    return _case(96, 64, [(FLAT, None, clip, None, col)], viewport=UNIT_VIEWPORT)
+
+
+def zero_max_neg_first_96x64():
+    """Every depth <= 0: max ends at the first zero written (-0 by triangles 20-22, +0 by 23-25 after them), RGBA."""
+    clip, col = scenes.random_triangles(200, 96, 64, seed=44, rmin=2, rmax=12)
+    clip = fold_depths(clip, -1.0)
+    set_zero_depths(clip, range(20, 23), -1.0)
+    set_zero_depths(clip, range(23, 26), 1.0)
+    return _case(96, 64, [(FLAT, None, clip, None, col)], bpp=4)
+
+
+def zero_checker_discarded_first_96x64():
+    """CHECKER (cells = 2) triangle with vertex depths (-0, -0, +0): its first column x = 10 lies on the edge v0 v1 (-0 there) and
+    is discarded all the way (exactly one of pc0, pc1 is >= 0.5 on it), so the first zero WRITTEN is +0 from column 11.  A later
+    all -0 triangle leaves -0 in the z-buffer as well.  Discarded fragments count nowhere: the range ends at +0."""
+    w, h = 96, 64
+    base, bcol = scenes.random_triangles(200, w, h, seed=45, rmin=3, rmax=24)
+    base = fold_depths(to_screen_space(base, w, h), 1.0)
+    tris, tcol = scenes.random_triangles(200, w, h, seed=46, rmin=3, rmax=24)
+    tris = fold_depths(to_screen_space(tris, w, h), 1.0)
+    first = screen_triangle((10.5, 50.7), (10.5, 11.3), (40.5, 30.5), z=(-0.0, -0.0, 0.0))
+    later = screen_triangle((60.5, 40.5), (85.5, 45.5), (70.5, 58.5), z=(-0.0, -0.0, -0.0))
+    tris = np.concatenate([tris[:80], first[None], tris[80:140], later[None], tris[140:]])
+    tcol = np.concatenate([tcol[:80], np.array([0xFF3060C0], np.uint32), tcol[80:140], np.array([0xFFC06030], np.uint32), tcol[140:]])
+    return _case(w, h, [(FLAT, None, base, None, bcol), (CHECKER, make_uniforms(cells=2), tris, None, tcol)],
+                 viewport=UNIT_VIEWPORT)
+
+
+def phong_soup_varyings(n, seed):
+    """PHONG / EYE varyings [n, 24] of a triangle soup: uv outside [0, 1), unnormalised and zero normals, degenerate uv frames."""
+    vr = scenes.SplitMix64(seed)
+    uv = vr.uniform(n * 6, -0.5, 1.5).reshape(n, 6)
+    pos = vr.uniform(n * 9, -2.0, 2.0).reshape(n, 9)
+    nrm = vr.uniform(n * 9, -1.0, 1.0).reshape(n, 9)
+    nrm[::17] = 0.0
+    uv[::13, 2:4] = uv[::13, 0:2]
+    return np.ascontiguousarray(np.concatenate([uv, pos, nrm], 1))
+
+
+def zero_phong_128x96():
+    """PHONG soup (visibility buffer + k_shade) whose range ends at +0: +0 triangles 90-92 come before -0 triangles 200-202."""
+    w, h = 128, 96
+    clip, _ = scenes.random_triangles(360, w, h, seed=47, rmin=3, rmax=30, perspective_w=True)
+    clip = fold_depths(clip, 1.0)
+    set_zero_depths(clip, range(90, 93), 1.0)
+    set_zero_depths(clip, range(200, 203), -1.0)
+    hd, tx = _head(1, w, h, 64)
+    u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 0.7, 0, 1, 2)
+    return _case(w, h, [(PHONG, u, clip, phong_soup_varyings(360, 48), None)], textures=tx)
+
+
+# the sign each zero case's z range must end at: (min end, max end) as copysign(1, .) of the printed value, None = not zero
+ZERO_CASES = {"zero_min_neg_first_96x64": (-1.0, None), "zero_min_pos_first_96x64": (1.0, None),
+              "zero_signs_in_one_triangle_96x64": (-1.0, None), "zero_max_neg_first_96x64": (None, -1.0),
+              "zero_checker_discarded_first_96x64": (1.0, None), "zero_phong_128x96": (1.0, None)}
+
+
 CASES = {f.__name__: f for f in (
     flat_small_64, flat_800, flat_persp_512, flat_big_tris_512, edge_256, grid_256, grid_fine_128, gouraud_256_rgba,
     phong_512, phong_nomaps_256, eye_256, multi_draw_320x200, odd_dims_101x67, gray_bpp1_96x64,
-    viewport_offset_256x160, zclear_finite_128, huge_depths_128, empty_scene_64, checker_256, checker_mixed_200x120)}
+    viewport_offset_256x160, zclear_finite_128, huge_depths_128, empty_scene_64, checker_256, checker_mixed_200x120,
+    zero_min_neg_first_96x64, zero_min_pos_first_96x64, zero_signs_in_one_triangle_96x64, zero_max_neg_first_96x64,
+    zero_checker_discarded_first_96x64, zero_phong_128x96)}
 
 # cases whose full buffers are stored in tests/golden/ (small enough to commit)
 FULL_BUFFER_CASES = ("flat_small_64", "odd_dims_101x67", "gray_bpp1_96x64")

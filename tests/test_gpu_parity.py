@@ -576,21 +576,22 @@ def test_mixed_flush_with_gouraud_runs_the_any_kernel():
     ginten = scenes.SplitMix64(72).uniform(3000 * 3, -0.2, 1.3).reshape(3000, 3)
     fclip, fcol = scenes.random_triangles(800, w, h, seed=73, rmin=2, rmax=24)
     small = scenes.head_standin(2, w, h, seed=5, distance=4.0)
-    case = cases._case(w, h, [(GOURAUD, None, gclip[:1500], ginten[:1500], gcol[:1500]), (PHONG, u, hd["clip"], hd["varyings"], None),
-                              (GOURAUD, None, gclip[1500:], ginten[1500:], gcol[1500:]), (FLAT, None, fclip, None, fcol),
-                              (EYE, u, small["clip"], small["varyings"], None)],
-                       textures={0: d, 1: n, 2: sp}, clear=(3, 2, 1, 255))
-    ofb, oz, ost = cases.run_oracle(case)
-    for bpp in (3,):
+    for bpp in (1, 3, 4):
+        case = cases._case(w, h, [(GOURAUD, None, gclip[:1500], ginten[:1500], gcol[:1500]), (PHONG, u, hd["clip"], hd["varyings"], None),
+                                  (GOURAUD, None, gclip[1500:], ginten[1500:], gcol[1500:]), (FLAT, None, fclip, None, fcol),
+                                  (EYE, u, small["clip"], small["varyings"], None)],
+                           bpp=bpp, textures={0: d, 1: n, 2: sp}, clear=(3, 2, 1, 255))
+        ofb, oz, ost = cases.run_oracle(case)
         fb, z, st, _ = cases.run_gpu(case)
+        assert fb.shape[-1] == bpp
         assert np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and st == ost
         diff = np.abs(fb.astype(np.int16) - ofb.astype(np.int16))           # EYE: pow(x, 8), at most 1 LSB on at most 0.1 % of the bytes
         assert diff.max() <= 1 and (diff != 0).mean() <= 1e-3
-    # the same frame without the EYE draw is byte-exact
-    case["draws"] = case["draws"][:4]
-    ofb, oz, ost = cases.run_oracle(case)
-    fb, z, st, _ = cases.run_gpu(case)
-    assert np.array_equal(fb, ofb) and np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and st == ost
+        # the same frame without the EYE draw is byte-exact
+        case["draws"] = case["draws"][:4]
+        ofb, oz, ost = cases.run_oracle(case)
+        fb, z, st, _ = cases.run_gpu(case)
+        assert np.array_equal(fb, ofb) and np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and st == ost
 
 
 def test_more_draws_than_descriptors_between_flushes():
