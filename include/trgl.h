@@ -71,6 +71,39 @@ extern "C" {
 #define TRGL_SHADER_CHECKER 4
 #define TRGL_NUM_SHADERS    5
 
+/*
+ * User shaders: a fragment body in HIP C++, compiled at run time for the GPU (hiprtc) and shaded like PHONG / EYE, once per
+ * visible pixel (IShader::fragment, our_gl.h:36-52, for the kinds the kernels do not implement).  The source defines exactly
+ *
+ *     __device__ uint32_t trgl_fragment(const trgl_frag_in& in);
+ *
+ * returning packed B,G,R,A (b | g<<8 | r<<16 | a<<24), written with TGAImage::set semantics (bpp bytes, tgaimage.cpp:32-39).
+ * A prelude compiled ahead of it provides
+ *
+ *     struct trgl_frag_in {
+ *         double bar[3];              perspective-correct barycentrics (our_gl.cpp:168-185): what IShader::fragment receives
+ *         const double* vary;         this triangle's K varyings (K fixed at registration; null when K = 0)
+ *         const trgl_uniforms* u;     the draw's uniform block (texture slots -1 when the draw passed none)
+ *         uint32_t color;             this triangle's `colors` entry, 0xffffffff when the draw has none
+ *         ...                         (the texture table, for the sampler)
+ *     };
+ *     struct trgl_texel { uint32_t bgra; int bytespp; };                          TGAColor
+ *     __device__ trgl_texel trgl_sample2D(const trgl_frag_in& in, int slot, const double uv[2]);
+ *
+ * trgl_sample2D has the clamp and nearest-texel rules of IShader::sample2D / Model::diffuse (model.cpp:415-459); an empty slot
+ * samples as opaque white.  The contract that makes shading once per visible pixel exact: the shader cannot discard (the
+ * signature has no flag) and has no side effects (writing memory from trgl_fragment is undefined behaviour).  Names starting
+ * with trgl_ and those of the library's device headers are reserved.
+ * The source is compiled with the library's own flags, -O3 -std=c++17 -ffp-contract=off -fno-fast-math
+ * -fhip-fp32-correctly-rounded-divide-sqrt, for the architecture the library was built for: results are bit-identical to a
+ * host build of the same body for + - * /, sqrt, conversions and comparisons.  Device libm calls (pow, sin, ...) are not glibc's.
+ * TRGL_USER_VARY is defined to K ahead of the source.  Kinds TRGL_SHADER_USER_FIRST + i are handed out by trgl_register_shader
+ * in registration order, per context.
+ */
+#define TRGL_SHADER_USER_FIRST 64
+#define TRGL_MAX_USER_SHADERS  32   /* per context */
+#define TRGL_MAX_USER_VARY     64   /* K */
+
 /* doubles of varyings per triangle for each kind */
 #define TRGL_VARY_FLAT    0
 #define TRGL_VARY_GOURAUD 3
@@ -171,8 +204,9 @@ int trgl_rccl_comm_destroy(void* nccl_comm);
 /* Replaces: n consecutive calls of rasterize(clip, shader, framebuffer) (our_gl.h:58,
  * our_gl.cpp:89-201) with the same shader object.
  *   clip     : n x 12 doubles, the `Triangle` = vec<4>[3] memory image (our_gl.h:55)
- *   varyings : n x K doubles (K by kind, above) or NULL when K = 0
- *   colors   : n x uint32 (b | g<<8 | r<<16 | a<<24) for FLAT/GOURAUD, else NULL
+ *   varyings : n x K doubles (K by kind, above; for a user kind the K it was registered with) or NULL when K = 0
+ *   colors   : n x uint32 (b | g<<8 | r<<16 | a<<24) for FLAT/GOURAUD, optional for user kinds, else NULL
+ * uniforms may be NULL for FLAT, GOURAUD and user kinds (texture slots -1).
  * Triangles are drawn in array order after everything submitted earlier (submission order is
  * observable: z ties keep the earlier triangle, our_gl.cpp:165).
  * n is not limited by the batching inside: a submission is cut into draws of 2^24 triangles and a new flush is
@@ -190,10 +224,20 @@ int trgl_draw(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms,
  *   vertices             : n_vertices x vertex_stride doubles; position at +0, normal at +3, texcoord at +6
  *                          (the reference's `Vertex`, model.h:14-20, has stride 14)
  *   indices              : 3*n_faces uint32 (Model::indices, model.h:115)
- * shader_kind is TRGL_SHADER_PHONG or TRGL_SHADER_EYE.  Host arrays are copied before return. */
+ * shader_kind is TRGL_SHADER_PHONG or TRGL_SHADER_EYE, or a user kind registered with K = 24, whose varyings are then the
+ * PHONG layout.  Host arrays are copied before return. */
 int trgl_draw_indexed(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms, const double projection[16],
                       const double* vertices, int vertex_stride, uint64_t n_vertices,
                       const uint32_t* indices, uint64_t n_faces, int mem_kind);
+
+/* User shaders (see the contract above).  hiprtc is loaded when first needed; without it both return TRGL_E_UNSUPPORTED and
+ * everything else works.  Code objects are cached for the process, keyed by source, K and flags.
+ * Compile only: needs no GPU and no context.  TRGL_E_INVALID on a compile error or K outside 0..TRGL_MAX_USER_VARY; `log`
+ * (may be NULL) gets the compiler log, truncated to log_len - 1 bytes. */
+int trgl_shader_compile(const char* source, int n_varyings, char* log, size_t log_len);
+/* Compile (or take from the cache) and load on the context's device; *kind = TRGL_SHADER_USER_FIRST + i for the i-th
+ * registration on this context.  The module belongs to the context and is unloaded by trgl_destroy. */
+int trgl_register_shader(trgl_ctx* ctx, const char* source, int n_varyings, int* kind);
 
 /* Execute everything submitted so far (asynchronously on the context's stream). */
 int trgl_flush(trgl_ctx* ctx);

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(HERE, "libtrgl.so")
 
 FLAT, GOURAUD, PHONG, EYE, CHECKER = 0, 1, 2, 3, 4
 VARY = {FLAT: 0, GOURAUD: 3, PHONG: 24, EYE: 24, CHECKER: 0}
+SHADER_USER_FIRST, MAX_USER_SHADERS, MAX_USER_VARY = 64, 32, 64      # user shaders: kinds handed out by Context.register_shader
 MEM_HOST, MEM_DEVICE = 0, 1
 PHASE_SETUP, PHASE_BIN, PHASE_RASTER, PHASE_TOTAL, PHASE_RASTER_KERNEL = 0, 1, 2, 3, 4
 NUM_PHASES = 5        # TRGL_NUM_PHASES
@@ -31,6 +32,7 @@ SYMBOLS = [
     "trgl_selftest_division", "trgl_selftest_sampler", "trgl_tga_max_size", "trgl_tga_encode", "trgl_tga_info", "trgl_tga_decode", "trgl_draw_indexed", "trgl_ssao_defaults",
     "trgl_postprocess", "trgl_obj_load", "trgl_obj_free",
     "trgl_gather", "trgl_rccl_unique_id", "trgl_rccl_comm_create", "trgl_rccl_comm_destroy",
+    "trgl_shader_compile", "trgl_register_shader",
 ]
 
 
@@ -147,6 +149,8 @@ def load_library(path: str = None):
     L.trgl_rccl_unique_id.argtypes = [C.c_void_p]
     L.trgl_rccl_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.trgl_rccl_comm_destroy.argtypes = [C.c_void_p]
+    L.trgl_shader_compile.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.trgl_register_shader.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -178,6 +182,17 @@ def rccl_comm_create(unique_id: bytes, rank: int, world: int, device: int = 0):
 
 def rccl_comm_destroy(comm):
     load_library().trgl_rccl_comm_destroy(comm)
+
+
+def shader_compile(source: str, n_varyings: int):
+    """trgl_shader_compile: compile a user shader (include/trgl.h, "User shaders") without a GPU or a context.
+    Returns (ok, compiler log); raises when user shaders are unavailable (no hiprtc)."""
+    L = load_library()
+    log = C.create_string_buffer(16384)
+    rc = L.trgl_shader_compile(source.encode(), int(n_varyings), log, len(log))
+    if rc not in (0, -1):
+        raise TrglError(f"trgl_shader_compile failed ({rc}): {log.value.decode(errors='replace')}")
+    return rc == 0, log.value.decode(errors="replace")
 
 
 def _ptr(a):
@@ -250,6 +265,7 @@ class Context:
             raise TrglError(f"trgl_create failed ({rc}): {self.L.trgl_last_error(None).decode()}")
         self.width, self.height, self.bpp, self.device = width, height, bpp, device
         self._keep = []
+        self._user_vary = {}        # kind -> K of the user shaders registered here
 
     def _chk(self, rc):
         if rc != 0:
@@ -303,10 +319,19 @@ class Context:
         self._chk(self.L.trgl_gather(self.h, comm, rank, world, int(bool(with_z))))
 
     # ---- submission ----
+    def register_shader(self, source: str, n_varyings: int) -> int:
+        """trgl_register_shader: compile (or take from the process cache) a user shader and load it on this context; returns its
+        kind, for draw() with n x n_varyings varyings."""
+        kind = C.c_int(-1)
+        self._chk(self.L.trgl_register_shader(self.h, source.encode(), int(n_varyings), C.byref(kind)))
+        self._user_vary[kind.value] = int(n_varyings)
+        return kind.value
+
     def draw(self, kind, clip, varyings=None, colors=None, uniforms=None, n=None, device=False):
         """Host arrays (numpy) are copied before return; with device=True pass torch CUDA tensors (or raw
         pointers with n) that stay alive until the flush has completed."""
-        K = VARY[kind]
+        # (a kind in the user range that was not registered here goes to the library, which refuses it)
+        K = self._user_vary.get(kind, 0) if kind >= SHADER_USER_FIRST else VARY[kind]
         if not device:
             clip = np.ascontiguousarray(clip, np.float64)
             n = clip.shape[0] if n is None else n

@@ -13,8 +13,10 @@
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"
 #include "launch.h"
+#include "shade_common.h"
 
 namespace {
+using namespace trgl_shade;
 
 // v_max_f64 as one instruction (a NaN operand yields the other one): for the depth maxima, where a pixel holding NaN can
 // never be written again (z < NaN is false), so leaving it out of a maximum keeps the maximum a valid bound
@@ -46,7 +48,6 @@ __device__ __forceinline__ float f32_down(double d) {
     if ((double)f > d) { const uint32_t b = __float_as_uint(f); f = __uint_as_float((b >> 31) ? b + 1u : b - 1u); }
     return f;
 }
-__device__ __forceinline__ int iclamp(int v, int lo, int hi) { return (v < lo) ? lo : (hi < v) ? hi : v; }
 __device__ __forceinline__ double dot3(const double* a, const double* b) {
     double sum = 0; sum += a[0] * b[0]; sum += a[1] * b[1]; sum += a[2] * b[2]; return sum;   // geometry.h:122-127
 }
@@ -56,33 +57,6 @@ __device__ __forceinline__ void normalized3(const double* v, double* out) {     
     out[0] = v[0] / length; out[1] = v[1] / length; out[2] = v[2] / length;
 }
 
-// ---- samplers: model.cpp:415-459 + TGAImage::get tgaimage.cpp:24-30 ----------------------------
-struct Color { uint32_t bgra; int bytespp; };   // TGAColor (tgaimage.h:29-31), bgra[0] in the low byte
-
-// (TX: pointer to DevTexture in the generic or in the constant address space - k_shade reads descriptors through scalar loads)
-template <class TX>
-__device__ __forceinline__ TX tex_slot(TX tex, int slot) {
-    if (slot < 0 || slot >= TRGL_MAX_TEXTURES) return nullptr;
-    if (!tex[slot].data || tex[slot].w <= 0) return nullptr;
-    return &tex[slot];
-}
-// TGAImage::get at the clamped texel (model.cpp:420-425 etc.): ONE unaligned 4-byte load per texel (the device copy
-// of every texture is padded by 4 bytes), masked to bpp bytes = TGAColor(p, bpp) with the rest 0 (tgaimage.h:46-50).
-template <class TX>
-__device__ __forceinline__ uint32_t tex_fetch_raw(TX t, const double* uv) {
-    int x = iclamp(x86_cvttsd2si(uv[0] * t->w), 0, t->w - 1);
-    int y = iclamp(x86_cvttsd2si(uv[1] * t->h), 0, t->h - 1);
-    const uint8_t* p = t->data + ((size_t)x + (size_t)y * t->w) * t->bpp;
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-template <class TX>
-__device__ __forceinline__ uint32_t tex_mask(TX t) { return t->bpp >= 4 ? 0xffffffffu : ((1u << (8 * t->bpp)) - 1u); }
-template <class TX>
-__device__ __forceinline__ Color tex_fetch(TX t, const double* uv) {
-    return Color{ tex_fetch_raw(t, uv) & tex_mask(t), t->bpp };
-}
 __device__ __forceinline__ void interp(const double* v0, const double* v1, const double* v2, const double* b, int n, double* out) {
     for (int i = 0; i < n; ++i) out[i] = (v0[i] * b[0] + v1[i] * b[1]) + v2[i] * b[2];       // main.cpp:94-104
 }
@@ -230,18 +204,6 @@ __device__ __forceinline__ uint32_t frag_gouraud(uint32_t base, const double* va
 __device__ __forceinline__ bool frag_checker_discards(int cells, const double* b) {
     const int a = x86_cvttsd2si(b[0] * (double)cells), c = x86_cvttsd2si(b[1] * (double)cells);
     return ((a ^ c) & 1) != 0;
-}
-
-// a / uz, correctly rounded, for the per-triangle constant uz with ruz = RN(1/uz) (Markstein):
-// q0 = RN(a*ruz) is within 2 ulp of a/uz; one FMA residual step makes q1 faithful (error < 1 ulp),
-// and for a faithful q1 the second step q1 + (a - uz*q1)*ruz rounds to RN(a/uz) exactly.
-// Valid when nothing over/underflows: only used for "well scaled" triangles (see k_setup).
-__device__ __forceinline__ double div_by_uz(double a, double uz, double ruz) {
-    const double q0 = a * ruz;
-    const double e0 = __builtin_fma(-q0, uz, a);
-    const double q1 = __builtin_fma(e0, ruz, q0);
-    const double e1 = __builtin_fma(-q1, uz, a);
-    return __builtin_fma(e1, ruz, q1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -394,10 +356,10 @@ __device__ __forceinline__ void resolve(BlockState& S, unsigned long long pend, 
                 color = recs[S.ptri].color;
                 const DrawDesc* d = draws + TRGL_DL_DRAW(dl);
                 const int kind = KIND == KIND_ANY ? d->kind : KIND;
-                if (kind == TRGL_SHADER_PHONG || kind == TRGL_SHADER_EYE) {
-                    // not shaded here: the pixel remembers which triangle owns it and k_shade runs the fragment shader once per
-                    // visible pixel (the two shaders have no side effects and never discard, so the image is the same as shading
-                    // every z-pass in order, and the counters do not depend on colours)
+                if (kind == TRGL_SHADER_PHONG || kind == TRGL_SHADER_EYE || kind >= TRGL_SHADER_USER_FIRST) {
+                    // not shaded here: the pixel remembers which triangle owns it and k_shade (or the user kind's shade kernel,
+                    // shade_user.h) runs the fragment shader once per visible pixel (these shaders have no side effects and never
+                    // discard, so the image is the same as shading every z-pass in order, and the counters do not depend on colours)
                     id = TRGL_DL_ID(dl);
                 } else if (kind != TRGL_SHADER_FLAT) {
                     const TriW w = recs_w[S.ptri];
@@ -500,9 +462,6 @@ __device__ __forceinline__ void clear_rows(const FrameParams& fp, int lane, int 
     }
 }
 
-// Work items (k_make_items): one per workgroup.
-//   bits 0-23 tile, bits 24-25 row of blocks inside the tile, bit 31: the tile has no triangles and is only cleared
-#define TRGL_ITEM_CLEAR 0x80000000u
 #ifndef TRGL_RASTER_WAVES
 #define TRGL_RASTER_WAVES 5        // waves per SIMD the register allocation of k_raster aims at (96 vector registers; 6 waves = 80 registers spill 8 dwords per list step: 2 % slower)
 #endif
@@ -982,7 +941,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRGL_RASTER
 // 220-261), so calling it for that triangle only gives the same framebuffer as calling it for every z-pass in order
 // (our_gl.cpp:187-192) - with 64 busy lanes per wave instead of the few pixels of one small triangle.  One 256-thread
 // block per work item of k_raster (so tiles this flush did not touch are not visited), one 8x8 block per wave; the
-// barycentrics are recomputed per pixel with exactly the operations of the scan (same bits).
+// barycentrics are recomputed per pixel with exactly the operations of the scan (same bits).  k_shade<KIND_ANY> leaves the
+// pixels of user kinds alone: each user kind's own kernel (shade_user.h) shades them behind it.
 // ---------------------------------------------------------------------------------------------
 template <int KIND>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_shade(FrameParams fp, const TriRec* __restrict__ recs, const TriW* __restrict__ recs_w,
@@ -1007,13 +967,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     if (dl == 0xffffffffu) return;
     // the draw (uniforms, varyings array, first record) is wave-uniform in all but exotic flushes: serve one draw at a time
     uint32_t color = 0;
+    bool user = false;
+    typedef const __attribute__((address_space(4))) DrawDesc CDrawK;
     unsigned long long todo = __ballot(true);
     while (todo) {
         const int src = __builtin_ctzll(todo);
         const uint32_t di = (uint32_t)__builtin_amdgcn_readlane((int)(dl >> 24), src);
         const bool here = (dl >> 24) == di;
         todo &= ~__ballot(here);
-        if (here) {
+        if (KIND == KIND_ANY && here && ((CDrawK*)draws)[di].kind >= TRGL_SHADER_USER_FIRST) {
+            user = true;                                      // a user kind's pixel: its own kernel shades it (shade_user.h)
+        } else if (here) {
             // descriptors through the CONSTANT address space: the draw index is wave-uniform, so every field (uniforms, texture
             // descriptors) comes in by scalar loads through the scalar cache.  As plain global loads they were vector loads, each
             // waited for on its own: ~20 memory round trips in a row per block, 68 % of the kernel's wave time in s_waitcnt.
@@ -1027,30 +991,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             const TriRec& r = recs[d.first + local];
             const TriW& rw = recs_w[d.first + local];
             const double* vary = d.vary + (size_t)local * 24;
-            // barycentric(), our_gl.cpp:77-86, as in k_raster
-            const double pxc = (double)x + 0.5, pyc = (double)y + 0.5;
-            const double s0z = r.ax - pxc, s1z = r.ay - pyc;
-            const double ux = r.s0y * s1z - s0z * r.s1y;
-            const double uy = s0z * r.s1x - r.s0x * s1z;
-            const double us = ux + uy;
-            double b0, b1, b2;
-            if (r.ruz != 0.0) {
-                b0 = 1.0 - div_by_uz(us, r.uz, r.ruz); b1 = div_by_uz(uy, r.uz, r.ruz); b2 = div_by_uz(ux, r.uz, r.ruz);
-            } else {
-                b0 = 1.0 - us / r.uz; b1 = uy / r.uz; b2 = ux / r.uz;
-            }
             double pc[3];
-            const double denom = b0 * rw.iw0 + b1 * rw.iw1 + b2 * rw.iw2;                     // our_gl.cpp:172-174
-            if (fabs(denom) < 1e-15) { pc[0] = b0; pc[1] = b1; pc[2] = b2; }                  // :177-185
-            else { pc[0] = (b0 * rw.iw0) / denom; pc[1] = (b1 * rw.iw1) / denom; pc[2] = (b2 * rw.iw2) / denom; }
+            TRGL_OWNER_BARYCENTRICS(r, rw, x, y, pc);                   // barycentric(), our_gl.cpp:77-86, as in k_raster
             const int kind = KIND == KIND_ANY ? d.kind : KIND;        // wave-uniform inside this iteration
             color = kind == TRGL_SHADER_PHONG ? frag_phong(d.u, ctex, vary, pc).bgra : frag_eye(d.u, ctex, vary, pc).bgra;
         }
     }
-    uint8_t* dst = fp.fb + idx * fp.bpp;                                               // TGAImage::set, tgaimage.cpp:32-39
-    if (fp.bpp == 3) { dst[0] = (uint8_t)color; dst[1] = (uint8_t)(color >> 8); dst[2] = (uint8_t)(color >> 16); }
-    else if (fp.bpp == 4) *reinterpret_cast<uint32_t*>(dst) = color;
-    else dst[0] = (uint8_t)color;                                  // bpp is 1, 3 or 4 (trgl_create)
+    if (KIND == KIND_ANY && user) return;
+    store_pixel(fp, idx, color);                                   // TGAImage::set, tgaimage.cpp:32-39
 }
 
 // ---- self-test of the two exactness shortcuts, against the hardware's IEEE division ------------------
@@ -1236,7 +1184,8 @@ void launch_raster(hipStream_t s, const FrameParams& fp, int kind /* TRGL_SHADER
                    const TriRec* recs, const TriW* recs_w, const uint32_t* vals, const uint16_t* bmask,
                    const uint32_t* tile_start, const uint32_t* tile_end, const DrawDesc* draws,
                    const DevTexture* tex, DevStats* stats, uint32_t max_items, uint4* items,
-                   uint32_t* n_items, unsigned long long* item_stats, hipEvent_t ev_before, hipEvent_t ev_after) {
+                   uint32_t* n_items, unsigned long long* item_stats, bool builtin_shade, const UserShade* user, int n_user,
+                   hipEvent_t ev_before, hipEvent_t ev_after) {
     const int tiles = (fp.strip_ty1 - fp.strip_ty0) * fp.tiles_x;
     if (tiles <= 0 || max_items == 0) {          // a context that owns no rows (a rank beyond the image's bands): nothing to draw
         if (ev_before) (void)hipEventRecord(ev_before, s);
@@ -1266,12 +1215,19 @@ void launch_raster(hipStream_t s, const FrameParams& fp, int kind /* TRGL_SHADER
     }
 #undef TRGL_LAUNCH_RASTER
     if (ev_after) (void)hipEventRecord(ev_after, s);
-    if (fp.idbuf) {                                     // the flush has PHONG / EYE draws: shade the visible pixels they own
+    if (fp.idbuf && builtin_shade) {                    // the flush has PHONG / EYE draws: shade the visible pixels they own
 #define TRGL_LAUNCH_SHADE(K) hipLaunchKernelGGL(k_shade<K>, dim3(max_items), dim3(256), 0, s, fp, recs, recs_w, draws, tex, items, n_items)
         if (kind == TRGL_SHADER_PHONG) TRGL_LAUNCH_SHADE(TRGL_SHADER_PHONG);
         else if (kind == TRGL_SHADER_EYE) TRGL_LAUNCH_SHADE(TRGL_SHADER_EYE);
         else TRGL_LAUNCH_SHADE(KIND_ANY);
 #undef TRGL_LAUNCH_SHADE
+    }
+    // ... and those of every user kind of the flush, one kernel each, over the same work items (before k_fold_stats clears their count)
+    for (int i = 0; i < n_user && fp.idbuf; ++i) {
+        FrameParams fpa = fp; const TriRec* a1 = recs; const TriW* a2 = recs_w; const DrawDesc* a3 = draws; const DevTexture* a4 = tex;
+        const uint4* a5 = items; const uint32_t* a6 = n_items; int a7 = user[i].kind;
+        void* args[] = { &fpa, &a1, &a2, &a3, &a4, &a5, &a6, &a7 };
+        (void)hipModuleLaunchKernel(user[i].fn, max_items, 1, 1, 256, 1, 1, 0, s, args, nullptr);
     }
     hipLaunchKernelGGL(k_fold_stats, dim3(FOLD_BLOCKS), dim3(1024), 0, s, stats, n_items, item_stats);
 }

@@ -19,12 +19,14 @@
 #include "../../include/trgl.h"
 #include "launch.h"
 #include "trgl_device.h"
+#include "user_shaders.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
 using namespace trgl;
 
 static thread_local std::string g_create_error;
+void trgl::set_global_error(const std::string& msg) { g_create_error = msg; }
 
 struct StageChunk { char* base; size_t cap, used; };
 struct trgl_ctx;
@@ -52,7 +54,11 @@ static size_t pair_capacity(size_t need) {
 }
 
 // a flush whose first half (setup + binning) has run and whose raster half is still to be launched (trgl_flush_begin)
-struct PendingRaster { bool active = false; FrameParams fp; int flush_kind = 0; uint32_t cap = 0; int cur = 0; uint64_t N = 0; };
+// (builtin_shade: the flush has PHONG / EYE draws; user_kinds: bit i = it has draws of user kind TRGL_SHADER_USER_FIRST + i)
+struct PendingRaster { bool active = false; FrameParams fp; int flush_kind = 0; uint32_t cap = 0; int cur = 0; uint64_t N = 0;
+                       bool builtin_shade = false; uint32_t user_kinds = 0; };
+// a user shader registered on the context (trgl_register_shader): its module and shade kernel
+struct UserKind { hipModule_t mod; hipFunction_t fn; int K; };
 
 struct trgl_ctx {
     int device = 0;
@@ -101,6 +107,8 @@ struct trgl_ctx {
     hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     double phase_ms[TRGL_NUM_PHASES] = { 0, 0, 0, 0, 0 };
     uint64_t flushes_timed = 0;
+
+    std::vector<UserKind> user;         // kind TRGL_SHADER_USER_FIRST + i is user[i]
 
     std::string err;
 
@@ -209,6 +217,7 @@ int trgl_destroy(trgl_ctx* c) {
     if (c->stats_pinned) (void)hipHostFree(c->stats_pinned);
     for (int i = 0; i < 6; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_pairs) (void)hipEventDestroy(c->ev_pairs);
+    for (auto& u : c->user) (void)hipModuleUnload(u.mod);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                   // (the device buffers free themselves)
     return TRGL_OK;
@@ -318,10 +327,11 @@ int trgl_draw(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip,
               const uint32_t* colors, uint64_t n, int mem_kind) {
     CHKCTX(c);
     int r = end_pending_raster(c); if (r) return r;
-    if (kind < 0 || kind >= TRGL_NUM_SHADERS) return fail(c, TRGL_E_INVALID, "trgl_draw: unknown shader kind");
+    const bool user = kind >= TRGL_SHADER_USER_FIRST && kind - TRGL_SHADER_USER_FIRST < (int)c->user.size();
+    if ((kind < 0 || kind >= TRGL_NUM_SHADERS) && !user) return fail(c, TRGL_E_INVALID, "trgl_draw: unknown shader kind");
     if (n == 0) return TRGL_OK;
     if (!clip) return fail(c, TRGL_E_INVALID, "trgl_draw: clip is null");
-    int K = vary_count(kind);
+    int K = user ? c->user[kind - TRGL_SHADER_USER_FIRST].K : vary_count(kind);
     if (K && !vary) return fail(c, TRGL_E_INVALID, "trgl_draw: this shader kind needs varyings");
     if ((kind == TRGL_SHADER_PHONG || kind == TRGL_SHADER_EYE) && !u) return fail(c, TRGL_E_INVALID, "trgl_draw: PHONG/EYE need uniforms");
     if (kind == TRGL_SHADER_CHECKER && (!u || u->reserved < 1)) return fail(c, TRGL_E_INVALID, "trgl_draw: CHECKER needs uniforms with reserved = cells >= 1");
@@ -359,7 +369,10 @@ int trgl_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const doubl
                       int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind) {
     CHKCTX(c);
     int r = end_pending_raster(c); if (r) return r;
-    if (kind != TRGL_SHADER_PHONG && kind != TRGL_SHADER_EYE) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: kind must be PHONG or EYE");
+    const bool user24 = kind >= TRGL_SHADER_USER_FIRST && kind - TRGL_SHADER_USER_FIRST < (int)c->user.size() &&
+                        c->user[kind - TRGL_SHADER_USER_FIRST].K == TRGL_VARY_PHONG;     // (its varyings: the PHONG layout)
+    if (kind != TRGL_SHADER_PHONG && kind != TRGL_SHADER_EYE && !user24)
+        return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: kind must be PHONG, EYE or a user kind registered with 24 varyings");
     if (!u || !projection || !vertices || !indices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: null argument");
     if (stride < 8) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: vertex stride must be >= 8 doubles (pos3, normal3, uv2)");
     if (mem_kind != TRGL_MEM_HOST && mem_kind != TRGL_MEM_DEVICE) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: bad mem_kind");
@@ -524,9 +537,13 @@ int trgl_flush_begin(trgl_ctx* c) {
 
     int flush_kind = c->draws.empty() ? TRGL_SHADER_FLAT : c->draws[0].kind;     // one kind for the whole flush, or -1
     for (auto& d : c->draws) if (d.kind != flush_kind) flush_kind = -1;
-    bool shade_later = false;
-    for (auto& d : c->draws) if (d.kind == TRGL_SHADER_PHONG || d.kind == TRGL_SHADER_EYE) shade_later = true;
-    if (shade_later) {                                                            // shaded once per visible pixel (k_shade)
+    bool builtin_shade = false;
+    uint32_t user_kinds = 0;
+    for (auto& d : c->draws) {
+        if (d.kind == TRGL_SHADER_PHONG || d.kind == TRGL_SHADER_EYE) builtin_shade = true;
+        if (d.kind >= TRGL_SHADER_USER_FIRST) user_kinds |= 1u << (d.kind - TRGL_SHADER_USER_FIRST);
+    }
+    if (builtin_shade || user_kinds) {                                            // shaded once per visible pixel (k_shade, shade_user.h)
         if ((r = c->idbuf.grow(c, (size_t)c->W * c->H))) return r;
         fp.idbuf = c->idbuf.p;
     }
@@ -565,6 +582,7 @@ int trgl_flush_begin(trgl_ctx* c) {
     }
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], s));
     c->rp.active = true; c->rp.fp = fp; c->rp.flush_kind = flush_kind; c->rp.cap = cap; c->rp.cur = cur; c->rp.N = N;
+    c->rp.builtin_shade = builtin_shade; c->rp.user_kinds = user_kinds;
     return TRGL_OK;
 }
 
@@ -607,8 +625,12 @@ int trgl_flush_end(trgl_ctx* c) {
     // k_setup counted the triangles that are not well scaled (it came over with the pair count): without any, the kernel without the literal path
     const bool all_well_scaled = N == 0 || c->stats_pinned->literal_tris == 0;
     fp.zq_cull = (N != 0 && c->stats_pinned->large_tris != 0) ? 1 : 0;      // (k_setup counted them; the count came over with the pair count)
+    UserShade user[TRGL_MAX_USER_SHADERS];
+    int n_user = 0;
+    for (int i = 0; i < (int)c->user.size(); ++i)
+        if (c->rp.user_kinds >> i & 1u) user[n_user++] = UserShade{ c->user[i].fn, TRGL_SHADER_USER_FIRST + i };
     launch_raster(s, fp, flush_kind, all_well_scaled, recs_arg, c->recs_w.p, vals_arg, bmask_arg, c->tile_start.p, c->tile_end(), c->draws_dev.p, c->tex_dev.p,
-                  c->stats_dev.p, max_items, c->items.p, c->n_items.p, c->item_stats.p,
+                  c->stats_dev.p, max_items, c->items.p, c->n_items.p, c->item_stats.p, c->rp.builtin_shade, user, n_user,
                   c->profiling ? c->ev[4] : nullptr, c->profiling ? c->ev[5] : nullptr);
     if (c->profiling) { HIPCHK(c, hipEventRecord(c->ev[3], s)); c->events_pending = true; }
     HIPCHK(c, hipGetLastError());
@@ -625,6 +647,26 @@ int trgl_flush_end(trgl_ctx* c) {
         if (!c->stage_hold)                // ... and not while a draw call in progress still owns staged arrays
             for (auto& ch : c->stage) ch.used = 0;
     }
+    return TRGL_OK;
+}
+
+int trgl_register_shader(trgl_ctx* c, const char* source, int n_varyings, int* kind) {
+    CHKCTX(c);
+    if (!kind) return fail(c, TRGL_E_INVALID, "trgl_register_shader: kind is null");
+    if (c->user.size() >= TRGL_MAX_USER_SHADERS) return fail(c, TRGL_E_INVALID, "trgl_register_shader: TRGL_MAX_USER_SHADERS already registered");
+    std::string log;
+    const std::vector<char>* code = nullptr;
+    if (int r = user_shader_code(source, n_varyings, &log, &code)) { c->err = "trgl_register_shader: " + log; return r; }
+    UserKind u{ nullptr, nullptr, n_varyings };
+    HIPCHK(c, hipModuleLoadData(&u.mod, code->data()));
+    const hipError_t e = hipModuleGetFunction(&u.fn, u.mod, USER_SHADE_KERNEL);
+    if (e != hipSuccess) {
+        (void)hipModuleUnload(u.mod);
+        c->err = std::string("hipModuleGetFunction: ") + hipGetErrorString(e);
+        return TRGL_E_HIP;
+    }
+    c->user.push_back(u);
+    *kind = TRGL_SHADER_USER_FIRST + (int)c->user.size() - 1;
     return TRGL_OK;
 }
 

@@ -1,0 +1,22 @@
+// user_prelude.h — what a user shader's source sees (include/trgl.h, "User shaders"): compiled by hiprtc ahead of the source,
+// from the copy user_shaders.cpp embeds.  The sampler is the one k_shade uses (shade_common.h).
+#pragma once
+#include "shade_common.h"
+
+struct trgl_frag_in {
+    double bar[3];               // perspective-correct barycentrics (our_gl.cpp:168-185)
+    const double* vary;          // this triangle's K varyings (null when K = 0)
+    const trgl_uniforms* u;      // the draw's uniform block
+    uint32_t color;              // this triangle's `colors` entry, 0xffffffff when the draw has none (k_setup)
+    const DevTexture* tex;       // the context's texture table (trgl_sample2D)
+};
+struct trgl_texel { uint32_t bgra; int bytespp; };   // TGAColor (tgaimage.h:29-31), bgra[0] in the low byte
+
+// IShader::sample2D / Model::diffuse (model.cpp:415-459): clamp(int(uv * size), 0, size - 1), nearest texel; an empty slot samples
+// as opaque white (model.cpp:416-418)
+__device__ __forceinline__ trgl_texel trgl_sample2D(const trgl_frag_in& in, int slot, const double uv[2]) {
+    const DevTexture* t = trgl_shade::tex_slot(in.tex, slot);
+    if (!t) return trgl_texel{ 0xffffffffu, 4 };
+    const trgl_shade::Color c = trgl_shade::tex_fetch(t, uv);
+    return trgl_texel{ c.bgra, c.bytespp };
+}

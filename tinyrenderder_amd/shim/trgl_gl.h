@@ -16,6 +16,9 @@
 //   * a C++ virtual cannot be called from a kernel: IShader gains describe(), returning the POD descriptor of a
 //     shader kind the device implements (trgl_shaders.h: FlatShader, GouraudShader, PhongShader, EyeShader).
 //     A subclass without one makes rasterize() fail loudly — there is NO CPU fallback.
+//   * a fragment stage the device does not implement is a user shader: HIP C++ source registered with gl_register_shader()
+//     (compiled at run time for the GPU; the contract is in include/trgl.h) and drawn through a UserShader (trgl_shaders.h).
+//     Its kind stays the same when the shim recreates its context for a framebuffer of another size.
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -136,6 +139,8 @@ struct State {
     std::vector<double> clip, vary;
     std::vector<std::uint32_t> colors;
     mat<4, 4> viewport_at_batch;
+    struct UserSource { std::string source; int n_varyings; };
+    std::vector<UserSource> user;         // gl_register_shader(): registered on every context, in order (kind = USER_FIRST + index)
     int err = TRGL_OK;                    // first C-ABI error since gl_clear_error() (a TRGL_E_* code)
     std::string err_msg;
 };
@@ -161,6 +166,14 @@ inline bool bind(TGAImage& fb) {
         const int rc = trgl_create(device_from_env(), fb.width(), fb.height(), fb_bpp, &s.ctx);
         if (rc != TRGL_OK) { s.ctx = nullptr; return fail("trgl_create", rc, nullptr); }
         s.w = fb.width(); s.h = fb.height(); s.bpp = fb_bpp;
+        // the user shaders, with the kinds they had on earlier contexts (a context that misses one is not kept: the next bind()
+        // tries again with a new one)
+        for (std::size_t i = 0; i < s.user.size(); ++i) {
+            int kind = -1;
+            bool ok = TRGL_SHIM_OK(trgl_register_shader(s.ctx, s.user[i].source.c_str(), s.user[i].n_varyings, &kind));
+            if (ok && kind != TRGL_SHADER_USER_FIRST + int(i)) ok = fail("gl_register_shader: kinds out of order", TRGL_E_STATE, nullptr);
+            if (!ok) { trgl_destroy(s.ctx); s.ctx = nullptr; return false; }
+        }
         if (!TRGL_SHIM_OK(trgl_write_framebuffer(s.ctx, fb.buffer()))) return false;
         s.zbuffer_dirty_on_host = true;
     }
@@ -190,6 +203,8 @@ inline bool submit_batch() {
 }
 
 inline int vary_count(int kind) {
+    const State& s = state();
+    if (kind >= TRGL_SHADER_USER_FIRST && kind - TRGL_SHADER_USER_FIRST < int(s.user.size())) return s.user[kind - TRGL_SHADER_USER_FIRST].n_varyings;
     return kind == TRGL_SHADER_GOURAUD ? TRGL_VARY_GOURAUD : (kind == TRGL_SHADER_PHONG || kind == TRGL_SHADER_EYE) ? TRGL_VARY_PHONG : 0;   // FLAT, CHECKER: 0
 }
 inline bool same_matrix(const mat<4, 4>& a, const mat<4, 4>& b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
@@ -200,6 +215,28 @@ inline bool same_matrix(const mat<4, 4>& a, const mat<4, 4>& b) { return std::me
 inline int gl_last_error() { return trgl_shim::state().err; }
 inline const char* gl_last_error_message() { return trgl_shim::state().err_msg.c_str(); }
 inline void gl_clear_error() { trgl_shim::State& s = trgl_shim::state(); s.err = TRGL_OK; s.err_msg.clear(); }
+
+// A user shader (include/trgl.h, "User shaders"): HIP C++ source defining trgl_fragment, with n_varyings doubles of varyings per
+// triangle.  The source is compiled at once (a compile error is reported through gl_last_error(), with the compiler's log, and
+// -1 comes back); the kind returned is what UserShader::kind takes, and it stays valid on every context the shim creates.
+inline int gl_register_shader(const char* source, int n_varyings) {
+    trgl_shim::State& s = trgl_shim::state();
+    if (s.user.size() >= TRGL_MAX_USER_SHADERS) { trgl_shim::fail("gl_register_shader", TRGL_E_INVALID, nullptr); return -1; }
+    std::string log(4096, '\0');
+    const int rc = trgl_shader_compile(source, n_varyings, &log[0], log.size());
+    if (rc != TRGL_OK) {
+        if (s.err == TRGL_OK) { s.err = rc; s.err_msg = std::string("gl_register_shader: ") + log.c_str(); }
+        return -1;
+    }
+    s.user.push_back({ source, n_varyings });
+    const int kind = TRGL_SHADER_USER_FIRST + int(s.user.size()) - 1;
+    if (s.ctx) {
+        trgl_shim::submit_batch();
+        int k = -1;
+        if (!TRGL_SHIM_OK(trgl_register_shader(s.ctx, source, n_varyings, &k))) { s.user.pop_back(); return -1; }
+    }
+    return kind;
+}
 
 // ---- our_gl.h:25-31 ------------------------------------------------------------------------------
 inline void lookat(const vec3 eye, const vec3 center, const vec3 up) {            // our_gl.cpp:25-41
@@ -275,6 +312,10 @@ inline void rasterize(const Triangle& clip, const IShader& shader, TGAImage& fra
     }
     if (!bind(framebuffer)) return;                               // (reported through gl_last_error(); rasterize() is void, our_gl.h:58)
     const int K = vary_count(d.kind);
+    if (K && !d.varyings) {                                       // (a UserShader whose varyings are not its K doubles)
+        std::fprintf(stderr, "trgl: rasterize(): shader kind %d needs %d doubles of varyings per triangle\n", d.kind, K);
+        std::abort();
+    }
     if (s.have_batch && (s.kind != d.kind || std::memcmp(&s.uniforms, &d.uniforms, sizeof(trgl_uniforms)) != 0 ||
                          !same_matrix(s.viewport_at_batch, Viewport)))
         submit_batch();
@@ -300,8 +341,10 @@ inline bool gl_draw_indexed(const IShader& shader, const double* vertices, int s
     if (!bind(framebuffer)) return false;
     bool ok = submit_batch();                                   // earlier rasterize() calls come first
     trgl_shader_desc d;
-    if (!shader.describe(d) || (d.kind != TRGL_SHADER_PHONG && d.kind != TRGL_SHADER_EYE)) {
-        std::fprintf(stderr, "trgl: gl_draw_indexed(): needs a PHONG or EYE shader with a device descriptor\n");
+    // (a user kind registered with K = 24 takes the varyings the device vertex stage writes: the PHONG layout)
+    if (!shader.describe(d) || (d.kind != TRGL_SHADER_PHONG && d.kind != TRGL_SHADER_EYE &&
+                                !(d.kind >= TRGL_SHADER_USER_FIRST && vary_count(d.kind) == TRGL_VARY_PHONG))) {
+        std::fprintf(stderr, "trgl: gl_draw_indexed(): needs a PHONG or EYE shader, or a user shader with 24 varyings, with a device descriptor\n");
         std::abort();
     }
     double vp[16], pj[16];

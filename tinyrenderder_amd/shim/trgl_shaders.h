@@ -29,6 +29,29 @@ struct GouraudShader : IShader {
     }
 };
 
+// A user shader (gl_register_shader, include/trgl.h "User shaders"): `kind` is what gl_register_shader returned; per triangle,
+// `varyings` holds the K doubles it was registered with and `color` is what trgl_frag_in::color receives.  `uniforms` is passed
+// as it is (texture slots -1 by default).  Varyings of another size are a programming error: rasterize() aborts.  Through
+// gl_draw_model() / gl_draw_indexed() (a kind registered with K = 24) the device vertex stage makes the varyings: `varyings` and
+// `color` are not used there (trgl_frag_in::color is 0xffffffff).
+struct UserShader : IShader {
+    int kind = -1;
+    std::vector<double> varyings;
+    TGAColor color = TGAColor(255, 255, 255);
+    trgl_uniforms uniforms{};
+    UserShader() { uniforms.tex_diffuse = uniforms.tex_normal = uniforms.tex_specular = -1; }
+    explicit UserShader(int k) : UserShader() { kind = k; }
+    bool describe(trgl_shader_desc& d) const override {
+        if (kind < TRGL_SHADER_USER_FIRST || kind - TRGL_SHADER_USER_FIRST >= int(trgl_shim::state().user.size())) {
+            std::fprintf(stderr, "trgl: UserShader: kind %d is not a registered user shader\n", kind);
+            return false;
+        }
+        d.kind = kind; d.uniforms = uniforms; d.color = trgl_shim::pack_bgra(color);
+        d.varyings = int(varyings.size()) == trgl_shim::vary_count(kind) ? varyings.data() : nullptr;   // (rasterize() checks)
+        return true;
+    }
+};
+
 namespace trgl_shim {
 inline void fill_lights(trgl_uniforms& u, const vec3& key, const vec3& fill, const vec3& rim) {
     for (int i = 0; i < 3; ++i) { u.key_light_dir_eye[i] = key[i]; u.fill_light_dir_eye[i] = fill[i]; u.rim_light_dir_eye[i] = rim[i]; }
