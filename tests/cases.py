@@ -1,6 +1,7 @@
-"""Named parity scenes shared by the golden-fixture generator, the oracle tests and the GPU tests.
+"""Named parity scenes shared by the golden-fixture generator, the oracle tests and the GPU tests, and the one harness that
+renders a scene and checks it (run_oracle, run_gpu, assert_same_frame and friends, below).
 
-Each builder returns a dict: width, height, bpp, viewport (4x4), draws = [(kind, uniforms|None, clip,
+Each builder returns a dict (make_case): width, height, bpp, viewport (4x4), draws = [(kind, uniforms|None, clip,
 varyings|None, colors|None)], textures = {slot: array}, clear (4 bytes), zclear.
 Inputs come from tinyrenderder_amd.scenes (bit-reproducible everywhere).
 """
@@ -12,50 +13,50 @@ from tinyrenderder_amd.api import FLAT, GOURAUD, PHONG, EYE, CHECKER, make_unifo
 DEFAULT_CLEAR = (0, 0, 0, 255)
 
 
-def _case(w, h, draws, bpp=3, viewport=None, textures=None, clear=DEFAULT_CLEAR, zclear=np.inf):
+def make_case(w, h, draws, bpp=3, viewport=None, textures=None, clear=DEFAULT_CLEAR, zclear=np.inf):
     return dict(width=w, height=h, bpp=bpp, viewport=scenes.init_viewport(0, 0, w, h) if viewport is None else viewport,
                 draws=draws, textures=textures or {}, clear=tuple(clear), zclear=zclear)
 
 
 def flat_small_64():
     clip, col = scenes.random_triangles(300, 64, 64, seed=11, rmin=2, rmax=32)
-    return _case(64, 64, [(FLAT, None, clip, None, col)])
+    return make_case(64, 64, [(FLAT, None, clip, None, col)])
 
 
 def flat_800():          # BASELINE config 0 shape: 800x800, flat, CPU-runnable
     clip, col = scenes.random_triangles(100_000, 800, 800, seed=12, rmin=1, rmax=16)
-    return _case(800, 800, [(FLAT, None, clip, None, col)])
+    return make_case(800, 800, [(FLAT, None, clip, None, col)])
 
 
 def flat_persp_512():
     clip, col = scenes.random_triangles(20_000, 512, 512, seed=13, rmin=2, rmax=64, perspective_w=True)
-    return _case(512, 512, [(FLAT, None, clip, None, col)])
+    return make_case(512, 512, [(FLAT, None, clip, None, col)])
 
 
 def flat_big_tris_512():
     clip, col = scenes.random_triangles(400, 512, 512, seed=14, rmin=64, rmax=512)
-    return _case(512, 512, [(FLAT, None, clip, None, col)])
+    return make_case(512, 512, [(FLAT, None, clip, None, col)])
 
 
 def edge_256():
     clip, col = scenes.edge_case_triangles(256, 256)
-    return _case(256, 256, [(FLAT, None, clip, None, col)])
+    return make_case(256, 256, [(FLAT, None, clip, None, col)])
 
 
 def grid_256():
     clip, col = scenes.shared_edge_grid(8, 8, 256, 256)
-    return _case(256, 256, [(FLAT, None, clip, None, col)])
+    return make_case(256, 256, [(FLAT, None, clip, None, col)])
 
 
 def grid_fine_128():
     clip, col = scenes.shared_edge_grid(32, 32, 128, 128, z_slope=0.0)   # all z equal: every shared pixel is a tie
-    return _case(128, 128, [(FLAT, None, clip, None, col)])
+    return make_case(128, 128, [(FLAT, None, clip, None, col)])
 
 
 def gouraud_256_rgba():
     clip, col = scenes.random_triangles(5000, 256, 256, seed=15, rmin=2, rmax=64, perspective_w=True)
     inten = scenes.SplitMix64(5).uniform(5000 * 3, -0.2, 1.3).reshape(5000, 3)
-    return _case(256, 256, [(GOURAUD, None, clip, inten, col)], bpp=4)
+    return make_case(256, 256, [(GOURAUD, None, clip, inten, col)], bpp=4)
 
 
 def _head(level, w, h, tex):
@@ -67,19 +68,19 @@ def _head(level, w, h, tex):
 def phong_512():
     hd, tx = _head(4, 512, 512, 256)
     u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0, 0, 1, 2)
-    return _case(512, 512, [(PHONG, u, hd["clip"], hd["varyings"], None)], textures=tx)
+    return make_case(512, 512, [(PHONG, u, hd["clip"], hd["varyings"], None)], textures=tx)
 
 
 def phong_nomaps_256():
     hd, _ = _head(3, 256, 256, 64)
     u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 0.5, -1, -1, -1)
-    return _case(256, 256, [(PHONG, u, hd["clip"], hd["varyings"], None)])
+    return make_case(256, 256, [(PHONG, u, hd["clip"], hd["varyings"], None)])
 
 
 def eye_256():
     hd, tx = _head(3, 256, 256, 128)
     u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0, 0, -1, 2)
-    return _case(256, 256, [(EYE, u, hd["clip"], hd["varyings"], None)], textures=tx)
+    return make_case(256, 256, [(EYE, u, hd["clip"], hd["varyings"], None)], textures=tx)
 
 
 def multi_draw_320x200():
@@ -92,30 +93,30 @@ def multi_draw_320x200():
     u_ey = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0, 0, -1, -1)
     small = scenes.head_standin(2, w, h, seed=5, distance=4.0)
     fclip, fcol = scenes.random_triangles(500, w, h, seed=17, rmin=2, rmax=24)
-    return _case(w, h, [(PHONG, u_bg, big["clip"], big["varyings"], None),
-                        (PHONG, u_hd, hd["clip"], hd["varyings"], None),
-                        (EYE, u_ey, small["clip"], small["varyings"], None),
-                        (FLAT, None, fclip, None, fcol)], textures=tx, clear=(30, 20, 10, 255))
+    return make_case(w, h, [(PHONG, u_bg, big["clip"], big["varyings"], None),
+                            (PHONG, u_hd, hd["clip"], hd["varyings"], None),
+                            (EYE, u_ey, small["clip"], small["varyings"], None),
+                            (FLAT, None, fclip, None, fcol)], textures=tx, clear=(30, 20, 10, 255))
 
 
 def odd_dims_101x67():
     clip, col = scenes.random_triangles(2000, 101, 67, seed=18, rmin=1, rmax=24)
-    return _case(101, 67, [(FLAT, None, clip, None, col)])
+    return make_case(101, 67, [(FLAT, None, clip, None, col)])
 
 
 def gray_bpp1_96x64():
     clip, col = scenes.random_triangles(1500, 96, 64, seed=19, rmin=1, rmax=24)
-    return _case(96, 64, [(FLAT, None, clip, None, col)], bpp=1)
+    return make_case(96, 64, [(FLAT, None, clip, None, col)], bpp=1)
 
 
 def viewport_offset_256x160():
     clip, col = scenes.random_triangles(3000, 200, 120, seed=20, rmin=1, rmax=32)
-    return _case(256, 160, [(FLAT, None, clip, None, col)], viewport=scenes.init_viewport(16, 8, 200, 120))
+    return make_case(256, 160, [(FLAT, None, clip, None, col)], viewport=scenes.init_viewport(16, 8, 200, 120))
 
 
 def zclear_finite_128():
     clip, col = scenes.random_triangles(3000, 128, 128, seed=21, rmin=2, rmax=32)
-    return _case(128, 128, [(FLAT, None, clip, None, col)], bpp=4, clear=(7, 8, 9, 10), zclear=0.25)
+    return make_case(128, 128, [(FLAT, None, clip, None, col)], bpp=4, clear=(7, 8, 9, 10), zclear=0.25)
 
 
 def huge_depths_128():
@@ -128,7 +129,7 @@ def huge_depths_128():
     clip[1::5, 6] = -1.7e308;  clip[1::5, 10] = -1.7e308      # ... to -inf (would win every z-test if it were written)
     clip[2::5, 6] = 1.7e308;   clip[2::5, 10] = -1.7e308      # huge cancelling terms: finite or not depending on the pixel
     clip[3::5, 6] = -1e300                                     # huge but finite: wins where covered
-    return _case(128, 128, [(FLAT, None, clip, None, col)])
+    return make_case(128, 128, [(FLAT, None, clip, None, col)])
 
 
 def checker_256():
@@ -136,7 +137,7 @@ def checker_256():
     write nothing - no depth, no colour, no counter - so what lies behind them shows through and later fragments are tested against
     the depth they left alone.  Perspective w makes the perspective-correct barycentrics differ from the screen-space ones."""
     clip, col = scenes.random_triangles(4000, 256, 256, seed=31, rmin=4, rmax=48, perspective_w=True)
-    return _case(256, 256, [(CHECKER, make_uniforms(cells=6), clip, None, col)])
+    return make_case(256, 256, [(CHECKER, make_uniforms(cells=6), clip, None, col)])
 
 
 def checker_mixed_200x120():
@@ -146,11 +147,11 @@ def checker_mixed_200x120():
     c1, k1 = scenes.random_triangles(1500, w, h, seed=33, rmin=4, rmax=40, perspective_w=True)
     c2, k2 = scenes.random_triangles(600, w, h, seed=34, rmin=2, rmax=24, perspective_w=True)
     v2 = scenes.SplitMix64(35).uniform(600 * 3, 0.1, 1.2).reshape(600, 3)
-    return _case(w, h, [(FLAT, None, c0, None, k0), (CHECKER, make_uniforms(cells=3), c1, None, k1), (GOURAUD, None, c2, v2, k2)], bpp=4)
+    return make_case(w, h, [(FLAT, None, c0, None, k0), (CHECKER, make_uniforms(cells=3), c1, None, k1), (GOURAUD, None, c2, v2, k2)], bpp=4)
 
 
 def empty_scene_64():
-    return _case(64, 64, [])
+    return make_case(64, 64, [])
 
 
 # ---- z ranges that end in a signed zero.  std::min / std::max (our_gl.cpp:197-198) keep the first of two equal values and
@@ -196,7 +197,7 @@ def zero_min_neg_first_96x64():
     clip = fold_depths(clip, 1.0)
     set_zero_depths(clip, range(100, 103), -1.0)
     set_zero_depths(clip, range(250, 253), 1.0)
-    return _case(96, 64, [(FLAT, None, clip, None, col)])
+    return make_case(96, 64, [(FLAT, None, clip, None, col)])
 
 
 def zero_min_pos_first_96x64():
@@ -205,7 +206,7 @@ def zero_min_pos_first_96x64():
     clip = fold_depths(clip, 1.0)
     set_zero_depths(clip, range(120, 123), 1.0)
     set_zero_depths(clip, range(200, 203), -1.0)
-    return _case(96, 64, [(FLAT, None, clip, None, col)])
+    return make_case(96, 64, [(FLAT, None, clip, None, col)])
 
 
 def zero_signs_in_one_triangle_96x64():
@@ -217,7 +218,7 @@ def zero_signs_in_one_triangle_96x64():
     tri = screen_triangle((20.5, 52.5), (20.5, 18.5), (60.5, 10.2), z=(-0.0, -0.0, 0.0))
     clip = np.concatenate([clip[:150], tri[None], clip[150:]])
     col = np.concatenate([col[:150], np.array([0xFF10E0F0], np.uint32), col[150:]])
-    return _case(96, 64, [(FLAT, None, clip, None, col)], viewport=UNIT_VIEWPORT)
+    return make_case(96, 64, [(FLAT, None, clip, None, col)], viewport=UNIT_VIEWPORT)
 
 
 def zero_max_neg_first_96x64():
@@ -226,7 +227,7 @@ def zero_max_neg_first_96x64():
     clip = fold_depths(clip, -1.0)
     set_zero_depths(clip, range(20, 23), -1.0)
     set_zero_depths(clip, range(23, 26), 1.0)
-    return _case(96, 64, [(FLAT, None, clip, None, col)], bpp=4)
+    return make_case(96, 64, [(FLAT, None, clip, None, col)], bpp=4)
 
 
 def zero_checker_discarded_first_96x64():
@@ -242,8 +243,8 @@ def zero_checker_discarded_first_96x64():
     later = screen_triangle((60.5, 40.5), (85.5, 45.5), (70.5, 58.5), z=(-0.0, -0.0, -0.0))
     tris = np.concatenate([tris[:80], first[None], tris[80:140], later[None], tris[140:]])
     tcol = np.concatenate([tcol[:80], np.array([0xFF3060C0], np.uint32), tcol[80:140], np.array([0xFFC06030], np.uint32), tcol[140:]])
-    return _case(w, h, [(FLAT, None, base, None, bcol), (CHECKER, make_uniforms(cells=2), tris, None, tcol)],
-                 viewport=UNIT_VIEWPORT)
+    return make_case(w, h, [(FLAT, None, base, None, bcol), (CHECKER, make_uniforms(cells=2), tris, None, tcol)],
+                     viewport=UNIT_VIEWPORT)
 
 
 def phong_soup_varyings(n, seed):
@@ -266,7 +267,7 @@ def zero_phong_128x96():
     set_zero_depths(clip, range(200, 203), -1.0)
     hd, tx = _head(1, w, h, 64)
     u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 0.7, 0, 1, 2)
-    return _case(w, h, [(PHONG, u, clip, phong_soup_varyings(360, 48), None)], textures=tx)
+    return make_case(w, h, [(PHONG, u, clip, phong_soup_varyings(360, 48), None)], textures=tx)
 
 
 # the sign each zero case's z range must end at: (min end, max end) as copysign(1, .) of the printed value, None = not zero
@@ -297,44 +298,127 @@ def vecops_inputs(n=2000):
     return data, packed
 
 
-def run_oracle(case, strip=None):
-    """Render a case with the CPU oracle; returns (fb, z, stats tuple)."""
+# ---- render a case and check it: the one harness of the GPU tests ---------------------------------------------------
+def run_oracle(case, strip=None, start=None):
+    """Render a case with the CPU oracle; returns (fb, z, stats tuple).  strip = (y0, y1): only those rows are drawn.
+    start = (fb, z): the frame starts from these buffers instead of the clear (a None one is cleared)."""
     from oracle import orc
     o = orc.Oracle(case["width"], case["height"], case["bpp"], viewport=case["viewport"], clear_bgra=case["clear"],
                    z_clear=case["zclear"], strip=strip)
+    fb0, z0 = start or (None, None)
+    if fb0 is not None:
+        o.fb[:] = fb0
+    if z0 is not None:
+        o.z[:] = z0
     for slot, t in case["textures"].items():
         o.upload_texture(slot, t)
     for kind, u, clip, vary, col in case["draws"]:
-        ou = None
-        if u is not None:
-            ou = orc.Uniforms.from_buffer_copy(bytes(u))
-        o.draw(kind, clip, vary, col, ou)
+        o.draw(kind, clip, vary, col, None if u is None else orc.Uniforms.from_buffer_copy(bytes(u)))
     return o.fb, o.z, o.stats
 
 
-def run_gpu(case, strip=None, split=None):
-    """Render a case through the C ABI on the GPU; split=k submits each draw in k flushes."""
+def run_gpu(case, strip=None, interleave=None, split=None, flush_after=None, halves=False, start=None, shaders=None):
+    """Render a case through the C ABI on the GPU; returns (fb, z, stats tuple, stats line).
+    strip = (y0, y1): a strip context (set_strip); interleave = (band_rows, rank, world): one rank's bands (set_interleave).
+    split = k: each draw in k flushes; flush_after = i: a flush after draw i; halves: the last flush as flush_begin / flush_end.
+    start = (fb, z): as for run_oracle, through write_framebuffer / write_zbuffer.
+    shaders: per draw, None or (source, K): the draw uses the user kind the context registers for that source.
+    Clip and colour arrays that are torch CUDA tensors are drawn from device memory."""
     from tinyrenderder_amd.api import Context
+    shaders = shaders or [None] * len(case["draws"])
     with Context(case["width"], case["height"], case["bpp"]) as ctx:
+        user = {sh: ctx.register_shader(*sh) for sh in dict.fromkeys(sh for sh in shaders if sh)}
         ctx.set_viewport(case["viewport"])
-        ctx.clear(case["clear"], case["zclear"])
+        fb0, z0 = start or (None, None)
+        if fb0 is None or z0 is None:
+            ctx.clear(case["clear"], case["zclear"])
+        if fb0 is not None:
+            ctx.write_framebuffer(fb0)
+        if z0 is not None:
+            ctx.write_zbuffer(z0)
         if strip is not None:
             ctx.set_strip(*strip)
+        if interleave is not None:
+            ctx.set_interleave(*interleave)
         for slot, t in case["textures"].items():
             ctx.upload_texture(slot, t)
-        for kind, u, clip, vary, col in case["draws"]:
+        for i, ((kind, u, clip, vary, col), sh) in enumerate(zip(case["draws"], shaders)):
             n = clip.shape[0]
-            parts = 1 if not split else split
-            edges = [n * i // parts for i in range(parts + 1)]
+            parts = split or 1
+            edges = [n * k // parts for k in range(parts + 1)]
             for a, b in zip(edges[:-1], edges[1:]):
                 if a == b:
                     continue
-                ctx.draw(kind, clip[a:b], None if vary is None else vary[a:b], None if col is None else col[a:b], u)
+                ctx.draw(user[sh] if sh else kind, clip[a:b], None if vary is None else vary[a:b],
+                         None if col is None else col[a:b], u, device=not isinstance(clip, np.ndarray))
                 if split:
                     ctx.flush()
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-        line = ctx.stats_line()
-    return fb, z, st, line
+            if i == flush_after:
+                ctx.flush()
+        if halves:
+            ctx.flush_begin()
+            ctx.flush_end()
+        return ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats(), ctx.stats_line()
+
+
+def has_eye(case):
+    """EYE draws shade with pow(x, 8), whose last ulp may differ from the oracle's (see assert_same_frame)."""
+    return any(d[0] == EYE for d in case["draws"])
+
+
+def band_rows(height, interleave):
+    """Row ranges [y0, y1) that set_interleave(band_rows, rank, world) = interleave gives its rank (all rows for one rank)."""
+    from tinyrenderder_amd import shard
+    band, rank, world = interleave
+    return shard.band_rows_of(height, world, rank, band) if world > 1 else [(0, height)]
+
+
+def assert_same_frame(got, want, rows=None, eye=False, stats=True, what="frame"):
+    """got, want: (fb, z, stats tuple[, stats line]) as run_gpu / run_oracle return them.  In `rows` (None: every row; one
+    (y0, y1) or a list of them) the z bits and the framebuffer bytes are equal; so are the stats tuples unless stats=False (a
+    strip or band against the whole frame), and then the stats lines when both sides have one.
+    eye: a colour byte may be 1 LSB off, on at most 0.1 % of the pixels of each row range (EYE's pow(x, 8)); z stays exact."""
+    ranges = [(0, got[0].shape[0])] if rows is None else [rows] if np.isscalar(rows[0]) else rows
+    for y0, y1 in ranges:
+        _assert_none(got[1][y0:y1].view(np.uint64) != want[1][y0:y1].view(np.uint64), y0, f"{what}: z values differ")
+        fb, ref = got[0][y0:y1], want[0][y0:y1]
+        if not eye:
+            _assert_none(fb != ref, y0, f"{what}: framebuffer bytes differ")
+            continue
+        d = np.abs(fb.astype(np.int16) - ref.astype(np.int16))
+        _assert_none(d > 1, y0, f"{what}: colour bytes differ by more than 1 LSB")
+        px = d.max(axis=-1) > 0
+        assert px.mean() <= 1e-3, f"{what}: {px.sum()} of {px.size} pixels differ, first at {_first(px, y0)}"
+    if stats:
+        assert got[2] == want[2], f"{what}: stats {got[2]} != {want[2]}"
+        if len(got) > 3 and len(want) > 3:
+            assert got[3] == want[3], f"{what}: stats line {got[3]!r} != {want[3]!r}"
+
+
+def _first(bad, y0):
+    at = np.argwhere(bad)[:5]
+    at[:, 0] += y0
+    return at.tolist()
+
+
+def _assert_none(bad, y0, what):
+    assert not bad.any(), f"{what}: {int(bad.sum())} of them, first at {_first(bad, y0)}"
+
+
+def check_gpu(case, strip=None, split=None):
+    """run_gpu against run_oracle with the same strip, on the strip's rows (EYE draws within their tolerance); returns run_gpu's."""
+    got = run_gpu(case, strip=strip, split=split)
+    assert_same_frame(got, run_oracle(case, strip=strip), rows=strip, eye=has_eye(case))
+    return got
+
+
+def assert_golden(got, g, eye=False):
+    """got (run_gpu) against a golden entry (the reference's own frame): its stats line and the digests of its z bits and,
+    unless eye (the oracle comparison bounds EYE colours), of its framebuffer bytes."""
+    assert got[3] == g["stats"], (got[3], g["stats"])
+    assert scenes.digest(got[1]) == g["z"], "z-buffer digest differs"
+    if not eye:
+        assert scenes.digest(got[0]) == g["fb"], "framebuffer digest differs"
 
 
 # ---- BASELINE configs[3] / [4] at their stated sizes (SURVEY.md §8(d): C4 = 10 M random triangles at 4096^2,
@@ -343,12 +427,12 @@ def run_gpu(case, strip=None, split=None):
 # digests of its framebuffer bytes, z-buffer bits and its print_render_stats() line.
 def c4_4096_10m():
     clip, col = scenes.random_triangles(10_000_000, 4096, 4096)          # = bench.py's default workload
-    return _case(4096, 4096, [(FLAT, None, clip, None, col)])
+    return make_case(4096, 4096, [(FLAT, None, clip, None, col)])
 
 
 def c5_8192_10m():
     clip, col = scenes.random_triangles(10_000_000, 8192, 8192, seed=0x5EED0005, rmin=2, rmax=40)
-    return _case(8192, 8192, [(FLAT, None, clip, None, col)])
+    return make_case(8192, 8192, [(FLAT, None, clip, None, col)])
 
 
 FULLSIZE_CASES = {f.__name__: f for f in (c4_4096_10m, c5_8192_10m)}

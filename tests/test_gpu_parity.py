@@ -2,7 +2,7 @@
 
 Bar: z-buffer bit-identical, framebuffer byte-identical, stats tuple identical.  The only
 tolerance is for EYE (std::pow with exponent 8 vs device pow): at most 1 LSB per colour byte on at most 0.1 % of
-pixels; z and stats stay exact.
+pixels; z and stats stay exact (cases.assert_same_frame).
 """
 import json
 import os
@@ -15,102 +15,74 @@ from oracle import orc
 from tinyrenderder_amd import scenes
 from tinyrenderder_amd.api import Context, FLAT
 
+check, same = cases.check_gpu, cases.assert_same_frame
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = json.load(open(os.path.join(HERE, "golden", "golden.json")))
 GOLDEN_FULL = json.load(open(os.path.join(HERE, "golden", "golden_fullsize.json")))
-POW_CASES = {"eye_256", "multi_draw_320x200"}      # contain EYE fragments
 
 
-def _assert_fb(fb, ref, name):
-    if name in POW_CASES and not np.array_equal(fb, ref):
-        d = np.abs(fb.astype(np.int16) - ref.astype(np.int16))
-        assert d.max() <= 1, f"{name}: colour differs by more than 1 LSB"
-        assert (d.max(axis=-1) > 0).mean() <= 1e-3, f"{name}: more than 0.1 % of pixels differ"
-    else:
-        bad = np.argwhere(fb != ref)
-        assert bad.size == 0, f"{name}: {len(bad)} framebuffer bytes differ, first at {bad[:5].tolist()}"
+def _flat(W, H, clip, col, **kw):
+    return cases.make_case(W, H, [(FLAT, None, clip, None, col)], **kw)
+
+
+def _on_device(case):
+    """The case with its clip and colour arrays in device memory (torch CUDA tensors: run_gpu draws them with device=True)."""
+    import torch
+    draws = [(kind, u, torch.from_numpy(clip).cuda(), vary, torch.from_numpy(col.view(np.int32)).cuda())
+             for kind, u, clip, vary, col in case["draws"]]
+    return dict(case, draws=draws)
 
 
 @pytest.mark.parametrize("name", sorted(cases.CASES))
 def test_gpu_matches_reference_golden_and_oracle(name):
     case = cases.CASES[name]()
-    g = GOLDEN[name]
-    fb, z, st, line = cases.run_gpu(case)
-    ofb, oz, ost = cases.run_oracle(case)
-    bad = np.argwhere(z.view(np.uint64) != oz.view(np.uint64))
-    assert bad.size == 0, f"{name}: {len(bad)} z values differ, first at {bad[:5].tolist()}"
-    _assert_fb(fb, ofb, name)
-    assert st == ost
-    assert line == g["stats"]
-    assert scenes.digest(z) == g["z"]
-    if name not in POW_CASES:
-        assert scenes.digest(fb) == g["fb"]
+    cases.assert_golden(check(case), GOLDEN[name], eye=cases.has_eye(case))
 
 
 @pytest.mark.parametrize("name", ["flat_persp_512", "multi_draw_320x200", "grid_fine_128"])
 def test_split_submission_is_invisible(name):
     """Submitting the same triangles over several flushes (read-modify-write of tiles) changes nothing."""
     case = cases.CASES[name]()
-    fb, z, st, _ = cases.run_gpu(case)
-    fb2, z2, st2, _ = cases.run_gpu(case, split=3)
-    assert np.array_equal(z.view(np.uint64), z2.view(np.uint64))
-    assert np.array_equal(fb, fb2)
-    assert st == st2
+    same(cases.run_gpu(case, split=3), cases.run_gpu(case))
 
 
 @pytest.mark.parametrize("cut", [200, 256, 31])
 def test_strips_compose(cut):
     """Multi-GPU shard, run sequentially on one GPU: two strip contexts give the rows of the whole image."""
     case = cases.CASES["flat_persp_512"]()
-    fb, z, st, _ = cases.run_gpu(case)
+    whole = cases.run_gpu(case)
+    st = whole[2]
     h = case["height"]
-    fb0, z0, s0, _ = cases.run_gpu(case, strip=(0, cut))
-    fb1, z1, s1, _ = cases.run_gpu(case, strip=(cut, h))
-    assert np.array_equal(np.concatenate([fb0[:cut], fb1[cut:]]), fb)
-    assert np.array_equal(np.concatenate([z0[:cut], z1[cut:]]).view(np.uint64), z.view(np.uint64))
+    s0 = cases.run_gpu(case, strip=(0, cut))
+    s1 = cases.run_gpu(case, strip=(cut, h))
+    same(s0, whole, rows=(0, cut), stats=False, what="strip 0")
+    same(s1, whole, rows=(cut, h), stats=False, what="strip 1")
+    s0, s1 = s0[2], s1[2]
     assert s0[1] + s1[1] == st[1] and min(s0[6], s1[6]) == st[6] and max(s0[7], s1[7]) == st[7]
     assert s0[2:6] == st[2:6]
     # and the strip itself matches the oracle restricted to the same rows
-    ofb, oz, os_ = cases.run_oracle(case, strip=(0, cut))
-    assert np.array_equal(fb0[:cut], ofb[:cut]) and s0 == os_
+    check(case, strip=(0, cut))
 
 
 def test_c4_prefix_4096_vs_oracle():
     """BASELINE config 3 at full resolution, 300k-triangle prefix (the oracle needs ~1.5 s for it)."""
     W = H = 4096
-    clip, col = scenes.random_triangles(300_000, W, H)
-    with Context(W, H, 3) as ctx:
-        ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
+    check(_flat(W, H, *scenes.random_triangles(300_000, W, H)))
 
 
 def test_c4_full_size_properties():
     """10 M triangles at 4096x4096 (BASELINE config 3): too slow for the scalar oracle, so check the
     size-independent properties: determinism, split-submission invariance, and the counters' invariants."""
-    import torch
     W = H = 4096
     N = 10_000_000
-    clip, col = scenes.random_triangles(N, W, H)
-    dclip = torch.from_numpy(clip).cuda()
-    dcol = torch.from_numpy(col.view(np.int32)).cuda()
-    res = []
-    for parts in (1, 1, 4):
-        with Context(W, H, 3) as ctx:
-            edges = [N * i // parts for i in range(parts + 1)]
-            for a, b in zip(edges[:-1], edges[1:]):
-                ctx.draw(FLAT, dclip[a:b], colors=dcol[a:b], device=True)
-                ctx.flush()
-            res.append((scenes.digest(ctx.read_framebuffer()), scenes.digest(ctx.read_zbuffer()), ctx.stats()))
-    assert res[0] == res[1], "two identical runs differ"
-    assert res[0] == res[2], "4 flushes differ from 1 flush"
-    st = res[0][2]
+    case = _on_device(cases.FULLSIZE_CASES["c4_4096_10m"]())      # scenes.random_triangles(N, W, H)
+    first = cases.run_gpu(case, split=1)
+    same(cases.run_gpu(case, split=1), first, what="two identical runs")
+    same(cases.run_gpu(case, split=4), first, what="4 flushes against 1 flush")
+    st = first[2]
     assert st[0] == N and st[2:6] == (0, 0, W - 1, H - 1) and st[1] > 0 and -1.0 <= st[6] < st[7] <= 1.0
 
 
@@ -118,18 +90,7 @@ def test_c4_full_size_equals_the_reference_frame():
     """BASELINE configs[3] at its stated size — the frame bench.py times: all 10 M triangles at 4096x4096 against the
     frame the reference's own rasterize() rendered (tests/golden/golden_fullsize.json: sha256 of its framebuffer bytes and
     z-buffer bits, its print_render_stats() line)."""
-    import torch
-    g = GOLDEN_FULL["c4_4096_10m"]
-    case = cases.FULLSIZE_CASES["c4_4096_10m"]()
-    _, _, clip, _, col = case["draws"][0]
-    dclip = torch.from_numpy(clip).cuda()
-    dcol = torch.from_numpy(col.view(np.int32)).cuda()
-    with Context(4096, 4096, 3) as ctx:
-        ctx.draw(FLAT, dclip, colors=dcol, device=True)
-        fb, z, line = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats_line()
-    assert line == g["stats"]
-    assert scenes.digest(z) == g["z"]
-    assert scenes.digest(fb) == g["fb"]
+    cases.assert_golden(cases.run_gpu(_on_device(cases.FULLSIZE_CASES["c4_4096_10m"]())), GOLDEN_FULL["c4_4096_10m"])
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -170,14 +131,7 @@ def test_block_masks_on_adversarial_shapes(seed):
         zs = [-1.0, 1.0, -1.0 + 2.0 * u[i, 3]] if kind == 2 else [2.0 * u[i, 3] - 1.0, 2.0 * u[i, 1] - 1.0, 2.0 * u[i, 2] - 1.0]
         for v in range(3):
             clip[i, 4 * v + 0], clip[i, 4 * v + 1], clip[i, 4 * v + 2], clip[i, 4 * v + 3] = p[v][0], p[v][1], zs[v], 1.0
-    with Context(W, H, 3) as ctx:
-        ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
+    check(_flat(W, H, clip, col))
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -212,20 +166,10 @@ def test_depth_plane_early_test_on_extreme_depths(seed):
     # stored depths the flush starts from: finite band, NaN, -inf, +inf columns
     z0 = np.full((H, W), np.inf)
     z0[:, 0:40] = 0.25; z0[:, 40:70] = np.nan; z0[:, 70:100] = -np.inf; z0[:, 100:130] = -0.5; z0[10:20, :] = 1e-310
-    with Context(W, H, 3) as ctx:
-        ctx.clear((1, 2, 3, 255))
-        ctx.write_zbuffer(z0)
-        half = n // 2
-        ctx.draw(FLAT, clip[:half], colors=col[:half]); ctx.flush()
-        ctx.draw(FLAT, clip[half:], colors=col[half:])
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3, clear_bgra=(1, 2, 3, 255))
-    o.z[:] = z0
-    o.draw(orc.FLAT, clip, colors=col)
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
-    assert st[1] > 50_000
+    case = _flat(W, H, clip, col, clear=(1, 2, 3, 255))
+    got = cases.run_gpu(case, start=(None, z0), split=2)       # (two flushes of n / 2)
+    same(got, cases.run_oracle(case, start=(None, z0)))
+    assert got[2][1] > 50_000
 
 
 @pytest.mark.parametrize("bpp", [1, 4])
@@ -238,15 +182,8 @@ def test_phong_and_eye_on_gray_and_rgba_framebuffers(bpp):
     d, n, sp = scenes.procedural_textures(64)
     u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0, 0, 1, 2)
     for kind in (PHONG, EYE):
-        case = cases._case(w, h, [(kind, u, hd["clip"], hd["varyings"], None)], bpp=bpp, textures={0: d, 1: n, 2: sp}, clear=(30, 20, 10, 200))
-        ofb, oz, ost = cases.run_oracle(case)
-        fb, z, st, _ = cases.run_gpu(case)
-        assert np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and st == ost
-        if kind == PHONG:
-            assert np.array_equal(fb, ofb)
-        else:                       # EYE: pow(x, 8) may differ in the last ulp -> at most 1 LSB on at most 0.1 % of the bytes
-            diff = np.abs(fb.astype(np.int16) - ofb.astype(np.int16))
-            assert diff.max() <= 1 and (diff != 0).mean() <= 1e-3
+        check(cases.make_case(w, h, [(kind, u, hd["clip"], hd["varyings"], None)], bpp=bpp, textures={0: d, 1: n, 2: sp},
+                              clear=(30, 20, 10, 200)))
 
 
 def test_flush_in_two_halves():
@@ -254,7 +191,7 @@ def test_flush_in_two_halves():
     called in between completes the begun flush first (here: a second draw, then a read-back)."""
     case = cases.CASES["flat_persp_512"]()
     kind, u, clip, vary, col = case["draws"][0]
-    ofb, oz, ost = cases.run_oracle(case)
+    want = cases.run_oracle(case)
     half = clip.shape[0] // 2
     with Context(case["width"], case["height"], case["bpp"]) as ctx:
         ctx.draw(kind, clip[:half], colors=col[:half])
@@ -265,13 +202,12 @@ def test_flush_in_two_halves():
         ctx.draw(kind, clip[half:], colors=col[half:])
         ctx.flush_begin()
         fb = ctx.read_framebuffer()                         # completes the begun flush
-        z, st = ctx.read_zbuffer(), ctx.stats()
-    assert np.array_equal(fb, ofb) and np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and st == ost
+        same((fb, ctx.read_zbuffer(), ctx.stats()), want)
     with Context(case["width"], case["height"], case["bpp"]) as ctx:
         ctx.draw(kind, clip[:half], colors=col[:half])
         ctx.flush_begin()
         ctx.draw(kind, clip[half:], colors=col[half:])      # completes the begun flush, then queues
-        assert np.array_equal(ctx.read_framebuffer(), ofb)
+        same((ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()), want)
 
 
 def test_two_phong_draws_in_one_flush_and_strips():
@@ -285,14 +221,11 @@ def test_two_phong_draws_in_one_flush_and_strips():
     d, n, sp = scenes.procedural_textures(128)
     u_bg = make_uniforms(big["model_view"], big["key"], big["fill"], big["rim"], 0.5, 0, 1, -1)
     u_hd = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0, 0, 1, 2)
-    case = cases._case(w, h, [(PHONG, u_bg, big["clip"], big["varyings"], None), (PHONG, u_hd, hd["clip"], hd["varyings"], None)],
-                       textures={0: d, 1: n, 2: sp}, clear=(30, 20, 10, 255))
-    ofb, oz, ost = cases.run_oracle(case)
-    fb, z, st, _ = cases.run_gpu(case)
-    assert np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and np.array_equal(fb, ofb) and st == ost
-    for y0, y1 in ((0, 77), (77, 131), (131, h)):
-        sfb, sz, _, _ = cases.run_gpu(case, strip=(y0, y1))
-        assert np.array_equal(sfb[y0:y1], ofb[y0:y1]) and np.array_equal(sz[y0:y1].view(np.uint64), oz[y0:y1].view(np.uint64))
+    case = cases.make_case(w, h, [(PHONG, u_bg, big["clip"], big["varyings"], None), (PHONG, u_hd, hd["clip"], hd["varyings"], None)],
+                           textures={0: d, 1: n, 2: sp}, clear=(30, 20, 10, 255))
+    check(case)
+    for strip in ((0, 77), (77, 131), (131, h)):
+        check(case, strip=strip)
 
 
 def test_c5_8192_eight_strips_compose():
@@ -300,29 +233,18 @@ def test_c5_8192_eight_strips_compose():
     strips the 8 ranks of `bench.py --gpus 8` own and rendered one after the other by strip contexts.  The unsharded frame
     equals the frame the reference's own rasterize() rendered (golden_fullsize.json), and the strips equal its rows,
     depths, summed fragment counts and z range.  (What RCCL then does with the strips is a plain all-gather.)"""
-    import torch
-    g = GOLDEN_FULL["c5_8192_10m"]
-    case = cases.FULLSIZE_CASES["c5_8192_10m"]()
-    W = H = 8192
+    case = _on_device(cases.FULLSIZE_CASES["c5_8192_10m"]())
+    H = 8192
     G = 8
-    _, _, clip, _, col = case["draws"][0]
-    dclip = torch.from_numpy(clip).cuda()
-    dcol = torch.from_numpy(col.view(np.int32)).cuda()
-    with Context(W, H, 3) as ctx:
-        ctx.draw(FLAT, dclip, colors=dcol, device=True)
-        fb, z, st, line = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats(), ctx.stats_line()
-    assert line == g["stats"]
-    assert scenes.digest(z) == g["z"]
-    assert scenes.digest(fb) == g["fb"]
+    whole = cases.run_gpu(case)
+    cases.assert_golden(whole, GOLDEN_FULL["c5_8192_10m"])
+    st = whole[2]
     frags, zmin, zmax = 0, np.inf, -np.inf
     for r in range(G):
         y0, y1 = H * r // G, H * (r + 1) // G
-        with Context(W, H, 3) as ctx:
-            ctx.set_strip(y0, y1)
-            ctx.draw(FLAT, dclip, colors=dcol, device=True)
-            sfb, sz, sst = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-        assert np.array_equal(sfb[y0:y1], fb[y0:y1]), f"strip {r}: colours"
-        assert np.array_equal(sz[y0:y1].view(np.uint64), z[y0:y1].view(np.uint64)), f"strip {r}: depths"
+        strip = cases.run_gpu(case, strip=(y0, y1))
+        same(strip, whole, rows=(y0, y1), stats=False, what=f"strip {r}")
+        sst = strip[2]
         assert sst[0] == st[0] and sst[2:6] == st[2:6]
         frags += sst[1]; zmin = min(zmin, sst[6]); zmax = max(zmax, sst[7])
     assert (frags, zmin, zmax) == (st[1], st[6], st[7])
@@ -336,12 +258,10 @@ def test_readback_roundtrip_and_zbuffer_restore():
         ctx.draw(kind, clip[:150], colors=col[:150])
         z_before = ctx.read_zbuffer()
         ctx.draw(kind, clip[150:], colors=col[150:])
-        fb_after = ctx.read_framebuffer()
+        after = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats())
         ctx.write_zbuffer(z_before)
-        assert np.array_equal(ctx.read_zbuffer().view(np.uint64), z_before.view(np.uint64))
-        assert np.array_equal(ctx.read_framebuffer(), fb_after)
-    ofb, _, _ = cases.run_oracle(case)
-    assert np.array_equal(fb_after, ofb)
+        same((ctx.read_framebuffer(), ctx.read_zbuffer()), (after[0], z_before), stats=False, what="after the restore")
+    same(after, cases.run_oracle(case))
 
 
 def test_clear_between_frames_and_error_paths():
@@ -352,10 +272,8 @@ def test_clear_between_frames_and_error_paths():
         a = ctx.read_framebuffer()
         ctx.clear((1, 2, 3, 4), 0.0)          # nothing passes z < 0 ... except negative z
         ctx.draw(FLAT, clip, colors=col)
-        b, zb = ctx.read_framebuffer(), ctx.read_zbuffer()
-        o = orc.Oracle(96, 64, 4, clear_bgra=(1, 2, 3, 4), z_clear=0.0)
-        o.draw(orc.FLAT, clip, colors=col)
-        assert np.array_equal(b, o.fb) and np.array_equal(zb.view(np.uint64), o.z.view(np.uint64))
+        b = ctx.read_framebuffer()
+        same((b, ctx.read_zbuffer()), cases.run_oracle(_flat(96, 64, clip, col, bpp=4, clear=(1, 2, 3, 4), zclear=0.0)), stats=False)
         assert not np.array_equal(a, b)
         with pytest.raises(TrglError):
             ctx.draw(PHONG, clip, varyings=np.zeros((500, 24)))   # PHONG without uniforms
@@ -379,14 +297,7 @@ def test_badly_scaled_triangles_take_the_literal_path():
     clip[::7, 0] = -1e250          # one vertex absurdly far left
     clip[3::11, 5] = -1e200        # or far below
     clip[5::13, 0:2] *= 1e-300     # or collapsing towards the origin (tiny edge deltas)
-    with Context(W, H, 3) as ctx:
-        ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
+    check(_flat(W, H, clip, col))
 
 
 def test_literal_and_well_scaled_flushes_alternate_on_one_context():
@@ -405,9 +316,7 @@ def test_literal_and_well_scaled_flushes_alternate_on_one_context():
             part = batch[k * 1000:(k + 1) * 1000]; pc = col[k * 1000:(k + 1) * 1000]
             ctx.draw(FLAT, part, colors=pc); ctx.flush()
             o.draw(orc.FLAT, part, colors=pc)
-            assert np.array_equal(ctx.read_zbuffer().view(np.uint64), o.z.view(np.uint64)), k
-            assert np.array_equal(ctx.read_framebuffer(), o.fb), k
-        assert ctx.stats() == o.stats
+            same((ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()), (o.fb, o.z, o.stats), what=f"flush {k}")
 
 
 def test_bench_rccl_strip_gather_path_single_rank():
@@ -438,18 +347,7 @@ def test_baseline_phong_configs_full_size(cfg):
     slots = (0, -1, -1) if cfg.startswith("c2") else (0, 1, 2)
     tex = {0: d} if cfg.startswith("c2") else {0: d, 1: n, 2: s}
     args = (hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0) + slots
-    with Context(size, size, 3) as ctx:
-        for k, t in tex.items():
-            ctx.upload_texture(k, t)
-        ctx.draw(PHONG, hd["clip"], hd["varyings"], uniforms=make_uniforms(*args))
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(size, size, 3)
-    for k, t in tex.items():
-        o.upload_texture(k, t)
-    o.draw(orc.PHONG, hd["clip"], hd["varyings"], uniforms=orc.make_uniforms(*args))
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
+    st = check(cases.make_case(size, size, [(PHONG, make_uniforms(*args), hd["clip"], hd["varyings"], None)], textures=tex))[2]
     assert st[1] > 100_000          # the head covers a good part of the screen
 
 
@@ -475,21 +373,7 @@ def test_fuzz_flat_scenes_against_oracle(seed):
     clip[3 * k:4 * k, [2, 6, 10]] = np.round(clip[3 * k:4 * k, [2, 6, 10]] * 4) / 4 * clip[3 * k:4 * k, [3, 7, 11]]   # few distinct depths
     zclear = np.inf if seed % 4 else float(0.3 * (u[6] - 0.5))
     strip = None if seed % 5 else (H // 3, H - H // 5)
-    parts = 1 + seed % 3
-    with Context(W, H, 3) as ctx:
-        ctx.clear((9, 8, 7, 255), zclear)
-        if strip:
-            ctx.set_strip(*strip)
-        edges = [n * i // parts for i in range(parts + 1)]
-        for a, b in zip(edges[:-1], edges[1:]):
-            ctx.draw(FLAT, clip[a:b], colors=col[a:b]); ctx.flush()
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3, clear_bgra=(9, 8, 7, 255), z_clear=zclear, strip=strip)
-    o.draw(orc.FLAT, clip, colors=col)
-    rows = slice(None) if strip is None else slice(*strip)
-    assert np.array_equal(z[rows].view(np.uint64), o.z[rows].view(np.uint64))
-    assert np.array_equal(fb[rows], o.fb[rows])
-    assert st == o.stats
+    check(_flat(W, H, clip, col, clear=(9, 8, 7, 255), zclear=zclear), strip=strip, split=1 + seed % 3)
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -507,16 +391,7 @@ def test_fuzz_gouraud_scenes_against_oracle(seed):
     inten = scenes.SplitMix64(9300 + seed).uniform(n * 3, -0.3, 1.4).reshape(n, 3)
     clip[::5, [2, 6, 10]] *= 1.0 + 3.0 * u[4]                  # some depths beyond the clip range
     clip[1::9, 6] = clip[1::9, 7] * 1e6                          # a far vertex: steep depth planes
-    half = n // 2
-    with Context(W, H, bpp) as ctx:
-        ctx.draw(GOURAUD, clip[:half], varyings=inten[:half], colors=col[:half]); ctx.flush()
-        ctx.draw(GOURAUD, clip[half:], varyings=inten[half:], colors=col[half:])
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, bpp)
-    o.draw(orc.GOURAUD, clip, inten, colors=col)
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
+    check(cases.make_case(W, H, [(GOURAUD, None, clip, inten, col)], bpp=bpp), split=2)
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -545,23 +420,7 @@ def test_fuzz_phong_soup_against_oracle(seed):
     hd = scenes.head_standin(1, W, H)
     uni = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 0.7, 0, 1, 2)
     strip = None if seed % 2 else (H // 4, H - H // 3)
-    half = n // 2
-    with Context(W, H, 3) as ctx:
-        for slot, t in ((0, d), (1, nm), (2, sp)):
-            ctx.upload_texture(slot, t)
-        if strip:
-            ctx.set_strip(*strip)
-        ctx.draw(PHONG, clip[:half], varyings=vary[:half], uniforms=uni); ctx.flush()
-        ctx.draw(PHONG, clip[half:], varyings=vary[half:], uniforms=uni)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3, strip=strip)
-    for slot, t in ((0, d), (1, nm), (2, sp)):
-        o.upload_texture(slot, t)
-    o.draw(orc.PHONG, clip, vary, uniforms=orc.Uniforms.from_buffer_copy(bytes(uni)))
-    rows = slice(None) if strip is None else slice(*strip)
-    assert np.array_equal(z[rows].view(np.uint64), o.z[rows].view(np.uint64))
-    assert np.array_equal(fb[rows], o.fb[rows])
-    assert st == o.stats
+    check(cases.make_case(W, H, [(PHONG, uni, clip, vary, None)], textures={0: d, 1: nm, 2: sp}), strip=strip, split=2)
 
 
 def test_mixed_flush_with_gouraud_runs_the_any_kernel():
@@ -577,21 +436,14 @@ def test_mixed_flush_with_gouraud_runs_the_any_kernel():
     fclip, fcol = scenes.random_triangles(800, w, h, seed=73, rmin=2, rmax=24)
     small = scenes.head_standin(2, w, h, seed=5, distance=4.0)
     for bpp in (1, 3, 4):
-        case = cases._case(w, h, [(GOURAUD, None, gclip[:1500], ginten[:1500], gcol[:1500]), (PHONG, u, hd["clip"], hd["varyings"], None),
-                                  (GOURAUD, None, gclip[1500:], ginten[1500:], gcol[1500:]), (FLAT, None, fclip, None, fcol),
-                                  (EYE, u, small["clip"], small["varyings"], None)],
-                           bpp=bpp, textures={0: d, 1: n, 2: sp}, clear=(3, 2, 1, 255))
-        ofb, oz, ost = cases.run_oracle(case)
-        fb, z, st, _ = cases.run_gpu(case)
-        assert fb.shape[-1] == bpp
-        assert np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and st == ost
-        diff = np.abs(fb.astype(np.int16) - ofb.astype(np.int16))           # EYE: pow(x, 8), at most 1 LSB on at most 0.1 % of the bytes
-        assert diff.max() <= 1 and (diff != 0).mean() <= 1e-3
+        case = cases.make_case(w, h, [(GOURAUD, None, gclip[:1500], ginten[:1500], gcol[:1500]), (PHONG, u, hd["clip"], hd["varyings"], None),
+                                      (GOURAUD, None, gclip[1500:], ginten[1500:], gcol[1500:]), (FLAT, None, fclip, None, fcol),
+                                      (EYE, u, small["clip"], small["varyings"], None)],
+                               bpp=bpp, textures={0: d, 1: n, 2: sp}, clear=(3, 2, 1, 255))
+        assert check(case)[0].shape[-1] == bpp
         # the same frame without the EYE draw is byte-exact
         case["draws"] = case["draws"][:4]
-        ofb, oz, ost = cases.run_oracle(case)
-        fb, z, st, _ = cases.run_gpu(case)
-        assert np.array_equal(fb, ofb) and np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and st == ost
+        check(case)
 
 
 def test_more_draws_than_descriptors_between_flushes():
@@ -600,13 +452,8 @@ def test_more_draws_than_descriptors_between_flushes():
     alive.  The frame equals the oracle's, which sees one rasterize() loop."""
     W, H = 200, 120
     clip, col = scenes.random_triangles(70 * 37, W, H, seed=81, rmin=2, rmax=30, perspective_w=True)
-    with Context(W, H, 3) as ctx:
-        for i in range(70):
-            ctx.draw(FLAT, clip[37 * i: 37 * (i + 1)], colors=col[37 * i: 37 * (i + 1)])
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    assert np.array_equal(fb, o.fb) and np.array_equal(z.view(np.uint64), o.z.view(np.uint64)) and st == o.stats
+    many = cases.make_case(W, H, [(FLAT, None, clip[37 * i: 37 * (i + 1)], None, col[37 * i: 37 * (i + 1)]) for i in range(70)])
+    same(cases.run_gpu(many), cases.run_oracle(_flat(W, H, clip, col)))
 
 
 @pytest.mark.parametrize("log2n", [24, 25])
@@ -629,13 +476,7 @@ def test_one_draw_of_more_than_2_to_24_triangles(log2n):
     reps = -(-n_small // 3000)
     clip[:n_small] = np.tile(base, (reps, 1))[:n_small]
     clip[n_small:] = vis[3000:]
-    with Context(W, H, 3) as ctx:
-        ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    assert st == o.stats and st[0] == n_small + n_vis
-    assert np.array_equal(fb, o.fb) and np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
+    assert check(_flat(W, H, clip, col))[2][0] == n_small + n_vis
 
 
 def test_pair_buffers_grow_behind_an_optimistic_launch():
@@ -647,15 +488,14 @@ def test_pair_buffers_grow_behind_an_optimistic_launch():
     big, bcol = scenes.random_triangles(300, W, H, seed=96, rmin=600, rmax=1200)
     with Context(W, H, 3) as ctx:
         ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
+        got = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats())
         assert ctx.last_flush_info()["pairs"] > 2 * 100 + 4096
         o = orc.Oracle(W, H, 3)
         o.draw(orc.FLAT, clip, colors=col)
-        assert np.array_equal(fb, o.fb) and np.array_equal(z.view(np.uint64), o.z.view(np.uint64)) and st == o.stats
+        same(got, (o.fb, o.z, o.stats), what="first frame")
         ctx.draw(FLAT, big, colors=bcol)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
         o.draw(orc.FLAT, big, colors=bcol)
-        assert np.array_equal(fb, o.fb) and np.array_equal(z.view(np.uint64), o.z.view(np.uint64)) and st == o.stats
+        same((ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()), (o.fb, o.z, o.stats), what="second frame")
 
 
 def test_frames_beyond_65536_tiles_use_wide_keys():
@@ -666,14 +506,7 @@ def test_frames_beyond_65536_tiles_use_wide_keys():
     clip, col = scenes.random_triangles(n, W, H, seed=4242, rmin=4, rmax=60)
     clip = clip.copy()
     clip[: n // 2, [1, 5, 9]] = clip[: n // 2, [1, 5, 9]] * 0.02 + 0.975 * clip[: n // 2, [3, 7, 11]]     # half of them into the top rows (NDC y near +1)
-    with Context(W, H, 3) as ctx:
-        ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    assert st == o.stats
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
+    z = check(_flat(W, H, clip, col))[1]
     ys = np.nonzero(np.isfinite(z).any(axis=1))[0]
     assert ys.max() >= 8192 or ys.min() < 32          # the frame's extreme tile rows were hit (whichever way y is flipped)
 
@@ -695,10 +528,8 @@ def test_more_than_2_to_32_pairs_is_refused_not_wrapped():
         small, scol = scenes.random_triangles(2000, W, H, seed=97, rmin=4, rmax=40)
         ctx.clear()
         ctx.draw(FLAT, small, colors=scol)
-        fb = ctx.read_framebuffer()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, small, colors=scol)
-    assert np.array_equal(fb, o.fb)
+        got = (ctx.read_framebuffer(), ctx.read_zbuffer())
+    same(got, cases.run_oracle(_flat(W, H, small, scol)), stats=False)
 
 
 def test_strip_loop_two_contexts_interleaved_frames():
@@ -784,27 +615,15 @@ def test_interleaved_bands_compose(name, world, band):
     """trgl_set_interleave: bands of `band` rows dealt round-robin to `world` contexts (the load-balanced alternative to one
     strip per rank).  Every context's own bands equal the rows of the unsharded frame (colours and depths; PHONG goes through
     the visibility buffer + k_shade), the fragment counts add up and the z range is the min / max over ranks."""
-    from tinyrenderder_amd import shard
     case = cases.CASES[name]()
-    W, H = case["width"], case["height"]
-    fb, z, st, _ = cases.run_gpu(case)
+    whole = cases.run_gpu(case)
+    st = whole[2]
     frags, zmin, zmax = 0, np.inf, -np.inf
     for rank in range(world):
-        with Context(W, H, case["bpp"]) as ctx:
-            ctx.set_viewport(case["viewport"]); ctx.clear(case["clear"], case["zclear"])
-            ctx.set_interleave(band, rank, world)
-            for slot, t in case["textures"].items():
-                ctx.upload_texture(slot, t)
-            for kind, u, clip, vary, col in case["draws"]:
-                ctx.draw(kind, clip, vary, col, u)
-            rfb, rz, rst = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-        rows = shard.band_rows_of(H, world, rank, band) if world > 1 else [(0, H)]
-        for y0, y1 in rows:
-            if name in POW_CASES:
-                _assert_fb(rfb[y0:y1], fb[y0:y1], name)
-            else:
-                assert np.array_equal(rfb[y0:y1], fb[y0:y1]), f"rank {rank}: colours of rows {y0}..{y1}"
-            assert np.array_equal(rz[y0:y1].view(np.uint64), z[y0:y1].view(np.uint64)), f"rank {rank}: depths of rows {y0}..{y1}"
+        il = (band, rank, world)
+        got = cases.run_gpu(case, interleave=il)
+        same(got, whole, rows=cases.band_rows(case["height"], il), eye=cases.has_eye(case), stats=False, what=f"rank {rank}")
+        rst = got[2]
         assert rst[0] == st[0] and rst[2:6] == st[2:6]
         frags += rst[1]; zmin = min(zmin, rst[6]); zmax = max(zmax, rst[7])
     assert (frags, zmin, zmax) == (st[1], st[6], st[7])
@@ -839,7 +658,6 @@ def test_c_abi_gather_single_rank_communicator(partition):
     covers the composition over gloo, examples/demo_multi.cpp is the C++ caller.)"""
     from tinyrenderder_amd import api
     case = cases.CASES["flat_persp_512"]()
-    ofb, oz, ost = cases.run_oracle(case)
     comm = api.rccl_comm_create(api.rccl_unique_id(), 0, 1, 0)
     try:
         with api.Context(case["width"], case["height"], case["bpp"]) as ctx:
@@ -849,10 +667,10 @@ def test_c_abi_gather_single_rank_communicator(partition):
             for kind, u, clip, vary, col in case["draws"]:
                 ctx.draw(kind, clip, vary, col, u)
             ctx.gather(comm, 0, 1, with_z=True)
-            fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
+            got = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats())
     finally:
         api.rccl_comm_destroy(comm)
-    assert np.array_equal(z.view(np.uint64), oz.view(np.uint64)) and np.array_equal(fb, ofb) and st == ost
+    same(got, cases.run_oracle(case))
 
 
 def test_interleaved_rank_without_rows_draws_nothing_and_stays_usable():
@@ -871,10 +689,8 @@ def test_interleaved_rank_without_rows_draws_nothing_and_stays_usable():
         ctx.set_strip(0, H)
         ctx.reset_stats(); ctx.clear()
         ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    assert np.array_equal(fb, o.fb) and np.array_equal(z.view(np.uint64), o.z.view(np.uint64)) and st == o.stats
+        got = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats())
+    same(got, cases.run_oracle(_flat(W, H, clip, col)))
 
 
 @pytest.mark.gpu
@@ -902,18 +718,15 @@ def test_depth_bound_in_the_pair_on_large_triangles(seed):
     col = np.concatenate([scol[:3000], bcol[:2000], scol[3000:], bcol[2000:]])
     with Context(W, H, 3) as ctx:
         ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
+        got = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats())
         # the same scene in two flushes, the second starting from the depths of the first
         ctx.clear()
         ctx.draw(FLAT, clip[:5000], colors=col[:5000]); ctx.flush()
         ctx.draw(FLAT, clip[5000:], colors=col[5000:])
-        fb2, z2 = ctx.read_framebuffer(), ctx.read_zbuffer()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
-    assert np.array_equal(z2.view(np.uint64), o.z.view(np.uint64)) and np.array_equal(fb2, o.fb)
+        got2 = (ctx.read_framebuffer(), ctx.read_zbuffer())
+    want = cases.run_oracle(_flat(W, H, clip, col))
+    same(got, want, what="one flush")
+    same(got2, want, stats=False, what="two flushes")
 
 
 @pytest.mark.gpu
@@ -931,19 +744,8 @@ def test_fuzz_discarding_scenes_against_oracle(seed):
     cells = int(1 + u[3] * 40)
     clip, col = scenes.random_triangles(n, W, H, seed=9100 + seed, rmin=1 + 4 * u[4], rmax=10 + 150 * u[5], perspective_w=True)
     base, bcol = scenes.random_triangles(n // 3, W, H, seed=9200 + seed, rmin=3, rmax=60)
-    uni = make_uniforms(cells=cells)
-    with Context(W, H, 3) as ctx:
-        if seed & 1:
-            ctx.draw(FLAT, base, colors=bcol)
-            ctx.draw(CHECKER, clip, colors=col, uniforms=uni)
-        else:
-            ctx.draw(CHECKER, clip[: n // 2], colors=col[: n // 2], uniforms=uni); ctx.flush()
-            ctx.draw(CHECKER, clip[n // 2:], colors=col[n // 2:], uniforms=uni)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    if seed & 1:
-        o.draw(orc.FLAT, base, colors=bcol)
-    o.draw(orc.CHECKER, clip, colors=col, uniforms=orc.make_uniforms(cells=cells))
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64))
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
+    checker = (CHECKER, make_uniforms(cells=cells), clip, None, col)
+    if seed & 1:                                    # a flat draw underneath, in the same flush
+        check(cases.make_case(W, H, [(FLAT, None, base, None, bcol), checker]))
+    else:                                           # two flushes
+        check(cases.make_case(W, H, [checker]), split=2)

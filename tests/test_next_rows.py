@@ -50,28 +50,16 @@ def test_gpu_draw_indexed_equals_host_vertex_stage():
     hd, verts, idx = _indexed_head(5, W, H)
     d, n, s = scenes.procedural_textures(256)
     u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 0.8, 0, 1, 2)
-    res = []
-    for indexed in (False, True):
-        with Context(W, H, 3) as ctx:
-            for k, t in enumerate((d, n, s)):
-                ctx.upload_texture(k, t)
-            if indexed:
-                ctx.draw_indexed(PHONG, u, hd["projection"], verts, idx)
-                ctx.draw_indexed(EYE, u, hd["projection"], verts, idx[::4])
-            else:
-                ctx.draw(PHONG, hd["clip"], hd["varyings"], uniforms=u)
-                ctx.draw(EYE, hd["clip"][::4], hd["varyings"][::4], uniforms=u)
-            res.append((ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()))
-    assert np.array_equal(res[0][1].view(np.uint64), res[1][1].view(np.uint64))
-    assert np.array_equal(res[0][0], res[1][0])
-    assert res[0][2] == res[1][2]
-    o = orc.Oracle(W, H, 3)
-    for k, t in enumerate((d, n, s)):
-        o.upload_texture(k, t)
-    ou = orc.make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 0.8, 0, 1, 2)
-    o.draw(orc.PHONG, hd["clip"], hd["varyings"], uniforms=ou)
-    o.draw(orc.EYE, hd["clip"][::4], hd["varyings"][::4], uniforms=ou)
-    assert np.array_equal(res[1][1].view(np.uint64), o.z.view(np.uint64)) and res[1][2] == o.stats
+    case = cases.make_case(W, H, [(PHONG, u, hd["clip"], hd["varyings"], None), (EYE, u, hd["clip"][::4], hd["varyings"][::4], None)],
+                           textures={0: d, 1: n, 2: s})
+    with Context(W, H, 3) as ctx:
+        for k, t in enumerate((d, n, s)):
+            ctx.upload_texture(k, t)
+        ctx.draw_indexed(PHONG, u, hd["projection"], verts, idx)
+        ctx.draw_indexed(EYE, u, hd["projection"], verts, idx[::4])
+        indexed = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats(), ctx.stats_line())
+    cases.assert_same_frame(indexed, cases.run_gpu(case), what="draw_indexed against draw")
+    cases.assert_same_frame(indexed, cases.run_oracle(case), eye=True, what="draw_indexed against the oracle")
 
 
 @pytest.mark.gpu
@@ -204,14 +192,10 @@ def test_obj_to_screen_through_device_vertex_stage(tmp_path):
         for k, t in enumerate((d, n, s)):
             ctx.upload_texture(k, t)
         ctx.draw_indexed(PHONG, u, hd["projection"], verts, idx)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
+        got = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats())
     clip, vary = orc.vertex_stage(hd["model_view"], hd["projection"], verts, idx)
-    o = orc.Oracle(W, H, 3)
-    for k, t in enumerate((d, n, s)):
-        o.upload_texture(k, t)
-    o.draw(orc.PHONG, clip, vary, uniforms=orc.make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0, 0, 1, 2))
-    assert np.array_equal(z.view(np.uint64), o.z.view(np.uint64)) and np.array_equal(fb, o.fb) and st == o.stats
-    assert st[1] > 10_000
+    cases.assert_same_frame(got, cases.run_oracle(cases.make_case(W, H, [(PHONG, u, clip, vary, None)], textures={0: d, 1: n, 2: s})))
+    assert got[2][1] > 10_000
 
 
 def _c_round(v):

@@ -8,8 +8,8 @@ z ranges, the reference's own goldens through cases.CASES):
   D. frames that start from caller-written buffers (no init_from_clear: the block-out stores only pixels with fragments);
   E. the mixed flush at every pixel size, and short tile lists after a large frame on one context.
 
-Bar: z bits, framebuffer bytes and the stats tuple equal the oracle's; EYE colours within 1 LSB on at most 0.1 % of the bytes.
-The tests without the gpu mark check that the scenes really reach the paths they are meant for.
+Bar (cases.assert_same_frame): z bits, framebuffer bytes and the stats tuple equal the oracle's; EYE colours within 1 LSB on at
+most 0.1 % of the pixels.  The tests without the gpu mark check that the scenes really reach the paths they are meant for.
 """
 import numpy as np
 import pytest
@@ -23,59 +23,7 @@ MIXED = "mixed"                       # FLAT + GOURAUD + PHONG + CHECKER draws i
 KINDS = [FLAT, GOURAUD, PHONG, EYE, CHECKER, MIXED]
 KIND_NAMES = {FLAT: "flat", GOURAUD: "gouraud", PHONG: "phong", EYE: "eye", CHECKER: "checker", MIXED: "mixed"}
 
-
-# ---- shared checks -------------------------------------------------------------------------------------------------
-def _same_z(z, oz, rows=slice(None)):
-    bad = np.argwhere(z[rows].view(np.uint64) != oz[rows].view(np.uint64))
-    assert bad.size == 0, f"{len(bad)} z values differ, first at {bad[:5].tolist()}"
-
-
-def _same_fb(fb, ofb, eye, rows=slice(None)):
-    a, b = fb[rows], ofb[rows]
-    if eye:                                   # EYE: pow(x, 8) may differ in the last ulp
-        d = np.abs(a.astype(np.int16) - b.astype(np.int16))
-        assert d.max() <= 1 and (d != 0).mean() <= 1e-3, f"EYE colours: max diff {d.max()}, {(d != 0).mean():.2e} of the bytes"
-    else:
-        bad = np.argwhere(a != b)
-        assert bad.size == 0, f"{len(bad)} framebuffer bytes differ, first at {bad[:5].tolist()}"
-
-
-def _has_eye(case):
-    return any(d[0] == EYE for d in case["draws"])
-
-
-def _check_case(case, strip=None, split=None):
-    """GPU (whole, or one strip context, or split into flushes) against the oracle restricted to the same rows."""
-    ofb, oz, ost = cases.run_oracle(case, strip=strip)
-    fb, z, st, _ = cases.run_gpu(case, strip=strip, split=split)
-    rows = slice(None) if strip is None else slice(*strip)
-    _same_z(z, oz, rows)
-    _same_fb(fb, ofb, _has_eye(case), rows)
-    assert st == ost
-    return st
-
-
-def _check_bands(case, band, world):
-    """trgl_set_interleave over `world` contexts: every rank's rows equal the oracle's and the fragment counts add up."""
-    from tinyrenderder_amd import shard
-    W, H = case["width"], case["height"]
-    ofb, oz, ost = cases.run_oracle(case)
-    frags = 0
-    for rank in range(world):
-        with Context(W, H, case["bpp"]) as ctx:
-            ctx.set_viewport(case["viewport"]); ctx.clear(case["clear"], case["zclear"])
-            ctx.set_interleave(band, rank, world)
-            for slot, t in case["textures"].items():
-                ctx.upload_texture(slot, t)
-            for kind, u, clip, vary, col in case["draws"]:
-                ctx.draw(kind, clip, vary, col, u)
-            fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-        for y0, y1 in shard.band_rows_of(H, world, rank, band):
-            _same_z(z, oz, slice(y0, y1))
-            _same_fb(fb, ofb, _has_eye(case), slice(y0, y1))
-        assert st[0] == ost[0] and st[2:6] == ost[2:6]
-        frags += st[1]
-    assert frags == ost[1]
+check, same = cases.check_gpu, cases.assert_same_frame
 
 
 # ---- scene inputs per kind -----------------------------------------------------------------------------------------
@@ -98,7 +46,7 @@ def _kind_case(kind, clip, col, w, h, bpp, seed, viewport=None, clear=(30, 20, 1
     else:
         draws = [(kind, {PHONG: u_ph, EYE: u_ph, CHECKER: u_ck}.get(kind), clip,
                   {GOURAUD: inten, PHONG: vary, EYE: vary}.get(kind), None if kind in (PHONG, EYE) else col)]
-    return cases._case(w, h, draws, bpp=bpp, viewport=viewport, textures=tx if kind in (PHONG, EYE, MIXED) else {}, clear=clear)
+    return cases.make_case(w, h, draws, bpp=bpp, viewport=viewport, textures=tx if kind in (PHONG, EYE, MIXED) else {}, clear=clear)
 
 
 # =====================================================================================================================
@@ -216,18 +164,28 @@ def test_literal_triangles_in_every_kernel_variant(kind, bpp):
     """Literal triangles mixed into a dense scene: one flush, two flushes, two strip contexts cut at an odd row."""
     clip, col, _, _ = literal_scene(3100 + bpp)
     case = _kind_case(kind, clip, col, LW, LH, bpp, seed=3200 + bpp, viewport=cases.UNIT_VIEWPORT)
-    st = _check_case(case)
-    assert st[1] > 5000
-    _check_case(case, split=2)
+    assert check(case)[2][1] > 5000
+    check(case, split=2)
     for strip in ((0, 45), (45, LH)):
-        _check_case(case, strip=strip)
+        check(case, strip=strip)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", [FLAT, PHONG], ids=KIND_NAMES.get)
 def test_literal_triangles_in_interleaved_bands(kind):
+    """trgl_set_interleave over two contexts: every rank's rows equal the oracle's and the fragment counts add up."""
     clip, col, _, _ = literal_scene(3103)
-    _check_bands(_kind_case(kind, clip, col, LW, LH, 3, seed=3203, viewport=cases.UNIT_VIEWPORT), band=32, world=2)
+    case = _kind_case(kind, clip, col, LW, LH, 3, seed=3203, viewport=cases.UNIT_VIEWPORT)
+    want = cases.run_oracle(case)
+    frags = 0
+    for rank in range(2):
+        il = (32, rank, 2)
+        got = cases.run_gpu(case, interleave=il)
+        same(got, want, rows=cases.band_rows(LH, il), eye=cases.has_eye(case), stats=False, what=f"rank {rank}")
+        st = got[2]
+        assert st[0] == want[2][0] and st[2:6] == want[2][2:6]
+        frags += st[1]
+    assert frags == want[2][1]
 
 
 # =====================================================================================================================
@@ -269,9 +227,9 @@ def test_zero_cases_in_strips_and_two_flushes(name):
     """Each strip counts its own first zero; two flushes lock the sign of the first one."""
     case = cases.CASES[name]()
     H = case["height"]
-    _check_case(case, split=2)
+    check(case, split=2)
     for strip in ((0, 19), (19, H)):
-        _check_case(case, strip=strip)
+        check(case, strip=strip)
 
 
 def _zero_background(n, W, H, seed, sign=1.0):
@@ -299,8 +257,7 @@ def test_zero_sign_lock_over_draws_and_flushes():
             ctx.flush()
             assert ctx.stats() == o.stats
             assert ctx.stats_line() == orc.format_stats_line(o.stats)
-        _same_z(ctx.read_zbuffer(), o.z)
-        assert np.array_equal(ctx.read_framebuffer(), o.fb)
+        same((ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()), (o.fb, o.z, o.stats))
     assert o.stats[8] == -1.0 and o.stats[6] == 0.0
     # the first zero comes in a later flush than the first fragments
     clip2, col2 = _zero_background(800, W, H, seed=52)
@@ -332,8 +289,8 @@ def test_reset_stats_clears_the_zero_lock():
         o.L.orc_stats_init(orc.C.byref(o.t.stats))
         ctx.draw(FLAT, clip[300:], colors=col[300:])
         o.draw(orc.FLAT, clip[300:], colors=col[300:])
-        assert ctx.stats() == o.stats and o.stats[8] == 1.0
-        _same_z(ctx.read_zbuffer(), o.z)
+        assert o.stats[8] == 1.0
+        same((ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()), (o.fb, o.z, o.stats))
 
 
 @pytest.mark.gpu
@@ -351,8 +308,8 @@ def test_literal_triangles_write_zeros():
         case = _kind_case(kind, clip, col, W, H, 3, seed=3204, viewport=cases.UNIT_VIEWPORT)
         ofb, oz, ost = cases.run_oracle(case)
         assert ost[6] == 0.0 and min(_zero_bits(oz)) > 0
-        _check_case(case)
-        _check_case(case, split=3)
+        check(case)
+        check(case, split=3)
 
 
 @pytest.mark.gpu
@@ -372,16 +329,11 @@ def test_zero_race_on_a_2048_frame():
     for i in (1,):
         for v in (1, 2):
             clip[i, 4 * v: 4 * v + 2] = clip[i, 0:2] + (clip[i, 4 * v: 4 * v + 2] - clip[i, 0:2]) * 0.1
-    with Context(W, H, 3) as ctx:
-        ctx.draw(FLAT, clip, colors=col)
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-    o = orc.Oracle(W, H, 3)
-    o.draw(orc.FLAT, clip, colors=col)
-    pos, neg = _zero_bits(o.z)
-    assert pos > 0 and neg > 0 and o.stats[6] == 0.0
-    _same_z(z, o.z)
-    assert np.array_equal(fb, o.fb)
-    assert st == o.stats
+    case = cases.make_case(W, H, [(FLAT, None, clip, None, col)])
+    want = cases.run_oracle(case)
+    pos, neg = _zero_bits(want[1])
+    assert pos > 0 and neg > 0 and want[2][6] == 0.0
+    same(cases.run_gpu(case), want)
 
 
 # =====================================================================================================================
@@ -435,9 +387,8 @@ def test_perspective_fallback_against_oracle(kind):
     clip, col, _, _ = fallback_scene(3300)
     for bpp in (3, 4):
         case = _kind_case(kind, clip, col, FW, FH, bpp, seed=3400)
-        st = _check_case(case)
-        assert st[1] > 5000
-    _check_case(case, split=2)
+        assert check(case)[2][1] > 5000
+    check(case, split=2)
 
 
 # =====================================================================================================================
@@ -454,30 +405,6 @@ def _loaded_buffers(W, H, bpp):
     return fb, z
 
 
-def _run_loaded(case, fb0, z0, strip=None):
-    W, H, bpp = case["width"], case["height"], case["bpp"]
-    with Context(W, H, bpp) as ctx:
-        ctx.set_viewport(case["viewport"])
-        ctx.write_framebuffer(fb0); ctx.write_zbuffer(z0)
-        if strip:
-            ctx.set_strip(*strip)
-        for slot, t in case["textures"].items():
-            ctx.upload_texture(slot, t)
-        for kind, u, clip, vary, col in case["draws"]:
-            ctx.draw(kind, clip, vary, col, u)
-        return ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-
-
-def _oracle_loaded(case, fb0, z0, strip=None):
-    o = orc.Oracle(case["width"], case["height"], case["bpp"], viewport=case["viewport"], strip=strip)
-    o.fb[:] = fb0; o.z[:] = z0
-    for slot, t in case["textures"].items():
-        o.upload_texture(slot, t)
-    for kind, u, clip, vary, col in case["draws"]:
-        o.draw(kind, clip, vary, col, None if u is None else orc.Uniforms.from_buffer_copy(bytes(u)))
-    return o
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("W", [97, 98, 99])
 @pytest.mark.parametrize("bpp", [1, 3, 4])
@@ -490,12 +417,9 @@ def test_draws_on_caller_written_buffers(bpp, W):
     for kind in KINDS:
         case = _kind_case(kind, clip, col, W, H, bpp, seed=3600 + W)
         for strip in (None, (13, 51)):
-            o = _oracle_loaded(case, fb0, z0, strip)
-            fb, z, st = _run_loaded(case, fb0, z0, strip)
-            _same_z(z, o.z)
-            _same_fb(fb, o.fb, kind == EYE)
-            assert st == o.stats
-            kept = (o.fb == fb0).all(-1)
+            want = cases.run_oracle(case, strip=strip, start=(fb0, z0))
+            same(cases.run_gpu(case, strip=strip, start=(fb0, z0)), want, eye=kind == EYE)     # every row: outside the strip too
+            kept = (want[0] == fb0).all(-1)
             assert 0.05 < kept.mean() < 0.95, kept.mean()          # both written and untouched pixels in the frame
 
 
@@ -510,25 +434,17 @@ def test_clear_and_write_order():
         ctx.clear((9, 8, 7, 6), 0.5)
         ctx.write_framebuffer(fb0)                                # z stays the pending clear's 0.5
         ctx.draw(FLAT, clip[100:], colors=col[100:])
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-        o = orc.Oracle(W, H, bpp, z_clear=0.5)
-        o.fb[:] = fb0
-        o.draw(orc.FLAT, clip[100:], colors=col[100:])
-        _same_z(z, o.z); assert np.array_equal(fb, o.fb)
+        want = cases.run_oracle(cases.make_case(W, H, [(FLAT, None, clip[100:], None, col[100:])], zclear=0.5), start=(fb0, None))
+        same((ctx.read_framebuffer(), ctx.read_zbuffer()), want, stats=False, what="write after clear")
+        flat = cases.make_case(W, H, [(FLAT, None, clip, None, col)], clear=(1, 2, 3, 4), zclear=0.25)
         ctx.clear((1, 2, 3, 4), 0.25)
         ctx.write_zbuffer(z0); ctx.write_framebuffer(fb0)         # both written after the clear: they win
         ctx.draw(FLAT, clip, colors=col)
-        fb, z = ctx.read_framebuffer(), ctx.read_zbuffer()
-        o = orc.Oracle(W, H, bpp); o.fb[:] = fb0; o.z[:] = z0
-        o.draw(orc.FLAT, clip, colors=col)
-        _same_z(z, o.z); assert np.array_equal(fb, o.fb)
+        same((ctx.read_framebuffer(), ctx.read_zbuffer()), cases.run_oracle(flat, start=(fb0, z0)), stats=False, what="writes after clear")
         ctx.write_zbuffer(z0); ctx.write_framebuffer(fb0)
         ctx.clear((1, 2, 3, 4), 0.25)                             # the clear after the writes wins
         ctx.draw(FLAT, clip, colors=col)
-        fb, z = ctx.read_framebuffer(), ctx.read_zbuffer()
-        o = orc.Oracle(W, H, bpp, clear_bgra=(1, 2, 3, 4), z_clear=0.25)
-        o.draw(orc.FLAT, clip, colors=col)
-        _same_z(z, o.z); assert np.array_equal(fb, o.fb)
+        same((ctx.read_framebuffer(), ctx.read_zbuffer()), cases.run_oracle(flat), stats=False, what="clear after writes")
 
 
 # =====================================================================================================================
@@ -573,7 +489,5 @@ def test_short_tile_lists_after_a_large_frame():
             ctx.clear()
             ctx.reset_stats()
             ctx.draw(FLAT, clip, colors=col)
-            fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-            o = orc.Oracle(W, H, 3)
-            o.draw(orc.FLAT, clip, colors=col)
-            _same_z(z, o.z); assert np.array_equal(fb, o.fb); assert st == o.stats
+            got = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats())
+            same(got, cases.run_oracle(cases.make_case(W, H, [(FLAT, None, clip, None, col)])), what=f"seed {seed}")

@@ -21,14 +21,7 @@ GOLDEN = json.load(open(os.path.join(HERE, "golden", "golden.json")))
 # name -> (source, K)
 SOURCES = {"flat": (S.FLAT, 0), "gouraud": (S.GOURAUD, 3), "gouraud5": (S.GOURAUD_PADDED, 5), "phong": (S.PHONG, 24),
            "eye": (S.EYE, 24)}
-# the built-in kind each source restates, and how its varyings map onto the user kind's
-BUILTIN = {"flat": FLAT, "gouraud": GOURAUD, "gouraud5": GOURAUD, "phong": PHONG, "eye": EYE}
-
-
-def _vary(name, vary, n):
-    if name == "gouraud5":
-        return np.concatenate([np.full((n, 2), 7.5), vary], 1)
-    return vary
+same = cases.assert_same_frame
 
 
 @pytest.fixture(scope="module")
@@ -40,44 +33,16 @@ def compiled():
     return SOURCES
 
 
-def _render(case, plan, compiled, strip=None, interleave=None, mode="one"):
-    """plan: per draw of the case, None (the built-in kind) or the name of the source to draw it with.
-    mode: "one" (one flush), "halves" (trgl_flush_begin / trgl_flush_end), "two" (a flush after the first half of the draws)."""
-    with Context(case["width"], case["height"], case["bpp"]) as ctx:
-        kinds = {}
-        for name in sorted({p for p in plan if p}):
-            kinds[name] = ctx.register_shader(*compiled[name])
-        ctx.set_viewport(case["viewport"])
-        ctx.clear(case["clear"], case["zclear"])
-        if strip is not None:
-            ctx.set_strip(*strip)
-        if interleave is not None:
-            ctx.set_interleave(*interleave)
-        for slot, t in case["textures"].items():
-            ctx.upload_texture(slot, t)
-        draws = case["draws"]
-        for i, ((kind, u, clip, vary, col), p) in enumerate(zip(draws, plan)):
-            if p:
-                ctx.draw(kinds[p], clip, _vary(p, vary, clip.shape[0]) if compiled[p][1] else None, col, u)
-            else:
-                ctx.draw(kind, clip, vary, col, u)
-            if mode == "two" and i == len(draws) // 2 - 1:
-                ctx.flush()
-        if mode == "halves":
-            ctx.flush_begin()
-            ctx.flush_end()
-        fb, z, st = ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats()
-        line = ctx.stats_line()
-    return fb, z, st, line
+def _user(case, plan, **kw):
+    """run_gpu with draw i of the case drawn by the source plan[i] (None: its built-in kind); gouraud5 reads two leading varyings
+    of its own."""
+    draws = [(kind, u, clip, np.concatenate([np.full((clip.shape[0], 2), 7.5), vary], 1) if p == "gouraud5" else vary, col)
+             for (kind, u, clip, vary, col), p in zip(case["draws"], plan)]
+    return cases.run_gpu(dict(case, draws=draws), shaders=[SOURCES[p] if p else None for p in plan], **kw)
 
 
-def _same(a, b, what):
-    fa, za, sa, la = a
-    fb, zb, sb, lb = b
-    assert np.array_equal(za.view(np.uint64), zb.view(np.uint64)), f"{what}: z differs"
-    bad = np.argwhere(fa != fb)
-    assert bad.size == 0, f"{what}: {len(bad)} framebuffer bytes differ, first at {bad[:5].tolist()}"
-    assert sa == sb and la == lb, (what, la, lb)
+# one flush; trgl_flush_begin / trgl_flush_end; a flush after the first half of the six draws of _mixed_case
+MODES = {"one": {}, "halves": dict(halves=True), "two": dict(flush_after=2)}
 
 
 FLAT_ONLY = sorted(n for n, f in cases.CASES.items() if f()["draws"] and all(d[0] == FLAT for d in f()["draws"]))
@@ -87,21 +52,18 @@ FLAT_ONLY = sorted(n for n, f in cases.CASES.items() if f()["draws"] and all(d[0
 @pytest.mark.parametrize("name", FLAT_ONLY)
 def test_flat_source_equals_flat_and_golden(compiled, name):
     case = cases.CASES[name]()
-    plan = ["flat"] * len(case["draws"])
-    got = _render(case, plan, compiled)
-    _same(got, _render(case, [None] * len(plan), compiled), name)
-    g = GOLDEN[name]
-    assert got[3] == g["stats"] and scenes.digest(got[1]) == g["z"] and scenes.digest(got[0]) == g["fb"]
+    got = _user(case, ["flat"] * len(case["draws"]))
+    same(got, cases.run_gpu(case), what=name)
+    cases.assert_golden(got, GOLDEN[name])
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("src", ["gouraud", "gouraud5"])
 def test_gouraud_source_equals_gouraud_and_golden(compiled, src):
     case = cases.gouraud_256_rgba()
-    got = _render(case, [src], compiled)
-    _same(got, _render(case, [None], compiled), src)
-    g = GOLDEN["gouraud_256_rgba"]
-    assert got[3] == g["stats"] and scenes.digest(got[1]) == g["z"] and scenes.digest(got[0]) == g["fb"]
+    got = _user(case, [src])
+    same(got, cases.run_gpu(case), what=src)
+    cases.assert_golden(got, GOLDEN["gouraud_256_rgba"])
 
 
 def _head_4096():
@@ -109,7 +71,7 @@ def _head_4096():
     hd = scenes.head_standin(7, W, H)
     d, n, s = scenes.procedural_textures(1024)
     u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0, 0, 1, 2)
-    return cases._case(W, H, [(PHONG, u, hd["clip"], hd["varyings"], None)], textures={0: d, 1: n, 2: s})
+    return cases.make_case(W, H, [(PHONG, u, hd["clip"], hd["varyings"], None)], textures={0: d, 1: n, 2: s})
 
 
 @pytest.mark.gpu
@@ -117,7 +79,7 @@ def _head_4096():
                                       ("head_4096", "phong")])
 def test_phong_and_eye_sources_equal_builtin(compiled, name, src):
     case = _head_4096() if name == "head_4096" else cases.CASES[name]()
-    _same(_render(case, [src], compiled), _render(case, [None], compiled), name)
+    same(_user(case, [src]), cases.run_gpu(case), what=name)
 
 
 def _mixed_case(w, h, bpp, seed=3):
@@ -135,7 +97,7 @@ def _mixed_case(w, h, bpp, seed=3):
     gi2 = scenes.SplitMix64(seed + 6).uniform(300 * 3, -0.2, 1.3).reshape(300, 3)
     draws = [(FLAT, None, fc, None, fcol), (PHONG, ub, big["clip"], big["varyings"], None), (EYE, u, hd["clip"], hd["varyings"], None),
              (CHECKER, make_uniforms(cells=6), cc, None, ccol), (GOURAUD, None, gc, gi, gcol), (GOURAUD, None, gc2, gi2, gcol2)]
-    return cases._case(w, h, draws, bpp=bpp, textures={0: d, 1: n, 2: s})
+    return cases.make_case(w, h, draws, bpp=bpp, textures={0: d, 1: n, 2: s})
 
 
 MIXED_PLAN = [None, None, "eye", None, "gouraud5", None]
@@ -145,7 +107,7 @@ MIXED_PLAN = [None, None, "eye", None, "gouraud5", None]
 @pytest.mark.parametrize("mode", ["one", "halves", "two"])
 def test_mixed_flush_equals_builtin(compiled, mode):
     case = _mixed_case(320, 200, 3)
-    _same(_render(case, MIXED_PLAN, compiled, mode=mode), _render(case, [None] * 6, compiled, mode=mode), mode)
+    same(_user(case, MIXED_PLAN, **MODES[mode]), cases.run_gpu(case, **MODES[mode]), what=mode)
 
 
 @pytest.mark.gpu
@@ -154,17 +116,16 @@ def test_strips_and_bands_equal_builtin(compiled, bpp):
     w, h = 200, 160
     case = _mixed_case(w, h, bpp, seed=11)
     for strip, il in [((37, 131), None), (None, (32, 0, 2)), (None, (32, 1, 2)), (None, (64, 2, 3))]:
-        _same(_render(case, MIXED_PLAN, compiled, strip=strip, interleave=il),
-              _render(case, [None] * 6, compiled, strip=strip, interleave=il), f"bpp {bpp} strip {strip} bands {il}")
+        same(_user(case, MIXED_PLAN, strip=strip, interleave=il), cases.run_gpu(case, strip=strip, interleave=il),
+             what=f"bpp {bpp} strip {strip} bands {il}")
 
 
 @pytest.mark.gpu
 def test_odd_dims_equal_builtin(compiled):
     case = cases.odd_dims_101x67()
-    plan = ["flat" if d[0] == FLAT else None for d in case["draws"]]
-    _same(_render(case, plan, compiled), _render(case, [None] * len(plan), compiled), "odd_dims_101x67 flat")
+    same(_user(case, ["flat" if d[0] == FLAT else None for d in case["draws"]]), cases.run_gpu(case), what="odd_dims_101x67 flat")
     mixed = _mixed_case(101, 67, 3, seed=21)
-    _same(_render(mixed, MIXED_PLAN, compiled), _render(mixed, [None] * 6, compiled), "odd dims mixed")
+    same(_user(mixed, MIXED_PLAN), cases.run_gpu(mixed), what="odd dims mixed")
 
 
 @pytest.mark.gpu
@@ -184,7 +145,7 @@ def test_draw_indexed_with_user_kind_equals_phong(compiled):
                 ctx.upload_texture(k, t)
             ctx.draw_indexed(kind, u, hd["projection"], verts, idx)
             res.append((ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats(), ctx.stats_line()))
-    _same(res[1], res[0], "draw_indexed")
+    same(res[1], res[0], what="draw_indexed")
 
 
 @pytest.mark.gpu
