@@ -92,17 +92,33 @@ extern "C" {
  *
  * trgl_sample2D has the clamp and nearest-texel rules of IShader::sample2D / Model::diffuse (model.cpp:415-459); an empty slot
  * samples as opaque white.  The contract that makes shading once per visible pixel exact: the shader cannot discard (the
- * signature has no flag) and has no side effects (writing memory from trgl_fragment is undefined behaviour).  Names starting
+ * signature has no flag; see TRGL_SHADER_MAY_DISCARD below for one that can) and has no side effects (writing memory from trgl_fragment is undefined behaviour).  Names starting
  * with trgl_ and those of the library's device headers are reserved.
  * The source is compiled with the library's own flags, -O3 -std=c++17 -ffp-contract=off -fno-fast-math
  * -fhip-fp32-correctly-rounded-divide-sqrt, for the architecture the library was built for: results are bit-identical to a
  * host build of the same body for + - * /, sqrt, conversions and comparisons.  Device libm calls (pow, sin, ...) are not glibc's.
  * TRGL_USER_VARY is defined to K ahead of the source.  Kinds TRGL_SHADER_USER_FIRST + i are handed out by trgl_register_shader
  * in registration order, per context.
+ *
+ * User shaders that can discard (registered with the flag TRGL_SHADER_MAY_DISCARD): the source defines instead
+ *
+ *     __device__ trgl_frag_out trgl_fragment(const trgl_frag_in& in);
+ *
+ * where the prelude declares struct trgl_frag_out { bool discard; uint32_t bgra; } - the std::pair<bool, TGAColor> that
+ * IShader::fragment returns (our_gl.h:51).  trgl_frag_in, trgl_sample2D, the compiler flags and the reserved names are those above,
+ * and side effects are still undefined behaviour.  What differs is where the function is called: for EVERY fragment that passes
+ * the z-test, in submission order per pixel, exactly where our_gl.cpp:187 calls it.  A discarded fragment writes no depth, no
+ * colour and no counter (our_gl.cpp:188), so the fragments behind it are tested against the depth it left alone.  Such a kind is
+ * rasterized by a kernel compiled behind its source, in flushes of its own: trgl_draw starts a new flush where draws of such a kind
+ * meet draws of any other kind (invisible in the frame and the counters, as every flush boundary).  TRGL_USER_MAY_DISCARD is
+ * defined to 1 ahead of such a source and to 0 ahead of any other, so one source can serve both contracts.  A source written for
+ * one contract and compiled under the other is a compile error that names trgl_fragment.
  */
 #define TRGL_SHADER_USER_FIRST 64
 #define TRGL_MAX_USER_SHADERS  32   /* per context */
 #define TRGL_MAX_USER_VARY     64   /* K */
+/* flags of trgl_shader_compile_ex / trgl_register_shader_ex */
+#define TRGL_SHADER_MAY_DISCARD 1u  /* trgl_fragment returns trgl_frag_out and is called for every z-pass, in order */
 
 /* doubles of varyings per triangle for each kind */
 #define TRGL_VARY_FLAT    0
@@ -238,6 +254,10 @@ int trgl_shader_compile(const char* source, int n_varyings, char* log, size_t lo
 /* Compile (or take from the cache) and load on the context's device; *kind = TRGL_SHADER_USER_FIRST + i for the i-th
  * registration on this context.  The module belongs to the context and is unloaded by trgl_destroy. */
 int trgl_register_shader(trgl_ctx* ctx, const char* source, int n_varyings, int* kind);
+/* The same with flags (TRGL_SHADER_MAY_DISCARD or 0; any other bit is TRGL_E_INVALID).  The two calls above are these with
+ * flags = 0.  Kinds with and without the flag share the numbering and the TRGL_MAX_USER_SHADERS limit. */
+int trgl_shader_compile_ex(const char* source, int n_varyings, uint32_t flags, char* log, size_t log_len);
+int trgl_register_shader_ex(trgl_ctx* ctx, const char* source, int n_varyings, uint32_t flags, int* kind);
 
 /* Execute everything submitted so far (asynchronously on the context's stream). */
 int trgl_flush(trgl_ctx* ctx);

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(HERE, "libtrgl.so")
 FLAT, GOURAUD, PHONG, EYE, CHECKER = 0, 1, 2, 3, 4
 VARY = {FLAT: 0, GOURAUD: 3, PHONG: 24, EYE: 24, CHECKER: 0}
 SHADER_USER_FIRST, MAX_USER_SHADERS, MAX_USER_VARY = 64, 32, 64      # user shaders: kinds handed out by Context.register_shader
+SHADER_MAY_DISCARD = 1        # TRGL_SHADER_MAY_DISCARD: the user shader's trgl_fragment returns trgl_frag_out (it can discard)
 MEM_HOST, MEM_DEVICE = 0, 1
 PHASE_SETUP, PHASE_BIN, PHASE_RASTER, PHASE_TOTAL, PHASE_RASTER_KERNEL = 0, 1, 2, 3, 4
 NUM_PHASES = 5        # TRGL_NUM_PHASES
@@ -32,7 +33,7 @@ SYMBOLS = [
     "trgl_selftest_division", "trgl_selftest_sampler", "trgl_tga_max_size", "trgl_tga_encode", "trgl_tga_info", "trgl_tga_decode", "trgl_draw_indexed", "trgl_ssao_defaults",
     "trgl_postprocess", "trgl_obj_load", "trgl_obj_free",
     "trgl_gather", "trgl_rccl_unique_id", "trgl_rccl_comm_create", "trgl_rccl_comm_destroy",
-    "trgl_shader_compile", "trgl_register_shader",
+    "trgl_shader_compile", "trgl_register_shader", "trgl_shader_compile_ex", "trgl_register_shader_ex",
 ]
 
 
@@ -151,6 +152,8 @@ def load_library(path: str = None):
     L.trgl_rccl_comm_destroy.argtypes = [C.c_void_p]
     L.trgl_shader_compile.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
     L.trgl_register_shader.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    L.trgl_shader_compile_ex.argtypes = [C.c_char_p, C.c_int, C.c_uint32, C.c_char_p, C.c_size_t]
+    L.trgl_register_shader_ex.argtypes = [vp, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_int)]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -184,12 +187,13 @@ def rccl_comm_destroy(comm):
     load_library().trgl_rccl_comm_destroy(comm)
 
 
-def shader_compile(source: str, n_varyings: int):
-    """trgl_shader_compile: compile a user shader (include/trgl.h, "User shaders") without a GPU or a context.
+def shader_compile(source: str, n_varyings: int, may_discard: bool = False):
+    """trgl_shader_compile_ex: compile a user shader (include/trgl.h, "User shaders") without a GPU or a context; may_discard: one
+    whose trgl_fragment returns trgl_frag_out (TRGL_SHADER_MAY_DISCARD).
     Returns (ok, compiler log); raises when user shaders are unavailable (no hiprtc)."""
     L = load_library()
     log = C.create_string_buffer(16384)
-    rc = L.trgl_shader_compile(source.encode(), int(n_varyings), log, len(log))
+    rc = L.trgl_shader_compile_ex(source.encode(), int(n_varyings), SHADER_MAY_DISCARD if may_discard else 0, log, len(log))
     if rc not in (0, -1):
         raise TrglError(f"trgl_shader_compile failed ({rc}): {log.value.decode(errors='replace')}")
     return rc == 0, log.value.decode(errors="replace")
@@ -319,11 +323,13 @@ class Context:
         self._chk(self.L.trgl_gather(self.h, comm, rank, world, int(bool(with_z))))
 
     # ---- submission ----
-    def register_shader(self, source: str, n_varyings: int) -> int:
-        """trgl_register_shader: compile (or take from the process cache) a user shader and load it on this context; returns its
-        kind, for draw() with n x n_varyings varyings."""
+    def register_shader(self, source: str, n_varyings: int, may_discard: bool = False) -> int:
+        """trgl_register_shader_ex: compile (or take from the process cache) a user shader and load it on this context; returns its
+        kind, for draw() with n x n_varyings varyings.  may_discard: its trgl_fragment returns trgl_frag_out and runs for every
+        z-pass in order (TRGL_SHADER_MAY_DISCARD)."""
         kind = C.c_int(-1)
-        self._chk(self.L.trgl_register_shader(self.h, source.encode(), int(n_varyings), C.byref(kind)))
+        self._chk(self.L.trgl_register_shader_ex(self.h, source.encode(), int(n_varyings), SHADER_MAY_DISCARD if may_discard else 0,
+                                                  C.byref(kind)))
         self._user_vary[kind.value] = int(n_varyings)
         return kind.value
 

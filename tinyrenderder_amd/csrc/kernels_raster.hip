@@ -410,58 +410,6 @@ __device__ __forceinline__ void resolve(BlockState& S, unsigned long long pend, 
 #endif
 }
 
-// Rows of a cleared tile without triangles: the clear values, row-contiguous (this is the whole kernel on a clear-only frame, the
-// "framebuffer + z write-out" figure of BASELINE.json).  Wave w of the workgroup stores rows [py0 + 8 w, py0 + 8 w + 7].
-__device__ __forceinline__ void clear_rows(const FrameParams& fp, int lane, int px0, int y0, int y1) {
-    const int xa1 = min(px0 + TRGL_TILE - 1, fp.W - 1);
-    const bool full_x = (px0 + TRGL_TILE - 1) <= xa1;
-    // z: 16 B per lane, 4 rows per store instruction
-    if (full_x && (fp.W & 1) == 0) {
-        for (int r4 = 0; r4 < 8; r4 += 4) {
-            const int x = px0 + ((lane & 15) << 1), y = y0 + r4 + (lane >> 4);
-            if (y <= y1) {
-                typedef double nt_d2 __attribute__((ext_vector_type(2)));
-                nt_d2 nv = { fp.clear_z, fp.clear_z };
-                __builtin_nontemporal_store(nv, reinterpret_cast<nt_d2*>(&fp.zb[(size_t)x + (size_t)y * fp.W]));
-            }
-        }
-    } else {
-        for (int r2 = 0; r2 < 8; r2 += 2) {
-            const int x = px0 + (lane & 31), y = y0 + r2 + (lane >> 5);
-            if (x <= xa1 && y <= y1) fp.zb[(size_t)x + (size_t)y * fp.W] = fp.clear_z;
-        }
-    }
-    // colour: 4 pixels per lane (12 B for RGB, 16 B for RGBA), 8 rows per store instruction
-    if (full_x && (fp.W & 3) == 0 && (fp.bpp == 3 || fp.bpp == 4)) {
-        const int x = px0 + ((lane & 7) << 2), y = y0 + (lane >> 3);
-        if (y <= y1) {
-            const uint32_t c = fp.clear_color;
-            const size_t idx = (size_t)x + (size_t)y * fp.W;
-            if (fp.bpp == 4) {
-                *reinterpret_cast<uint4*>(fp.fb + idx * 4) = make_uint4(c, c, c, c);
-            } else {
-                uint32_t* dst = reinterpret_cast<uint32_t*>(fp.fb + idx * 3);
-                dst[0] = (c & 0xffffffu) | (c << 24); dst[1] = ((c >> 8) & 0xffffu) | (c << 16); dst[2] = ((c >> 16) & 0xffu) | (c << 8);
-            }
-        }
-    } else {
-        for (int r2 = 0; r2 < 8; r2 += 2) {
-            const int x = px0 + (lane & 31), y = y0 + r2 + (lane >> 5);
-            if (x <= xa1 && y <= y1) {
-                const uint32_t c = fp.clear_color;
-                uint8_t* dst = fp.fb + ((size_t)x + (size_t)y * fp.W) * fp.bpp;
-                for (int i = 0; i < fp.bpp; ++i) dst[i] = (uint8_t)(c >> (8 * i));
-            }
-        }
-    }
-    if (fp.idbuf) {
-        for (int r2 = 0; r2 < 8; r2 += 2) {
-            const int x = px0 + (lane & 31), y = y0 + r2 + (lane >> 5);
-            if (x <= xa1 && y <= y1) fp.idbuf[(size_t)x + (size_t)y * fp.W] = 0xffffffffu;
-        }
-    }
-}
-
 #ifndef TRGL_RASTER_WAVES
 #define TRGL_RASTER_WAVES 5        // waves per SIMD the register allocation of k_raster aims at (96 vector registers; 6 waves = 80 registers spill 8 dwords per list step: 2 % slower)
 #endif
@@ -1185,7 +1133,7 @@ void launch_raster(hipStream_t s, const FrameParams& fp, int kind /* TRGL_SHADER
                    const uint32_t* tile_start, const uint32_t* tile_end, const DrawDesc* draws,
                    const DevTexture* tex, DevStats* stats, uint32_t max_items, uint4* items,
                    uint32_t* n_items, unsigned long long* item_stats, bool builtin_shade, const UserShade* user, int n_user,
-                   hipEvent_t ev_before, hipEvent_t ev_after) {
+                   hipFunction_t user_raster, hipEvent_t ev_before, hipEvent_t ev_after) {
     const int tiles = (fp.strip_ty1 - fp.strip_ty0) * fp.tiles_x;
     if (tiles <= 0 || max_items == 0) {          // a context that owns no rows (a rank beyond the image's bands): nothing to draw
         if (ev_before) (void)hipEventRecord(ev_before, s);
@@ -1196,6 +1144,16 @@ void launch_raster(hipStream_t s, const FrameParams& fp, int kind /* TRGL_SHADER
     hipLaunchKernelGGL(k_make_items, dim3((tiles + 255) / 256), dim3(256), 0, s, fp, tile_start, tile_end, items, n_items, const_cast<TriRec*>(recs));
     dim3 grid(((max_items + 7u) / 8u) * 8u);    // workgroup b -> item (b mod 8) * ceil(G / 8) + b / 8 (k_raster)
     if (ev_before) (void)hipEventRecord(ev_before, s);
+    if (user_raster) {                          // a flush of one user kind that may discard: its own raster kernel (raster_user.h)
+        FrameParams fpa = fp; const TriRec* a1 = recs; const TriW* a2 = recs_w; const uint32_t* a3 = vals; const uint16_t* a4 = bmask;
+        const DrawDesc* a5 = draws; const DevTexture* a6 = tex; DevStats* a7 = stats; const uint4* a8 = items; const uint32_t* a9 = n_items;
+        unsigned long long* a10 = item_stats;
+        void* args[] = { &fpa, &a1, &a2, &a3, &a4, &a5, &a6, &a7, &a8, &a9, &a10 };
+        (void)hipModuleLaunchKernel(user_raster, grid.x, 1, 1, 256, 1, 1, 0, s, args, nullptr);
+        if (ev_after) (void)hipEventRecord(ev_after, s);
+        hipLaunchKernelGGL(k_fold_stats, dim3(FOLD_BLOCKS), dim3(1024), 0, s, stats, n_items, item_stats);
+        return;
+    }
 #define TRGL_LAUNCH_RASTER(...) hipLaunchKernelGGL((k_raster<__VA_ARGS__>), grid, dim3(256), 0, s, fp, recs, recs_w, vals, bmask, tile_start, tile_end, draws, stats, items, n_items, item_stats)
     switch (kind) {
     case TRGL_SHADER_FLAT:

@@ -38,12 +38,15 @@ uint32_t raster_max_items(const FrameParams& fp);   // work items (workgroups of
 struct UserShade { hipFunction_t fn; int kind; };
 // item_stats: 4 x uint64 per work item (one partial of the counters per workgroup)
 // builtin_shade: the flush has PHONG / EYE draws (k_shade runs); user[0..n_user): the user kinds it has, shaded behind it
+// user_raster: the raster kernel of a user kind that may discard (raster_user.h), which runs in place of k_raster when the flush
+// holds only draws of that kind; null: k_raster
 void launch_raster(hipStream_t s, const FrameParams& fp, int kind, bool all_well_scaled, const TriRec* recs, const TriW* recs_w,
                    const uint32_t* vals, const uint16_t* bmask,
                    const uint32_t* tile_start, const uint32_t* tile_end, const DrawDesc* draws,
                    const DevTexture* tex, DevStats* stats, uint32_t max_items, uint4* items,
                    uint32_t* n_items, unsigned long long* item_stats, bool builtin_shade, const UserShade* user, int n_user,
-                   hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr);     // optional events recorded right around the k_raster launch
+                   hipFunction_t user_raster,
+                   hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr);     // optional events recorded right around the raster kernel's launch
 
 void launch_vertex_stage(hipStream_t s, const double mv[16], const double proj[16], const double* vertices, int stride,
                          const uint32_t* indices, uint32_t nfaces, double* clip, double* vary);

@@ -1,0 +1,148 @@
+// raster_user.h — the raster kernel of a user kind that may discard (include/trgl.h, TRGL_SHADER_MAY_DISCARD), compiled by hiprtc
+// behind the user's source, which defines `trgl_frag_out trgl_fragment(const trgl_frag_in&)`.
+//
+// Such a kind cannot be shaded once per visible pixel: a discarded fragment leaves the depth behind it in place, so the fragments
+// that follow are tested against it (our_gl.cpp:187-188).  This kernel does for a flush of one such kind what k_raster
+// (kernels_raster.hip) does for a CHECKER flush, in the plainest form: the same work items (k_make_items), the same sorted pair
+// lists, the same item_stats partials for k_fold_stats behind it.  One 256-thread workgroup per work item, one 8x8 block per
+// wave, one pixel per lane; the block's depths and colours stay in registers from the first candidate to the block-out.  Per
+// candidate, in list order: the record's bbox test, barycentric() of our_gl.cpp:77-86 with exactly the operations of the scan
+// (TRGL_OWNER_BARYCENTRICS), the coverage test on the quotients, the depth of :156-158, the finite check and the strict z-test, the
+// perspective-correct barycentrics of :168-185 and then trgl_fragment - called for every fragment that passes the z-test, in
+// submission order per pixel, exactly where our_gl.cpp:187 calls it.  k_raster's accelerations (depth-plane cull, depth bound in
+// the pair, deferred resolves) are left out: they only skip work, and nothing here depends on them.
+#pragma once
+#include "user_prelude.h"
+
+static_assert(__is_same(decltype(trgl_fragment(*(const trgl_frag_in*)nullptr)), trgl_frag_out),
+              "registered with TRGL_SHADER_MAY_DISCARD: trgl_fragment must return trgl_frag_out { bool discard; uint32_t bgra; }");
+
+extern "C" __global__ __launch_bounds__(256)
+void trgl_raster_user(FrameParams fp, const TriRec* __restrict__ recs, const TriW* __restrict__ recs_w, const uint32_t* __restrict__ vals,
+                      const uint16_t* __restrict__ bmask, const DrawDesc* __restrict__ draws, const DevTexture* __restrict__ tex,
+                      DevStats* __restrict__ stats, const uint4* __restrict__ items,
+                      const uint32_t* __restrict__ n_items, unsigned long long* __restrict__ item_stats) {
+    typedef const __attribute__((address_space(4))) TriRec CRec;       // records and descriptors through the scalar cache
+    typedef const __attribute__((address_space(4))) DrawDesc CDraw;
+    typedef const __attribute__((address_space(4))) DevTexture CTex;
+    __shared__ unsigned long long s_red[4][3];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // work item of this workgroup: the mapping of k_raster (each group of eight consecutive workgroups, which the dispatcher deals to
+    // the eight XCDs, takes items one eighth of the list apart, so that neighbouring items share an L2; speed only)
+    const uint32_t G = n_items[0];
+    const uint32_t per = (G + 7u) >> 3, xj = blockIdx.x >> 3;
+    const uint32_t g = (blockIdx.x & 7u) * per + xj;
+    if (xj >= per || g >= G) return;                      // (workgroup-uniform: the barrier at the end is safe)
+    const uint4 item4 = items[g];
+    const uint32_t item = item4.x;
+    const int t = (int)(item & 0xffffffu);
+    const int tile_y = t / fp.tiles_x, tile_x = t - tile_y * fp.tiles_x;
+    const int px0 = tile_x << TRGL_TILE_LOG2, py0 = tile_y << TRGL_TILE_LOG2;
+    unsigned long long* my_stats = item_stats + (size_t)g * 4;
+    if (item & TRGL_ITEM_CLEAR) {                         // cleared and empty: the clear values, as k_raster stores them
+        const int ya = max(py0 + 8 * w, fp.strip_y0), yb = min(min(py0 + 8 * w + 7, fp.H - 1), fp.strip_y1 - 1);
+        if (ya <= yb) trgl_shade::clear_rows(fp, lane, px0, ya, yb);
+        if (threadIdx.x == 0) {
+            my_stats[0] = 0ull; my_stats[1] = ~0ull; my_stats[2] = 0ull; my_stats[3] = 0ull;
+        }
+        return;
+    }
+    const int brow = (int)((item >> 24) & 3u);
+    const int kblk = 4 * brow + w;                        // this wave's block of the tile: bit 4 cy + cx of the pair masks
+    const int X0 = px0 + 8 * w, Y0 = py0 + 8 * brow;
+    const int x = X0 + (lane & 7), y = Y0 + (lane >> 3);
+    // k_make_items gives items to owned tile rows only; inside them, rows outside the strip and pixels beyond the image hold -inf
+    // (no fragment passes there) and are not stored
+    const bool owned = x < fp.W && y < fp.H && y >= fp.strip_y0 && y < fp.strip_y1;
+    const size_t pix = (size_t)x + (size_t)y * fp.W;
+    double z = -__builtin_inf();
+    if (owned) z = fp.init_from_clear ? fp.clear_z : fp.zb[pix];
+    uint32_t color = fp.clear_color;
+    uint32_t frags = 0;
+    double zmax = -__builtin_inf();
+    const bool zero_locked = stats->zero_locked != 0;
+
+    const uint32_t beg = item4.y, end = item4.z;
+    // the list, 64 entries per step: lane l reads entry p0 + l, and the entries whose block mask has this wave's bit are visited
+    // in list order
+    for (uint32_t p0 = beg; p0 < end; p0 += 64) {
+        const uint32_t p = p0 + (uint32_t)lane;
+        uint32_t v = 0;
+        bool hit = false;
+        if (p < end) { v = vals[p]; hit = (bmask[p] >> kblk) & 1u; }
+        unsigned long long cand = __ballot(hit);
+        while (cand) {
+            const int j = __builtin_ctzll(cand);
+            cand &= cand - 1;
+            const uint32_t tri = TRGL_VAL_TRI((uint32_t)__builtin_amdgcn_readlane((int)v, j));   // index of the triangle in the flush
+            CRec& r = ((CRec*)recs)[tri];
+            // our_gl.cpp:147-148 visits the clamped bbox only
+            if (!(x >= (int)r.bx0 && x <= (int)r.bx1 && y >= (int)r.by0 && y <= (int)r.by1)) continue;
+            double b[3];
+            {
+                const double pxc = (double)x + 0.5, pyc = (double)y + 0.5;          // :149
+                const double s0z = r.ax - pxc, s1z = r.ay - pyc;
+                const double ux = r.s0y * s1z - s0z * r.s1y;                        // geometry.h:145
+                const double uy = s0z * r.s1x - r.s0x * s1z;                        // geometry.h:146
+                const double us = ux + uy;
+                if (r.ruz != 0.0) {                                                 // :85 through the reciprocal ("exactness")
+                    b[0] = 1.0 - trgl_shade::div_by_uz(us, r.uz, r.ruz); b[1] = trgl_shade::div_by_uz(uy, r.uz, r.ruz);
+                    b[2] = trgl_shade::div_by_uz(ux, r.uz, r.ruz);
+                } else {                                                            // :85, as written (TRGL_DL_LITERAL)
+                    b[0] = 1.0 - us / r.uz; b[1] = uy / r.uz; b[2] = ux / r.uz;
+                }
+            }
+            if (b[0] < 0 || b[1] < 0 || b[2] < 0) continue;                        // :152
+            const double zn = b[0] * r.z0 + b[1] * r.z1 + b[2] * r.z2;               // :156-158
+            if (!__builtin_isfinite(zn) || !(zn < z)) continue;                      // :160, :165
+            const uint32_t dl = r.dl;
+            const uint32_t di = (uint32_t)__builtin_amdgcn_readfirstlane((int)TRGL_DL_DRAW(dl));
+            CDraw& d = ((CDraw*)draws)[di];
+            const TriW rw = recs_w[tri];
+            trgl_frag_in in;
+            const double denom = b[0] * rw.iw0 + b[1] * rw.iw1 + b[2] * rw.iw2;      // :172-174
+            if (fabs(denom) < 1e-15) { in.bar[0] = b[0]; in.bar[1] = b[1]; in.bar[2] = b[2]; }                  // :177-185
+            else { in.bar[0] = (b[0] * rw.iw0) / denom; in.bar[1] = (b[1] * rw.iw1) / denom; in.bar[2] = (b[2] * rw.iw2) / denom; }
+            const uint32_t local = TRGL_DL_LOCAL(dl);
+            in.vary = d.vary ? d.vary + (size_t)local * (uint32_t)d.K : nullptr;
+            in.u = (const trgl_uniforms*)&d.u;
+            in.color = r.color;
+            in.tex = (const DevTexture*)(CTex*)tex;
+            const trgl_frag_out o = trgl_fragment(in);                               // :187
+            if (o.discard) continue;                                                 // :188
+            z = zn;                                                                  // :191
+            color = o.bgra;                                                          // :192 (TGAImage::set at block-out)
+            ++frags;                                                                 // :194
+            asm("v_max_f64 %0, %0, %1" : "+v"(zmax) : "v"(zn));                      // :198 (the sign of a zero end: below)
+            // std::min / std::max keep the first of equal values and +0.0 == -0.0: when the z range ends in a zero its sign is that
+            // of the first zero written in the reference's order (triangle, x, y), see DevStats
+            if (zn == 0.0 && !zero_locked) {
+                const unsigned long long order = ((unsigned long long)tri << 32) | ((unsigned long long)x << 16) | (unsigned long long)y;
+                atomicMin(__builtin_signbit(zn) ? &stats->zero_neg_key : &stats->zero_pos_key, order);
+            }
+        }
+    }
+
+    // ---- block out: every owned pixel once (the colour only where this flush wrote it, or from the clear) ----------------
+    if (owned) {
+        fp.zb[pix] = z;
+        if (fp.init_from_clear || frags) trgl_shade::store_pixel(fp, pix, color);
+    }
+    // ---- one partial of our_gl.cpp:194-198 per work item, in k_raster's layout: fragments, smallest and largest depth key, 0
+    // (the smallest depth a pixel was written with is its last one: the z-test only lets smaller ones through)
+    unsigned long long fr = frags, kmin = zkey(frags ? z : __builtin_inf()), kmax = zkey(zmax);
+    for (int o = 32; o; o >>= 1) {
+        fr += __shfl_xor(fr, o);
+        const unsigned long long a = __shfl_xor(kmin, o); kmin = a < kmin ? a : kmin;
+        const unsigned long long c = __shfl_xor(kmax, o); kmax = c > kmax ? c : kmax;
+    }
+    if (lane == 0) { s_red[w][0] = fr; s_red[w][1] = kmin; s_red[w][2] = kmax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            fr += s_red[k][0]; kmin = s_red[k][1] < kmin ? s_red[k][1] : kmin; kmax = s_red[k][2] > kmax ? s_red[k][2] : kmax;
+        }
+        my_stats[0] = fr; my_stats[1] = kmin; my_stats[2] = kmax; my_stats[3] = 0ull;
+    }
+}

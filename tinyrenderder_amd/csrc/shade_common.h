@@ -1,6 +1,6 @@
-// shade_common.h — device code shared by k_raster / k_shade (kernels_raster.hip) and the shade kernel of user shaders, which
-// hiprtc compiles at run time from shade_user.h (user_shaders.cpp embeds this file as text).  One copy of the samplers, of the
-// division by u.z and of the per-pixel prologue of deferred shading.
+// shade_common.h — device code shared by k_raster / k_shade (kernels_raster.hip) and the kernels of user shaders, which hiprtc
+// compiles at run time from shade_user.h and raster_user.h (user_shaders.cpp embeds this file as text).  One copy of the samplers,
+// of the division by u.z, of the per-pixel prologue of deferred shading and of the store of a cleared tile.
 #pragma once
 #include "trgl_device.h"
 
@@ -81,6 +81,58 @@ __device__ __forceinline__ void store_pixel(const FrameParams& fp, size_t idx, u
     if (fp.bpp == 3) { dst[0] = (uint8_t)color; dst[1] = (uint8_t)(color >> 8); dst[2] = (uint8_t)(color >> 16); }
     else if (fp.bpp == 4) *reinterpret_cast<uint32_t*>(dst) = color;
     else dst[0] = (uint8_t)color;
+}
+
+// Rows of a cleared tile without triangles: the clear values, row-contiguous (this is the whole kernel on a clear-only frame, the
+// "framebuffer + z write-out" figure of BASELINE.json).  Wave w of the workgroup stores rows [py0 + 8 w, py0 + 8 w + 7].
+__device__ __forceinline__ void clear_rows(const FrameParams& fp, int lane, int px0, int y0, int y1) {
+    const int xa1 = min(px0 + TRGL_TILE - 1, fp.W - 1);
+    const bool full_x = (px0 + TRGL_TILE - 1) <= xa1;
+    // z: 16 B per lane, 4 rows per store instruction
+    if (full_x && (fp.W & 1) == 0) {
+        for (int r4 = 0; r4 < 8; r4 += 4) {
+            const int x = px0 + ((lane & 15) << 1), y = y0 + r4 + (lane >> 4);
+            if (y <= y1) {
+                typedef double nt_d2 __attribute__((ext_vector_type(2)));
+                nt_d2 nv = { fp.clear_z, fp.clear_z };
+                __builtin_nontemporal_store(nv, reinterpret_cast<nt_d2*>(&fp.zb[(size_t)x + (size_t)y * fp.W]));
+            }
+        }
+    } else {
+        for (int r2 = 0; r2 < 8; r2 += 2) {
+            const int x = px0 + (lane & 31), y = y0 + r2 + (lane >> 5);
+            if (x <= xa1 && y <= y1) fp.zb[(size_t)x + (size_t)y * fp.W] = fp.clear_z;
+        }
+    }
+    // colour: 4 pixels per lane (12 B for RGB, 16 B for RGBA), 8 rows per store instruction
+    if (full_x && (fp.W & 3) == 0 && (fp.bpp == 3 || fp.bpp == 4)) {
+        const int x = px0 + ((lane & 7) << 2), y = y0 + (lane >> 3);
+        if (y <= y1) {
+            const uint32_t c = fp.clear_color;
+            const size_t idx = (size_t)x + (size_t)y * fp.W;
+            if (fp.bpp == 4) {
+                *reinterpret_cast<uint4*>(fp.fb + idx * 4) = make_uint4(c, c, c, c);
+            } else {
+                uint32_t* dst = reinterpret_cast<uint32_t*>(fp.fb + idx * 3);
+                dst[0] = (c & 0xffffffu) | (c << 24); dst[1] = ((c >> 8) & 0xffffu) | (c << 16); dst[2] = ((c >> 16) & 0xffu) | (c << 8);
+            }
+        }
+    } else {
+        for (int r2 = 0; r2 < 8; r2 += 2) {
+            const int x = px0 + (lane & 31), y = y0 + r2 + (lane >> 5);
+            if (x <= xa1 && y <= y1) {
+                const uint32_t c = fp.clear_color;
+                uint8_t* dst = fp.fb + ((size_t)x + (size_t)y * fp.W) * fp.bpp;
+                for (int i = 0; i < fp.bpp; ++i) dst[i] = (uint8_t)(c >> (8 * i));
+            }
+        }
+    }
+    if (fp.idbuf) {
+        for (int r2 = 0; r2 < 8; r2 += 2) {
+            const int x = px0 + (lane & 31), y = y0 + r2 + (lane >> 5);
+            if (x <= xa1 && y <= y1) fp.idbuf[(size_t)x + (size_t)y * fp.W] = 0xffffffffu;
+        }
+    }
 }
 
 }  // namespace trgl_shade

@@ -6,6 +6,9 @@
 #pragma once
 #include "user_prelude.h"
 
+static_assert(__is_same(decltype(trgl_fragment(*(const trgl_frag_in*)nullptr)), uint32_t),
+              "trgl_fragment must return uint32_t (a shader whose fragment returns trgl_frag_out is registered with TRGL_SHADER_MAY_DISCARD)");
+
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void trgl_shade_user(FrameParams fp, const TriRec* __restrict__ recs, const TriW* __restrict__ recs_w, const DrawDesc* __restrict__ draws,
                      const DevTexture* __restrict__ tex, const uint4* __restrict__ items, const uint32_t* __restrict__ n_items, int kind) {

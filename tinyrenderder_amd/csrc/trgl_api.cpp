@@ -57,8 +57,9 @@ static size_t pair_capacity(size_t need) {
 // (builtin_shade: the flush has PHONG / EYE draws; user_kinds: bit i = it has draws of user kind TRGL_SHADER_USER_FIRST + i)
 struct PendingRaster { bool active = false; FrameParams fp; int flush_kind = 0; uint32_t cap = 0; int cur = 0; uint64_t N = 0;
                        bool builtin_shade = false; uint32_t user_kinds = 0; };
-// a user shader registered on the context (trgl_register_shader): its module and shade kernel
-struct UserKind { hipModule_t mod; hipFunction_t fn; int K; };
+// a user shader registered on the context (trgl_register_shader_ex): its module and kernel - the shade kernel, or the raster kernel
+// of a kind that may discard (TRGL_SHADER_MAY_DISCARD)
+struct UserKind { hipModule_t mod; hipFunction_t fn; int K; bool may_discard; };
 
 struct trgl_ctx {
     int device = 0;
@@ -323,6 +324,11 @@ static int stage_copy(trgl_ctx* c, const void* src, size_t bytes, void** dev) {
     return TRGL_OK;
 }
 
+// a registered user kind that may discard (its draws are rasterized by its own kernel, in flushes of their own)
+static bool discarding_kind(const trgl_ctx* c, int kind) {
+    return kind >= TRGL_SHADER_USER_FIRST && kind - TRGL_SHADER_USER_FIRST < (int)c->user.size() && c->user[kind - TRGL_SHADER_USER_FIRST].may_discard;
+}
+
 int trgl_draw(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip, const double* vary,
               const uint32_t* colors, uint64_t n, int mem_kind) {
     CHKCTX(c);
@@ -351,7 +357,9 @@ int trgl_draw(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip,
     // a record addresses its triangle as (draw index, 24-bit index): split larger submissions
     for (uint64_t done = 0; done < n;) {
         uint64_t m = n - done; if (m > TRGL_DRAW_MAX_TRIS) m = TRGL_DRAW_MAX_TRIS;
-        if ((c->draws.size() >= TRGL_MAX_DRAWS || c->queued_tris + m > TRGL_FLUSH_MAX_TRIS) && (r = trgl_flush(c))) return r;
+        // a kind that may discard shares a flush only with draws of the same kind: its raster kernel runs the whole flush
+        const bool kind_cut = !c->draws.empty() && c->draws.back().kind != kind && (discarding_kind(c, kind) || discarding_kind(c, c->draws.back().kind));
+        if ((c->draws.size() >= TRGL_MAX_DRAWS || c->queued_tris + m > TRGL_FLUSH_MAX_TRIS || kind_cut) && (r = trgl_flush(c))) return r;
         DrawDesc d; std::memset(&d, 0, sizeof(d));
         d.n = (uint32_t)m; d.first = (uint32_t)c->queued_tris; d.kind = kind; d.K = K;
         if (u) d.u = *u; else { d.u.tex_diffuse = d.u.tex_normal = d.u.tex_specular = -1; }
@@ -538,10 +546,11 @@ int trgl_flush_begin(trgl_ctx* c) {
     int flush_kind = c->draws.empty() ? TRGL_SHADER_FLAT : c->draws[0].kind;     // one kind for the whole flush, or -1
     for (auto& d : c->draws) if (d.kind != flush_kind) flush_kind = -1;
     bool builtin_shade = false;
-    uint32_t user_kinds = 0;
+    uint32_t user_kinds = 0;           // (kinds that may discard are rasterized by their own kernel: no visibility buffer, no shade kernel)
     for (auto& d : c->draws) {
         if (d.kind == TRGL_SHADER_PHONG || d.kind == TRGL_SHADER_EYE) builtin_shade = true;
-        if (d.kind >= TRGL_SHADER_USER_FIRST) user_kinds |= 1u << (d.kind - TRGL_SHADER_USER_FIRST);
+        if (d.kind >= TRGL_SHADER_USER_FIRST && !discarding_kind(c, d.kind)) user_kinds |= 1u << (d.kind - TRGL_SHADER_USER_FIRST);
+        if (discarding_kind(c, d.kind) && d.kind != flush_kind) return fail(c, TRGL_E_STATE, "flush: a kind that may discard shares a flush with another kind");
     }
     if (builtin_shade || user_kinds) {                                            // shaded once per visible pixel (k_shade, shade_user.h)
         if ((r = c->idbuf.grow(c, (size_t)c->W * c->H))) return r;
@@ -629,8 +638,10 @@ int trgl_flush_end(trgl_ctx* c) {
     int n_user = 0;
     for (int i = 0; i < (int)c->user.size(); ++i)
         if (c->rp.user_kinds >> i & 1u) user[n_user++] = UserShade{ c->user[i].fn, TRGL_SHADER_USER_FIRST + i };
+    // a flush of a kind that may discard: its own raster kernel in place of k_raster
+    const hipFunction_t user_raster = discarding_kind(c, flush_kind) ? c->user[flush_kind - TRGL_SHADER_USER_FIRST].fn : nullptr;
     launch_raster(s, fp, flush_kind, all_well_scaled, recs_arg, c->recs_w.p, vals_arg, bmask_arg, c->tile_start.p, c->tile_end(), c->draws_dev.p, c->tex_dev.p,
-                  c->stats_dev.p, max_items, c->items.p, c->n_items.p, c->item_stats.p, c->rp.builtin_shade, user, n_user,
+                  c->stats_dev.p, max_items, c->items.p, c->n_items.p, c->item_stats.p, c->rp.builtin_shade, user, n_user, user_raster,
                   c->profiling ? c->ev[4] : nullptr, c->profiling ? c->ev[5] : nullptr);
     if (c->profiling) { HIPCHK(c, hipEventRecord(c->ev[3], s)); c->events_pending = true; }
     HIPCHK(c, hipGetLastError());
@@ -650,16 +661,17 @@ int trgl_flush_end(trgl_ctx* c) {
     return TRGL_OK;
 }
 
-int trgl_register_shader(trgl_ctx* c, const char* source, int n_varyings, int* kind) {
+int trgl_register_shader_ex(trgl_ctx* c, const char* source, int n_varyings, uint32_t flags, int* kind) {
     CHKCTX(c);
     if (!kind) return fail(c, TRGL_E_INVALID, "trgl_register_shader: kind is null");
     if (c->user.size() >= TRGL_MAX_USER_SHADERS) return fail(c, TRGL_E_INVALID, "trgl_register_shader: TRGL_MAX_USER_SHADERS already registered");
     std::string log;
     const std::vector<char>* code = nullptr;
-    if (int r = user_shader_code(source, n_varyings, &log, &code)) { c->err = "trgl_register_shader: " + log; return r; }
-    UserKind u{ nullptr, nullptr, n_varyings };
+    if (int r = user_shader_code(source, n_varyings, flags, &log, &code)) { c->err = "trgl_register_shader: " + log; return r; }
+    const bool may_discard = (flags & TRGL_SHADER_MAY_DISCARD) != 0;
+    UserKind u{ nullptr, nullptr, n_varyings, may_discard };
     HIPCHK(c, hipModuleLoadData(&u.mod, code->data()));
-    const hipError_t e = hipModuleGetFunction(&u.fn, u.mod, USER_SHADE_KERNEL);
+    const hipError_t e = hipModuleGetFunction(&u.fn, u.mod, may_discard ? USER_RASTER_KERNEL : USER_SHADE_KERNEL);
     if (e != hipSuccess) {
         (void)hipModuleUnload(u.mod);
         c->err = std::string("hipModuleGetFunction: ") + hipGetErrorString(e);
@@ -668,6 +680,10 @@ int trgl_register_shader(trgl_ctx* c, const char* source, int n_varyings, int* k
     c->user.push_back(u);
     *kind = TRGL_SHADER_USER_FIRST + (int)c->user.size() - 1;
     return TRGL_OK;
+}
+
+int trgl_register_shader(trgl_ctx* c, const char* source, int n_varyings, int* kind) {
+    return trgl_register_shader_ex(c, source, n_varyings, 0u, kind);
 }
 
 int trgl_sync(trgl_ctx* c) {

@@ -1,5 +1,5 @@
 // user_prelude.h — what a user shader's source sees (include/trgl.h, "User shaders"): compiled by hiprtc ahead of the source,
-// from the copy user_shaders.cpp embeds.  The sampler is the one k_shade uses (shade_common.h).
+// from the copy user_shaders.cpp embeds, for both contracts (shade_user.h and raster_user.h).  The sampler is the one k_shade uses (shade_common.h).
 #pragma once
 #include "shade_common.h"
 
@@ -11,6 +11,8 @@ struct trgl_frag_in {
     const DevTexture* tex;       // the context's texture table (trgl_sample2D)
 };
 struct trgl_texel { uint32_t bgra; int bytespp; };   // TGAColor (tgaimage.h:29-31), bgra[0] in the low byte
+// what trgl_fragment returns with TRGL_SHADER_MAY_DISCARD: std::pair<bool, TGAColor> of IShader::fragment (our_gl.h:51)
+struct trgl_frag_out { bool discard; uint32_t bgra; };
 
 // IShader::sample2D / Model::diffuse (model.cpp:415-459): clamp(int(uv * size), 0, size - 1), nearest texel; an empty slot samples
 // as opaque white (model.cpp:416-418)

@@ -1,9 +1,10 @@
 // user_shaders.cpp — user shaders compiled at run time (include/trgl.h, "User shaders").
 //
-// The source of a user shader is compiled by hiprtc between the prelude (user_prelude.h) and the shade kernel template
-// (shade_user.h).  Those and the headers they include are built into the library as text (tools/embed_sources.py) and handed to
-// hiprtc as in-memory headers, with three stand-ins for the C headers hiprtc does not have.  libhiprtc is loaded when first
-// needed, as librccl is: without it the library loads and everything but the two calls here works.
+// The source of a user shader is compiled by hiprtc between the prelude (user_prelude.h) and a kernel template: the shade kernel
+// (shade_user.h), or for a shader that may discard the raster kernel (raster_user.h).  Those and the headers they include are built
+// into the library as text (tools/embed_sources.py) and handed to hiprtc as in-memory headers, with three stand-ins for the C headers
+// hiprtc does not have.  libhiprtc is loaded when first needed, as librccl is: without it the library loads and everything but the
+// compile calls here works.
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 #include <dlfcn.h>
@@ -108,14 +109,17 @@ int compile(Hiprtc& rtc, const std::string& program, std::string* log, std::vect
 
 namespace trgl {
 
-int user_shader_code(const char* source, int K, std::string* log, const std::vector<char>** code) {
+int user_shader_code(const char* source, int K, uint32_t flags, std::string* log, const std::vector<char>** code) {
     log->clear();
     if (!source) { *log = "source is null"; return TRGL_E_INVALID; }
     if (K < 0 || K > TRGL_MAX_USER_VARY) { *log = "n_varyings must be in 0.." + std::to_string(TRGL_MAX_USER_VARY); return TRGL_E_INVALID; }
+    if (flags & ~uint32_t(TRGL_SHADER_MAY_DISCARD)) { *log = "unknown flag bits " + std::to_string(flags & ~uint32_t(TRGL_SHADER_MAY_DISCARD)); return TRGL_E_INVALID; }
+    const bool may_discard = (flags & TRGL_SHADER_MAY_DISCARD) != 0;
     // the user's lines keep their own numbers in the log (#line)
     const std::string program = "#include \"user_prelude.h\"\n#define TRGL_USER_VARY " + std::to_string(K) +
-                                "\n#line 1 \"user_shader\"\n" + source + "\n#include \"shade_user.h\"\n";
-    std::string key;
+                                "\n#define TRGL_USER_MAY_DISCARD " + (may_discard ? "1" : "0") +
+                                "\n#line 1 \"user_shader\"\n" + source + "\n#include \"" + (may_discard ? "raster_user.h" : "shade_user.h") + "\"\n";
+    std::string key = "flags " + std::to_string(flags) + '\n';
     for (const char* o : kOptions) { key += o; key += ' '; }
     key += '\n'; key += program;
     Cache& c = cache();
@@ -135,10 +139,10 @@ int user_shader_code(const char* source, int K, std::string* log, const std::vec
 
 }  // namespace trgl
 
-extern "C" int trgl_shader_compile(const char* source, int n_varyings, char* log, size_t log_len) {
+extern "C" int trgl_shader_compile_ex(const char* source, int n_varyings, uint32_t flags, char* log, size_t log_len) {
     std::string msg;
     const std::vector<char>* code = nullptr;
-    const int r = trgl::user_shader_code(source, n_varyings, &msg, &code);
+    const int r = trgl::user_shader_code(source, n_varyings, flags, &msg, &code);
     if (r) trgl::set_global_error("trgl_shader_compile: " + msg);
     if (log && log_len) {
         const size_t n = msg.size() < log_len - 1 ? msg.size() : log_len - 1;
@@ -146,4 +150,8 @@ extern "C" int trgl_shader_compile(const char* source, int n_varyings, char* log
         log[n] = '\0';
     }
     return r;
+}
+
+extern "C" int trgl_shader_compile(const char* source, int n_varyings, char* log, size_t log_len) {
+    return trgl_shader_compile_ex(source, n_varyings, 0u, log, log_len);
 }

@@ -17,8 +17,9 @@
 //     shader kind the device implements (trgl_shaders.h: FlatShader, GouraudShader, PhongShader, EyeShader).
 //     A subclass without one makes rasterize() fail loudly — there is NO CPU fallback.
 //   * a fragment stage the device does not implement is a user shader: HIP C++ source registered with gl_register_shader()
-//     (compiled at run time for the GPU; the contract is in include/trgl.h) and drawn through a UserShader (trgl_shaders.h).
-//     Its kind stays the same when the shim recreates its context for a framebuffer of another size.
+//     (compiled at run time for the GPU; the contract is in include/trgl.h) and drawn through a UserShader (trgl_shaders.h);
+//     a fragment() that can discard is one too, registered with may_discard = true.  Its kind stays the same when the shim
+//     recreates its context for a framebuffer of another size.
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -139,7 +140,7 @@ struct State {
     std::vector<double> clip, vary;
     std::vector<std::uint32_t> colors;
     mat<4, 4> viewport_at_batch;
-    struct UserSource { std::string source; int n_varyings; };
+    struct UserSource { std::string source; int n_varyings; bool may_discard; };
     std::vector<UserSource> user;         // gl_register_shader(): registered on every context, in order (kind = USER_FIRST + index)
     int err = TRGL_OK;                    // first C-ABI error since gl_clear_error() (a TRGL_E_* code)
     std::string err_msg;
@@ -170,7 +171,8 @@ inline bool bind(TGAImage& fb) {
         // tries again with a new one)
         for (std::size_t i = 0; i < s.user.size(); ++i) {
             int kind = -1;
-            bool ok = TRGL_SHIM_OK(trgl_register_shader(s.ctx, s.user[i].source.c_str(), s.user[i].n_varyings, &kind));
+            bool ok = TRGL_SHIM_OK(trgl_register_shader_ex(s.ctx, s.user[i].source.c_str(), s.user[i].n_varyings,
+                                                           s.user[i].may_discard ? TRGL_SHADER_MAY_DISCARD : 0u, &kind));
             if (ok && kind != TRGL_SHADER_USER_FIRST + int(i)) ok = fail("gl_register_shader: kinds out of order", TRGL_E_STATE, nullptr);
             if (!ok) { trgl_destroy(s.ctx); s.ctx = nullptr; return false; }
         }
@@ -219,21 +221,24 @@ inline void gl_clear_error() { trgl_shim::State& s = trgl_shim::state(); s.err =
 // A user shader (include/trgl.h, "User shaders"): HIP C++ source defining trgl_fragment, with n_varyings doubles of varyings per
 // triangle.  The source is compiled at once (a compile error is reported through gl_last_error(), with the compiler's log, and
 // -1 comes back); the kind returned is what UserShader::kind takes, and it stays valid on every context the shim creates.
-inline int gl_register_shader(const char* source, int n_varyings) {
+// may_discard: the source's trgl_fragment returns trgl_frag_out, the std::pair<bool, TGAColor> of IShader::fragment, and runs for
+// every fragment that passes the z-test, in order (TRGL_SHADER_MAY_DISCARD).
+inline int gl_register_shader(const char* source, int n_varyings, bool may_discard = false) {
     trgl_shim::State& s = trgl_shim::state();
     if (s.user.size() >= TRGL_MAX_USER_SHADERS) { trgl_shim::fail("gl_register_shader", TRGL_E_INVALID, nullptr); return -1; }
+    const std::uint32_t flags = may_discard ? TRGL_SHADER_MAY_DISCARD : 0u;
     std::string log(4096, '\0');
-    const int rc = trgl_shader_compile(source, n_varyings, &log[0], log.size());
+    const int rc = trgl_shader_compile_ex(source, n_varyings, flags, &log[0], log.size());
     if (rc != TRGL_OK) {
         if (s.err == TRGL_OK) { s.err = rc; s.err_msg = std::string("gl_register_shader: ") + log.c_str(); }
         return -1;
     }
-    s.user.push_back({ source, n_varyings });
+    s.user.push_back({ source, n_varyings, may_discard });
     const int kind = TRGL_SHADER_USER_FIRST + int(s.user.size()) - 1;
     if (s.ctx) {
         trgl_shim::submit_batch();
         int k = -1;
-        if (!TRGL_SHIM_OK(trgl_register_shader(s.ctx, source, n_varyings, &k))) { s.user.pop_back(); return -1; }
+        if (!TRGL_SHIM_OK(trgl_register_shader_ex(s.ctx, source, n_varyings, flags, &k))) { s.user.pop_back(); return -1; }
     }
     return kind;
 }
