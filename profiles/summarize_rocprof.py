@@ -13,6 +13,9 @@ def short(name):
     m = re.search(r"k_raster<(\d)(?:, (\d))?(?:, (true|false))?>", name)
     if m:
         return "k_raster<" + ["flat", "gouraud", "phong", "eye", "checker", "any"][int(m.group(1))] + (", bpp " + m.group(2) if m.group(2) and m.group(2) != "0" else "") + (", all well scaled" if m.group(3) == "true" else "") + ">"
+    m = re.search(r"k_radix_scatter<(?:\d+, )?(true|false), (true|false)>", name)
+    if m:
+        return "k_radix_scatter" + (" (last pass)" if m.group(2) == "true" else "")
     m = re.search(r"k_shade<(\d)>", name)
     if m:
         return "k_shade<" + ["flat", "gouraud", "phong", "eye", "checker", "any"][int(m.group(1))] + ">"

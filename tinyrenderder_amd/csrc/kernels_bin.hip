@@ -5,8 +5,8 @@
 //   expand     : (tile id, triangle id) pairs in triangle order
 //   radix pass : stable LSD counting sort of the pairs by tile id, so every tile's slice lists its
 //                triangles in SUBMISSION ORDER (z ties keep the earlier triangle, our_gl.cpp:165;
-//                fragments_drawn / z-range are order dependent, our_gl.cpp:194-198)
-//   bounds     : per-tile [start,end) in the sorted pair list
+//                fragments_drawn / z-range are order dependent, our_gl.cpp:194-198); the last pass also
+//                leaves the per-tile [start,end) of the sorted pair list
 //
 // All integer / fp64 IEEE work; built with -ffp-contract=off so no product is fused into a sum.
 #include <hip/hip_runtime.h>
@@ -299,10 +299,11 @@ constexpr int SPINE_THREADS = 1024;
 __global__ __launch_bounds__(SPINE_THREADS) void k_chunk_spine(const uint32_t* __restrict__ blk_sums, uint32_t nblk,
                                                                uint32_t* __restrict__ chunk_off,
                                                                unsigned long long* __restrict__ total64, unsigned long long* __restrict__ host_copy,
-                                                               uint4* __restrict__ zero16, uint32_t n_zero16) {
+                                                               uint4* __restrict__ bounds16, uint32_t n_half16) {
     __shared__ unsigned long long s_wave[SPINE_THREADS / 64];
-    // (the tile bounds of the flush start from zero: cleared here instead of by a fill command of its own on the stream, 4.6 us)
-    for (uint32_t k = threadIdx.x; k < n_zero16; k += SPINE_THREADS) zero16[k] = make_uint4(0, 0, 0, 0);
+    // (the tile bounds of the flush start empty, tile_start at ~0 and tile_end at 0 - the last radix pass narrows them with atomics:
+    // set here instead of by fill commands of their own on the stream, 4.6 us each)
+    for (uint32_t k = threadIdx.x; k < 2 * n_half16; k += SPINE_THREADS) bounds16[k] = k < n_half16 ? make_uint4(~0u, ~0u, ~0u, ~0u) : make_uint4(0, 0, 0, 0);
     const uint32_t nchunks = (nblk + EXPAND_CHUNK - 1) / EXPAND_CHUNK;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     // One chunk (16 block sums = 64 bytes) per thread, 1024 chunks per round.  Offsets are 32-bit by design (a flush holds
@@ -347,11 +348,13 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_chunk_spine(const uint32_t* _
 // expand: triangle i owns pairs [off, off + cnt[i]) = its tiles in row-major order; off is computed here.
 // Triangles with many tiles are written by the whole wave.  One launch per draw (same blocks as k_setup).
 // The pairs of a block are consecutive in the output (the offsets are a prefix sum in submission order), so they are
-// assembled in LDS and written out linearly: whole cache lines instead of 64 lanes x a few elements each with a stride.
-// A block whose triangles cover more than EXPAND_STAGE tiles writes straight to memory.
+// assembled in LDS and written out linearly, 16 bytes per lane: pair j of the block sits at LDS slot (base & 3) + j, so a
+// group of four LDS slots is a 16-byte-aligned group of four pairs in memory.  A block whose triangles cover more than
+// EXPAND_STAGE tiles writes straight to memory.
 // Every pair also carries the 4 x 4 mask of the tile's 8 x 8-pixel blocks that the triangle's clamped bbox reaches (bit 4 cy + cx):
 // the raster wave that owns a block picks its candidates from the tile's list by that bit, without touching their records.
-// K: the key type, 16 bits while the frame has at most 65536 tiles (up to 8192x8192), 32 bits beyond.
+// The sort word of a pair: while the frame has at most 65536 tiles (up to 8192x8192) the tile id in its low 16 bits and the mask in
+// its high 16 (one 4-byte stream for both); beyond that (WIDE) the 32-bit tile id, and the mask in a 16-bit stream of its own.
 constexpr uint32_t EXPAND_STAGE = 3072;
 // blocks of tile (tx, ty) inside the block-unit box [qx0, qx1] x [qy0, qy1] (the box reaches the tile)
 __device__ __forceinline__ uint32_t tile_block_mask(uint32_t tx, uint32_t ty, uint32_t qx0, uint32_t qy0, uint32_t qx1, uint32_t qy1) {
@@ -359,16 +362,16 @@ __device__ __forceinline__ uint32_t tile_block_mask(uint32_t tx, uint32_t ty, ui
     const uint32_t r0 = qy0 > 4 * ty ? qy0 - 4 * ty : 0u, r1 = qy1 < 4 * ty + 3 ? qy1 - 4 * ty : 3u;
     return (((2u << c1) - (1u << c0)) & 0xfu) * 0x1111u & ((0xffffu >> (12 - 4 * r1)) & (0xffffu << (4 * r0)));
 }
-template <typename K>
+template <bool WIDE>
 __global__ __launch_bounds__(256) void k_expand(FrameParams fp, uint32_t first, uint32_t n, int tiles_x, const uint32_t* __restrict__ cnt,
                                                 const uint32_t* __restrict__ blk_sums, const uint32_t* __restrict__ chunk_off,
                                                 uint32_t blk_base, const uint2* __restrict__ tilebox,
-                                                K* __restrict__ keys, uint32_t* __restrict__ vals, uint16_t* __restrict__ bmask,
+                                                uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint16_t* __restrict__ bmask,
                                                 const unsigned long long* __restrict__ pairs_total, uint32_t cap) {
     __shared__ uint32_t smem[4];
-    __shared__ uint32_t s_v[EXPAND_STAGE];
-    __shared__ K s_k[EXPAND_STAGE];
-    __shared__ uint16_t s_m[EXPAND_STAGE];
+    __shared__ __attribute__((aligned(16))) uint32_t s_k[EXPAND_STAGE + 4];
+    __shared__ __attribute__((aligned(16))) uint32_t s_v[EXPAND_STAGE + 4];
+    __shared__ __attribute__((aligned(16))) uint16_t s_m[WIDE ? EXPAND_STAGE + 4 : 4];
     if (*pairs_total > cap) return;        // the host sized the buffers from an earlier flush: it will grow them and launch again
     const uint32_t local = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t i = first + local;                          // index of the triangle within the flush
@@ -387,7 +390,13 @@ __global__ __launch_bounds__(256) void k_expand(FrameParams fp, uint32_t first, 
     uint32_t tot;
     const uint32_t o = block_excl_scan(c, smem, &tot);         // offset inside the block's run of pairs
     const bool staged = tot <= EXPAND_STAGE;                   // block-uniform
-    K* const kdst = keys + base; uint32_t* const vdst = vals + base; uint16_t* const mdst = bmask + base;
+    const uint32_t sh = base & 3u;
+    uint32_t* const kdst = keys + base; uint32_t* const vdst = vals + base; uint16_t* const mdst = bmask + base;
+    auto put = [&](uint32_t j, uint32_t key, uint32_t iz, uint32_t m) {
+        const uint32_t word = WIDE ? key : key | (m << 16);
+        if (staged) { s_k[sh + j] = word; s_v[sh + j] = iz; if (WIDE) s_m[sh + j] = (uint16_t)m; }
+        else { kdst[j] = word; vdst[j] = iz; if (WIDE) mdst[j] = (uint16_t)m; }
+    };
     constexpr uint32_t SMALL = 8;
     if (c && c <= SMALL) {
         // row-major walk with running counters instead of a division and a modulo per pair
@@ -397,9 +406,7 @@ __global__ __launch_bounds__(256) void k_expand(FrameParams fp, uint32_t first, 
         uint32_t tx = tx0, row = 0;
         uint32_t ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, 0) : ty0;
         for (uint32_t k = 0; k < c; ++k) {
-            const K key = (K)(ty * tiles_x + tx);
-            const uint16_t m = (uint16_t)tile_block_mask(tx, ty, qx0, qy0, qx1, qy1);
-            if (staged) { s_k[o + k] = key; s_v[o + k] = iz; s_m[o + k] = m; } else { kdst[o + k] = key; vdst[o + k] = iz; mdst[o + k] = m; }
+            put(o + k, ty * tiles_x + tx, iz, tile_block_mask(tx, ty, qx0, qy0, qx1, qy1));
             if (++tx > tx1) { tx = tx0; ++row; ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, (int)row) : ty0 + row; }
         }
     }
@@ -416,44 +423,50 @@ __global__ __launch_bounds__(256) void k_expand(FrameParams fp, uint32_t first, 
         uint32_t wdt = tx1 - tx0 + 1;
         for (uint32_t k = lane; k < cc; k += 64) {
             uint32_t ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, (int)(k / wdt)) : ty0 + k / wdt, tx = tx0 + k % wdt;
-            const K key = (K)(ty * tiles_x + tx);
-            const uint16_t m = (uint16_t)tile_block_mask(tx, ty, qx0, qy0, qx1, qy1);
-            if (staged) { s_k[oo + k] = key; s_v[oo + k] = ii; s_m[oo + k] = m; } else { kdst[oo + k] = key; vdst[oo + k] = ii; mdst[oo + k] = m; }
+            put(oo + k, ty * tiles_x + tx, ii, tile_block_mask(tx, ty, qx0, qy0, qx1, qy1));
         }
     }
     if (staged) {
         __syncthreads();
-        for (uint32_t j = threadIdx.x; j < tot; j += 256) { kdst[j] = s_k[j]; vdst[j] = s_v[j]; mdst[j] = s_m[j]; }
+        // LDS slots [sh, sh + tot) = pairs [base, base + tot); slot group q = the 16-byte-aligned pairs base - sh + 4q .. + 3.
+        // Groups the run covers entirely go out as one 16-byte store per stream; the (at most two) partial ones pair by pair.
+        uint32_t* const kq = keys + (base - sh); uint32_t* const vq = vals + (base - sh); uint16_t* const mq = bmask + (base - sh);
+        const uint32_t end = sh + tot;
+        for (uint32_t q = threadIdx.x; 4 * q < end; q += 256) {
+            const uint32_t j0 = 4 * q;
+            if (j0 >= sh && j0 + 4 <= end) {
+                *reinterpret_cast<uint4*>(kq + j0) = *reinterpret_cast<const uint4*>(s_k + j0);
+                *reinterpret_cast<uint4*>(vq + j0) = *reinterpret_cast<const uint4*>(s_v + j0);
+                if (WIDE) *reinterpret_cast<uint2*>(mq + j0) = *reinterpret_cast<const uint2*>(s_m + j0);
+            } else {
+                for (uint32_t j = j0; j < j0 + 4; ++j)
+                    if (j >= sh && j < end) { kq[j] = s_k[j]; vq[j] = s_v[j]; if (WIDE) mq[j] = s_m[j]; }
+            }
+        }
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// stable LSD radix pass on `bits` key bits at `shift`.  A 256-thread block owns RADIX_CHUNK consecutive
-// pairs; wave w owns the w-th quarter and walks it in order, 64 pairs a step, ranking equal digits
+// stable LSD radix pass on `bits` key bits at `shift`.  A block of RADIX_WAVES waves owns RADIX_CHUNK = RADIX_WAVES x 1024 consecutive
+// pairs; wave w owns the w-th part and walks it in order, 64 pairs a step, ranking equal digits
 // with ballots, so equal keys keep their input order (= triangle submission order).  The chunk is
 // then reordered by digit in LDS and written out linearly, so global stores are contiguous runs
 // (RADIX_CHUNK / 2^bits pairs per digit on average) instead of 64 scattered 4-byte elements per
 // instruction.  hist layout: [digit][block] so one exclusive scan yields every block's base per digit.
+// A pair is its sort word (k_expand) and its triangle word; WIDE frames also move the 16-bit mask stream.  The last pass writes
+// what k_raster reads - triangle words and masks, no sort words - and the tile bounds (k_radix_scatter).
 // ---------------------------------------------------------------------------------------------
-constexpr int RADIX_CHUNK = 4096;
-constexpr int RADIX_WAVE_CHUNK = RADIX_CHUNK / 4;
-constexpr int RADIX_ROUNDS = RADIX_WAVE_CHUNK / 64;      // 16
+// A block has RADIX_WAVES waves: 8 (8192 pairs, 74 KB of LDS, two blocks per CU) when the pair buffers hold at least
+// RADIX_BIG_CAP pairs, else 4 (4096 pairs, four blocks per CU).  8 waves give runs of 64 pairs per digit at 7-bit digits; measured
+// against 4 on the 4096^2 frame (18 M pairs): first pass 94 -> 85 us, last pass 107 -> 101 us, row scans 8 -> 5 us.  On the head frames
+// (C2 / C3, a few hundred thousand pairs: under 100 blocks of 8192 for 256 CUs) 8 waves made the binning 4 us slower.
+constexpr int RADIX_ROUNDS = 16;
+constexpr int RADIX_WAVE_CHUNK = RADIX_ROUNDS * 64;      // 1024
+constexpr uint32_t RADIX_BIG_CAP = 4u << 20;
 constexpr int RADIX_MAX_BITS = 8;
 
-// four consecutive keys with one load (the pair buffers hold a multiple of 4 entries and p is a multiple of 4)
-template <typename K> __device__ __forceinline__ void load4(const K* __restrict__ keys, uint64_t p, uint32_t k[4]);
-template <> __device__ __forceinline__ void load4<uint32_t>(const uint32_t* __restrict__ keys, uint64_t p, uint32_t k[4]) {
-    const uint4 q = *reinterpret_cast<const uint4*>(keys + p);
-    k[0] = q.x; k[1] = q.y; k[2] = q.z; k[3] = q.w;
-}
-template <> __device__ __forceinline__ void load4<uint16_t>(const uint16_t* __restrict__ keys, uint64_t p, uint32_t k[4]) {
-    const uint2 q = *reinterpret_cast<const uint2*>(keys + p);
-    k[0] = q.x & 0xffffu; k[1] = q.x >> 16; k[2] = q.y & 0xffffu; k[3] = q.y >> 16;
-}
-
-template <typename K>
-__global__ __launch_bounds__(256) void k_radix_hist(const K* __restrict__ keys, const unsigned long long* __restrict__ pairs_total,
-                                                    uint32_t cap, int shift, int bits,
+__global__ __launch_bounds__(256) void k_radix_hist(const uint32_t* __restrict__ keys, const unsigned long long* __restrict__ pairs_total,
+                                                    uint32_t cap, int shift, int bits, uint32_t chunk,
                                                     uint32_t nblocks, uint32_t* __restrict__ hist) {
     __shared__ uint32_t s_cnt[1 << RADIX_MAX_BITS];
     const unsigned long long P64 = *pairs_total;
@@ -461,13 +474,13 @@ __global__ __launch_bounds__(256) void k_radix_hist(const K* __restrict__ keys, 
     const uint32_t nb = 1u << bits, mask = nb - 1;
     for (uint32_t b = threadIdx.x; b < nb; b += 256) s_cnt[b] = 0;
     __syncthreads();
-    const uint64_t beg = (uint64_t)blockIdx.x * RADIX_CHUNK;
-    uint64_t end = beg + RADIX_CHUNK; if (end > P) end = P;      // blocks past the last pair (the grid covers the capacity) add zeros
+    const uint64_t beg = (uint64_t)blockIdx.x * chunk;
+    uint64_t end = beg + chunk; if (end > P) end = P;      // blocks past the last pair (the grid covers the capacity) add zeros
     for (uint64_t p = beg + 4u * threadIdx.x; p < end; p += 1024) {
-        uint32_t k[4];
-        load4<K>(keys, p, k);
+        const uint4 q = *reinterpret_cast<const uint4*>(keys + p);   // (the pair buffers hold a multiple of 4 entries, p is one too)
+        const uint32_t k[4] = { q.x, q.y, q.z, q.w };
 #pragma unroll
-        for (int q = 0; q < 4; ++q) if (p + q < end) atomicAdd(&s_cnt[(k[q] >> shift) & mask], 1u);
+        for (int j = 0; j < 4; ++j) if (p + j < end) atomicAdd(&s_cnt[(k[j] >> shift) & mask], 1u);
     }
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < nb; b += 256) hist[(size_t)b * nblocks + blockIdx.x] = s_cnt[b];
@@ -503,26 +516,35 @@ __global__ __launch_bounds__(ROWSCAN_THREADS) void k_radix_scan_rows(uint32_t* _
     if (threadIdx.x == 0) totals[blockIdx.x] = running;
 }
 
-template <typename K>
-__global__ __launch_bounds__(256) void k_radix_scatter(const K* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
-                                                       const uint16_t* __restrict__ msk_in,
-                                                       const unsigned long long* __restrict__ pairs_total, uint32_t cap,
-                                                       int shift, int bits, uint32_t nblocks,
-                                                       const uint32_t* __restrict__ base, const uint32_t* __restrict__ totals,
-                                                       K* __restrict__ keys_out, uint32_t* __restrict__ vals_out, uint16_t* __restrict__ msk_out) {
-    __shared__ uint32_t s_cnt[4][1 << RADIX_MAX_BITS];     // per wave: running count, then (after phase 2) local start
+// LAST: the pass that leaves the list k_raster reads.  It writes the triangle words and the 16-bit masks only (the sort words are not
+// needed behind it) and the tile bounds: in the sorted chunk every run of one tile id is a run of consecutive positions of the
+// output, and a tile's slice is the union of its runs over the blocks, so each run takes its first position into tile_start[key]
+// (atomicMin; k_chunk_spine sets it to ~0) and its end into tile_end[key] (atomicMax; set to 0).  That is two atomics per run - about
+// 128 per block - where k_bounds read the whole sorted key list again.
+template <int RADIX_WAVES, bool WIDE, bool LAST>
+__global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+                                                                 const uint16_t* __restrict__ msk_in,
+                                                                 const unsigned long long* __restrict__ pairs_total, uint32_t cap,
+                                                                 int shift, int bits, uint32_t nblocks,
+                                                                 const uint32_t* __restrict__ base, const uint32_t* __restrict__ totals,
+                                                                 uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
+                                                                 uint16_t* __restrict__ msk_out,
+                                                                 uint32_t* __restrict__ tile_start, uint32_t* __restrict__ tile_end) {
+    constexpr int RADIX_THREADS = RADIX_WAVES * 64, RADIX_CHUNK = RADIX_WAVES * RADIX_WAVE_CHUNK;
+    __shared__ uint32_t s_cnt[RADIX_WAVES][1 << RADIX_MAX_BITS];     // per wave: running count, then (after phase 2) local start
     __shared__ uint32_t s_start[1 << RADIX_MAX_BITS];      // first local position of each digit in the chunk
     __shared__ uint32_t s_gbase[1 << RADIX_MAX_BITS];      // global position of the chunk's first pair of each digit
     __shared__ uint32_t s_val[RADIX_CHUNK];
-    __shared__ K s_key[RADIX_CHUNK];
-    __shared__ uint16_t s_msk[RADIX_CHUNK];
+    __shared__ uint32_t s_key[RADIX_CHUNK];
+    __shared__ uint16_t s_msk[WIDE ? RADIX_CHUNK : 2];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const unsigned long long P64 = *pairs_total;
     const uint32_t P = P64 > cap ? 0u : (uint32_t)P64;
     if ((uint64_t)blockIdx.x * RADIX_CHUNK >= P) return;     // the grid covers the capacity of the buffers, not the pairs of this flush
     const uint32_t nb = 1u << bits, mask = nb - 1;
-    for (uint32_t b = threadIdx.x; b < nb; b += 256) {
-        s_cnt[0][b] = 0; s_cnt[1][b] = 0; s_cnt[2][b] = 0; s_cnt[3][b] = 0;
+    for (uint32_t b = threadIdx.x; b < nb; b += RADIX_THREADS) {
+#pragma unroll
+        for (int ww = 0; ww < RADIX_WAVES; ++ww) s_cnt[ww][b] = 0;
         s_gbase[b] = base[(size_t)b * nblocks + blockIdx.x];      // pairs of this digit in the blocks before this one (k_radix_scan_rows)
     }
     if (w == 0) {       // + the pairs of all smaller digits: exclusive scan of the row totals (nb <= 256: up to 4 digits per lane)
@@ -536,7 +558,7 @@ __global__ __launch_bounds__(256) void k_radix_scatter(const K* __restrict__ key
         for (int q = 0; q < 4; ++q) { const uint32_t d = lane * 4 + q; if (d < nb) s_start[d] = ex; ex += tot[q]; }
     }
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < nb; b += 256) s_gbase[b] += s_start[b];
+    for (uint32_t b = threadIdx.x; b < nb; b += RADIX_THREADS) s_gbase[b] += s_start[b];
     __syncthreads();
     const uint64_t cbeg = (uint64_t)blockIdx.x * RADIX_CHUNK;
     uint64_t cend = cbeg + RADIX_CHUNK; if (cend > P) cend = P;
@@ -544,15 +566,15 @@ __global__ __launch_bounds__(256) void k_radix_scatter(const K* __restrict__ key
     const uint64_t wbeg = cbeg + (uint64_t)w * RADIX_WAVE_CHUNK;
     const unsigned long long lt = (1ull << lane) - 1ull;
 
-    // ---- phase 1: stable rank of every pair among the equal digits of its wave's quarter ------------
-    // (key and block mask share a register: key in the low 16 bits when K is 16 bits wide; else the mask rides in its own)
+    // ---- phase 1: stable rank of every pair among the equal digits of its wave's part ------------
     uint32_t k[RADIX_ROUNDS], v[RADIX_ROUNDS], rk[RADIX_ROUNDS];
-    uint16_t mk[RADIX_ROUNDS];
+    uint16_t mk[WIDE ? RADIX_ROUNDS : 1];
 #pragma unroll
     for (int r = 0; r < RADIX_ROUNDS; ++r) {
         const uint64_t p = wbeg + (uint64_t)r * 64 + lane;
         const bool act = p < cend;
-        k[r] = act ? (uint32_t)keys_in[p] : 0; v[r] = act ? vals_in[p] : 0; mk[r] = act ? msk_in[p] : (uint16_t)0;
+        k[r] = act ? keys_in[p] : 0; v[r] = act ? vals_in[p] : 0;
+        if (WIDE) mk[WIDE ? r : 0] = act ? msk_in[p] : (uint16_t)0;
     }
 #pragma unroll
     for (int r = 0; r < RADIX_ROUNDS; ++r) {
@@ -578,7 +600,12 @@ __global__ __launch_bounds__(256) void k_radix_scatter(const K* __restrict__ key
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const uint32_t d = lane * 4 + q;
-            tot[q] = d < nb ? s_cnt[0][d] + s_cnt[1][d] + s_cnt[2][d] + s_cnt[3][d] : 0;
+            uint32_t t = 0;
+            if (d < nb) {
+#pragma unroll
+                for (int ww = 0; ww < RADIX_WAVES; ++ww) t += s_cnt[ww][d];
+            }
+            tot[q] = t;
             run += tot[q];
         }
         uint32_t inc = run;
@@ -588,52 +615,39 @@ __global__ __launch_bounds__(256) void k_radix_scatter(const K* __restrict__ key
         for (int q = 0; q < 4; ++q) { const uint32_t d = lane * 4 + q; if (d < nb) s_start[d] = ex; ex += tot[q]; }
     }
     __syncthreads();
-    for (uint32_t d = threadIdx.x; d < nb; d += 256) {
+    for (uint32_t d = threadIdx.x; d < nb; d += RADIX_THREADS) {
         uint32_t run = s_start[d];
 #pragma unroll
-        for (int ww = 0; ww < 4; ++ww) { const uint32_t c = s_cnt[ww][d]; s_cnt[ww][d] = run; run += c; }
+        for (int ww = 0; ww < RADIX_WAVES; ++ww) { const uint32_t c = s_cnt[ww][d]; s_cnt[ww][d] = run; run += c; }
     }
     __syncthreads();
-    // ---- phase 3: reorder in LDS ------------------------------------------------------------------------------
+    // ---- phase 3: reorder in LDS (4-byte words: lanes of one digit write consecutive banks) ---------------------------
 #pragma unroll
     for (int r = 0; r < RADIX_ROUNDS; ++r) {
         if (wbeg + (uint64_t)r * 64 + lane < cend) {
             const uint32_t dgt = (k[r] >> shift) & mask;
             const uint32_t lp = s_cnt[w][dgt] + rk[r];
-            s_key[lp] = (K)k[r]; s_val[lp] = v[r]; s_msk[lp] = mk[r];
+            s_key[lp] = k[r]; s_val[lp] = v[r];
+            if (WIDE) s_msk[lp] = mk[WIDE ? r : 0];
         }
     }
     __syncthreads();
     // ---- phase 4: linear read-out, contiguous global runs per digit ------------------------------------------
-    for (uint32_t i = threadIdx.x; i < n_chunk; i += 256) {
-        const uint32_t key = s_key[i];
-        const uint32_t dgt = (key >> shift) & mask;
+    constexpr uint32_t KEY_MASK = WIDE ? 0xffffffffu : 0xffffu;
+    for (uint32_t i = threadIdx.x; i < n_chunk; i += RADIX_THREADS) {
+        const uint32_t word = s_key[i];
+        const uint32_t dgt = (word >> shift) & mask;
         const uint32_t dst = s_gbase[dgt] + (i - s_start[dgt]);
-        keys_out[dst] = (K)key; vals_out[dst] = s_val[i]; msk_out[dst] = s_msk[i];
-    }
-}
-
-// per-tile slice [start, end) of the sorted pair list: four consecutive pairs per thread (one load)
-template <typename K>
-__global__ __launch_bounds__(256) void k_bounds(const K* __restrict__ keys, const unsigned long long* __restrict__ pairs_total, uint32_t cap,
-                                                uint32_t* __restrict__ tile_start, uint32_t* __restrict__ tile_end) {
-    const unsigned long long P64 = *pairs_total;
-    const uint32_t P = P64 > cap ? 0u : (uint32_t)P64;
-    const uint32_t p0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4u;
-    if (p0 >= P) return;
-    uint32_t k[4];
-    load4<K>(keys, p0, k);                                              // the buffers hold a multiple of 4 entries (pair_capacity)
-    uint32_t prev = p0 ? (uint32_t)keys[p0 - 1] : 0u;
-    const uint32_t after = (p0 + 4 < P) ? (uint32_t)keys[p0 + 4] : 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t p = p0 + (uint32_t)i;
-        if (p < P) {
-            const uint32_t next = i < 3 ? k[i + 1] : after;
-            if (p == 0 || prev != k[i]) tile_start[k[i]] = p;
-            if (p == P - 1 || next != k[i]) tile_end[k[i]] = p + 1;
+        vals_out[dst] = s_val[i];
+        if (!LAST) {
+            keys_out[dst] = word;
+            if (WIDE) msk_out[dst] = s_msk[i];
+        } else {
+            msk_out[dst] = WIDE ? s_msk[i] : (uint16_t)(word >> 16);
+            const uint32_t key = word & KEY_MASK;
+            if (i == 0 || (s_key[i - 1] & KEY_MASK) != key) atomicMin(&tile_start[key], dst);
+            if (i + 1 == n_chunk || (s_key[i + 1] & KEY_MASK) != key) atomicMax(&tile_end[key], dst + 1);
         }
-        prev = k[i];
     }
 }
 
@@ -652,49 +666,51 @@ void launch_setup(hipStream_t s, const FrameParams& fp, const DrawDesc& draw, Dr
 }
 
 void launch_chunk_spine(hipStream_t s, const uint32_t* blk_sums, uint32_t nblk, uint32_t* chunk_off, unsigned long long* total64, unsigned long long* host_copy,
-                        void* zero, size_t zero_bytes) {
-    hipLaunchKernelGGL(k_chunk_spine, dim3(1), dim3(SPINE_THREADS), 0, s, blk_sums, nblk, chunk_off, total64, host_copy, (uint4*)zero, (uint32_t)(zero_bytes / 16));
+                        uint32_t* tile_bounds, size_t half_words) {
+    hipLaunchKernelGGL(k_chunk_spine, dim3(1), dim3(SPINE_THREADS), 0, s, blk_sums, nblk, chunk_off, total64, host_copy, (uint4*)tile_bounds,
+                       (uint32_t)(half_words / 4));
 }
 
 void launch_expand(hipStream_t s, const FrameParams& fp, uint32_t first, uint32_t n, int tiles_x, const uint32_t* cnt, const uint32_t* blk_sums,
-                   const uint32_t* chunk_off, uint32_t blk_base, const uint2* tilebox, void* keys, bool key16, uint32_t* vals, uint16_t* bmask,
+                   const uint32_t* chunk_off, uint32_t blk_base, const uint2* tilebox, uint32_t* keys, bool wide, uint32_t* vals, uint16_t* bmask,
                    const unsigned long long* pairs_total, uint32_t cap) {
     if (!n) return;
-    if (key16)
-        hipLaunchKernelGGL(k_expand<uint16_t>, dim3(setup_num_blocks(n)), dim3(SETUP_THREADS), 0, s, fp, first, n, tiles_x, cnt, blk_sums, chunk_off,
-                           blk_base, tilebox, (uint16_t*)keys, vals, bmask, pairs_total, cap);
+    if (wide)
+        hipLaunchKernelGGL(k_expand<true>, dim3(setup_num_blocks(n)), dim3(SETUP_THREADS), 0, s, fp, first, n, tiles_x, cnt, blk_sums, chunk_off,
+                           blk_base, tilebox, keys, vals, bmask, pairs_total, cap);
     else
-        hipLaunchKernelGGL(k_expand<uint32_t>, dim3(setup_num_blocks(n)), dim3(SETUP_THREADS), 0, s, fp, first, n, tiles_x, cnt, blk_sums, chunk_off,
-                           blk_base, tilebox, (uint32_t*)keys, vals, bmask, pairs_total, cap);
+        hipLaunchKernelGGL(k_expand<false>, dim3(setup_num_blocks(n)), dim3(SETUP_THREADS), 0, s, fp, first, n, tiles_x, cnt, blk_sums, chunk_off,
+                           blk_base, tilebox, keys, vals, bmask, pairs_total, cap);
 }
 
-uint32_t radix_num_workers(uint32_t P) { return (uint32_t)(((uint64_t)P + RADIX_CHUNK - 1) / RADIX_CHUNK); }   // = blocks of a pass
+static uint32_t radix_waves(uint32_t cap) { return cap >= RADIX_BIG_CAP ? 8u : 4u; }
+// blocks of a pass over pair buffers of capacity `cap`
+uint32_t radix_num_workers(uint32_t cap) { const uint64_t chunk = radix_waves(cap) * RADIX_WAVE_CHUNK; return (uint32_t)((cap + chunk - 1) / chunk); }
 
 // The pair count of the flush stays on the device (`pairs_total`): grids cover `cap`, the capacity of the pair buffers,
 // and blocks past the last pair do nothing, so the host never has to wait for the count before it can queue these.
-template <typename K>
-static void radix_pass_t(hipStream_t s, const K* keys_in, const uint32_t* vals_in, const uint16_t* msk_in, K* keys_out, uint32_t* vals_out, uint16_t* msk_out,
-                         const unsigned long long* pairs_total, uint32_t cap, int shift, int bits, uint32_t* hist, uint32_t* scan_tmp) {
-    uint32_t nblk = radix_num_workers(cap);
-    hipLaunchKernelGGL(k_radix_hist<K>, dim3(nblk), dim3(256), 0, s, keys_in, pairs_total, cap, shift, bits, nblk, hist);
-    hipLaunchKernelGGL(k_radix_scan_rows, dim3(1u << bits), dim3(ROWSCAN_THREADS), 0, s, hist, nblk, scan_tmp);
-    hipLaunchKernelGGL(k_radix_scatter<K>, dim3(nblk), dim3(256), 0, s, keys_in, vals_in, msk_in, pairs_total, cap, shift, bits, nblk, hist, scan_tmp,
-                       keys_out, vals_out, msk_out);
+template <int WAVES, bool WIDE, bool LAST>
+static void radix_pass_t(hipStream_t s, const RadixPass& ps, const unsigned long long* pairs_total, uint32_t cap, uint32_t* hist, uint32_t* scan_tmp) {
+    const uint32_t nblk = radix_num_workers(cap);
+    hipLaunchKernelGGL(k_radix_hist, dim3(nblk), dim3(256), 0, s, ps.keys_in, pairs_total, cap, ps.shift, ps.bits, (uint32_t)(WAVES * RADIX_WAVE_CHUNK),
+                       nblk, hist);
+    hipLaunchKernelGGL(k_radix_scan_rows, dim3(1u << ps.bits), dim3(ROWSCAN_THREADS), 0, s, hist, nblk, scan_tmp);
+    hipLaunchKernelGGL((k_radix_scatter<WAVES, WIDE, LAST>), dim3(nblk), dim3(WAVES * 64), 0, s, ps.keys_in, ps.vals_in, ps.msk_in, pairs_total, cap,
+                       ps.shift, ps.bits, nblk, hist, scan_tmp, ps.keys_out, ps.vals_out, ps.msk_out, ps.tile_start, ps.tile_end);
 }
 
-void launch_radix_pass(hipStream_t s, const void* keys_in, const uint32_t* vals_in, const uint16_t* msk_in, void* keys_out,
-                       uint32_t* vals_out, uint16_t* msk_out, bool key16, const unsigned long long* pairs_total, uint32_t cap, int shift, int bits,
+template <int WAVES>
+static void radix_pass_w(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
+                         uint32_t* hist, uint32_t* scan_tmp) {
+    if (wide) { if (last) radix_pass_t<WAVES, true, true>(s, ps, pairs_total, cap, hist, scan_tmp); else radix_pass_t<WAVES, true, false>(s, ps, pairs_total, cap, hist, scan_tmp); }
+    else { if (last) radix_pass_t<WAVES, false, true>(s, ps, pairs_total, cap, hist, scan_tmp); else radix_pass_t<WAVES, false, false>(s, ps, pairs_total, cap, hist, scan_tmp); }
+}
+
+void launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
                        uint32_t* hist, uint32_t* scan_tmp) {
     if (!cap) return;
-    if (key16) radix_pass_t<uint16_t>(s, (const uint16_t*)keys_in, vals_in, msk_in, (uint16_t*)keys_out, vals_out, msk_out, pairs_total, cap, shift, bits, hist, scan_tmp);
-    else radix_pass_t<uint32_t>(s, (const uint32_t*)keys_in, vals_in, msk_in, (uint32_t*)keys_out, vals_out, msk_out, pairs_total, cap, shift, bits, hist, scan_tmp);
-}
-
-void launch_bounds(hipStream_t s, const void* keys, bool key16, const unsigned long long* pairs_total, uint32_t cap,
-                   uint32_t* tile_start, uint32_t* tile_end) {
-    if (!cap) return;
-    if (key16) hipLaunchKernelGGL(k_bounds<uint16_t>, dim3((unsigned)(((uint64_t)cap + 1023) / 1024)), dim3(256), 0, s, (const uint16_t*)keys, pairs_total, cap, tile_start, tile_end);
-    else hipLaunchKernelGGL(k_bounds<uint32_t>, dim3((unsigned)(((uint64_t)cap + 1023) / 1024)), dim3(256), 0, s, (const uint32_t*)keys, pairs_total, cap, tile_start, tile_end);
+    if (radix_waves(cap) == 8) radix_pass_w<8>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp);
+    else radix_pass_w<4>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp);
 }
 
 }  // namespace trgl

@@ -1032,6 +1032,7 @@ __global__ __launch_bounds__(256) void k_make_items(FrameParams fp, const uint32
     if (k < ntiles_strip) {
         t = (uint32_t)(fp.strip_ty0 * fp.tiles_x + k);
         beg = tile_start[t]; end = tile_end[t];
+        if (end <= beg) beg = end = 0;         // an empty tile: the last radix pass leaves it at [~0, 0)
         const uint32_t n = end - beg;
         const int ty = (int)(t / (uint32_t)fp.tiles_x);
         if ((n || fp.init_from_clear) && tile_row_owned(fp, ty)) {

@@ -11,26 +11,32 @@ void launch_setup(hipStream_t s, const FrameParams& fp, const DrawDesc& draw, Dr
                   TriRec* recs, TriW* recs_w, uint32_t* cnt, uint2* tilebox, DevStats* stats, uint32_t* blk_sums, uint32_t blk_base);
 // chunk_off[c] = pairs before setup block 16c; *total64 = all pairs of the flush
 // (host_copy: pinned host memory that receives the pair count and the two counts behind it in DevStats)
-// zero, zero_bytes (a multiple of 16, 16-byte aligned): also cleared by the kernel (the tile bounds of the flush)
+// tile_bounds: tile_start followed by tile_end, `half_words` (a multiple of 4) each, 16-byte aligned; set to the empty bounds
+// the last radix pass starts from (tile_start ~0, tile_end 0)
 void launch_chunk_spine(hipStream_t s, const uint32_t* blk_sums, uint32_t nblk, uint32_t* chunk_off, unsigned long long* total64, unsigned long long* host_copy,
-                        void* zero, size_t zero_bytes);
+                        uint32_t* tile_bounds, size_t half_words);
 
 
-// expand / radix / bounds read the flush's pair count from device memory and cover `cap` (the capacity of the pair buffers)
+// expand / radix read the flush's pair count from device memory and cover `cap` (the capacity of the pair buffers)
 // with their grids; they do nothing when the count exceeds it (the host then grows the buffers and queues them again)
+// wide: the frame has more than 65536 tiles.  Else a pair's sort word holds the 16-bit tile id in its low half and the 4x4 block
+// mask in its high half, and `bmask` is only written by the last radix pass; wide frames sort 32-bit tile ids and carry the mask
+// in `bmask` from k_expand on.
 void launch_expand(hipStream_t s, const FrameParams& fp, uint32_t first, uint32_t n, int tiles_x, const uint32_t* cnt, const uint32_t* blk_sums,
-                   const uint32_t* chunk_off, uint32_t blk_base, const uint2* tilebox, void* keys, bool key16, uint32_t* vals, uint16_t* bmask,
+                   const uint32_t* chunk_off, uint32_t blk_base, const uint2* tilebox, uint32_t* keys, bool wide, uint32_t* vals, uint16_t* bmask,
                    const unsigned long long* pairs_total, uint32_t cap);
 
-uint32_t radix_num_workers(uint32_t P);
-// key16: the keys (tile indices) are 16-bit words (frames of at most 65536 tiles), else 32-bit
-// (the 4x4 block mask of every pair travels with it)
-void launch_radix_pass(hipStream_t s, const void* keys_in, const uint32_t* vals_in, const uint16_t* msk_in, void* keys_out,
-                       uint32_t* vals_out, uint16_t* msk_out, bool key16, const unsigned long long* pairs_total, uint32_t cap, int shift, int bits,
+uint32_t radix_num_workers(uint32_t cap);      // blocks of a radix pass over pair buffers of capacity `cap` (4 or 8 waves each)
+// one stable pass on `bits` bits of the tile id at `shift`.  The last pass writes vals_out and msk_out (what the raster reads, no sort
+// words) and the per-tile slices [tile_start, tile_end) of the sorted list; the others write keys_out, vals_out (and msk_out when wide).
+struct RadixPass {
+    const uint32_t* keys_in; const uint32_t* vals_in; const uint16_t* msk_in;
+    uint32_t* keys_out; uint32_t* vals_out; uint16_t* msk_out;
+    uint32_t* tile_start; uint32_t* tile_end;
+    int shift, bits;
+};
+void launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
                        uint32_t* hist, uint32_t* scan_tmp);
-
-void launch_bounds(hipStream_t s, const void* keys, bool key16, const unsigned long long* pairs_total, uint32_t cap,
-                   uint32_t* tile_start, uint32_t* tile_end);
 
 uint32_t owned_tiles(const FrameParams& fp);       // tiles of the rows this context owns (strip or interleaved bands)
 uint32_t raster_max_items(const FrameParams& fp);   // work items (workgroups of k_raster) of a flush, at most

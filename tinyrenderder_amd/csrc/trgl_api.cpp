@@ -46,7 +46,7 @@ template <class T> struct DevBuf {
     int grow(trgl_ctx* c, size_t need, size_t ncap) { return need <= cap ? TRGL_OK : alloc(c, ncap); }
     int grow(trgl_ctx* c, size_t need) { return grow(c, need, headroom(need)); }
 };
-// ... and of the pair buffers: a multiple of 4 entries (k_bounds reads 16 bytes at a time), at most 0xffffe000 (grids are sized by
+// ... and of the pair buffers: a multiple of 4 entries (k_radix_hist reads 16 bytes at a time, k_raster 4 entries), at most 0xffffe000 (grids are sized by
 // cap + 4095 in 32 bits; a flush of 2^32 - 16 pairs and more is refused)
 static size_t pair_capacity(size_t need) {
     const size_t ncap = (headroom(need) + 3) & ~size_t(3);
@@ -94,7 +94,7 @@ struct trgl_ctx {
     DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
     DevBuf<uint32_t> keys[2], vals[2]; DevBuf<uint16_t> bmask[2];     // (tile, triangle, block mask) pairs, ping-pong; grown together
     DevBuf<uint32_t> hist, scan_tmp;
-    DevBuf<uint32_t> tile_start;        // tile_start[ntiles] followed by tile_end[ntiles]: cleared together per flush (in 16-byte words)
+    DevBuf<uint32_t> tile_start;        // tile_start[bounds_half()] followed by tile_end[bounds_half()]: set together per flush (in 16-byte words)
     DevBuf<uint4> items; DevBuf<uint32_t> n_items;
     DevBuf<unsigned long long> item_stats;
     DevBuf<DrawDesc> draws_dev;
@@ -113,7 +113,8 @@ struct trgl_ctx {
 
     std::string err;
 
-    uint32_t* tile_end() const { return tile_start.p + (size_t)tiles_x * tiles_y; }
+    size_t bounds_half() const { return ((size_t)tiles_x * tiles_y + 3) & ~size_t(3); }
+    uint32_t* tile_end() const { return tile_start.p + bounds_half(); }
 };
 
 #define HIPCHK(ctx, expr)                                                                      \
@@ -168,13 +169,13 @@ static int flush_sync(trgl_ctx* c) {
 
 // the stream, the fixed-size buffers, the events and the initial state of a new context
 static int init_ctx(trgl_ctx* c) {
-    const size_t npx = (size_t)c->W * c->H, ntiles = (size_t)c->tiles_x * c->tiles_y;
+    const size_t npx = (size_t)c->W * c->H;
     HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
     int r;
     if ((r = c->fb.alloc(c, npx * c->bpp)) || (r = c->zb.alloc(c, npx)) || (r = c->tex_dev.alloc(c, TRGL_MAX_TEXTURES))) return r;
     HIPCHK(c, hipMemset(c->tex_dev.p, 0, sizeof(c->tex_host)));
-    if ((r = c->tile_start.alloc(c, ntiles * 2 + 4))) return r;
+    if ((r = c->tile_start.alloc(c, c->bounds_half() * 2 + 4))) return r;
     if ((r = c->n_items.alloc(c, 2))) return r;                    // work items of the flush
     HIPCHK(c, hipMemset(c->n_items.p, 0, 8));                       // k_fold_stats leaves it at 0 for the next flush
     if ((r = c->draws_dev.alloc(c, TRGL_MAX_DRAWS)) || (r = c->stats_dev.alloc(c, 1))) return r;
@@ -469,17 +470,17 @@ int trgl_flush(trgl_ctx* c) {
     return r ? r : trgl_flush_end(c);
 }
 
-// expand -> stable radix passes by tile id -> per-tile bounds, for pair buffers of capacity `cap`.  All of it reads the pair
-// count from device memory; when the count exceeds `cap` every kernel here does nothing.
+// expand -> stable radix passes by tile id, the last of which leaves the per-tile bounds, for pair buffers of capacity `cap`.  All of
+// it reads the pair count from device memory; when the count exceeds `cap` every kernel here does nothing.
 static int queue_binning(trgl_ctx* c, const FrameParams& fp, uint32_t cap, int* cur_out) {
     hipStream_t s = c->stream;
     const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
     const unsigned long long* pairs_dev = &c->stats_dev.p->pairs_total;
     int r;
     uint32_t blk_base = 0;
-    const bool key16 = ntiles <= 65536;        // tile indices as 16-bit keys: a third less traffic in every binning kernel
+    const bool wide = ntiles > 65536;          // else tile id and block mask share one 32-bit sort word
     for (auto& d : c->draws) {
-        launch_expand(s, fp, d.first, d.n, c->tiles_x, c->cnt.p, c->blk_sums.p, c->chunk_off.p, blk_base, c->tilebox.p, c->keys[0].p, key16, c->vals[0].p,
+        launch_expand(s, fp, d.first, d.n, c->tiles_x, c->cnt.p, c->blk_sums.p, c->chunk_off.p, blk_base, c->tilebox.p, c->keys[0].p, wide, c->vals[0].p,
                       c->bmask[0].p, pairs_dev, cap);
         blk_base += setup_num_blocks(d.n);
     }
@@ -491,11 +492,11 @@ static int queue_binning(trgl_ctx* c, const FrameParams& fp, uint32_t cap, int* 
     if ((r = c->scan_tmp.grow(c, 256 + 16))) return r;   // the digit totals of a pass (k_radix_scan_rows)
     int cur = 0;
     for (int ps = 0; ps < passes; ++ps) {
-        launch_radix_pass(s, c->keys[cur].p, c->vals[cur].p, c->bmask[cur].p, c->keys[cur ^ 1].p, c->vals[cur ^ 1].p, c->bmask[cur ^ 1].p, key16, pairs_dev, cap,
-                          ps * bits_per, bits_per, c->hist.p, c->scan_tmp.p);
+        const RadixPass rp{ c->keys[cur].p, c->vals[cur].p, c->bmask[cur].p, c->keys[cur ^ 1].p, c->vals[cur ^ 1].p, c->bmask[cur ^ 1].p,
+                            c->tile_start.p, c->tile_end(), ps * bits_per, bits_per };
+        launch_radix_pass(s, rp, wide, ps == passes - 1, pairs_dev, cap, c->hist.p, c->scan_tmp.p);
         cur ^= 1;
     }
-    launch_bounds(s, c->keys[cur].p, key16, pairs_dev, cap, c->tile_start.p, c->tile_end());
     *cur_out = cur;
     return TRGL_OK;
 }
@@ -539,7 +540,6 @@ int trgl_flush_begin(trgl_ctx* c) {
     int r;
     if ((r = resolve_events(c))) return r;
     const uint64_t N = c->queued_tris;
-    const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
     hipStream_t s = c->stream;
     FrameParams fp = frame_params(c);
 
@@ -579,15 +579,15 @@ int trgl_flush_begin(trgl_ctx* c) {
             }
         }
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], s));
-        // (+ literal_tris, large_tris into pinned memory; the kernel also clears tile_start and tile_end)
+        // (+ literal_tris, large_tris into pinned memory; the kernel also sets tile_start and tile_end to empty bounds)
         launch_chunk_spine(s, c->blk_sums.p, nblk, c->chunk_off.p, &c->stats_dev.p->pairs_total, &c->stats_pinned->pairs_total,
-                           c->tile_start.p, (ntiles * 8 + 15) & ~size_t(15));
+                           c->tile_start.p, c->bounds_half());
         HIPCHK(c, hipEventRecord(c->ev_pairs, s));
         cap = (uint32_t)c->keys[0].cap;
         if ((r = queue_binning(c, fp, cap, &cur))) return r;
     } else {
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], s));
-        HIPCHK(c, hipMemsetAsync(c->tile_start.p, 0, ntiles * 8, s));
+        HIPCHK(c, hipMemsetAsync(c->tile_start.p, 0, c->bounds_half() * 8, s));
     }
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], s));
     c->rp.active = true; c->rp.fp = fp; c->rp.flush_kind = flush_kind; c->rp.cap = cap; c->rp.cur = cur; c->rp.N = N;

@@ -7,8 +7,9 @@
 //   recs_w  TriW   [N]              1/w of the vertices, for draws whose fragments need perspective-correct barycentrics
 //   cnt/off uint32 [N]              tiles overlapped per triangle and its exclusive scan
 //   keys/vals/bmask [P] x2          (tile id, triangle id, 4x4 mask of the tile's blocks the bbox reaches) triples, ping-pong
-//                                   for the radix passes
-//   tile_start/tile_end uint32[T]   per-tile slice of the sorted pair list
+//                                   for the radix passes; up to 65536 tiles a key word holds the tile id in its low 16 bits and the
+//                                   mask in its high 16, and only the last pass writes bmask
+//   tile_start/tile_end uint32[T]   per-tile slice of the sorted pair list (an empty tile: end <= start)
 #pragma once
 #include <limits.h>
 #include <stddef.h>
