@@ -1,8 +1,9 @@
 """ctypes binding of the CPU oracle (oracle/libtrgl_oracle.so) — TEST INFRASTRUCTURE, NOT PRODUCT.
 
 Importable only from tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.
-Also holds the writer/runner for oracle/_ref/ref_harness (the reference's own rasterize() compiled
-in place from /root/reference; exists only in the build container).
+Also holds the writers/runners for oracle/_ref/ref_harness (the reference's own rasterize() compiled in place from the
+reference tree) and oracle/_ref/ref_shaders (the same plus the reference's own main.cpp shaders, vertex stage, z-buffer
+image and SSAO, and model.cpp samplers); both exist only where the reference tree does.
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libtrgl_oracle.so")
 REF_HARNESS = os.path.join(HERE, "_ref", "ref_harness")
 REF_HARNESS_FAST = os.path.join(HERE, "_ref", "ref_harness_fast")   # -O3 -DNDEBUG build, for cpu_baseline timing
+REF_SHADERS = os.path.join(HERE, "_ref", "ref_shaders")             # the reference's own PhongShader / EyeShader
 
 MAX_TEXTURES = 16
 FLAT, GOURAUD, PHONG, EYE, CHECKER = 0, 1, 2, 3, 4
@@ -150,7 +152,7 @@ class Oracle:
 # reference harness (build container only)
 # ---------------------------------------------------------------------------------------------
 def ref_available() -> bool:
-    return os.path.exists(REF_HARNESS)
+    return os.path.exists(REF_HARNESS) and os.path.exists(REF_SHADERS)
 
 
 def _pad8(b: bytes) -> bytes:
@@ -195,15 +197,22 @@ def parse_stats_line(line: str):
 def run_reference(width, height, bpp, viewport, draws, textures=None, clear_bgra=(0, 0, 0, 255), z_clear=np.inf,
                   harness=None, with_time=False):
     """Render with the reference's own rasterize(); returns (fb[h,w,bpp] u8, z[h,w] f64, stats line)
-    [+ seconds spent in the rasterize() loops when with_time]."""
+    [+ seconds spent in the rasterize() loops when with_time].  A scene with a PHONG or EYE draw goes to ref_shaders (the
+    reference's own PhongShader / EyeShader), any other to ref_harness, unless `harness` names one."""
+    if harness is None:
+        harness = REF_SHADERS if any(d[0] in (PHONG, EYE) for d in draws) else REF_HARNESS
     with tempfile.TemporaryDirectory() as d:
         sp, op = os.path.join(d, "scene.bin"), os.path.join(d, "out.bin")
         write_scene(sp, width, height, bpp, viewport, draws, textures, clear_bgra, z_clear)
-        subprocess.run([harness or REF_HARNESS, "scene", sp, op], check=True)
+        subprocess.run([harness, "scene", sp, op], check=True)
         raw = open(op, "rb").read()
+    return _parse_frame(raw, 0, width, height, bpp, with_time)
+
+
+def _parse_frame(raw, off, width, height, bpp, with_time=False):
     nfb = width * height * bpp
-    fb = np.frombuffer(raw, np.uint8, nfb).reshape(height, width, bpp).copy()
-    off = (nfb + 7) & ~7
+    fb = np.frombuffer(raw, np.uint8, nfb, off).reshape(height, width, bpp).copy()
+    off += (nfb + 7) & ~7
     z = np.frombuffer(raw, np.float64, width * height, off).reshape(height, width).copy()
     off += width * height * 8
     (ln,) = struct.unpack_from("<i", raw, off)
@@ -327,3 +336,105 @@ def run_reference_sample2d(texels, uv):
         subprocess.run([REF_HARNESS, "sample2d", ip, op], check=True)
         raw = np.frombuffer(open(op, "rb").read(), np.uint8).reshape(-1, 8)
     return raw[:, :5].copy()
+
+
+# ---- oracle/_ref/ref_shaders: the reference's own main.cpp / model.cpp code (build container only) ----------------------------
+def _write_textures(f, textures):
+    for slot, t in textures.items():
+        t = np.ascontiguousarray(t, np.uint8)
+        if t.ndim == 2:
+            t = t[..., None]
+        f.write(struct.pack("<4i", slot, t.shape[1], t.shape[0], t.shape[2]))
+        f.write(_pad8(t.tobytes()))
+
+
+def _run_ref_shaders(mode, payload: bytes) -> bytes:
+    with tempfile.TemporaryDirectory() as d:
+        ip, op = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        open(ip, "wb").write(payload)
+        subprocess.run([REF_SHADERS, mode, ip, op], check=True, stderr=subprocess.DEVNULL)
+        return open(op, "rb").read()
+
+
+def run_reference_fragments(textures, kinds, uniforms, varyings, bary):
+    """PhongShader / EyeShader ::fragment (main.cpp:92-170, 220-261) of the compiled reference, one call per row: kinds [n],
+    uniforms [n] (Uniforms), varyings [n, 24], bary [n, 3].  Returns [n, 5] uint8: bgra[4], bytespp."""
+    import io
+    varyings = np.ascontiguousarray(varyings, np.float64)
+    bary = np.ascontiguousarray(bary, np.float64)
+    f = io.BytesIO()
+    f.write(b"TRGFRG01" + struct.pack("<2i", len(textures), len(kinds)))
+    _write_textures(f, textures)
+    for i, k in enumerate(kinds):
+        f.write(struct.pack("<2i", int(k), 0) + bytes(uniforms[i]) + varyings[i].tobytes() + bary[i].tobytes())
+    raw = np.frombuffer(_run_ref_shaders("frag", f.getvalue()), np.uint8).reshape(-1, 8)
+    assert not raw[:, 5].any(), "a PHONG / EYE fragment discarded"
+    return raw[:, :5].copy()
+
+
+def fragments(textures, kinds, uniforms, varyings, bary):
+    """orc_fragment (the restatement) over the same rows as run_reference_fragments: [n, 5] uint8."""
+    tex = (Texture * MAX_TEXTURES)()
+    keep = []
+    for slot, t in textures.items():
+        t = np.ascontiguousarray(t, np.uint8)
+        t = t[..., None] if t.ndim == 2 else t
+        keep.append(t)
+        tex[slot] = Texture(t.ctypes.data, t.shape[1], t.shape[0], t.shape[2])
+    varyings = np.ascontiguousarray(varyings, np.float64)
+    bary = np.ascontiguousarray(bary, np.float64)
+    out = np.zeros((len(kinds), 5), np.uint8)
+    px = (C.c_uint8 * 4)()
+    L = lib()
+    for i, k in enumerate(kinds):
+        b = (C.c_double * 3)(*bary[i])
+        u = Uniforms.from_buffer_copy(bytes(uniforms[i]))
+        out[i, 4] = L.orc_fragment(int(k), C.byref(u), tex, varyings[i].ctypes.data, 0, b, px)
+        out[i, :4] = np.frombuffer(bytes(px), np.uint8)
+    return out
+
+
+def run_reference_lights(model_views, key, fill, rim):
+    """PhongShader::initLightDirections(key, fill, rim) and EyeShader::initLightDirections(key, rim) (main.cpp:55-69, 187-197)
+    of the compiled reference: model_views [n, 16], world directions [n, 3] each.  Returns [n, 15] f64: Phong key, fill, rim,
+    Eye key, rim (eye space)."""
+    mv = np.ascontiguousarray(model_views, np.float64).reshape(-1, 16)
+    rows = np.concatenate([mv, np.asarray(key, np.float64), np.asarray(fill, np.float64), np.asarray(rim, np.float64)], 1)
+    raw = _run_ref_shaders("lights", struct.pack("<2i", rows.shape[0], 0) + np.ascontiguousarray(rows).tobytes())
+    return np.frombuffer(raw, np.float64).reshape(-1, 15).copy()
+
+
+def run_reference_mesh(width, height, bpp, kind, viewport, projection, uniforms, vertices, indices, textures=None):
+    """A mesh through the reference's Model::load (via the Assimp stand-ins) and shader.vertex(f, v) for every face
+    (main.cpp:71-90 / 199-218), then rasterize() of each face as main.cpp:692-698.  vertices [nv, 8] float32 (position,
+    normal, uv), indices [nf, 3].  Returns (clip [nf, 12], varyings [nf, 24], fb, z, stats line)."""
+    import io
+    textures = textures or {}
+    v = np.ascontiguousarray(vertices, np.float32)
+    idx = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+    f = io.BytesIO()
+    f.write(b"TRGMSH01" + struct.pack("<8i", width, height, bpp, kind, len(textures), v.shape[0], idx.shape[0], 0))
+    f.write(np.asarray(viewport, np.float64).reshape(16).tobytes() + np.asarray(projection, np.float64).reshape(16).tobytes())
+    f.write(bytes(uniforms))
+    _write_textures(f, textures)
+    f.write(v.tobytes() + idx.tobytes())
+    raw = _run_ref_shaders("mesh", f.getvalue())
+    nf = idx.shape[0]
+    clip = np.frombuffer(raw, np.float64, nf * 12).reshape(nf, 12).copy()
+    vary = np.frombuffer(raw, np.float64, nf * 24, nf * 96).reshape(nf, 24).copy()
+    fb, z, line = _parse_frame(raw, nf * 288, width, height, bpp)
+    return clip, vary, fb, z, line
+
+
+def run_reference_zbuffer_image(z):
+    """save_zbuffer_image (main.cpp:269-314) of the compiled reference, read back with TGAImage::read_tga_file: [h, w, 3] uint8."""
+    z = np.ascontiguousarray(z, np.float64); h, w = z.shape
+    raw = _run_ref_shaders("zimage", struct.pack("<2i", w, h) + z.tobytes())
+    return np.frombuffer(raw, np.uint8).reshape(h, w, 3).copy()
+
+
+def run_reference_ssao(z):
+    """compute_ssao_at (main.cpp:324-362) in the loop of main.cpp:756-763, compiled reference: [h, w, 3] uint8."""
+    z = np.ascontiguousarray(z, np.float64); h, w = z.shape
+    raw = _run_ref_shaders("ssao", struct.pack("<2i", w, h) + z.tobytes())
+    return np.frombuffer(raw, np.uint8).reshape(h, w, 3).copy()

@@ -2,7 +2,7 @@
 //
 // Drives the reference's own rasterize() (compiled, unmodified, from /root/reference/our_gl.cpp +
 // tgaimage.cpp where they lie — see oracle/Makefile; nothing of the reference is copied here) over
-// scene files written by tests/refharness.py, and dumps framebuffer, z-buffer and the
+// scene files written by oracle/orc.py, and dumps framebuffer, z-buffer and the
 // print_render_stats() line.  Used only in the build container to (1) validate the C restatement
 // oracle/trgl_oracle.c bit-for-bit and (2) generate the golden fixtures under tests/golden/.
 //
@@ -11,66 +11,23 @@
 //
 // Shaders here are IShader subclasses (our_gl.h:36-52):
 //   FLAT / GOURAUD / CHECKER are defined on the reference's own TGAColor (tgaimage.h:29-63); CHECKER is the one that discards;
-//   PHONG / EYE call the C restatement's fragment (orc_fragment): main.cpp cannot be compiled here
-//   (model.h includes Assimp), so those bodies are NOT pinned by this harness — what it pins for
-//   them is everything around the up-call: the perspective-correct bary handed to fragment(), the
-//   z-test order and TGAImage::set of the returned colour.
+//   PHONG / EYE call the C restatement's fragment (orc_fragment).  This harness does not link main.cpp;
+//   the restated bodies are pinned by the second harness, oracle/ref_shaders.cpp, which does (against
+//   declaration-only Assimp stand-ins) and shades with the reference's own PhongShader / EyeShader.
+//   oracle/orc.py run_reference sends every scene with a PHONG or EYE draw there, so the goldens of
+//   such scenes come from the reference's shaders; ref_harness keeps FLAT / GOURAUD / CHECKER scenes
+//   and the restated up-call for direct comparison.
 // Mode "vecops" evaluates geometry.h / tgaimage.h value ops on given inputs so the restatement's
 // helpers can be compared with the real ones.
 
-#include "our_gl.h"          // from -I/root/reference
-#include "trgl_oracle.h"
-
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <vector>
+#include "ref_scene.h"
 
 namespace {
 
-struct Reader {
-    std::vector<unsigned char> buf; size_t pos = 0;
-    bool load(const char* path) {
-        std::ifstream in(path, std::ios::binary);
-        if (!in) return false;
-        buf.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
-        return true;
-    }
-    template <class T> T get() { T v; std::memcpy(&v, &buf[pos], sizeof(T)); pos += sizeof(T); return v; }
-    const unsigned char* take(size_t n) { const unsigned char* p = &buf[pos]; pos += n; return p; }
-    void align8() { pos = (pos + 7) & ~size_t(7); }
-};
+using refscene::Reader;
+using refscene::color_from_packed;
 
-TGAColor color_from_packed(uint32_t v) {
-    return TGAColor((uint8_t)((v >> 16) & 0xff), (uint8_t)((v >> 8) & 0xff), (uint8_t)(v & 0xff), (uint8_t)((v >> 24) & 0xff));
-}
-
-struct FlatShader : IShader {
-    TGAColor color;
-    std::pair<bool, TGAColor> fragment(const vec3) const override { return { false, color }; }
-};
-
-struct GouraudShader : IShader {
-    double intensity[3]; TGAColor base;
-    std::pair<bool, TGAColor> fragment(const vec3 bar) const override {
-        double i = intensity[0] * bar[0] + intensity[1] * bar[1] + intensity[2] * bar[2];
-        return { false, base * (float)i };      // TGAColor::operator*(float), tgaimage.h:55-62
-    }
-};
-
-// The discarding kind (include/trgl.h, TRGL_SHADER_CHECKER): exercises `if (discard) continue;` of the reference's rasterize()
-// (our_gl.cpp:187-188) - no depth write, no colour write, no counters for a discarded fragment.
-struct CheckerShader : IShader {
-    TGAColor color; int cells;
-    std::pair<bool, TGAColor> fragment(const vec3 bar) const override {
-        const int a = (int)(bar[0] * cells), c = (int)(bar[1] * cells);
-        return { ((a ^ c) & 1) != 0, color };
-    }
-};
-
+// PHONG / EYE through the C restatement's fragment (orc_fragment), for every triangle of the draw.
 struct RestatedFragShader : IShader {
     int kind; const trgl_uniforms* u; const orc_texture* tex; const double* vary;
     std::pair<bool, TGAColor> fragment(const vec3 bar) const override {
@@ -83,83 +40,17 @@ struct RestatedFragShader : IShader {
     }
 };
 
+struct RestatedLit {
+    RestatedFragShader rest; trgl_uniforms u;
+    void draw(int kind, const trgl_uniforms& uu, const std::vector<orc_texture>& tex) {
+        u = uu; rest.kind = kind; rest.u = &u; rest.tex = tex.data();
+    }
+    const IShader& triangle(const double* vary) { rest.vary = vary; return rest; }
+};
+
 int run_scene(const char* in_path, const char* out_path) {
-    Reader r;
-    if (!r.load(in_path)) { std::fprintf(stderr, "cannot read %s\n", in_path); return 2; }
-    if (std::memcmp(r.take(8), "TRGSCN01", 8) != 0) { std::fprintf(stderr, "bad magic\n"); return 2; }
-    int W = r.get<int32_t>(), H = r.get<int32_t>(), bpp = r.get<int32_t>();
-    int ndraws = r.get<int32_t>(), ntex = r.get<int32_t>(); r.get<int32_t>();
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) Viewport[i][j] = r.get<double>();
-    uint8_t clear[4]; std::memcpy(clear, r.take(4), 4); r.take(4);
-    double zclear = r.get<double>();
-
-    std::vector<orc_texture> tex(TRGL_MAX_TEXTURES, orc_texture{ nullptr, 0, 0, 0 });
-    for (int t = 0; t < ntex; ++t) {
-        int slot = r.get<int32_t>(), w = r.get<int32_t>(), h = r.get<int32_t>(), tb = r.get<int32_t>();
-        tex[slot] = orc_texture{ r.take((size_t)w * h * tb), w, h, tb };
-        r.align8();
-    }
-
-    TGAColor clear_color(clear, (uint8_t)4);
-    TGAImage framebuffer(W, H, bpp, clear_color);
-    init_zbuffer(W, H);
-    if (!(zclear == std::numeric_limits<double>::infinity()))
-        for (auto& z : zbuffer) z = zclear;
-
-    double raster_seconds = 0.0;      // time inside the per-triangle rasterize() loops only
-    for (int d = 0; d < ndraws; ++d) {
-        int kind = r.get<int32_t>(); r.get<int32_t>();
-        uint64_t n = r.get<uint64_t>();
-        trgl_uniforms u; std::memcpy(&u, r.take(sizeof(u)), sizeof(u));
-        const double* clip = (const double*)r.take(n * 12 * sizeof(double));
-        int K = kind == TRGL_SHADER_GOURAUD ? TRGL_VARY_GOURAUD : (kind == TRGL_SHADER_PHONG || kind == TRGL_SHADER_EYE) ? 24 : 0;
-        const double* vary = (const double*)r.take(n * K * sizeof(double));
-        const uint32_t* colors = (const uint32_t*)r.take(n * sizeof(uint32_t));
-        r.align8();
-
-        FlatShader flat; GouraudShader gour; RestatedFragShader rest; CheckerShader chk;
-        chk.cells = u.reserved;
-        rest.kind = kind; rest.u = &u; rest.tex = tex.data();
-        auto t0 = std::chrono::steady_clock::now();
-        for (uint64_t i = 0; i < n; ++i) {
-            vec4 tri[3];
-            for (int v = 0; v < 3; ++v) for (int c = 0; c < 4; ++c) tri[v][c] = clip[i * 12 + v * 4 + c];
-            if (kind == TRGL_SHADER_FLAT) {
-                flat.color = color_from_packed(colors[i]);
-                rasterize(tri, flat, framebuffer);
-            } else if (kind == TRGL_SHADER_CHECKER) {
-                chk.color = color_from_packed(colors[i]);
-                rasterize(tri, chk, framebuffer);
-            } else if (kind == TRGL_SHADER_GOURAUD) {
-                for (int v = 0; v < 3; ++v) gour.intensity[v] = vary[i * 3 + v];
-                gour.base = color_from_packed(colors[i]);
-                rasterize(tri, gour, framebuffer);
-            } else {
-                rest.vary = vary + i * 24;
-                rasterize(tri, rest, framebuffer);
-            }
-        }
-        raster_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-
-    std::ostringstream captured;
-    std::streambuf* old = std::cerr.rdbuf(captured.rdbuf());
-    print_render_stats();                                   // our_gl.cpp:204-210
-    std::cerr.rdbuf(old);
-    std::string line = captured.str();
-
-    std::ofstream out(out_path, std::ios::binary);
-    size_t fb_bytes = (size_t)W * H * bpp;
-    out.write((const char*)framebuffer.buffer(), fb_bytes);
-    static const char pad[8] = { 0 };
-    out.write(pad, (8 - fb_bytes % 8) % 8);
-    out.write((const char*)zbuffer.data(), zbuffer.size() * sizeof(double));
-    int32_t len = (int32_t)line.size();
-    out.write((const char*)&len, 4);
-    out.write(line.data(), len);
-    out.write(pad, (8 - (4 + len) % 8) % 8);
-    out.write((const char*)&raster_seconds, 8);
-    return out ? 0 : 3;
+    RestatedLit lit;
+    return refscene::run_scene(in_path, out_path, lit);
 }
 
 // vecops: input = int32 count, then per item 3+3+16+9+3+1 doubles (v, n, M, v0v1v2, b, intensity) and

@@ -8,10 +8,10 @@
  *
  * Pinning: rasterize()/barycentric()/TGAImage::set/TGAColor::operator* are pinned bit-for-bit
  * against the reference itself compiled from /root/reference (oracle/_ref, see oracle/Makefile
- * and tests/golden/).  The PHONG / EYE fragment bodies live in main.cpp, which cannot be compiled
- * here (model.h needs Assimp, absent): they are restated from the text and checked against the
- * same restatement run through the reference's own rasterize()+geometry.h — "parity unpinned"
- * against a compiled main.cpp.
+ * and tests/golden/).  The PHONG / EYE fragment bodies, the light directions, the vertex stage and
+ * the z-buffer image / SSAO live in main.cpp: they are pinned against the reference's own main.cpp
+ * and model.cpp, compiled against declaration-only Assimp stand-ins (oracle/_ref/ref_shaders,
+ * tests/golden/make_golden.py and make_shader_golden.py).
  */
 #ifndef TRGL_ORACLE_H
 #define TRGL_ORACLE_H
@@ -67,7 +67,7 @@ uint64_t orc_tga_encode(const uint8_t* data, int w, int h, int bpp, int vflip, i
 /* TGAImage::read_tga_file + load_rle_data (tgaimage.cpp:76-160) on a file image in memory; 1 = the reference returns true. */
 int orc_tga_decode(const uint8_t* file, uint64_t size, int* w, int* h, int* bpp, uint8_t* data, uint64_t cap);
 
-/* ---- SURVEY.md §8(f) next rows, restated from main.cpp (unbuildable here: "parity unpinned" vs a compiled main.cpp) ---- */
+/* ---- SURVEY.md §8(f) next rows, restated from main.cpp (pinned against the compiled main.cpp: oracle/_ref/ref_shaders) ---- */
 
 /* N1: PhongShader::vertex / EyeShader::vertex (main.cpp:71-90,199-218) for every face-vertex of an indexed mesh.
  * vertices: nverts x stride doubles, position at +0, normal at +3, texcoord at +6 (model.h:14-20 Vertex);

@@ -276,12 +276,186 @@ ZERO_CASES = {"zero_min_neg_first_96x64": (-1.0, None), "zero_min_pos_first_96x6
               "zero_checker_discarded_first_96x64": (1.0, None), "zero_phong_128x96": (1.0, None)}
 
 
+# ---- shading edges: small PHONG / EYE frames whose varyings reach the places where a reading of main.cpp:92-170, 220-261 and
+# model.cpp:428-459 can go wrong.  Their goldens come from the reference's own PhongShader / EyeShader (oracle/_ref/ref_shaders).
+def _texels(rng, w, h, bpp):
+    return (rng.u64(w * h * bpp) & np.uint64(0xFF)).astype(np.uint8).reshape(h, w, bpp)
+
+
+def _threshold_texels(rng, w, h, bpp):
+    """Diffuse texels around the eye-pixel threshold (main.cpp:110-112): channel sums 650 (brightness 0.8497) and 651 (0.8510),
+    with a quarter left random."""
+    t = _texels(rng, w, h, bpp)
+    pick = (rng.u64(w * h) % np.uint64(4)).astype(np.int64).reshape(h, w)
+    t[pick == 0, :3] = (217, 217, 216)
+    t[pick == 1, :3] = (216, 217, 217)
+    t[pick == 2, :3] = (217, 217, 217)
+    return t
+
+
+def edge_textures():
+    """Non-power-of-two textures of 1, 3 and 4 bytes per pixel.  Slots: diffuse 0 (bpp 3, threshold texels), 3 (bpp 1), 4 (bpp 4,
+    threshold texels); normal 1 (bpp 3), 5 (bpp 4), 6 (bpp 1); specular 2 (bpp 1), 7 (bpp 4), 8 (bpp 3)."""
+    r = scenes.SplitMix64(0x5EAD)
+    return {0: _threshold_texels(r, 37, 23, 3), 1: _texels(r, 31, 19, 3), 2: _texels(r, 11, 5, 1), 3: _texels(r, 13, 7, 1),
+            4: _threshold_texels(r, 29, 17, 4), 5: _texels(r, 7, 9, 4), 6: _texels(r, 5, 3, 1), 7: _texels(r, 9, 6, 4),
+            8: _texels(r, 3, 5, 3)}
+
+
+EDGE_UV = np.array([-0.5, 1.5, 1e12, -1e12, np.nan, 0.0, 1.0])
+
+
+def edge_varyings(n, seed, uv_edges=0.3, normal_edges=0.3, position_edges=0.2, nonfinite=0.04):
+    """PHONG / EYE varyings [n, 24] (uv[6], position_eye[9], normal_eye[9]).  A fraction of the rows reach the edges:
+    uv_edges - uv components from EDGE_UV (outside [0, 1], +-1e12, NaN); normal_edges - zero normals on every vertex, or
+    n1 = -n0 with n2 = 0 (the interpolated normal cancels where b0 = b1), or one zero vertex normal; position_edges -
+    position_eye through zero (p1 = -p0, p2 = 0) or zero at every vertex; nonfinite - one normal or position component NaN
+    or +-inf (a NaN dot product: the operand order of std::max(0.0, d) and std::min(255.0, v) decides the colour)."""
+    r = scenes.SplitMix64(seed)
+    uv = r.uniform(n * 6, -0.1, 1.1).reshape(n, 6)
+    pos = r.uniform(n * 9, -2.0, 2.0).reshape(n, 9)
+    nrm = r.uniform(n * 9, -1.0, 1.0).reshape(n, 9)
+    pick = r.uniform(n * 3).reshape(n, 3)
+    sub = (r.u64(n * 3) % np.uint64(3)).astype(np.int64).reshape(n, 3)
+    uvsel = (r.u64(n * 6) % np.uint64(len(EDGE_UV) + 2)).astype(np.int64).reshape(n, 6)
+    rows = pick[:, 0] < uv_edges
+    special = rows[:, None] & (uvsel < len(EDGE_UV))
+    uv[special] = EDGE_UV[uvsel[special]]
+    rows = pick[:, 1] < normal_edges
+    nrm[rows & (sub[:, 1] == 0)] = 0.0
+    m = rows & (sub[:, 1] == 1)
+    nrm[m, 3:6] = -nrm[m, 0:3]; nrm[m, 6:9] = 0.0
+    m = rows & (sub[:, 1] == 2)
+    nrm[m, 0:3] = 0.0
+    rows = pick[:, 2] < position_edges
+    m = rows & (sub[:, 2] != 2)
+    pos[m, 3:6] = -pos[m, 0:3]; pos[m, 6:9] = 0.0
+    pos[rows & (sub[:, 2] == 2)] = 0.0
+    out = np.concatenate([uv, pos, nrm], 1)
+    bad = np.flatnonzero(r.uniform(n) < nonfinite)
+    col = 6 + (r.u64(bad.size) % np.uint64(18)).astype(np.int64)
+    out[bad, col] = np.array([np.nan, np.inf, -np.inf])[(r.u64(bad.size) % np.uint64(3)).astype(np.int64)]
+    return np.ascontiguousarray(out)
+
+
+def _edge_uniforms(seed, strength=1.0, slots=(0, 1, 2)):
+    hd = scenes.head_standin(0, 16, 16, seed=seed)
+    return make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], strength, *slots)
+
+
+def _edge_draw(kind, n, w, h, seed, strength=1.0, slots=(0, 1, 2), **edges):
+    clip, _ = scenes.random_triangles(n, w, h, seed=seed, rmin=3, rmax=28, perspective_w=True)
+    return (kind, _edge_uniforms(seed, strength, slots), clip, edge_varyings(n, seed + 1, **edges), None)
+
+
+def shade_zero_normals_96x64():
+    """PHONG: zero and cancelling interpolated normals (normalized() leaves a zero vector as it is, geometry.h:136-140), on and off
+    eye pixels, and position_eye through zero (view direction of a zero vector)."""
+    return make_case(96, 64, [_edge_draw(PHONG, 260, 96, 64, 601, normal_edges=0.7, position_edges=0.5)], textures=edge_textures())
+
+
+def shade_zero_normals_eye_96x64_rgba():
+    """EYE on an RGBA frame with a 4-byte diffuse map: zero / cancelling normals and position_eye through zero."""
+    return make_case(96, 64, [_edge_draw(EYE, 260, 96, 64, 611, slots=(4, -1, 7), normal_edges=0.7, position_edges=0.5)],
+                     bpp=4, textures=edge_textures())
+
+
+def shade_uv_extremes_128x64():
+    """PHONG with uv of -0.5, 1.5, +-1e12 and NaN (x86's INT_MIN clamps to texel 0) on 1-, 3- and 4-byte maps of odd sizes."""
+    return make_case(128, 64, [_edge_draw(PHONG, 300, 128, 64, 621, uv_edges=0.8),
+                               _edge_draw(PHONG, 300, 128, 64, 623, slots=(3, 5, 8), uv_edges=0.8),
+                               _edge_draw(PHONG, 200, 128, 64, 625, slots=(4, 6, 7), uv_edges=0.8)], textures=edge_textures())
+
+
+def shade_strengths_128x96_rgba():
+    """normal_map_strength 0, 0.5, 1 and 1.7: the blend geometry_normal * (1 - s) + normal_map_eye * s (main.cpp:122-125)."""
+    draws = [_edge_draw(PHONG, 200, 128, 96, 631 + 2 * i, strength=s, slots=((0, 1, 2), (4, 5, 7), (3, 6, 8), (0, 5, -1))[i])
+             for i, s in enumerate((0.0, 0.5, 1.0, 1.7))]
+    return make_case(128, 96, draws, bpp=4, textures=edge_textures(), clear=(1, 2, 3, 4))
+
+
+def shade_eye_threshold_96x64_gray():
+    """Diffuse texels with channel sums 650 and 651 on either side of brightness >= 0.85 (main.cpp:110-112), into a 1-byte
+    frame: on eye pixels the unnormalized geometry normal is used (main.cpp:122-123)."""
+    return make_case(96, 64, [_edge_draw(PHONG, 300, 96, 64, 641, strength=0.5, uv_edges=0.0),
+                              _edge_draw(PHONG, 200, 96, 64, 643, slots=(4, 1, -1), uv_edges=0.0)],
+                     bpp=1, textures=edge_textures())
+
+
+def shade_no_textures_64x64():
+    """PHONG and EYE without maps: white diffuse, (0, 0, 1) normal map, specular 1.0f (model.cpp:415-459 fallbacks)."""
+    return make_case(64, 64, [_edge_draw(PHONG, 150, 64, 64, 651, strength=0.5, slots=(-1, -1, -1)),
+                              _edge_draw(EYE, 100, 64, 64, 653, slots=(-1, -1, -1))])
+
+
+SHADING_EDGE_CASES = ("shade_zero_normals_96x64", "shade_zero_normals_eye_96x64_rgba", "shade_uv_extremes_128x64",
+                      "shade_strengths_128x96_rgba", "shade_eye_threshold_96x64_gray", "shade_no_textures_64x64")
+
+
+def shader_fragment_inputs(n=20000, seed=0x51AD):
+    """Single fragment() calls for tests/golden/shader_golden.npz: (textures, kinds [n], uniforms [n], varyings [n, 24],
+    bary [n, 3]).  Weighted towards the edges of edge_varyings; bary is a vertex, an edge midpoint (where n1 = -n0 cancels
+    exactly) or random; lights are unit, unnormalized, zero or hold a NaN; strengths 0, 0.5, 1, 1.7 or random."""
+    r = scenes.SplitMix64(seed)
+    vary = edge_varyings(n, seed + 1, uv_edges=0.35, normal_edges=0.4, position_edges=0.3)
+    kinds = np.where(r.uniform(n) < 0.6, PHONG, EYE).astype(np.int32)
+    b = r.uniform(n * 3, 0.0, 1.0).reshape(n, 3)
+    b /= b.sum(1, keepdims=True)
+    form = (r.u64(n) % np.uint64(4)).astype(np.int64)
+    b[form == 0] = (1.0, 0.0, 0.0)
+    b[form == 1] = (0.5, 0.5, 0.0)
+    b[form == 2] = (0.0, 0.5, 0.5)
+    slot_sets = [(0, 1, 2), (3, 5, 8), (4, 6, 7), (-1, -1, -1), (0, -1, 2), (4, 1, -1), (-1, 5, 7)]
+    sets = (r.u64(n) % np.uint64(len(slot_sets))).astype(np.int64)
+    strengths = np.array([0.0, 0.5, 1.0, 1.7])
+    ssel = (r.u64(n) % np.uint64(5)).astype(np.int64)
+    srand = r.uniform(n, -0.5, 2.0)
+    mvs = [scenes.head_standin(0, 16, 16, seed=s)["model_view"] for s in (1, 2, 3)] + [np.eye(4)]
+    msel = (r.u64(n) % np.uint64(len(mvs))).astype(np.int64)
+    lights = r.uniform(n * 9, -1.0, 1.0).reshape(n, 3, 3)
+    lform = (r.u64(n) % np.uint64(5)).astype(np.int64)
+    lights[lform <= 1] /= np.linalg.norm(lights[lform <= 1], axis=2, keepdims=True)
+    lights[lform == 3, 0] = 0.0
+    lights[lform == 4, 1, 2] = np.nan
+    uniforms = [make_uniforms(mvs[msel[i]], lights[i, 0], lights[i, 1], lights[i, 2],
+                              strengths[ssel[i]] if ssel[i] < 4 else srand[i], *slot_sets[sets[i]]) for i in range(n)]
+    return edge_textures(), kinds, uniforms, vary, np.ascontiguousarray(b)
+
+
+def fixture_mesh():
+    """The mesh of the N1 fixtures (tests/golden/next_rows_golden.json): the head stand-in's vertices, float-representable (the
+    reference reads them through Assimp's float aiVector3D), shared between faces through a shuffled index buffer.  Returns
+    (vertices [nv, 8] f64: position, normal, uv; indices [nf, 3] u32, uniforms, projection, width, height)."""
+    w, h = 160, 120
+    hd = scenes.head_standin(2, w, h)
+    pos, nrm, uv = hd["positions"].reshape(-1, 3), hd["normals"].reshape(-1, 3), hd["uvs"].reshape(-1, 2)
+    verts = np.concatenate([pos, nrm, uv], 1).astype(np.float32).astype(np.float64)
+    perm = np.argsort(scenes.SplitMix64(19).u64(pos.shape[0]), kind="stable")
+    inv = np.empty_like(perm); inv[perm] = np.arange(perm.size)
+    u = make_uniforms(hd["model_view"], hd["key"], hd["fill"], hd["rim"], 0.8, 0, 1, 2)
+    return np.ascontiguousarray(verts[perm]), inv.astype(np.uint32).reshape(-1, 3), u, hd["projection"], w, h
+
+
+def fixture_zbuffers():
+    """z-buffers of the N4 fixtures: name -> [h, w] f64.  Random depths with +-inf and NaN holes, a constant one (max - min
+    below 1e-7), one with no finite depth, and depth steps that the SSAO threshold 1e-3 sees on one side only."""
+    r = scenes.SplitMix64(0x2B0F)
+    a = r.uniform(64 * 48, -1.0, 1.0).reshape(48, 64)
+    a[r.uniform(64 * 48).reshape(48, 64) < 0.15] = np.inf
+    a[5, 7] = -np.inf; a[9, 30] = np.nan
+    steps = np.repeat(np.repeat(r.uniform(8 * 6, 0.0, 0.01).reshape(6, 8), 8, 0), 9, 1)[:, :70]
+    steps[20:30, 30:40] = np.inf
+    return {"random_holes_64x48": a, "constant_40x24": np.full((24, 40), 0.125), "all_inf_24x16": np.full((16, 24), np.inf),
+            "steps_70x48": np.ascontiguousarray(steps)}
+
+
 CASES = {f.__name__: f for f in (
     flat_small_64, flat_800, flat_persp_512, flat_big_tris_512, edge_256, grid_256, grid_fine_128, gouraud_256_rgba,
     phong_512, phong_nomaps_256, eye_256, multi_draw_320x200, odd_dims_101x67, gray_bpp1_96x64,
     viewport_offset_256x160, zclear_finite_128, huge_depths_128, empty_scene_64, checker_256, checker_mixed_200x120,
     zero_min_neg_first_96x64, zero_min_pos_first_96x64, zero_signs_in_one_triangle_96x64, zero_max_neg_first_96x64,
-    zero_checker_discarded_first_96x64, zero_phong_128x96)}
+    zero_checker_discarded_first_96x64, zero_phong_128x96, shade_zero_normals_96x64, shade_zero_normals_eye_96x64_rgba,
+    shade_uv_extremes_128x64, shade_strengths_128x96_rgba, shade_eye_threshold_96x64_gray, shade_no_textures_64x64)}
 
 # cases whose full buffers are stored in tests/golden/ (small enough to commit)
 FULL_BUFFER_CASES = ("flat_small_64", "odd_dims_101x67", "gray_bpp1_96x64")

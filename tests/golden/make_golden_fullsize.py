@@ -25,7 +25,8 @@ def main():
     for name, build in cases.FULLSIZE_CASES.items():
         c = build()
         fb, z, line, secs = orc.run_reference(c["width"], c["height"], c["bpp"], c["viewport"], c["draws"], c["textures"], c["clear"],
-                                              c["zclear"], harness=orc.REF_HARNESS_FAST, with_time=True)
+                                              c["zclear"], harness=orc.REF_SHADERS if any(d[0] in (orc.PHONG, orc.EYE) for d in c["draws"])
+                                              else orc.REF_HARNESS_FAST, with_time=True)
         out[name] = dict(inputs=input_digest(c), fb=scenes.digest(fb), z=scenes.digest(z), stats=line,
                          width=c["width"], height=c["height"], bpp=c["bpp"], reference_rasterize_seconds=round(secs, 2))
         print(name, line, f"{secs:.1f} s", flush=True)
