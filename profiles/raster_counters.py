@@ -1,4 +1,5 @@
-"""k_raster work counters on the C4 frame (diagnostic build: make -C tinyrenderder_amd/csrc ../libtrgl_dbg.so)."""
+"""k_raster work counters on the C4 frame (diagnostic build with the phase clocks:
+make -C tinyrenderder_amd/csrc DBG_DEFS=-DTRGL_DEBUG_COUNTERS ../libtrgl_dbg.so; the default build of that library leaves them out)."""
 import ctypes as C, sys
 sys.path.insert(0, '.')
 import numpy as np, torch

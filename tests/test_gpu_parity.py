@@ -134,13 +134,8 @@ def test_block_masks_on_adversarial_shapes(seed):
     check(_flat(W, H, clip, col))
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_depth_plane_early_test_on_extreme_depths(seed):
-    """k_raster skips the three divisions of a block when a plane c0 + u.y g1 + u.x g2 (a lower bound of every covered pixel's
-    computed z, 2^-40 max|z_i| below the exact plane) is not below the stored depth.  Depths chosen against it, on dense
-    overdraw: vertices at +-1e0..1e300 next to one inside [-1,1] (slopes overflow: the test must switch itself off), depths of
-    1e-300..1e-320 (subnormal planes), planes one ulp from flat, exactly flat duplicates (ties), perspective w, and a stored
-    z-buffer with NaN, -inf, +inf and finite patches.  A pixel killed wrongly is a missing fragment: bits must equal the oracle's."""
+def extreme_depths_scene(seed):
+    """The scene of test_depth_plane_early_test_on_extreme_depths (its docstring says what is in it): (W, H, clip, colours, stored depths)."""
     rng = scenes.SplitMix64(8000 + seed)
     W, H = 192, 128
     n = 15000
@@ -166,6 +161,17 @@ def test_depth_plane_early_test_on_extreme_depths(seed):
     # stored depths the flush starts from: finite band, NaN, -inf, +inf columns
     z0 = np.full((H, W), np.inf)
     z0[:, 0:40] = 0.25; z0[:, 40:70] = np.nan; z0[:, 70:100] = -np.inf; z0[:, 100:130] = -0.5; z0[10:20, :] = 1e-310
+    return W, H, clip, col, z0
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_depth_plane_early_test_on_extreme_depths(seed):
+    """k_raster skips the three divisions of a block when a plane c0 + u.y g1 + u.x g2 (a lower bound of every covered pixel's
+    computed z, 2^-40 max|z_i| below the exact plane) is not below the stored depth.  Depths chosen against it, on dense
+    overdraw: vertices at +-1e0..1e300 next to one inside [-1,1] (slopes overflow: the test must switch itself off), depths of
+    1e-300..1e-320 (subnormal planes), planes one ulp from flat, exactly flat duplicates (ties), perspective w, and a stored
+    z-buffer with NaN, -inf, +inf and finite patches.  A pixel killed wrongly is a missing fragment: bits must equal the oracle's."""
+    W, H, clip, col, z0 = extreme_depths_scene(seed)
     case = _flat(W, H, clip, col, clear=(1, 2, 3, 255))
     got = cases.run_gpu(case, start=(None, z0), split=2)       # (two flushes of n / 2)
     same(got, cases.run_oracle(case, start=(None, z0)))
@@ -693,14 +699,8 @@ def test_interleaved_rank_without_rows_draws_nothing_and_stays_usable():
     same(got, cases.run_oracle(_flat(W, H, clip, col)))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("seed", range(4))
-def test_depth_bound_in_the_pair_on_large_triangles(seed):
-    """A flush that holds triangles of 64 pixels and more lets k_raster's list steps drop entries by the 7-bit depth bound that rides in
-    the pair's triangle word (TRGL_VAL_ZQ): 4000 triangles of 20 - 300 px on 320 x 200, depth complexity in the hundreds, so that
-    nearly every later entry is occluded - and has to be dropped ONLY then.  A third of them get a vertex depth outside [-1, 1]
-    (bound 0 = says nothing), every fifth is nearly flat in depth (bound as tight as the 1/64 grid allows), all on top of small
-    triangles that share the tiles.  z bits, colours and counters must equal the oracle's."""
+def large_triangles_scene(seed):
+    """The scene of test_depth_bound_in_the_pair_on_large_triangles (its docstring says what is in it): (W, H, clip, colours)."""
     W, H = 320, 200
     big, bcol = scenes.random_triangles(4000, W, H, seed=8100 + seed, rmin=20, rmax=300)
     small, scol = scenes.random_triangles(6000, W, H, seed=8200 + seed, rmin=1, rmax=12)
@@ -716,6 +716,18 @@ def test_depth_bound_in_the_pair_on_large_triangles(seed):
                 big[i, 4 * v + 2] = z0 + 1e-4 * v
     clip = np.concatenate([small[:3000], big[:2000], small[3000:], big[2000:]])
     col = np.concatenate([scol[:3000], bcol[:2000], scol[3000:], bcol[2000:]])
+    return W, H, clip, col
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", range(4))
+def test_depth_bound_in_the_pair_on_large_triangles(seed):
+    """A flush that holds triangles of 64 pixels and more lets k_raster's list steps drop entries by the 7-bit depth bound that rides in
+    the pair's triangle word (TRGL_VAL_ZQ): 4000 triangles of 20 - 300 px on 320 x 200, depth complexity in the hundreds, so that
+    nearly every later entry is occluded - and has to be dropped ONLY then.  A third of them get a vertex depth outside [-1, 1]
+    (bound 0 = says nothing), every fifth is nearly flat in depth (bound as tight as the 1/64 grid allows), all on top of small
+    triangles that share the tiles.  z bits, colours and counters must equal the oracle's."""
+    W, H, clip, col = large_triangles_scene(seed)
     with Context(W, H, 3) as ctx:
         ctx.draw(FLAT, clip, colors=col)
         got = (ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats())

@@ -168,6 +168,18 @@ def test_literal_triangles_in_every_kernel_variant(kind, bpp):
     check(case, split=2)
     for strip in ((0, 45), (45, LH)):
         check(case, strip=strip)
+    # observed, not only predicted: k_setup's own count of the triangles it sent down the literal path (every row that
+    # setup_literal marks by a margin survives culling with a non-empty bbox and a u.z that is not tiny, so it has pairs)
+    with Context(LW, LH, bpp) as ctx:
+        ctx.set_viewport(case["viewport"])
+        for slot, t in case["textures"].items():
+            ctx.upload_texture(slot, t)
+        for k, u, c, vary, cl in case["draws"]:
+            ctx.draw(k, c, vary, cl, u)
+        ctx.flush()
+        observed = ctx.debug_snapshot()["info"]["literal_tris"]
+    predicted = sum(int(setup_literal(d[2], cases.UNIT_VIEWPORT, LW, LH)[0].sum()) for d in case["draws"])
+    assert observed >= predicted >= 150, (observed, predicted)
 
 
 @pytest.mark.gpu

@@ -81,6 +81,17 @@ class TrglError(RuntimeError):
     pass
 
 
+# ---- diagnostic read-back of a flush's intermediate buffers (trgl_debug_read; not part of include/trgl.h) ----
+# struct TriRec of csrc/trgl_device.h, one 128-byte line per triangle
+TRI_REC = np.dtype([(n, "<f8") for n in ("ax", "ay", "s0x", "s0y", "s1x", "s1y", "c0", "uz", "g1", "g2", "ruz", "z0", "z1", "z2")]
+                   + [(n, "<u2") for n in ("bx0", "by0", "bx1", "by1")] + [("color", "<u4"), ("dl", "<u4")])
+assert TRI_REC.itemsize == 128, "TRI_REC must mirror sizeof(TriRec) == 128"
+DBG_RECS, DBG_CNT, DBG_TILEBOX, DBG_VALS, DBG_BMASK, DBG_TILE_START, DBG_TILE_END, DBG_INFO = range(8)
+DBG_INFO_FIELDS = ("N", "P", "capacity", "wide", "literal_tris", "large_tris", "zq_cull", "pending", "W", "H", "tiles_x", "tiles_y",
+                   "strip_y0", "strip_y1", "strip_ty0", "strip_ty1", "il_tiles", "il_world", "il_rank", "side")
+DL_LITERAL = 0x80000000       # TRGL_DL_LITERAL
+
+
 _lib = None
 
 
@@ -132,6 +143,8 @@ def load_library(path: str = None):
     L.trgl_get_phase_ms.argtypes = [vp, dp, u64p]
     L.trgl_reset_phase_ms.argtypes = [vp]
     L.trgl_get_last_flush_info.argtypes = [vp, u64p, u64p, u64p]
+    if hasattr(L, "trgl_debug_read"):      # (diagnostic, not part of include/trgl.h: an older build named by TRGL_LIB may lack it)
+        L.trgl_debug_read.argtypes = [vp, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.trgl_selftest_division.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
     L.trgl_selftest_sampler.argtypes = [vp, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.trgl_draw_indexed.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
@@ -477,3 +490,23 @@ class Context:
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._chk(self.L.trgl_get_last_flush_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(triangles=a.value, pairs=b.value, tiles=c.value)
+
+    def _debug_read(self, what, dtype):
+        need = C.c_size_t()
+        self._chk(self.L.trgl_debug_read(self.h, what, None, 0, C.byref(need)))
+        out = np.zeros(need.value // np.dtype(dtype).itemsize, dtype)
+        if need.value:
+            self._chk(self.L.trgl_debug_read(self.h, what, out.ctypes.data, out.nbytes, None))
+        return out
+
+    def debug_snapshot(self):
+        """The intermediate buffers of the flush begun with flush_begin() (which stays pending: this call does not complete
+        it) or of the last complete flush (until the next draw or clear): what k_setup and the binning left for k_raster.
+        recs [N + 1] TRI_REC (rows of triangles without pairs are not written; row N exists after the complete flush), cnt [N],
+        tilebox [N, 2], vals / bmask [P] (the side k_raster reads), tile_start / tile_end [tiles], info: dict of DBG_INFO_FIELDS.
+        Raises TrglError where no flush can be read."""
+        info = dict(zip(DBG_INFO_FIELDS, (int(v) for v in self._debug_read(DBG_INFO, np.int64))))
+        return dict(info=info, recs=self._debug_read(DBG_RECS, TRI_REC), cnt=self._debug_read(DBG_CNT, np.uint32),
+                    tilebox=self._debug_read(DBG_TILEBOX, np.uint32).reshape(-1, 2), vals=self._debug_read(DBG_VALS, np.uint32),
+                    bmask=self._debug_read(DBG_BMASK, np.uint16), tile_start=self._debug_read(DBG_TILE_START, np.uint32),
+                    tile_end=self._debug_read(DBG_TILE_END, np.uint32))

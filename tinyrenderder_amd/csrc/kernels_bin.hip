@@ -201,7 +201,7 @@ __global__ __launch_bounds__(SETUP_THREADS) void k_setup(FrameParams fp, DrawDes
                     if (t >= 1.0) zq = t >= 127.0 ? 127u : (uint32_t)x86_cvttsd2si(floor(t));
                 }
                 tb.x |= (zq & 7u) << 13; tb.y |= ((zq >> 3) & 7u) << 13; tb.y |= (zq >> 6) << 29;
-                large = bx1 - bx0 >= 64 || y_hi - y_lo >= 64;
+                large = ntiles != 0 && (bx1 - bx0 >= 64 || y_hi - y_lo >= 64);      // (no tile in this context's bands: no pair to profit)
             }
         }
         cnt[d.first + i] = ntiles;

@@ -103,6 +103,8 @@ struct trgl_ctx {
 
     uint64_t triangles_total = 0;       // our_gl.cpp:90 counts every call, host side
     uint64_t last_tris = 0, last_pairs = 0;
+    // what trgl_debug_read reports of the last complete flush (valid until the next trgl_draw / trgl_clear)
+    struct Snapshot { bool valid = false; FrameParams fp; uint64_t N = 0, P = 0, cap = 0, literal_tris = 0, large_tris = 0; int cur = 0; } snap;
 
     bool profiling = false, events_pending = false;
     hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
@@ -252,6 +254,7 @@ int trgl_clear(trgl_ctx* c, const uint8_t bgra[4], double z_clear) {
     c->clear_color = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
     c->clear_z = z_clear;
     c->clear_pending = true;
+    c->snap.valid = false;
     return TRGL_OK;
 }
 
@@ -337,6 +340,7 @@ int trgl_draw(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip,
     const bool user = kind >= TRGL_SHADER_USER_FIRST && kind - TRGL_SHADER_USER_FIRST < (int)c->user.size();
     if ((kind < 0 || kind >= TRGL_NUM_SHADERS) && !user) return fail(c, TRGL_E_INVALID, "trgl_draw: unknown shader kind");
     if (n == 0) return TRGL_OK;
+    c->snap.valid = false;
     if (!clip) return fail(c, TRGL_E_INVALID, "trgl_draw: clip is null");
     int K = user ? c->user[kind - TRGL_SHADER_USER_FIRST].K : vary_count(kind);
     if (K && !vary) return fail(c, TRGL_E_INVALID, "trgl_draw: this shader kind needs varyings");
@@ -539,6 +543,7 @@ int trgl_flush_begin(trgl_ctx* c) {
     if (c->draws.empty() && !c->clear_pending) return TRGL_OK;
     int r;
     if ((r = resolve_events(c))) return r;
+    c->snap.valid = false;              // the buffers are about to be rewritten; trgl_debug_read reads the flush begun here
     const uint64_t N = c->queued_tris;
     hipStream_t s = c->stream;
     FrameParams fp = frame_params(c);
@@ -648,6 +653,8 @@ int trgl_flush_end(trgl_ctx* c) {
 
     c->triangles_total += N;
     c->last_tris = N; c->last_pairs = P;
+    c->snap.valid = true; c->snap.fp = fp; c->snap.N = N; c->snap.P = P; c->snap.cap = c->keys[0].cap; c->snap.cur = cur;
+    c->snap.literal_tris = N ? c->stats_pinned->literal_tris : 0; c->snap.large_tris = N ? c->stats_pinned->large_tris : 0;
     c->clear_pending = false;
     bool had_stage = false;
     for (auto& ch : c->stage) if (ch.used) had_stage = true;
@@ -887,6 +894,58 @@ extern "C" int trgl_debug_counters(trgl_ctx* c, unsigned long long out[16]) {
     int r = flush_sync(c); if (r) return r;
     HIPCHK(c, hipMemcpy(c->stats_pinned, c->stats_dev.p, sizeof(DevStats), hipMemcpyDeviceToHost));
     for (int k = 0; k < 16; ++k) out[k] = c->stats_pinned->dbg[k];
+    return TRGL_OK;
+}
+
+// Diagnostic read-back of one flush's intermediate buffers (tests/test_stage_outputs_gpu.py; not part of include/trgl.h).
+// Valid between trgl_flush_begin and trgl_flush_end - the one entry point that does NOT complete a begun flush - and after a
+// complete flush until the next trgl_draw / trgl_clear; TRGL_E_STATE otherwise.  Synchronises the stream and copies device ->
+// host; launches nothing.  *needed receives the size in bytes of `what`; with dst == nullptr that is all the call does.
+//   what 0 RECS       TriRec[N + 1]   (the record behind the last is written by the raster half)
+//        1 CNT        uint32[N]       2 TILEBOX uint2[N]
+//        3 VALS       uint32[P]       4 BMASK   uint16[P]      the ping-pong side k_raster is (or was) handed
+//        5 TILE_START uint32[tiles]   6 TILE_END uint32[tiles]
+//        7 INFO       int64[24]: N, P, pair capacity, wide, literal_tris, large_tris, zq_cull, pending, W, H, tiles_x, tiles_y,
+//                     strip_y0, strip_y1, strip_ty0, strip_ty1, il_tiles, il_world, il_rank, side, 0...
+// While a flush is pending whose pairs exceed the capacity (trgl_flush_end will grow the buffers and bin again), the pair lists
+// and tile bounds do not exist yet: TRGL_E_STATE for what 3-6; INFO still reports P and the capacity.
+extern "C" int trgl_debug_read(trgl_ctx* c, int what, void* dst, size_t bytes, size_t* needed) {
+    CHKCTX(c);
+    const bool pending = c->rp.active;
+    if (!pending && !c->snap.valid) return fail(c, TRGL_E_STATE, "trgl_debug_read: no flush to read (between trgl_flush_begin and trgl_flush_end, or after a flush until the next draw or clear)");
+    if (what < 0 || what > 7) return fail(c, TRGL_E_INVALID, "trgl_debug_read: unknown buffer");
+    FrameParams fp; uint64_t N, P, cap, lit, lrg; int cur;
+    if (pending) {
+        fp = c->rp.fp; N = c->rp.N; cap = c->rp.cap; cur = c->rp.cur; P = lit = lrg = 0;
+        if (N) {
+            HIPCHK(c, hipEventSynchronize(c->ev_pairs));
+            P = c->stats_pinned->pairs_total; lit = c->stats_pinned->literal_tris; lrg = c->stats_pinned->large_tris;
+        }
+        fp.zq_cull = (N != 0 && lrg != 0) ? 1 : 0;         // what trgl_flush_end will decide
+    } else {
+        fp = c->snap.fp; N = c->snap.N; P = c->snap.P; cap = c->snap.cap; cur = c->snap.cur; lit = c->snap.literal_tris; lrg = c->snap.large_tris;
+    }
+    const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
+    if (what >= 3 && what <= 6 && P > cap) return fail(c, TRGL_E_STATE, "trgl_debug_read: the pending flush has more pairs than the pair buffers hold; its lists exist after trgl_flush_end");
+    int64_t info[24] = { (int64_t)N, (int64_t)P, (int64_t)cap, ntiles > 65536 ? 1 : 0, (int64_t)lit, (int64_t)lrg, fp.zq_cull, pending ? 1 : 0,
+                         fp.W, fp.H, fp.tiles_x, fp.tiles_y, fp.strip_y0, fp.strip_y1, fp.strip_ty0, fp.strip_ty1, fp.il_tiles, fp.il_world, fp.il_rank, cur };
+    const void* src = nullptr; size_t need = 0;
+    switch (what) {
+    case 0: src = c->recs.p; need = N ? (size_t)(N + 1) * sizeof(TriRec) : 0; break;
+    case 1: src = c->cnt.p; need = (size_t)N * sizeof(uint32_t); break;
+    case 2: src = c->tilebox.p; need = (size_t)N * sizeof(uint2); break;
+    case 3: src = c->vals[cur].p; need = (size_t)P * sizeof(uint32_t); break;
+    case 4: src = c->bmask[cur].p; need = (size_t)P * sizeof(uint16_t); break;
+    case 5: src = c->tile_start.p; need = ntiles * sizeof(uint32_t); break;
+    case 6: src = c->tile_end(); need = ntiles * sizeof(uint32_t); break;
+    default: need = sizeof(info); break;
+    }
+    if (needed) *needed = need;
+    if (!dst) return TRGL_OK;
+    if (bytes < need) return fail(c, TRGL_E_INVALID, "trgl_debug_read: destination too small");
+    if (what == 7) { std::memcpy(dst, info, sizeof(info)); return TRGL_OK; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (need) HIPCHK(c, hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
     return TRGL_OK;
 }
 
