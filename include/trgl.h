@@ -39,6 +39,11 @@ extern "C" {
 /* where the pointers handed to trgl_draw() live */
 #define TRGL_MEM_HOST   0      /* copied before trgl_draw returns */
 #define TRGL_MEM_DEVICE 1      /* HBM-resident; must stay valid until trgl_flush has completed */
+/* TRGL_MEM_DEVICE arrays are read by the kernels of the flush through the caller's pointers as they are, not at trgl_draw time.
+ * Natural alignment suffices: 8 bytes for clip / varyings / vertices, 4 for colors / indices (nothing wider is assumed).
+ * Their contents must be complete on the context's stream (trgl_stream) when the flush runs (vertices / indices: when
+ * trgl_draw_indexed queues its vertex stage) - that stream does not wait for any other, the legacy default stream included - so either the caller synchronises its producers before that, or
+ * it shares one stream with the context through trgl_set_stream; the same holds before it overwrites or frees them. */
 
 /*
  * Shader kinds: the device-side restatements of IShader::fragment() bodies (our_gl.h:51).

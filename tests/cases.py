@@ -491,13 +491,42 @@ def run_oracle(case, strip=None, start=None):
     return o.fb, o.z, o.stats
 
 
+def device_array(a, off=0):
+    """A torch CUDA tensor holding the numpy array `a` (f64, or u32 carried as int32), its first element `off` bytes into a
+    larger allocation (off: a multiple of the item size; torch's allocations themselves start on 512-byte boundaries)."""
+    import torch
+    a = np.ascontiguousarray(a)
+    a = a.view(np.int32) if a.dtype == np.uint32 else a
+    assert off % a.itemsize == 0, (off, a.dtype)
+    lead = off // a.itemsize
+    buf = torch.empty(a.size + lead + (1 if lead else 0), dtype=torch.from_numpy(a[:0]).dtype, device="cuda")
+    t = buf[lead:lead + a.size].view(a.shape)
+    t.copy_(torch.from_numpy(a))
+    assert t.is_cuda and t.is_contiguous() and t.data_ptr() == buf.data_ptr() + off
+    return t
+
+
+def on_device(case, clip_off=0, vary_off=0, col_off=0, producer_sync=True):
+    """The case with the clip, varyings and colour arrays of every draw in device memory (torch CUDA tensors: run_gpu draws
+    them with device=True, slicing them for split=), each placed *_off bytes into a larger allocation (a multiple of 8 for
+    the doubles, of 4 for the colours).  producer_sync: wait for the uploads, which run on torch's stream - a context's own
+    stream is not ordered behind it."""
+    import torch
+    draws = [(kind, u, device_array(clip, clip_off), None if vary is None else device_array(vary, vary_off),
+              None if col is None else device_array(col, col_off)) for kind, u, clip, vary, col in case["draws"]]
+    if producer_sync:
+        torch.cuda.synchronize()
+    return dict(case, draws=draws)
+
+
 def run_gpu(case, strip=None, interleave=None, split=None, flush_after=None, halves=False, start=None, shaders=None):
     """Render a case through the C ABI on the GPU; returns (fb, z, stats tuple, stats line).
     strip = (y0, y1): a strip context (set_strip); interleave = (band_rows, rank, world): one rank's bands (set_interleave).
     split = k: each draw in k flushes; flush_after = i: a flush after draw i; halves: the last flush as flush_begin / flush_end.
     start = (fb, z): as for run_oracle, through write_framebuffer / write_zbuffer.
     shaders: per draw, None or (source, K): the draw uses the user kind the context registers for that source.
-    Clip and colour arrays that are torch CUDA tensors are drawn from device memory."""
+    A draw whose clip array is a torch CUDA tensor is drawn from device memory (on_device: all of its arrays are); the
+    binding refuses a host array in such a draw."""
     from tinyrenderder_amd.api import Context
     shaders = shaders or [None] * len(case["draws"])
     with Context(case["width"], case["height"], case["bpp"]) as ctx:

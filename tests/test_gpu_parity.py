@@ -28,14 +28,6 @@ def _flat(W, H, clip, col, **kw):
     return cases.make_case(W, H, [(FLAT, None, clip, None, col)], **kw)
 
 
-def _on_device(case):
-    """The case with its clip and colour arrays in device memory (torch CUDA tensors: run_gpu draws them with device=True)."""
-    import torch
-    draws = [(kind, u, torch.from_numpy(clip).cuda(), vary, torch.from_numpy(col.view(np.int32)).cuda())
-             for kind, u, clip, vary, col in case["draws"]]
-    return dict(case, draws=draws)
-
-
 @pytest.mark.parametrize("name", sorted(cases.CASES))
 def test_gpu_matches_reference_golden_and_oracle(name):
     case = cases.CASES[name]()
@@ -78,7 +70,7 @@ def test_c4_full_size_properties():
     size-independent properties: determinism, split-submission invariance, and the counters' invariants."""
     W = H = 4096
     N = 10_000_000
-    case = _on_device(cases.FULLSIZE_CASES["c4_4096_10m"]())      # scenes.random_triangles(N, W, H)
+    case = cases.on_device(cases.FULLSIZE_CASES["c4_4096_10m"]())      # scenes.random_triangles(N, W, H)
     first = cases.run_gpu(case, split=1)
     same(cases.run_gpu(case, split=1), first, what="two identical runs")
     same(cases.run_gpu(case, split=4), first, what="4 flushes against 1 flush")
@@ -90,7 +82,7 @@ def test_c4_full_size_equals_the_reference_frame():
     """BASELINE configs[3] at its stated size — the frame bench.py times: all 10 M triangles at 4096x4096 against the
     frame the reference's own rasterize() rendered (tests/golden/golden_fullsize.json: sha256 of its framebuffer bytes and
     z-buffer bits, its print_render_stats() line)."""
-    cases.assert_golden(cases.run_gpu(_on_device(cases.FULLSIZE_CASES["c4_4096_10m"]())), GOLDEN_FULL["c4_4096_10m"])
+    cases.assert_golden(cases.run_gpu(cases.on_device(cases.FULLSIZE_CASES["c4_4096_10m"]())), GOLDEN_FULL["c4_4096_10m"])
 
 
 @pytest.mark.parametrize("seed", range(6))
@@ -239,7 +231,7 @@ def test_c5_8192_eight_strips_compose():
     strips the 8 ranks of `bench.py --gpus 8` own and rendered one after the other by strip contexts.  The unsharded frame
     equals the frame the reference's own rasterize() rendered (golden_fullsize.json), and the strips equal its rows,
     depths, summed fragment counts and z range.  (What RCCL then does with the strips is a plain all-gather.)"""
-    case = _on_device(cases.FULLSIZE_CASES["c5_8192_10m"]())
+    case = cases.on_device(cases.FULLSIZE_CASES["c5_8192_10m"]())
     H = 8192
     G = 8
     whole = cases.run_gpu(case)
@@ -341,11 +333,23 @@ def test_bench_rccl_strip_gather_path_single_rank():
     assert d["rccl_ranks"] == 1 and len(d["rank_phase_ms"]) == 1 and d["rank_phase_ms"][0]["raster_kernel"] > 0     # what the driver's SCALE record can be checked against
 
 
+@pytest.fixture(scope="module")
+def baseline_oracle_frames():
+    """cfg -> the oracle's frame of a BASELINE PHONG config: rendered once (the scalar oracle takes most of the test's time) and
+    shared by the two `memory` variants of the test below."""
+    frames = {}
+    yield frames
+    frames.clear()
+
+
+@pytest.mark.parametrize("memory", ["host", "device"])
 @pytest.mark.parametrize("cfg", ["c2_2048_phong_diffuse", "c3_4096_phong_diffuse_normal_spec"])
-def test_baseline_phong_configs_full_size(cfg):
+def test_baseline_phong_configs_full_size(cfg, memory, baseline_oracle_frames):
     """BASELINE configs[1] and [2] at full resolution: PHONG on the 327 680-triangle head stand-in (african_head.obj
     is absent from the reference tree) with 1024x1024 procedural maps, against the CPU oracle: z bit-identical,
-    colour byte-identical (PHONG's pow exponent is always 1.0, so no tolerance is needed), stats identical."""
+    colour byte-identical (PHONG's pow exponent is always 1.0, so no tolerance is needed), stats identical.
+    memory = device: clip and varyings are submitted from the caller's device tensors, as bench.py's secondary workloads
+    submit them (k_shade reads d.vary + local * 24 from the caller's buffer)."""
     from tinyrenderder_amd.api import PHONG, make_uniforms
     size = 2048 if cfg.startswith("c2") else 4096
     hd = scenes.head_standin(7, size, size)
@@ -353,8 +357,12 @@ def test_baseline_phong_configs_full_size(cfg):
     slots = (0, -1, -1) if cfg.startswith("c2") else (0, 1, 2)
     tex = {0: d} if cfg.startswith("c2") else {0: d, 1: n, 2: s}
     args = (hd["model_view"], hd["key"], hd["fill"], hd["rim"], 1.0) + slots
-    st = check(cases.make_case(size, size, [(PHONG, make_uniforms(*args), hd["clip"], hd["varyings"], None)], textures=tex))[2]
-    assert st[1] > 100_000          # the head covers a good part of the screen
+    case = cases.make_case(size, size, [(PHONG, make_uniforms(*args), hd["clip"], hd["varyings"], None)], textures=tex)
+    if cfg not in baseline_oracle_frames:
+        baseline_oracle_frames[cfg] = cases.run_oracle(case)
+    got = cases.run_gpu(cases.on_device(case) if memory == "device" else case)
+    same(got, baseline_oracle_frames[cfg], eye=cases.has_eye(case))
+    assert got[2][1] > 100_000          # the head covers a good part of the screen
 
 
 @pytest.mark.parametrize("seed", range(12))

@@ -223,6 +223,20 @@ def _ptr(a):
     return a.ctypes.data
 
 
+def _device_ptr(a, what="array"):
+    """The address of an array handed over with device=True: an int (a raw device pointer), or an object with data_ptr() whose
+    is_cuda is true (a torch CUDA tensor); None stays None.  Anything else - a numpy array, a CPU tensor - raises TypeError
+    before the library is called: its address would reach a kernel as it is."""
+    if a is None:
+        return None
+    if isinstance(a, int) and not isinstance(a, bool):
+        return a
+    if hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) is True:
+        return a.data_ptr()
+    raise TypeError(f"device=True: {what} must be a device tensor or an int device pointer, not {type(a).__name__}"
+                    + (" in host memory" if hasattr(a, "data_ptr") else ""))
+
+
 def tga_encode(img, vflip: bool = True, rle: bool = True) -> bytes:
     """The bytes the reference's TGAImage::write_tga_file would write for an [h,w,bpp] uint8 image (host only)."""
     L = load_library()
@@ -348,7 +362,8 @@ class Context:
 
     def draw(self, kind, clip, varyings=None, colors=None, uniforms=None, n=None, device=False):
         """Host arrays (numpy) are copied before return; with device=True pass torch CUDA tensors (or raw
-        pointers with n) that stay alive until the flush has completed."""
+        pointers with n) that stay alive until the flush has completed: every array of such a draw, a host array
+        among them is a TypeError (_device_ptr).  include/trgl.h, TRGL_MEM_DEVICE: alignment and stream ordering."""
         # (a kind in the user range that was not registered here goes to the library, which refuses it)
         K = self._user_vary.get(kind, 0) if kind >= SHADER_USER_FIRST else VARY[kind]
         if not device:
@@ -360,12 +375,16 @@ class Context:
             if colors is not None:
                 colors = np.ascontiguousarray(colors, np.uint32)
                 assert colors.shape == (n,)
+            ptrs = (_ptr(clip), _ptr(varyings) if K else None, _ptr(colors))
         else:
+            ptrs = (_device_ptr(clip, "clip"), _device_ptr(varyings, "varyings"), _device_ptr(colors, "colors"))
+            if not K:
+                ptrs = (ptrs[0], None, ptrs[2])
             assert n is not None or hasattr(clip, "shape")
             n = clip.shape[0] if n is None else n
             self._keep.append((clip, varyings, colors))
-        self._chk(self.L.trgl_draw(self.h, kind, None if uniforms is None else C.byref(uniforms), _ptr(clip),
-                                   _ptr(varyings) if K else None, _ptr(colors), int(n), MEM_DEVICE if device else MEM_HOST))
+        self._chk(self.L.trgl_draw(self.h, kind, None if uniforms is None else C.byref(uniforms), ptrs[0], ptrs[1], ptrs[2], int(n),
+                                   MEM_DEVICE if device else MEM_HOST))
 
     def draw_indexed(self, kind, uniforms, projection, vertices, indices, device=False):
         """Vertex stage on the device (main.cpp:71-90) + draw.  vertices [nv, stride>=8] f64, indices [nf,3] u32."""
@@ -373,12 +392,14 @@ class Context:
         if not device:
             vertices = np.ascontiguousarray(vertices, np.float64)
             indices = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+            ptrs = (_ptr(vertices), _ptr(indices))
         else:
+            ptrs = (_device_ptr(vertices, "vertices"), _device_ptr(indices, "indices"))
             self._keep.append((vertices, indices))
         nv, stride = vertices.shape
         nf = indices.shape[0]
-        self._chk(self.L.trgl_draw_indexed(self.h, kind, C.byref(uniforms), pj.ctypes.data_as(C.POINTER(C.c_double)), _ptr(vertices),
-                                           stride, nv, _ptr(indices), nf, MEM_DEVICE if device else MEM_HOST))
+        self._chk(self.L.trgl_draw_indexed(self.h, kind, C.byref(uniforms), pj.ctypes.data_as(C.POINTER(C.c_double)), ptrs[0],
+                                           stride, nv, ptrs[1], nf, MEM_DEVICE if device else MEM_HOST))
 
     def postprocess(self, zbuffer_image=True, ao=True, final=True, params=None):
         """main.cpp:269-311,317-362,757-783 on the device; returns dict of [h,w,3] uint8 images."""
