@@ -125,6 +125,39 @@ extern "C" {
 /* flags of trgl_shader_compile_ex / trgl_register_shader_ex */
 #define TRGL_SHADER_MAY_DISCARD 1u  /* trgl_fragment returns trgl_frag_out and is called for every z-pass, in order */
 
+/*
+ * User vertex shaders: the other half of IShader (our_gl.h:36-52), vertex(face, nth), as HIP C++ source compiled at run time for the
+ * GPU and run over an indexed mesh in place of the face loop of main.cpp:660-666.  The source defines exactly
+ *
+ *     __device__ void trgl_vertex(const trgl_vert_in& in, trgl_vert_out& out);
+ *
+ * and the prelude compiled ahead of it (the one of the fragment shaders) declares
+ *
+ *     struct trgl_vert_in {
+ *         const double* vertex;       this vertex's record: `stride` doubles, vertices + index * stride (Model::vertices, model.h:114)
+ *         int stride;
+ *         uint32_t index;             the entry of the index buffer, indices[3 * face + nth] (Model::indices, model.h:115)
+ *         int face, nth;              the arguments of IShader::vertex; nth is 0, 1 or 2
+ *         const trgl_uniforms* u;     the draw's uniform block (zeros and texture slots -1 when the draw passed NULL)
+ *         const double* projection;   the global Perspective: 16 doubles, row-major
+ *     };
+ *     struct trgl_vert_out {
+ *         double clip[4];             the return value of vertex(); (0, 0, 0, 0) until written
+ *         double* vary;               this TRIANGLE's block of K doubles (null when K = 0)
+ *     };
+ *
+ * `vary` is one block per face, shared by the three calls of that face: the memory image of the shader's varying member arrays,
+ * exactly what a fragment kind with the same K receives as trgl_frag_in::vary (and what describe() hands over in the shim).  It
+ * is zero before the calls; call `nth` writes the slots that belong to it, as `varying_uv[nth] = ...` does in main.cpp:75-87, and a
+ * slot that no call writes stays 0.  The three calls of a face may run concurrently, in any order: a slot written by more than one
+ * `nth` has an undefined value, and so has the result of reading a slot that another call writes (reading `vary` at all is only
+ * meaningful for slots the same call wrote).
+ * The rest is the fragment contract: TRGL_USER_VARY is defined to K ahead of the source, the compiler flags are the ones named
+ * above, the function has no side effects beyond `out` (and writes no more than K doubles through out.vary), names starting with
+ * trgl_ are reserved, and results are bit-identical to a host build of the same body for + - * /, sqrt, conversions and comparisons.
+ */
+#define TRGL_MAX_USER_VERTEX_SHADERS 32   /* per context; numbered apart from the fragment kinds */
+
 /* doubles of varyings per triangle for each kind */
 #define TRGL_VARY_FLAT    0
 #define TRGL_VARY_GOURAUD 3
@@ -246,7 +279,7 @@ int trgl_draw(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms,
  *                          (the reference's `Vertex`, model.h:14-20, has stride 14)
  *   indices              : 3*n_faces uint32 (Model::indices, model.h:115)
  * shader_kind is TRGL_SHADER_PHONG or TRGL_SHADER_EYE, or a user kind registered with K = 24, whose varyings are then the
- * PHONG layout.  Host arrays are copied before return. */
+ * PHONG layout.  Host arrays are copied before return.  (Another vertex() body, or another K: trgl_draw_indexed_vs below.) */
 int trgl_draw_indexed(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms, const double projection[16],
                       const double* vertices, int vertex_stride, uint64_t n_vertices,
                       const uint32_t* indices, uint64_t n_faces, int mem_kind);
@@ -263,6 +296,37 @@ int trgl_register_shader(trgl_ctx* ctx, const char* source, int n_varyings, int*
  * flags = 0.  Kinds with and without the flag share the numbering and the TRGL_MAX_USER_SHADERS limit. */
 int trgl_shader_compile_ex(const char* source, int n_varyings, uint32_t flags, char* log, size_t log_len);
 int trgl_register_shader_ex(trgl_ctx* ctx, const char* source, int n_varyings, uint32_t flags, int* kind);
+
+/* User vertex shaders (see the contract above).
+ * Replaces: IShader::vertex (our_gl.h:36-52) of a subclass the library does not contain, as the face loop of main.cpp:660-666 calls it.
+ * Compile only: needs no GPU and no context.  Error codes and `log` as for trgl_shader_compile; a source that does not define
+ * trgl_vertex is a compile error whose log names trgl_vertex.  The process-wide cache keeps a vertex program apart from a fragment
+ * program with the same text. */
+int trgl_vertex_shader_compile(const char* source, int n_varyings, char* log, size_t log_len);
+/* Replaces: constructing that IShader subclass (our_gl.h:36-52; main.cpp:660-666 then calls its vertex()).  Compile (or take from the
+ * cache) and load on the context's device; *vs = i for the i-th registration on this context, counted apart from the fragment kinds,
+ * at most TRGL_MAX_USER_VERTEX_SHADERS.  The module belongs to the context and is unloaded by trgl_destroy. */
+int trgl_register_vertex_shader(trgl_ctx* ctx, const char* source, int n_varyings, int* vs);
+/* Replaces: the face loop `for v in 0..2: clip[v] = shader.vertex(face, v); rasterize(clip, shader, framebuffer)` (main.cpp:660-666)
+ * for ANY IShader (our_gl.h:36-52): trgl_vertex of `vs` runs over the indexed mesh on the device, then the faces are drawn with
+ * shader_kind as trgl_draw would draw them - any built-in or user kind, discarding ones included, whose K equals the vertex shader's.
+ *   vertices : n_vertices x vertex_stride doubles, in whatever layout trgl_vertex reads (vertex_stride >= 1)
+ *   indices  : 3 * n_faces uint32; host indices are checked against n_vertices
+ *   colors   : n_faces x uint32, one per face as for trgl_draw, or NULL
+ * uniforms may be NULL where trgl_draw allows it (trgl_vertex then sees zeros and texture slots -1).  Host arrays are copied before
+ * return; for TRGL_MEM_DEVICE arrays the rules written for trgl_draw_indexed hold (colors: those of trgl_draw).
+ * TRGL_E_INVALID for an unknown vs or kind, kinds whose K differ, a null array, or a host index out of range. */
+int trgl_draw_indexed_vs(trgl_ctx* ctx, int vs, int shader_kind, const trgl_uniforms* uniforms, const double projection[16],
+                         const double* vertices, int vertex_stride, uint64_t n_vertices,
+                         const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind);
+/* Replaces: the vertex() calls of that loop alone (our_gl.h:36-52, main.cpp:660-666), for a caller that wants their results - to
+ * check them, or to draw one transform several times with trgl_draw.  clip_out receives n_faces x 12 doubles and vary_out n_faces x K
+ * (may be NULL when K = 0), in host or device memory as mem_kind says for ALL five arrays.  vs = -1 selects the built-in stage of
+ * trgl_draw_indexed (K = 24, vertex_stride >= 8, uniforms required).  Host memory: complete on return.  Device memory: queued on the
+ * context's stream, in order with the draws; the outputs must be 16-byte aligned (they are written 16 bytes at a time). */
+int trgl_vertex_stage(trgl_ctx* ctx, int vs, const trgl_uniforms* uniforms, const double projection[16],
+                      const double* vertices, int vertex_stride, uint64_t n_vertices,
+                      const uint32_t* indices, uint64_t n_faces, double* clip_out, double* vary_out, int mem_kind);
 
 /* Execute everything submitted so far (asynchronously on the context's stream). */
 int trgl_flush(trgl_ctx* ctx);

@@ -18,6 +18,7 @@ FLAT, GOURAUD, PHONG, EYE, CHECKER = 0, 1, 2, 3, 4
 VARY = {FLAT: 0, GOURAUD: 3, PHONG: 24, EYE: 24, CHECKER: 0}
 SHADER_USER_FIRST, MAX_USER_SHADERS, MAX_USER_VARY = 64, 32, 64      # user shaders: kinds handed out by Context.register_shader
 SHADER_MAY_DISCARD = 1        # TRGL_SHADER_MAY_DISCARD: the user shader's trgl_fragment returns trgl_frag_out (it can discard)
+MAX_USER_VERTEX_SHADERS = 32  # TRGL_MAX_USER_VERTEX_SHADERS: vertex shaders handed out by Context.register_vertex_shader, from 0
 MEM_HOST, MEM_DEVICE = 0, 1
 PHASE_SETUP, PHASE_BIN, PHASE_RASTER, PHASE_TOTAL, PHASE_RASTER_KERNEL = 0, 1, 2, 3, 4
 NUM_PHASES = 5        # TRGL_NUM_PHASES
@@ -34,6 +35,7 @@ SYMBOLS = [
     "trgl_postprocess", "trgl_obj_load", "trgl_obj_free",
     "trgl_gather", "trgl_rccl_unique_id", "trgl_rccl_comm_create", "trgl_rccl_comm_destroy",
     "trgl_shader_compile", "trgl_register_shader", "trgl_shader_compile_ex", "trgl_register_shader_ex",
+    "trgl_vertex_shader_compile", "trgl_register_vertex_shader", "trgl_draw_indexed_vs", "trgl_vertex_stage",
 ]
 
 
@@ -167,6 +169,12 @@ def load_library(path: str = None):
     L.trgl_register_shader.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     L.trgl_shader_compile_ex.argtypes = [C.c_char_p, C.c_int, C.c_uint32, C.c_char_p, C.c_size_t]
     L.trgl_register_shader_ex.argtypes = [vp, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_int)]
+    L.trgl_vertex_shader_compile.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.trgl_register_vertex_shader.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    L.trgl_draw_indexed_vs.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_int]
+    L.trgl_vertex_stage.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -209,6 +217,17 @@ def shader_compile(source: str, n_varyings: int, may_discard: bool = False):
     rc = L.trgl_shader_compile_ex(source.encode(), int(n_varyings), SHADER_MAY_DISCARD if may_discard else 0, log, len(log))
     if rc not in (0, -1):
         raise TrglError(f"trgl_shader_compile failed ({rc}): {log.value.decode(errors='replace')}")
+    return rc == 0, log.value.decode(errors="replace")
+
+
+def vertex_shader_compile(source: str, n_varyings: int):
+    """trgl_vertex_shader_compile: compile a user vertex shader (include/trgl.h, "User vertex shaders") without a GPU or a context.
+    Returns (ok, compiler log); raises when user shaders are unavailable (no hiprtc)."""
+    L = load_library()
+    log = C.create_string_buffer(16384)
+    rc = L.trgl_vertex_shader_compile(source.encode(), int(n_varyings), log, len(log))
+    if rc not in (0, -1):
+        raise TrglError(f"trgl_vertex_shader_compile failed ({rc}): {log.value.decode(errors='replace')}")
     return rc == 0, log.value.decode(errors="replace")
 
 
@@ -297,6 +316,7 @@ class Context:
         self.width, self.height, self.bpp, self.device = width, height, bpp, device
         self._keep = []
         self._user_vary = {}        # kind -> K of the user shaders registered here
+        self._vertex_vary = {}      # vertex shader -> K of the user vertex shaders registered here
 
     def _chk(self, rc):
         if rc != 0:
@@ -386,9 +406,43 @@ class Context:
         self._chk(self.L.trgl_draw(self.h, kind, None if uniforms is None else C.byref(uniforms), ptrs[0], ptrs[1], ptrs[2], int(n),
                                    MEM_DEVICE if device else MEM_HOST))
 
-    def draw_indexed(self, kind, uniforms, projection, vertices, indices, device=False):
-        """Vertex stage on the device (main.cpp:71-90) + draw.  vertices [nv, stride>=8] f64, indices [nf,3] u32."""
+    def register_vertex_shader(self, source: str, n_varyings: int) -> int:
+        """trgl_register_vertex_shader: compile (or take from the process cache) a user vertex shader and load it on this context;
+        returns its number (from 0, apart from the fragment kinds), for draw_indexed(vertex_shader=) and vertex_stage()."""
+        vs = C.c_int(-1)
+        self._chk(self.L.trgl_register_vertex_shader(self.h, source.encode(), int(n_varyings), C.byref(vs)))
+        self._vertex_vary[vs.value] = int(n_varyings)
+        return vs.value
+
+    def _mesh_ptrs(self, vertices, indices, colors, device):
+        """The arrays of an indexed mesh as (vertices, indices, colors, their three addresses): host arrays made contiguous, device
+        arrays checked by _device_ptr before anything reaches the library."""
+        if not device:
+            vertices = np.ascontiguousarray(vertices, np.float64)
+            indices = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+            if colors is not None:
+                colors = np.ascontiguousarray(colors, np.uint32)
+                assert colors.shape == (indices.shape[0],), colors.shape
+            return vertices, indices, colors, (_ptr(vertices), _ptr(indices), _ptr(colors))
+        return vertices, indices, colors, (_device_ptr(vertices, "vertices"), _device_ptr(indices, "indices"), _device_ptr(colors, "colors"))
+
+    def draw_indexed(self, kind, uniforms, projection, vertices, indices, device=False, vertex_shader=None, colors=None):
+        """Vertex stage on the device (main.cpp:71-90) + draw.  vertices [nv, stride>=8] f64, indices [nf,3] u32.
+        vertex_shader: a number from register_vertex_shader - its trgl_vertex runs in place of the built-in stage
+        (trgl_draw_indexed_vs): any `kind` with the vertex shader's K, vertices [nv, stride>=1] in the layout the shader reads,
+        uniforms None where draw() allows it, colors [nf] u32 per face or None."""
         pj = np.ascontiguousarray(projection, np.float64).reshape(16)
+        if vertex_shader is not None:
+            vertices, indices, colors, ptrs = self._mesh_ptrs(vertices, indices, colors, device)
+            if device:
+                self._keep.append((vertices, indices, colors))
+            nv, stride = vertices.shape
+            nf = indices.shape[0]
+            self._chk(self.L.trgl_draw_indexed_vs(self.h, int(vertex_shader), kind, None if uniforms is None else C.byref(uniforms),
+                                                  pj.ctypes.data_as(C.POINTER(C.c_double)), ptrs[0], stride, nv, ptrs[1], nf, ptrs[2],
+                                                  MEM_DEVICE if device else MEM_HOST))
+            return
+        assert colors is None, "colors: only with vertex_shader="
         if not device:
             vertices = np.ascontiguousarray(vertices, np.float64)
             indices = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
@@ -400,6 +454,29 @@ class Context:
         nf = indices.shape[0]
         self._chk(self.L.trgl_draw_indexed(self.h, kind, C.byref(uniforms), pj.ctypes.data_as(C.POINTER(C.c_double)), ptrs[0],
                                            stride, nv, ptrs[1], nf, MEM_DEVICE if device else MEM_HOST))
+
+    def vertex_stage(self, vertex_shader, uniforms, projection, vertices, indices, device=False, out=None):
+        """trgl_vertex_stage: the vertex stage alone.  vertex_shader: a number from register_vertex_shader, or -1 for the built-in
+        stage of draw_indexed (K = 24).  Host arrays: returns (clip [nf, 12], varyings [nf, K]) as numpy arrays.  device=True:
+        vertices, indices and out = (clip, varyings) are device tensors (varyings may be None when K = 0), 16-byte aligned outputs
+        that the stage fills on the context's stream; returns out."""
+        vs = int(vertex_shader)
+        K = VARY[PHONG] if vs < 0 else getattr(self, "_vertex_vary", {}).get(vs, 0)   # (an unknown number goes to the library, which refuses it)
+        pj = np.ascontiguousarray(projection, np.float64).reshape(16)
+        vertices, indices, _, ptrs = self._mesh_ptrs(vertices, indices, None, device)
+        nv, stride = vertices.shape
+        nf = indices.shape[0]
+        if device:
+            clip, vary = out
+            optrs = (_device_ptr(clip, "clip"), _device_ptr(vary, "varyings"))
+            self._keep.append((vertices, indices, clip, vary))
+        else:
+            assert out is None, "out: only with device=True"
+            clip, vary = np.zeros((nf, 12), np.float64), np.zeros((nf, K), np.float64)
+            optrs = (clip.ctypes.data, vary.ctypes.data if K else None)
+        self._chk(self.L.trgl_vertex_stage(self.h, vs, None if uniforms is None else C.byref(uniforms), pj.ctypes.data_as(C.POINTER(C.c_double)),
+                                           ptrs[0], stride, nv, ptrs[1], nf, optrs[0], optrs[1], MEM_DEVICE if device else MEM_HOST))
+        return clip, vary
 
     def postprocess(self, zbuffer_image=True, ao=True, final=True, params=None):
         """main.cpp:269-311,317-362,757-783 on the device; returns dict of [h,w,3] uint8 images."""

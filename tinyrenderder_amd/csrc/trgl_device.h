@@ -73,6 +73,20 @@ struct DrawDesc {             // one trgl_draw() call, resident on the device fo
     trgl_uniforms   u;
 };
 
+// The one argument of the kernel of a user vertex shader (vertex_user.h), filled by trgl_api.cpp: the draw's uniforms and the
+// projection travel by value, as k_vertex_stage's matrices do.
+#define TRGL_VERTEX_USER_FACES 64   // faces per block of that kernel (three threads each)
+struct VertexUserParams {
+    trgl_uniforms   u;
+    double          proj[16];     // row-major
+    const double*   vertices;     // [n_vertices][stride]
+    const uint32_t* indices;      // [3 * nfaces]
+    double*         clip;         // [nfaces][12], 16-byte aligned
+    double*         vary;         // [nfaces][K], 16-byte aligned (unused when K = 0)
+    uint32_t        nfaces;       // <= 0xffffffff / 3
+    int32_t         stride;
+};
+
 // Device-side mirror of the reference's counters (our_gl.cpp:18-22).  z range is kept as
 // order-preserving uint64 keys so atomicMin/atomicMax work on it.
 struct DevStats {

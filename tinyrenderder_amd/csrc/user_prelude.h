@@ -1,5 +1,6 @@
 // user_prelude.h — what a user shader's source sees (include/trgl.h, "User shaders"): compiled by hiprtc ahead of the source,
-// from the copy user_shaders.cpp embeds, for both contracts (shade_user.h and raster_user.h).  The sampler is the one k_shade uses (shade_common.h).
+// from the copy user_shaders.cpp embeds, for both fragment contracts (shade_user.h and raster_user.h) and for vertex shaders
+// (vertex_user.h).  The sampler is the one k_shade uses (shade_common.h).
 #pragma once
 #include "shade_common.h"
 
@@ -22,3 +23,19 @@ __device__ __forceinline__ trgl_texel trgl_sample2D(const trgl_frag_in& in, int 
     const trgl_shade::Color c = trgl_shade::tex_fetch(t, uv);
     return trgl_texel{ c.bgra, c.bytespp };
 }
+
+// ---- user vertex shaders (include/trgl.h, "User vertex shaders"; the kernel behind the source is vertex_user.h) ----
+// what IShader::vertex(face, nth) (our_gl.h:46) reads: the vertex the index buffer names, the draw's uniforms, the global Perspective
+struct trgl_vert_in {
+    const double* vertex;        // this vertex's record, `stride` doubles (Model::vertices[index])
+    int stride;
+    uint32_t index;              // the entry of the index buffer, indices[3 * face + nth]
+    int face, nth;               // the arguments of IShader::vertex; nth is 0, 1 or 2
+    const trgl_uniforms* u;      // the draw's uniform block (texture slots -1 when the draw passed none)
+    const double* projection;    // 16 doubles, row-major
+};
+// what it leaves: its return value and the shader's varying member arrays
+struct trgl_vert_out {
+    double clip[4];              // the return value of vertex(); (0, 0, 0, 0) until written
+    double* vary;                // this TRIANGLE's K doubles, shared by the three calls of the face, zero before them (null when K = 0)
+};

@@ -1,7 +1,8 @@
 // user_shaders.cpp — user shaders compiled at run time (include/trgl.h, "User shaders").
 //
 // The source of a user shader is compiled by hiprtc between the prelude (user_prelude.h) and a kernel template: the shade kernel
-// (shade_user.h), or for a shader that may discard the raster kernel (raster_user.h).  Those and the headers they include are built
+// (shade_user.h), for a shader that may discard the raster kernel (raster_user.h), or for a vertex shader the vertex-stage kernel
+// (vertex_user.h).  Those and the headers they include are built
 // into the library as text (tools/embed_sources.py) and handed to hiprtc as in-memory headers, with three stand-ins for the C headers
 // hiprtc does not have.  libhiprtc is loaded when first needed, as librccl is: without it the library loads and everything but the
 // compile calls here works.
@@ -71,7 +72,7 @@ const char* const kStubs[] = { "#pragma once\n#define INT_MIN (-2147483647 - 1)\
 struct Compiled { std::vector<char> code; std::string log; };   // the code object and the compiler's log (its warnings)
 struct Cache {
     std::mutex mu;
-    std::unordered_map<std::string, std::unique_ptr<Compiled>> entries;   // key: flags, K and source
+    std::unordered_map<std::string, std::unique_ptr<Compiled>> entries;   // key: stage (fragment flags, or vertex), K and source
 };
 Cache& cache() { static Cache c; return c; }
 
@@ -109,17 +110,9 @@ int compile(Hiprtc& rtc, const std::string& program, std::string* log, std::vect
 
 namespace trgl {
 
-int user_shader_code(const char* source, int K, uint32_t flags, std::string* log, const std::vector<char>** code) {
-    log->clear();
-    if (!source) { *log = "source is null"; return TRGL_E_INVALID; }
-    if (K < 0 || K > TRGL_MAX_USER_VARY) { *log = "n_varyings must be in 0.." + std::to_string(TRGL_MAX_USER_VARY); return TRGL_E_INVALID; }
-    if (flags & ~uint32_t(TRGL_SHADER_MAY_DISCARD)) { *log = "unknown flag bits " + std::to_string(flags & ~uint32_t(TRGL_SHADER_MAY_DISCARD)); return TRGL_E_INVALID; }
-    const bool may_discard = (flags & TRGL_SHADER_MAY_DISCARD) != 0;
-    // the user's lines keep their own numbers in the log (#line)
-    const std::string program = "#include \"user_prelude.h\"\n#define TRGL_USER_VARY " + std::to_string(K) +
-                                "\n#define TRGL_USER_MAY_DISCARD " + (may_discard ? "1" : "0") +
-                                "\n#line 1 \"user_shader\"\n" + source + "\n#include \"" + (may_discard ? "raster_user.h" : "shade_user.h") + "\"\n";
-    std::string key = "flags " + std::to_string(flags) + '\n';
+// the code object of `program` from the cache, or compiled now; `key_head` tells programs of different stages apart
+static int cached_code(const std::string& key_head, const std::string& program, std::string* log, const std::vector<char>** code) {
+    std::string key = key_head + '\n';
     for (const char* o : kOptions) { key += o; key += ' '; }
     key += '\n'; key += program;
     Cache& c = cache();
@@ -135,6 +128,31 @@ int user_shader_code(const char* source, int K, uint32_t flags, std::string* log
     *code = &obj->code;
     c.entries.emplace(key, std::move(obj));
     return TRGL_OK;
+}
+
+static bool source_and_k_ok(const char* source, int K, std::string* log) {
+    log->clear();
+    if (!source) { *log = "source is null"; return false; }
+    if (K < 0 || K > TRGL_MAX_USER_VARY) { *log = "n_varyings must be in 0.." + std::to_string(TRGL_MAX_USER_VARY); return false; }
+    return true;
+}
+
+int user_shader_code(const char* source, int K, uint32_t flags, std::string* log, const std::vector<char>** code) {
+    if (!source_and_k_ok(source, K, log)) return TRGL_E_INVALID;
+    if (flags & ~uint32_t(TRGL_SHADER_MAY_DISCARD)) { *log = "unknown flag bits " + std::to_string(flags & ~uint32_t(TRGL_SHADER_MAY_DISCARD)); return TRGL_E_INVALID; }
+    const bool may_discard = (flags & TRGL_SHADER_MAY_DISCARD) != 0;
+    // the user's lines keep their own numbers in the log (#line)
+    const std::string program = "#include \"user_prelude.h\"\n#define TRGL_USER_VARY " + std::to_string(K) +
+                                "\n#define TRGL_USER_MAY_DISCARD " + (may_discard ? "1" : "0") +
+                                "\n#line 1 \"user_shader\"\n" + source + "\n#include \"" + (may_discard ? "raster_user.h" : "shade_user.h") + "\"\n";
+    return cached_code("flags " + std::to_string(flags), program, log, code);
+}
+
+int user_vertex_shader_code(const char* source, int K, std::string* log, const std::vector<char>** code) {
+    if (!source_and_k_ok(source, K, log)) return TRGL_E_INVALID;
+    const std::string program = "#include \"user_prelude.h\"\n#define TRGL_USER_VARY " + std::to_string(K) +
+                                "\n#line 1 \"user_shader\"\n" + source + "\n#include \"vertex_user.h\"\n";
+    return cached_code("vertex", program, log, code);       // (a fragment program's key starts with "flags")
 }
 
 }  // namespace trgl
@@ -154,4 +172,17 @@ extern "C" int trgl_shader_compile_ex(const char* source, int n_varyings, uint32
 
 extern "C" int trgl_shader_compile(const char* source, int n_varyings, char* log, size_t log_len) {
     return trgl_shader_compile_ex(source, n_varyings, 0u, log, log_len);
+}
+
+extern "C" int trgl_vertex_shader_compile(const char* source, int n_varyings, char* log, size_t log_len) {
+    std::string msg;
+    const std::vector<char>* code = nullptr;
+    const int r = trgl::user_vertex_shader_code(source, n_varyings, &msg, &code);
+    if (r) trgl::set_global_error("trgl_vertex_shader_compile: " + msg);
+    if (log && log_len) {
+        const size_t n = msg.size() < log_len - 1 ? msg.size() : log_len - 1;
+        std::memcpy(log, msg.data(), n);
+        log[n] = '\0';
+    }
+    return r;
 }

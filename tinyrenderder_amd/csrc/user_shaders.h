@@ -11,9 +11,13 @@ namespace trgl {
 // TRGL_E_UNSUPPORTED (no hiprtc).  *code stays valid for the life of the process; *log is the compiler's log (a cached entry
 // returns the log of its compilation, warnings included).
 int user_shader_code(const char* source, int n_varyings, uint32_t flags, std::string* log, const std::vector<char>** code);
+// The same for a user vertex shader (vertex_user.h behind the source, which defines trgl_vertex); its cache entries are apart from
+// those of fragment shaders with the same text.
+int user_vertex_shader_code(const char* source, int n_varyings, std::string* log, const std::vector<char>** code);
 // the message trgl_last_error(NULL) returns (trgl_api.cpp)
 void set_global_error(const std::string& msg);
 // the name of the kernel in that code object: shade_user.h, or raster_user.h with TRGL_SHADER_MAY_DISCARD
 constexpr const char* USER_SHADE_KERNEL = "trgl_shade_user";
 constexpr const char* USER_RASTER_KERNEL = "trgl_raster_user";
+constexpr const char* USER_VERTEX_KERNEL = "trgl_vertex_user";       // vertex_user.h
 }  // namespace trgl

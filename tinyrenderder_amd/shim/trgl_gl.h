@@ -20,6 +20,9 @@
 //     (compiled at run time for the GPU; the contract is in include/trgl.h) and drawn through a UserShader (trgl_shaders.h);
 //     a fragment() that can discard is one too, registered with may_discard = true.  Its kind stays the same when the shim
 //     recreates its context for a framebuffer of another size.
+//   * a vertex() the device does not implement is a user vertex shader: source registered with gl_register_vertex_shader() and named
+//     by UserShader::vertex_kind (trgl_shader_desc::vertex_kind); gl_draw_model() / gl_draw_indexed() then run it in place of the
+//     built-in vertex stage, for a shader of any kind with as many varyings.
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -99,6 +102,7 @@ struct trgl_shader_desc {
     trgl_uniforms uniforms{};
     const double* varyings = nullptr;   // K doubles for `kind`, valid until rasterize() returns
     std::uint32_t color = 0xffffffffu;  // FLAT / GOURAUD
+    int vertex_kind = -1;               // gl_draw_indexed() / gl_draw_model(): a user vertex shader (gl_register_vertex_shader), -1 = the built-in stage
 };
 
 struct IShader {
@@ -142,6 +146,8 @@ struct State {
     mat<4, 4> viewport_at_batch;
     struct UserSource { std::string source; int n_varyings; bool may_discard; };
     std::vector<UserSource> user;         // gl_register_shader(): registered on every context, in order (kind = USER_FIRST + index)
+    struct VertexSource { std::string source; int n_varyings; };
+    std::vector<VertexSource> vertex;     // gl_register_vertex_shader(): likewise (vertex kind = index)
     int err = TRGL_OK;                    // first C-ABI error since gl_clear_error() (a TRGL_E_* code)
     std::string err_msg;
 };
@@ -174,6 +180,12 @@ inline bool bind(TGAImage& fb) {
             bool ok = TRGL_SHIM_OK(trgl_register_shader_ex(s.ctx, s.user[i].source.c_str(), s.user[i].n_varyings,
                                                            s.user[i].may_discard ? TRGL_SHADER_MAY_DISCARD : 0u, &kind));
             if (ok && kind != TRGL_SHADER_USER_FIRST + int(i)) ok = fail("gl_register_shader: kinds out of order", TRGL_E_STATE, nullptr);
+            if (!ok) { trgl_destroy(s.ctx); s.ctx = nullptr; return false; }
+        }
+        for (std::size_t i = 0; i < s.vertex.size(); ++i) {
+            int vs = -1;
+            bool ok = TRGL_SHIM_OK(trgl_register_vertex_shader(s.ctx, s.vertex[i].source.c_str(), s.vertex[i].n_varyings, &vs));
+            if (ok && vs != int(i)) ok = fail("gl_register_vertex_shader: vertex kinds out of order", TRGL_E_STATE, nullptr);
             if (!ok) { trgl_destroy(s.ctx); s.ctx = nullptr; return false; }
         }
         if (!TRGL_SHIM_OK(trgl_write_framebuffer(s.ctx, fb.buffer()))) return false;
@@ -241,6 +253,28 @@ inline int gl_register_shader(const char* source, int n_varyings, bool may_disca
         if (!TRGL_SHIM_OK(trgl_register_shader_ex(s.ctx, source, n_varyings, flags, &k))) { s.user.pop_back(); return -1; }
     }
     return kind;
+}
+
+// A user vertex shader (include/trgl.h, "User vertex shaders"): HIP C++ source defining trgl_vertex - the body of an
+// IShader::vertex(face, nth) the device does not implement - that leaves n_varyings doubles of varyings per triangle.  Compiled at
+// once, errors as for gl_register_shader; the number returned is what UserShader::vertex_kind takes (from 0, counted apart from the
+// fragment kinds), valid on every context the shim creates.
+inline int gl_register_vertex_shader(const char* source, int n_varyings) {
+    trgl_shim::State& s = trgl_shim::state();
+    if (s.vertex.size() >= TRGL_MAX_USER_VERTEX_SHADERS) { trgl_shim::fail("gl_register_vertex_shader", TRGL_E_INVALID, nullptr); return -1; }
+    std::string log(4096, '\0');
+    const int rc = trgl_vertex_shader_compile(source, n_varyings, &log[0], log.size());
+    if (rc != TRGL_OK) {
+        if (s.err == TRGL_OK) { s.err = rc; s.err_msg = std::string("gl_register_vertex_shader: ") + log.c_str(); }
+        return -1;
+    }
+    s.vertex.push_back({ source, n_varyings });
+    if (s.ctx) {
+        trgl_shim::submit_batch();
+        int vs = -1;
+        if (!TRGL_SHIM_OK(trgl_register_vertex_shader(s.ctx, source, n_varyings, &vs))) { s.vertex.pop_back(); return -1; }
+    }
+    return int(s.vertex.size()) - 1;
 }
 
 // ---- our_gl.h:25-31 ------------------------------------------------------------------------------
@@ -339,6 +373,9 @@ inline void rasterize(const Triangle& clip, const IShader& shader, TGAImage& fra
 // (main.cpp:71-90 = 199-218: eye = ModelView*(p,1), normal_eye = ModelView*(n,0), clip = Perspective*eye) runs on the
 // device over the indexed mesh.  `vertices`: nv rows of `stride` doubles starting with position[3], normal[3], uv[2]
 // (the reference's Vertex, model.h:14-20, has stride 14); `indices`: 3 per face.
+// A shader whose describe() names a user vertex shader (trgl_shader_desc::vertex_kind >= 0, UserShader::vertex_kind) has that
+// shader's trgl_vertex run instead (trgl_draw_indexed_vs): then any kind - built-in ones included - with as many varyings as the
+// vertex shader is drawn, every face with the descriptor's colour, and the vertex records are whatever trgl_vertex reads.
 inline bool gl_draw_indexed(const IShader& shader, const double* vertices, int stride, std::size_t nv,
                             const unsigned int* indices, std::size_t nfaces, TGAImage& framebuffer) {
     using namespace trgl_shim;
@@ -346,15 +383,29 @@ inline bool gl_draw_indexed(const IShader& shader, const double* vertices, int s
     if (!bind(framebuffer)) return false;
     bool ok = submit_batch();                                   // earlier rasterize() calls come first
     trgl_shader_desc d;
+    const bool described = shader.describe(d);
+    double vp[16], pj[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { vp[4 * r + c] = Viewport[r][c]; pj[4 * r + c] = Perspective[r][c]; }
+    static_assert(sizeof(unsigned int) == sizeof(std::uint32_t), "indices are 32-bit");
+    if (described && d.vertex_kind >= 0) {
+        if (d.vertex_kind >= int(s.vertex.size()) || s.vertex[d.vertex_kind].n_varyings != vary_count(d.kind)) {
+            std::fprintf(stderr, "trgl: gl_draw_indexed(): vertex kind %d is not a registered vertex shader with the %d varyings of shader kind %d\n",
+                         d.vertex_kind, vary_count(d.kind), d.kind);
+            std::abort();
+        }
+        const std::vector<std::uint32_t> colors(nfaces, d.color);
+        ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
+             TRGL_SHIM_OK(trgl_draw_indexed_vs(s.ctx, d.vertex_kind, d.kind, &d.uniforms, pj, vertices, stride, nv,
+                                               reinterpret_cast<const std::uint32_t*>(indices), nfaces, colors.data(), TRGL_MEM_HOST)) && ok;
+        s.zbuffer_stale_on_host = true;
+        return ok;
+    }
     // (a user kind registered with K = 24 takes the varyings the device vertex stage writes: the PHONG layout)
-    if (!shader.describe(d) || (d.kind != TRGL_SHADER_PHONG && d.kind != TRGL_SHADER_EYE &&
+    if (!described || (d.kind != TRGL_SHADER_PHONG && d.kind != TRGL_SHADER_EYE &&
                                 !(d.kind >= TRGL_SHADER_USER_FIRST && vary_count(d.kind) == TRGL_VARY_PHONG))) {
         std::fprintf(stderr, "trgl: gl_draw_indexed(): needs a PHONG or EYE shader, or a user shader with 24 varyings, with a device descriptor\n");
         std::abort();
     }
-    double vp[16], pj[16];
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { vp[4 * r + c] = Viewport[r][c]; pj[4 * r + c] = Perspective[r][c]; }
-    static_assert(sizeof(unsigned int) == sizeof(std::uint32_t), "indices are 32-bit");
     ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
          TRGL_SHIM_OK(trgl_draw_indexed(s.ctx, d.kind, &d.uniforms, pj, vertices, stride, nv,
                                         reinterpret_cast<const std::uint32_t*>(indices), nfaces, TRGL_MEM_HOST)) && ok;

@@ -1,8 +1,8 @@
 // trgl_shaders.h — the shader kinds the device implements, as IShader subclasses with the reference's member
 // names (main.cpp:39-90, 176-218) so a main.cpp-shaped face loop compiles unchanged:
 //     for v in 0..2: clip[v] = shader.vertex(face, v);  rasterize(clip, shader, framebuffer);
-// vertex() runs on the host (3 mat*vec per vertex, as in the reference); fragment() runs on the GPU, selected by
-// describe().  `ModelT` is anything with vert(face,v), normal(face,v), uv(face,v) and texture slots.
+// vertex() runs on the host (3 mat*vec per vertex, as in the reference) - or, through gl_draw_model(), on the device: the built-in
+// stage, or a user vertex shader (UserShader::vertex_kind); fragment() runs on the GPU, selected by describe().  `ModelT` is anything with vert(face,v), normal(face,v), uv(face,v) and texture slots.
 #pragma once
 #include "trgl_gl.h"
 
@@ -34,19 +34,24 @@ struct GouraudShader : IShader {
 // as it is (texture slots -1 by default).  Varyings of another size are a programming error: rasterize() aborts.  Through
 // gl_draw_model() / gl_draw_indexed() (a kind registered with K = 24) the device vertex stage makes the varyings: `varyings` and
 // `color` are not used there (trgl_frag_in::color is 0xffffffff).
+// vertex_kind: a user vertex shader (gl_register_vertex_shader), -1 = none.  With one, gl_draw_model() / gl_draw_indexed() run its
+// trgl_vertex over the mesh in place of the built-in stage; `kind` may then also be a BUILT-IN kind (TRGL_SHADER_GOURAUD with a
+// vertex shader of 3 varyings, say), the varyings are the vertex shader's, and every face gets `color`.
 struct UserShader : IShader {
     int kind = -1;
+    int vertex_kind = -1;
     std::vector<double> varyings;
     TGAColor color = TGAColor(255, 255, 255);
     trgl_uniforms uniforms{};
     UserShader() { uniforms.tex_diffuse = uniforms.tex_normal = uniforms.tex_specular = -1; }
     explicit UserShader(int k) : UserShader() { kind = k; }
     bool describe(trgl_shader_desc& d) const override {
-        if (kind < TRGL_SHADER_USER_FIRST || kind - TRGL_SHADER_USER_FIRST >= int(trgl_shim::state().user.size())) {
+        const bool builtin = vertex_kind >= 0 && kind >= 0 && kind < TRGL_NUM_SHADERS;        // (drawn through the vertex shader only)
+        if (!builtin && (kind < TRGL_SHADER_USER_FIRST || kind - TRGL_SHADER_USER_FIRST >= int(trgl_shim::state().user.size()))) {
             std::fprintf(stderr, "trgl: UserShader: kind %d is not a registered user shader\n", kind);
             return false;
         }
-        d.kind = kind; d.uniforms = uniforms; d.color = trgl_shim::pack_bgra(color);
+        d.kind = kind; d.uniforms = uniforms; d.color = trgl_shim::pack_bgra(color); d.vertex_kind = vertex_kind;
         d.varyings = int(varyings.size()) == trgl_shim::vary_count(kind) ? varyings.data() : nullptr;   // (rasterize() checks)
         return true;
     }
