@@ -393,6 +393,47 @@ void trgl_ssao_defaults(trgl_ssao_params* p);
  * computed too (it is, internally).  params NULL = the reference's constants.  Implies flush + sync. */
 int trgl_postprocess(trgl_ctx* ctx, const trgl_ssao_params* params, uint8_t* zbuffer_image, uint8_t* ao_map, uint8_t* final_image);
 
+/* ---- scene logic around the draws: model bounds, frustum culling, depth snapshots ------------------- */
+
+/* Replaces: Model::computeAABB (model.cpp:15-40) for a mesh in host memory or in HBM: the position sits at +0 of each record of
+ * vertex_stride >= 3 doubles (vertices 8-byte aligned, as for trgl_draw_indexed).  out_min / out_max receive localAABB.min / .max,
+ * bit for bit: zeros for an empty mesh (:16-19); else the running std::min / std::max from 1e9 / -1e9 (:21-32: a NaN never replaces a
+ * bound, and of values that compare equal - +0.0 and -0.0 - the earlier vertex stays), then the margin (max - min) * 0.01 subtracted
+ * and added (:35-36).  TRGL_MEM_HOST: plain C++, ctx may be NULL, no GPU is touched.  TRGL_MEM_DEVICE: a reduction queued on the
+ * context's stream in order with the draws (the mesh must be complete on that stream, as for trgl_draw_indexed), which carries
+ * (value, vertex index) pairs so that the result does not depend on how the GPU schedules it; the call waits for the 48 bytes
+ * (one stream sync, like trgl_get_stats) but does not flush queued draws. */
+int trgl_mesh_bounds(trgl_ctx* ctx, const double* vertices, int vertex_stride, uint64_t n_vertices,
+                     int mem_kind, double out_min[3], double out_max[3]);
+
+/* Replaces: AABB::transform (geometry.h:297-327), the body of Model::getWorldAABB: the eight corners (x fastest, then y, then z) times
+ * the row-major m, each divided by its w WITHOUT a guard (w = 0 gives inf / NaN exactly as the reference), folded with std::min /
+ * std::max from 1e9 / -1e9.  Needs no GPU and no context. */
+int trgl_aabb_transform(const double bmin[3], const double bmax[3], const double m[16], double out_min[3], double out_max[3]);
+/* Replaces: Frustum::createFromMatrix (our_gl.cpp:212-262).  planes: LEFT, RIGHT, BOTTOM, TOP, NEAR, FAR (Frustum::PlaneIndex,
+ * our_gl.h:71-78), each nx, ny, nz, d.  Literally what the reference adds: normal = (m[0][3] +- m[0][k], m[1][3] +- m[1][k],
+ * m[2][3] +- m[2][k]) and d = m[3][3] +- m[3][k] with k = 0, 1, 2 for the three pairs, then all four divided by |normal| when that is
+ * > 0.0 (:253-259).  Needs no GPU and no context. */
+int trgl_frustum_from_matrix(const double m[16], double planes[24]);
+/* Replaces: Frustum::intersects (our_gl.cpp:264-280): per plane the corner with max where the normal's component is >= 0 and min
+ * elsewhere; outside when dot(normal, corner) + d < 0 (Plane::distance, geometry.h:264-266; a distance of exactly 0 intersects).
+ * Returns 1 (intersects), 0 (culled) or TRGL_E_INVALID for a null argument.  Needs no GPU and no context. */
+int trgl_frustum_intersects(const double planes[24], const double bmin[3], const double bmax[3]);
+
+/* Depth snapshots kept in HBM.
+ * trgl_zbuffer_snapshot replaces: `std::vector<double> zbuffer_before_eyes = zbuffer;` (main.cpp:700);
+ * trgl_zbuffer_restore  replaces: `zbuffer = zbuffer_before_eyes;` (main.cpp:730), after which save_zbuffer_image and the SSAO loop
+ * (main.cpp:751-763, trgl_postprocess) see the depths without the eyes.
+ * Both complete a begun flush, flush what is queued (a pending trgl_clear included) and queue ONE device-to-device copy of all W * H
+ * depths on the context's stream; neither waits, and neither touches the framebuffer or the counters (the reference's assignments do
+ * not).  On a strip / band context the whole buffer is copied: rows outside the strip are as stale afterwards as before.
+ * A slot is allocated when first used and freed by trgl_zbuffer_snapshot_free or trgl_destroy.
+ * TRGL_E_INVALID: slot outside 0..TRGL_MAX_Z_SNAPSHOTS-1; TRGL_E_STATE: restore from a slot that holds nothing; TRGL_E_NOMEM. */
+#define TRGL_MAX_Z_SNAPSHOTS 4
+int trgl_zbuffer_snapshot(trgl_ctx* ctx, int slot);
+int trgl_zbuffer_restore(trgl_ctx* ctx, int slot);
+int trgl_zbuffer_snapshot_free(trgl_ctx* ctx, int slot);
+
 /* ---- TGA writer and reader (host only) ------------------------------------- */
 
 /* Replaces: TGAImage::write_tga_file(name, vflip, rle) (tgaimage.cpp:161-242): produces exactly the bytes the

@@ -23,6 +23,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 PHASE_SETUP, PHASE_BIN, PHASE_RASTER, PHASE_TOTAL, PHASE_RASTER_KERNEL = 0, 1, 2, 3, 4
 NUM_PHASES = 5        # TRGL_NUM_PHASES
 MAX_TEXTURES = 16
+MAX_Z_SNAPSHOTS = 4           # TRGL_MAX_Z_SNAPSHOTS
+FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
 
 # every symbol include/trgl.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -36,6 +38,8 @@ SYMBOLS = [
     "trgl_gather", "trgl_rccl_unique_id", "trgl_rccl_comm_create", "trgl_rccl_comm_destroy",
     "trgl_shader_compile", "trgl_register_shader", "trgl_shader_compile_ex", "trgl_register_shader_ex",
     "trgl_vertex_shader_compile", "trgl_register_vertex_shader", "trgl_draw_indexed_vs", "trgl_vertex_stage",
+    "trgl_mesh_bounds", "trgl_aabb_transform", "trgl_frustum_from_matrix", "trgl_frustum_intersects",
+    "trgl_zbuffer_snapshot", "trgl_zbuffer_restore", "trgl_zbuffer_snapshot_free",
 ]
 
 
@@ -175,6 +179,12 @@ def load_library(path: str = None):
                                        C.c_void_p, C.c_int]
     L.trgl_vertex_stage.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64,
                                     C.c_void_p, C.c_void_p, C.c_int]
+    L.trgl_mesh_bounds.argtypes = [vp, C.c_void_p, C.c_int, C.c_uint64, C.c_int, dp, dp]
+    L.trgl_aabb_transform.argtypes = [dp, dp, dp, dp, dp]
+    L.trgl_frustum_from_matrix.argtypes = [dp, dp]
+    L.trgl_frustum_intersects.argtypes = [dp, dp, dp]
+    for name in ("trgl_zbuffer_snapshot", "trgl_zbuffer_restore", "trgl_zbuffer_snapshot_free"):
+        getattr(L, name).argtypes = [vp, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -254,6 +264,66 @@ def _device_ptr(a, what="array"):
         return a.data_ptr()
     raise TypeError(f"device=True: {what} must be a device tensor or an int device pointer, not {type(a).__name__}"
                     + (" in host memory" if hasattr(a, "data_ptr") else ""))
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _f64(a, n, what):
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    if a.size != n:
+        raise ValueError(f"{what}: {n} doubles expected, got {a.size}")
+    return a
+
+
+def _mesh_bounds(L, handle, vertices, device):
+    lo, hi = np.empty(3, np.float64), np.empty(3, np.float64)
+    if device:
+        ptr = _device_ptr(vertices, "vertices")
+    else:
+        vertices = np.ascontiguousarray(vertices, np.float64)
+        ptr = vertices.ctypes.data
+    if len(vertices.shape) != 2:
+        raise ValueError("mesh_bounds: vertices must be [n, stride]")
+    nv, stride = vertices.shape
+    rc = L.trgl_mesh_bounds(handle, ptr, int(stride), int(nv), MEM_DEVICE if device else MEM_HOST, _dp(lo), _dp(hi))
+    if rc != 0:
+        raise TrglError(f"trgl_mesh_bounds failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return lo, hi
+
+
+def mesh_bounds(vertices):
+    """trgl_mesh_bounds for a host array without a context: Model::computeAABB (model.cpp:15-40) of vertices [n, stride >= 3] with the
+    position at +0; returns (min[3], max[3]) with the reference's 1 % margin.  Needs no GPU."""
+    return _mesh_bounds(load_library(), None, vertices, False)
+
+
+def aabb_transform(bmin, bmax, m):
+    """trgl_aabb_transform: AABB::transform (geometry.h:297-327) of the box by the row-major 4x4 m; returns (min[3], max[3])."""
+    lo, hi = np.empty(3, np.float64), np.empty(3, np.float64)
+    rc = load_library().trgl_aabb_transform(_dp(_f64(bmin, 3, "bmin")), _dp(_f64(bmax, 3, "bmax")), _dp(_f64(m, 16, "m")), _dp(lo), _dp(hi))
+    if rc != 0:
+        raise TrglError(f"trgl_aabb_transform failed ({rc})")
+    return lo, hi
+
+
+def frustum_from_matrix(m):
+    """trgl_frustum_from_matrix: Frustum::createFromMatrix (our_gl.cpp:212-262); returns planes [6, 4] = nx, ny, nz, d in the order
+    FRUSTUM_LEFT .. FRUSTUM_FAR."""
+    planes = np.empty((6, 4), np.float64)
+    rc = load_library().trgl_frustum_from_matrix(_dp(_f64(m, 16, "m")), _dp(planes))
+    if rc != 0:
+        raise TrglError(f"trgl_frustum_from_matrix failed ({rc})")
+    return planes
+
+
+def frustum_intersects(planes, bmin, bmax) -> bool:
+    """trgl_frustum_intersects: Frustum::intersects (our_gl.cpp:264-280)."""
+    rc = load_library().trgl_frustum_intersects(_dp(_f64(planes, 24, "planes")), _dp(_f64(bmin, 3, "bmin")), _dp(_f64(bmax, 3, "bmax")))
+    if rc < 0:
+        raise TrglError(f"trgl_frustum_intersects failed ({rc})")
+    return rc == 1
 
 
 def tga_encode(img, vflip: bool = True, rle: bool = True) -> bytes:
@@ -477,6 +547,22 @@ class Context:
         self._chk(self.L.trgl_vertex_stage(self.h, vs, None if uniforms is None else C.byref(uniforms), pj.ctypes.data_as(C.POINTER(C.c_double)),
                                            ptrs[0], stride, nv, ptrs[1], nf, optrs[0], optrs[1], MEM_DEVICE if device else MEM_HOST))
         return clip, vary
+
+    def mesh_bounds(self, vertices, device=False):
+        """trgl_mesh_bounds: Model::computeAABB (model.cpp:15-40) of vertices [n, stride >= 3]; returns (min[3], max[3]).  device=True:
+        a device tensor, reduced on the context's stream in order with the draws (nothing is flushed); the call waits for the result."""
+        return _mesh_bounds(self.L, self.h, vertices, device)
+
+    def zbuffer_snapshot(self, slot=0):
+        """trgl_zbuffer_snapshot: main.cpp:700 as one device-to-device copy (flushes what is queued, does not wait)."""
+        self._chk(self.L.trgl_zbuffer_snapshot(self.h, int(slot)))
+
+    def zbuffer_restore(self, slot=0):
+        """trgl_zbuffer_restore: main.cpp:730 likewise; the framebuffer and the stats stay as they are."""
+        self._chk(self.L.trgl_zbuffer_restore(self.h, int(slot)))
+
+    def zbuffer_snapshot_free(self, slot=0):
+        self._chk(self.L.trgl_zbuffer_snapshot_free(self.h, int(slot)))
 
     def postprocess(self, zbuffer_image=True, ao=True, final=True, params=None):
         """main.cpp:269-311,317-362,757-783 on the device; returns dict of [h,w,3] uint8 images."""

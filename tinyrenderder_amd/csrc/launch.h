@@ -61,6 +61,13 @@ void launch_ssao(hipStream_t s, const double* zb, int W, int H, const double* di
                  double radius, double threshold, double intensity, uint8_t* out);
 void launch_composite(hipStream_t s, const uint8_t* fb, int bpp, const uint8_t* ao, int W, int H, uint8_t* out);
 
+// Model::computeAABB (model.cpp:15-40) over `n` vertex records of `stride` doubles in device memory (8-byte aligned).
+// scratch: 1 + MESH_BOUNDS_MAX_BLOCKS entries; entry 0 receives the result - v[0..2] = AABB min, v[3..5] = AABB max, margin applied -
+// and the others the per-block partials of the first launch, which the second (one block) folds.  n > 0.
+struct BoundsPartial { double v[6]; unsigned long long i[6]; };      // running min x, y, z, max x, y, z and the vertex each came from
+constexpr uint32_t MESH_BOUNDS_MAX_BLOCKS = 1024;
+void launch_mesh_bounds(hipStream_t s, const double* vertices, int stride, uint64_t n, BoundsPartial* scratch);
+
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,
                               unsigned long long* mismatches);

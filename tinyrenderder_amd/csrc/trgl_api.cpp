@@ -45,6 +45,8 @@ template <class T> struct DevBuf {
     // at least `need` elements: `ncap` of them (by default headroom(need)) when the buffer has to grow
     int grow(trgl_ctx* c, size_t need, size_t ncap) { return need <= cap ? TRGL_OK : alloc(c, ncap); }
     int grow(trgl_ctx* c, size_t need) { return grow(c, need, headroom(need)); }
+    // give the memory back before the owner goes (the stream is synchronised first)
+    int release(trgl_ctx* c);
 };
 // ... and of the pair buffers: a multiple of 4 entries (k_radix_hist reads 16 bytes at a time, k_raster 4 entries), at most 0xffffe000 (grids are sized by
 // cap + 4095 in 32 bits; a flush of 2^32 - 16 pairs and more is refused)
@@ -91,6 +93,8 @@ struct trgl_ctx {
     PendingRaster rp;
     hipEvent_t ev_pairs = nullptr;      // recorded behind the copy of the flush's pair count into pinned memory
     DevBuf<uint32_t> idbuf;             // visibility buffer of PHONG / EYE flushes, [H][W]
+    DevBuf<BoundsPartial> bounds_scratch;   // trgl_mesh_bounds: the result + the per-block partials, allocated by the first call
+    DevBuf<double> zsnap[TRGL_MAX_Z_SNAPSHOTS];   // trgl_zbuffer_snapshot: [H][W] depths per slot in use
     DevBuf<uint8_t> pp_out;             // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
     DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
@@ -137,6 +141,11 @@ template <class T> int DevBuf<T>::alloc(trgl_ctx* c, size_t n) {
     if (p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p)); p = nullptr; cap = 0; }
     HIPCHK(c, hipMalloc((void**)&p, n * sizeof(T)));
     cap = n;
+    return TRGL_OK;
+}
+
+template <class T> int DevBuf<T>::release(trgl_ctx* c) {
+    if (p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(p)); p = nullptr; cap = 0; }
     return TRGL_OK;
 }
 
@@ -886,6 +895,129 @@ int trgl_format_stats(const trgl_stats* s, char* buf, size_t buflen) {   // our_
                           (unsigned long long)s->triangles_rasterized, (unsigned long long)s->fragments_drawn,
                           s->min_x, s->min_y, s->max_x, s->max_y, lo, hi);
     return (n < 0 || (size_t)n >= buflen) ? TRGL_E_INVALID : TRGL_OK;
+}
+
+// ---- scene logic around the draws (model.cpp:15-40, geometry.h:264-266,297-327, our_gl.cpp:212-280) ------------------------------
+// std::min(a, b) = (b < a) ? b : a and std::max(a, b) = (a < b) ? b : a with a the running bound: what decides NaNs and signed zeros
+static inline double keep_min(double bound, double p) { return p < bound ? p : bound; }
+static inline double keep_max(double bound, double p) { return bound < p ? p : bound; }
+// dot<n> (geometry.h:122-127): summed left to right from 0
+static inline double dot3_from_zero(const double* a, double x, double y, double z) { double sum = 0; sum += a[0] * x; sum += a[1] * y; sum += a[2] * z; return sum; }
+
+int trgl_mesh_bounds(trgl_ctx* c, const double* vertices, int stride, uint64_t n, int mem_kind, double out_min[3], double out_max[3]) {
+    auto bad = [&](const char* msg) { if (c) c->err = msg; else g_create_error = msg; return TRGL_E_INVALID; };
+    if (!out_min || !out_max) return bad("trgl_mesh_bounds: null output");
+    if (mem_kind != TRGL_MEM_HOST && mem_kind != TRGL_MEM_DEVICE) return bad("trgl_mesh_bounds: bad mem_kind");
+    if (stride < 3) return bad("trgl_mesh_bounds: vertex stride must be >= 3 doubles (the position)");
+    if (n && !vertices) return bad("trgl_mesh_bounds: vertices is null");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return bad("trgl_mesh_bounds: TRGL_MEM_DEVICE needs a context");
+    if (n == 0) {                                                               // model.cpp:16-19
+        for (int a = 0; a < 3; ++a) out_min[a] = out_max[a] = 0.0;
+        return TRGL_OK;
+    }
+    if (mem_kind == TRGL_MEM_HOST) {
+        double lo[3] = { 1e9, 1e9, 1e9 }, hi[3] = { -1e9, -1e9, -1e9 };         // :21-22
+        for (uint64_t i = 0; i < n; ++i) {
+            const double* p = vertices + i * (uint64_t)stride;
+            for (int a = 0; a < 3; ++a) lo[a] = keep_min(lo[a], p[a]);          // :25-27
+            for (int a = 0; a < 3; ++a) hi[a] = keep_max(hi[a], p[a]);          // :29-31
+        }
+        for (int a = 0; a < 3; ++a) {
+            const double margin = (hi[a] - lo[a]) * 0.01;                       // :35
+            out_min[a] = lo[a] - margin; out_max[a] = hi[a] + margin;           // :36
+        }
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    if (!c->bounds_scratch.p && (r = c->bounds_scratch.alloc(c, 1 + MESH_BOUNDS_MAX_BLOCKS))) return r;
+    launch_mesh_bounds(c->stream, vertices, stride, n, c->bounds_scratch.p);
+    HIPCHK(c, hipGetLastError());
+    double res[6];
+    HIPCHK(c, hipMemcpyAsync(res, c->bounds_scratch.p->v, sizeof(res), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int a = 0; a < 3; ++a) { out_min[a] = res[a]; out_max[a] = res[3 + a]; }
+    return TRGL_OK;
+}
+
+int trgl_aabb_transform(const double bmin[3], const double bmax[3], const double m[16], double out_min[3], double out_max[3]) {
+    if (!bmin || !bmax || !m || !out_min || !out_max) return TRGL_E_INVALID;
+    double lo[3] = { 1e9, 1e9, 1e9 }, hi[3] = { -1e9, -1e9, -1e9 };             // geometry.h:309-310
+    for (int i = 0; i < 8; ++i) {                                               // :300-307: corner i takes max.x for bit 0, max.y for bit 1, max.z for bit 2
+        const double x = (i & 1) ? bmax[0] : bmin[0], y = (i & 2) ? bmax[1] : bmin[1], z = (i & 4) ? bmax[2] : bmin[2];
+        double t[4];
+        for (int row = 0; row < 4; ++row) {                                     // :314, mat * vec4(corner, 1.0): one dot<4> per row
+            double sum = 0;
+            sum += m[4 * row] * x; sum += m[4 * row + 1] * y; sum += m[4 * row + 2] * z; sum += m[4 * row + 3] * 1.0;
+            t[row] = sum;
+        }
+        for (int a = 0; a < 3; ++a) {
+            const double pos = t[a] / t[3];                                     // :315, no guard
+            lo[a] = keep_min(lo[a], pos);                                       // :317-319
+            hi[a] = keep_max(hi[a], pos);                                       // :321-323
+        }
+    }
+    for (int a = 0; a < 3; ++a) { out_min[a] = lo[a]; out_max[a] = hi[a]; }
+    return TRGL_OK;
+}
+
+int trgl_frustum_from_matrix(const double m[16], double planes[24]) {
+    if (!m || !planes) return TRGL_E_INVALID;
+    for (int pair = 0; pair < 3; ++pair)                                        // our_gl.cpp:217-250: LEFT/RIGHT with k = 0, BOTTOM/TOP 1, NEAR/FAR 2
+        for (int side = 0; side < 2; ++side) {
+            double* pl = planes + 4 * (2 * pair + side);
+            for (int row = 0; row < 4; ++row)                                   // rows 0..2 give the normal, row 3 gives d
+                pl[row] = side == 0 ? m[4 * row + 3] + m[4 * row + pair] : m[4 * row + 3] - m[4 * row + pair];
+        }
+    for (int i = 0; i < 6; ++i) {                                               // :253-259
+        double* pl = planes + 4 * i;
+        const double length = std::sqrt(dot3_from_zero(pl, pl[0], pl[1], pl[2]));
+        if (length > 0.0) { pl[0] = pl[0] / length; pl[1] = pl[1] / length; pl[2] = pl[2] / length; pl[3] /= length; }
+    }
+    return TRGL_OK;
+}
+
+int trgl_frustum_intersects(const double planes[24], const double bmin[3], const double bmax[3]) {
+    if (!planes || !bmin || !bmax) return TRGL_E_INVALID;
+    for (int i = 0; i < 6; ++i) {                                               // our_gl.cpp:265-278
+        const double* pl = planes + 4 * i;
+        double positive[3] = { bmin[0], bmin[1], bmin[2] };                     // :269
+        for (int a = 0; a < 3; ++a) if (pl[a] >= 0) positive[a] = bmax[a];      // :270-272
+        if (dot3_from_zero(pl, positive[0], positive[1], positive[2]) + pl[3] < 0) return 0;   // :275, Plane::distance
+    }
+    return 1;
+}
+
+static int zsnap_slot(trgl_ctx* c, int slot, const char* who) {
+    if (slot >= 0 && slot < TRGL_MAX_Z_SNAPSHOTS) return TRGL_OK;
+    c->err = std::string(who) + ": slot must be 0.." + std::to_string(TRGL_MAX_Z_SNAPSHOTS - 1);
+    return TRGL_E_INVALID;
+}
+
+int trgl_zbuffer_snapshot(trgl_ctx* c, int slot) {
+    CHKCTX(c);
+    int r = zsnap_slot(c, slot, "trgl_zbuffer_snapshot"); if (r) return r;
+    if ((r = trgl_flush(c))) return r;                // completes a begun flush, draws what is queued, runs a pending clear
+    const size_t npx = (size_t)c->W * c->H;
+    if (!c->zsnap[slot].p && c->zsnap[slot].alloc(c, npx)) return fail(c, TRGL_E_NOMEM, "trgl_zbuffer_snapshot: out of device memory");
+    HIPCHK(c, hipMemcpyAsync(c->zsnap[slot].p, c->zb.p, npx * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return TRGL_OK;
+}
+
+int trgl_zbuffer_restore(trgl_ctx* c, int slot) {
+    CHKCTX(c);
+    int r = zsnap_slot(c, slot, "trgl_zbuffer_restore"); if (r) return r;
+    if (!c->zsnap[slot].p) return fail(c, TRGL_E_STATE, "trgl_zbuffer_restore: the slot holds no snapshot");
+    if ((r = trgl_flush(c))) return r;                // what is queued was submitted against the depths as they are now
+    HIPCHK(c, hipMemcpyAsync(c->zb.p, c->zsnap[slot].p, (size_t)c->W * c->H * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return TRGL_OK;
+}
+
+int trgl_zbuffer_snapshot_free(trgl_ctx* c, int slot) {
+    CHKCTX(c);
+    int r = zsnap_slot(c, slot, "trgl_zbuffer_snapshot_free"); if (r) return r;
+    if ((r = end_pending_raster(c))) return r;
+    return c->zsnap[slot].release(c);
 }
 
 void* trgl_framebuffer_device_ptr(trgl_ctx* c) { return c ? c->fb.p : nullptr; }

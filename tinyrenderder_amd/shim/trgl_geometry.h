@@ -1,4 +1,4 @@
-// trgl_geometry.h — the small value types the shim and the demo caller use: vec2 / vec3 / vec4 and mat<R,C>.
+// trgl_geometry.h — the small value types the shim and the demo caller use: vec2 / vec3 / vec4, mat<R,C>, Plane and AABB.
 //
 // A maintainer who puts the library under the reference's main.cpp keeps the reference's own geometry.h: define
 // TRGL_GEOMETRY_HEADER to its path before including trgl_gl.h and this file is never seen.  It exists so that the
@@ -89,5 +89,43 @@ template <int R, int K, int C> inline mat<R, C> operator*(const mat<R, K>& a, co
         }
     return out;
 }
+// ---- what frustum culling needs (the reference's Plane and AABB, geometry.h:253-328, by their member names) ------------------
+// a plane n . p + d = 0; distance() is signed, positive on the side the normal points to
+struct Plane {
+    vec3 normal;
+    double d;
+    Plane() : normal(make_vec3(0.0, 0.0, 1.0)), d(0.0) {}
+    Plane(const vec3& n, const vec3& point) : normal(normalized(n)), d(0.0) { d = -dot(normal, point); }
+    double distance(const vec3& point) const { return dot(normal, point) + d; }
+};
+
+// an axis-aligned box by its two extreme corners
+struct AABB {
+    vec3 min, max;
+    AABB() {}
+    AABB(const vec3& lo, const vec3& hi) : min(lo), max(hi) {}
+    vec3 getCenter() const { return (min + max) * 0.5; }
+    vec3 getSize() const { return max - min; }
+    vec3 getHalfSize() const { return getSize() * 0.5; }
+    bool intersects(const AABB& o) const {
+        for (int a = 0; a < 3; ++a) if (!(min[a] <= o.max[a] && max[a] >= o.min[a])) return false;
+        return true;
+    }
+    // the box around the eight corners after m, each divided by its w (no guard against w = 0, as the reference has none); bounds
+    // start at +-1e9 and a corner replaces one only when strictly beyond it, so NaN corners are ignored
+    AABB transform(const mat<4, 4>& m) const {
+        vec3 lo = make_vec3(1e9, 1e9, 1e9), hi = make_vec3(-1e9, -1e9, -1e9);
+        for (int i = 0; i < 8; ++i) {        // x changes fastest, then y, then z
+            const vec4 t = m * make_vec4((i & 1) ? max[0] : min[0], (i & 2) ? max[1] : min[1], (i & 4) ? max[2] : min[2], 1.0);
+            const vec3 p = t.xyz() / t[3];
+            for (int a = 0; a < 3; ++a) {
+                if (p[a] < lo[a]) lo[a] = p[a];
+                if (hi[a] < p[a]) hi[a] = p[a];
+            }
+        }
+        return AABB(lo, hi);
+    }
+};
+
 static_assert(sizeof(vec<4>) == 4 * sizeof(double) && sizeof(vec<3>) == 3 * sizeof(double) && sizeof(vec<2>) == 2 * sizeof(double),
               "vec<N> must be N packed doubles");

@@ -4,6 +4,7 @@
 //   globals  ModelView / Perspective / Viewport / zbuffer        (our_gl.h:17-20)
 //   lookat, init_perspective, init_viewport, init_zbuffer        (our_gl.h:25-31)
 //   struct IShader, typedef Triangle, rasterize(), print_render_stats()  (our_gl.h:36-61)
+//   struct Frustum with createFromMatrix / intersects                    (our_gl.h:68-86), over the Plane / AABB of the geometry header in use
 // What changes for a caller, and why:
 //   * rasterize() is DEFERRED: it snapshots the clip coordinates, the shader's varyings and the uniforms that can
 //     change between calls (the global ModelView is read inside fragment(), main.cpp:116) and batches them; the GPU
@@ -23,6 +24,8 @@
 //   * a vertex() the device does not implement is a user vertex shader: source registered with gl_register_vertex_shader() and named
 //     by UserShader::vertex_kind (trgl_shader_desc::vertex_kind); gl_draw_model() / gl_draw_indexed() then run it in place of the
 //     built-in vertex stage, for a shader of any kind with as many varyings.
+//   * gl_zbuffer_snapshot(slot) / gl_zbuffer_restore(slot) do what `saved = zbuffer;` / `zbuffer = saved;` (main.cpp:700,730) do without
+//     the depths crossing PCIe twice; gl_mesh_bounds(model) is Model::computeAABB (model.cpp:15-40) for a model of the caller's own.
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -444,6 +447,60 @@ inline bool gl_postprocess(TGAImage& framebuffer, TGAImage* zbuffer_image, TGAIm
         return img->buffer();
     };
     return TRGL_SHIM_OK(trgl_postprocess(s.ctx, nullptr, prep(zbuffer_image), prep(ao_map), prep(final_result))) && ok;
+}
+
+// ---- our_gl.h:68-86 ------------------------------------------------------------------------------
+// The reference's Frustum (our_gl.cpp:212-280) over trgl_frustum_from_matrix / trgl_frustum_intersects, so that the shim, the C ABI
+// and Python cull alike.  Plane and AABB come from the geometry header in use (the reference's own, or trgl_geometry.h).
+struct Frustum {
+    Plane planes[6];            // left, right, bottom, top, near, far
+    enum PlaneIndex { LEFT = 0, RIGHT = 1, BOTTOM = 2, TOP = 3, NEAR = 4, FAR = 5 };
+    static Frustum createFromMatrix(const mat<4, 4>& matrix) {
+        double m[16], p[24];
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m[4 * r + c] = matrix[r][c];
+        trgl_frustum_from_matrix(m, p);
+        Frustum f;
+        for (int i = 0; i < 6; ++i) { for (int a = 0; a < 3; ++a) f.planes[i].normal[a] = p[4 * i + a]; f.planes[i].d = p[4 * i + 3]; }
+        return f;
+    }
+    bool intersects(const AABB& aabb) const {
+        double p[24], lo[3], hi[3];
+        for (int i = 0; i < 6; ++i) { for (int a = 0; a < 3; ++a) p[4 * i + a] = planes[i].normal[a]; p[4 * i + 3] = planes[i].d; }
+        for (int a = 0; a < 3; ++a) { lo[a] = aabb.min[a]; hi[a] = aabb.max[a]; }
+        return trgl_frustum_intersects(p, lo, hi) == 1;
+    }
+};
+
+// Model::computeAABB (model.cpp:15-40) for a model that keeps `vertices` as records of packed doubles starting with the position
+// (model.h:14-20,114): what the reference leaves in Model::localAABB.  Host memory, no GPU (trgl_mesh_bounds).
+template <class ModelT> inline AABB gl_mesh_bounds(const ModelT& model) {
+    using V = typename std::decay<decltype(model.vertices[0])>::type;
+    static_assert(sizeof(V) % sizeof(double) == 0 && sizeof(V) >= 3 * sizeof(double), "vertex records must be packed doubles starting with the position");
+    double lo[3], hi[3];
+    trgl_mesh_bounds(nullptr, reinterpret_cast<const double*>(model.vertices.data()), int(sizeof(V) / sizeof(double)), model.vertices.size(),
+                     TRGL_MEM_HOST, lo, hi);
+    AABB b;
+    for (int a = 0; a < 3; ++a) { b.min[a] = lo[a]; b.max[a] = hi[a]; }
+    return b;
+}
+
+// `std::vector<double> zbuffer_before_eyes = zbuffer;` (main.cpp:700) and `zbuffer = zbuffer_before_eyes;` (main.cpp:730) with the
+// depths staying in HBM: slot 0..TRGL_MAX_Z_SNAPSHOTS-1 names the copy.  Triangles batched so far are drawn first, as the proxy's
+// accessors do; depths the host wrote through the proxy are uploaded before a snapshot; after a restore the host copy is stale.
+inline bool gl_zbuffer_snapshot(TGAImage& framebuffer, int slot = 0) {
+    using namespace trgl_shim;
+    if (!bind(framebuffer)) return false;                       // (uploads a host copy still marked dirty)
+    const bool ok = submit_batch();
+    return TRGL_SHIM_OK(trgl_zbuffer_snapshot(state().ctx, slot)) && ok;
+}
+inline bool gl_zbuffer_restore(TGAImage& framebuffer, int slot = 0) {
+    using namespace trgl_shim;
+    State& s = state();
+    if (!bind(framebuffer)) return false;
+    const bool ok = submit_batch();                             // the batched triangles see the depths as they are now
+    if (!TRGL_SHIM_OK(trgl_zbuffer_restore(s.ctx, slot))) return false;
+    s.zbuffer_stale_on_host = true; s.zbuffer_dirty_on_host = false;
+    return ok;
 }
 
 inline void print_render_stats() {                                                // our_gl.cpp:204-210
