@@ -406,6 +406,40 @@ int trgl_postprocess(trgl_ctx* ctx, const trgl_ssao_params* params, uint8_t* zbu
 int trgl_mesh_bounds(trgl_ctx* ctx, const double* vertices, int vertex_stride, uint64_t n_vertices,
                      int mem_kind, double out_min[3], double out_max[3]);
 
+/* Smooth normals and tangent frames of an indexed mesh in host memory or in HBM, in place.  A record is the reference's Vertex
+ * (model.h:14-20): position +0, normal +3, texcoord +6, tangent +8, bitangent +11 doubles; indices are n_faces x 3 uint32.
+ *
+ * trgl_mesh_normals replaces: Model::generateNormalsIfNeeded (model.cpp:269-316), literally; vertex_stride >= 6.  Nothing is written
+ * unless some vertex has norm(normal) < 0.001 (:270-278; a NaN length does not count).  Otherwise every normal starts at +0.0 (:283-285);
+ * for each face in index order cross(v1 - v0, v2 - v0) is added to the normal of each of its three corners' vertices (:288-305; a face
+ * that names one vertex twice adds twice); a sum with norm > 0.001 is divided by that norm, every other vertex - in no face, a sum that
+ * cancels, a NaN sum - gets (0, 0, 1) (:308-315).  norm is sqrt of the dot product summed from 0 in component order (geometry.h:123-133).
+ *
+ * trgl_mesh_tangents replaces: Model::computeTangentsIfNeeded (model.cpp:318-388), literally; vertex_stride >= 14.  The need test runs
+ * on norm(tangent) (:319-327); tangents and bitangents are zeroed (:332-335); per face r = dUV1.x * dUV2.y - dUV2.x * dUV1.y, a face
+ * with fabs(r) < 1e-8 contributes nothing (a NaN r is not skipped), else (dPos1 * dUV2.y - dPos2 * dUV1.y) * (1.0 / r) is added to the
+ * tangents of its three corners (:338-368).  Per vertex, where norm(tangent) > 0.001 && norm(normal) > 0.001: n = normalized(normal),
+ * t = normalized(tangent), tangent = normalized(t - n * dot(n, t)), bitangent = cross(normal, tangent) with the stored normal, not n
+ * (:372-382; normalized returns a zero vector unchanged, geometry.h:136-140, which happens when t is parallel to n); any other vertex
+ * gets (1, 0, 0) and (0, 1, 0) (:384-385).
+ *
+ * Both: fields the reference function does not write keep their bits; no fused multiply-add; *generated (may be NULL) receives 1 if the
+ * arrays were rewritten and 0 if they were left alone.  n_vertices == 0 succeeds and does nothing.  TRGL_E_INVALID: 3 * n_faces does not
+ * fit in 32 bits, a null array (vertices with n_vertices > 0, indices with n_faces > 0), too small a stride, a bad mem_kind, a host index
+ * >= n_vertices (nothing is written then).  Device indices are the caller's responsibility, as for trgl_draw_indexed.
+ * TRGL_MEM_HOST: plain C++, ctx may be NULL, no GPU is touched.
+ * TRGL_MEM_DEVICE: queued on the context's stream in order with everything else - a trgl_draw_indexed issued earlier has queued its
+ * vertex stage already and sees the old normals, one issued later sees the new ones; nothing is flushed.  Alignment and stream rules are
+ * those of trgl_draw_indexed (vertices 8 bytes, indices 4, nothing wider assumed).  The sum at a vertex is the reference's chain of fp64
+ * additions: the corners are grouped by vertex with a stable integer sort and one thread adds a vertex's face vectors in face order from
+ * +0.0, so the result does not depend on how the GPU schedules it (no floating-point atomics).  Whether work is needed is decided on the
+ * device; with generated == NULL the call does not wait, with a pointer it waits for those 4 bytes (one stream sync, as trgl_mesh_bounds
+ * waits for its 48).  Scratch memory (under 100 bytes per face) belongs to the context, grows on demand and is freed by trgl_destroy. */
+int trgl_mesh_normals(trgl_ctx* ctx, double* vertices, int vertex_stride, uint64_t n_vertices,
+                      const uint32_t* indices, uint64_t n_faces, int mem_kind, int* generated);
+int trgl_mesh_tangents(trgl_ctx* ctx, double* vertices, int vertex_stride, uint64_t n_vertices,
+                       const uint32_t* indices, uint64_t n_faces, int mem_kind, int* generated);
+
 /* Replaces: AABB::transform (geometry.h:297-327), the body of Model::getWorldAABB: the eight corners (x fastest, then y, then z) times
  * the row-major m, each divided by its w WITHOUT a guard (w = 0 gives inf / NaN exactly as the reference), folded with std::min /
  * std::max from 1e9 / -1e9.  Needs no GPU and no context. */

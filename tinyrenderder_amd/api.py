@@ -40,6 +40,7 @@ SYMBOLS = [
     "trgl_vertex_shader_compile", "trgl_register_vertex_shader", "trgl_draw_indexed_vs", "trgl_vertex_stage",
     "trgl_mesh_bounds", "trgl_aabb_transform", "trgl_frustum_from_matrix", "trgl_frustum_intersects",
     "trgl_zbuffer_snapshot", "trgl_zbuffer_restore", "trgl_zbuffer_snapshot_free",
+    "trgl_mesh_normals", "trgl_mesh_tangents",
 ]
 
 
@@ -180,6 +181,8 @@ def load_library(path: str = None):
     L.trgl_vertex_stage.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64,
                                     C.c_void_p, C.c_void_p, C.c_int]
     L.trgl_mesh_bounds.argtypes = [vp, C.c_void_p, C.c_int, C.c_uint64, C.c_int, dp, dp]
+    for name in ("trgl_mesh_normals", "trgl_mesh_tangents"):
+        getattr(L, name).argtypes = [vp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_int)]
     L.trgl_aabb_transform.argtypes = [dp, dp, dp, dp, dp]
     L.trgl_frustum_from_matrix.argtypes = [dp, dp]
     L.trgl_frustum_intersects.argtypes = [dp, dp, dp]
@@ -297,6 +300,37 @@ def mesh_bounds(vertices):
     """trgl_mesh_bounds for a host array without a context: Model::computeAABB (model.cpp:15-40) of vertices [n, stride >= 3] with the
     position at +0; returns (min[3], max[3]) with the reference's 1 % margin.  Needs no GPU."""
     return _mesh_bounds(load_library(), None, vertices, False)
+
+
+def _mesh_attr(L, handle, name, ptrs, vertices, indices, device, wait):
+    if len(vertices.shape) != 2 or len(indices.shape) != 2 or indices.shape[1] != 3:
+        raise ValueError(f"{name}: vertices must be [n, stride] and indices [n_faces, 3]")
+    nv, stride = vertices.shape
+    generated = C.c_int(0)
+    rc = getattr(L, "trgl_" + name)(handle, ptrs[0], int(stride), int(nv), ptrs[1], int(indices.shape[0]), MEM_DEVICE if device else MEM_HOST,
+                                    C.byref(generated) if wait else None)
+    if rc != 0:
+        raise TrglError(f"trgl_{name} failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return bool(generated.value) if wait else None
+
+
+def _host_mesh(vertices, indices):
+    """A private, writable, contiguous copy of the vertices, and the indices as [n_faces, 3] uint32."""
+    return np.array(vertices, np.float64, order="C"), np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+
+
+def mesh_normals(vertices, indices):
+    """trgl_mesh_normals for host arrays without a context: Model::generateNormalsIfNeeded (model.cpp:269-316) on a copy of vertices
+    [n, stride >= 6] (normal at +3) with indices [n_faces, 3]; returns (vertices, generated).  Needs no GPU."""
+    v, i = _host_mesh(vertices, indices)
+    return v, _mesh_attr(load_library(), None, "mesh_normals", (v.ctypes.data, i.ctypes.data), v, i, False, True)
+
+
+def mesh_tangents(vertices, indices):
+    """trgl_mesh_tangents likewise: Model::computeTangentsIfNeeded (model.cpp:318-388) on a copy of vertices [n, stride >= 14]
+    (texcoord +6, tangent +8, bitangent +11); returns (vertices, generated).  Needs no GPU."""
+    v, i = _host_mesh(vertices, indices)
+    return v, _mesh_attr(load_library(), None, "mesh_tangents", (v.ctypes.data, i.ctypes.data), v, i, False, True)
 
 
 def aabb_transform(bmin, bmax, m):
@@ -552,6 +586,24 @@ class Context:
         """trgl_mesh_bounds: Model::computeAABB (model.cpp:15-40) of vertices [n, stride >= 3]; returns (min[3], max[3]).  device=True:
         a device tensor, reduced on the context's stream in order with the draws (nothing is flushed); the call waits for the result."""
         return _mesh_bounds(self.L, self.h, vertices, device)
+
+    def _mesh_attr(self, name, vertices, indices, device, wait):
+        if not device:
+            vertices, indices = _host_mesh(vertices, indices)
+        vertices, indices, _, ptrs = self._mesh_ptrs(vertices, indices, None, device)
+        if device and not wait:
+            self._keep.append((vertices, indices))
+        return vertices, _mesh_attr(self.L, self.h, name, ptrs, vertices, indices, device, wait or not device)
+
+    def mesh_normals(self, vertices, indices, device=False, wait=True):
+        """trgl_mesh_normals: Model::generateNormalsIfNeeded (model.cpp:269-316); returns (vertices, generated).  Host arrays: computed
+        on a copy.  device=True: device tensors [n, stride >= 6] f64 and [n_faces, 3] u32, rewritten in place on the context's stream in
+        order with the draws (nothing is flushed); wait=False queues without waiting and returns generated = None."""
+        return self._mesh_attr("mesh_normals", vertices, indices, device, wait)
+
+    def mesh_tangents(self, vertices, indices, device=False, wait=True):
+        """trgl_mesh_tangents: Model::computeTangentsIfNeeded (model.cpp:318-388) likewise, vertices [n, stride >= 14]."""
+        return self._mesh_attr("mesh_tangents", vertices, indices, device, wait)
 
     def zbuffer_snapshot(self, slot=0):
         """trgl_zbuffer_snapshot: main.cpp:700 as one device-to-device copy (flushes what is queued, does not wait)."""

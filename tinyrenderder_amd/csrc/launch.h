@@ -68,6 +68,13 @@ struct BoundsPartial { double v[6]; unsigned long long i[6]; };      // running 
 constexpr uint32_t MESH_BOUNDS_MAX_BLOCKS = 1024;
 void launch_mesh_bounds(hipStream_t s, const double* vertices, int stride, uint64_t n, BoundsPartial* scratch);
 
+// Model::generateNormalsIfNeeded (model.cpp:269-316) or, with `tangents`, Model::computeTangentsIfNeeded (model.cpp:318-388) over an
+// indexed mesh in device memory, in place (kernels_mesh.hip).  scratch: at least mesh_attr_scratch_bytes() bytes, 256-byte aligned;
+// *flag then points at the word in it that holds 1 once the arrays were rewritten and 0 when they were left alone.  nverts > 0.
+hipError_t mesh_attr_scratch_bytes(uint64_t nverts, uint32_t nfaces, size_t* bytes);
+hipError_t launch_mesh_attr(hipStream_t s, bool tangents, double* vertices, int stride, uint64_t nverts, const uint32_t* indices, uint32_t nfaces,
+                            void* scratch, size_t scratch_bytes, const uint32_t** flag);
+
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,
                               unsigned long long* mismatches);

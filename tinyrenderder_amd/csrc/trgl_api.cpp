@@ -94,6 +94,7 @@ struct trgl_ctx {
     hipEvent_t ev_pairs = nullptr;      // recorded behind the copy of the flush's pair count into pinned memory
     DevBuf<uint32_t> idbuf;             // visibility buffer of PHONG / EYE flushes, [H][W]
     DevBuf<BoundsPartial> bounds_scratch;   // trgl_mesh_bounds: the result + the per-block partials, allocated by the first call
+    DevBuf<uint8_t> mesh_scratch;       // trgl_mesh_normals / trgl_mesh_tangents: flag, face vectors, sorted corners, the sort's own space; grows on demand
     DevBuf<double> zsnap[TRGL_MAX_Z_SNAPSHOTS];   // trgl_zbuffer_snapshot: [H][W] depths per slot in use
     DevBuf<uint8_t> pp_out;             // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
@@ -938,6 +939,121 @@ int trgl_mesh_bounds(trgl_ctx* c, const double* vertices, int stride, uint64_t n
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int a = 0; a < 3; ++a) { out_min[a] = res[a]; out_max[a] = res[3 + a]; }
     return TRGL_OK;
+}
+
+// ---- Model::generateNormalsIfNeeded (model.cpp:269-316) and Model::computeTangentsIfNeeded (model.cpp:318-388) ----------------------
+// norm (geometry.h:130-133) of three consecutive doubles
+static inline double norm3_from_zero(const double* v) { return std::sqrt(dot3_from_zero(v, v[0], v[1], v[2])); }
+// normalized (geometry.h:136-140): a zero vector comes back unchanged
+static inline void normalize3(double* v) {
+    const double length = norm3_from_zero(v);
+    if (length == 0) return;
+    for (int a = 0; a < 3; ++a) v[a] = v[a] / length;
+}
+
+static void host_mesh_normals(double* vertices, uint64_t stride, uint64_t n, const uint32_t* indices, uint64_t nfaces) {
+    for (uint64_t i = 0; i < n; ++i) { double* nrm = vertices + i * stride + 3; nrm[0] = nrm[1] = nrm[2] = 0.0; }     // :283-285
+    for (uint64_t f = 0; f < nfaces; ++f) {                                                                          // :288-305
+        const double* v0 = vertices + indices[3 * f] * stride; const double* v1 = vertices + indices[3 * f + 1] * stride;
+        const double* v2 = vertices + indices[3 * f + 2] * stride;
+        double e1[3], e2[3];
+        for (int a = 0; a < 3; ++a) { e1[a] = v1[a] - v0[a]; e2[a] = v2[a] - v0[a]; }
+        const double fn[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+        for (int k = 0; k < 3; ++k) {
+            double* nrm = vertices + indices[3 * f + k] * stride + 3;
+            for (int a = 0; a < 3; ++a) nrm[a] = nrm[a] + fn[a];
+        }
+    }
+    for (uint64_t i = 0; i < n; ++i) {                                                                               // :308-315
+        double* nrm = vertices + i * stride + 3;
+        const double length = norm3_from_zero(nrm);
+        if (length > 0.001) { for (int a = 0; a < 3; ++a) nrm[a] = nrm[a] / length; }
+        else { nrm[0] = 0; nrm[1] = 0; nrm[2] = 1; }
+    }
+}
+
+static void host_mesh_tangents(double* vertices, uint64_t stride, uint64_t n, const uint32_t* indices, uint64_t nfaces) {
+    for (uint64_t i = 0; i < n; ++i) { double* t = vertices + i * stride + 8; for (int a = 0; a < 6; ++a) t[a] = 0.0; }   // :332-335
+    for (uint64_t f = 0; f < nfaces; ++f) {                                                                          // :338-368
+        const double* v0 = vertices + indices[3 * f] * stride; const double* v1 = vertices + indices[3 * f + 1] * stride;
+        const double* v2 = vertices + indices[3 * f + 2] * stride;
+        double dp1[3], dp2[3];
+        for (int a = 0; a < 3; ++a) { dp1[a] = v1[a] - v0[a]; dp2[a] = v2[a] - v0[a]; }
+        const double duv1x = v1[6] - v0[6], duv1y = v1[7] - v0[7], duv2x = v2[6] - v0[6], duv2y = v2[7] - v0[7];
+        const double r = duv1x * duv2y - duv2x * duv1y;                                                              // :353
+        if (std::fabs(r) < 1e-8) continue;
+        const double invr = 1.0 / r;
+        double tangent[3], bitangent[3];
+        for (int a = 0; a < 3; ++a) {
+            tangent[a] = (dp1[a] * duv2y - dp2[a] * duv1y) * invr;                                                   // :358
+            bitangent[a] = (dp2[a] * duv1x - dp1[a] * duv2x) * invr;                                                 // :359
+        }
+        for (int k = 0; k < 3; ++k) { double* t = vertices + indices[3 * f + k] * stride + 8; for (int a = 0; a < 3; ++a) t[a] = t[a] + tangent[a]; }
+        for (int k = 0; k < 3; ++k) { double* b = vertices + indices[3 * f + k] * stride + 11; for (int a = 0; a < 3; ++a) b[a] = b[a] + bitangent[a]; }
+    }
+    for (uint64_t i = 0; i < n; ++i) {                                                                               // :371-387
+        double* rec = vertices + i * stride;
+        double* t = rec + 8; double* b = rec + 11;
+        if (norm3_from_zero(t) > 0.001 && norm3_from_zero(rec + 3) > 0.001) {
+            double nn[3] = { rec[3], rec[4], rec[5] };
+            normalize3(nn);                                                                                          // :374
+            normalize3(t);                                                                                           // :375
+            const double d = dot3_from_zero(nn, t[0], t[1], t[2]);
+            for (int a = 0; a < 3; ++a) t[a] = t[a] - nn[a] * d;                                                     // :378
+            normalize3(t);
+            b[0] = rec[4] * t[2] - rec[5] * t[1]; b[1] = rec[5] * t[0] - rec[3] * t[2]; b[2] = rec[3] * t[1] - rec[4] * t[0];   // :381
+        } else {
+            t[0] = 1; t[1] = 0; t[2] = 0; b[0] = 0; b[1] = 1; b[2] = 0;                                              // :384-385
+        }
+    }
+}
+
+static int mesh_attr(trgl_ctx* c, bool tangents, double* vertices, int stride, uint64_t n, const uint32_t* indices, uint64_t nfaces,
+                     int mem_kind, int* generated) {
+    const char* who = tangents ? "trgl_mesh_tangents" : "trgl_mesh_normals";
+    auto bad = [&](const char* msg) { const std::string m = std::string(who) + ": " + msg; if (c) c->err = m; else g_create_error = m; return TRGL_E_INVALID; };
+    const int field = tangents ? 8 : 3, min_stride = tangents ? 14 : 6;
+    if (mem_kind != TRGL_MEM_HOST && mem_kind != TRGL_MEM_DEVICE) return bad("bad mem_kind");
+    if (stride < min_stride) return bad(tangents ? "vertex stride must be >= 14 doubles (pos3, normal3, uv2, tangent3, bitangent3)"
+                                                 : "vertex stride must be >= 6 doubles (pos3, normal3)");
+    if (nfaces > 0xffffffffull / 3) return bad("3 * n_faces must fit in 32 bits");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return bad("TRGL_MEM_DEVICE needs a context");
+    if (generated) *generated = 0;
+    if (n == 0) return TRGL_OK;
+    if (!vertices) return bad("vertices is null");
+    if (nfaces && !indices) return bad("indices is null");
+    if (mem_kind == TRGL_MEM_HOST) {
+        for (uint64_t k = 0; k < 3 * nfaces; ++k)
+            if (indices[k] >= n) return bad("index out of range");
+        bool need = false;                                                      // :270-276 / :319-325
+        for (uint64_t i = 0; i < n && !need; ++i) need = norm3_from_zero(vertices + i * (uint64_t)stride + field) < 0.001;
+        if (!need) return TRGL_OK;
+        if (tangents) host_mesh_tangents(vertices, (uint64_t)stride, n, indices, nfaces);
+        else host_mesh_normals(vertices, (uint64_t)stride, n, indices, nfaces);
+        if (generated) *generated = 1;
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    size_t bytes = 0;
+    HIPCHK(c, mesh_attr_scratch_bytes(n, (uint32_t)nfaces, &bytes));
+    if ((r = c->mesh_scratch.grow(c, bytes))) return r;
+    const uint32_t* flag = nullptr;
+    HIPCHK(c, launch_mesh_attr(c->stream, tangents, vertices, stride, n, indices, (uint32_t)nfaces, c->mesh_scratch.p, c->mesh_scratch.cap, &flag));
+    if (generated) {
+        uint32_t word = 0;
+        HIPCHK(c, hipMemcpyAsync(&word, flag, sizeof(word), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        *generated = word ? 1 : 0;
+    }
+    return TRGL_OK;
+}
+
+int trgl_mesh_normals(trgl_ctx* c, double* vertices, int stride, uint64_t n, const uint32_t* indices, uint64_t nfaces, int mem_kind, int* generated) {
+    return mesh_attr(c, false, vertices, stride, n, indices, nfaces, mem_kind, generated);
+}
+int trgl_mesh_tangents(trgl_ctx* c, double* vertices, int stride, uint64_t n, const uint32_t* indices, uint64_t nfaces, int mem_kind, int* generated) {
+    return mesh_attr(c, true, vertices, stride, n, indices, nfaces, mem_kind, generated);
 }
 
 int trgl_aabb_transform(const double bmin[3], const double bmax[3], const double m[16], double out_min[3], double out_max[3]) {

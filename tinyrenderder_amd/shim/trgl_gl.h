@@ -26,6 +26,7 @@
 //     built-in vertex stage, for a shader of any kind with as many varyings.
 //   * gl_zbuffer_snapshot(slot) / gl_zbuffer_restore(slot) do what `saved = zbuffer;` / `zbuffer = saved;` (main.cpp:700,730) do without
 //     the depths crossing PCIe twice; gl_mesh_bounds(model) is Model::computeAABB (model.cpp:15-40) for a model of the caller's own.
+//     gl_mesh_normals(model) / gl_mesh_tangents(model) are Model::generateNormalsIfNeeded / computeTangentsIfNeeded (model.cpp:269-388).
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -483,6 +484,25 @@ template <class ModelT> inline AABB gl_mesh_bounds(const ModelT& model) {
     for (int a = 0; a < 3; ++a) { b.min[a] = lo[a]; b.max[a] = hi[a]; }
     return b;
 }
+
+// Model::generateNormalsIfNeeded (model.cpp:269-316) and Model::computeTangentsIfNeeded (model.cpp:318-388) for such a model with
+// `indices` as packed 32-bit numbers (model.h:114-115), in place: what Model::load does behind the loader (model.cpp:59-62).  Host
+// memory, no GPU (trgl_mesh_normals / trgl_mesh_tangents).  Return whether the arrays were rewritten; false also when the call was
+// refused (an index past the last vertex), which gl_last_error() / gl_last_error_message() then tell, as for every C-ABI error.
+template <bool TANGENTS, class ModelT> inline bool gl_mesh_attr(ModelT& model) {
+    using V = typename std::decay<decltype(model.vertices[0])>::type;
+    static_assert(sizeof(V) % sizeof(double) == 0 && sizeof(V) >= (TANGENTS ? 14 : 6) * sizeof(double),
+                  "vertex records must be packed doubles: position, normal (and for tangents texcoord, tangent, bitangent)");
+    static_assert(sizeof(model.indices[0]) == sizeof(std::uint32_t), "indices must be 32-bit");
+    int generated = 0;
+    const int rc = (TANGENTS ? trgl_mesh_tangents : trgl_mesh_normals)(
+        nullptr, reinterpret_cast<double*>(model.vertices.data()), int(sizeof(V) / sizeof(double)), model.vertices.size(),
+        reinterpret_cast<const std::uint32_t*>(model.indices.data()), model.indices.size() / 3, TRGL_MEM_HOST, &generated);
+    if (rc != TRGL_OK) return trgl_shim::fail(TANGENTS ? "trgl_mesh_tangents" : "trgl_mesh_normals", rc, nullptr);   // (no context: the message is the creation error's)
+    return generated != 0;
+}
+template <class ModelT> inline bool gl_mesh_normals(ModelT& model) { return gl_mesh_attr<false>(model); }
+template <class ModelT> inline bool gl_mesh_tangents(ModelT& model) { return gl_mesh_attr<true>(model); }
 
 // `std::vector<double> zbuffer_before_eyes = zbuffer;` (main.cpp:700) and `zbuffer = zbuffer_before_eyes;` (main.cpp:730) with the
 // depths staying in HBM: slot 0..TRGL_MAX_Z_SNAPSHOTS-1 names the copy.  Triangles batched so far are drawn first, as the proxy's
