@@ -468,6 +468,50 @@ int trgl_zbuffer_snapshot(trgl_ctx* ctx, int slot);
 int trgl_zbuffer_restore(trgl_ctx* ctx, int slot);
 int trgl_zbuffer_snapshot_free(trgl_ctx* ctx, int slot);
 
+/* ---- image operations: Gaussian blur and nearest rescale, in host memory or in HBM ----------------------- */
+
+/* Images are TGAImage::buffer() (tgaimage.h:93): w * h * bpp bytes, index (x + y * w) * bpp, bpp in {1, 3, 4}; every channel is treated
+ * alike.  TRGL_MEM_HOST: plain C++, ctx may be NULL, no GPU is touched.  TRGL_MEM_DEVICE: needs a context; the work is queued on the
+ * context's stream in order with everything else, nothing is flushed and the call does not wait for it (the image must be complete on that
+ * stream, as for trgl_draw_indexed).  Device pointers need no alignment at all - a bpp = 3 image gives no better than 1 byte.  Scratch
+ * memory (the weights, the w * h * bpp image between the two passes) belongs to the context, grows on demand and is freed by
+ * trgl_destroy.  A blur whose radius differs from the previous one's uploads 2 * radius + 1 weights through pinned memory of the
+ * context first, and waits until the previous such upload - not the blur behind it - has left that memory. */
+#define TRGL_MAX_BLUR_RADIUS 46340   /* above it i * i overflows the reference's int (tgaimage.cpp:280) */
+
+/* Replaces: the weight vector of TGAImage::gaussian_blur (tgaimage.cpp:275-284), all in float: sigma = radius / 2.0f,
+ * v[i] = std::exp(-(i * i) / (2 * sigma * sigma)) for i = -radius..radius with the int -(i * i) converted to float, summed in index order
+ * from 0, each then divided by the sum.  Computed on the host with std::exp(float) exactly as the reference does; the device paths use
+ * these very numbers.  weights receives 2 * radius + 1 floats.  Needs no GPU and no context.
+ * TRGL_E_INVALID: radius <= 0 or a null pointer; TRGL_E_UNSUPPORTED: radius > TRGL_MAX_BLUR_RADIUS. */
+int trgl_gaussian_kernel(int radius, float* weights);
+
+/* Replaces: TGAImage::gaussian_blur(radius) (tgaimage.cpp:271-324), in place, byte for byte.
+ * Horizontal pass (:290-304): per pixel and channel a float sum that starts at 0.0f; for k = -radius..radius IN THAT ORDER
+ * sum += byte(clamp(x + k, 0, w - 1), y) * weight[k] - uint8 -> int -> float, one rounded multiply, one rounded add, never fused - and the
+ * stored byte is (uint8_t)sum, a truncation.  Vertical pass (:309-323): the same over the horizontal pass's BYTES, clamping y + k.
+ * radius <= 0 or w * h == 0: TRGL_OK and nothing is read or written (:272; checked after mem_kind, bpp and the sign of w and h).
+ * TRGL_E_INVALID: bpp not in {1, 3, 4}, w or h < 0, a null pointer with a non-empty image, a bad mem_kind, TRGL_MEM_DEVICE without a context.
+ * TRGL_E_UNSUPPORTED: radius > TRGL_MAX_BLUR_RADIUS, or w * h * bpp > INT_MAX (the reference's int byte index overflows).
+ * On the device both passes stage their tile and a clamped halo in LDS up to radius 32 and read clamped addresses from global memory
+ * above it; one thread owns an output byte and adds its taps in the order above either way, so the bytes do not depend on the path. */
+int trgl_image_blur(trgl_ctx* ctx, uint8_t* pixels, int w, int h, int bpp, int radius, int mem_kind);
+
+/* Replaces: TGAImage::scale(w2, h2) (tgaimage.cpp:246-267) from `src` (w x h) into `dst` (w2 x h2), which must not overlap:
+ * dst(x, y) = src(x * w / w2, y * h / h2) in int arithmetic (:253-254), bpp bytes copied per pixel.
+ * TRGL_E_INVALID where the reference returns false - w2 <= 0, h2 <= 0 or an empty source (w <= 0 or h <= 0) (:247) - and for bpp not
+ * in {1, 3, 4}, a null pointer, overlapping images, a bad mem_kind, TRGL_MEM_DEVICE without a context.
+ * TRGL_E_UNSUPPORTED: (w2 - 1) * w, (h2 - 1) * h, w2 * h2 * bpp or w * h * bpp > INT_MAX (the reference's int arithmetic overflows). */
+int trgl_image_scale(trgl_ctx* ctx, const uint8_t* src, int w, int h, int bpp,
+                     uint8_t* dst, int w2, int h2, int mem_kind);
+
+/* Replaces: framebuffer.gaussian_blur(radius) (tgaimage.cpp:271-324) on the frame where it lives: completes a begun flush, flushes
+ * what is queued (a pending trgl_clear included), then blurs the resident framebuffer in place on the context's stream and does not
+ * wait; trgl_read_framebuffer hands back the blurred pixels.  The z-buffer and the counters stay untouched.  radius <= 0: TRGL_OK, nothing
+ * is queued.  TRGL_E_STATE on a context with a strip or interleaved bands set (trgl_set_strip / trgl_set_interleave): the vertical pass
+ * would read rows that another rank owns - gather the frame and blur it on one context.  TRGL_E_UNSUPPORTED as for trgl_image_blur. */
+int trgl_framebuffer_blur(trgl_ctx* ctx, int radius);
+
 /* ---- TGA writer and reader (host only) ------------------------------------- */
 
 /* Replaces: TGAImage::write_tga_file(name, vflip, rle) (tgaimage.cpp:161-242): produces exactly the bytes the

@@ -24,6 +24,7 @@ PHASE_SETUP, PHASE_BIN, PHASE_RASTER, PHASE_TOTAL, PHASE_RASTER_KERNEL = 0, 1, 2
 NUM_PHASES = 5        # TRGL_NUM_PHASES
 MAX_TEXTURES = 16
 MAX_Z_SNAPSHOTS = 4           # TRGL_MAX_Z_SNAPSHOTS
+MAX_BLUR_RADIUS = 46340       # TRGL_MAX_BLUR_RADIUS
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
 
 # every symbol include/trgl.h declares (tests check the library exports all of them)
@@ -41,6 +42,7 @@ SYMBOLS = [
     "trgl_mesh_bounds", "trgl_aabb_transform", "trgl_frustum_from_matrix", "trgl_frustum_intersects",
     "trgl_zbuffer_snapshot", "trgl_zbuffer_restore", "trgl_zbuffer_snapshot_free",
     "trgl_mesh_normals", "trgl_mesh_tangents",
+    "trgl_gaussian_kernel", "trgl_image_blur", "trgl_image_scale", "trgl_framebuffer_blur",
 ]
 
 
@@ -188,6 +190,10 @@ def load_library(path: str = None):
     L.trgl_frustum_intersects.argtypes = [dp, dp, dp]
     for name in ("trgl_zbuffer_snapshot", "trgl_zbuffer_restore", "trgl_zbuffer_snapshot_free"):
         getattr(L, name).argtypes = [vp, C.c_int]
+    L.trgl_gaussian_kernel.argtypes = [C.c_int, C.c_void_p]
+    L.trgl_image_blur.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.trgl_image_scale.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.trgl_framebuffer_blur.argtypes = [vp, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -331,6 +337,63 @@ def mesh_tangents(vertices, indices):
     (texcoord +6, tangent +8, bitangent +11); returns (vertices, generated).  Needs no GPU."""
     v, i = _host_mesh(vertices, indices)
     return v, _mesh_attr(load_library(), None, "mesh_tangents", (v.ctypes.data, i.ctypes.data), v, i, False, True)
+
+
+def gaussian_kernel(radius: int) -> np.ndarray:
+    """trgl_gaussian_kernel: the 2 * radius + 1 float32 weights of TGAImage::gaussian_blur (tgaimage.cpp:275-284), computed on the host as
+    the reference computes them.  Needs no GPU."""
+    L = load_library()
+    out = np.empty(2 * max(int(radius), 0) + 1, np.float32)
+    rc = L.trgl_gaussian_kernel(int(radius), out.ctypes.data)
+    if rc != 0:
+        raise TrglError(f"trgl_gaussian_kernel failed ({rc}): {L.trgl_last_error(None).decode()}")
+    return out
+
+
+def _image_dims(img, what):
+    if len(img.shape) != 3 or img.shape[2] not in (1, 3, 4):
+        raise ValueError(f"{what}: the image must be [h, w, bpp] with bpp in (1, 3, 4)")
+    return int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
+
+
+def _image_blur(L, handle, ptr, img, radius, device):
+    h, w, bpp = _image_dims(img, "image_blur")
+    rc = L.trgl_image_blur(handle, ptr, w, h, bpp, int(radius), MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_image_blur failed ({rc}): {L.trgl_last_error(handle).decode()}")
+
+
+def _image_scale(L, handle, sptr, img, dptr, w2, h2, device):
+    h, w, bpp = _image_dims(img, "image_scale")
+    rc = L.trgl_image_scale(handle, sptr, w, h, bpp, dptr, int(w2), int(h2), MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_image_scale failed ({rc}): {L.trgl_last_error(handle).decode()}")
+
+
+def _device_image(img, what):
+    """The address of a device image: a contiguous uint8 CUDA tensor (its shape says w, h and bpp, so a bare pointer will not do)."""
+    if not hasattr(img, "data_ptr"):
+        raise TypeError(f"device=True: {what} must be a device tensor, not {type(img).__name__}")
+    if str(img.dtype) != "torch.uint8" or not img.is_contiguous():
+        raise ValueError(f"device=True: {what} must be a contiguous uint8 tensor")
+    return _device_ptr(img, what)
+
+
+def image_blur(img, radius: int) -> np.ndarray:
+    """trgl_image_blur for a host array without a context: TGAImage::gaussian_blur (tgaimage.cpp:271-324) on a copy of img [h, w, bpp] uint8;
+    returns the copy.  radius <= 0 returns it unchanged, as the reference does.  Needs no GPU."""
+    out = np.array(img, np.uint8, order="C")
+    _image_blur(load_library(), None, out.ctypes.data, out, radius, False)
+    return out
+
+
+def image_scale(img, w2: int, h2: int) -> np.ndarray:
+    """trgl_image_scale for a host array without a context: TGAImage::scale (tgaimage.cpp:246-267) of img [h, w, bpp] uint8 into a new
+    [h2, w2, bpp] array.  Raises where the reference returns false (a size <= 0, an empty image).  Needs no GPU."""
+    src = np.ascontiguousarray(img, np.uint8)
+    out = np.empty((max(int(h2), 0), max(int(w2), 0), src.shape[2] if len(src.shape) == 3 else 0), np.uint8)
+    _image_scale(load_library(), None, src.ctypes.data, src, out.ctypes.data, w2, h2, False)
+    return out
 
 
 def aabb_transform(bmin, bmax, m):
@@ -604,6 +667,46 @@ class Context:
     def mesh_tangents(self, vertices, indices, device=False, wait=True):
         """trgl_mesh_tangents: Model::computeTangentsIfNeeded (model.cpp:318-388) likewise, vertices [n, stride >= 14]."""
         return self._mesh_attr("mesh_tangents", vertices, indices, device, wait)
+
+    def image_blur(self, img, radius, device=False):
+        """trgl_image_blur: TGAImage::gaussian_blur (tgaimage.cpp:271-324); returns the blurred image.  Host array: computed on a copy, no
+        GPU work.  device=True: a contiguous uint8 device tensor [h, w, bpp], blurred in place on the context's stream in order with
+        everything else (nothing is flushed, the call does not wait); the tensor is kept alive until the next sync."""
+        if not device:
+            out = np.array(img, np.uint8, order="C")
+            _image_blur(self.L, self.h, out.ctypes.data, out, radius, False)
+            return out
+        ptr = _device_image(img, "img")
+        self._keep.append((img,))
+        _image_blur(self.L, self.h, ptr, img, radius, True)
+        return img
+
+    def image_scale(self, img, w2, h2, device=False, out=None):
+        """trgl_image_scale: TGAImage::scale (tgaimage.cpp:246-267) of img [h, w, bpp] into [h2, w2, bpp]; returns the result.  device=True:
+        contiguous uint8 device tensors, gathered on the context's stream (nothing is flushed, the call does not wait); `out` (must not
+        overlap img) is allocated with torch when not given.  Raises where the reference returns false."""
+        if not device:
+            src = np.ascontiguousarray(img, np.uint8)
+            if out is None:
+                out = np.empty((max(int(h2), 0), max(int(w2), 0), src.shape[2] if len(src.shape) == 3 else 0), np.uint8)
+            if out.dtype != np.uint8 or not out.flags.c_contiguous or out.shape != (int(h2), int(w2), src.shape[2]):
+                raise ValueError("image_scale: out must be a contiguous uint8 array [h2, w2, bpp]")
+            _image_scale(self.L, self.h, src.ctypes.data, src, out.ctypes.data, w2, h2, False)
+            return out
+        sptr = _device_image(img, "img")
+        if out is None:
+            import torch
+            out = torch.empty((max(int(h2), 0), max(int(w2), 0), int(img.shape[2])), dtype=torch.uint8, device=img.device)
+        elif tuple(out.shape) != (int(h2), int(w2), int(img.shape[2])):
+            raise ValueError("image_scale: out must be [h2, w2, bpp]")
+        self._keep.append((img, out))
+        _image_scale(self.L, self.h, sptr, img, _device_image(out, "out"), w2, h2, True)
+        return out
+
+    def framebuffer_blur(self, radius):
+        """trgl_framebuffer_blur: framebuffer.gaussian_blur(radius) on the resident frame (flushes what is queued, does not wait); the
+        z-buffer and the stats stay as they are.  Not on a strip / band context."""
+        self._chk(self.L.trgl_framebuffer_blur(self.h, int(radius)))
 
     def zbuffer_snapshot(self, slot=0):
         """trgl_zbuffer_snapshot: main.cpp:700 as one device-to-device copy (flushes what is queued, does not wait)."""

@@ -75,6 +75,20 @@ hipError_t mesh_attr_scratch_bytes(uint64_t nverts, uint32_t nfaces, size_t* byt
 hipError_t launch_mesh_attr(hipStream_t s, bool tangents, double* vertices, int stride, uint64_t nverts, const uint32_t* indices, uint32_t nfaces,
                             void* scratch, size_t scratch_bytes, const uint32_t** flag);
 
+// TGAImage::gaussian_blur (tgaimage.cpp:271-324) on w * h * bpp bytes in device memory, in place (kernels_image.hip): the horizontal pass
+// into `tmp` (as many bytes, not overlapping), the vertical pass back.  weights: the 2 * radius + 1 floats of trgl_gaussian_kernel in
+// device memory.  Pointers need no alignment.  radius >= 1, w * h * bpp in 1..INT_MAX, bpp in {1, 3, 4}.
+// Up to BLUR_LDS_RADIUS both passes work from LDS tiles with a clamped halo; above it the halo would outgrow the tile and each thread
+// reads its clamped taps from global memory.  Both paths add the same products in the same order: the bytes do not depend on the path.
+constexpr int BLUR_LDS_RADIUS = 32;                          // the switch radius
+constexpr int BLUR_H_BYTES = 256, BLUR_H_ROWS = 4;           // horizontal tile: bytes of a row (one per thread) x rows
+constexpr int BLUR_V_BYTES = 64, BLUR_V_ROWS = 64;           // vertical tile: bytes of a row (one per lane) x rows
+void launch_image_blur(hipStream_t s, uint8_t* pixels, int w, int h, int bpp, int radius, const float* weights, uint8_t* tmp);
+// TGAImage::scale (tgaimage.cpp:246-267): dst(x, y) = src(x * w / w2, y * h / h2), bpp bytes each; src and dst do not overlap.
+// (w2 - 1) * w, (h2 - 1) * h and both byte counts fit an int.
+constexpr int SCALE_BYTES = 256, SCALE_ROWS = 8;             // tile: bytes of an output row (one per thread) x output rows
+void launch_image_scale(hipStream_t s, const uint8_t* src, int w, int h, int bpp, uint8_t* dst, int w2, int h2);
+
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,
                               unsigned long long* mismatches);

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -96,6 +97,10 @@ struct trgl_ctx {
     DevBuf<BoundsPartial> bounds_scratch;   // trgl_mesh_bounds: the result + the per-block partials, allocated by the first call
     DevBuf<uint8_t> mesh_scratch;       // trgl_mesh_normals / trgl_mesh_tangents: flag, face vectors, sorted corners, the sort's own space; grows on demand
     DevBuf<double> zsnap[TRGL_MAX_Z_SNAPSHOTS];   // trgl_zbuffer_snapshot: [H][W] depths per slot in use
+    // trgl_image_blur / trgl_framebuffer_blur: the weights of blur_radius (0: none) and the image between the two passes; grow on demand.
+    // The weights travel through blur_w_pinned; ev_blur_w is recorded behind that copy, so that the next upload knows when it may rewrite it
+    DevBuf<float> blur_weights; DevBuf<uint8_t> blur_tmp; int blur_radius = 0;
+    float* blur_w_pinned = nullptr; size_t blur_w_pinned_cap = 0; hipEvent_t ev_blur_w = nullptr;
     DevBuf<uint8_t> pp_out;             // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
     DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
@@ -234,6 +239,8 @@ int trgl_destroy(trgl_ctx* c) {
     if (c->stats_pinned) (void)hipHostFree(c->stats_pinned);
     for (int i = 0; i < 6; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_pairs) (void)hipEventDestroy(c->ev_pairs);
+    if (c->ev_blur_w) (void)hipEventDestroy(c->ev_blur_w);
+    if (c->blur_w_pinned) (void)hipHostFree(c->blur_w_pinned);
     for (auto& u : c->user) (void)hipModuleUnload(u.mod);
     for (auto& v : c->vertex) (void)hipModuleUnload(v.mod);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1134,6 +1141,97 @@ int trgl_zbuffer_snapshot_free(trgl_ctx* c, int slot) {
     int r = zsnap_slot(c, slot, "trgl_zbuffer_snapshot_free"); if (r) return r;
     if ((r = end_pending_raster(c))) return r;
     return c->zsnap[slot].release(c);
+}
+
+// ---- TGAImage::gaussian_blur and TGAImage::scale (tgaimage.cpp:246-324) ------------------------------------------------------------
+static int image_fail(trgl_ctx* c, int code, const std::string& msg) { if (c) c->err = msg; else g_create_error = msg; return code; }
+
+int trgl_gaussian_kernel(int radius, float* weights) {
+    if (radius <= 0 || !weights) return image_fail(nullptr, TRGL_E_INVALID, "trgl_gaussian_kernel: need radius >= 1 and room for 2 * radius + 1 weights");
+    if (radius > TRGL_MAX_BLUR_RADIUS) return image_fail(nullptr, TRGL_E_UNSUPPORTED, "trgl_gaussian_kernel: radius above 46340 (i * i overflows the reference's int)");
+    trgl_image::gaussian_weights(radius, weights);
+    return TRGL_OK;
+}
+
+// The weights of `radius` in c->blur_weights, uploaded on the stream unless the previous blur left the same ones there.
+static int upload_blur_weights(trgl_ctx* c, int radius) {
+    if (c->blur_radius == radius) return TRGL_OK;
+    const size_t n = 2 * (size_t)radius + 1;
+    if (!c->ev_blur_w) HIPCHK(c, hipEventCreateWithFlags(&c->ev_blur_w, hipEventDisableTiming));
+    HIPCHK(c, hipEventSynchronize(c->ev_blur_w));            // the previous upload has read the pinned weights (no wait when none was queued)
+    c->blur_radius = 0;
+    if (n > c->blur_w_pinned_cap) {
+        if (c->blur_w_pinned) { HIPCHK(c, hipHostFree(c->blur_w_pinned)); c->blur_w_pinned = nullptr; c->blur_w_pinned_cap = 0; }
+        HIPCHK(c, hipHostMalloc((void**)&c->blur_w_pinned, headroom(n) * sizeof(float)));
+        c->blur_w_pinned_cap = headroom(n);
+    }
+    if (int r = c->blur_weights.grow(c, n)) return r;
+    trgl_image::gaussian_weights(radius, c->blur_w_pinned);
+    HIPCHK(c, hipMemcpyAsync(c->blur_weights.p, c->blur_w_pinned, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_blur_w, c->stream));
+    c->blur_radius = radius;
+    return TRGL_OK;
+}
+
+// both passes of the blur over device memory, queued on the stream; nbytes = w * h * bpp
+static int queue_blur(trgl_ctx* c, uint8_t* pixels, int w, int h, int bpp, int radius, size_t nbytes) {
+    int r = upload_blur_weights(c, radius); if (r) return r;
+    if ((r = c->blur_tmp.grow(c, nbytes))) return r;
+    launch_image_blur(c->stream, pixels, w, h, bpp, radius, c->blur_weights.p, c->blur_tmp.p);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_image_blur(trgl_ctx* c, uint8_t* pixels, int w, int h, int bpp, int radius, int mem_kind) {
+    if (mem_kind != TRGL_MEM_HOST && mem_kind != TRGL_MEM_DEVICE) return image_fail(c, TRGL_E_INVALID, "trgl_image_blur: bad mem_kind");
+    if (!(bpp == 1 || bpp == 3 || bpp == 4) || w < 0 || h < 0) return image_fail(c, TRGL_E_INVALID, "trgl_image_blur: need w, h >= 0 and bpp in {1, 3, 4}");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return image_fail(c, TRGL_E_INVALID, "trgl_image_blur: TRGL_MEM_DEVICE needs a context");
+    if (radius <= 0 || w == 0 || h == 0) return TRGL_OK;                         // tgaimage.cpp:272
+    if (!pixels) return image_fail(c, TRGL_E_INVALID, "trgl_image_blur: pixels is null");
+    if (radius > TRGL_MAX_BLUR_RADIUS) return image_fail(c, TRGL_E_UNSUPPORTED, "trgl_image_blur: radius above 46340 (i * i overflows the reference's int)");
+    if ((int64_t)w * h * bpp > INT_MAX) return image_fail(c, TRGL_E_UNSUPPORTED, "trgl_image_blur: w * h * bpp above INT_MAX (the reference's int byte index overflows)");
+    const size_t nbytes = (size_t)w * h * bpp;
+    if (mem_kind == TRGL_MEM_HOST) {
+        try {
+            std::vector<float> weights(2 * (size_t)radius + 1);
+            std::vector<uint8_t> tmp(nbytes);
+            trgl_image::gaussian_weights(radius, weights.data());
+            trgl_image::blur_bytes(pixels, w, h, bpp, radius, weights.data(), tmp.data());
+        } catch (const std::bad_alloc&) { return image_fail(c, TRGL_E_NOMEM, "trgl_image_blur: out of memory"); }
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    return queue_blur(c, pixels, w, h, bpp, radius, nbytes);
+}
+
+int trgl_image_scale(trgl_ctx* c, const uint8_t* src, int w, int h, int bpp, uint8_t* dst, int w2, int h2, int mem_kind) {
+    if (mem_kind != TRGL_MEM_HOST && mem_kind != TRGL_MEM_DEVICE) return image_fail(c, TRGL_E_INVALID, "trgl_image_scale: bad mem_kind");
+    if (!(bpp == 1 || bpp == 3 || bpp == 4)) return image_fail(c, TRGL_E_INVALID, "trgl_image_scale: bpp must be 1, 3 or 4");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return image_fail(c, TRGL_E_INVALID, "trgl_image_scale: TRGL_MEM_DEVICE needs a context");
+    if (w2 <= 0 || h2 <= 0 || w <= 0 || h <= 0) return image_fail(c, TRGL_E_INVALID, "trgl_image_scale: a size <= 0 or an empty source (the reference returns false)");   // tgaimage.cpp:247
+    if (!src || !dst) return image_fail(c, TRGL_E_INVALID, "trgl_image_scale: null image");
+    if ((int64_t)(w2 - 1) * w > INT_MAX || (int64_t)(h2 - 1) * h > INT_MAX || (int64_t)w2 * h2 * bpp > INT_MAX || (int64_t)w * h * bpp > INT_MAX)
+        return image_fail(c, TRGL_E_UNSUPPORTED, "trgl_image_scale: (w2 - 1) * w, (h2 - 1) * h or a byte count above INT_MAX (the reference's int arithmetic overflows)");
+    const size_t nsrc = (size_t)w * h * bpp, ndst = (size_t)w2 * h2 * bpp;
+    if ((uintptr_t)src < (uintptr_t)dst + ndst && (uintptr_t)dst < (uintptr_t)src + nsrc) return image_fail(c, TRGL_E_INVALID, "trgl_image_scale: src and dst overlap");
+    if (mem_kind == TRGL_MEM_HOST) { trgl_image::scale_bytes(src, w, h, bpp, dst, w2, h2); return TRGL_OK; }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    launch_image_scale(c->stream, src, w, h, bpp, dst, w2, h2);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_framebuffer_blur(trgl_ctx* c, int radius) {
+    CHKCTX(c);
+    if (c->strip_y0 != 0 || c->strip_y1 != c->H || c->il_world > 1)
+        return fail(c, TRGL_E_STATE, "trgl_framebuffer_blur: the context owns a strip or interleaved bands; the vertical pass would read rows of another rank");
+    if (radius <= 0) return TRGL_OK;                                             // tgaimage.cpp:272
+    if (radius > TRGL_MAX_BLUR_RADIUS) return fail(c, TRGL_E_UNSUPPORTED, "trgl_framebuffer_blur: radius above 46340 (i * i overflows the reference's int)");
+    if ((int64_t)c->W * c->H * c->bpp > INT_MAX) return fail(c, TRGL_E_UNSUPPORTED, "trgl_framebuffer_blur: W * H * bpp above INT_MAX (the reference's int byte index overflows)");
+    int r = trgl_flush(c); if (r) return r;          // completes a begun flush, draws what is queued, runs a pending clear
+    return queue_blur(c, c->fb.p, c->W, c->H, c->bpp, radius, (size_t)c->W * c->H * c->bpp);
 }
 
 void* trgl_framebuffer_device_ptr(trgl_ctx* c) { return c ? c->fb.p : nullptr; }

@@ -27,6 +27,8 @@
 //   * gl_zbuffer_snapshot(slot) / gl_zbuffer_restore(slot) do what `saved = zbuffer;` / `zbuffer = saved;` (main.cpp:700,730) do without
 //     the depths crossing PCIe twice; gl_mesh_bounds(model) is Model::computeAABB (model.cpp:15-40) for a model of the caller's own.
 //     gl_mesh_normals(model) / gl_mesh_tangents(model) are Model::generateNormalsIfNeeded / computeTangentsIfNeeded (model.cpp:269-388).
+//   * gl_gaussian_blur(framebuffer, radius) is framebuffer.gaussian_blur(radius) (tgaimage.cpp:271-324) on the frame in HBM, byte for
+//     byte; TGAImage::scale / gaussian_blur themselves are host loops in trgl_image.h, as in the reference.
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -521,6 +523,16 @@ inline bool gl_zbuffer_restore(TGAImage& framebuffer, int slot = 0) {
     if (!TRGL_SHIM_OK(trgl_zbuffer_restore(s.ctx, slot))) return false;
     s.zbuffer_stale_on_host = true; s.zbuffer_dirty_on_host = false;
     return ok;
+}
+
+// framebuffer.gaussian_blur(radius) (tgaimage.cpp:271-324) on the frame where it lives, in HBM: triangles batched so far are drawn first,
+// then trgl_framebuffer_blur runs on the device without waiting.  The caller's TGAImage still holds the old pixels; a later
+// gl_flush(framebuffer) hands back the blurred ones.  (An image that is not the framebuffer: TGAImage::gaussian_blur, on the host.)
+inline bool gl_gaussian_blur(TGAImage& framebuffer, int radius) {
+    using namespace trgl_shim;
+    if (!bind(framebuffer)) return false;
+    const bool ok = submit_batch();
+    return TRGL_SHIM_OK(trgl_framebuffer_blur(state().ctx, radius)) && ok;
 }
 
 inline void print_render_stats() {                                                // our_gl.cpp:204-210

@@ -3,13 +3,83 @@
 // imagedescriptor 0x00 when vflip (the default), RLE packets formed exactly as the reference forms
 // them (its raw packets run up to AND INCLUDING the first pixel of the next repeated pair).
 // The reader follows read_tga_file / load_rle_data (tgaimage.cpp:76-160).  Host-only; this is SURVEY.md §8(f) row N3.
+// scale() and gaussian_blur() (tgaimage.cpp:246-324) are host loops over trgl_image::scale_bytes / blur_bytes below, the same functions
+// the C ABI's TRGL_MEM_HOST paths run (trgl_image_scale, trgl_image_blur); compile with -ffp-contract=off, as everything that must
+// match the reference's bytes.
 #pragma once
+#include <cmath>
 #include <cstdint>
+#include <cstddef>
 #include <cstring>
 #include <fstream>
 #include <iterator>
 #include <string>
 #include <vector>
+
+namespace trgl_image {
+
+// The weights of TGAImage::gaussian_blur (tgaimage.cpp:275-284) for radius >= 1, all in float: sigma = radius / 2, v[i] =
+// exp(-(i * i) / (2 * sigma * sigma)) with the int -(i * i) converted, summed in index order from 0, each then divided by the sum.
+// radius <= 46340, so that i * i fits an int.
+inline void gaussian_weights(int radius, float* weights) {
+    const float sigma = radius / 2.0f;
+    float sum = 0;
+    for (int i = -radius; i <= radius; ++i) {
+        const float v = std::exp(float(-(i * i)) / (2 * sigma * sigma));
+        weights[i + radius] = v;
+        sum += v;
+    }
+    for (int k = 0; k <= 2 * radius; ++k) weights[k] /= sum;
+}
+
+// One pass of the separable blur (tgaimage.cpp:290-304 or :309-323) from `src` into `dst`, two images of w * h * bpp bytes that do not
+// overlap: per byte a float sum from 0.0f over the taps k = -radius..radius in that order of byte(clamped neighbour) * weight - one
+// rounded multiply and one rounded add per tap - stored truncated.  Neighbours lie along x (stride bpp, clamped to 0..w-1) or along y
+// (stride w * bpp, clamped to 0..h-1); every channel is treated alike.  The sums of one row are kept side by side and the tap loop runs
+// outside them: every sum still receives its own taps in the reference's order, and the inner loops are plain arrays for the compiler.
+inline void blur_pass(const std::uint8_t* src, std::uint8_t* dst, int w, int h, int bpp, int radius, const float* weights, bool vertical) {
+    const std::size_t row = std::size_t(w) * bpp;
+    std::vector<float> accum(row);
+    float* acc = accum.data();
+    auto add = [acc](std::size_t b, std::uint8_t byte, float kv) { const float term = float(int(byte)) * kv; acc[b] = acc[b] + term; };
+    for (int y = 0; y < h; ++y) {
+        for (std::size_t b = 0; b < row; ++b) acc[b] = 0.0f;
+        for (int k = -radius; k <= radius; ++k) {
+            const float kv = weights[k + radius];
+            if (vertical) {
+                const int yy = y + k < 0 ? 0 : y + k > h - 1 ? h - 1 : y + k;
+                const std::uint8_t* s = src + yy * row;
+                for (std::size_t b = 0; b < row; ++b) add(b, s[b], kv);
+            } else {
+                const std::uint8_t* s = src + y * row;
+                const int lo = k < 0 ? (-k < w ? -k : w) : 0, hi = k > 0 ? (w - k > 0 ? w - k : 0) : w;     // x in [lo, hi): x + k needs no clamp
+                for (int x = 0; x < lo; ++x) for (int ch = 0; ch < bpp; ++ch) add(std::size_t(x) * bpp + ch, s[ch], kv);
+                const std::ptrdiff_t shift = std::ptrdiff_t(k) * bpp;
+                for (std::size_t b = std::size_t(lo) * bpp; b < std::size_t(hi > lo ? hi : lo) * bpp; ++b) add(b, s[std::ptrdiff_t(b) + shift], kv);
+                for (int x = hi > lo ? hi : lo; x < w; ++x) for (int ch = 0; ch < bpp; ++ch) add(std::size_t(x) * bpp + ch, s[std::size_t(w - 1) * bpp + ch], kv);
+            }
+        }
+        for (std::size_t b = 0; b < row; ++b) dst[y * row + b] = std::uint8_t(acc[b]);
+    }
+}
+// TGAImage::gaussian_blur (tgaimage.cpp:286-323) in place on w * h * bpp bytes: the horizontal pass into `tmp` (as many bytes), the
+// vertical pass back - so the vertical pass reads the horizontal pass's truncated bytes, as the reference's second copy does.
+inline void blur_bytes(std::uint8_t* pixels, int w, int h, int bpp, int radius, const float* weights, std::uint8_t* tmp) {
+    blur_pass(pixels, tmp, w, h, bpp, radius, weights, false);
+    blur_pass(tmp, pixels, w, h, bpp, radius, weights, true);
+}
+
+// TGAImage::scale (tgaimage.cpp:251-261): dst(x, y) = src(x * w / w2, y * h / h2) in int arithmetic, bpp bytes per pixel.  The caller
+// has checked that (w2 - 1) * w, (h2 - 1) * h and the byte counts fit an int.
+inline void scale_bytes(const std::uint8_t* src, int w, int h, int bpp, std::uint8_t* dst, int w2, int h2) {
+    for (int y = 0; y < h2; ++y) {
+        const std::uint8_t* srow = src + std::size_t(y * h / h2) * w * bpp;
+        std::uint8_t* drow = dst + std::size_t(y) * w2 * bpp;
+        for (int x = 0; x < w2; ++x) std::memcpy(drow + std::size_t(x) * bpp, srow + std::size_t(x * w / w2) * bpp, bpp);
+    }
+}
+
+}  // namespace trgl_image
 
 struct TGAColor {
     std::uint8_t bgra[4] = { 0, 0, 0, 255 };
@@ -62,6 +132,24 @@ public:
     void flip_horizontally() {
         for (int y = 0; y < h; ++y) for (int x = 0; x < w / 2; ++x) for (int k = 0; k < bpp; ++k)
             std::swap(data[(std::size_t(x) + std::size_t(y) * w) * bpp + k], data[(std::size_t(w - 1 - x) + std::size_t(y) * w) * bpp + k]);
+    }
+    // tgaimage.cpp:246-267: nearest-texel resize in the reference's int arithmetic; false (and nothing changed) for a size <= 0 or an empty image
+    bool scale(int w2, int h2) {
+        if (w2 <= 0 || h2 <= 0 || data.empty()) return false;
+        std::vector<std::uint8_t> tdata(std::size_t(w2) * h2 * bpp);
+        trgl_image::scale_bytes(data.data(), w, h, bpp, tdata.data(), w2, h2);
+        w = w2; h = h2;
+        data.swap(tdata);
+        return true;
+    }
+    // tgaimage.cpp:271-324: separable Gaussian blur with clamped edges, float weights and a byte-quantised intermediate; does nothing for
+    // radius <= 0 or an empty image.  (The reference's int i * i overflows beyond radius 46340; such a radius is not meaningful there either.)
+    void gaussian_blur(const int radius) {
+        if (radius <= 0 || data.empty()) return;
+        std::vector<float> kernel(std::size_t(radius) * 2 + 1);
+        trgl_image::gaussian_weights(radius, kernel.data());
+        std::vector<std::uint8_t> tmp(data.size());
+        trgl_image::blur_bytes(data.data(), w, h, bpp, radius, kernel.data(), tmp.data());
     }
 
     // The exact bytes TGAImage::write_tga_file(name, vflip, rle) puts on disk.
