@@ -97,7 +97,8 @@ TRI_REC = np.dtype([(n, "<f8") for n in ("ax", "ay", "s0x", "s0y", "s1x", "s1y",
 assert TRI_REC.itemsize == 128, "TRI_REC must mirror sizeof(TriRec) == 128"
 DBG_RECS, DBG_CNT, DBG_TILEBOX, DBG_VALS, DBG_BMASK, DBG_TILE_START, DBG_TILE_END, DBG_INFO = range(8)
 DBG_INFO_FIELDS = ("N", "P", "capacity", "wide", "literal_tris", "large_tris", "zq_cull", "pending", "W", "H", "tiles_x", "tiles_y",
-                   "strip_y0", "strip_y1", "strip_ty0", "strip_ty1", "il_tiles", "il_world", "il_rank", "side")
+                   "strip_y0", "strip_y1", "strip_ty0", "strip_ty1", "il_tiles", "il_world", "il_rank", "side", "direct", "fell_back")
+BIN_AUTO, BIN_EXPAND, BIN_DIRECT = 0, 1, 2      # trgl_debug_binning: how the next flushes bin
 DL_LITERAL = 0x80000000       # TRGL_DL_LITERAL
 
 
@@ -154,6 +155,8 @@ def load_library(path: str = None):
     L.trgl_get_last_flush_info.argtypes = [vp, u64p, u64p, u64p]
     if hasattr(L, "trgl_debug_read"):      # (diagnostic, not part of include/trgl.h: an older build named by TRGL_LIB may lack it)
         L.trgl_debug_read.argtypes = [vp, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "trgl_debug_binning"):
+        L.trgl_debug_binning.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.trgl_selftest_division.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
     L.trgl_selftest_sampler.argtypes = [vp, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.trgl_draw_indexed.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
@@ -829,6 +832,14 @@ class Context:
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._chk(self.L.trgl_get_last_flush_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(triangles=a.value, pairs=b.value, tiles=c.value)
+
+    def debug_binning(self, mode=None, S=0, G=0):
+        """Test hook (trgl_debug_binning).  mode BIN_AUTO / BIN_EXPAND / BIN_DIRECT (with segments of S pair slots and groups of G
+        setup blocks) sets how the next flushes bin; None changes nothing.  Returns what the last complete flush did:
+        dict(direct=..., fell_back=...)."""
+        d, f = C.c_int(), C.c_int()
+        self._chk(self.L.trgl_debug_binning(self.h, -1 if mode is None else mode, S, G, C.byref(d), C.byref(f)))
+        return dict(direct=bool(d.value), fell_back=bool(f.value))
 
     def _debug_read(self, what, dtype):
         need = C.c_size_t()

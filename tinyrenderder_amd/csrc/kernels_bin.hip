@@ -33,6 +33,79 @@ __device__ __forceinline__ int wave_max_i(int v) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// block-level scan helpers (the radix histograms are scanned row by row in k_radix_scan_rows)
+// ---------------------------------------------------------------------------------------------
+constexpr int SCAN_THREADS = 256;
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+    int lane = threadIdx.x & 63;
+    for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(v, o); if (lane >= o) v += t; }
+    return v;
+}
+
+// block-wide exclusive scan of one value per thread (256 threads); returns exclusive prefix, total in *total
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* smem /*[4]*/, uint32_t* total) {
+    uint32_t inc = wave_incl_scan(v);
+    int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __syncthreads();
+    if (lane == 63) smem[w] = inc;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_THREADS / 64; ++k) { uint32_t s = smem[k]; if (k < w) base += s; tot += s; }
+    *total = tot;
+    return base + inc - v;
+}
+
+// blocks of tile (tx, ty) inside the block-unit box [qx0, qx1] x [qy0, qy1] (the box reaches the tile)
+__device__ __forceinline__ uint32_t tile_block_mask(uint32_t tx, uint32_t ty, uint32_t qx0, uint32_t qy0, uint32_t qx1, uint32_t qy1) {
+    const uint32_t c0 = qx0 > 4 * tx ? qx0 - 4 * tx : 0u, c1 = qx1 < 4 * tx + 3 ? qx1 - 4 * tx : 3u;
+    const uint32_t r0 = qy0 > 4 * ty ? qy0 - 4 * ty : 0u, r1 = qy1 < 4 * ty + 3 ? qy1 - 4 * ty : 3u;
+    return (((2u << c1) - (1u << c0)) & 0xfu) * 0x1111u & ((0xffffu >> (12 - 4 * r1)) & (0xffffu << (4 * r0)));
+}
+// The pairs of a block of 256 triangles, the one statement of their rules for k_expand and for k_setup's direct path.  Thread `tid` holds
+// triangle i of the flush: c tiles, the box `tb` k_setup left in `tilebox`, and o = the pairs of the block's earlier triangles.
+// put(j, tile id, triangle word, mask) receives pair j of the block: a triangle's tiles in row-major order over the tile rows this
+// context owns, the triangle word = index | zq << 25 (TRGL_VAL_TRI | TRGL_VAL_ZQ).  Triangles with more than 8 tiles are written
+// by the whole wave.  No barrier inside.
+template <class Put>
+__device__ __forceinline__ void block_pairs(const FrameParams& fp, int tiles_x, uint32_t i, uint32_t c, uint2 tb, uint32_t o, Put put) {
+    constexpr uint32_t SMALL = 8;
+    if (c && c <= SMALL) {
+        // row-major walk with running counters instead of a division and a modulo per pair
+        const uint32_t qx0 = tb.x & 0x1fff, qy0 = (tb.x >> 16) & 0x1fff, qx1 = tb.y & 0x1fff, qy1 = (tb.y >> 16) & 0x1fff;
+        const uint32_t iz = i | ((((tb.x >> 13) & 7u) | (((tb.y >> 13) & 7u) << 3) | ((tb.y >> 29) << 6)) << 25);      // TRGL_VAL_TRI | TRGL_VAL_ZQ
+        const uint32_t tx0 = qx0 >> 2, ty0 = qy0 >> 2, tx1 = qx1 >> 2;
+        uint32_t tx = tx0, row = 0;
+        uint32_t ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, 0) : ty0;
+        for (uint32_t k = 0; k < c; ++k) {
+            put(o + k, ty * tiles_x + tx, iz, tile_block_mask(tx, ty, qx0, qy0, qx1, qy1));
+            if (++tx > tx1) { tx = tx0; ++row; ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, (int)row) : ty0 + row; }
+        }
+    }
+    unsigned long long big = __ballot(c > SMALL);
+    const int lane = threadIdx.x & 63;
+    while (big) {
+        int src = __ffsll((long long)big) - 1;
+        big &= big - 1;
+        uint32_t cc = __shfl(c, src), oo = __shfl(o, src), ii = __shfl(i, src);
+        uint32_t bx = __shfl(tb.x, src), by = __shfl(tb.y, src);
+        const uint32_t qx0 = bx & 0x1fff, qy0 = (bx >> 16) & 0x1fff, qx1 = by & 0x1fff, qy1 = (by >> 16) & 0x1fff;
+        ii |= (((bx >> 13) & 7u) | (((by >> 13) & 7u) << 3) | ((by >> 29) << 6)) << 25;
+        uint32_t tx0 = qx0 >> 2, ty0 = qy0 >> 2, tx1 = qx1 >> 2;
+        uint32_t wdt = tx1 - tx0 + 1;
+        for (uint32_t k = lane; k < cc; k += 64) {
+            uint32_t ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, (int)(k / wdt)) : ty0 + k / wdt, tx = tx0 + k % wdt;
+            put(oo + k, ty * tiles_x + tx, ii, tile_block_mask(tx, ty, qx0, qy0, qx1, qy1));
+        }
+    }
+}
+
+// the direct path's segments: at most SEG_MAX pair slots per setup block (two words per pair fill k_setup's 32 KB of LDS), a multiple of 4;
+// a block of the first radix pass owns at most SEG_MAX_GROUP consecutive segments
+constexpr uint32_t SEG_MAX = 4096, SEG_MAX_GROUP = 16;
+
+// ---------------------------------------------------------------------------------------------
 // setup: one thread per triangle of one draw.  Follows our_gl.cpp:89-141 line by line.
 // HBM traffic is staged through LDS so that both the 96-B/triangle clip stream and the 128-B/triangle
 // record stream move as 16 B per lane, fully coalesced (a lane reading its own 96-B triangle straight
@@ -43,8 +116,9 @@ constexpr int SETUP_THREADS = 256;
 __global__ __launch_bounds__(SETUP_THREADS) void k_setup(FrameParams fp, DrawDesc d, DrawDesc* __restrict__ draws_out, int draw_idx,
                                                          TriRec* __restrict__ recs, TriW* __restrict__ recs_w, uint32_t* __restrict__ cnt,
                                                          uint2* __restrict__ tilebox, DevStats* __restrict__ stats,
-                                                         uint32_t* __restrict__ blk_sums, uint32_t blk_base) {
-    __shared__ __attribute__((aligned(16))) double s_buf[SETUP_THREADS * 16];    // 32 KB: in [256][12], then out [256][16]
+                                                         uint32_t* __restrict__ blk_sums, uint32_t blk_base,
+                                                         uint32_t* __restrict__ seg_k, uint32_t* __restrict__ seg_v, uint32_t seg_S) {
+    __shared__ __attribute__((aligned(16))) double s_buf[SETUP_THREADS * 16];    // 32 KB: in [256][12], then out [256][16], then the block's pairs
     // The draw's descriptor arrives as a kernel argument (scalar loads from the argument segment; no copy command on the stream before
     // the flush's first kernel) and is left in device memory for the kernels behind this one, which read uniforms and arrays through it.
     if (blockIdx.x == 0 && threadIdx.x == 0) draws_out[draw_idx] = d;
@@ -230,17 +304,6 @@ __global__ __launch_bounds__(SETUP_THREADS) void k_setup(FrameParams fp, DrawDes
             }
         }
     }
-    // pairs of this block of 256 triangles: k_expand derives every triangle's slice of the pair list from these sums
-    // (k_chunk_spine) and a block-level scan of `cnt`, so no scan pass ever walks the N-element arrays
-    {
-        uint32_t ws = ntiles;
-        for (int o = 32; o; o >>= 1) ws += __shfl_xor(ws, o);
-        __syncthreads();                                   // every wave is done with the staging buffer
-        uint32_t* s_ws = reinterpret_cast<uint32_t*>(s_buf);
-        if (lane == 0) s_ws[tid >> 6] = ws;
-        __syncthreads();
-        if (tid == 0) blk_sums[blk_base + blockIdx.x] = s_ws[0] + s_ws[1] + s_ws[2] + s_ws[3];
-    }
     // triangles with pairs that take the literal (dividing) path of k_raster: none in any realistic frame, and then the host
     // launches the raster kernel that does not contain that path (trgl_flush_end)
     {
@@ -260,31 +323,30 @@ __global__ __launch_bounds__(SETUP_THREADS) void k_setup(FrameParams fp, DrawDes
         if (wx1 > __builtin_nontemporal_load(&stats->max_x)) atomicMax(&stats->max_x, wx1);
         if (wy1 > __builtin_nontemporal_load(&stats->max_y)) atomicMax(&stats->max_y, wy1);
     }
-}
-
-// ---------------------------------------------------------------------------------------------
-// block-level scan helpers (the radix histograms are scanned row by row in k_radix_scan_rows)
-// ---------------------------------------------------------------------------------------------
-constexpr int SCAN_THREADS = 256;
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(v, o); if (lane >= o) v += t; }
-    return v;
-}
-
-// block-wide exclusive scan of one value per thread (256 threads); returns exclusive prefix, total in *total
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* smem /*[4]*/, uint32_t* total) {
-    uint32_t inc = wave_incl_scan(v);
-    int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 63) smem[w] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_THREADS / 64; ++k) { uint32_t s = smem[k]; if (k < w) base += s; tot += s; }
-    *total = tot;
-    return base + inc - v;
+    // pairs of this block of 256 triangles: the offset of every triangle's pairs inside the block's run, and the run's length.
+    // k_expand derives every triangle's slice of the pair list from these sums (k_chunk_spine) and a block-level scan of `cnt`,
+    // so no scan pass ever walks the N-element arrays.
+    uint32_t tot;
+    const uint32_t off = block_excl_scan(ntiles, reinterpret_cast<uint32_t*>(s_buf), &tot);      // (its first barrier: every wave is done with the staging buffer)
+    if (tid == 0) blk_sums[blk_base + blockIdx.x] = tot;
+    // The direct path (seg_S != 0): the block leaves its pairs itself, in submission order, in its own segment of seg_S slots -
+    // no offset from any other block is needed.  They are assembled in the staging buffer (sort words in its first half, triangle
+    // words in its second: SEG_MAX slots each) and go out linearly, 16 bytes per lane.  A block with more pairs than the segment
+    // holds writes none: k_chunk_spine sees its sum and flags the flush, which then takes k_expand.
+    if (seg_S && tot && tot <= seg_S) {                      // block-uniform
+        __syncthreads();                                     // the scan's wave totals have been read
+        uint32_t* const s_k = reinterpret_cast<uint32_t*>(s_buf);
+        uint32_t* const s_v = s_k + SEG_MAX;
+        block_pairs(fp, fp.tiles_x, d.first + i, ntiles, tb, off, [&](uint32_t j, uint32_t key, uint32_t iz, uint32_t m) { s_k[j] = key | (m << 16); s_v[j] = iz; });
+        __syncthreads();
+        uint4* const kq = reinterpret_cast<uint4*>(seg_k + (size_t)(blk_base + blockIdx.x) * seg_S);
+        uint4* const vq = reinterpret_cast<uint4*>(seg_v + (size_t)(blk_base + blockIdx.x) * seg_S);
+        // (seg_S is a multiple of 4: the last 16-byte group stays inside the segment; its words past `tot` are never read)
+        for (uint32_t q = tid; 4 * q < tot; q += SETUP_THREADS) {
+            kq[q] = *reinterpret_cast<const uint4*>(s_k + 4 * q);
+            vq[q] = *reinterpret_cast<const uint4*>(s_v + 4 * q);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -299,8 +361,30 @@ constexpr int SPINE_THREADS = 1024;
 __global__ __launch_bounds__(SPINE_THREADS) void k_chunk_spine(const uint32_t* __restrict__ blk_sums, uint32_t nblk,
                                                                uint32_t* __restrict__ chunk_off,
                                                                unsigned long long* __restrict__ total64, unsigned long long* __restrict__ host_copy,
-                                                               uint4* __restrict__ bounds16, uint32_t n_half16) {
+                                                               uint4* __restrict__ bounds16, uint32_t n_half16,
+                                                               uint32_t seg_S, uint32_t seg_G, uint32_t seg_chunk,
+                                                               uint32_t* __restrict__ seg_flag, uint32_t* __restrict__ seg_flag_host) {
     __shared__ unsigned long long s_wave[SPINE_THREADS / 64];
+    // Do the flush's counts fit the direct path's segments (k_setup) and groups (the first radix pass)?  seg_flag = 1 when a setup block
+    // has more than seg_S pairs or seg_G consecutive blocks have more than seg_chunk (or seg_S is 0: no sizes to fit).  The kernels of
+    // the direct path do nothing then, and the host queues k_expand and the dense passes (trgl_flush_end).  Evaluated for every
+    // flush, also one that takes k_expand anyway: the host returns to the direct path once a flush fits.
+    // (the blocks against seg_S, and groups of 16 - which are the chunks - against seg_chunk, in the scan loop below; groups of another
+    // size here: one group per thread, its up to 16 loads issued together)
+    int seg_bad = seg_S == 0;
+    if (seg_S && seg_G != EXPAND_CHUNK) {
+        for (uint32_t g = threadIdx.x; (uint64_t)g * seg_G < nblk; g += SPINE_THREADS) {
+            uint32_t t[EXPAND_CHUNK];
+#pragma unroll
+            for (uint32_t k = 0; k < EXPAND_CHUNK; ++k) { const uint32_t q = g * seg_G + k; t[k] = (k < seg_G && q < nblk) ? blk_sums[q] : 0u; }
+            unsigned long long sum = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < EXPAND_CHUNK; ++k) sum += t[k];
+            seg_bad |= sum > seg_chunk;
+        }
+    }
+    const uint32_t blk_max = seg_S ? seg_S : ~0u;
+    const unsigned long long grp_max = (seg_S && seg_G == EXPAND_CHUNK) ? seg_chunk : ~0ull;
     // (the tile bounds of the flush start empty, tile_start at ~0 and tile_end at 0 - the last radix pass narrows them with atomics:
     // set here instead of by fill commands of their own on the stream, 4.6 us each)
     for (uint32_t k = threadIdx.x; k < 2 * n_half16; k += SPINE_THREADS) bounds16[k] = k < n_half16 ? make_uint4(~0u, ~0u, ~0u, ~0u) : make_uint4(0, 0, 0, 0);
@@ -319,10 +403,14 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_chunk_spine(const uint32_t* _
             if (q0 + EXPAND_CHUNK <= nblk) {
                 const uint4* p4 = reinterpret_cast<const uint4*>(blk_sums + q0);
 #pragma unroll
-                for (int k = 0; k < EXPAND_CHUNK / 4; ++k) { const uint4 t = p4[k]; v += (unsigned long long)t.x + t.y + t.z + t.w; }
+                for (int k = 0; k < EXPAND_CHUNK / 4; ++k) {
+                    const uint4 t = p4[k]; v += (unsigned long long)t.x + t.y + t.z + t.w;
+                    seg_bad |= max(max(t.x, t.y), max(t.z, t.w)) > blk_max;
+                }
             } else {
-                for (uint32_t q = q0; q < nblk; ++q) v += blk_sums[q];
+                for (uint32_t q = q0; q < nblk; ++q) { const uint32_t t = blk_sums[q]; v += t; seg_bad |= t > blk_max; }
             }
+            seg_bad |= v > grp_max;
         }
         unsigned long long inc = v;                                   // inclusive scan inside the wave
         for (int o = 1; o < 64; o <<= 1) { const unsigned long long t = __shfl_up(inc, o); if (lane >= o) inc += t; }
@@ -335,11 +423,13 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_chunk_spine(const uint32_t* _
         running += tot;
         __syncthreads();
     }
+    seg_bad = __syncthreads_or(seg_bad);
     if (threadIdx.x == 0) {
         *total64 = running;
         // The host needs the pair count and the two triangle counts that k_setup left behind it (DevStats: literal_tris, large_tris at
         // total64[1] and [2], pinned by the static_asserts under DevStats in trgl_device.h)
         // before it launches the raster: written straight into its pinned memory instead of a copy command on the stream (4.6 us).
+        *seg_flag = (uint32_t)seg_bad; *seg_flag_host = (uint32_t)seg_bad;
         host_copy[0] = running; host_copy[1] = total64[1]; host_copy[2] = total64[2];
         __threadfence_system();
     }
@@ -356,12 +446,6 @@ __global__ __launch_bounds__(SPINE_THREADS) void k_chunk_spine(const uint32_t* _
 // The sort word of a pair: while the frame has at most 65536 tiles (up to 8192x8192) the tile id in its low 16 bits and the mask in
 // its high 16 (one 4-byte stream for both); beyond that (WIDE) the 32-bit tile id, and the mask in a 16-bit stream of its own.
 constexpr uint32_t EXPAND_STAGE = 3072;
-// blocks of tile (tx, ty) inside the block-unit box [qx0, qx1] x [qy0, qy1] (the box reaches the tile)
-__device__ __forceinline__ uint32_t tile_block_mask(uint32_t tx, uint32_t ty, uint32_t qx0, uint32_t qy0, uint32_t qx1, uint32_t qy1) {
-    const uint32_t c0 = qx0 > 4 * tx ? qx0 - 4 * tx : 0u, c1 = qx1 < 4 * tx + 3 ? qx1 - 4 * tx : 3u;
-    const uint32_t r0 = qy0 > 4 * ty ? qy0 - 4 * ty : 0u, r1 = qy1 < 4 * ty + 3 ? qy1 - 4 * ty : 3u;
-    return (((2u << c1) - (1u << c0)) & 0xfu) * 0x1111u & ((0xffffu >> (12 - 4 * r1)) & (0xffffu << (4 * r0)));
-}
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_expand(FrameParams fp, uint32_t first, uint32_t n, int tiles_x, const uint32_t* __restrict__ cnt,
                                                 const uint32_t* __restrict__ blk_sums, const uint32_t* __restrict__ chunk_off,
@@ -397,35 +481,7 @@ __global__ __launch_bounds__(256) void k_expand(FrameParams fp, uint32_t first, 
         if (staged) { s_k[sh + j] = word; s_v[sh + j] = iz; if (WIDE) s_m[sh + j] = (uint16_t)m; }
         else { kdst[j] = word; vdst[j] = iz; if (WIDE) mdst[j] = (uint16_t)m; }
     };
-    constexpr uint32_t SMALL = 8;
-    if (c && c <= SMALL) {
-        // row-major walk with running counters instead of a division and a modulo per pair
-        const uint32_t qx0 = tb.x & 0x1fff, qy0 = (tb.x >> 16) & 0x1fff, qx1 = tb.y & 0x1fff, qy1 = (tb.y >> 16) & 0x1fff;
-        const uint32_t iz = i | ((((tb.x >> 13) & 7u) | (((tb.y >> 13) & 7u) << 3) | ((tb.y >> 29) << 6)) << 25);      // TRGL_VAL_TRI | TRGL_VAL_ZQ
-        const uint32_t tx0 = qx0 >> 2, ty0 = qy0 >> 2, tx1 = qx1 >> 2;
-        uint32_t tx = tx0, row = 0;
-        uint32_t ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, 0) : ty0;
-        for (uint32_t k = 0; k < c; ++k) {
-            put(o + k, ty * tiles_x + tx, iz, tile_block_mask(tx, ty, qx0, qy0, qx1, qy1));
-            if (++tx > tx1) { tx = tx0; ++row; ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, (int)row) : ty0 + row; }
-        }
-    }
-    unsigned long long big = __ballot(c > SMALL);
-    int lane = threadIdx.x & 63;
-    while (big) {
-        int src = __ffsll((long long)big) - 1;
-        big &= big - 1;
-        uint32_t cc = __shfl(c, src), oo = __shfl(o, src), ii = __shfl(i, src);
-        uint32_t bx = __shfl(tb.x, src), by = __shfl(tb.y, src);
-        const uint32_t qx0 = bx & 0x1fff, qy0 = (bx >> 16) & 0x1fff, qx1 = by & 0x1fff, qy1 = (by >> 16) & 0x1fff;
-        ii |= (((bx >> 13) & 7u) | (((by >> 13) & 7u) << 3) | ((by >> 29) << 6)) << 25;
-        uint32_t tx0 = qx0 >> 2, ty0 = qy0 >> 2, tx1 = qx1 >> 2;
-        uint32_t wdt = tx1 - tx0 + 1;
-        for (uint32_t k = lane; k < cc; k += 64) {
-            uint32_t ty = fp.il_tiles ? (uint32_t)il_nth_owned_from(fp, (int)ty0, (int)(k / wdt)) : ty0 + k / wdt, tx = tx0 + k % wdt;
-            put(oo + k, ty * tiles_x + tx, ii, tile_block_mask(tx, ty, qx0, qy0, qx1, qy1));
-        }
-    }
+    block_pairs(fp, tiles_x, i, c, tb, o, put);
     if (staged) {
         __syncthreads();
         // LDS slots [sh, sh + tot) = pairs [base, base + tot); slot group q = the 16-byte-aligned pairs base - sh + 4q .. + 3.
@@ -467,10 +523,12 @@ constexpr int RADIX_MAX_BITS = 8;
 
 __global__ __launch_bounds__(256) void k_radix_hist(const uint32_t* __restrict__ keys, const unsigned long long* __restrict__ pairs_total,
                                                     uint32_t cap, int shift, int bits, uint32_t chunk,
-                                                    uint32_t nblocks, uint32_t* __restrict__ hist) {
+                                                    uint32_t nblocks, uint32_t* __restrict__ hist, const uint32_t* __restrict__ skip) {
     __shared__ uint32_t s_cnt[1 << RADIX_MAX_BITS];
     const unsigned long long P64 = *pairs_total;
-    const uint32_t P = P64 > cap ? 0u : (uint32_t)P64;      // over capacity: nothing was expanded; every block counts nothing
+    // over capacity: nothing was expanded; every block counts nothing.  skip: a later pass of the direct path, whose first pass did
+    // nothing when the flush did not fit the segments (k_chunk_spine's flag) - its input is not this flush's
+    const uint32_t P = (P64 > cap || (skip && *skip)) ? 0u : (uint32_t)P64;
     const uint32_t nb = 1u << bits, mask = nb - 1;
     for (uint32_t b = threadIdx.x; b < nb; b += 256) s_cnt[b] = 0;
     __syncthreads();
@@ -481,6 +539,53 @@ __global__ __launch_bounds__(256) void k_radix_hist(const uint32_t* __restrict__
         const uint32_t k[4] = { q.x, q.y, q.z, q.w };
 #pragma unroll
         for (int j = 0; j < 4; ++j) if (p + j < end) atomicAdd(&s_cnt[(k[j] >> shift) & mask], 1u);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < nb; b += 256) hist[(size_t)b * nblocks + blockIdx.x] = s_cnt[b];
+}
+
+// The first pass of the direct path reads k_setup's segments: a block owns seg.G consecutive setup blocks, whose pairs - segment after
+// segment, blk_sums[b] of them at b * seg.S - are its chunk in submission order.
+struct SegIn { const uint32_t* blk_sums; const uint32_t* flag; uint32_t nsetup, S, G; };
+
+__global__ __launch_bounds__(256) void k_radix_hist_seg(const uint32_t* __restrict__ seg_k, SegIn seg, const unsigned long long* __restrict__ pairs_total,
+                                                        uint32_t cap, int shift, int bits, uint32_t nblocks, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t s_cnt[1 << RADIX_MAX_BITS];
+    const bool live = *seg.flag == 0 && *pairs_total <= cap;      // else nothing is sorted from the segments: every block counts nothing
+    const uint32_t nb = 1u << bits, mask = nb - 1;
+    for (uint32_t b = threadIdx.x; b < nb; b += 256) s_cnt[b] = 0;
+    __syncthreads();
+    const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (live) {
+        // one wave per segment, wave w the segments w, w + 4, ...: the first 512 sort words of its (up to) four segments are requested
+        // together, the rare rest of a segment in a loop behind them
+        static_assert(SEG_MAX_GROUP == 16, "four waves of four segments");
+        auto count4 = [&](const uint4 q, uint32_t p, uint32_t n) {
+            const uint32_t k[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (p + j < n) atomicAdd(&s_cnt[(k[j] >> shift) & mask], 1u);
+        };
+        uint32_t n[4]; const uint32_t* keys[4]; uint4 q[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t sg = w + 4 * j, b = blockIdx.x * seg.G + sg;
+            const bool has = sg < seg.G && b < seg.nsetup;
+            n[j] = has ? min(seg.blk_sums[b], seg.S) : 0u;
+            keys[j] = seg_k + (size_t)(has ? b : 0u) * seg.S;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const uint32_t p = 4 * lane + 256 * it;                       // (S is a multiple of 4)
+                q[j][it] = p < n[j] ? *reinterpret_cast<const uint4*>(keys[j] + p) : make_uint4(0, 0, 0, 0);
+            }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int it = 0; it < 2; ++it) count4(q[j][it], 4 * lane + 256 * it, n[j]);
+            for (uint32_t p = 512 + 4 * lane; p < n[j]; p += 256) count4(*reinterpret_cast<const uint4*>(keys[j] + p), p, n[j]);
+        }
     }
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < nb; b += 256) hist[(size_t)b * nblocks + blockIdx.x] = s_cnt[b];
@@ -521,7 +626,18 @@ __global__ __launch_bounds__(ROWSCAN_THREADS) void k_radix_scan_rows(uint32_t* _
 // output, and a tile's slice is the union of its runs over the blocks, so each run takes its first position into tile_start[key]
 // (atomicMin; k_chunk_spine sets it to ~0) and its end into tile_end[key] (atomicMax; set to 0).  That is two atomics per run - about
 // 128 per block - where k_bounds read the whole sorted key list again.
-template <int RADIX_WAVES, bool WIDE, bool LAST>
+// f(r) for the rounds r = R, R + 1, ... < N of a wave whose part holds `part` pairs: as long as 64 r < part (r a constant in every call)
+template <int R, int N, class F>
+__device__ __forceinline__ void rounds_below(uint32_t part, F& f) {
+    if constexpr (R < N) {
+        if ((uint32_t)(R * 64) < part) { f(R); rounds_below<R + 1, N>(part, f); }
+    }
+}
+
+// SEG: the first pass of the direct path.  keys_in / vals_in are k_setup's segments and the block's chunk is the pairs of its seg.G setup
+// blocks: logical pair p of the chunk, in submission order, sits in segment s at p - s_off[s], for the s with s_off[s] <= p < s_off[s + 1].
+// Everything behind the loads - ranks, the reorder, the dense output - is the same code.
+template <int RADIX_WAVES, bool WIDE, bool LAST, bool SEG>
 __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                                                                  const uint16_t* __restrict__ msk_in,
                                                                  const unsigned long long* __restrict__ pairs_total, uint32_t cap,
@@ -529,8 +645,10 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
                                                                  const uint32_t* __restrict__ base, const uint32_t* __restrict__ totals,
                                                                  uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
                                                                  uint16_t* __restrict__ msk_out,
-                                                                 uint32_t* __restrict__ tile_start, uint32_t* __restrict__ tile_end) {
+                                                                 uint32_t* __restrict__ tile_start, uint32_t* __restrict__ tile_end, SegIn seg) {
     constexpr int RADIX_THREADS = RADIX_WAVES * 64, RADIX_CHUNK = RADIX_WAVES * RADIX_WAVE_CHUNK;
+    static_assert(!(SEG && WIDE), "the direct path sorts 32-bit sort words only");
+    __shared__ uint32_t s_off[SEG ? SEG_MAX_GROUP + 1 : 1];        // pairs of the group before segment s; [SEG_MAX_GROUP] = all of them
     __shared__ uint32_t s_cnt[RADIX_WAVES][1 << RADIX_MAX_BITS];     // per wave: running count, then (after phase 2) local start
     __shared__ uint32_t s_start[1 << RADIX_MAX_BITS];      // first local position of each digit in the chunk
     __shared__ uint32_t s_gbase[1 << RADIX_MAX_BITS];      // global position of the chunk's first pair of each digit
@@ -539,8 +657,17 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
     __shared__ uint16_t s_msk[WIDE ? RADIX_CHUNK : 2];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const unsigned long long P64 = *pairs_total;
-    const uint32_t P = P64 > cap ? 0u : (uint32_t)P64;
-    if ((uint64_t)blockIdx.x * RADIX_CHUNK >= P) return;     // the grid covers the capacity of the buffers, not the pairs of this flush
+    const uint32_t P = (P64 > cap || (!SEG && seg.flag && *seg.flag)) ? 0u : (uint32_t)P64;      // (seg.flag in a dense pass: a later pass of the direct path, k_radix_hist)
+    if (!SEG && (uint64_t)blockIdx.x * RADIX_CHUNK >= P) return;     // the grid covers the capacity of the buffers, not the pairs of this flush
+    if (SEG) {
+        if (*seg.flag || P64 > cap) return;                 // the flush does not fit the segments, or the output buffers: the host bins again
+        const uint32_t b = blockIdx.x * seg.G + lane;
+        if (w == 0) {
+            const uint32_t c = (lane < seg.G && b < seg.nsetup) ? seg.blk_sums[b] : 0u;
+            const uint32_t inc = wave_incl_scan(c);
+            if (lane <= SEG_MAX_GROUP) s_off[lane] = inc - c;     // (lanes from seg.G on hold the total: no pair is looked for behind it)
+        }
+    }
     const uint32_t nb = 1u << bits, mask = nb - 1;
     for (uint32_t b = threadIdx.x; b < nb; b += RADIX_THREADS) {
 #pragma unroll
@@ -560,10 +687,18 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < nb; b += RADIX_THREADS) s_gbase[b] += s_start[b];
     __syncthreads();
-    const uint64_t cbeg = (uint64_t)blockIdx.x * RADIX_CHUNK;
+    const uint64_t cbeg = SEG ? 0 : (uint64_t)blockIdx.x * RADIX_CHUNK;      // (SEG: positions inside the group)
     uint64_t cend = cbeg + RADIX_CHUNK; if (cend > P) cend = P;
+    // (SEG: a group rarely fills the chunk, so its pairs are dealt to the waves in equal parts, in order - fewer rounds for every wave
+    // instead of idle last waves; a part is a multiple of 64, and the rounds behind it are skipped)
+    uint32_t wave_part = RADIX_WAVE_CHUNK;
+    if (SEG) {
+        cend = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_off[SEG_MAX_GROUP]);
+        if (cend > (uint64_t)RADIX_CHUNK || seg.S > SEG_MAX || seg.G > SEG_MAX_GROUP) return;      // (k_chunk_spine flags such a flush: never taken; block-uniform)
+        wave_part = (((uint32_t)cend + RADIX_THREADS - 1) / RADIX_THREADS) * 64;
+    }
     const uint32_t n_chunk = (uint32_t)(cend - cbeg);
-    const uint64_t wbeg = cbeg + (uint64_t)w * RADIX_WAVE_CHUNK;
+    const uint64_t wbeg = cbeg + (uint64_t)w * wave_part;
     const unsigned long long lt = (1ull << lane) - 1ull;
 
     // ---- phase 1: stable rank of every pair among the equal digits of its wave's part ------------
@@ -572,12 +707,24 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
 #pragma unroll
     for (int r = 0; r < RADIX_ROUNDS; ++r) {
         const uint64_t p = wbeg + (uint64_t)r * 64 + lane;
-        const bool act = p < cend;
-        k[r] = act ? keys_in[p] : 0; v[r] = act ? vals_in[p] : 0;
-        if (WIDE) mk[WIDE ? r : 0] = act ? msk_in[p] : (uint16_t)0;
-    }
+        const bool act = p < cend && (!SEG || r * 64 < (int)wave_part);
+        if (SEG) {
+            // (a binary search over the group's 17 offsets per pair; measured against a table of the segment every 64th pair sits in
+            // and a walk from there: 98.6 against 104.5 us on the C4 frame)
+            const uint32_t lp = (uint32_t)p;
+            uint32_t sg = 0;
+            if (act) {
 #pragma unroll
-    for (int r = 0; r < RADIX_ROUNDS; ++r) {
+                for (uint32_t st = SEG_MAX_GROUP / 2; st; st >>= 1) if (lp >= s_off[sg + st]) sg += st;
+            }
+            const size_t a = (size_t)(blockIdx.x * seg.G + sg) * seg.S + (lp - s_off[sg]);
+            k[r] = act ? keys_in[a] : 0; v[r] = act ? vals_in[a] : 0;
+        } else {
+            k[r] = act ? keys_in[p] : 0; v[r] = act ? vals_in[p] : 0;
+            if (WIDE) mk[WIDE ? r : 0] = act ? msk_in[p] : (uint16_t)0;
+        }
+    }
+    auto rank_round = [&](const int r) {
         const bool act = wbeg + (uint64_t)r * 64 + lane < cend;
         const uint32_t dgt = (k[r] >> shift) & mask;
         unsigned long long same = __ballot(act);
@@ -591,6 +738,12 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
         rk[r] = cur + r_in;
         if (act && r_in == 0) s_cnt[w][dgt] = cur + (uint32_t)__popcll(same);
         __builtin_amdgcn_wave_barrier();
+    };
+    if constexpr (SEG) {
+        rounds_below<0, RADIX_ROUNDS>(wave_part, rank_round);       // (one forward branch out of the unrolled rounds, wave-uniform)
+    } else {
+#pragma unroll
+        for (int r = 0; r < RADIX_ROUNDS; ++r) rank_round(r);
     }
     __syncthreads();
     // ---- phase 2: local layout: digits ascending, inside a digit waves ascending ------------------------
@@ -622,14 +775,19 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
     }
     __syncthreads();
     // ---- phase 3: reorder in LDS (4-byte words: lanes of one digit write consecutive banks) ---------------------------
-#pragma unroll
-    for (int r = 0; r < RADIX_ROUNDS; ++r) {
+    auto place_round = [&](const int r) {
         if (wbeg + (uint64_t)r * 64 + lane < cend) {
             const uint32_t dgt = (k[r] >> shift) & mask;
             const uint32_t lp = s_cnt[w][dgt] + rk[r];
             s_key[lp] = k[r]; s_val[lp] = v[r];
             if (WIDE) s_msk[lp] = mk[WIDE ? r : 0];
         }
+    };
+    if constexpr (SEG) {
+        rounds_below<0, RADIX_ROUNDS>(wave_part, place_round);
+    } else {
+#pragma unroll
+        for (int r = 0; r < RADIX_ROUNDS; ++r) place_round(r);
     }
     __syncthreads();
     // ---- phase 4: linear read-out, contiguous global runs per digit ------------------------------------------
@@ -659,16 +817,18 @@ namespace trgl {
 uint32_t setup_num_blocks(uint32_t n) { return (n + SETUP_THREADS - 1) / SETUP_THREADS; }
 
 void launch_setup(hipStream_t s, const FrameParams& fp, const DrawDesc& draw, DrawDesc* draws_dev, int draw_idx, uint32_t n,
-                  TriRec* recs, TriW* recs_w, uint32_t* cnt, uint2* tilebox, DevStats* stats, uint32_t* blk_sums, uint32_t blk_base) {
+                  TriRec* recs, TriW* recs_w, uint32_t* cnt, uint2* tilebox, DevStats* stats, uint32_t* blk_sums, uint32_t blk_base,
+                  const SegLayout* seg) {
     if (!n) return;
     hipLaunchKernelGGL(k_setup, dim3(setup_num_blocks(n)), dim3(SETUP_THREADS), 0, s, fp, draw, draws_dev, draw_idx, recs, recs_w, cnt, tilebox,
-                       stats, blk_sums, blk_base);
+                       stats, blk_sums, blk_base, seg ? seg->keys : nullptr, seg ? seg->vals : nullptr, seg ? seg->S : 0u);
 }
 
 void launch_chunk_spine(hipStream_t s, const uint32_t* blk_sums, uint32_t nblk, uint32_t* chunk_off, unsigned long long* total64, unsigned long long* host_copy,
-                        uint32_t* tile_bounds, size_t half_words) {
+                        uint32_t* tile_bounds, size_t half_words, uint32_t seg_S, uint32_t seg_G, uint32_t seg_chunk, uint32_t* seg_flag,
+                        uint32_t* seg_flag_host) {
     hipLaunchKernelGGL(k_chunk_spine, dim3(1), dim3(SPINE_THREADS), 0, s, blk_sums, nblk, chunk_off, total64, host_copy, (uint4*)tile_bounds,
-                       (uint32_t)(half_words / 4));
+                       (uint32_t)(half_words / 4), seg_S, seg_G, seg_chunk, seg_flag, seg_flag_host);
 }
 
 void launch_expand(hipStream_t s, const FrameParams& fp, uint32_t first, uint32_t n, int tiles_x, const uint32_t* cnt, const uint32_t* blk_sums,
@@ -684,33 +844,49 @@ void launch_expand(hipStream_t s, const FrameParams& fp, uint32_t first, uint32_
 }
 
 static uint32_t radix_waves(uint32_t cap) { return cap >= RADIX_BIG_CAP ? 8u : 4u; }
+uint32_t radix_chunk(uint32_t cap) { return radix_waves(cap) * RADIX_WAVE_CHUNK; }
 // blocks of a pass over pair buffers of capacity `cap`
-uint32_t radix_num_workers(uint32_t cap) { const uint64_t chunk = radix_waves(cap) * RADIX_WAVE_CHUNK; return (uint32_t)((cap + chunk - 1) / chunk); }
+uint32_t radix_num_workers(uint32_t cap) { const uint64_t chunk = radix_chunk(cap); return (uint32_t)((cap + chunk - 1) / chunk); }
+uint32_t seg_num_groups(const SegLayout& seg) { return (seg.nsetup + seg.G - 1) / seg.G; }
+bool seg_layout_ok(const SegLayout& seg) { return seg.S >= 4 && seg.S <= SEG_MAX && seg.S % 4 == 0 && seg.G >= 1 && seg.G <= SEG_MAX_GROUP; }
 
 // The pair count of the flush stays on the device (`pairs_total`): grids cover `cap`, the capacity of the pair buffers,
 // and blocks past the last pair do nothing, so the host never has to wait for the count before it can queue these.
 template <int WAVES, bool WIDE, bool LAST>
-static void radix_pass_t(hipStream_t s, const RadixPass& ps, const unsigned long long* pairs_total, uint32_t cap, uint32_t* hist, uint32_t* scan_tmp) {
+static void radix_pass_t(hipStream_t s, const RadixPass& ps, const unsigned long long* pairs_total, uint32_t cap, uint32_t* hist, uint32_t* scan_tmp,
+                         const uint32_t* skip) {
     const uint32_t nblk = radix_num_workers(cap);
     hipLaunchKernelGGL(k_radix_hist, dim3(nblk), dim3(256), 0, s, ps.keys_in, pairs_total, cap, ps.shift, ps.bits, (uint32_t)(WAVES * RADIX_WAVE_CHUNK),
-                       nblk, hist);
+                       nblk, hist, skip);
     hipLaunchKernelGGL(k_radix_scan_rows, dim3(1u << ps.bits), dim3(ROWSCAN_THREADS), 0, s, hist, nblk, scan_tmp);
-    hipLaunchKernelGGL((k_radix_scatter<WAVES, WIDE, LAST>), dim3(nblk), dim3(WAVES * 64), 0, s, ps.keys_in, ps.vals_in, ps.msk_in, pairs_total, cap,
-                       ps.shift, ps.bits, nblk, hist, scan_tmp, ps.keys_out, ps.vals_out, ps.msk_out, ps.tile_start, ps.tile_end);
+    hipLaunchKernelGGL((k_radix_scatter<WAVES, WIDE, LAST, false>), dim3(nblk), dim3(WAVES * 64), 0, s, ps.keys_in, ps.vals_in, ps.msk_in, pairs_total, cap,
+                       ps.shift, ps.bits, nblk, hist, scan_tmp, ps.keys_out, ps.vals_out, ps.msk_out, ps.tile_start, ps.tile_end, SegIn{ nullptr, skip, 0, 0, 0 });
+}
+// the first pass of the direct path: one block per group of seg.G setup blocks, input from their segments
+template <int WAVES, bool LAST>
+static void radix_pass_seg(hipStream_t s, const RadixPass& ps, const SegLayout& sl, const unsigned long long* pairs_total, uint32_t cap, uint32_t* hist,
+                           uint32_t* scan_tmp) {
+    const uint32_t nblk = seg_num_groups(sl);
+    const SegIn seg{ sl.blk_sums, sl.flag, sl.nsetup, sl.S, sl.G };
+    hipLaunchKernelGGL(k_radix_hist_seg, dim3(nblk), dim3(256), 0, s, sl.keys, seg, pairs_total, cap, ps.shift, ps.bits, nblk, hist);
+    hipLaunchKernelGGL(k_radix_scan_rows, dim3(1u << ps.bits), dim3(ROWSCAN_THREADS), 0, s, hist, nblk, scan_tmp);
+    hipLaunchKernelGGL((k_radix_scatter<WAVES, false, LAST, true>), dim3(nblk), dim3(WAVES * 64), 0, s, sl.keys, sl.vals, ps.msk_in, pairs_total, cap,
+                       ps.shift, ps.bits, nblk, hist, scan_tmp, ps.keys_out, ps.vals_out, ps.msk_out, ps.tile_start, ps.tile_end, seg);
 }
 
 template <int WAVES>
 static void radix_pass_w(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
-                         uint32_t* hist, uint32_t* scan_tmp) {
-    if (wide) { if (last) radix_pass_t<WAVES, true, true>(s, ps, pairs_total, cap, hist, scan_tmp); else radix_pass_t<WAVES, true, false>(s, ps, pairs_total, cap, hist, scan_tmp); }
-    else { if (last) radix_pass_t<WAVES, false, true>(s, ps, pairs_total, cap, hist, scan_tmp); else radix_pass_t<WAVES, false, false>(s, ps, pairs_total, cap, hist, scan_tmp); }
+                         uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg, const uint32_t* skip) {
+    if (seg) { if (last) radix_pass_seg<WAVES, true>(s, ps, *seg, pairs_total, cap, hist, scan_tmp); else radix_pass_seg<WAVES, false>(s, ps, *seg, pairs_total, cap, hist, scan_tmp); }
+    else if (wide) { if (last) radix_pass_t<WAVES, true, true>(s, ps, pairs_total, cap, hist, scan_tmp, skip); else radix_pass_t<WAVES, true, false>(s, ps, pairs_total, cap, hist, scan_tmp, skip); }
+    else { if (last) radix_pass_t<WAVES, false, true>(s, ps, pairs_total, cap, hist, scan_tmp, skip); else radix_pass_t<WAVES, false, false>(s, ps, pairs_total, cap, hist, scan_tmp, skip); }
 }
 
 void launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
-                       uint32_t* hist, uint32_t* scan_tmp) {
-    if (!cap) return;
-    if (radix_waves(cap) == 8) radix_pass_w<8>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp);
-    else radix_pass_w<4>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp);
+                       uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg, const uint32_t* skip) {
+    if (!cap || (seg && (wide || !seg->nsetup))) return;
+    if (radix_waves(cap) == 8) radix_pass_w<8>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp, seg, skip);
+    else radix_pass_w<4>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp, seg, skip);
 }
 
 }  // namespace trgl

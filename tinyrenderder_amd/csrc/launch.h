@@ -5,16 +5,28 @@
 
 namespace trgl {
 
+// The direct path: every setup block writes its pairs into a segment of S slots of its own (keys / vals at
+// block * S; S a multiple of 4, at most 4096), and a block of the first radix pass sorts the segments of G <= 16 consecutive setup
+// blocks.  flag: device word k_chunk_spine sets to 1 when a block has more than S pairs or a group more than the radix chunk -
+// the kernels of the direct path then do nothing.  nsetup: setup blocks of the flush.
+struct SegLayout { uint32_t* keys; uint32_t* vals; const uint32_t* blk_sums; const uint32_t* flag; uint32_t nsetup, S, G; };
+bool seg_layout_ok(const SegLayout& seg);
+uint32_t seg_num_groups(const SegLayout& seg);      // blocks of the direct path's first radix pass
+
 uint32_t setup_num_blocks(uint32_t n);      // blocks of 256 triangles of one draw (k_setup and k_expand use the same)
 // (`draw` travels as a kernel argument; the kernel leaves it at draws_dev[draw_idx] for the kernels behind it)
 void launch_setup(hipStream_t s, const FrameParams& fp, const DrawDesc& draw, DrawDesc* draws_dev, int draw_idx, uint32_t n,
-                  TriRec* recs, TriW* recs_w, uint32_t* cnt, uint2* tilebox, DevStats* stats, uint32_t* blk_sums, uint32_t blk_base);
+                  TriRec* recs, TriW* recs_w, uint32_t* cnt, uint2* tilebox, DevStats* stats, uint32_t* blk_sums, uint32_t blk_base,
+                  const SegLayout* seg);      // seg: the flush takes the direct path - the pairs go to seg->keys / seg->vals as well
 // chunk_off[c] = pairs before setup block 16c; *total64 = all pairs of the flush
 // (host_copy: pinned host memory that receives the pair count and the two counts behind it in DevStats)
 // tile_bounds: tile_start followed by tile_end, `half_words` (a multiple of 4) each, 16-byte aligned; set to the empty bounds
 // the last radix pass starts from (tile_start ~0, tile_end 0)
 void launch_chunk_spine(hipStream_t s, const uint32_t* blk_sums, uint32_t nblk, uint32_t* chunk_off, unsigned long long* total64, unsigned long long* host_copy,
-                        uint32_t* tile_bounds, size_t half_words);
+                        uint32_t* tile_bounds, size_t half_words, uint32_t seg_S, uint32_t seg_G, uint32_t seg_chunk, uint32_t* seg_flag,
+                        uint32_t* seg_flag_host);
+// (seg_S, seg_G, seg_chunk: the segment and group sizes the flush is checked against, and the pairs a block of the first radix pass
+// holds; *seg_flag and its pinned copy *seg_flag_host receive 1 when the flush does not fit them - or seg_S is 0 - else 0)
 
 
 // expand / radix read the flush's pair count from device memory and cover `cap` (the capacity of the pair buffers)
@@ -27,6 +39,7 @@ void launch_expand(hipStream_t s, const FrameParams& fp, uint32_t first, uint32_
                    const unsigned long long* pairs_total, uint32_t cap);
 
 uint32_t radix_num_workers(uint32_t cap);      // blocks of a radix pass over pair buffers of capacity `cap` (4 or 8 waves each)
+uint32_t radix_chunk(uint32_t cap);            // pairs per block of such a pass: 4096 or 8192
 // one stable pass on `bits` bits of the tile id at `shift`.  The last pass writes vals_out and msk_out (what the raster reads, no sort
 // words) and the per-tile slices [tile_start, tile_end) of the sorted list; the others write keys_out, vals_out (and msk_out when wide).
 struct RadixPass {
@@ -35,8 +48,10 @@ struct RadixPass {
     uint32_t* tile_start; uint32_t* tile_end;
     int shift, bits;
 };
+// seg: the pass reads k_setup's segments in place of keys_in / vals_in (the first pass of the direct path; not wide)
+// skip: a later pass of the direct path - it does nothing when *skip (the flag of SegLayout) is set, as the first pass did
 void launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
-                       uint32_t* hist, uint32_t* scan_tmp);
+                       uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg = nullptr, const uint32_t* skip = nullptr);
 
 uint32_t owned_tiles(const FrameParams& fp);       // tiles of the rows this context owns (strip or interleaved bands)
 uint32_t raster_max_items(const FrameParams& fp);   // work items (workgroups of k_raster) of a flush, at most

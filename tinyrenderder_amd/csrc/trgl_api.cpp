@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -58,8 +59,11 @@ static size_t pair_capacity(size_t need) {
 
 // a flush whose first half (setup + binning) has run and whose raster half is still to be launched (trgl_flush_begin)
 // (builtin_shade: the flush has PHONG / EYE draws; user_kinds: bit i = it has draws of user kind TRGL_SHADER_USER_FIRST + i)
+// direct: the binning queued by trgl_flush_begin reads k_setup's segments (seg); settled: the pair count has been looked at and the
+// binning that leaves the lists is queued (settle_binning); fell_back: the direct path's kernels did nothing and k_expand's chain ran
 struct PendingRaster { bool active = false; FrameParams fp; int flush_kind = 0; uint32_t cap = 0; int cur = 0; uint64_t N = 0;
-                       bool builtin_shade = false; uint32_t user_kinds = 0; };
+                       bool builtin_shade = false; uint32_t user_kinds = 0;
+                       bool direct = false, settled = false, fell_back = false; SegLayout seg{}; uint32_t nblk = 0; };
 // a user shader registered on the context (trgl_register_shader_ex): its module and kernel - the shade kernel, or the raster kernel
 // of a kind that may discard (TRGL_SHADER_MAY_DISCARD)
 struct UserKind { hipModule_t mod; hipFunction_t fn; int K; bool may_discard; };
@@ -106,6 +110,15 @@ struct trgl_ctx {
     DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
     DevBuf<uint32_t> keys[2], vals[2]; DevBuf<uint16_t> bmask[2];     // (tile, triangle, block mask) pairs, ping-pong; grown together
     DevBuf<uint32_t> hist, scan_tmp;
+    // The direct path of the binning: the segments k_setup writes its pairs to, the word k_chunk_spine sets when a
+    // flush does not fit them (+ its pinned copy), and how the path is chosen: bin_mode 0 by the rule of seg_sizes(), 1 always k_expand's
+    // chain, 2 always direct with bin_S / bin_G (trgl_debug_binning).  seg_hold: a flush fell back - k_expand's chain until a flush fits.
+    DevBuf<uint32_t> seg_keys, seg_vals, seg_flag;
+    uint32_t* seg_flag_pinned = nullptr;
+    int bin_mode = 0; uint32_t bin_S = 0, bin_G = 0;
+    bool seg_hold = false;
+    uint64_t last_nblk = 0;             // setup blocks of the last flush (with last_pairs: its pairs per block)
+    int last_direct = 0, last_fell_back = 0;
     DevBuf<uint32_t> tile_start;        // tile_start[bounds_half()] followed by tile_end[bounds_half()]: set together per flush (in 16-byte words)
     DevBuf<uint4> items; DevBuf<uint32_t> n_items;
     DevBuf<unsigned long long> item_stats;
@@ -116,7 +129,8 @@ struct trgl_ctx {
     uint64_t triangles_total = 0;       // our_gl.cpp:90 counts every call, host side
     uint64_t last_tris = 0, last_pairs = 0;
     // what trgl_debug_read reports of the last complete flush (valid until the next trgl_draw / trgl_clear)
-    struct Snapshot { bool valid = false; FrameParams fp; uint64_t N = 0, P = 0, cap = 0, literal_tris = 0, large_tris = 0; int cur = 0; } snap;
+    struct Snapshot { bool valid = false; FrameParams fp; uint64_t N = 0, P = 0, cap = 0, literal_tris = 0, large_tris = 0; int cur = 0;
+                      int direct = 0, fell_back = 0; } snap;
 
     bool profiling = false, events_pending = false;
     hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
@@ -200,6 +214,9 @@ static int init_ctx(trgl_ctx* c) {
     HIPCHK(c, hipMemset(c->n_items.p, 0, 8));                       // k_fold_stats leaves it at 0 for the next flush
     if ((r = c->draws_dev.alloc(c, TRGL_MAX_DRAWS)) || (r = c->stats_dev.alloc(c, 1))) return r;
     HIPCHK(c, hipHostMalloc((void**)&c->stats_pinned, sizeof(DevStats)));
+    if ((r = c->seg_flag.alloc(c, 4))) return r;
+    HIPCHK(c, hipHostMalloc((void**)&c->seg_flag_pinned, 16));
+    *c->seg_flag_pinned = 1;
     for (int i = 0; i < 6; ++i) HIPCHK(c, hipEventCreate(&c->ev[i]));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_pairs, hipEventDisableTiming));
     // init_viewport(0,0,W,H), our_gl.cpp:59-69
@@ -237,6 +254,7 @@ int trgl_destroy(trgl_ctx* c) {
     for (auto& s : c->stage) (void)hipFree(s.base);
     for (int i = 0; i < TRGL_MAX_TEXTURES; ++i) if (c->tex_host[i].data) (void)hipFree((void*)c->tex_host[i].data);
     if (c->stats_pinned) (void)hipHostFree(c->stats_pinned);
+    if (c->seg_flag_pinned) (void)hipHostFree(c->seg_flag_pinned);
     for (int i = 0; i < 6; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_pairs) (void)hipEventDestroy(c->ev_pairs);
     if (c->ev_blur_w) (void)hipEventDestroy(c->ev_blur_w);
@@ -497,7 +515,8 @@ int trgl_flush(trgl_ctx* c) {
 
 // expand -> stable radix passes by tile id, the last of which leaves the per-tile bounds, for pair buffers of capacity `cap`.  All of
 // it reads the pair count from device memory; when the count exceeds `cap` every kernel here does nothing.
-static int queue_binning(trgl_ctx* c, const FrameParams& fp, uint32_t cap, int* cur_out) {
+// seg: the direct path - k_setup has left the pairs in its segments, no k_expand, and the first pass reads them from there.
+static int queue_binning(trgl_ctx* c, const FrameParams& fp, uint32_t cap, int* cur_out, const SegLayout* seg) {
     hipStream_t s = c->stream;
     const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
     const unsigned long long* pairs_dev = &c->stats_dev.p->pairs_total;
@@ -505,6 +524,7 @@ static int queue_binning(trgl_ctx* c, const FrameParams& fp, uint32_t cap, int* 
     uint32_t blk_base = 0;
     const bool wide = ntiles > 65536;          // else tile id and block mask share one 32-bit sort word
     for (auto& d : c->draws) {
+        if (seg) break;
         launch_expand(s, fp, d.first, d.n, c->tiles_x, c->cnt.p, c->blk_sums.p, c->chunk_off.p, blk_base, c->tilebox.p, c->keys[0].p, wide, c->vals[0].p,
                       c->bmask[0].p, pairs_dev, cap);
         blk_base += setup_num_blocks(d.n);
@@ -512,14 +532,15 @@ static int queue_binning(trgl_ctx* c, const FrameParams& fp, uint32_t cap, int* 
     int key_bits = 1; while ((size_t(1) << key_bits) < ntiles) ++key_bits;
     int passes = (key_bits + 7) / 8;
     int bits_per = (key_bits + passes - 1) / passes;
-    size_t hist_need = ((size_t)radix_num_workers(cap) << bits_per) + 16;
+    size_t hist_need = ((size_t)std::max(radix_num_workers(cap), seg ? seg_num_groups(*seg) : 0u) << bits_per) + 16;
     if ((r = c->hist.grow(c, hist_need))) return r;
     if ((r = c->scan_tmp.grow(c, 256 + 16))) return r;   // the digit totals of a pass (k_radix_scan_rows)
     int cur = 0;
     for (int ps = 0; ps < passes; ++ps) {
         const RadixPass rp{ c->keys[cur].p, c->vals[cur].p, c->bmask[cur].p, c->keys[cur ^ 1].p, c->vals[cur ^ 1].p, c->bmask[cur ^ 1].p,
                             c->tile_start.p, c->tile_end(), ps * bits_per, bits_per };
-        launch_radix_pass(s, rp, wide, ps == passes - 1, pairs_dev, cap, c->hist.p, c->scan_tmp.p);
+        launch_radix_pass(s, rp, wide, ps == passes - 1, pairs_dev, cap, c->hist.p, c->scan_tmp.p, ps == 0 ? seg : nullptr,
+                          (seg && ps > 0) ? seg->flag : nullptr);
         cur ^= 1;
     }
     *cur_out = cur;
@@ -532,6 +553,46 @@ static int grow_pairs(trgl_ctx* c, size_t need) {
     int r;
     for (int k = 0; k < 2; ++k)
         if ((r = c->keys[k].grow(c, need, ncap)) || (r = c->vals[k].grow(c, need, ncap)) || (r = c->bmask[k].grow(c, need, ncap))) return r;
+    return TRGL_OK;
+}
+
+// The direct path's sizes for a flush expected to hold `avg` pairs per setup block, `chunk` pairs per block of the first radix pass:
+// a segment of S = 1.5 avg + 128 slots, rounded up to a multiple of 64, and groups of G = 0.9 chunk / avg segments, at most 16 - the
+// expected group then fills nine tenths of the radix block.  false: no such sizes (S beyond what k_setup's LDS holds, or groups of
+// fewer than two blocks) - such a flush takes k_expand's chain from the start.
+static bool seg_sizes(double avg, uint32_t chunk, uint32_t* S, uint32_t* G) {
+    if (avg < 1.0) avg = 1.0;
+    const uint64_t s = ((uint64_t)(avg * 1.5) + 128 + 63) & ~uint64_t(63);
+    uint64_t g = (uint64_t)(0.9 * chunk / avg);
+    if (g > 16) g = 16;
+    if (s > 4096 || g < 2) return false;
+    *S = (uint32_t)s; *G = (uint32_t)g;
+    return true;
+}
+constexpr uint64_t SEG_MAX_BYTES = uint64_t(1) << 30;      // both segment buffers together; a flush that would need more takes k_expand's chain
+
+// The pending flush's counts have reached pinned memory: queue again what the kernels queued by trgl_flush_begin left undone.  They did
+// nothing when the pairs exceed the buffers (grown here, when may_grow) and, on the direct path, when the flush did not fit its
+// segments or groups (k_chunk_spine's flag): that flush falls back to k_expand and the dense passes.  Shared by trgl_flush_end and
+// trgl_debug_read (may_grow = false: a pending flush beyond the capacity stays as it is).  Also keeps the rule of the automatic
+// choice: after a fallback the context stays on k_expand's chain until a flush's counts fit the sizes it would have been given.
+static int settle_binning(trgl_ctx* c, bool may_grow) {
+    PendingRaster& rp = c->rp;
+    if (!rp.N || rp.settled) return TRGL_OK;
+    HIPCHK(c, hipEventSynchronize(c->ev_pairs));
+    const unsigned long long P64 = c->stats_pinned->pairs_total;
+    if (P64 > 0xffffe000ull) return TRGL_OK;              // (trgl_flush_end refuses the flush)
+    const bool bad = *c->seg_flag_pinned != 0, over = P64 > rp.cap, fell = rp.direct && bad;
+    if (over && !may_grow) return TRGL_OK;
+    int r;
+    if (over || fell) {
+        if (over && (r = grow_pairs(c, (size_t)P64))) return r;
+        if ((r = queue_binning(c, rp.fp, (uint32_t)c->keys[0].cap, &rp.cur, fell ? nullptr : (rp.direct ? &rp.seg : nullptr)))) return r;
+        rp.cap = (uint32_t)c->keys[0].cap;
+        if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    }
+    if (c->bin_mode == 0) { if (fell) c->seg_hold = true; else if (!rp.direct && !bad) c->seg_hold = false; }
+    rp.fell_back = fell; rp.settled = true;
     return TRGL_OK;
 }
 
@@ -596,28 +657,42 @@ int trgl_flush_begin(trgl_ctx* c) {
         for (auto& d : c->draws) nblk += setup_num_blocks(d.n);
         if ((r = c->blk_sums.grow(c, (size_t)nblk + 16))) return r;
         if ((r = c->chunk_off.grow(c, (size_t)nblk / 16 + 16))) return r;
+        cap = (uint32_t)c->keys[0].cap;
+        // The path of the binning.  Automatic: direct with the sizes seg_sizes() gives for the last flush's pairs per setup block (2 per
+        // triangle the first time), unless a flush fell back and none has fitted since (seg_hold) - then the sizes are only checked.
+        uint32_t S = 0, G = 0;
+        bool direct = false;
+        if ((size_t)c->tiles_x * c->tiles_y <= 65536) {
+            if (c->bin_mode == 2) { S = c->bin_S; G = c->bin_G; direct = true; }
+            else if (c->bin_mode == 0 && seg_sizes(c->last_nblk ? (double)c->last_pairs / (double)c->last_nblk : 512.0, radix_chunk(cap), &S, &G))
+                direct = !c->seg_hold && (uint64_t)nblk * S * 8 <= SEG_MAX_BYTES;      // (forced k_expand: S = 0, k_chunk_spine checks nothing)
+        }
+        if (direct && ((r = c->seg_keys.grow(c, (size_t)nblk * S + 4)) || (r = c->seg_vals.grow(c, (size_t)nblk * S + 4)))) return r;
+        const SegLayout seg{ c->seg_keys.p, c->seg_vals.p, c->blk_sums.p, c->seg_flag.p, nblk, S, G };
+        c->rp.direct = direct; c->rp.seg = seg; c->rp.nblk = nblk;
         {
             uint32_t blk_base = 0;
             for (size_t i = 0; i < c->draws.size(); ++i) {
                 launch_setup(s, fp, c->draws[i], c->draws_dev.p, (int)i, c->draws[i].n, c->recs.p, c->recs_w.p, c->cnt.p, c->tilebox.p, c->stats_dev.p,
-                             c->blk_sums.p, blk_base);
+                             c->blk_sums.p, blk_base, direct ? &seg : nullptr);
                 blk_base += setup_num_blocks(c->draws[i].n);
             }
         }
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], s));
         // (+ literal_tris, large_tris into pinned memory; the kernel also sets tile_start and tile_end to empty bounds)
         launch_chunk_spine(s, c->blk_sums.p, nblk, c->chunk_off.p, &c->stats_dev.p->pairs_total, &c->stats_pinned->pairs_total,
-                           c->tile_start.p, c->bounds_half());
+                           c->tile_start.p, c->bounds_half(), S, G, radix_chunk(cap), c->seg_flag.p, c->seg_flag_pinned);
         HIPCHK(c, hipEventRecord(c->ev_pairs, s));
-        cap = (uint32_t)c->keys[0].cap;
-        if ((r = queue_binning(c, fp, cap, &cur))) return r;
+        if ((r = queue_binning(c, fp, cap, &cur, direct ? &seg : nullptr))) return r;
     } else {
+        c->rp.direct = false; c->rp.nblk = 0;
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], s));
         HIPCHK(c, hipMemsetAsync(c->tile_start.p, 0, c->bounds_half() * 8, s));
     }
     if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], s));
     c->rp.active = true; c->rp.fp = fp; c->rp.flush_kind = flush_kind; c->rp.cap = cap; c->rp.cur = cur; c->rp.N = N;
     c->rp.builtin_shade = builtin_shade; c->rp.user_kinds = user_kinds;
+    c->rp.settled = false; c->rp.fell_back = false;
     return TRGL_OK;
 }
 
@@ -642,11 +717,8 @@ int trgl_flush_end(trgl_ctx* c) {
             return fail(c, TRGL_E_UNSUPPORTED, "flush: more than 2^32 triangle-tile pairs; submit in smaller batches");
         }
         P = (uint32_t)P64;
-        if (P > c->rp.cap) {                               // the buffers were too small: the queued binning did nothing
-            if ((r = grow_pairs(c, P))) return r;
-            if ((r = queue_binning(c, fp, (uint32_t)c->keys[0].cap, &cur))) return r;
-            if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], s));
-        }
+        if ((r = settle_binning(c, true))) return r;       // (the buffers were too small, or the direct path did not fit: binned again)
+        cur = c->rp.cur;
     }
     // with no pairs every tile list is empty; the kernel must not (and does not) dereference these, but give it
     // valid addresses anyway
@@ -674,6 +746,9 @@ int trgl_flush_end(trgl_ctx* c) {
 
     c->triangles_total += N;
     c->last_tris = N; c->last_pairs = P;
+    if (N) c->last_nblk = c->rp.nblk;
+    c->last_direct = (N && c->rp.direct) ? 1 : 0; c->last_fell_back = (N && c->rp.fell_back) ? 1 : 0;
+    c->snap.direct = c->last_direct; c->snap.fell_back = c->last_fell_back;
     c->snap.valid = true; c->snap.fp = fp; c->snap.N = N; c->snap.P = P; c->snap.cap = c->keys[0].cap; c->snap.cur = cur;
     c->snap.literal_tris = N ? c->stats_pinned->literal_tris : 0; c->snap.large_tris = N ? c->stats_pinned->large_tris : 0;
     c->clear_pending = false;
@@ -1371,13 +1446,15 @@ extern "C" int trgl_debug_counters(trgl_ctx* c, unsigned long long out[16]) {
 // Diagnostic read-back of one flush's intermediate buffers (tests/test_stage_outputs_gpu.py; not part of include/trgl.h).
 // Valid between trgl_flush_begin and trgl_flush_end - the one entry point that does NOT complete a begun flush - and after a
 // complete flush until the next trgl_draw / trgl_clear; TRGL_E_STATE otherwise.  Synchronises the stream and copies device ->
-// host; launches nothing.  *needed receives the size in bytes of `what`; with dst == nullptr that is all the call does.
+// host; launches nothing unless the pending flush fell back from the direct path: then k_expand's chain is queued first, as
+// trgl_flush_end would (settle_binning).  *needed receives the size in bytes of `what`; with dst == nullptr that is all the call does.
 //   what 0 RECS       TriRec[N + 1]   (the record behind the last is written by the raster half)
 //        1 CNT        uint32[N]       2 TILEBOX uint2[N]
 //        3 VALS       uint32[P]       4 BMASK   uint16[P]      the ping-pong side k_raster is (or was) handed
 //        5 TILE_START uint32[tiles]   6 TILE_END uint32[tiles]
 //        7 INFO       int64[24]: N, P, pair capacity, wide, literal_tris, large_tris, zq_cull, pending, W, H, tiles_x, tiles_y,
-//                     strip_y0, strip_y1, strip_ty0, strip_ty1, il_tiles, il_world, il_rank, side, 0...
+//                     strip_y0, strip_y1, strip_ty0, strip_ty1, il_tiles, il_world, il_rank, side, direct (trgl_flush_begin queued the
+//                     direct path), fell_back (its kernels did nothing: the flush did not fit, k_expand's chain bins it), 0...
 // While a flush is pending whose pairs exceed the capacity (trgl_flush_end will grow the buffers and bin again), the pair lists
 // and tile bounds do not exist yet: TRGL_E_STATE for what 3-6; INFO still reports P and the capacity.
 extern "C" int trgl_debug_read(trgl_ctx* c, int what, void* dst, size_t bytes, size_t* needed) {
@@ -1385,21 +1462,25 @@ extern "C" int trgl_debug_read(trgl_ctx* c, int what, void* dst, size_t bytes, s
     const bool pending = c->rp.active;
     if (!pending && !c->snap.valid) return fail(c, TRGL_E_STATE, "trgl_debug_read: no flush to read (between trgl_flush_begin and trgl_flush_end, or after a flush until the next draw or clear)");
     if (what < 0 || what > 7) return fail(c, TRGL_E_INVALID, "trgl_debug_read: unknown buffer");
-    FrameParams fp; uint64_t N, P, cap, lit, lrg; int cur;
+    FrameParams fp; uint64_t N, P, cap, lit, lrg; int cur, direct = 0, fell = 0;
     if (pending) {
         fp = c->rp.fp; N = c->rp.N; cap = c->rp.cap; cur = c->rp.cur; P = lit = lrg = 0;
         if (N) {
+            if (int r = settle_binning(c, false)) return r;      // (a flush that fell back from the direct path is binned by k_expand's chain first)
+            cap = c->rp.cap; cur = c->rp.cur;
             HIPCHK(c, hipEventSynchronize(c->ev_pairs));
             P = c->stats_pinned->pairs_total; lit = c->stats_pinned->literal_tris; lrg = c->stats_pinned->large_tris;
         }
         fp.zq_cull = (N != 0 && lrg != 0) ? 1 : 0;         // what trgl_flush_end will decide
+        direct = (N && c->rp.direct) ? 1 : 0; fell = (direct && *c->seg_flag_pinned != 0 && P <= 0xffffe000ull) ? 1 : 0;
     } else {
+        direct = c->snap.direct; fell = c->snap.fell_back;
         fp = c->snap.fp; N = c->snap.N; P = c->snap.P; cap = c->snap.cap; cur = c->snap.cur; lit = c->snap.literal_tris; lrg = c->snap.large_tris;
     }
     const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
     if (what >= 3 && what <= 6 && P > cap) return fail(c, TRGL_E_STATE, "trgl_debug_read: the pending flush has more pairs than the pair buffers hold; its lists exist after trgl_flush_end");
     int64_t info[24] = { (int64_t)N, (int64_t)P, (int64_t)cap, ntiles > 65536 ? 1 : 0, (int64_t)lit, (int64_t)lrg, fp.zq_cull, pending ? 1 : 0,
-                         fp.W, fp.H, fp.tiles_x, fp.tiles_y, fp.strip_y0, fp.strip_y1, fp.strip_ty0, fp.strip_ty1, fp.il_tiles, fp.il_world, fp.il_rank, cur };
+                         fp.W, fp.H, fp.tiles_x, fp.tiles_y, fp.strip_y0, fp.strip_y1, fp.strip_ty0, fp.strip_ty1, fp.il_tiles, fp.il_world, fp.il_rank, cur, direct, fell };
     const void* src = nullptr; size_t need = 0;
     switch (what) {
     case 0: src = c->recs.p; need = N ? (size_t)(N + 1) * sizeof(TriRec) : 0; break;
@@ -1417,6 +1498,21 @@ extern "C" int trgl_debug_read(trgl_ctx* c, int what, void* dst, size_t bytes, s
     if (what == 7) { std::memcpy(dst, info, sizeof(info)); return TRGL_OK; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (need) HIPCHK(c, hipMemcpy(dst, src, need, hipMemcpyDeviceToHost));
+    return TRGL_OK;
+}
+
+// Test hook beside trgl_debug_read (not part of include/trgl.h): how the NEXT flushes bin.  mode 0: the automatic choice; 1: always
+// k_expand's chain; 2: always the direct path, with segments of S slots (a multiple of 4 in 4..4096) and groups of G (1..16) setup
+// blocks - a flush that does not fit them falls back; -1: change nothing.  *last_direct / *last_fell_back (may be null): what the last
+// complete flush did.
+extern "C" int trgl_debug_binning(trgl_ctx* c, int mode, uint32_t S, uint32_t G, int* last_direct, int* last_fell_back) {
+    CHKCTX(c);
+    if (mode < -1 || mode > 2) return fail(c, TRGL_E_INVALID, "trgl_debug_binning: mode is -1 (report only), 0 (automatic), 1 (k_expand) or 2 (direct)");
+    if (mode == 2 && !seg_layout_ok(SegLayout{ nullptr, nullptr, nullptr, nullptr, 0, S, G }))
+        return fail(c, TRGL_E_INVALID, "trgl_debug_binning: S is a multiple of 4 in 4..4096, G in 1..16");
+    if (mode >= 0) { c->bin_mode = mode; c->bin_S = mode == 2 ? S : 0; c->bin_G = mode == 2 ? G : 0; c->seg_hold = false; }
+    if (last_direct) *last_direct = c->last_direct;
+    if (last_fell_back) *last_fell_back = c->last_fell_back;
     return TRGL_OK;
 }
 
