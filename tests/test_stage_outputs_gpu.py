@@ -128,7 +128,7 @@ def check_setup(s, m, what=""):
     assert info["large_tris"] == int(m.large.sum()), (what, info["large_tris"], int(m.large.sum()))
     assert info["zq_cull"] == int(m.large.any()) and info["wide"] == int(m.tiles_x * m.tiles_y > 65536)
     assert (info["W"], info["H"], info["tiles_x"], info["tiles_y"]) == (m.W, m.H, m.tiles_x, m.tiles_y)
-    if N and not info["pending"]:
+    if N and not info["pending"] and m.owned_rows.any():     # (k_make_items writes it; a context without tile rows launches no raster)
         p = recs[N]
         assert p["c0"] == np.inf and p["uz"] == 1.0 and p["bx0"] > p["bx1"] and p["by0"] > p["by1"], f"{what}: partner record {p}"
 
@@ -378,7 +378,9 @@ def test_pair_lists_with_wide_tile_keys():
 
 def test_pair_lists_in_eight_wave_radix_blocks():
     """pair buffers of at least 4 M entries sort in radix blocks of 8 waves: a first flush of 2.1 M triangles (all rejected: w = 0)
-    sizes the buffers at 2 pairs per triangle, the small flush behind it is read back"""
+    sizes the buffers at 2 pairs per triangle, the small flush behind it is read back.  That flush is NOT sorted from the segments:
+    after a flush without pairs the automatic choice offers it segments of 192 slots, its blocks hold more, and it falls back - the
+    8-wave kernels of the direct path do nothing here (tests/test_direct_pairs_big_gpu.py runs them)."""
     W, H = 256, 192
     clip, col = scenes.random_triangles(9000, W, H, seed=761, rmin=2, rmax=50)
     with Context(W, H, 3) as ctx:
@@ -387,6 +389,8 @@ def test_pair_lists_in_eight_wave_radix_blocks():
         assert ctx.debug_snapshot()["info"]["P"] == 0
         s, m = flush_and_check(_flat(W, H, clip, col), ctx=ctx, what="8-wave blocks")
     assert s["info"]["capacity"] >= RADIX_BIG_CAP and s["info"]["P"] > 8192, s["info"]
+    assert (s["info"]["seg_S"], s["info"]["seg_G"], s["info"]["direct"], s["info"]["fell_back"]) == (192, 16, 1, 1), s["info"]
+    assert np.add.reduceat(s["cnt"], np.arange(0, len(s["cnt"]), SETUP_BLOCK)).max() > 192
 
 
 def test_pair_lists_after_the_buffers_grew():

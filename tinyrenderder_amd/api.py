@@ -97,7 +97,8 @@ TRI_REC = np.dtype([(n, "<f8") for n in ("ax", "ay", "s0x", "s0y", "s1x", "s1y",
 assert TRI_REC.itemsize == 128, "TRI_REC must mirror sizeof(TriRec) == 128"
 DBG_RECS, DBG_CNT, DBG_TILEBOX, DBG_VALS, DBG_BMASK, DBG_TILE_START, DBG_TILE_END, DBG_INFO = range(8)
 DBG_INFO_FIELDS = ("N", "P", "capacity", "wide", "literal_tris", "large_tris", "zq_cull", "pending", "W", "H", "tiles_x", "tiles_y",
-                   "strip_y0", "strip_y1", "strip_ty0", "strip_ty1", "il_tiles", "il_world", "il_rank", "side", "direct", "fell_back")
+                   "strip_y0", "strip_y1", "strip_ty0", "strip_ty1", "il_tiles", "il_world", "il_rank", "side", "direct", "fell_back",
+                   "seg_S", "seg_G")
 BIN_AUTO, BIN_EXPAND, BIN_DIRECT = 0, 1, 2      # trgl_debug_binning: how the next flushes bin
 DL_LITERAL = 0x80000000       # TRGL_DL_LITERAL
 

@@ -117,7 +117,7 @@ struct trgl_ctx {
     uint32_t* seg_flag_pinned = nullptr;
     int bin_mode = 0; uint32_t bin_S = 0, bin_G = 0;
     bool seg_hold = false;
-    uint64_t last_nblk = 0;             // setup blocks of the last flush (with last_pairs: its pairs per block)
+    uint64_t rule_pairs = 0, rule_nblk = 0;     // pairs and setup blocks of the last flush that had triangles: a, the input of seg_sizes()
     int last_direct = 0, last_fell_back = 0;
     DevBuf<uint32_t> tile_start;        // tile_start[bounds_half()] followed by tile_end[bounds_half()]: set together per flush (in 16-byte words)
     DevBuf<uint4> items; DevBuf<uint32_t> n_items;
@@ -130,7 +130,7 @@ struct trgl_ctx {
     uint64_t last_tris = 0, last_pairs = 0;
     // what trgl_debug_read reports of the last complete flush (valid until the next trgl_draw / trgl_clear)
     struct Snapshot { bool valid = false; FrameParams fp; uint64_t N = 0, P = 0, cap = 0, literal_tris = 0, large_tris = 0; int cur = 0;
-                      int direct = 0, fell_back = 0; } snap;
+                      int direct = 0, fell_back = 0; uint32_t seg_S = 0, seg_G = 0; } snap;
 
     bool profiling = false, events_pending = false;
     hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
@@ -658,13 +658,14 @@ int trgl_flush_begin(trgl_ctx* c) {
         if ((r = c->blk_sums.grow(c, (size_t)nblk + 16))) return r;
         if ((r = c->chunk_off.grow(c, (size_t)nblk / 16 + 16))) return r;
         cap = (uint32_t)c->keys[0].cap;
-        // The path of the binning.  Automatic: direct with the sizes seg_sizes() gives for the last flush's pairs per setup block (2 per
-        // triangle the first time), unless a flush fell back and none has fitted since (seg_hold) - then the sizes are only checked.
+        // The path of the binning.  Automatic: direct with the sizes seg_sizes() gives for the pairs per setup block of the last flush
+        // that had triangles (2 per triangle the first time), unless a flush fell back and none has fitted since (seg_hold) - then the
+        // sizes are only checked.
         uint32_t S = 0, G = 0;
         bool direct = false;
         if ((size_t)c->tiles_x * c->tiles_y <= 65536) {
             if (c->bin_mode == 2) { S = c->bin_S; G = c->bin_G; direct = true; }
-            else if (c->bin_mode == 0 && seg_sizes(c->last_nblk ? (double)c->last_pairs / (double)c->last_nblk : 512.0, radix_chunk(cap), &S, &G))
+            else if (c->bin_mode == 0 && seg_sizes(c->rule_nblk ? (double)c->rule_pairs / (double)c->rule_nblk : 512.0, radix_chunk(cap), &S, &G))
                 direct = !c->seg_hold && (uint64_t)nblk * S * 8 <= SEG_MAX_BYTES;      // (forced k_expand: S = 0, k_chunk_spine checks nothing)
         }
         if (direct && ((r = c->seg_keys.grow(c, (size_t)nblk * S + 4)) || (r = c->seg_vals.grow(c, (size_t)nblk * S + 4)))) return r;
@@ -685,7 +686,7 @@ int trgl_flush_begin(trgl_ctx* c) {
         HIPCHK(c, hipEventRecord(c->ev_pairs, s));
         if ((r = queue_binning(c, fp, cap, &cur, direct ? &seg : nullptr))) return r;
     } else {
-        c->rp.direct = false; c->rp.nblk = 0;
+        c->rp.direct = false; c->rp.nblk = 0; c->rp.seg = SegLayout{};
         if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], s));
         HIPCHK(c, hipMemsetAsync(c->tile_start.p, 0, c->bounds_half() * 8, s));
     }
@@ -746,9 +747,10 @@ int trgl_flush_end(trgl_ctx* c) {
 
     c->triangles_total += N;
     c->last_tris = N; c->last_pairs = P;
-    if (N) c->last_nblk = c->rp.nblk;
+    if (N) { c->rule_pairs = P; c->rule_nblk = c->rp.nblk; }       // (a flush that only clears has no pairs per block: the rule keeps its input)
     c->last_direct = (N && c->rp.direct) ? 1 : 0; c->last_fell_back = (N && c->rp.fell_back) ? 1 : 0;
     c->snap.direct = c->last_direct; c->snap.fell_back = c->last_fell_back;
+    c->snap.seg_S = N ? c->rp.seg.S : 0; c->snap.seg_G = N ? c->rp.seg.G : 0;
     c->snap.valid = true; c->snap.fp = fp; c->snap.N = N; c->snap.P = P; c->snap.cap = c->keys[0].cap; c->snap.cur = cur;
     c->snap.literal_tris = N ? c->stats_pinned->literal_tris : 0; c->snap.large_tris = N ? c->stats_pinned->large_tris : 0;
     c->clear_pending = false;
@@ -1454,7 +1456,9 @@ extern "C" int trgl_debug_counters(trgl_ctx* c, unsigned long long out[16]) {
 //        5 TILE_START uint32[tiles]   6 TILE_END uint32[tiles]
 //        7 INFO       int64[24]: N, P, pair capacity, wide, literal_tris, large_tris, zq_cull, pending, W, H, tiles_x, tiles_y,
 //                     strip_y0, strip_y1, strip_ty0, strip_ty1, il_tiles, il_world, il_rank, side, direct (trgl_flush_begin queued the
-//                     direct path), fell_back (its kernels did nothing: the flush did not fit, k_expand's chain bins it), 0...
+//                     direct path), fell_back (its kernels did nothing: the flush did not fit, k_expand's chain bins it), seg_S, seg_G (the
+//                     segment and group sizes k_chunk_spine was given: the direct path's, or on k_expand's chain those it only checks;
+//                     0, 0 without sizes: forced k_expand, WIDE, the rule gives none), 0...
 // While a flush is pending whose pairs exceed the capacity (trgl_flush_end will grow the buffers and bin again), the pair lists
 // and tile bounds do not exist yet: TRGL_E_STATE for what 3-6; INFO still reports P and the capacity.
 extern "C" int trgl_debug_read(trgl_ctx* c, int what, void* dst, size_t bytes, size_t* needed) {
@@ -1462,7 +1466,7 @@ extern "C" int trgl_debug_read(trgl_ctx* c, int what, void* dst, size_t bytes, s
     const bool pending = c->rp.active;
     if (!pending && !c->snap.valid) return fail(c, TRGL_E_STATE, "trgl_debug_read: no flush to read (between trgl_flush_begin and trgl_flush_end, or after a flush until the next draw or clear)");
     if (what < 0 || what > 7) return fail(c, TRGL_E_INVALID, "trgl_debug_read: unknown buffer");
-    FrameParams fp; uint64_t N, P, cap, lit, lrg; int cur, direct = 0, fell = 0;
+    FrameParams fp; uint64_t N, P, cap, lit, lrg; int cur, direct = 0, fell = 0; uint32_t seg_S = 0, seg_G = 0;
     if (pending) {
         fp = c->rp.fp; N = c->rp.N; cap = c->rp.cap; cur = c->rp.cur; P = lit = lrg = 0;
         if (N) {
@@ -1473,14 +1477,15 @@ extern "C" int trgl_debug_read(trgl_ctx* c, int what, void* dst, size_t bytes, s
         }
         fp.zq_cull = (N != 0 && lrg != 0) ? 1 : 0;         // what trgl_flush_end will decide
         direct = (N && c->rp.direct) ? 1 : 0; fell = (direct && *c->seg_flag_pinned != 0 && P <= 0xffffe000ull) ? 1 : 0;
+        if (N) { seg_S = c->rp.seg.S; seg_G = c->rp.seg.G; }
     } else {
-        direct = c->snap.direct; fell = c->snap.fell_back;
+        direct = c->snap.direct; fell = c->snap.fell_back; seg_S = c->snap.seg_S; seg_G = c->snap.seg_G;
         fp = c->snap.fp; N = c->snap.N; P = c->snap.P; cap = c->snap.cap; cur = c->snap.cur; lit = c->snap.literal_tris; lrg = c->snap.large_tris;
     }
     const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
     if (what >= 3 && what <= 6 && P > cap) return fail(c, TRGL_E_STATE, "trgl_debug_read: the pending flush has more pairs than the pair buffers hold; its lists exist after trgl_flush_end");
     int64_t info[24] = { (int64_t)N, (int64_t)P, (int64_t)cap, ntiles > 65536 ? 1 : 0, (int64_t)lit, (int64_t)lrg, fp.zq_cull, pending ? 1 : 0,
-                         fp.W, fp.H, fp.tiles_x, fp.tiles_y, fp.strip_y0, fp.strip_y1, fp.strip_ty0, fp.strip_ty1, fp.il_tiles, fp.il_world, fp.il_rank, cur, direct, fell };
+                         fp.W, fp.H, fp.tiles_x, fp.tiles_y, fp.strip_y0, fp.strip_y1, fp.strip_ty0, fp.strip_ty1, fp.il_tiles, fp.il_world, fp.il_rank, cur, direct, fell, seg_S, seg_G };
     const void* src = nullptr; size_t need = 0;
     switch (what) {
     case 0: src = c->recs.p; need = N ? (size_t)(N + 1) * sizeof(TriRec) : 0; break;
