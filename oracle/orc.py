@@ -124,6 +124,24 @@ class Oracle:
         cb = None if clear_bgra is None else np.asarray(clear_bgra, np.uint8)
         self.L.orc_clear(C.byref(self.t), None if cb is None else cb.ctypes.data, float(z_clear))
 
+    # ---- the reference's globals, changed between rasterize() calls (each takes effect at once: the reference is immediate) ----
+    def set_viewport(self, m):
+        """The global Viewport (our_gl.cpp:14) as a row-major 4x4."""
+        self.t.viewport[:] = np.asarray(m, np.float64).reshape(16).tolist()
+
+    def clear(self, clear_bgra=None, z_clear=np.inf):
+        """A fresh TGAImage(w, h, bpp, clear) and init_zbuffer (tgaimage.cpp:8-17, our_gl.cpp:72-74): every row, whatever the strip."""
+        cb = None if clear_bgra is None else np.asarray(clear_bgra, np.uint8)
+        self.L.orc_clear(C.byref(self.t), None if cb is None else cb.ctypes.data, float(z_clear))
+
+    def reset_stats(self):
+        """The counters back to their initial values (our_gl.cpp:18-22)."""
+        self.L.orc_stats_init(C.byref(self.t.stats))
+
+    def set_strip(self, y0, y1):
+        """Later draws write rows [y0, y1) only (they still count and bound every triangle)."""
+        self.t.clip_y0, self.t.clip_y1 = int(y0), int(y1)
+
     def upload_texture(self, slot, texels):
         t = np.ascontiguousarray(texels, np.uint8)
         if t.ndim == 2:

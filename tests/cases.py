@@ -472,6 +472,19 @@ def vecops_inputs(n=2000):
     return data, packed
 
 
+def loaded_buffers(W, H, bpp):
+    """A framebuffer and a z-buffer for a frame that starts from caller-written buffers (write_framebuffer / write_zbuffer): a colour
+    pattern, and depth bands with NaN, -inf and +inf columns and a row band nothing passes."""
+    y, x = np.mgrid[0:H, 0:W]
+    fb = np.stack([(x * 7 + y * 13 + c * 31 + 5) & 0xFF for c in range(bpp)], -1).astype(np.uint8)
+    z = np.where((y // 8) % 2 == 0, 0.6, -0.2) + 0.001 * x
+    z[:, 5:9] = np.nan
+    z[:, 20:23] = -np.inf
+    z[:, 30:34] = np.inf
+    z[40:44, :] = 0.95
+    return fb, z
+
+
 # ---- render a case and check it: the one harness of the GPU tests ---------------------------------------------------
 def run_oracle(case, strip=None, start=None):
     """Render a case with the CPU oracle; returns (fb, z, stats tuple).  strip = (y0, y1): only those rows are drawn.

@@ -406,15 +406,7 @@ def test_perspective_fallback_against_oracle(kind):
 # =====================================================================================================================
 # D. frames that start from caller-written buffers
 # =====================================================================================================================
-def _loaded_buffers(W, H, bpp):
-    y, x = np.mgrid[0:H, 0:W]
-    fb = np.stack([(x * 7 + y * 13 + c * 31 + 5) & 0xFF for c in range(bpp)], -1).astype(np.uint8)
-    z = np.where((y // 8) % 2 == 0, 0.6, -0.2) + 0.001 * x
-    z[:, 5:9] = np.nan
-    z[:, 20:23] = -np.inf
-    z[:, 30:34] = np.inf
-    z[40:44, :] = 0.95
-    return fb, z
+_loaded_buffers = cases.loaded_buffers
 
 
 @pytest.mark.gpu
