@@ -512,6 +512,79 @@ int trgl_image_scale(trgl_ctx* ctx, const uint8_t* src, int w, int h, int bpp,
  * would read rows that another rank owns - gather the frame and blur it on one context.  TRGL_E_UNSUPPORTED as for trgl_image_blur. */
 int trgl_framebuffer_blur(trgl_ctx* ctx, int radius);
 
+/* ---- shadow mapping as a post-pass: a mask from the light's depths, multiplied into an image -------------- */
+
+/* New work: the reference has no shadows, so nothing here "replaces" a function of it.  The arithmetic is borrowed from the lines named
+ * below.  A light's view is drawn like any other, trgl_zbuffer_snapshot keeps its depths (the light's depth map), the camera's view is
+ * drawn, and these calls darken the camera pixels the light does not see - without a frame-sized array crossing PCIe:
+ *     draw from the light; trgl_zbuffer_snapshot(ctx, 1); trgl_clear; draw from the camera;
+ *     trgl_shadow_mask(ctx, &params, 1, d_mask, TRGL_MEM_DEVICE);
+ *     trgl_image_blur(ctx, d_mask, W, H, 1, r, TRGL_MEM_DEVICE);        (optional: a softer edge)
+ *     trgl_framebuffer_modulate(ctx, d_mask, TRGL_MEM_DEVICE);
+ *
+ * The mask is w * h bytes, one per pixel i = x + y * w.  All arithmetic is fp64 without contraction, in this order:
+ *  1. z = depth[i]; not finite (background): the byte is 255.
+ *  2. p = (x + 0.5, y + 0.5, z, 1.0), the pixel centre of our_gl.cpp:149; q[r] = the sum from 0.0 of M[r][c] * p[c], c = 0..3 in that
+ *     order (geometry.h:122-127,187-192) with M = screen_to_light, row-major.
+ *  3. !(q[3] > 1e-12) (behind the light, our_gl.cpp:94; a NaN lands here): 255.
+ *  4. s[k] = q[k] / q[3], k = 0..2, a true division (geometry.h:117); any s[k] not finite: 255.
+ *  5. s[2] < -1.0 || s[2] > 1.0 (our_gl.cpp:103): 255.
+ *  6. !(s[0] >= 0.0 && s[0] < (double)map_w && s[1] >= 0.0 && s[1] < (double)map_h), tested in double before any conversion: 255.
+ *  7. ix = (int)s[0], iy = (int)s[1], limit = s[2] - bias, r = pcf_radius, total = (2r+1)^2; occluded = the number of taps
+ *     (ix + dx, iy + dy), dx, dy in [-r, r], that lie inside the map and hold map[tx + ty * map_w] < limit.  A tap outside the map never
+ *     occludes; neither does one that holds +inf or NaN.
+ *  8. factor = 1.0 - ((double)occluded / (double)total) * darkness, the shape of main.cpp:360-361; the byte is
+ *     (unsigned char)(255.0 * factor) (main.cpp:760).
+ * Modulate: per pixel f = (double)mask[i] / 255.0 (main.cpp:775) and, for each channel c < min(bpp, 3),
+ * px[c] = (unsigned char)std::min(255.0, (double)px[c] * f) (main.cpp:777-781).  Alpha is untouched; a mask byte of 255 is f = 1.0 exactly
+ * and leaves the pixel's bits alone.
+ *
+ * Memory kinds as for trgl_image_blur.  TRGL_MEM_HOST: plain C++, ctx may be NULL, no GPU is touched.  TRGL_MEM_DEVICE: needs a context;
+ * the work is queued on the context's stream in order with everything else, nothing is flushed and the call does not wait.  Depth arrays
+ * are 8-byte aligned (16-byte aligned ones are read in 16-byte loads); byte images need no alignment at all.
+ * Errors of every call below.  TRGL_E_INVALID: pcf_radius outside 0..TRGL_MAX_PCF_RADIUS, reserved != 0, darkness outside [0, 1] or NaN, a
+ * bias that is not finite, a null pointer with a non-empty image, a negative dimension, map_w or map_h <= 0 with a non-empty depth image,
+ * bpp not in {1, 3, 4}, a bad mem_kind, TRGL_MEM_DEVICE without a context.  TRGL_E_UNSUPPORTED: a pixel count (w * h, map_w * map_h) or
+ * w * h * bpp above INT_MAX.  An empty image (w * h == 0) with valid parameters: TRGL_OK, nothing is read or written. */
+#define TRGL_MAX_PCF_RADIUS 4
+typedef struct trgl_shadow_params {
+    double  screen_to_light[16];  /* row-major M: camera pixel (x+0.5, y+0.5, z_ndc, 1) -> light (sx, sy, z_ndc, w) before the divide */
+    double  bias;                 /* finite */
+    double  darkness;             /* 0..1: how much a fully shadowed pixel loses */
+    int32_t pcf_radius;           /* 0..TRGL_MAX_PCF_RADIUS: (2r+1)^2 taps */
+    int32_t reserved;             /* 0 */
+} trgl_shadow_params;
+
+/* out = (Lvp * Lproj * Lmv) * inverse(Cvp * Cproj * Cmv), row-major: the matrix that carries a camera pixel with its depth to the light's
+ * screen.  The products are geometry.h:196's (each entry a sum from 0 over k, left to right, as Viewport * Perspective * ModelView
+ * evaluates); the viewports are the full 4x4 of init_viewport with the identity z row (our_gl.cpp:67-68, trgl_init_viewport).  The
+ * inverse is Gauss-Jordan elimination with partial pivoting in fp64 - the reference has no inverse, so this one function is not pinned
+ * bit for bit.  TRGL_E_INVALID: a null pointer, or a pivot that is 0 or not finite (a singular camera matrix).  Host only, needs no context. */
+int trgl_shadow_matrix(const double light_mv[16], const double light_proj[16], const double light_vp[16],
+                       const double cam_mv[16], const double cam_proj[16], const double cam_vp[16], double out[16]);
+
+/* The mask of a w x h depth image against a map_w x map_h depth map (steps 1-8 above); one mem_kind covers depth, map and mask. */
+int trgl_shadow_mask_image(trgl_ctx* ctx, const trgl_shadow_params* params, const double* depth, int w, int h,
+                           const double* map, int map_w, int map_h, uint8_t* mask, int mem_kind);
+
+/* The resident form: depth is the context's z-buffer, map the depths of snapshot_slot (trgl_zbuffer_snapshot; the context's own W x H).
+ * Completes a begun flush and flushes what is queued (a pending trgl_clear included), as trgl_framebuffer_blur does, then queues the
+ * kernel; waits only when mask is host memory (mask_mem_kind; the W * H bytes then cross PCIe once).  The frame, the depths and the
+ * counters stay untouched.  TRGL_E_INVALID also for a slot outside 0..TRGL_MAX_Z_SNAPSHOTS-1; TRGL_E_STATE for a slot that holds nothing,
+ * and on a context with a strip or interleaved bands set: its snapshot holds only that rank's rows - gather with with_z and mask on one
+ * context. */
+int trgl_shadow_mask(trgl_ctx* ctx, const trgl_shadow_params* params, int snapshot_slot, uint8_t* mask, int mask_mem_kind);
+
+/* Multiplies an image of w * h * bpp bytes by a mask of w * h bytes, in place (Modulate above); one mem_kind covers both. */
+int trgl_image_modulate(trgl_ctx* ctx, uint8_t* pixels, int w, int h, int bpp, const uint8_t* mask, int mem_kind);
+
+/* The same on the resident frame: flushes as trgl_shadow_mask does, multiplies the context's framebuffer by the W * H mask in place and
+ * does not wait; the z-buffer and the counters stay untouched.  A host mask is first copied to the device by a copy queued on the
+ * context's stream: from pageable memory its bytes are taken before the call returns, but a mask in pinned (hipHostMalloc / registered)
+ * memory is read when the stream reaches the copy, and must stay unchanged until then (trgl_sync, or any call that waits).  On a strip / band context
+ * every row is multiplied, the rows of other ranks as stale afterwards as before. */
+int trgl_framebuffer_modulate(trgl_ctx* ctx, const uint8_t* mask, int mask_mem_kind);
+
 /* ---- TGA writer and reader (host only) ------------------------------------- */
 
 /* Replaces: TGAImage::write_tga_file(name, vflip, rle) (tgaimage.cpp:161-242): produces exactly the bytes the

@@ -25,6 +25,7 @@ NUM_PHASES = 5        # TRGL_NUM_PHASES
 MAX_TEXTURES = 16
 MAX_Z_SNAPSHOTS = 4           # TRGL_MAX_Z_SNAPSHOTS
 MAX_BLUR_RADIUS = 46340       # TRGL_MAX_BLUR_RADIUS
+MAX_PCF_RADIUS = 4            # TRGL_MAX_PCF_RADIUS
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
 
 # every symbol include/trgl.h declares (tests check the library exports all of them)
@@ -43,6 +44,7 @@ SYMBOLS = [
     "trgl_zbuffer_snapshot", "trgl_zbuffer_restore", "trgl_zbuffer_snapshot_free",
     "trgl_mesh_normals", "trgl_mesh_tangents",
     "trgl_gaussian_kernel", "trgl_image_blur", "trgl_image_scale", "trgl_framebuffer_blur",
+    "trgl_shadow_matrix", "trgl_shadow_mask_image", "trgl_shadow_mask", "trgl_image_modulate", "trgl_framebuffer_modulate",
 ]
 
 
@@ -71,6 +73,20 @@ class SsaoParams(C.Structure):
     """trgl_ssao_params"""
     _fields_ = [("num_directions", C.c_int32), ("steps_per_direction", C.c_int32), ("sample_radius", C.c_double),
                 ("occlusion_threshold", C.c_double), ("intensity", C.c_double)]
+
+
+class ShadowParams(C.Structure):
+    """trgl_shadow_params"""
+    _fields_ = [("screen_to_light", C.c_double * 16), ("bias", C.c_double), ("darkness", C.c_double),
+                ("pcf_radius", C.c_int32), ("reserved", C.c_int32)]
+
+
+def make_shadow_params(screen_to_light, bias=1e-3, darkness=0.5, pcf_radius=0) -> ShadowParams:
+    """trgl_shadow_params from a row-major 4x4 (shadow_matrix), the depth bias, how much a shadowed pixel loses and the PCF radius."""
+    p = ShadowParams()
+    p.screen_to_light[:] = np.asarray(screen_to_light, np.float64).reshape(16).tolist()
+    p.bias, p.darkness, p.pcf_radius, p.reserved = float(bias), float(darkness), int(pcf_radius), 0
+    return p
 
 
 def make_uniforms(model_view=None, key=(0, 0, 1), fill=(0, 0, 1), rim=(0, 0, 1), normal_map_strength=1.0,
@@ -198,6 +214,11 @@ def load_library(path: str = None):
     L.trgl_image_blur.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.trgl_image_scale.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.trgl_framebuffer_blur.argtypes = [vp, C.c_int]
+    L.trgl_shadow_matrix.argtypes = [dp, dp, dp, dp, dp, dp, dp]
+    L.trgl_shadow_mask_image.argtypes = [vp, C.POINTER(ShadowParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.trgl_shadow_mask.argtypes = [vp, C.POINTER(ShadowParams), C.c_int, C.c_void_p, C.c_int]
+    L.trgl_image_modulate.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.trgl_framebuffer_modulate.argtypes = [vp, C.c_void_p, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -398,6 +419,66 @@ def image_scale(img, w2: int, h2: int) -> np.ndarray:
     out = np.empty((max(int(h2), 0), max(int(w2), 0), src.shape[2] if len(src.shape) == 3 else 0), np.uint8)
     _image_scale(load_library(), None, src.ctypes.data, src, out.ctypes.data, w2, h2, False)
     return out
+
+
+def shadow_matrix(light_mv, light_proj, light_vp, cam_mv, cam_proj, cam_vp) -> np.ndarray:
+    """trgl_shadow_matrix: (Lvp * Lproj * Lmv) * inverse(Cvp * Cproj * Cmv) as a row-major [4, 4] - ShadowParams.screen_to_light.
+    Raises where the camera's matrix is singular.  Needs no GPU."""
+    L = load_library()
+    ms = [_f64(m, 16, "shadow_matrix") for m in (light_mv, light_proj, light_vp, cam_mv, cam_proj, cam_vp)]
+    out = np.empty(16, np.float64)
+    rc = L.trgl_shadow_matrix(*[_dp(m) for m in ms], _dp(out))
+    if rc != 0:
+        raise TrglError(f"trgl_shadow_matrix failed ({rc}): {L.trgl_last_error(None).decode()}")
+    return out.reshape(4, 4)
+
+
+def _depth_dims(a, what):
+    if len(a.shape) != 2:
+        raise ValueError(f"{what} must be [h, w]")
+    return int(a.shape[0]), int(a.shape[1])
+
+
+def _shadow_mask_image(L, handle, params, dptr, depth, mptr, zmap, optr, device):
+    h, w = _depth_dims(depth, "shadow_mask_image: depth")
+    mh, mw = _depth_dims(zmap, "shadow_mask_image: map")
+    rc = L.trgl_shadow_mask_image(handle, C.byref(params), dptr, w, h, mptr, mw, mh, optr, MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_shadow_mask_image failed ({rc}): {L.trgl_last_error(handle).decode()}")
+
+
+def _image_modulate(L, handle, ptr, img, mptr, mask, device):
+    h, w, bpp = _image_dims(img, "image_modulate")
+    if tuple(mask.shape[:2]) != (h, w) or int(np.prod(tuple(mask.shape))) != h * w:
+        raise ValueError("image_modulate: the mask must be [h, w] (or [h, w, 1]) like the image")
+    rc = L.trgl_image_modulate(handle, ptr, w, h, bpp, mptr, MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_image_modulate failed ({rc}): {L.trgl_last_error(handle).decode()}")
+
+
+def _host_shadow_mask_image(L, handle, params, depth, zmap):
+    depth, zmap = np.ascontiguousarray(depth, np.float64), np.ascontiguousarray(zmap, np.float64)
+    out = np.empty(depth.shape, np.uint8)
+    _shadow_mask_image(L, handle, params, depth.ctypes.data, depth, zmap.ctypes.data, zmap, out.ctypes.data, False)
+    return out
+
+
+def _host_image_modulate(L, handle, img, mask):
+    out, mask = np.array(img, np.uint8, order="C"), np.ascontiguousarray(mask, np.uint8)
+    _image_modulate(L, handle, out.ctypes.data, out, mask.ctypes.data, mask, False)
+    return out
+
+
+def shadow_mask_image(params: ShadowParams, depth, zmap) -> np.ndarray:
+    """trgl_shadow_mask_image for host arrays without a context: the [h, w] uint8 mask of the depths [h, w] against the light's depth map
+    [map_h, map_w] (the steps are written down in include/trgl.h).  Needs no GPU."""
+    return _host_shadow_mask_image(load_library(), None, params, depth, zmap)
+
+
+def image_modulate(img, mask) -> np.ndarray:
+    """trgl_image_modulate for host arrays without a context: a copy of img [h, w, bpp] uint8 with its colour channels multiplied by
+    mask [h, w] / 255 (main.cpp:775-781); alpha stays.  Needs no GPU."""
+    return _host_image_modulate(load_library(), None, img, mask)
 
 
 def aabb_transform(bmin, bmax, m):
@@ -711,6 +792,68 @@ class Context:
         """trgl_framebuffer_blur: framebuffer.gaussian_blur(radius) on the resident frame (flushes what is queued, does not wait); the
         z-buffer and the stats stay as they are.  Not on a strip / band context."""
         self._chk(self.L.trgl_framebuffer_blur(self.h, int(radius)))
+
+    def shadow_mask_image(self, params, depth, zmap, device=False, out=None):
+        """trgl_shadow_mask_image; returns the [h, w] uint8 mask.  Host arrays: no GPU work.  device=True: contiguous float64 device tensors
+        [h, w] and [map_h, map_w], masked on the context's stream in order with everything else (nothing is flushed, the call does not
+        wait); `out` is allocated with torch when not given."""
+        if not device:
+            return _host_shadow_mask_image(self.L, self.h, params, depth, zmap)
+        for t, what in ((depth, "depth"), (zmap, "zmap")):
+            if not hasattr(t, "data_ptr") or str(t.dtype) != "torch.float64" or not t.is_contiguous():
+                raise ValueError(f"device=True: {what} must be a contiguous float64 device tensor")
+        if out is None:
+            import torch
+            out = torch.empty(tuple(depth.shape), dtype=torch.uint8, device=depth.device)
+        elif tuple(out.shape) != tuple(depth.shape):
+            raise ValueError("shadow_mask_image: out must be [h, w]")
+        self._keep.append((depth, zmap, out))
+        _shadow_mask_image(self.L, self.h, params, _device_ptr(depth, "depth"), depth, _device_ptr(zmap, "zmap"), zmap, _device_image(out, "out"), True)
+        return out
+
+    def image_modulate(self, img, mask, device=False):
+        """trgl_image_modulate; returns the multiplied image.  Host arrays: computed on a copy.  device=True: contiguous uint8 device tensors
+        [h, w, bpp] and [h, w], img multiplied in place on the context's stream (nothing is flushed, the call does not wait)."""
+        if not device:
+            return _host_image_modulate(self.L, self.h, img, mask)
+        ptr, mptr = _device_image(img, "img"), _device_image(mask, "mask")
+        self._keep.append((img, mask))
+        _image_modulate(self.L, self.h, ptr, img, mptr, mask, True)
+        return img
+
+    def shadow_mask(self, params, slot=0, out=None, device=False):
+        """trgl_shadow_mask: the mask of the resident z-buffer against the depths of snapshot `slot` (flushes what is queued).  Returns a
+        [H, W] uint8 numpy array (the call waits for it), or with device=True a device tensor (allocated with torch when `out` is not
+        given; the call does not wait).  Not on a strip / band context."""
+        if device:
+            if out is None:
+                import torch
+                out = torch.empty((self.height, self.width), dtype=torch.uint8, device=f"cuda:{self.device}")
+            ptr = _device_image(out, "out")
+            self._keep.append((out,))
+        else:
+            if out is None:
+                out = np.empty((self.height, self.width), np.uint8)
+            if out.dtype != np.uint8 or not out.flags.c_contiguous:
+                raise ValueError("shadow_mask: out must be a contiguous uint8 array")
+            ptr = out.ctypes.data
+        if int(np.prod(tuple(out.shape))) != self.width * self.height:
+            raise ValueError("shadow_mask: out must hold W * H bytes")
+        self._chk(self.L.trgl_shadow_mask(self.h, C.byref(params), int(slot), ptr, MEM_DEVICE if device else MEM_HOST))
+        return out
+
+    def framebuffer_modulate(self, mask, device=False):
+        """trgl_framebuffer_modulate: the resident frame multiplied by mask [H, W] / 255 in place (flushes what is queued, does not wait);
+        the z-buffer and the stats stay as they are.  mask: a host array, or with device=True a contiguous uint8 device tensor."""
+        if device:
+            ptr = _device_image(mask, "mask")
+            self._keep.append((mask,))
+        else:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            ptr = mask.ctypes.data
+        if int(np.prod(tuple(mask.shape))) != self.width * self.height:
+            raise ValueError("framebuffer_modulate: the mask must hold W * H bytes")
+        self._chk(self.L.trgl_framebuffer_modulate(self.h, ptr, MEM_DEVICE if device else MEM_HOST))
 
     def zbuffer_snapshot(self, slot=0):
         """trgl_zbuffer_snapshot: main.cpp:700 as one device-to-device copy (flushes what is queued, does not wait)."""

@@ -1,4 +1,5 @@
-// launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_raster.hip).
+// launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_raster.hip, kernels_post.hip, kernels_mesh.hip,
+// kernels_image.hip, kernels_shadow.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"
@@ -103,6 +104,21 @@ void launch_image_blur(hipStream_t s, uint8_t* pixels, int w, int h, int bpp, in
 // (w2 - 1) * w, (h2 - 1) * h and both byte counts fit an int.
 constexpr int SCALE_BYTES = 256, SCALE_ROWS = 8;             // tile: bytes of an output row (one per thread) x output rows
 void launch_image_scale(hipStream_t s, const uint8_t* src, int w, int h, int bpp, uint8_t* dst, int w2, int h2);
+
+// The shadow post-pass (kernels_shadow.hip; the arithmetic is written down at trgl_shadow_mask_image in include/trgl.h).
+// depth: w * h depths, map: map_w * map_h depths of the light's view, both 8-byte aligned (16-byte aligned arrays are read as 16-byte
+// loads); mask: w * h bytes at any address.  w * h and map_w * map_h in 1..INT_MAX, radius in 0..TRGL_MAX_PCF_RADIUS.  The struct
+// travels as the kernel's argument.
+struct ShadowArgs {
+    double M[16]; double bias, darkness;
+    const double* depth; const double* map; uint8_t* mask;
+    int32_t w, h, map_w, map_h, radius;
+};
+constexpr int SHADOW_TILE_W = 32, SHADOW_TILE_H = 32;        // pixels of a block: four waves of 32 x 8 below one another
+void launch_shadow_mask(hipStream_t s, const ShadowArgs& a);
+// px[c] = (unsigned char)std::min(255.0, px[c] * (mask / 255.0)) for the colour channels c < min(bpp, 3) of npixels pixels, in place
+// (main.cpp:775-781); pixels and mask at any address, not overlapping.  npixels * bpp in 1..INT_MAX, bpp in {1, 3, 4}.
+void launch_modulate(hipStream_t s, uint8_t* pixels, uint64_t npixels, int bpp, const uint8_t* mask);
 
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,

@@ -105,6 +105,7 @@ struct trgl_ctx {
     // The weights travel through blur_w_pinned; ev_blur_w is recorded behind that copy, so that the next upload knows when it may rewrite it
     DevBuf<float> blur_weights; DevBuf<uint8_t> blur_tmp; int blur_radius = 0;
     float* blur_w_pinned = nullptr; size_t blur_w_pinned_cap = 0; hipEvent_t ev_blur_w = nullptr;
+    DevBuf<uint8_t> shadow_tmp;         // trgl_shadow_mask / trgl_framebuffer_modulate with a host mask: the W * H bytes on their way; grows on demand
     DevBuf<uint8_t> pp_out;             // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
     DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
@@ -1309,6 +1310,139 @@ int trgl_framebuffer_blur(trgl_ctx* c, int radius) {
     if ((int64_t)c->W * c->H * c->bpp > INT_MAX) return fail(c, TRGL_E_UNSUPPORTED, "trgl_framebuffer_blur: W * H * bpp above INT_MAX (the reference's int byte index overflows)");
     int r = trgl_flush(c); if (r) return r;          // completes a begun flush, draws what is queued, runs a pending clear
     return queue_blur(c, c->fb.p, c->W, c->H, c->bpp, radius, (size_t)c->W * c->H * c->bpp);
+}
+
+// ---- the shadow post-pass (include/trgl.h; host loops in shim/trgl_image.h, kernels in kernels_shadow.hip) ----------------------------
+static int check_shadow_params(trgl_ctx* c, const char* who, const trgl_shadow_params* p) {
+    const std::string w(who);
+    if (!p) return image_fail(c, TRGL_E_INVALID, w + ": params is null");
+    if (p->pcf_radius < 0 || p->pcf_radius > TRGL_MAX_PCF_RADIUS || p->reserved != 0)
+        return image_fail(c, TRGL_E_INVALID, w + ": need pcf_radius in 0.." + std::to_string(TRGL_MAX_PCF_RADIUS) + " and reserved == 0");
+    if (!(p->darkness >= 0.0 && p->darkness <= 1.0) || !std::isfinite(p->bias))
+        return image_fail(c, TRGL_E_INVALID, w + ": need darkness in [0, 1] and a finite bias");
+    return TRGL_OK;
+}
+
+static ShadowArgs shadow_args(const trgl_shadow_params* p, const double* depth, int w, int h, const double* map, int map_w, int map_h, uint8_t* mask) {
+    ShadowArgs a;
+    std::memcpy(a.M, p->screen_to_light, sizeof(a.M));
+    a.bias = p->bias; a.darkness = p->darkness;
+    a.depth = depth; a.map = map; a.mask = mask;
+    a.w = w; a.h = h; a.map_w = map_w; a.map_h = map_h; a.radius = p->pcf_radius;
+    return a;
+}
+
+int trgl_shadow_matrix(const double light_mv[16], const double light_proj[16], const double light_vp[16],
+                       const double cam_mv[16], const double cam_proj[16], const double cam_vp[16], double out[16]) {
+    if (!light_mv || !light_proj || !light_vp || !cam_mv || !cam_proj || !cam_vp || !out)
+        return image_fail(nullptr, TRGL_E_INVALID, "trgl_shadow_matrix: null matrix");
+    auto mul = [](const double* a, const double* b, double* r) {                     // geometry.h:196-205
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) {
+                double sum = 0;
+                for (int k = 0; k < 4; ++k) sum += a[4 * i + k] * b[4 * k + j];
+                r[4 * i + j] = sum;
+            }
+    };
+    double t[16], L[16], Cm[16], inv[16];
+    mul(light_vp, light_proj, t); mul(t, light_mv, L);                               // Viewport * Perspective * ModelView, left to right
+    mul(cam_vp, cam_proj, t); mul(t, cam_mv, Cm);
+    // Gauss-Jordan with partial pivoting on [Cm | I]
+    for (int i = 0; i < 16; ++i) inv[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    for (int col = 0; col < 4; ++col) {
+        int piv = col;
+        for (int r = col + 1; r < 4; ++r) if (std::fabs(Cm[4 * r + col]) > std::fabs(Cm[4 * piv + col])) piv = r;
+        const double pv = Cm[4 * piv + col];
+        if (pv == 0.0 || !std::isfinite(pv)) return image_fail(nullptr, TRGL_E_INVALID, "trgl_shadow_matrix: the camera's matrix is singular (a pivot is 0 or not finite)");
+        if (piv != col)
+            for (int k = 0; k < 4; ++k) { std::swap(Cm[4 * piv + k], Cm[4 * col + k]); std::swap(inv[4 * piv + k], inv[4 * col + k]); }
+        for (int k = 0; k < 4; ++k) { Cm[4 * col + k] /= pv; inv[4 * col + k] /= pv; }
+        for (int r = 0; r < 4; ++r) {
+            if (r == col) continue;
+            const double f = Cm[4 * r + col];
+            for (int k = 0; k < 4; ++k) { Cm[4 * r + k] -= f * Cm[4 * col + k]; inv[4 * r + k] -= f * inv[4 * col + k]; }
+        }
+    }
+    mul(L, inv, t);
+    std::memcpy(out, t, sizeof(t));
+    return TRGL_OK;
+}
+
+int trgl_shadow_mask_image(trgl_ctx* c, const trgl_shadow_params* params, const double* depth, int w, int h,
+                           const double* map, int map_w, int map_h, uint8_t* mask, int mem_kind) {
+    if (mem_kind != TRGL_MEM_HOST && mem_kind != TRGL_MEM_DEVICE) return image_fail(c, TRGL_E_INVALID, "trgl_shadow_mask_image: bad mem_kind");
+    if (int r = check_shadow_params(c, "trgl_shadow_mask_image", params)) return r;
+    if (w < 0 || h < 0 || map_w < 0 || map_h < 0) return image_fail(c, TRGL_E_INVALID, "trgl_shadow_mask_image: a negative dimension");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return image_fail(c, TRGL_E_INVALID, "trgl_shadow_mask_image: TRGL_MEM_DEVICE needs a context");
+    if (w == 0 || h == 0) return TRGL_OK;
+    if (map_w == 0 || map_h == 0) return image_fail(c, TRGL_E_INVALID, "trgl_shadow_mask_image: an empty depth map");
+    if (!depth || !map || !mask) return image_fail(c, TRGL_E_INVALID, "trgl_shadow_mask_image: null array");
+    if ((int64_t)w * h > INT_MAX || (int64_t)map_w * map_h > INT_MAX) return image_fail(c, TRGL_E_UNSUPPORTED, "trgl_shadow_mask_image: w * h or map_w * map_h above INT_MAX");
+    if (mem_kind == TRGL_MEM_HOST) {
+        trgl_image::shadow_mask_bytes(depth, w, h, params->screen_to_light, map, map_w, map_h, params->bias, params->darkness, params->pcf_radius, mask);
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    launch_shadow_mask(c->stream, shadow_args(params, depth, w, h, map, map_w, map_h, mask));
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_shadow_mask(trgl_ctx* c, const trgl_shadow_params* params, int slot, uint8_t* mask, int mask_mem_kind) {
+    CHKCTX(c);
+    if (mask_mem_kind != TRGL_MEM_HOST && mask_mem_kind != TRGL_MEM_DEVICE) return fail(c, TRGL_E_INVALID, "trgl_shadow_mask: bad mask_mem_kind");
+    int r = check_shadow_params(c, "trgl_shadow_mask", params); if (r) return r;
+    if ((r = zsnap_slot(c, slot, "trgl_shadow_mask"))) return r;
+    if (!mask) return fail(c, TRGL_E_INVALID, "trgl_shadow_mask: mask is null");
+    if (c->strip_y0 != 0 || c->strip_y1 != c->H || c->il_world > 1)
+        return fail(c, TRGL_E_STATE, "trgl_shadow_mask: the context owns a strip or interleaved bands; its snapshot holds only this rank's rows (gather with with_z and mask on one context)");
+    if (!c->zsnap[slot].p) return fail(c, TRGL_E_STATE, "trgl_shadow_mask: the slot holds no snapshot");
+    const size_t npx = (size_t)c->W * c->H;
+    if (npx > (size_t)INT_MAX) return fail(c, TRGL_E_UNSUPPORTED, "trgl_shadow_mask: W * H above INT_MAX");
+    if ((r = trgl_flush(c))) return r;                // completes a begun flush, draws what is queued, runs a pending clear
+    uint8_t* d_mask = mask;
+    if (mask_mem_kind == TRGL_MEM_HOST) { if ((r = c->shadow_tmp.grow(c, npx))) return r; d_mask = c->shadow_tmp.p; }
+    launch_shadow_mask(c->stream, shadow_args(params, c->zb.p, c->W, c->H, c->zsnap[slot].p, c->W, c->H, d_mask));
+    HIPCHK(c, hipGetLastError());
+    if (mask_mem_kind == TRGL_MEM_HOST) {
+        HIPCHK(c, hipMemcpyAsync(mask, d_mask, npx, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return TRGL_OK;
+}
+
+int trgl_image_modulate(trgl_ctx* c, uint8_t* pixels, int w, int h, int bpp, const uint8_t* mask, int mem_kind) {
+    if (mem_kind != TRGL_MEM_HOST && mem_kind != TRGL_MEM_DEVICE) return image_fail(c, TRGL_E_INVALID, "trgl_image_modulate: bad mem_kind");
+    if (!(bpp == 1 || bpp == 3 || bpp == 4) || w < 0 || h < 0) return image_fail(c, TRGL_E_INVALID, "trgl_image_modulate: need w, h >= 0 and bpp in {1, 3, 4}");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return image_fail(c, TRGL_E_INVALID, "trgl_image_modulate: TRGL_MEM_DEVICE needs a context");
+    if (w == 0 || h == 0) return TRGL_OK;
+    if (!pixels || !mask) return image_fail(c, TRGL_E_INVALID, "trgl_image_modulate: null image");
+    if ((int64_t)w * h * bpp > INT_MAX) return image_fail(c, TRGL_E_UNSUPPORTED, "trgl_image_modulate: w * h * bpp above INT_MAX");
+    if (mem_kind == TRGL_MEM_HOST) { trgl_image::modulate_bytes(pixels, (size_t)w * h, bpp, mask); return TRGL_OK; }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    launch_modulate(c->stream, pixels, (uint64_t)w * h, bpp, mask);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_framebuffer_modulate(trgl_ctx* c, const uint8_t* mask, int mask_mem_kind) {
+    CHKCTX(c);
+    if (mask_mem_kind != TRGL_MEM_HOST && mask_mem_kind != TRGL_MEM_DEVICE) return fail(c, TRGL_E_INVALID, "trgl_framebuffer_modulate: bad mask_mem_kind");
+    if (!mask) return fail(c, TRGL_E_INVALID, "trgl_framebuffer_modulate: mask is null");
+    const size_t npx = (size_t)c->W * c->H;
+    if (npx * c->bpp > (size_t)INT_MAX) return fail(c, TRGL_E_UNSUPPORTED, "trgl_framebuffer_modulate: W * H * bpp above INT_MAX");
+    int r = trgl_flush(c); if (r) return r;          // completes a begun flush, draws what is queued, runs a pending clear
+    if (mask_mem_kind == TRGL_MEM_HOST) {
+        if ((r = c->shadow_tmp.grow(c, npx))) return r;
+        // in stream order behind an earlier modulate that may still read shadow_tmp; a pinned mask is read when the stream gets here (include/trgl.h)
+        HIPCHK(c, hipMemcpyAsync(c->shadow_tmp.p, mask, npx, hipMemcpyHostToDevice, c->stream));
+        mask = c->shadow_tmp.p;
+    }
+    launch_modulate(c->stream, c->fb.p, npx, c->bpp, mask);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
 }
 
 void* trgl_framebuffer_device_ptr(trgl_ctx* c) { return c ? c->fb.p : nullptr; }

@@ -29,6 +29,8 @@
 //     gl_mesh_normals(model) / gl_mesh_tangents(model) are Model::generateNormalsIfNeeded / computeTangentsIfNeeded (model.cpp:269-388).
 //   * gl_gaussian_blur(framebuffer, radius) is framebuffer.gaussian_blur(radius) (tgaimage.cpp:271-324) on the frame in HBM, byte for
 //     byte; TGAImage::scale / gaussian_blur themselves are host loops in trgl_image.h, as in the reference.
+//   * shadows (new; the reference has none): gl_shadow_matrix / gl_shadow_mask / gl_modulate turn the depths of a light's view, kept with
+//     gl_zbuffer_snapshot, into a mask and multiply it into the frame in HBM (see below, and include/trgl.h).
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -533,6 +535,45 @@ inline bool gl_gaussian_blur(TGAImage& framebuffer, int radius) {
     if (!bind(framebuffer)) return false;
     const bool ok = submit_batch();
     return TRGL_SHIM_OK(trgl_framebuffer_blur(state().ctx, radius)) && ok;
+}
+
+// Shadow mapping as a post-pass (include/trgl.h, "shadow mapping as a post-pass"; new work, the reference has none).  Draw the light's
+// view, gl_zbuffer_snapshot(framebuffer, slot), clear, draw the camera's view, then:
+//   gl_shadow_matrix   the matrix of trgl_shadow_params::screen_to_light from the two views' ModelView / Perspective / Viewport as they
+//                      were when each was drawn; false for a singular camera matrix (gl_last_error())
+//   gl_shadow_mask     the mask of the depths in HBM against the snapshot in `slot` (trgl_shadow_mask): triangles batched so far are drawn
+//                      first.  `mask` becomes a W x H GRAYSCALE image holding it (the call waits for those bytes); a caller may soften it
+//                      with TGAImage::gaussian_blur.  The shim's images are host objects: a null `mask` is an error (TRGL_E_INVALID), and the
+//                      sequence that keeps the mask in HBM is the C ABI's (trgl_shadow_mask with TRGL_MEM_DEVICE).
+//   gl_modulate        the frame in HBM multiplied by the mask (trgl_framebuffer_modulate), without waiting; the caller's TGAImage still
+//                      holds the old pixels, a later gl_flush(framebuffer) hands back the darkened ones.
+inline bool gl_shadow_matrix(const mat<4, 4>& light_mv, const mat<4, 4>& light_proj, const mat<4, 4>& light_vp,
+                             const mat<4, 4>& cam_mv, const mat<4, 4>& cam_proj, const mat<4, 4>& cam_vp, mat<4, 4>& out) {
+    const mat<4, 4>* in[6] = { &light_mv, &light_proj, &light_vp, &cam_mv, &cam_proj, &cam_vp };
+    double m[6][16], o[16];
+    for (int k = 0; k < 6; ++k) for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m[k][4 * r + c] = (*in[k])[r][c];
+    const int rc = trgl_shadow_matrix(m[0], m[1], m[2], m[3], m[4], m[5], o);
+    if (rc != TRGL_OK) return trgl_shim::fail("trgl_shadow_matrix", rc, nullptr);
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) out[r][c] = o[4 * r + c];
+    return true;
+}
+inline bool gl_shadow_mask(TGAImage& framebuffer, const trgl_shadow_params& params, int slot, TGAImage* mask) {
+    using namespace trgl_shim;
+    State& s = state();
+    if (!mask) return fail("gl_shadow_mask: mask is null", TRGL_E_INVALID, nullptr);
+    if (!bind(framebuffer)) return false;
+    const bool ok = submit_batch();
+    if (mask->width() != s.w || mask->height() != s.h || image_bpp(*mask) != 1) *mask = TGAImage(s.w, s.h, TGAImage::GRAYSCALE);
+    return TRGL_SHIM_OK(trgl_shadow_mask(s.ctx, &params, slot, mask->buffer(), TRGL_MEM_HOST)) && ok;
+}
+inline bool gl_modulate(TGAImage& framebuffer, const TGAImage& mask) {
+    using namespace trgl_shim;
+    State& s = state();
+    if (!bind(framebuffer)) return false;
+    const bool ok = submit_batch();
+    if (mask.width() != s.w || mask.height() != s.h || image_bpp(mask) != 1)
+        return fail("gl_modulate: the mask must be a GRAYSCALE image of the framebuffer's size", TRGL_E_INVALID, nullptr);
+    return TRGL_SHIM_OK(trgl_framebuffer_modulate(s.ctx, image_bytes(mask), TRGL_MEM_HOST)) && ok;
 }
 
 inline void print_render_stats() {                                                // our_gl.cpp:204-210

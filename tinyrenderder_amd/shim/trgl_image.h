@@ -5,7 +5,8 @@
 // The reader follows read_tga_file / load_rle_data (tgaimage.cpp:76-160).  Host-only; this is SURVEY.md §8(f) row N3.
 // scale() and gaussian_blur() (tgaimage.cpp:246-324) are host loops over trgl_image::scale_bytes / blur_bytes below, the same functions
 // the C ABI's TRGL_MEM_HOST paths run (trgl_image_scale, trgl_image_blur); compile with -ffp-contract=off, as everything that must
-// match the reference's bytes.
+// match the reference's bytes.  shadow_mask_bytes / modulate_bytes are the host loops of the shadow post-pass (trgl_shadow_mask_image,
+// trgl_image_modulate), which has no counterpart in the reference.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -76,6 +77,60 @@ inline void scale_bytes(const std::uint8_t* src, int w, int h, int bpp, std::uin
         const std::uint8_t* srow = src + std::size_t(y * h / h2) * w * bpp;
         std::uint8_t* drow = dst + std::size_t(y) * w2 * bpp;
         for (int x = 0; x < w2; ++x) std::memcpy(drow + std::size_t(x) * bpp, srow + std::size_t(x * w / w2) * bpp, bpp);
+    }
+}
+
+// The shadow post-pass of trgl_shadow_mask_image (include/trgl.h, steps 1-8 there): one byte per camera pixel from its depth, the row-major
+// M that carries the pixel centre (x + 0.5, y + 0.5, z, 1) into the light's screen space, and the light's depth map.  fp64, no contraction.
+// A pixel that cannot be tested - background, behind the light, outside the light's depth range or its map - is lit (255).
+inline std::uint8_t shadow_byte(double z, int x, int y, const double* M, const double* map, int map_w, int map_h,
+                                double bias, double darkness, int radius) {
+    if (!std::isfinite(z)) return 255;
+    const double p[4] = { x + 0.5, y + 0.5, z, 1.0 };                          // the pixel centre of our_gl.cpp:149
+    double q[4];
+    for (int r = 0; r < 4; ++r) {                                              // geometry.h:122-127,187-192
+        double sum = 0;
+        for (int c = 0; c < 4; ++c) sum += M[4 * r + c] * p[c];
+        q[r] = sum;
+    }
+    if (!(q[3] > 1e-12)) return 255;                                           // our_gl.cpp:94
+    double s[3];
+    for (int k = 0; k < 3; ++k) { s[k] = q[k] / q[3]; if (!std::isfinite(s[k])) return 255; }   // geometry.h:117
+    if (s[2] < -1.0 || s[2] > 1.0) return 255;                                 // our_gl.cpp:103
+    if (!(s[0] >= 0.0 && s[0] < double(map_w) && s[1] >= 0.0 && s[1] < double(map_h))) return 255;
+    const int ix = int(s[0]), iy = int(s[1]);
+    const double limit = s[2] - bias;
+    // the taps that lie inside the map; one outside never occludes, and neither does +inf or NaN (`<` is false)
+    const int x_lo = ix - radius < 0 ? 0 : ix - radius, x_hi = ix > map_w - 1 - radius ? map_w - 1 : ix + radius;
+    const int y_lo = iy - radius < 0 ? 0 : iy - radius, y_hi = iy > map_h - 1 - radius ? map_h - 1 : iy + radius;
+    int occluded = 0;
+    for (int ty = y_lo; ty <= y_hi; ++ty) {
+        const double* row = map + std::size_t(ty) * map_w;
+        for (int tx = x_lo; tx <= x_hi; ++tx) occluded += row[tx] < limit ? 1 : 0;
+    }
+    const int total = (2 * radius + 1) * (2 * radius + 1);
+    const double factor = 1.0 - (double(occluded) / double(total)) * darkness;  // the shape of main.cpp:360-361
+    return (unsigned char)(255.0 * factor);                                    // main.cpp:760
+}
+inline void shadow_mask_bytes(const double* depth, int w, int h, const double* M, const double* map, int map_w, int map_h,
+                              double bias, double darkness, int radius, std::uint8_t* mask) {
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const std::size_t i = std::size_t(x) + std::size_t(y) * w;
+            mask[i] = shadow_byte(depth[i], x, y, M, map, map_w, map_h, bias, darkness, radius);
+        }
+}
+
+// The composite's arithmetic (main.cpp:775-781) with a one-byte factor per pixel, in place: the colour channels (at most three) are
+// multiplied by mask / 255.0 and truncated; alpha stays.  A mask byte of 255 is the factor 1.0 exactly and changes nothing.
+inline void modulate_bytes(std::uint8_t* pixels, std::size_t npixels, int bpp, const std::uint8_t* mask) {
+    const int nc = bpp < 3 ? bpp : 3;
+    for (std::size_t i = 0; i < npixels; ++i) {
+        const double f = double(mask[i]) / 255.0;                              // :775
+        for (int c = 0; c < nc; ++c) {
+            const double v = double(pixels[i * bpp + c]) * f;
+            pixels[i * bpp + c] = (unsigned char)(v < 255.0 ? v : 255.0);      // std::min(255.0, v), :777-781
+        }
     }
 }
 
