@@ -6,16 +6,16 @@ caller's pointers as they are, so every read below is checked from a caller's bu
      k_shade<ANY>), whole, in three flushes, in an odd-row strip and in one rank's bands;
   b. user kinds: in.vary = d.vary + local * K (shade_user.h:43; raster_user.h:108 for kinds that may discard), K = 24 and K = 5;
   c. alignment: k_setup's copy of a clip stream that is not 16-byte aligned (kernels_bin.hip:65-67: only a caller's device
-     pointer reaches it, the host path stages into 256-byte aligned chunks, trgl_api.cpp:312-323), whole and partial blocks,
+     pointer reaches it, the host path stages into 256-byte aligned chunks, stage_alloc in trgl_api.cpp), whole and partial blocks,
      8-aligned varyings, 4-aligned colours, the literal records;
-  d. host and device draws in one flush (trgl_api.cpp:353-361), and more device draws than a flush has descriptors
-     (trgl_api.cpp:367) while Context._keep holds the tensors;
+  d. host and device draws in one flush (trgl_draw in trgl_api.cpp), and more device draws than a flush has descriptors
+     (its cut at TRGL_MAX_DRAWS) while Context._keep holds the tensors;
   e. arrays are read by the flush and not afterwards: buffers reused between frames as bench.py's loop reuses them, and
      overwritten once the flush has completed;
-  f. stream ordering: the context's own stream is hipStreamNonBlocking (trgl_api.cpp:175) and waits for nobody; on a shared
+  f. stream ordering: the context's own stream is hipStreamNonBlocking (init_ctx in trgl_api.cpp) and waits for nobody; on a shared
      stream (trgl_set_stream) producers, flush and overwrites line up without a host sync, as bench.py and shard.StripLoop rely on;
   g. trgl_draw_indexed(TRGL_MEM_DEVICE): k_vertex_stage gathers through the caller's pointers (kernels_post.hip:43), whole
-     meshes and the block edges of 64 faces (trgl_api.cpp:394-412 does not stage or check on this path).
+     meshes and the block edges of 64 faces (trgl_draw_indexed in trgl_shader.cpp does not stage or check on this path).
 
 Bar: the device-memory frame equals the host-memory frame of the same GPU bit for bit - z bits, framebuffer bytes, stats tuple and
 stats line, EYE included (the same kernels on the same numbers) - and the oracle's / the reference's golden within the suite's bar

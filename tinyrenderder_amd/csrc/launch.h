@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_raster.hip, kernels_post.hip, kernels_mesh.hip,
-// kernels_image.hip, kernels_shadow.hip).
+// kernels_image.hip, kernels_shadow.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex stage) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"

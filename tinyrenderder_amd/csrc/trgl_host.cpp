@@ -1,0 +1,290 @@
+// trgl_host.cpp — the part of the C ABI in include/trgl.h that runs on the host alone and includes no HIP header: mesh attributes and
+// bounds in host memory, AABB / frustum / shadow-matrix maths, TGA and OBJ files, stats formatting, the global error string.
+// Its arithmetic is pinned bit for bit to the reference (-ffp-contract=off; the sums are chains of `sum += ...`, in the reference's order).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/trgl.h"
+#include "../shim/trgl_image.h"
+#include "../shim/trgl_obj.h"
+
+namespace trgl {
+static thread_local std::string g_error;
+void set_global_error(const std::string& msg) { g_error = msg; }
+const char* global_error() { return g_error.c_str(); }
+int fail(trgl_ctx* c, int code, const std::string& msg);       // trgl_api.cpp; called with c == nullptr here
+
+// ---- scene logic around the draws (model.cpp:15-40, geometry.h:264-266,297-327, our_gl.cpp:212-280) ------------------------------
+// std::min(a, b) = (b < a) ? b : a and std::max(a, b) = (a < b) ? b : a with a the running bound: what decides NaNs and signed zeros
+static inline double keep_min(double bound, double p) { return p < bound ? p : bound; }
+static inline double keep_max(double bound, double p) { return bound < p ? p : bound; }
+// dot<n> (geometry.h:122-127): summed left to right from 0
+static inline double dot3_from_zero(const double* a, double x, double y, double z) { double sum = 0; sum += a[0] * x; sum += a[1] * y; sum += a[2] * z; return sum; }
+
+void host_mesh_bounds(const double* vertices, int stride, uint64_t n, double out_min[3], double out_max[3]) {
+    double lo[3] = { 1e9, 1e9, 1e9 }, hi[3] = { -1e9, -1e9, -1e9 };         // model.cpp:21-22
+    for (uint64_t i = 0; i < n; ++i) {
+        const double* p = vertices + i * (uint64_t)stride;
+        for (int a = 0; a < 3; ++a) lo[a] = keep_min(lo[a], p[a]);          // :25-27
+        for (int a = 0; a < 3; ++a) hi[a] = keep_max(hi[a], p[a]);          // :29-31
+    }
+    for (int a = 0; a < 3; ++a) {
+        const double margin = (hi[a] - lo[a]) * 0.01;                       // :35
+        out_min[a] = lo[a] - margin; out_max[a] = hi[a] + margin;           // :36
+    }
+}
+
+// ---- Model::generateNormalsIfNeeded (model.cpp:269-316) and Model::computeTangentsIfNeeded (model.cpp:318-388) ----------------------
+// norm (geometry.h:130-133) of three consecutive doubles
+static inline double norm3_from_zero(const double* v) { return std::sqrt(dot3_from_zero(v, v[0], v[1], v[2])); }
+// normalized (geometry.h:136-140): a zero vector comes back unchanged
+static inline void normalize3(double* v) {
+    const double length = norm3_from_zero(v);
+    if (length == 0) return;
+    for (int a = 0; a < 3; ++a) v[a] = v[a] / length;
+}
+
+static void host_mesh_normals(double* vertices, uint64_t stride, uint64_t n, const uint32_t* indices, uint64_t nfaces) {
+    for (uint64_t i = 0; i < n; ++i) { double* nrm = vertices + i * stride + 3; nrm[0] = nrm[1] = nrm[2] = 0.0; }     // :283-285
+    for (uint64_t f = 0; f < nfaces; ++f) {                                                                          // :288-305
+        const double* v0 = vertices + indices[3 * f] * stride; const double* v1 = vertices + indices[3 * f + 1] * stride;
+        const double* v2 = vertices + indices[3 * f + 2] * stride;
+        double e1[3], e2[3];
+        for (int a = 0; a < 3; ++a) { e1[a] = v1[a] - v0[a]; e2[a] = v2[a] - v0[a]; }
+        const double fn[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+        for (int k = 0; k < 3; ++k) {
+            double* nrm = vertices + indices[3 * f + k] * stride + 3;
+            for (int a = 0; a < 3; ++a) nrm[a] = nrm[a] + fn[a];
+        }
+    }
+    for (uint64_t i = 0; i < n; ++i) {                                                                               // :308-315
+        double* nrm = vertices + i * stride + 3;
+        const double length = norm3_from_zero(nrm);
+        if (length > 0.001) { for (int a = 0; a < 3; ++a) nrm[a] = nrm[a] / length; }
+        else { nrm[0] = 0; nrm[1] = 0; nrm[2] = 1; }
+    }
+}
+
+static void host_mesh_tangents(double* vertices, uint64_t stride, uint64_t n, const uint32_t* indices, uint64_t nfaces) {
+    for (uint64_t i = 0; i < n; ++i) { double* t = vertices + i * stride + 8; for (int a = 0; a < 6; ++a) t[a] = 0.0; }   // :332-335
+    for (uint64_t f = 0; f < nfaces; ++f) {                                                                          // :338-368
+        const double* v0 = vertices + indices[3 * f] * stride; const double* v1 = vertices + indices[3 * f + 1] * stride;
+        const double* v2 = vertices + indices[3 * f + 2] * stride;
+        double dp1[3], dp2[3];
+        for (int a = 0; a < 3; ++a) { dp1[a] = v1[a] - v0[a]; dp2[a] = v2[a] - v0[a]; }
+        const double duv1x = v1[6] - v0[6], duv1y = v1[7] - v0[7], duv2x = v2[6] - v0[6], duv2y = v2[7] - v0[7];
+        const double r = duv1x * duv2y - duv2x * duv1y;                                                              // :353
+        if (std::fabs(r) < 1e-8) continue;
+        const double invr = 1.0 / r;
+        double tangent[3], bitangent[3];
+        for (int a = 0; a < 3; ++a) {
+            tangent[a] = (dp1[a] * duv2y - dp2[a] * duv1y) * invr;                                                   // :358
+            bitangent[a] = (dp2[a] * duv1x - dp1[a] * duv2x) * invr;                                                 // :359
+        }
+        for (int k = 0; k < 3; ++k) { double* t = vertices + indices[3 * f + k] * stride + 8; for (int a = 0; a < 3; ++a) t[a] = t[a] + tangent[a]; }
+        for (int k = 0; k < 3; ++k) { double* b = vertices + indices[3 * f + k] * stride + 11; for (int a = 0; a < 3; ++a) b[a] = b[a] + bitangent[a]; }
+    }
+    for (uint64_t i = 0; i < n; ++i) {                                                                               // :371-387
+        double* rec = vertices + i * stride;
+        double* t = rec + 8; double* b = rec + 11;
+        if (norm3_from_zero(t) > 0.001 && norm3_from_zero(rec + 3) > 0.001) {
+            double nn[3] = { rec[3], rec[4], rec[5] };
+            normalize3(nn);                                                                                          // :374
+            normalize3(t);                                                                                           // :375
+            const double d = dot3_from_zero(nn, t[0], t[1], t[2]);
+            for (int a = 0; a < 3; ++a) t[a] = t[a] - nn[a] * d;                                                     // :378
+            normalize3(t);
+            b[0] = rec[4] * t[2] - rec[5] * t[1]; b[1] = rec[5] * t[0] - rec[3] * t[2]; b[2] = rec[3] * t[1] - rec[4] * t[0];   // :381
+        } else {
+            t[0] = 1; t[1] = 0; t[2] = 0; b[0] = 0; b[1] = 1; b[2] = 0;                                              // :384-385
+        }
+    }
+}
+
+int host_mesh_attr(bool tangents, double* vertices, int stride, uint64_t n, const uint32_t* indices, uint64_t nfaces) {
+    for (uint64_t k = 0; k < 3 * nfaces; ++k)
+        if (indices[k] >= n) return -1;
+    bool need = false;                                                      // :270-276 / :319-325
+    for (uint64_t i = 0; i < n && !need; ++i) need = norm3_from_zero(vertices + i * (uint64_t)stride + (tangents ? 8 : 3)) < 0.001;
+    if (!need) return 0;
+    if (tangents) host_mesh_tangents(vertices, (uint64_t)stride, n, indices, nfaces);
+    else host_mesh_normals(vertices, (uint64_t)stride, n, indices, nfaces);
+    return 1;
+}
+}  // namespace trgl
+using namespace trgl;
+
+extern "C" {
+
+void trgl_ssao_defaults(trgl_ssao_params* p) {      // main.cpp:317-321
+    if (!p) return;
+    p->num_directions = 8; p->steps_per_direction = 8; p->sample_radius = 16.0; p->occlusion_threshold = 1e-3; p->intensity = 0.35;
+}
+
+int trgl_format_stats(const trgl_stats* s, char* buf, size_t buflen) {   // our_gl.cpp:205-209
+    if (!s || !buf) return TRGL_E_INVALID;
+    char lo[400], hi[400];      // "%f" of a double needs up to 317 characters
+    if (std::isfinite(s->min_z)) std::snprintf(lo, sizeof lo, "%f", s->min_z); else std::snprintf(lo, sizeof lo, "inf");
+    if (std::isfinite(s->max_z)) std::snprintf(hi, sizeof hi, "%f", s->max_z); else std::snprintf(hi, sizeof hi, "-inf");
+    int n = std::snprintf(buf, buflen, "DEBUG: triangles=%llu fragments_drawn=%llu bbox=[%d,%d] - [%d,%d] z-range=[%s,%s]\n",
+                          (unsigned long long)s->triangles_rasterized, (unsigned long long)s->fragments_drawn,
+                          s->min_x, s->min_y, s->max_x, s->max_y, lo, hi);
+    return (n < 0 || (size_t)n >= buflen) ? TRGL_E_INVALID : TRGL_OK;
+}
+
+int trgl_aabb_transform(const double bmin[3], const double bmax[3], const double m[16], double out_min[3], double out_max[3]) {
+    if (!bmin || !bmax || !m || !out_min || !out_max) return TRGL_E_INVALID;
+    double lo[3] = { 1e9, 1e9, 1e9 }, hi[3] = { -1e9, -1e9, -1e9 };             // geometry.h:309-310
+    for (int i = 0; i < 8; ++i) {                                               // :300-307: corner i takes max.x for bit 0, max.y for bit 1, max.z for bit 2
+        const double x = (i & 1) ? bmax[0] : bmin[0], y = (i & 2) ? bmax[1] : bmin[1], z = (i & 4) ? bmax[2] : bmin[2];
+        double t[4];
+        for (int row = 0; row < 4; ++row) {                                     // :314, mat * vec4(corner, 1.0): one dot<4> per row
+            double sum = 0;
+            sum += m[4 * row] * x; sum += m[4 * row + 1] * y; sum += m[4 * row + 2] * z; sum += m[4 * row + 3] * 1.0;
+            t[row] = sum;
+        }
+        for (int a = 0; a < 3; ++a) {
+            const double pos = t[a] / t[3];                                     // :315, no guard
+            lo[a] = keep_min(lo[a], pos);                                       // :317-319
+            hi[a] = keep_max(hi[a], pos);                                       // :321-323
+        }
+    }
+    for (int a = 0; a < 3; ++a) { out_min[a] = lo[a]; out_max[a] = hi[a]; }
+    return TRGL_OK;
+}
+
+int trgl_frustum_from_matrix(const double m[16], double planes[24]) {
+    if (!m || !planes) return TRGL_E_INVALID;
+    for (int pair = 0; pair < 3; ++pair)                                        // our_gl.cpp:217-250: LEFT/RIGHT with k = 0, BOTTOM/TOP 1, NEAR/FAR 2
+        for (int side = 0; side < 2; ++side) {
+            double* pl = planes + 4 * (2 * pair + side);
+            for (int row = 0; row < 4; ++row)                                   // rows 0..2 give the normal, row 3 gives d
+                pl[row] = side == 0 ? m[4 * row + 3] + m[4 * row + pair] : m[4 * row + 3] - m[4 * row + pair];
+        }
+    for (int i = 0; i < 6; ++i) {                                               // :253-259
+        double* pl = planes + 4 * i;
+        const double length = std::sqrt(dot3_from_zero(pl, pl[0], pl[1], pl[2]));
+        if (length > 0.0) { pl[0] = pl[0] / length; pl[1] = pl[1] / length; pl[2] = pl[2] / length; pl[3] /= length; }
+    }
+    return TRGL_OK;
+}
+
+int trgl_frustum_intersects(const double planes[24], const double bmin[3], const double bmax[3]) {
+    if (!planes || !bmin || !bmax) return TRGL_E_INVALID;
+    for (int i = 0; i < 6; ++i) {                                               // our_gl.cpp:265-278
+        const double* pl = planes + 4 * i;
+        double positive[3] = { bmin[0], bmin[1], bmin[2] };                     // :269
+        for (int a = 0; a < 3; ++a) if (pl[a] >= 0) positive[a] = bmax[a];      // :270-272
+        if (dot3_from_zero(pl, positive[0], positive[1], positive[2]) + pl[3] < 0) return 0;   // :275, Plane::distance
+    }
+    return 1;
+}
+
+int trgl_gaussian_kernel(int radius, float* weights) {      // TGAImage::gaussian_blur's weights (tgaimage.cpp:271-324)
+    if (radius <= 0 || !weights) return fail(nullptr, TRGL_E_INVALID, "trgl_gaussian_kernel: need radius >= 1 and room for 2 * radius + 1 weights");
+    if (radius > TRGL_MAX_BLUR_RADIUS) return fail(nullptr, TRGL_E_UNSUPPORTED, "trgl_gaussian_kernel: radius above 46340 (i * i overflows the reference's int)");
+    trgl_image::gaussian_weights(radius, weights);
+    return TRGL_OK;
+}
+
+int trgl_shadow_matrix(const double light_mv[16], const double light_proj[16], const double light_vp[16],
+                       const double cam_mv[16], const double cam_proj[16], const double cam_vp[16], double out[16]) {
+    if (!light_mv || !light_proj || !light_vp || !cam_mv || !cam_proj || !cam_vp || !out)
+        return fail(nullptr, TRGL_E_INVALID, "trgl_shadow_matrix: null matrix");
+    auto mul = [](const double* a, const double* b, double* r) {                     // geometry.h:196-205
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) {
+                double sum = 0;
+                for (int k = 0; k < 4; ++k) sum += a[4 * i + k] * b[4 * k + j];
+                r[4 * i + j] = sum;
+            }
+    };
+    double t[16], L[16], Cm[16], inv[16];
+    mul(light_vp, light_proj, t); mul(t, light_mv, L);                               // Viewport * Perspective * ModelView, left to right
+    mul(cam_vp, cam_proj, t); mul(t, cam_mv, Cm);
+    // Gauss-Jordan with partial pivoting on [Cm | I]
+    for (int i = 0; i < 16; ++i) inv[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    for (int col = 0; col < 4; ++col) {
+        int piv = col;
+        for (int r = col + 1; r < 4; ++r) if (std::fabs(Cm[4 * r + col]) > std::fabs(Cm[4 * piv + col])) piv = r;
+        const double pv = Cm[4 * piv + col];
+        if (pv == 0.0 || !std::isfinite(pv)) return fail(nullptr, TRGL_E_INVALID, "trgl_shadow_matrix: the camera's matrix is singular (a pivot is 0 or not finite)");
+        if (piv != col)
+            for (int k = 0; k < 4; ++k) { std::swap(Cm[4 * piv + k], Cm[4 * col + k]); std::swap(inv[4 * piv + k], inv[4 * col + k]); }
+        for (int k = 0; k < 4; ++k) { Cm[4 * col + k] /= pv; inv[4 * col + k] /= pv; }
+        for (int r = 0; r < 4; ++r) {
+            if (r == col) continue;
+            const double f = Cm[4 * r + col];
+            for (int k = 0; k < 4; ++k) { Cm[4 * r + k] -= f * Cm[4 * col + k]; inv[4 * r + k] -= f * inv[4 * col + k]; }
+        }
+    }
+    mul(L, inv, t);
+    std::memcpy(out, t, sizeof(t));
+    return TRGL_OK;
+}
+
+int trgl_obj_load(const char* path, double** vertices, uint64_t* n_vertices, uint32_t** indices, uint64_t* n_faces) {
+    if (!path || !vertices || !n_vertices || !indices || !n_faces) return TRGL_E_INVALID;
+    trgl_obj::Mesh m;
+    try {
+        if (!trgl_obj::load(path, m)) return fail(nullptr, TRGL_E_INVALID, m.error);
+    } catch (const std::bad_alloc&) {
+        return fail(nullptr, TRGL_E_NOMEM, "trgl_obj_load: out of memory");
+    }
+    *n_vertices = m.vertices.size() / 14; *n_faces = m.indices.size() / 3;
+    *vertices = (double*)std::malloc(m.vertices.size() * sizeof(double) + 8);
+    *indices = (uint32_t*)std::malloc(m.indices.size() * sizeof(uint32_t) + 8);
+    if (!*vertices || !*indices) { std::free(*vertices); std::free(*indices); return TRGL_E_NOMEM; }
+    std::memcpy(*vertices, m.vertices.data(), m.vertices.size() * sizeof(double));
+    std::memcpy(*indices, m.indices.data(), m.indices.size() * sizeof(uint32_t));
+    return TRGL_OK;
+}
+void trgl_obj_free(double* vertices, uint32_t* indices) { std::free(vertices); std::free(indices); }
+
+size_t trgl_tga_max_size(int w, int h, int bpp) {
+    if (w <= 0 || h <= 0 || bpp <= 0) return 18;
+    return size_t(18) + size_t(w) * h * bpp + size_t(w) * h;      // every pixel its own literal packet
+}
+
+int trgl_tga_encode(const uint8_t* pixels, int w, int h, int bpp, int vflip, int rle, uint8_t* out, size_t* out_len) {
+    if (!pixels || !out || !out_len || w <= 0 || h <= 0 || w > 65535 || h > 65535 || !(bpp == 1 || bpp == 3 || bpp == 4)) return TRGL_E_INVALID;
+    try {
+        TGAImage img(w, h, bpp);
+        std::memcpy(img.buffer(), pixels, size_t(w) * h * bpp);
+        std::vector<uint8_t> bytes = img.encode_tga(vflip != 0, rle != 0);
+        std::memcpy(out, bytes.data(), bytes.size());
+        *out_len = bytes.size();
+    } catch (const std::bad_alloc&) {
+        return TRGL_E_NOMEM;
+    }
+    return TRGL_OK;
+}
+
+int trgl_tga_info(const uint8_t* file, size_t size, int* width, int* height, int* bpp) {
+    if (!file || !width || !height || !bpp || size < 18) return TRGL_E_INVALID;            // tgaimage.cpp:85-90
+    const int w = file[12] | (file[13] << 8), h = file[14] | (file[15] << 8), b = file[16] >> 3;
+    if (w <= 0 || h <= 0 || (b != 1 && b != 3 && b != 4)) return TRGL_E_INVALID;           // :96-99
+    if (!(file[2] == 2 || file[2] == 3 || file[2] == 10 || file[2] == 11)) return TRGL_E_INVALID;   // :113-116
+    *width = w; *height = h; *bpp = b;
+    return TRGL_OK;
+}
+
+int trgl_tga_decode(const uint8_t* file, size_t size, uint8_t* pixels) {
+    if (!file || !pixels) return TRGL_E_INVALID;
+    try {                                          // a header may claim 65535 x 65535 x 4 bytes: nothing throws across the C ABI
+        TGAImage img;
+        if (!img.decode_tga(file, size)) return TRGL_E_INVALID;
+        std::memcpy(pixels, img.buffer(), size_t(img.width()) * img.height() * img.bytespp());
+    } catch (const std::bad_alloc&) {
+        return TRGL_E_NOMEM;
+    }
+    return TRGL_OK;
+}
+
+}  // extern "C"

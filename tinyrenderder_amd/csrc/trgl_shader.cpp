@@ -1,0 +1,171 @@
+// trgl_shader.cpp — run-time shader registration (fragment kinds and vertex shaders, compiled by user_shaders.cpp) and the entry points
+// that run a vertex stage over an indexed mesh: trgl_draw_indexed, trgl_draw_indexed_vs, trgl_vertex_stage.  The draws they make go
+// through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
+#include <cstring>
+
+#include "trgl_ctx.h"
+#include "user_shaders.h"
+
+// The vertex stage of `vs` (-1: k_vertex_stage) over an indexed mesh in device memory, queued on the context's stream.  clip and
+// vary (unused when K = 0) are 16-byte aligned; u == nullptr: zeros, texture slots -1.
+static int queue_vertex_stage(trgl_ctx* c, int vs, const trgl_uniforms* u, const double projection[16], const double* dv, int stride,
+                              const uint32_t* di, uint64_t n_faces, double* clip, double* vary) {
+    if (vs < 0) {
+        launch_vertex_stage(c->stream, u->model_view, projection, dv, stride, di, (uint32_t)n_faces, clip, vary);
+        HIPCHK(c, hipGetLastError());
+        return TRGL_OK;
+    }
+    VertexUserParams p; std::memset(&p, 0, sizeof(p));
+    if (u) p.u = *u; else p.u.tex_diffuse = p.u.tex_normal = p.u.tex_specular = -1;
+    std::memcpy(p.proj, projection, sizeof(p.proj));
+    p.vertices = dv; p.indices = di; p.clip = clip; p.vary = vary; p.nfaces = (uint32_t)n_faces; p.stride = stride;
+    void* args[] = { &p };
+    const uint64_t blocks = (n_faces + TRGL_VERTEX_USER_FACES - 1) / TRGL_VERTEX_USER_FACES;
+    HIPCHK(c, hipModuleLaunchKernel(c->vertex[vs].fn, (unsigned)blocks, 1, 1, TRGL_VERTEX_USER_FACES * 3, 1, 1, 0, c->stream, args, nullptr));
+    return TRGL_OK;
+}
+
+// what trgl_draw_indexed_vs and trgl_vertex_stage check alike; K of the stage comes back in *K
+static int check_vertex_call(trgl_ctx* c, const char* who, int vs, bool builtin_ok, const trgl_uniforms* u, const double* projection,
+                             const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind, int* K) {
+    const std::string w = std::string(who) + ": ";
+    if (!((builtin_ok && vs == -1) || (vs >= 0 && vs < (int)c->vertex.size()))) return fail(c, TRGL_E_INVALID, w + "unknown vertex shader");
+    *K = vs < 0 ? TRGL_VARY_PHONG : c->vertex[vs].K;
+    if (!projection || !vertices || !indices) return fail(c, TRGL_E_INVALID, w + "null argument");
+    if (vs < 0 && !u) return fail(c, TRGL_E_INVALID, w + "the built-in vertex stage needs uniforms (model_view)");
+    if (stride < (vs < 0 ? 8 : 1)) return fail(c, TRGL_E_INVALID, w + (vs < 0 ? "vertex stride must be >= 8 doubles (pos3, normal3, uv2)" : "vertex stride must be >= 1"));
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if (n_faces > 0xffffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, w + "too many faces in one call");
+    if (mem_kind == TRGL_MEM_HOST)
+        for (uint64_t k = 0; k < 3 * n_faces; ++k)
+            if (indices[k] >= n_vertices) return fail(c, TRGL_E_INVALID, w + "index out of range");
+    return TRGL_OK;
+}
+
+// What the indexed draws share once their arguments are checked (n_faces > 0): stage a host mesh, run the vertex stage of `vs` (K
+// varyings) into staged clip / vary arrays and hand those to trgl_draw.
+static int draw_indexed_checked(trgl_ctx* c, int vs, int K, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
+                                int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
+    int r;
+    const double* dv = vertices; const uint32_t* di = indices; const uint32_t* dcol = colors;
+    void* p = nullptr;
+    StageHold hold(c);
+    if (mem_kind == TRGL_MEM_HOST) {
+        if ((r = stage_copy(c, vertices, n_vertices * (size_t)stride * sizeof(double), &p))) return r;
+        dv = (const double*)p;
+        if ((r = stage_copy(c, indices, 3 * n_faces * sizeof(uint32_t), &p))) return r;
+        di = (const uint32_t*)p;
+        if (colors) { if ((r = stage_copy(c, colors, n_faces * sizeof(uint32_t), &p))) return r; dcol = (const uint32_t*)p; }
+    }
+    double* clip = nullptr; double* vary = nullptr;
+    if ((r = stage_alloc(c, n_faces * 12 * sizeof(double), &p))) return r;
+    clip = (double*)p;
+    if (K) { if ((r = stage_alloc(c, n_faces * (size_t)K * sizeof(double), &p))) return r; vary = (double*)p; }
+    if ((r = queue_vertex_stage(c, vs, u, projection, dv, stride, di, n_faces, clip, vary))) return r;
+    return trgl_draw(c, kind, u, clip, vary, dcol, n_faces, TRGL_MEM_DEVICE);
+}
+
+extern "C" {
+
+int trgl_register_shader_ex(trgl_ctx* c, const char* source, int n_varyings, uint32_t flags, int* kind) {
+    CHKCTX(c);
+    if (!kind) return fail(c, TRGL_E_INVALID, "trgl_register_shader: kind is null");
+    if (c->user.size() >= TRGL_MAX_USER_SHADERS) return fail(c, TRGL_E_INVALID, "trgl_register_shader: TRGL_MAX_USER_SHADERS already registered");
+    std::string log;
+    const std::vector<char>* code = nullptr;
+    if (int r = user_shader_code(source, n_varyings, flags, &log, &code)) return fail(c, r, "trgl_register_shader: " + log);
+    const bool may_discard = (flags & TRGL_SHADER_MAY_DISCARD) != 0;
+    UserKind u{ nullptr, nullptr, n_varyings, may_discard };
+    HIPCHK(c, hipModuleLoadData(&u.mod, code->data()));
+    const hipError_t e = hipModuleGetFunction(&u.fn, u.mod, may_discard ? USER_RASTER_KERNEL : USER_SHADE_KERNEL);
+    if (e != hipSuccess) {
+        (void)hipModuleUnload(u.mod);
+        return fail(c, TRGL_E_HIP, std::string("hipModuleGetFunction: ") + hipGetErrorString(e));
+    }
+    c->user.push_back(u);
+    *kind = TRGL_SHADER_USER_FIRST + (int)c->user.size() - 1;
+    return TRGL_OK;
+}
+
+int trgl_register_shader(trgl_ctx* c, const char* source, int n_varyings, int* kind) {
+    return trgl_register_shader_ex(c, source, n_varyings, 0u, kind);
+}
+
+int trgl_register_vertex_shader(trgl_ctx* c, const char* source, int n_varyings, int* vs) {
+    CHKCTX(c);
+    if (!vs) return fail(c, TRGL_E_INVALID, "trgl_register_vertex_shader: vs is null");
+    if (c->vertex.size() >= TRGL_MAX_USER_VERTEX_SHADERS) return fail(c, TRGL_E_INVALID, "trgl_register_vertex_shader: TRGL_MAX_USER_VERTEX_SHADERS already registered");
+    std::string log;
+    const std::vector<char>* code = nullptr;
+    if (int r = user_vertex_shader_code(source, n_varyings, &log, &code)) return fail(c, r, "trgl_register_vertex_shader: " + log);
+    UserVertex v{ nullptr, nullptr, n_varyings };
+    HIPCHK(c, hipModuleLoadData(&v.mod, code->data()));
+    const hipError_t e = hipModuleGetFunction(&v.fn, v.mod, USER_VERTEX_KERNEL);
+    if (e != hipSuccess) {
+        (void)hipModuleUnload(v.mod);
+        return fail(c, TRGL_E_HIP, std::string("hipModuleGetFunction: ") + hipGetErrorString(e));
+    }
+    c->vertex.push_back(v);
+    *vs = (int)c->vertex.size() - 1;
+    return TRGL_OK;
+}
+
+int trgl_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
+                      int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const UserKind* uk = user_kind(c, kind);
+    if (kind != TRGL_SHADER_PHONG && kind != TRGL_SHADER_EYE && !(uk && uk->K == TRGL_VARY_PHONG))     // (a user kind's varyings: the PHONG layout)
+        return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: kind must be PHONG, EYE or a user kind registered with 24 varyings");
+    if (!u || !projection || !vertices || !indices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: null argument");
+    if (stride < 8) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: vertex stride must be >= 8 doubles (pos3, normal3, uv2)");
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: bad mem_kind");
+    if (n_faces == 0) return TRGL_OK;
+    if (n_faces > 0xffffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, "trgl_draw_indexed: too many faces in one call");
+    if (mem_kind == TRGL_MEM_HOST)
+        for (uint64_t k = 0; k < 3 * n_faces; ++k)
+            if (indices[k] >= n_vertices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: index out of range");
+    return draw_indexed_checked(c, -1, TRGL_VARY_PHONG, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, nullptr, mem_kind);
+}
+
+int trgl_draw_indexed_vs(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
+                         int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    int K = 0;
+    if ((r = check_vertex_call(c, "trgl_draw_indexed_vs", vs, false, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &K))) return r;
+    // (what trgl_draw would refuse is refused before the vertex stage is queued)
+    const int kind_K = kind_vary_count(c, kind);
+    if (kind_K < 0) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed_vs: unknown shader kind");
+    if (kind_K != K) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed_vs: the shader kind and the vertex shader differ in their number of varyings");
+    if ((r = check_kind_uniforms(c, "trgl_draw_indexed_vs", kind, u))) return r;
+    if (n_faces == 0) return TRGL_OK;
+    return draw_indexed_checked(c, vs, K, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, colors, mem_kind);
+}
+
+int trgl_vertex_stage(trgl_ctx* c, int vs, const trgl_uniforms* u, const double projection[16], const double* vertices, int stride,
+                      uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, double* clip_out, double* vary_out, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    int K = 0;
+    if ((r = check_vertex_call(c, "trgl_vertex_stage", vs, true, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &K))) return r;
+    if (!clip_out || (K && !vary_out)) return fail(c, TRGL_E_INVALID, "trgl_vertex_stage: null output");
+    if (n_faces == 0) return TRGL_OK;
+    if (mem_kind == TRGL_MEM_DEVICE) {
+        if (((uintptr_t)clip_out | (K ? (uintptr_t)vary_out : 0)) & 15) return fail(c, TRGL_E_INVALID, "trgl_vertex_stage: device outputs must be 16-byte aligned");
+        return queue_vertex_stage(c, vs, u, projection, vertices, stride, indices, n_faces, clip_out, K ? vary_out : nullptr);
+    }
+    // host memory: through buffers of this call's own (nothing is left staged for a flush that may never come)
+    DevBuf<double> d_v, d_clip, d_vary; DevBuf<uint32_t> d_i;
+    if ((r = d_v.alloc(c, n_vertices * (size_t)stride)) || (r = d_i.alloc(c, 3 * n_faces)) || (r = d_clip.alloc(c, n_faces * 12)) ||
+        (K && (r = d_vary.alloc(c, n_faces * (size_t)K)))) return r;
+    HIPCHK(c, hipMemcpyAsync(d_v.p, vertices, n_vertices * (size_t)stride * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_i.p, indices, 3 * n_faces * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if ((r = queue_vertex_stage(c, vs, u, projection, d_v.p, stride, d_i.p, n_faces, d_clip.p, d_vary.p))) return r;
+    HIPCHK(c, hipMemcpyAsync(clip_out, d_clip.p, n_faces * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (K) HIPCHK(c, hipMemcpyAsync(vary_out, d_vary.p, n_faces * (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRGL_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// user_shaders.h — run-time compilation of user shaders (user_shaders.cpp) for the context code of trgl_api.cpp.
+// user_shaders.h — run-time compilation of user shaders (user_shaders.cpp) for the registration code of trgl_shader.cpp.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -14,7 +14,7 @@ int user_shader_code(const char* source, int n_varyings, uint32_t flags, std::st
 // The same for a user vertex shader (vertex_user.h behind the source, which defines trgl_vertex); its cache entries are apart from
 // those of fragment shaders with the same text.
 int user_vertex_shader_code(const char* source, int n_varyings, std::string* log, const std::vector<char>** code);
-// the message trgl_last_error(NULL) returns (trgl_api.cpp)
+// the message trgl_last_error(NULL) returns (trgl_host.cpp)
 void set_global_error(const std::string& msg);
 // the name of the kernel in that code object: shade_user.h, or raster_user.h with TRGL_SHADER_MAY_DISCARD
 constexpr const char* USER_SHADE_KERNEL = "trgl_shade_user";
