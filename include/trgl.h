@@ -328,6 +328,75 @@ int trgl_vertex_stage(trgl_ctx* ctx, int vs, const trgl_uniforms* uniforms, cons
                       const double* vertices, int vertex_stride, uint64_t n_vertices,
                       const uint32_t* indices, uint64_t n_faces, double* clip_out, double* vary_out, int mem_kind);
 
+/* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
+
+/* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and
+ * rejects by depth only when all three vertices are out of range (our_gl.cpp:103-106), so with the camera inside a mesh (main.cpp:587-594)
+ * faces that pass the eye plane vanish and faces in front of the near plane are drawn.  This stage cuts a triangle list against one plane
+ * before it reaches rasterize(); it is opt-in, and a caller that does not ask for it gets exactly what it got before.
+ *
+ * The operation is one pure function; the host path, the device path and the tests' numpy model compute it identically, in fp64 without
+ * contraction or reassociation.  Inputs: n triangles - clip (12 doubles each), vary (K doubles each; null when K = 0), colors (one
+ * uint32 each, or null) - a plane p[4] and a list of attributes.
+ *   Signed distance of a vertex (x, y, z, w): d = ((p0*x + p1*y) + p2*z) + p3*w; inside when d >= 0, so -0.0 is inside.  The near plane
+ *   of the reference's projection is (0, 0, 1, 1).
+ *   Attributes: {offset, components} names 3 * components consecutive varyings, vertex-major - vertex s owns
+ *   vary[offset + s * components .. + components), the memory image of `vecC varying_x[3]`.  Slots that no attribute names are
+ *   per-triangle constants and are copied.  A list is valid when every offset >= 0, components >= 1, offset + 3 * components <= K, no
+ *   two attributes overlap and there are at most TRGL_MAX_CLIP_ATTRS of them; anything else is TRGL_E_INVALID.  Built-in layouts
+ *   (trgl_clip_layout): FLAT and CHECKER none, GOURAUD {0,1}, PHONG and EYE {0,2}, {6,3}, {15,3}.
+ *   Classification: some d not finite - copied through unchanged (rasterize() then decides as it does today, our_gl.cpp:108-114); all
+ *   three inside - copied through unchanged, every bit; none inside - dropped; otherwise cut.
+ *   Intersection of an inside vertex a with an outside vertex b: t = da / (da - db), and each of the 4 clip components and each attribute
+ *   component is a + t * (b - a) - always from the inside vertex toward the outside one, so two triangles that share an edge produce
+ *   the same bits there and a clipped mesh stays watertight.
+ *   Output slots: (i, j, k) is the rotation of (0, 1, 2) that puts the odd vertex at i; slots keep their positions (the winding stays).
+ *     one inside (i):            one output:  slot i = V_i,    slot j = P(i->j), slot k = P(i->k)
+ *     two inside (j, k; i out):  two outputs, adjacent, in this order:
+ *                                first:       slot i = P(j->i), slot j = V_j,     slot k = V_k
+ *                                second:      slot i = P(k->i), slot j = P(j->i), slot k = V_k
+ *   Outputs appear in input order (submission order is observable, our_gl.cpp:165); constant slots and the colour go to every output.
+ * Consequences a caller sees:
+ *   - the counters count what reaches rasterize() (our_gl.cpp:90): a dropped triangle is not in triangles_rasterized, a split one twice;
+ *   - for CHECKER and user shaders the barycentrics a fragment receives are those of the OUTPUT triangle;
+ *   - TRGL_MEM_DEVICE inputs are read at call time (when the stage runs on the context's stream, queued by the call), not at the flush:
+ *     they must be complete on that stream by then, and may be overwritten once the call has returned and the stream has passed it. */
+#define TRGL_MAX_CLIP_ATTRS 24
+typedef struct trgl_clip_attr { int32_t offset, components; } trgl_clip_attr;
+
+/* The built-in layout of a kind (TRGL_SHADER_FLAT .. TRGL_SHADER_CHECKER): attrs (room for TRGL_MAX_CLIP_ATTRS; may be NULL to ask for the
+ * count alone) and *n_attrs.  TRGL_E_INVALID for any other kind or a null n_attrs.  Host only, needs no context. */
+int trgl_clip_layout(int builtin_kind, trgl_clip_attr* attrs, int* n_attrs);
+
+/* The stage alone.  clip_out / vary_out / colors_out have room for 2 * n triangles (vary_out may be NULL when K = 0, colors_out when colors
+ * is NULL); *n_out (host memory) receives the number of output triangles, and nothing outside the first *n_out output triangles is
+ * written.  K in 0..TRGL_MAX_USER_VARY.  One mem_kind covers all six arrays; inputs and outputs must not overlap.
+ * TRGL_MEM_HOST: plain C++, ctx may be NULL, no GPU is touched.  TRGL_MEM_DEVICE: needs a context; natural alignment suffices (8 bytes
+ * for doubles, 4 for colours); the kernels are queued on the context's stream in order with everything else (a classify-and-count pass,
+ * an order-preserving scan in two levels, a scatter pass), nothing is flushed, and the call waits for the stream to fill *n_out (one stream
+ * sync, like trgl_mesh_bounds).  TRGL_E_UNSUPPORTED: n >= 2^31 in device memory. */
+int trgl_clip_stage(trgl_ctx* ctx, const double plane[4], const trgl_clip_attr* attrs, int n_attrs, int K,
+                    const double* clip, const double* vary, const uint32_t* colors, uint64_t n,
+                    double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out, int mem_kind);
+
+/* trgl_draw of the clipped list: arguments and checks are trgl_draw's, plus the plane and the attribute list; n_attrs = -1 selects the
+ * kind's built-in layout (for a user kind with K > 0 that is TRGL_E_INVALID: only its author knows which varyings belong to vertices).
+ * Host arrays are clipped in C++ and drawn as host arrays.  Device arrays are clipped on the stream into buffers the context owns until the
+ * flush is done, and drawn from there with TRGL_MEM_DEVICE - the 2^24 cut and the flush rules are trgl_draw's.
+ * SYNCHRONISATION: this call waits for the context's stream once, at draw time, to learn the 8-byte count of output triangles (the draw
+ * that is queued needs it on the host); it does not flush, and no flush waits on its account.  An empty result queues nothing. */
+int trgl_draw_clipped(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms, const double plane[4],
+                      const trgl_clip_attr* attrs, int n_attrs,
+                      const double* clip, const double* varyings, const uint32_t* colors, uint64_t n, int mem_kind);
+
+/* trgl_draw_indexed (vs = -1: the built-in vertex stage; colors as for trgl_draw_indexed_vs) or trgl_draw_indexed_vs (vs >= 0) with the
+ * clip stage between the vertex stage and the draw: checks are those of the call it stands for, the attribute list and the one wait are
+ * trgl_draw_clipped's.  Vertex stage and clip stage run on the stream back to back; the faces never leave HBM. */
+int trgl_draw_indexed_vs_clipped(trgl_ctx* ctx, int vs, int shader_kind, const trgl_uniforms* uniforms, const double projection[16],
+                                 const double plane[4], const trgl_clip_attr* attrs, int n_attrs,
+                                 const double* vertices, int vertex_stride, uint64_t n_vertices,
+                                 const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind);
+
 /* Execute everything submitted so far (asynchronously on the context's stream). */
 int trgl_flush(trgl_ctx* ctx);
 /* The same in two halves, for a caller that overlaps something with the first one: trgl_flush_begin runs per-triangle

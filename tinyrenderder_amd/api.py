@@ -26,6 +26,8 @@ MAX_TEXTURES = 16
 MAX_Z_SNAPSHOTS = 4           # TRGL_MAX_Z_SNAPSHOTS
 MAX_BLUR_RADIUS = 46340       # TRGL_MAX_BLUR_RADIUS
 MAX_PCF_RADIUS = 4            # TRGL_MAX_PCF_RADIUS
+MAX_CLIP_ATTRS = 24           # TRGL_MAX_CLIP_ATTRS
+NEAR_PLANE = (0.0, 0.0, 1.0, 1.0)     # the near plane of the reference's projection in clip space: z + w >= 0
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
 
 # every symbol include/trgl.h declares (tests check the library exports all of them)
@@ -45,6 +47,7 @@ SYMBOLS = [
     "trgl_mesh_normals", "trgl_mesh_tangents",
     "trgl_gaussian_kernel", "trgl_image_blur", "trgl_image_scale", "trgl_framebuffer_blur",
     "trgl_shadow_matrix", "trgl_shadow_mask_image", "trgl_shadow_mask", "trgl_image_modulate", "trgl_framebuffer_modulate",
+    "trgl_clip_layout", "trgl_clip_stage", "trgl_draw_clipped", "trgl_draw_indexed_vs_clipped",
 ]
 
 
@@ -79,6 +82,11 @@ class ShadowParams(C.Structure):
     """trgl_shadow_params"""
     _fields_ = [("screen_to_light", C.c_double * 16), ("bias", C.c_double), ("darkness", C.c_double),
                 ("pcf_radius", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ClipAttr(C.Structure):
+    """trgl_clip_attr"""
+    _fields_ = [("offset", C.c_int32), ("components", C.c_int32)]
 
 
 def make_shadow_params(screen_to_light, bias=1e-3, darkness=0.5, pcf_radius=0) -> ShadowParams:
@@ -219,6 +227,13 @@ def load_library(path: str = None):
     L.trgl_shadow_mask.argtypes = [vp, C.POINTER(ShadowParams), C.c_int, C.c_void_p, C.c_int]
     L.trgl_image_modulate.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     L.trgl_framebuffer_modulate.argtypes = [vp, C.c_void_p, C.c_int]
+    cap = C.POINTER(ClipAttr)
+    L.trgl_clip_layout.argtypes = [C.c_int, cap, C.POINTER(C.c_int)]
+    L.trgl_clip_stage.argtypes = [vp, dp, cap, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.c_int]
+    L.trgl_draw_clipped.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, cap, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+    L.trgl_draw_indexed_vs_clipped.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Uniforms), dp, dp, cap, C.c_int, C.c_void_p, C.c_int, C.c_uint64,
+                                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -481,6 +496,57 @@ def image_modulate(img, mask) -> np.ndarray:
     return _host_image_modulate(load_library(), None, img, mask)
 
 
+def clip_layout(kind: int):
+    """trgl_clip_layout: the built-in clip attribute layout of a built-in kind as a list of (offset, components).  Needs no GPU."""
+    L = load_library()
+    attrs, n = (ClipAttr * MAX_CLIP_ATTRS)(), C.c_int(0)
+    rc = L.trgl_clip_layout(int(kind), attrs, C.byref(n))
+    if rc != 0:
+        raise TrglError(f"trgl_clip_layout failed ({rc}): {L.trgl_last_error(None).decode()}")
+    return [(attrs[i].offset, attrs[i].components) for i in range(n.value)]
+
+
+def _clip_attrs(attrs):
+    """(ctypes array or None, count) of a list of (offset, components); None stands for the kind's built-in layout (-1)."""
+    if attrs is None:
+        return None, -1
+    attrs = [(int(o), int(k)) for o, k in attrs]
+    arr = (ClipAttr * max(len(attrs), 1))()
+    for i, (o, k) in enumerate(attrs):
+        arr[i].offset, arr[i].components = o, k
+    return arr, len(attrs)
+
+
+def _clip_stage(L, handle, plane, attrs, K, ptrs, n, optrs, device):
+    arr, na = _clip_attrs([] if attrs is None else attrs)
+    n_out = C.c_uint64(0)
+    rc = L.trgl_clip_stage(handle, _dp(_f64(plane, 4, "plane")), arr, na, int(K), ptrs[0], ptrs[1], ptrs[2], int(n),
+                           optrs[0], optrs[1], optrs[2], C.byref(n_out), MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_clip_stage failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return int(n_out.value)
+
+
+def _host_clip_stage(L, handle, plane, attrs, clip, varyings, colors):
+    clip = np.ascontiguousarray(clip, np.float64).reshape(-1, 12)
+    n = clip.shape[0]
+    vary = None if varyings is None else np.ascontiguousarray(varyings, np.float64).reshape(n, np.shape(varyings)[-1] if np.ndim(varyings) == 2 else -1)
+    K = 0 if vary is None else vary.shape[1]
+    col = None if colors is None else np.ascontiguousarray(colors, np.uint32).reshape(n)
+    oclip, ovary = np.empty((2 * n, 12), np.float64), np.empty((2 * n, K), np.float64)
+    ocol = None if col is None else np.empty(2 * n, np.uint32)
+    m = _clip_stage(L, handle, plane, attrs, K, (_ptr(clip), _ptr(vary) if K else None, _ptr(col)), n,
+                    (_ptr(oclip), _ptr(ovary) if K else None, _ptr(ocol)), False)
+    return oclip[:m].copy(), (ovary[:m].copy() if K else None), (None if ocol is None else ocol[:m].copy())
+
+
+def clip_stage(plane, clip, varyings=None, colors=None, attrs=None):
+    """trgl_clip_stage for host arrays without a context (include/trgl.h writes the operation down): clip [n, 12], varyings [n, K] or
+    None, colors [n] or None, attrs a list of (offset, components) (None: no attributes, every varying is a per-triangle constant).
+    Returns (clip, varyings, colors) of the output triangles.  Needs no GPU."""
+    return _host_clip_stage(load_library(), None, plane, attrs, clip, varyings, colors)
+
+
 def aabb_transform(bmin, bmax, m):
     """trgl_aabb_transform: AABB::transform (geometry.h:297-327) of the box by the row-major 4x4 m; returns (min[3], max[3])."""
     lo, hi = np.empty(3, np.float64), np.empty(3, np.float64)
@@ -632,8 +698,10 @@ class Context:
         self._user_vary[kind.value] = int(n_varyings)
         return kind.value
 
-    def draw(self, kind, clip, varyings=None, colors=None, uniforms=None, n=None, device=False):
-        """Host arrays (numpy) are copied before return; with device=True pass torch CUDA tensors (or raw
+    def draw(self, kind, clip, varyings=None, colors=None, uniforms=None, n=None, device=False, clip_plane=None, clip_attrs=None):
+        """clip_plane: four doubles - the list is cut against that plane first (trgl_draw_clipped; the call waits for the stream once, for
+        the count of output triangles), with clip_attrs a list of (offset, components) or None for the kind's built-in layout.
+        Host arrays (numpy) are copied before return; with device=True pass torch CUDA tensors (or raw
         pointers with n) that stay alive until the flush has completed: every array of such a draw, a host array
         among them is a TypeError (_device_ptr).  include/trgl.h, TRGL_MEM_DEVICE: alignment and stream ordering."""
         # (a kind in the user range that was not registered here goes to the library, which refuses it)
@@ -655,8 +723,33 @@ class Context:
             assert n is not None or hasattr(clip, "shape")
             n = clip.shape[0] if n is None else n
             self._keep.append((clip, varyings, colors))
+        if clip_plane is not None:
+            arr, na = _clip_attrs(clip_attrs)
+            self._chk(self.L.trgl_draw_clipped(self.h, kind, None if uniforms is None else C.byref(uniforms), _dp(_f64(clip_plane, 4, "clip_plane")),
+                                               arr, na, ptrs[0], ptrs[1], ptrs[2], int(n), MEM_DEVICE if device else MEM_HOST))
+            return
+        assert clip_attrs is None, "clip_attrs: only with clip_plane="
         self._chk(self.L.trgl_draw(self.h, kind, None if uniforms is None else C.byref(uniforms), ptrs[0], ptrs[1], ptrs[2], int(n),
                                    MEM_DEVICE if device else MEM_HOST))
+
+    def clip_stage(self, plane, clip, varyings=None, colors=None, attrs=None, device=False, out=None):
+        """trgl_clip_stage.  Host arrays: as the module's clip_stage.  device=True: clip [n, 12] f64, varyings [n, K] f64 or None and
+        colors [n] (32-bit) or None are device tensors, out = (clip_out, varyings_out, colors_out) device tensors with room for 2 n
+        triangles (allocated with torch when not given); the stage runs on the context's stream and the call waits for the count.
+        Returns (clip_out, varyings_out, colors_out, n_out) - only the first n_out triangles of the outputs were written."""
+        if not device:
+            return _host_clip_stage(self.L, self.h, plane, attrs, clip, varyings, colors)
+        n = int(clip.shape[0])
+        K = 0 if varyings is None else int(varyings.shape[1])
+        if out is None:
+            import torch
+            out = (torch.empty((2 * n, 12), dtype=torch.float64, device=clip.device),
+                   None if varyings is None else torch.empty((2 * n, K), dtype=torch.float64, device=clip.device),
+                   None if colors is None else torch.empty(2 * n, dtype=colors.dtype, device=clip.device))
+        ptrs = (_device_ptr(clip, "clip"), _device_ptr(varyings, "varyings"), _device_ptr(colors, "colors"))
+        optrs = (_device_ptr(out[0], "clip_out"), _device_ptr(out[1], "varyings_out"), _device_ptr(out[2], "colors_out"))
+        m = _clip_stage(self.L, self.h, plane, attrs, K, ptrs, n, optrs, True)
+        return out[0], out[1], out[2], m
 
     def register_vertex_shader(self, source: str, n_varyings: int) -> int:
         """trgl_register_vertex_shader: compile (or take from the process cache) a user vertex shader and load it on this context;
@@ -678,12 +771,26 @@ class Context:
             return vertices, indices, colors, (_ptr(vertices), _ptr(indices), _ptr(colors))
         return vertices, indices, colors, (_device_ptr(vertices, "vertices"), _device_ptr(indices, "indices"), _device_ptr(colors, "colors"))
 
-    def draw_indexed(self, kind, uniforms, projection, vertices, indices, device=False, vertex_shader=None, colors=None):
-        """Vertex stage on the device (main.cpp:71-90) + draw.  vertices [nv, stride>=8] f64, indices [nf,3] u32.
+    def draw_indexed(self, kind, uniforms, projection, vertices, indices, device=False, vertex_shader=None, colors=None,
+                     clip_plane=None, clip_attrs=None):
+        """clip_plane / clip_attrs: as for draw() - the faces are cut between the vertex stage and the draw (trgl_draw_indexed_vs_clipped).
+        Vertex stage on the device (main.cpp:71-90) + draw.  vertices [nv, stride>=8] f64, indices [nf,3] u32.
         vertex_shader: a number from register_vertex_shader - its trgl_vertex runs in place of the built-in stage
         (trgl_draw_indexed_vs): any `kind` with the vertex shader's K, vertices [nv, stride>=1] in the layout the shader reads,
         uniforms None where draw() allows it, colors [nf] u32 per face or None."""
         pj = np.ascontiguousarray(projection, np.float64).reshape(16)
+        if clip_plane is not None:
+            assert vertex_shader is not None or colors is None, "colors: only with vertex_shader="
+            vertices, indices, colors, ptrs = self._mesh_ptrs(vertices, indices, colors, device)
+            if device:
+                self._keep.append((vertices, indices, colors))
+            arr, na = _clip_attrs(clip_attrs)
+            self._chk(self.L.trgl_draw_indexed_vs_clipped(
+                self.h, -1 if vertex_shader is None else int(vertex_shader), kind, None if uniforms is None else C.byref(uniforms), _dp(pj),
+                _dp(_f64(clip_plane, 4, "clip_plane")), arr, na, ptrs[0], vertices.shape[1], vertices.shape[0], ptrs[1], indices.shape[0], ptrs[2],
+                MEM_DEVICE if device else MEM_HOST))
+            return
+        assert clip_attrs is None, "clip_attrs: only with clip_plane="
         if vertex_shader is not None:
             vertices, indices, colors, ptrs = self._mesh_ptrs(vertices, indices, colors, device)
             if device:

@@ -1,8 +1,10 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_raster.hip, kernels_post.hip, kernels_mesh.hip,
-// kernels_image.hip, kernels_shadow.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex stage) and trgl_passes.cpp (the rest).
+// kernels_image.hip, kernels_shadow.hip, kernels_clip.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"
+#include "clip_core.h"
 
 namespace trgl {
 
@@ -119,6 +121,23 @@ void launch_shadow_mask(hipStream_t s, const ShadowArgs& a);
 // px[c] = (unsigned char)std::min(255.0, px[c] * (mask / 255.0)) for the colour channels c < min(bpp, 3) of npixels pixels, in place
 // (main.cpp:775-781); pixels and mask at any address, not overlapping.  npixels * bpp in 1..INT_MAX, bpp in {1, 3, 4}.
 void launch_modulate(hipStream_t s, uint8_t* pixels, uint64_t npixels, int bpp, const uint8_t* mask);
+
+// The clip stage (kernels_clip.hip; the operation is written down at trgl_clip_stage in include/trgl.h, its arithmetic is clip_core.h's).
+// clip / vary / colors: n triangles (vary unused when K = 0, colors may be null - colors_out is then not written); the outputs have room
+// for 2 n triangles; doubles 8-byte aligned, colours 4.  n < 2^31, K <= TRGL_MAX_USER_VARY.  The struct travels as the kernels' argument.
+struct ClipArgs {
+    double plane[4];
+    const double* clip; const double* vary; const uint32_t* colors;
+    double* clip_out; double* vary_out; uint32_t* colors_out;
+    uint64_t n; int32_t K;
+    ClipTable tab;
+};
+constexpr int CLIP_BLOCK_TRIS = 256;         // triangles of a block of k_clip_count / k_clip_scatter, one per lane
+constexpr int CLIP_SCAN_CHUNK = 256;         // block sums a block of the scan's lower level takes; more of them need its upper level
+uint32_t clip_num_blocks(uint64_t n);
+size_t clip_scratch_words(uint64_t n);       // the block sums and, behind them, the sums of the scan's chunks
+// scratch: clip_scratch_words(n) words; *total receives the number of output triangles.  Four launches, in order on `s`.
+void launch_clip_stage(hipStream_t s, const ClipArgs& a, uint32_t* scratch, unsigned long long* total);
 
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,

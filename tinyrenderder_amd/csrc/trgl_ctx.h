@@ -85,6 +85,7 @@ struct trgl_ctx {
     // The weights travel through blur_w_pinned; ev_blur_w is recorded behind that copy, so that the next upload knows when it may rewrite it
     DevBuf<float> blur_weights; DevBuf<uint8_t> blur_tmp; int blur_radius = 0;
     float* blur_w_pinned = nullptr; size_t blur_w_pinned_cap = 0; hipEvent_t ev_blur_w = nullptr;
+    DevBuf<uint32_t> clip_scratch;      // trgl_clip_stage and the clipped draws: the 8-byte count of outputs, then the words of the stage's scan; grows on demand
     DevBuf<uint8_t> shadow_tmp;         // trgl_shadow_mask / trgl_framebuffer_modulate with a host mask: the W * H bytes on their way; grows on demand
     DevBuf<uint8_t> pp_out;             // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
@@ -171,4 +172,7 @@ const char* global_error();                 // what trgl_last_error(NULL) return
 void host_mesh_bounds(const double* vertices, int stride, uint64_t n, double out_min[3], double out_max[3]);      // n > 0
 // normals (or tangents) of an indexed mesh in place, where a vertex lacks them: 1 generated, 0 left alone, -1 an index out of range
 int host_mesh_attr(bool tangents, double* vertices, int stride, uint64_t n, const uint32_t* indices, uint64_t nfaces);
+// the clip stage over host arrays (outputs with room for 2 n triangles); returns the number of output triangles
+uint64_t host_clip_stage(const double plane[4], const ClipTable& tab, int K, const double* clip, const double* vary, const uint32_t* colors,
+                         uint64_t n, double* clip_out, double* vary_out, uint32_t* colors_out);
 }  // namespace trgl

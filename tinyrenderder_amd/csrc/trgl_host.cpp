@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/trgl.h"
+#include "clip_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -117,6 +118,24 @@ int host_mesh_attr(bool tangents, double* vertices, int stride, uint64_t n, cons
     else host_mesh_normals(vertices, (uint64_t)stride, n, indices, nfaces);
     return 1;
 }
+
+// ---- the clip stage in host memory (include/trgl.h, trgl_clip_stage; the arithmetic is clip_core.h's) -------------------------------
+uint64_t host_clip_stage(const double plane[4], const ClipTable& tab, int K, const double* clip, const double* vary, const uint32_t* colors,
+                         uint64_t n, double* clip_out, double* vary_out, uint32_t* colors_out) {
+    uint64_t o = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const double* tri = clip + i * 12;
+        const double* vin = K ? vary + i * (uint64_t)K : nullptr;
+        double t[2];
+        const int code = clip_classify(tri, plane, t);
+        for (int which = 0; which < clip_outputs(code); ++which, ++o) {
+            clip_emit_clip(tri, code, which, t, clip_out + o * 12);
+            for (int c = 0; c < K; ++c) vary_out[o * (uint64_t)K + c] = clip_emit_vary(vin, c, tab.slot[c], code, which, t);
+            if (colors) colors_out[o] = colors[i];
+        }
+    }
+    return o;
+}
 }  // namespace trgl
 using namespace trgl;
 
@@ -184,6 +203,22 @@ int trgl_frustum_intersects(const double planes[24], const double bmin[3], const
         if (dot3_from_zero(pl, positive[0], positive[1], positive[2]) + pl[3] < 0) return 0;   // :275, Plane::distance
     }
     return 1;
+}
+
+int trgl_clip_layout(int kind, trgl_clip_attr* attrs, int* n_attrs) {
+    static const trgl_clip_attr gouraud[] = { { 0, 1 } };
+    static const trgl_clip_attr phong[] = { { 0, 2 }, { 6, 3 }, { 15, 3 } };      // uv[3], position_eye[3], normal_eye[3] (main.cpp:47-49)
+    if (!n_attrs) return fail(nullptr, TRGL_E_INVALID, "trgl_clip_layout: n_attrs is null");
+    const trgl_clip_attr* src = nullptr; int n = 0;
+    switch (kind) {
+    case TRGL_SHADER_FLAT: case TRGL_SHADER_CHECKER: break;
+    case TRGL_SHADER_GOURAUD: src = gouraud; n = 1; break;
+    case TRGL_SHADER_PHONG: case TRGL_SHADER_EYE: src = phong; n = 3; break;
+    default: return fail(nullptr, TRGL_E_INVALID, "trgl_clip_layout: not a built-in shader kind");
+    }
+    for (int a = 0; attrs && a < n; ++a) attrs[a] = src[a];
+    *n_attrs = n;
+    return TRGL_OK;
 }
 
 int trgl_gaussian_kernel(int radius, float* weights) {      // TGAImage::gaussian_blur's weights (tgaimage.cpp:271-324)

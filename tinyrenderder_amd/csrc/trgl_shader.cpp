@@ -1,7 +1,9 @@
 // trgl_shader.cpp — run-time shader registration (fragment kinds and vertex shaders, compiled by user_shaders.cpp) and the entry points
-// that run a vertex stage over an indexed mesh: trgl_draw_indexed, trgl_draw_indexed_vs, trgl_vertex_stage.  The draws they make go
-// through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
+// that run a stage in front of a draw: the vertex stage over an indexed mesh (trgl_draw_indexed, trgl_draw_indexed_vs, trgl_vertex_stage)
+// and the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped).  The draws they make go through trgl_draw
+// (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <cstring>
+#include <new>
 
 #include "trgl_ctx.h"
 #include "user_shaders.h"
@@ -42,11 +44,72 @@ static int check_vertex_call(trgl_ctx* c, const char* who, int vs, bool builtin_
     return TRGL_OK;
 }
 
-// What the indexed draws share once their arguments are checked (n_faces > 0): stage a host mesh, run the vertex stage of `vs` (K
-// varyings) into staged clip / vary arrays and hand those to trgl_draw.
-static int draw_indexed_checked(trgl_ctx* c, int vs, int K, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
-                                int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
+// A plane and an attribute list as the clipped draws take them; null plane: no clipping
+struct ClipSpec { const double* plane; const trgl_clip_attr* attrs; int n_attrs; };
+
+// the table of `spec` for a draw of `kind` with K varyings; n_attrs = -1: the kind's built-in layout
+static int clip_spec_table(trgl_ctx* c, const char* who, const ClipSpec& spec, int kind, int K, ClipTable* tab) {
+    const std::string w = std::string(who) + ": ";
+    if (!spec.plane) return fail(c, TRGL_E_INVALID, w + "plane is null");
+    trgl_clip_attr builtin[TRGL_MAX_CLIP_ATTRS];
+    const trgl_clip_attr* attrs = spec.attrs; int n_attrs = spec.n_attrs;
+    if (n_attrs == -1) {
+        attrs = builtin; n_attrs = 0;
+        if (kind >= 0 && kind < TRGL_NUM_SHADERS) (void)trgl_clip_layout(kind, builtin, &n_attrs);
+        else if (K > 0) return fail(c, TRGL_E_INVALID, w + "a user kind with varyings has no built-in clip layout: pass its attributes");
+    }
+    if (!clip_table(attrs, n_attrs, K, tab)) return fail(c, TRGL_E_INVALID, w + "invalid clip attribute list");
+    return TRGL_OK;
+}
+
+// The clip stage over device arrays, queued on the context's stream; *n_out is complete when the stream has been waited for.
+static int queue_clip_stage(trgl_ctx* c, const double plane[4], const ClipTable& tab, int K, const double* clip, const double* vary,
+                            const uint32_t* colors, uint64_t n, double* clip_out, double* vary_out, uint32_t* colors_out, unsigned long long* n_out) {
     int r;
+    if ((r = c->clip_scratch.grow(c, 2 + clip_scratch_words(n)))) return r;
+    ClipArgs a; std::memset(&a, 0, sizeof(a));
+    std::memcpy(a.plane, plane, sizeof(a.plane));
+    a.clip = clip; a.vary = K ? vary : nullptr; a.colors = colors;
+    a.clip_out = clip_out; a.vary_out = K ? vary_out : nullptr; a.colors_out = colors ? colors_out : nullptr;
+    a.n = n; a.K = K; a.tab = tab;
+    unsigned long long* total = reinterpret_cast<unsigned long long*>(c->clip_scratch.p);
+    launch_clip_stage(c->stream, a, c->clip_scratch.p + 2, total);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(n_out, total, sizeof(*n_out), hipMemcpyDeviceToHost, c->stream));
+    return TRGL_OK;
+}
+
+// trgl_draw of device arrays, through the clip stage when `spec` has a plane (checked: tab is spec's table).  The arrays are read when the
+// stage runs; its outputs are staged, under the caller's StageHold.
+static int draw_device_clipped(trgl_ctx* c, int kind, int K, const trgl_uniforms* u, const ClipSpec* spec, const ClipTable& tab,
+                               const double* clip, const double* vary, const uint32_t* colors, uint64_t n) {
+    if (!spec) return trgl_draw(c, kind, u, clip, vary, colors, n, TRGL_MEM_DEVICE);
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "clip stage: 2^31 or more triangles in one call");
+    int r; void* p = nullptr;
+    double* oclip = nullptr; double* ovary = nullptr; uint32_t* ocol = nullptr;
+    if ((r = stage_alloc(c, 2 * n * 12 * sizeof(double), &p))) return r;
+    oclip = (double*)p;
+    if (K) { if ((r = stage_alloc(c, 2 * n * (size_t)K * sizeof(double), &p))) return r; ovary = (double*)p; }
+    if (colors) { if ((r = stage_alloc(c, 2 * n * sizeof(uint32_t), &p))) return r; ocol = (uint32_t*)p; }
+    unsigned long long n_out = 0;
+    if ((r = queue_clip_stage(c, spec->plane, tab, K, clip, vary, colors, n, oclip, ovary, ocol, &n_out))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait of a clipped draw: the queue needs the count on the host
+    if (n_out == 0) {
+        // nothing is queued; with no draw waiting for a flush either, nobody refers to the staged arrays (the stream has just been waited for)
+        if (c->draws.empty() && c->stage_hold == 1) for (auto& ch : c->stage) ch.used = 0;
+        return TRGL_OK;
+    }
+    return trgl_draw(c, kind, u, oclip, ovary, ocol, n_out, TRGL_MEM_DEVICE);
+}
+
+// What the indexed draws share once their arguments are checked (n_faces > 0): stage a host mesh, run the vertex stage of `vs` (K
+// varyings) into staged clip / vary arrays and hand those to trgl_draw - through the clip stage when `spec` is given.
+static int draw_indexed_checked(trgl_ctx* c, int vs, int K, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
+                                int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind,
+                                const ClipSpec* spec = nullptr) {
+    int r;
+    ClipTable tab;
+    if (spec && (r = clip_spec_table(c, "trgl_draw_indexed_vs_clipped", *spec, kind, K, &tab))) return r;
     const double* dv = vertices; const uint32_t* di = indices; const uint32_t* dcol = colors;
     void* p = nullptr;
     StageHold hold(c);
@@ -62,7 +125,41 @@ static int draw_indexed_checked(trgl_ctx* c, int vs, int K, int kind, const trgl
     clip = (double*)p;
     if (K) { if ((r = stage_alloc(c, n_faces * (size_t)K * sizeof(double), &p))) return r; vary = (double*)p; }
     if ((r = queue_vertex_stage(c, vs, u, projection, dv, stride, di, n_faces, clip, vary))) return r;
-    return trgl_draw(c, kind, u, clip, vary, dcol, n_faces, TRGL_MEM_DEVICE);
+    return draw_device_clipped(c, kind, K, u, spec, tab, clip, vary, dcol, n_faces);
+}
+
+// the checks of trgl_draw_indexed; *go: there is something to draw
+static int check_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* projection, const double* vertices, int stride,
+                              uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind, bool* go) {
+    *go = false;
+    const UserKind* uk = user_kind(c, kind);
+    if (kind != TRGL_SHADER_PHONG && kind != TRGL_SHADER_EYE && !(uk && uk->K == TRGL_VARY_PHONG))     // (a user kind's varyings: the PHONG layout)
+        return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: kind must be PHONG, EYE or a user kind registered with 24 varyings");
+    if (!u || !projection || !vertices || !indices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: null argument");
+    if (stride < 8) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: vertex stride must be >= 8 doubles (pos3, normal3, uv2)");
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: bad mem_kind");
+    if (n_faces == 0) return TRGL_OK;
+    if (n_faces > 0xffffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, "trgl_draw_indexed: too many faces in one call");
+    if (mem_kind == TRGL_MEM_HOST)
+        for (uint64_t k = 0; k < 3 * n_faces; ++k)
+            if (indices[k] >= n_vertices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: index out of range");
+    *go = true;
+    return TRGL_OK;
+}
+
+// the checks of trgl_draw_indexed_vs; K of the stage comes back in *K
+static int check_draw_indexed_vs(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double* projection, const double* vertices, int stride,
+                                 uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind, int* K, bool* go) {
+    *go = false;
+    int r;
+    if ((r = check_vertex_call(c, "trgl_draw_indexed_vs", vs, false, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, K))) return r;
+    // (what trgl_draw would refuse is refused before the vertex stage is queued)
+    const int kind_K = kind_vary_count(c, kind);
+    if (kind_K < 0) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed_vs: unknown shader kind");
+    if (kind_K != *K) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed_vs: the shader kind and the vertex shader differ in their number of varyings");
+    if ((r = check_kind_uniforms(c, "trgl_draw_indexed_vs", kind, u))) return r;
+    *go = n_faces != 0;
+    return TRGL_OK;
 }
 
 extern "C" {
@@ -114,17 +211,8 @@ int trgl_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const doubl
                       int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind) {
     CHKCTX(c);
     int r = end_pending_raster(c); if (r) return r;
-    const UserKind* uk = user_kind(c, kind);
-    if (kind != TRGL_SHADER_PHONG && kind != TRGL_SHADER_EYE && !(uk && uk->K == TRGL_VARY_PHONG))     // (a user kind's varyings: the PHONG layout)
-        return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: kind must be PHONG, EYE or a user kind registered with 24 varyings");
-    if (!u || !projection || !vertices || !indices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: null argument");
-    if (stride < 8) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: vertex stride must be >= 8 doubles (pos3, normal3, uv2)");
-    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: bad mem_kind");
-    if (n_faces == 0) return TRGL_OK;
-    if (n_faces > 0xffffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, "trgl_draw_indexed: too many faces in one call");
-    if (mem_kind == TRGL_MEM_HOST)
-        for (uint64_t k = 0; k < 3 * n_faces; ++k)
-            if (indices[k] >= n_vertices) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed: index out of range");
+    bool go;
+    if ((r = check_draw_indexed(c, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &go)) || !go) return r;
     return draw_indexed_checked(c, -1, TRGL_VARY_PHONG, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, nullptr, mem_kind);
 }
 
@@ -132,15 +220,76 @@ int trgl_draw_indexed_vs(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, 
                          int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
     CHKCTX(c);
     int r = end_pending_raster(c); if (r) return r;
-    int K = 0;
-    if ((r = check_vertex_call(c, "trgl_draw_indexed_vs", vs, false, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &K))) return r;
-    // (what trgl_draw would refuse is refused before the vertex stage is queued)
-    const int kind_K = kind_vary_count(c, kind);
-    if (kind_K < 0) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed_vs: unknown shader kind");
-    if (kind_K != K) return fail(c, TRGL_E_INVALID, "trgl_draw_indexed_vs: the shader kind and the vertex shader differ in their number of varyings");
-    if ((r = check_kind_uniforms(c, "trgl_draw_indexed_vs", kind, u))) return r;
-    if (n_faces == 0) return TRGL_OK;
+    int K = 0; bool go;
+    if ((r = check_draw_indexed_vs(c, vs, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &K, &go)) || !go) return r;
     return draw_indexed_checked(c, vs, K, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, colors, mem_kind);
+}
+
+int trgl_draw_indexed_vs_clipped(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16], const double plane[4],
+                                 const trgl_clip_attr* attrs, int n_attrs, const double* vertices, int stride, uint64_t n_vertices,
+                                 const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    int K = TRGL_VARY_PHONG; bool go;
+    if (vs == -1) r = check_draw_indexed(c, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &go);
+    else r = check_draw_indexed_vs(c, vs, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &K, &go);
+    if (r) return r;
+    const ClipSpec spec{ plane, attrs, n_attrs };
+    ClipTable tab;
+    if ((r = clip_spec_table(c, "trgl_draw_indexed_vs_clipped", spec, kind, K, &tab)) || !go) return r;
+    return draw_indexed_checked(c, vs, K, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, colors, mem_kind, &spec);
+}
+
+int trgl_draw_clipped(trgl_ctx* c, int kind, const trgl_uniforms* u, const double plane[4], const trgl_clip_attr* attrs, int n_attrs,
+                      const double* clip, const double* vary, const uint32_t* colors, uint64_t n, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const int K = kind_vary_count(c, kind);
+    if (K < 0) return fail(c, TRGL_E_INVALID, "trgl_draw_clipped: unknown shader kind");
+    const ClipSpec spec{ plane, attrs, n_attrs };
+    ClipTable tab;
+    if ((r = clip_spec_table(c, "trgl_draw_clipped", spec, kind, K, &tab))) return r;
+    if (n == 0) return TRGL_OK;
+    if (!clip) return fail(c, TRGL_E_INVALID, "trgl_draw_clipped: clip is null");
+    if (K && !vary) return fail(c, TRGL_E_INVALID, "trgl_draw_clipped: this shader kind needs varyings");
+    if ((r = check_kind_uniforms(c, "trgl_draw_clipped", kind, u))) return r;
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_draw_clipped: bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE) {
+        StageHold hold(c);
+        return draw_device_clipped(c, kind, K, u, &spec, tab, clip, vary, colors, n);
+    }
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_draw_clipped: 2^31 or more triangles in one call");
+    try {
+        std::vector<double> oclip(2 * n * 12), ovary(2 * n * (size_t)K);
+        std::vector<uint32_t> ocol(colors ? 2 * n : 0);
+        const uint64_t n_out = host_clip_stage(plane, tab, K, clip, vary, colors, n, oclip.data(), ovary.data(), ocol.data());
+        return trgl_draw(c, kind, u, oclip.data(), K ? ovary.data() : nullptr, colors ? ocol.data() : nullptr, n_out, TRGL_MEM_HOST);
+    } catch (const std::bad_alloc&) {
+        return fail(c, TRGL_E_NOMEM, "trgl_draw_clipped: out of memory");
+    }
+}
+
+int trgl_clip_stage(trgl_ctx* c, const double plane[4], const trgl_clip_attr* attrs, int n_attrs, int K, const double* clip, const double* vary,
+                    const uint32_t* colors, uint64_t n, double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out, int mem_kind) {
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_clip_stage: bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_clip_stage: TRGL_MEM_DEVICE needs a context");
+    if (!plane || !n_out) return fail(c, TRGL_E_INVALID, "trgl_clip_stage: null plane or n_out");
+    ClipTable tab;
+    if (!clip_table(attrs, n_attrs, K, &tab)) return fail(c, TRGL_E_INVALID, "trgl_clip_stage: invalid clip attribute list (or K outside 0..TRGL_MAX_USER_VARY)");
+    *n_out = 0;
+    if (n == 0) return TRGL_OK;
+    if (!clip || !clip_out || (K && (!vary || !vary_out)) || (colors && !colors_out)) return fail(c, TRGL_E_INVALID, "trgl_clip_stage: null array");
+    if (mem_kind == TRGL_MEM_HOST) { *n_out = host_clip_stage(plane, tab, K, clip, vary, colors, n, clip_out, vary_out, colors_out); return TRGL_OK; }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_clip_stage: 2^31 or more triangles in one call");
+    if (((uintptr_t)clip | (uintptr_t)clip_out | (K ? (uintptr_t)vary | (uintptr_t)vary_out : 0)) & 7 || (colors && (((uintptr_t)colors | (uintptr_t)colors_out) & 3)))
+        return fail(c, TRGL_E_INVALID, "trgl_clip_stage: device arrays need natural alignment (8 bytes for doubles, 4 for colours)");
+    unsigned long long total = 0;
+    if ((r = queue_clip_stage(c, plane, tab, K, clip, vary, colors, n, clip_out, vary_out, colors_out, &total))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_out = total;
+    return TRGL_OK;
 }
 
 int trgl_vertex_stage(trgl_ctx* c, int vs, const trgl_uniforms* u, const double projection[16], const double* vertices, int stride,

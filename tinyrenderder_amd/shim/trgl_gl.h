@@ -31,6 +31,8 @@
 //     byte; TGAImage::scale / gaussian_blur themselves are host loops in trgl_image.h, as in the reference.
 //   * shadows (new; the reference has none): gl_shadow_matrix / gl_shadow_mask / gl_modulate turn the depths of a light's view, kept with
 //     gl_zbuffer_snapshot, into a mask and multiply it into the frame in HBM (see below, and include/trgl.h).
+//   * clipping (new; the reference has none): gl_clip_plane(&plane) cuts everything drawn from then on against a plane in clip space
+//     before it is rasterized (include/trgl.h, trgl_clip_stage); gl_clip_plane(nullptr) returns to the reference's behaviour.
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -156,6 +158,10 @@ struct State {
     std::vector<UserSource> user;         // gl_register_shader(): registered on every context, in order (kind = USER_FIRST + index)
     struct VertexSource { std::string source; int n_varyings; };
     std::vector<VertexSource> vertex;     // gl_register_vertex_shader(): likewise (vertex kind = index)
+    bool clip_on = false;                 // gl_clip_plane(): draws go through the clipped entry points
+    double clip_plane[4] = { 0, 0, 0, 0 };
+    struct ClipLayout { int kind; std::vector<trgl_clip_attr> attrs; };
+    std::vector<ClipLayout> clip_layouts; // gl_clip_layout(): the attribute lists of user kinds
     int err = TRGL_OK;                    // first C-ABI error since gl_clear_error() (a TRGL_E_* code)
     std::string err_msg;
 };
@@ -209,15 +215,31 @@ inline bool bind(TGAImage& fb) {
     return true;
 }
 
+// the clip attribute list of a kind: gl_clip_layout()'s, else n = -1, the kind's built-in layout (which a user kind with varyings
+// does not have: the C ABI refuses the draw, reported through gl_last_error())
+inline const trgl_clip_attr* clip_layout_of(int kind, int* n) {
+    for (const State::ClipLayout& l : state().clip_layouts)
+        if (l.kind == kind) { *n = int(l.attrs.size()); return l.attrs.data(); }
+    *n = -1;
+    return nullptr;
+}
+
 // hand the batched triangles to the device (on an error the batch is dropped: the call that met it reports false)
 inline bool submit_batch() {
     State& s = state();
     if (!s.have_batch) return true;
     double vp[16];
     for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) vp[4 * r + c] = s.viewport_at_batch[r][c];
-    const bool ok = s.ctx && TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
-                    TRGL_SHIM_OK(trgl_draw(s.ctx, s.kind, &s.uniforms, s.clip.data(), s.vary.empty() ? nullptr : s.vary.data(),
-                                           s.colors.data(), s.clip.size() / 12, TRGL_MEM_HOST));
+    bool ok = s.ctx && TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp));
+    const double* vary = s.vary.empty() ? nullptr : s.vary.data();
+    if (ok && s.clip_on) {                                      // (a change of plane ends the batch: the plane is the batch's)
+        int n_attrs = -1;
+        const trgl_clip_attr* attrs = clip_layout_of(s.kind, &n_attrs);
+        ok = TRGL_SHIM_OK(trgl_draw_clipped(s.ctx, s.kind, &s.uniforms, s.clip_plane, attrs, n_attrs, s.clip.data(), vary, s.colors.data(),
+                                            s.clip.size() / 12, TRGL_MEM_HOST));
+    } else if (ok) {
+        ok = TRGL_SHIM_OK(trgl_draw(s.ctx, s.kind, &s.uniforms, s.clip.data(), vary, s.colors.data(), s.clip.size() / 12, TRGL_MEM_HOST));
+    }
     s.clip.clear(); s.vary.clear(); s.colors.clear();
     s.have_batch = false;
     s.zbuffer_stale_on_host = true;
@@ -237,6 +259,30 @@ inline bool same_matrix(const mat<4, 4>& a, const mat<4, 4>& b) { return std::me
 inline int gl_last_error() { return trgl_shim::state().err; }
 inline const char* gl_last_error_message() { return trgl_shim::state().err_msg.c_str(); }
 inline void gl_clear_error() { trgl_shim::State& s = trgl_shim::state(); s.err = TRGL_OK; s.err_msg.clear(); }
+
+// Clipping (include/trgl.h, trgl_clip_stage).  gl_clip_plane(&p): every triangle drawn from now on - rasterize(), gl_draw_indexed(),
+// gl_draw_model() - is cut against the plane p in clip space before it is rasterized (inside: dot(p, v) >= 0; the near plane of
+// init_perspective is (0, 0, 1, 1)); gl_clip_plane(nullptr) switches clipping off.  A change of plane ends the current batch.
+// The counters then count the triangles that reach the rasterizer, and each clipped submission waits for the GPU once (trgl_draw_clipped).
+inline void gl_clip_plane(const vec4* plane) {
+    trgl_shim::State& s = trgl_shim::state();
+    double p[4] = { 0, 0, 0, 0 };
+    if (plane) for (int k = 0; k < 4; ++k) p[k] = (*plane)[k];
+    if (s.clip_on == (plane != nullptr) && std::memcmp(p, s.clip_plane, sizeof(p)) == 0) return;
+    trgl_shim::submit_batch();
+    s.clip_on = plane != nullptr;
+    std::memcpy(s.clip_plane, p, sizeof(p));
+}
+// Which varyings of a user kind belong to vertices: n attributes {offset, components}, each 3 * components doubles, vertex-major (the
+// memory image of `vecC varying_x[3]`); the other varyings are per-triangle constants.  Built-in kinds have their layouts.  A user kind
+// with varyings and no layout cannot be clipped: its draws fail through gl_last_error().
+inline void gl_clip_layout(int kind, const trgl_clip_attr* attrs, int n) {
+    trgl_shim::State& s = trgl_shim::state();
+    trgl_shim::submit_batch();
+    for (std::size_t i = 0; i < s.clip_layouts.size(); ++i)
+        if (s.clip_layouts[i].kind == kind) { s.clip_layouts.erase(s.clip_layouts.begin() + i); break; }
+    s.clip_layouts.push_back({ kind, std::vector<trgl_clip_attr>(attrs, attrs + (n > 0 ? n : 0)) });
+}
 
 // A user shader (include/trgl.h, "User shaders"): HIP C++ source defining trgl_fragment, with n_varyings doubles of varyings per
 // triangle.  The source is compiled at once (a compile error is reported through gl_last_error(), with the compiler's log, and
@@ -402,9 +448,13 @@ inline bool gl_draw_indexed(const IShader& shader, const double* vertices, int s
             std::abort();
         }
         const std::vector<std::uint32_t> colors(nfaces, d.color);
+        int n_attrs = -1;
+        const trgl_clip_attr* attrs = clip_layout_of(d.kind, &n_attrs);
         ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
-             TRGL_SHIM_OK(trgl_draw_indexed_vs(s.ctx, d.vertex_kind, d.kind, &d.uniforms, pj, vertices, stride, nv,
-                                               reinterpret_cast<const std::uint32_t*>(indices), nfaces, colors.data(), TRGL_MEM_HOST)) && ok;
+             (s.clip_on ? TRGL_SHIM_OK(trgl_draw_indexed_vs_clipped(s.ctx, d.vertex_kind, d.kind, &d.uniforms, pj, s.clip_plane, attrs, n_attrs, vertices, stride, nv,
+                                                                    reinterpret_cast<const std::uint32_t*>(indices), nfaces, colors.data(), TRGL_MEM_HOST))
+                        : TRGL_SHIM_OK(trgl_draw_indexed_vs(s.ctx, d.vertex_kind, d.kind, &d.uniforms, pj, vertices, stride, nv,
+                                                            reinterpret_cast<const std::uint32_t*>(indices), nfaces, colors.data(), TRGL_MEM_HOST))) && ok;
         s.zbuffer_stale_on_host = true;
         return ok;
     }
@@ -414,9 +464,13 @@ inline bool gl_draw_indexed(const IShader& shader, const double* vertices, int s
         std::fprintf(stderr, "trgl: gl_draw_indexed(): needs a PHONG or EYE shader, or a user shader with 24 varyings, with a device descriptor\n");
         std::abort();
     }
+    int n_attrs = -1;
+    const trgl_clip_attr* attrs = d.kind >= TRGL_SHADER_USER_FIRST ? clip_layout_of(d.kind, &n_attrs) : nullptr;
     ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
-         TRGL_SHIM_OK(trgl_draw_indexed(s.ctx, d.kind, &d.uniforms, pj, vertices, stride, nv,
-                                        reinterpret_cast<const std::uint32_t*>(indices), nfaces, TRGL_MEM_HOST)) && ok;
+         (s.clip_on ? TRGL_SHIM_OK(trgl_draw_indexed_vs_clipped(s.ctx, -1, d.kind, &d.uniforms, pj, s.clip_plane, attrs, n_attrs, vertices, stride, nv,
+                                                                reinterpret_cast<const std::uint32_t*>(indices), nfaces, nullptr, TRGL_MEM_HOST))
+                    : TRGL_SHIM_OK(trgl_draw_indexed(s.ctx, d.kind, &d.uniforms, pj, vertices, stride, nv,
+                                                     reinterpret_cast<const std::uint32_t*>(indices), nfaces, TRGL_MEM_HOST))) && ok;
     s.zbuffer_stale_on_host = true;
     return ok;
 }
