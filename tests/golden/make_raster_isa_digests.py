@@ -1,6 +1,7 @@
 """Writes tests/golden/raster_isa_digests.json: SHA-256 of the device assembly of every k_raster instantiation but KIND_ANY and of
 k_shade<PHONG> / k_shade<EYE>, one per function, comments and blank lines dropped (tests/test_user_shaders.py compares the build's
--save-temps assembly with them).
+-save-temps assembly with them).  A basic-block label `.LBB<f>_<n>` carries the function's ordinal <f> in its file: it is read as
+`.LBB_<n>`, where it is defined and where a branch names it, so that a kernel's digest does not depend on what else the file holds.
 
     python tests/golden/make_raster_isa_digests.py [path/to/kernels_raster-hip-amdgcn-amd-amdhsa-gfx950.s]
 
@@ -18,7 +19,8 @@ DEFAULT = os.path.join(HERE, "..", "..", "tinyrenderder_amd", "csrc", "build", "
 
 
 def functions(path):
-    """{mangled name: [instruction lines]} of an amdgcn .s file, comments and blank lines dropped."""
+    """{mangled name: [instruction lines]} of an amdgcn .s file, comments and blank lines dropped, block labels without the
+    function's ordinal."""
     out, cur, buf = {}, None, []
     for line in open(path):
         m = re.match(r"^(_Z\S+):\s*(;.*)?$", line)
@@ -32,7 +34,7 @@ def functions(path):
         if cur:
             s = line.split(";")[0].rstrip()
             if s:
-                buf.append(s + "\n")
+                buf.append(re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", s) + "\n")
     return out
 
 

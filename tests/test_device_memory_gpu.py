@@ -1,11 +1,12 @@
 """Draws from caller-owned device memory (TRGL_MEM_DEVICE, include/trgl.h:39-46): the path bench.py times.  The kernels read the
 caller's pointers as they are, so every read below is checked from a caller's buffer, at every alignment the header allows.
 
-  a. every built-in kind: GOURAUD's d->vary + local * 3 (kernels_raster.hip:371), k_shade's d.vary + local * 24
-     (kernels_raster.hip:941), k_setup's d.colors[i] (kernels_bin.hip:144), alone and in the mixed flush (k_raster<ANY>,
+  a. every built-in kind: GOURAUD's d->vary + local * 3 (resolve() in kernels_raster.hip), k_shade's d.vary + local * 24
+     (kernels_raster.hip), k_setup's d.colors[i] (kernels_bin.hip), alone and in the mixed flush (k_raster<ANY>,
      k_shade<ANY>), whole, in three flushes, in an odd-row strip and in one rank's bands;
-  b. user kinds: in.vary = d.vary + local * K (shade_user.h:43; raster_user.h:108 for kinds that may discard), K = 24 and K = 5;
-  c. alignment: k_setup's copy of a clip stream that is not 16-byte aligned (kernels_bin.hip:65-67: only a caller's device
+  b. user kinds: in.vary = d.vary + local * K (trgl_shade_user in shade_user.h; trgl_raster_user in raster_user.h for kinds that may
+     discard), K = 24 and K = 5;
+  c. alignment: k_setup's copy of a clip stream that is not 16-byte aligned (its staging loop in kernels_bin.hip: only a caller's device
      pointer reaches it, the host path stages into 256-byte aligned chunks, stage_alloc in trgl_api.cpp), whole and partial blocks,
      8-aligned varyings, 4-aligned colours, the literal records;
   d. host and device draws in one flush (trgl_draw in trgl_api.cpp), and more device draws than a flush has descriptors
@@ -14,7 +15,7 @@ caller's pointers as they are, so every read below is checked from a caller's bu
      overwritten once the flush has completed;
   f. stream ordering: the context's own stream is hipStreamNonBlocking (init_ctx in trgl_api.cpp) and waits for nobody; on a shared
      stream (trgl_set_stream) producers, flush and overwrites line up without a host sync, as bench.py and shard.StripLoop rely on;
-  g. trgl_draw_indexed(TRGL_MEM_DEVICE): k_vertex_stage gathers through the caller's pointers (kernels_post.hip:43), whole
+  g. trgl_draw_indexed(TRGL_MEM_DEVICE): k_vertex_stage gathers through the caller's pointers (kernels_post.hip), whole
      meshes and the block edges of 64 faces (trgl_draw_indexed in trgl_shader.cpp does not stage or check on this path).
 
 Bar: the device-memory frame equals the host-memory frame of the same GPU bit for bit - z bits, framebuffer bytes, stats tuple and

@@ -12,16 +12,13 @@
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"
 #include "launch.h"
+#include "device_util.h"
 
 namespace {
 
 __device__ __forceinline__ double dmin3(double a, double b, double c) { double m = a; if (b < m) m = b; if (c < m) m = c; return m; }
 __device__ __forceinline__ double dmax3(double a, double b, double c) { double m = a; if (m < b) m = b; if (m < c) m = c; return m; }
-__device__ __forceinline__ double dot4(const double* m, const double* v) {
-    double sum = 0;                               // geometry.h:122-127: left to right from 0
-    sum += m[0] * v[0]; sum += m[1] * v[1]; sum += m[2] * v[2]; sum += m[3] * v[3];
-    return sum;
-}
+using trgl_dev::dot4; using trgl_dev::wave_incl_scan; using trgl_dev::block_excl_scan;
 
 __device__ __forceinline__ int wave_min_i(int v) {
     for (int o = 32; o; o >>= 1) { int t = __shfl_xor(v, o); v = t < v ? t : v; }
@@ -30,31 +27,6 @@ __device__ __forceinline__ int wave_min_i(int v) {
 __device__ __forceinline__ int wave_max_i(int v) {
     for (int o = 32; o; o >>= 1) { int t = __shfl_xor(v, o); v = t > v ? t : v; }
     return v;
-}
-
-// ---------------------------------------------------------------------------------------------
-// block-level scan helpers (the radix histograms are scanned row by row in k_radix_scan_rows)
-// ---------------------------------------------------------------------------------------------
-constexpr int SCAN_THREADS = 256;
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(v, o); if (lane >= o) v += t; }
-    return v;
-}
-
-// block-wide exclusive scan of one value per thread (256 threads); returns exclusive prefix, total in *total
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* smem /*[4]*/, uint32_t* total) {
-    uint32_t inc = wave_incl_scan(v);
-    int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 63) smem[w] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_THREADS / 64; ++k) { uint32_t s = smem[k]; if (k < w) base += s; tot += s; }
-    *total = tot;
-    return base + inc - v;
 }
 
 // blocks of tile (tx, ty) inside the block-unit box [qx0, qx1] x [qy0, qy1] (the box reaches the tile)
@@ -172,7 +144,7 @@ __global__ __launch_bounds__(SETUP_THREADS) void k_setup(FrameParams fp, DrawDes
         for (int k = 0; k < 12; ++k) ok = ok && __builtin_isfinite(ndc[k]);                // :109-114
         double sx[3], sy[3];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) { sx[q] = dot4(fp.vp, ndc + 4 * q); sy[q] = dot4(fp.vp + 4, ndc + 4 * q); }  // :117-121
+        for (int q = 0; q < 3; ++q) { const double* v = ndc + 4 * q; sx[q] = dot4(fp.vp, v[0], v[1], v[2], v[3]); sy[q] = dot4(fp.vp + 4, v[0], v[1], v[2], v[3]); }  // :117-121
         double e1x = sx[1] - sx[0], e1y = sy[1] - sy[0], e2x = sx[2] - sx[0], e2y = sy[2] - sy[0];
         double cross_product = e1x * e2y - e1y * e2x;                                      // :124-126
         ok = ok && !(cross_product <= 0);                                                  // :127

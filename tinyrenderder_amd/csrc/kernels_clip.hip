@@ -29,6 +29,7 @@ constexpr int T = CLIP_BLOCK_TRIS;
 static_assert(T == 256, "one triangle per lane of a 256-thread block");
 
 // the sum of v over the block (valid in every thread) and, in *excl, the sum over the threads before this one; s_w: 4 words of LDS
+// (an own copy, not device_util.h's block_excl_scan: written that way, all four kernels of this file get other instructions)
 __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* s_w, uint32_t* excl) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t inc = v;

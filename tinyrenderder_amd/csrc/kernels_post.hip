@@ -1,4 +1,5 @@
-// kernels_post.hip — the two callers either side of the rasterizer, gfx950.
+// kernels_post.hip — the vertex stage ahead of the rasterizer and the z-image / SSAO / composite passes behind it (SURVEY.md §8(f)
+// rows N1 and N4), gfx950.
 //
 //   N1  k_vertex_stage : PhongShader::vertex / EyeShader::vertex (main.cpp:71-90,199-218) for an indexed mesh:
 //                        eye = MV*(p,1), normal_eye = MV*(n,0), clip = P*eye; emits the clip / varyings arrays the
@@ -12,14 +13,11 @@
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"
 #include "launch.h"
+#include "device_util.h"
 
 namespace {
 
-__device__ __forceinline__ double dot4(const double* m, double x, double y, double z, double w) {
-    double sum = 0;                                   // geometry.h:122-127
-    sum += m[0] * x; sum += m[1] * y; sum += m[2] * z; sum += m[3] * w;
-    return sum;
-}
+using trgl_dev::dot4;
 
 struct VertexStageParams {
     double mv[16], proj[16];
@@ -350,107 +348,9 @@ __global__ __launch_bounds__(256) void k_composite(const uint8_t* __restrict__ f
     }
 }
 
-// ---- Model::computeAABB (model.cpp:15-40) ---------------------------------------------------------------------------
-// The reference's loop is `min = std::min(min, p)` = (p < min) ? p : min and `max = std::max(max, p)` = (max < p) ? p : max from
-// 1e9 / -1e9: a NaN never replaces a bound, and of two values that compare equal - only +0.0 and -0.0 differ in bits - the one met
-// first stays.  So a bound is the first vertex, in vertex order, that holds the smallest (largest) value: the reduction carries
-// (value, vertex index) and prefers the lower index among equal values, which makes it associative and commutative - the result is
-// the sequential loop's whatever the order in which lanes, waves and blocks are combined.  The start value carries the index ~0:
-// a vertex that equals it has the same bits.  Slots 0..2 are minima, 3..5 maxima.
-using trgl::BoundsPartial;
-__device__ __forceinline__ bool bounds_better(int k, double vb, unsigned long long ib, double va, unsigned long long ia) {
-    return (k < 3 ? vb < va : vb > va) || (vb == va && ib < ia);
-}
-
-// wave (xor butterfly: every lane ends with the same six pairs), then the block's four waves through LDS; the result is thread 0's
-__device__ __forceinline__ void bounds_block_reduce(double (&v)[6], unsigned long long (&ix)[6]) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        for (int o = 32; o; o >>= 1) {
-            const double ov = __shfl_xor(v[k], o);
-            const unsigned long long oi = __shfl_xor(ix[k], o);
-            if (bounds_better(k, ov, oi, v[k], ix[k])) { v[k] = ov; ix[k] = oi; }
-        }
-    __shared__ double s_v[4][6];
-    __shared__ unsigned long long s_i[4][6];
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { s_v[threadIdx.x >> 6][k] = v[k]; s_i[threadIdx.x >> 6][k] = ix[k]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (bounds_better(k, s_v[w][k], s_i[w][k], v[k], ix[k])) { v[k] = s_v[w][k]; ix[k] = s_i[w][k]; }
-    }
-}
-
-// Grid-stride over the vertices, four vertices = twelve independent 8-byte loads in flight per thread (positions are only 8-byte
-// aligned: no wider loads).  A thread meets its vertices in rising order, so `<` alone keeps the first among equals here; a vertex
-// past the end stands as NaN, which replaces nothing.  partials[blockIdx.x] leaves with plain stores: no atomics, no ordering
-// between blocks.
-constexpr int MB_UNROLL = 4;
-__global__ __launch_bounds__(256) void k_mesh_bounds(const double* __restrict__ vertices, int stride, uint64_t n, BoundsPartial* __restrict__ partials) {
-    double v[6] = { 1e9, 1e9, 1e9, -1e9, -1e9, -1e9 };                                  // model.cpp:21-22
-    unsigned long long ix[6] = { ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull };
-    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += MB_UNROLL * step) {
-        double p[MB_UNROLL][3];
-#pragma unroll
-        for (int u = 0; u < MB_UNROLL; ++u) {
-            const uint64_t j = i + u * step;
-            const double* rec = vertices + (j < n ? j : i) * (uint64_t)stride;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) p[u][a] = j < n ? rec[a] : __builtin_nan("");
-        }
-#pragma unroll
-        for (int u = 0; u < MB_UNROLL; ++u) {
-            const uint64_t j = i + u * step;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                if (p[u][a] < v[a]) { v[a] = p[u][a]; ix[a] = j; }                      // :25-27
-                if (v[3 + a] < p[u][a]) { v[3 + a] = p[u][a]; ix[3 + a] = j; }          // :29-31
-            }
-        }
-    }
-    bounds_block_reduce(v, ix);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { partials[blockIdx.x].v[k] = v[k]; partials[blockIdx.x].i[k] = ix[k]; }
-    }
-}
-
-// one block: folds the partials and applies the margin once (model.cpp:35-36); out->v = min x, y, z, max x, y, z of localAABB
-__global__ __launch_bounds__(256) void k_mesh_bounds_fold(const BoundsPartial* __restrict__ partials, uint32_t nparts, BoundsPartial* __restrict__ out) {
-    double v[6] = { 1e9, 1e9, 1e9, -1e9, -1e9, -1e9 };
-    unsigned long long ix[6] = { ~0ull, ~0ull, ~0ull, ~0ull, ~0ull, ~0ull };
-    for (uint32_t b = threadIdx.x; b < nparts; b += 256)
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            if (bounds_better(k, partials[b].v[k], partials[b].i[k], v[k], ix[k])) { v[k] = partials[b].v[k]; ix[k] = partials[b].i[k]; }
-    bounds_block_reduce(v, ix);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double margin = (v[3 + a] - v[a]) * 0.01;                             // :35
-            out->v[a] = v[a] - margin; out->v[3 + a] = v[3 + a] + margin;               // :36
-            out->i[a] = ix[a]; out->i[3 + a] = ix[3 + a];
-        }
-    }
-}
-
 }  // namespace
 
 namespace trgl {
-
-void launch_mesh_bounds(hipStream_t s, const double* vertices, int stride, uint64_t n, BoundsPartial* scratch) {
-    const uint64_t per_block = 256ull * MB_UNROLL;
-    const uint64_t want = (n + per_block - 1) / per_block;
-    const uint32_t blocks = (uint32_t)(want < MESH_BOUNDS_MAX_BLOCKS ? want : MESH_BOUNDS_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_mesh_bounds, dim3(blocks), dim3(256), 0, s, vertices, stride, n, scratch + 1);
-    hipLaunchKernelGGL(k_mesh_bounds_fold, dim3(1), dim3(256), 0, s, scratch + 1, blocks, scratch);
-}
 
 void launch_vertex_stage(hipStream_t s, const double mv[16], const double proj[16], const double* vertices, int stride,
                          const uint32_t* indices, uint32_t nfaces, double* clip, double* vary) {

@@ -14,6 +14,7 @@
 #include "trgl_device.h"
 #include "launch.h"
 #include "shade_common.h"
+#include "frag_builtin.h"
 
 namespace {
 using namespace trgl_shade;
@@ -22,9 +23,6 @@ using namespace trgl_shade;
 // never be written again (z < NaN is false), so leaving it out of a maximum keeps the maximum a valid bound
 __device__ __forceinline__ double vmax(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ double vmin(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// v_min3_f32 / v_max_f32 as single instructions (a NaN operand is skipped)
-__device__ __forceinline__ float fmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float fmax2(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // maximum over the 64 lanes, in every lane (NaN operands are skipped by v_max_f32)
 __device__ __forceinline__ float wave_max_f32(float v) {
     float t;
@@ -37,173 +35,11 @@ __device__ __forceinline__ float wave_max_f32(float v) {
     asm volatile("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf" : "=&v"(t) : "v"(v), "0"(v)); v = t;
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
-// double -> float rounded towards +inf / -inf (NaN stays NaN): bounds that stay bounds in single precision
+// double -> float rounded towards +inf (NaN stays NaN): a bound that stays a bound in single precision
 __device__ __forceinline__ float f32_up(double d) {
     float f = (float)d;
     if ((double)f < d) { const uint32_t b = __float_as_uint(f); f = __uint_as_float((b >> 31) ? b - 1u : b + 1u); }
     return f;
-}
-__device__ __forceinline__ float f32_down(double d) {
-    float f = (float)d;
-    if ((double)f > d) { const uint32_t b = __float_as_uint(f); f = __uint_as_float((b >> 31) ? b + 1u : b - 1u); }
-    return f;
-}
-__device__ __forceinline__ double dot3(const double* a, const double* b) {
-    double sum = 0; sum += a[0] * b[0]; sum += a[1] * b[1]; sum += a[2] * b[2]; return sum;   // geometry.h:122-127
-}
-__device__ __forceinline__ void normalized3(const double* v, double* out) {                   // geometry.h:136-140
-    double length = sqrt(dot3(v, v));
-    if (length == 0) { out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; return; }
-    out[0] = v[0] / length; out[1] = v[1] / length; out[2] = v[2] / length;
-}
-
-__device__ __forceinline__ void interp(const double* v0, const double* v1, const double* v2, const double* b, int n, double* out) {
-    for (int i = 0; i < n; ++i) out[i] = (v0[i] * b[0] + v1[i] * b[1]) + v2[i] * b[2];       // main.cpp:94-104
-}
-__device__ __forceinline__ double spec_pow(double x, double y) {
-    // std::pow(x, 1.0) == x exactly; PhongShader's exponent is always 1.0
-    return (y == 1.0) ? x : pow(x, y);
-}
-
-// PhongShader::fragment — main.cpp:92-170
-template <class UN, class TX>
-__device__ __forceinline__ Color frag_phong(const UN& u, TX tx, const double* vary, const double* b) {
-    const double* uvv = vary; const double* pos = vary + 6; const double* nrm = vary + 15;
-    double position_eye[3], geometry_normal[3], uv[2];
-    interp(pos, pos + 3, pos + 6, b, 3, position_eye);
-    interp(nrm, nrm + 3, nrm + 6, b, 3, geometry_normal);
-    interp(uvv, uvv + 2, uvv + 4, b, 2, uv);
-
-    // the three maps are independent: issue all texel loads first, consume afterwards (the slots are per draw,
-    // so these branches are wave-uniform)
-    const TX td = tex_slot(tx, u.tex_diffuse);
-    const TX ts = tex_slot(tx, u.tex_specular);
-    const TX tn = tex_slot(tx, u.tex_normal);
-    uint32_t raw_d = 0, raw_s = 0, raw_n = 0;
-    if (td) raw_d = tex_fetch_raw(td, uv);
-    if (ts) raw_s = tex_fetch_raw(ts, uv);
-    if (tn) raw_n = tex_fetch_raw(tn, uv);
-    Color base = td ? Color{ raw_d & tex_mask(td), td->bpp } : Color{ 0xffffffffu, 4 };       // model.cpp:415-426
-    float specf = ts ? (float)(int)(raw_s & 0xff) / 255.0f : 1.0f;                            // model.cpp:447-459
-    double specular_power = dmax(1.0, (double)specf);
-
-    int bsum = (int)(base.bgra & 0xff) + (int)((base.bgra >> 8) & 0xff) + (int)((base.bgra >> 16) & 0xff);
-    double brightness = bsum / (3.0 * 255.0);
-    bool is_eye_pixel = (brightness >= 0.85) && (specular_power <= 5.0);
-
-    double nmv[3] = { 0, 0, 1 };                                                              // model.cpp:428-445
-    if (tn) {
-        const uint32_t c = raw_n & tex_mask(tn);
-        double n[3];
-        n[0] = (double)((c >> 16) & 0xff) / 255.0 * 2.0 - 1.0;
-        n[1] = (double)((c >> 8) & 0xff) / 255.0 * 2.0 - 1.0;
-        n[2] = (double)(c & 0xff) / 255.0 * 2.0 - 1.0;
-        normalized3(n, nmv);
-    }
-    double nme[3];                                                                            // main.cpp:116-119
-    for (int r = 0; r < 3; ++r) {
-        const auto* m = u.model_view + 4 * r;
-        double sum = 0; sum += m[0] * nmv[0]; sum += m[1] * nmv[1]; sum += m[2] * nmv[2]; sum += m[3] * 0.0;
-        nme[r] = sum;
-    }
-    double N[3];
-    if (is_eye_pixel) { N[0] = geometry_normal[0]; N[1] = geometry_normal[1]; N[2] = geometry_normal[2]; }
-    else {
-        double s = u.normal_map_strength, mix[3];
-        for (int i = 0; i < 3; ++i) mix[i] = geometry_normal[i] * (1.0 - s) + nme[i] * s;
-        normalized3(mix, N);
-    }
-    double negp[3], V[3];
-    for (int i = 0; i < 3; ++i) negp[i] = position_eye[i] * -1.0;
-    normalized3(negp, V);
-
-    const double Lk[3] = { u.key_light_dir_eye[0], u.key_light_dir_eye[1], u.key_light_dir_eye[2] };
-    double key_diffuse = dmax(0.0, dot3(N, Lk)) * 1.0;
-    double k2 = 2.0 * dot3(N, Lk), rr[3], R[3];
-    for (int i = 0; i < 3; ++i) rr[i] = N[i] * k2 - Lk[i];
-    normalized3(rr, R);
-    double rvd = dmax(0.0, dot3(R, V));
-    double key_specular = (rvd > 0.0 ? spec_pow(rvd, specular_power) : 0.0) * 1.0;
-    const double Lf[3] = { u.fill_light_dir_eye[0], u.fill_light_dir_eye[1], u.fill_light_dir_eye[2] };
-    double fill_diffuse = dmax(0.0, dot3(N, Lf)) * 0.35;
-    const double Lr[3] = { u.rim_light_dir_eye[0], u.rim_light_dir_eye[1], u.rim_light_dir_eye[2] };
-    double rim_diffuse = dmax(0.0, dot3(N, Lr)) * 0.6;
-    double total_diffuse = key_diffuse + fill_diffuse + rim_diffuse;
-    double total_specular = key_specular;
-    double ambient = 0.10;
-
-    uint32_t out = base.bgra & 0xff000000u;
-    for (int ch = 0; ch < 3; ++ch) {
-        double channel_value = (double)((base.bgra >> (8 * ch)) & 0xff);
-        double final_value = channel_value * (ambient + total_diffuse) + 255.0 * (0.35 * total_specular);
-        out |= (uint32_t)(unsigned char)dmin(255.0, final_value) << (8 * ch);
-    }
-    return Color{ out, base.bytespp };
-}
-
-// EyeShader::fragment — main.cpp:220-261
-template <class UN, class TX>
-__device__ __forceinline__ Color frag_eye(const UN& u, TX tx, const double* vary, const double* b) {
-    const double* uvv = vary; const double* pos = vary + 6; const double* nrm = vary + 15;
-    double position_eye[3], ni[3], N[3], uv[2];
-    interp(pos, pos + 3, pos + 6, b, 3, position_eye);
-    interp(nrm, nrm + 3, nrm + 6, b, 3, ni);
-    normalized3(ni, N);
-    interp(uvv, uvv + 2, uvv + 4, b, 2, uv);
-
-    const TX td = tex_slot(tx, u.tex_diffuse);
-    const TX ts = tex_slot(tx, u.tex_specular);
-    uint32_t raw_d = 0, raw_s = 0;
-    if (td) raw_d = tex_fetch_raw(td, uv);
-    if (ts) raw_s = tex_fetch_raw(ts, uv);
-    Color base = td ? Color{ raw_d & tex_mask(td), td->bpp } : Color{ 0xffffffffu, 4 };
-    double negp[3], V[3];
-    for (int i = 0; i < 3; ++i) negp[i] = position_eye[i] * -1.0;
-    normalized3(negp, V);
-
-    const double Lk[3] = { u.key_light_dir_eye[0], u.key_light_dir_eye[1], u.key_light_dir_eye[2] };
-    double key_diffuse = dmax(0.0, dot3(N, Lk)) * 1.0;
-    const double Lr[3] = { u.rim_light_dir_eye[0], u.rim_light_dir_eye[1], u.rim_light_dir_eye[2] };
-    double rim_diffuse = dmax(0.0, dot3(N, Lr)) * 0.6;
-    double total_diffuse = key_diffuse + rim_diffuse;
-
-    float specf = ts ? (float)(int)(raw_s & 0xff) / 255.0f : 1.0f;
-    double specular_power = dmax(1.0, (double)specf) * 8.0;
-    double k2 = 2.0 * dot3(N, Lk), rr[3], R[3];
-    for (int i = 0; i < 3; ++i) rr[i] = N[i] * k2 - Lk[i];
-    normalized3(rr, R);
-    double rvd = dmax(0.0, dot3(R, V));
-    double specular = (rvd > 0.0 ? spec_pow(rvd, specular_power) : 0.0);
-
-    uint32_t out = base.bgra & 0xff000000u;
-    for (int ch = 0; ch < 3; ++ch) {
-        double channel_value = (double)((base.bgra >> (8 * ch)) & 0xff);
-        double final_value = channel_value * (0.1 + total_diffuse) + 255.0 * (1.5 * specular);
-        out |= (uint32_t)(unsigned char)dmin(255.0, final_value) << (8 * ch);
-    }
-    return Color{ out, base.bytespp };
-}
-
-// GOURAUD: base * (float)(i0*b0 + i1*b1 + i2*b2), TGAColor::operator*(float) tgaimage.h:55-62
-__device__ __forceinline__ uint32_t frag_gouraud(uint32_t base, const double* vary, const double* b) {
-    double id = (vary[0] * b[0] + vary[1] * b[1]) + vary[2] * b[2];
-    float intensity = (float)id;
-    if (intensity < 0.f) intensity = 0.f;
-    if (intensity > 1.f) intensity = 1.f;
-    uint32_t out = 0;
-    for (int i = 0; i < 4; ++i) {
-        float c = (float)(int)((base >> (8 * i)) & 0xff) * intensity;
-        out |= (uint32_t)(uint8_t)c << (8 * i);
-    }
-    return out;
-}
-
-
-// CHECKER: a FLAT colour that discards on a predicate of the perspective-correct barycentrics - the device kind that exercises
-// `if (discard) continue;` (our_gl.cpp:187-188): cell parities of bar[0] and bar[1] on a cells x cells grid differ -> discard.
-__device__ __forceinline__ bool frag_checker_discards(int cells, const double* b) {
-    const int a = x86_cvttsd2si(b[0] * (double)cells), c = x86_cvttsd2si(b[1] * (double)cells);
-    return ((a ^ c) & 1) != 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -258,7 +94,6 @@ constexpr int RING = 512;                           // candidate ring of a wave 
 #define TRGL_STAMP(i) ((void)0)
 #endif
 
-typedef const __attribute__((address_space(4))) TriRec CRec;      // records through the scalar cache
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 
 // The scan constants of one triangle, wave-uniform (SGPRs): its whole record, two scalar loads of 64 B.
@@ -272,9 +107,6 @@ struct TriScan {
 };
 __device__ __forceinline__ TriScan load_scan(const TriRec* __restrict__ recs, uint32_t tri) {
     TriScan T;
-#ifdef TRGL_EXP_SAMEREC
-    tri &= 63u;          // timing experiment only (wrong frames): every visit reads one of 64 records = scalar-cache hits
-#endif
 #if __HIP_DEVICE_COMPILE__
     // (a flush holds at most TRGL_FLUSH_MAX_TRIS = 2^25 records: the byte offset fits the 32-bit scalar offset of s_load)
     // The record as TWO requests of 16 dwords, written out: from C++ the second half becomes three (8 + 4 + 2 dwords around the bbox,
@@ -430,30 +262,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRGL_RASTER
     __shared__ uint32_t s_out[4][64];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2): workgroup b runs on the XCD of b mod 8.  Give every
-    // XCD one contiguous eighth of the item list, so that the four block rows of a tile - and its neighbours, which share
-    // triangles with it - read their list and records through the same L2.  (Placement is an observed property, used for speed only.)
-    const uint32_t G = n_items[0];
-    const uint32_t per = (G + 7u) >> 3, xj = blockIdx.x >> 3;
-    const uint32_t g = (blockIdx.x & 7u) * per + xj;
-    if (xj >= per || g >= G) return;                      // (block-uniform, like the clear-only exit below: the one barrier at the end is safe)
+    uint32_t g;                                           // this workgroup's item (work_items.h: an eighth of the list per XCD)
+    if (!trgl_item_of_workgroup(blockIdx.x, n_items[0], &g)) return;   // (block-uniform, like the clear-only exit below: the one barrier at the end is safe)
     const uint4 item4 = items[g];                         // work item, its tile's slice [beg, end) of the sorted pair list
     const uint32_t item = item4.x;
-    const int t = (int)(item & 0xffffffu);
+    const int t = (int)trgl_item_tile(item);
     const int tile_y = t / fp.tiles_x, tile_x = t - tile_y * fp.tiles_x;
     const int px0 = tile_x << TRGL_TILE_LOG2, py0 = tile_y << TRGL_TILE_LOG2;
-    unsigned long long* my_stats = item_stats + (size_t)g * 4;
+    unsigned long long* my_stats = item_stats + (size_t)g * TRGL_ITEM_STATS_WORDS;
     if (item & TRGL_ITEM_CLEAR) {                         // cleared and empty: store the clear values, nothing else
         // rows [py0 + 8 w, py0 + 8 w + 7] of the tile for wave w
         const int ya = max(py0 + 8 * w, fp.strip_y0), yb = min(min(py0 + 8 * w + 7, fp.H - 1), fp.strip_y1 - 1);
         if (ya <= yb) clear_rows(fp, lane, px0, ya, yb);
-        if (threadIdx.x == 0) {
-            ulonglong2* dst = reinterpret_cast<ulonglong2*>(my_stats);
-            dst[0] = make_ulonglong2(0ull, ~0ull); dst[1] = make_ulonglong2(0ull, 0ull);
-        }
+        if (threadIdx.x == 0) trgl_item_stats_store(my_stats, 0ull, TRGL_ITEM_KMIN_NONE, TRGL_ITEM_KMAX_NONE);
         return;
     }
-    const int brow = (int)((item >> 24) & 3u);
+    const int brow = (int)trgl_item_brow(item);
     const int kblk = 4 * brow + w;                        // this wave's block of the tile: bit 4 cy + cx of the pair masks
     const int X0 = px0 + 8 * w, Y0 = py0 + 8 * brow;
 
@@ -863,22 +687,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRGL_RASTER
 #endif
     __syncthreads();                 // the only block-level barrier of the kernel, when every wave of the workgroup is done
     if (w == 0) {
-        unsigned long long frags = 0, kmin = ~0ull, kmax = 0ull;
+        unsigned long long frags = 0, kmin = TRGL_ITEM_KMIN_NONE, kmax = TRGL_ITEM_KMAX_NONE;
         for (int k = 0; k < 4; ++k) {
             const unsigned long long* red = reinterpret_cast<const unsigned long long*>(s_ring[k]);
             const unsigned long long a = red[lane], b = red[64 + lane];
             frags += s_ring[k][256 + lane]; kmin = a < kmin ? a : kmin; kmax = b > kmax ? b : kmax;
         }
-        for (int o = 32; o; o >>= 1) {
+        for (int o = 32; o; o >>= 1) {                  // (one butterfly for the three: as three reductions in a row the kernel's instructions change)
             frags += __shfl_xor(frags, o);
             unsigned long long a = __shfl_xor(kmin, o); kmin = a < kmin ? a : kmin;
             unsigned long long b = __shfl_xor(kmax, o); kmax = b > kmax ? b : kmax;
         }
-        if (lane == 0) {
-            ulonglong2* dst = reinterpret_cast<ulonglong2*>(my_stats);
-            dst[0] = make_ulonglong2(frags, kmin);
-            dst[1] = make_ulonglong2(kmax, 0ull);
-        }
+        if (lane == 0) trgl_item_stats_store(my_stats, frags, kmin, kmax);
     }
 }
 
@@ -902,10 +722,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     if (item_idx >= *n_items) return;
     const uint32_t item = items[item_idx].x;
     if (item & TRGL_ITEM_CLEAR) return;                  // no triangles: no owners
-    const int t = (int)(item & 0xffffffu);
+    const int t = (int)trgl_item_tile(item);
     const int tile_y = t / fp.tiles_x, tile_x = t - tile_y * fp.tiles_x;
     const int x = (tile_x << TRGL_TILE_LOG2) + 8 * (int)(threadIdx.x >> 6) + (lane & 7);
-    const int y = (tile_y << TRGL_TILE_LOG2) + 8 * (int)((item >> 24) & 3u) + (lane >> 3);
+    const int y = (tile_y << TRGL_TILE_LOG2) + 8 * (int)trgl_item_brow(item) + (lane >> 3);
     const bool mine = x < fp.W && y < fp.H && y >= fp.strip_y0 && y < fp.strip_y1;
     const size_t idx = (size_t)x + (size_t)y * fp.W;
     // The kernel is bound by dependent memory latencies: owner -> record -> varyings -> texels.  The visibility buffer holds
@@ -949,185 +769,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     store_pixel(fp, idx, color);                                   // TGAImage::set, tgaimage.cpp:32-39
 }
 
-// ---- self-test of the two exactness shortcuts, against the hardware's IEEE division ------------------
-__device__ __forceinline__ unsigned long long sm64(unsigned long long& st) {
-    unsigned long long z = (st += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ double mk_double(unsigned long long mant, int exp2, bool neg) {
-    unsigned long long bits = (mant & 0x000fffffffffffffull) | ((unsigned long long)(exp2 + 1023) << 52) | (neg ? 0x8000000000000000ull : 0ull);
-    return __longlong_as_double((long long)bits);
-}
-__global__ void k_selftest_division(unsigned long long n_per_thread, unsigned long long seed, unsigned long long* mismatches) {
-    unsigned long long st = seed + 0x1000003ull * (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x);
-    unsigned long long bad = 0;
-    for (unsigned long long it = 0; it < n_per_thread; ++it) {
-        unsigned long long r0 = sm64(st), r1 = sm64(st), r2 = sm64(st);
-        int mode = (int)(r2 & 7);
-        int eb = (int)((r2 >> 8) % 440) - 40;           // |uz| in [2^-40, 2^400): the well-scaled range
-        int ea = (int)((r2 >> 24) % 700) - 350;
-        unsigned long long mb = r1;
-        if (mode == 1) mb = 0x000fffffffffffffull;                       // all-ones significand
-        if (mode == 2) mb = 0x000fffffffffffffull ^ (1ull << (r1 % 52));  // one zero bit
-        if (mode == 3) mb = 0;                                           // power of two
-        double uz = mk_double(mb, eb, true);                             // u.z < 0
-        double a = mk_double(r0, ea, (r2 >> 40) & 1);
-        if (mode >= 4 && mode <= 6) {
-            // numerator chosen so that a/uz lies next to a rounding midpoint: a = RN(uz * (q + ulp(q)/2 * (1 +- tiny)))
-            double q = mk_double(r0, ea - eb, (r2 >> 41) & 1);
-            double half_ulp = mk_double(0, ea - eb - 53, false);
-            a = __builtin_fma(uz, q, uz * half_ulp);
-            if (mode == 5) a = __longlong_as_double(__double_as_longlong(a) + 1);
-            if (mode == 6) a = __longlong_as_double(__double_as_longlong(a) - 1);
-        }
-        if (mode == 7) a = (r2 >> 42) & 1 ? 0.0 : -0.0;
-        double ruz = 1.0 / uz;
-        double ref = a / uz, got = div_by_uz(a, uz, ruz);
-        if (__double_as_longlong(ref) != __double_as_longlong(got)) ++bad;
-        // sign shortcuts of the coverage test
-        if ((ref < 0) != (a > 0.0)) ++bad;
-        if (((1.0 - ref) < 0) != (a < uz)) ++bad;
-        // numerator right next to uz, where 1 - q changes sign
-        double a2 = __longlong_as_double(__double_as_longlong(uz) + (long long)(r1 % 5) - 2);
-        double ref2 = a2 / uz;
-        if (__double_as_longlong(ref2) != __double_as_longlong(div_by_uz(a2, uz, ruz))) ++bad;
-        if (((1.0 - ref2) < 0) != (a2 < uz)) ++bad;
-    }
-    if (bad) atomicAdd(mismatches, bad);
-}
-
-// ---- self-test of the samplers' index math: tex_fetch on given uv (the fixtures come from the compiled reference's
-// IShader::sample2D, tests/golden/sampler_golden.npz) ---------------------------------------------------------------
-__global__ void k_selftest_sampler(const DevTexture* __restrict__ tex, int slot, const double* __restrict__ uv, unsigned long long n,
-                                   uint8_t* __restrict__ out) {
-    const unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const DevTexture* t = tex_slot(tex, slot);
-    Color c = t ? tex_fetch(t, uv + 2 * i) : Color{ 0xffffffffu, 4 };        // a missing map samples as opaque white (model.cpp:416-418)
-    for (int k = 0; k < 4; ++k) out[5 * i + k] = (uint8_t)(c.bgra >> (8 * k));
-    out[5 * i + 4] = (uint8_t)c.bytespp;
-}
-
-// Work items of the raster kernel: one per workgroup = one row of four 8x8 blocks of a tile with triangles (four items
-// per tile), or one whole tile that is only cleared.  Tiles outside the context's tile rows, empty tiles of a flush that
-// does not start from clear, and block rows entirely outside the strip get no item.
-__global__ __launch_bounds__(256) void k_make_items(FrameParams fp, const uint32_t* __restrict__ tile_start,
-                                                    const uint32_t* __restrict__ tile_end,
-                                                    uint4* __restrict__ items, uint32_t* __restrict__ n_items, TriRec* __restrict__ recs) {
-    const int ntiles_strip = (fp.strip_ty1 - fp.strip_ty0) * fp.tiles_x;
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    // The record behind the flush's last one belongs to no triangle: k_raster visits it when a cull round leaves an odd number of
-    // survivors (its visit loop runs in pairs).  Its depth plane is +inf everywhere, so no pixel is in front of its stored depth and
-    // the visit ends at its first test; should a pixel hold NaN (which lets every plane through), u.z = 1 > 0 = u.x + u.y fails coverage.
-    if (k == 0 && fp.n_tris) {
-        TriRec d;
-        d.ax = d.ay = d.s0x = d.s0y = d.s1x = d.s1y = 0.0; d.c0 = __builtin_inf(); d.uz = 1.0; d.g1 = d.g2 = 0.0;
-        d.ruz = 0.0; d.z0 = d.z1 = d.z2 = 0.0; d.bx0 = d.by0 = 1; d.bx1 = d.by1 = 0; d.color = 0; d.dl = 0;
-        recs[fp.n_tris] = d;
-    }
-    uint32_t nb = 0, t = 0, rows = 0;          // rows: bit r set = block row r of the tile gets an item
-    uint32_t beg = 0, end = 0;
-    bool clear_only = false;
-    if (k < ntiles_strip) {
-        t = (uint32_t)(fp.strip_ty0 * fp.tiles_x + k);
-        beg = tile_start[t]; end = tile_end[t];
-        if (end <= beg) beg = end = 0;         // an empty tile: the last radix pass leaves it at [~0, 0)
-        const uint32_t n = end - beg;
-        const int ty = (int)(t / (uint32_t)fp.tiles_x);
-        if ((n || fp.init_from_clear) && tile_row_owned(fp, ty)) {
-            if (n) {
-                for (int r = 0; r < 4; ++r) {
-                    const int y0 = ty * TRGL_TILE + 8 * r, y1 = y0 + 7;
-                    if (y0 < fp.H && y1 >= fp.strip_y0 && y0 < fp.strip_y1) rows |= 1u << r;
-                }
-                nb = (uint32_t)__popc(rows);
-            } else { clear_only = true; nb = 1; }
-        }
-    }
-    // wave-aggregated append (order of items is irrelevant)
-    uint32_t inc = nb;
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(inc, o); if (lane >= o) inc += v; }
-    const uint32_t total = __shfl(inc, 63);
-    uint32_t base = 0;
-    if (lane == 63 && total) base = atomicAdd(n_items, total);
-    base = __shfl(base, 63) + inc - nb;
-    // (an item carries its tile's slice of the pair list: one dependent load less at the start of every raster wave)
-    if (clear_only) items[base] = make_uint4(t | TRGL_ITEM_CLEAR, 0u, 0u, 0u);
-    else for (uint32_t r = 0; r < 4; ++r) if ((rows >> r) & 1u) items[base++] = make_uint4(t | (r << 24), beg, end, 0u);
-}
-
-// after the raster kernel of a flush: fold the per-item partials into the context's counters (our_gl.cpp:194-198) and fix the
-// sign of a zero z-range end (see DevStats).  FOLD_BLOCKS blocks take a slice each and add it with three atomics; the block
-// that finishes last (a counter behind a device-scope fence) settles the per-flush state.  (One block walking 65536 partials
-// took 39 us of a 2.9 ms frame.)
-constexpr int FOLD_BLOCKS = 32;
-__global__ __launch_bounds__(1024) void k_fold_stats(DevStats* __restrict__ s, uint32_t* __restrict__ n_items,
-                                                     const unsigned long long* __restrict__ item_stats) {
-    __shared__ unsigned long long sh[3][16];
-    __shared__ bool s_last;
-    const uint32_t n = *n_items;
-    unsigned long long fr = 0, kmin = ~0ull, kmax = 0ull;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const ulonglong2 a = reinterpret_cast<const ulonglong2*>(item_stats + (size_t)i * 4)[0];
-        const unsigned long long c = item_stats[(size_t)i * 4 + 2];
-        fr += a.x; kmin = a.y < kmin ? a.y : kmin; kmax = c > kmax ? c : kmax;
-    }
-    for (int o = 32; o; o >>= 1) {
-        fr += __shfl_xor(fr, o);
-        unsigned long long a = __shfl_xor(kmin, o); kmin = a < kmin ? a : kmin;
-        unsigned long long b = __shfl_xor(kmax, o); kmax = b > kmax ? b : kmax;
-    }
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { sh[0][w] = fr; sh[1][w] = kmin; sh[2][w] = kmax; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < (int)(blockDim.x >> 6); ++k) {
-            fr += sh[0][k]; kmin = sh[1][k] < kmin ? sh[1][k] : kmin; kmax = sh[2][k] > kmax ? sh[2][k] : kmax;
-        }
-        if (fr) {       // items without fragments carry the neutral keys
-            atomicAdd(&s->fragments, fr);
-            atomicMin(&s->zmin_key, kmin);
-            atomicMax(&s->zmax_key, kmax);
-        }
-        __threadfence();
-        s_last = atomicAdd(&n_items[1], 1u) == gridDim.x - 1;       // n_items[1]: blocks of this launch that are done
-    }
-    __syncthreads();
-    if (s_last && threadIdx.x == 0) {
-        __threadfence();
-        if (!s->zero_locked && (s->zero_pos_key != TRGL_ZERO_KEY_EMPTY || s->zero_neg_key != TRGL_ZERO_KEY_EMPTY)) {
-            s->zero_sign = s->zero_neg_key < s->zero_pos_key ? 1u : 0u;
-            s->zero_locked = 1u;
-        }
-        s->literal_tris = 0; s->large_tris = 0;    // counted per flush (k_setup)
-        s->zero_pos_key = TRGL_ZERO_KEY_EMPTY;
-        s->zero_neg_key = TRGL_ZERO_KEY_EMPTY;
-        n_items[0] = 0;         // every block read it before its atomic above; k_make_items of the next flush appends from 0
-        n_items[1] = 0;
-    }
-}
-
 }  // namespace
 
 namespace trgl {
 
-void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed, unsigned long long* mismatches) {
-    hipLaunchKernelGGL(k_selftest_division, dim3(1024), dim3(256), 0, s, n_per_thread, seed, mismatches);
+// a kernel compiled at run time (raster_user.h, shade_user.h), 256 threads per workgroup: its arguments by value, in its parameters' order
+template <class... Args>
+static void launch_user_kernel(hipFunction_t fn, uint32_t grid, hipStream_t s, Args... a) {
+    void* args[] = { &a... };
+    (void)hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, s, args, nullptr);
 }
-
-void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out) {
-    if (n) hipLaunchKernelGGL(k_selftest_sampler, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tex, slot, uv, n, out);
-}
-
-uint32_t owned_tiles(const FrameParams& fp) {
-    if (fp.il_tiles == 0) return (uint32_t)((fp.strip_ty1 - fp.strip_ty0) * fp.tiles_x);
-    return (uint32_t)(il_owned_below(fp, fp.tiles_y) * fp.tiles_x);
-}
-
-// at most four work items (rows of blocks) per owned tile
-uint32_t raster_max_items(const FrameParams& fp) { return owned_tiles(fp) * 4u; }
 
 void launch_raster(hipStream_t s, const FrameParams& fp, int kind /* TRGL_SHADER_* if uniform over the flush, else -1 */, bool all_well_scaled,
                    const TriRec* recs, const TriW* recs_w, const uint32_t* vals, const uint16_t* bmask,
@@ -1139,20 +790,16 @@ void launch_raster(hipStream_t s, const FrameParams& fp, int kind /* TRGL_SHADER
     if (tiles <= 0 || max_items == 0) {          // a context that owns no rows (a rank beyond the image's bands): nothing to draw
         if (ev_before) (void)hipEventRecord(ev_before, s);
         if (ev_after) (void)hipEventRecord(ev_after, s);
-        hipLaunchKernelGGL(k_fold_stats, dim3(FOLD_BLOCKS), dim3(1024), 0, s, stats, n_items, item_stats);     // n_items is 0: only resets the per-flush counts
+        launch_fold_stats(s, stats, n_items, item_stats);     // n_items is 0: only resets the per-flush counts
         return;
     }
-    hipLaunchKernelGGL(k_make_items, dim3((tiles + 255) / 256), dim3(256), 0, s, fp, tile_start, tile_end, items, n_items, const_cast<TriRec*>(recs));
-    dim3 grid(((max_items + 7u) / 8u) * 8u);    // workgroup b -> item (b mod 8) * ceil(G / 8) + b / 8 (k_raster)
+    launch_make_items(s, fp, tiles, tile_start, tile_end, items, n_items, const_cast<TriRec*>(recs));
+    dim3 grid(trgl_item_grid(max_items));       // the raster kernels; the shade kernels take one workgroup per item (work_items.h)
     if (ev_before) (void)hipEventRecord(ev_before, s);
     if (user_raster) {                          // a flush of one user kind that may discard: its own raster kernel (raster_user.h)
-        FrameParams fpa = fp; const TriRec* a1 = recs; const TriW* a2 = recs_w; const uint32_t* a3 = vals; const uint16_t* a4 = bmask;
-        const DrawDesc* a5 = draws; const DevTexture* a6 = tex; DevStats* a7 = stats; const uint4* a8 = items; const uint32_t* a9 = n_items;
-        unsigned long long* a10 = item_stats;
-        void* args[] = { &fpa, &a1, &a2, &a3, &a4, &a5, &a6, &a7, &a8, &a9, &a10 };
-        (void)hipModuleLaunchKernel(user_raster, grid.x, 1, 1, 256, 1, 1, 0, s, args, nullptr);
+        launch_user_kernel(user_raster, grid.x, s, fp, recs, recs_w, vals, bmask, draws, tex, stats, items, n_items, item_stats);
         if (ev_after) (void)hipEventRecord(ev_after, s);
-        hipLaunchKernelGGL(k_fold_stats, dim3(FOLD_BLOCKS), dim3(1024), 0, s, stats, n_items, item_stats);
+        launch_fold_stats(s, stats, n_items, item_stats);
         return;
     }
 #define TRGL_LAUNCH_RASTER(...) hipLaunchKernelGGL((k_raster<__VA_ARGS__>), grid, dim3(256), 0, s, fp, recs, recs_w, vals, bmask, tile_start, tile_end, draws, stats, items, n_items, item_stats)
@@ -1182,13 +829,8 @@ void launch_raster(hipStream_t s, const FrameParams& fp, int kind /* TRGL_SHADER
 #undef TRGL_LAUNCH_SHADE
     }
     // ... and those of every user kind of the flush, one kernel each, over the same work items (before k_fold_stats clears their count)
-    for (int i = 0; i < n_user && fp.idbuf; ++i) {
-        FrameParams fpa = fp; const TriRec* a1 = recs; const TriW* a2 = recs_w; const DrawDesc* a3 = draws; const DevTexture* a4 = tex;
-        const uint4* a5 = items; const uint32_t* a6 = n_items; int a7 = user[i].kind;
-        void* args[] = { &fpa, &a1, &a2, &a3, &a4, &a5, &a6, &a7 };
-        (void)hipModuleLaunchKernel(user[i].fn, max_items, 1, 1, 256, 1, 1, 0, s, args, nullptr);
-    }
-    hipLaunchKernelGGL(k_fold_stats, dim3(FOLD_BLOCKS), dim3(1024), 0, s, stats, n_items, item_stats);
+    for (int i = 0; i < n_user && fp.idbuf; ++i) launch_user_kernel(user[i].fn, max_items, s, fp, recs, recs_w, draws, tex, items, n_items, user[i].kind);
+    launch_fold_stats(s, stats, n_items, item_stats);
 }
 
 }  // namespace trgl

@@ -24,16 +24,13 @@
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"
 #include "launch.h"
+#include "device_util.h"
 
 namespace {
 
 using namespace trgl;
 
-__device__ __forceinline__ double dot4(const double* m, double x, double y, double z, double w) {
-    double sum = 0;                                   // geometry.h:122-127
-    sum += m[0] * x; sum += m[1] * y; sum += m[2] * z; sum += m[3] * w;
-    return sum;
-}
+using trgl_dev::dot4;
 
 constexpr uint32_t MAX_GRID = 1u << 20;               // tiles beyond it are walked by a grid-stride loop
 

@@ -1,10 +1,11 @@
-// launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_raster.hip, kernels_post.hip, kernels_mesh.hip,
-// kernels_image.hip, kernels_shadow.hip, kernels_clip.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
+// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"
 #include "clip_core.h"
+#include "work_items.h"
 
 namespace trgl {
 
@@ -58,9 +59,15 @@ void launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last,
 
 uint32_t owned_tiles(const FrameParams& fp);       // tiles of the rows this context owns (strip or interleaved bands)
 uint32_t raster_max_items(const FrameParams& fp);   // work items (workgroups of k_raster) of a flush, at most
+// The bookkeeping either side of the raster kernel (kernels_items.hip; launch_raster calls both).  launch_make_items: the work items
+// of the flush from the per-tile slices of the sorted pair list, over the `tiles` tiles of the context's strip; it also writes the
+// record behind the flush's last one (recs[fp.n_tris]).  launch_fold_stats: the items' partials into *stats; resets the per-flush counts.
+void launch_make_items(hipStream_t s, const FrameParams& fp, int tiles, const uint32_t* tile_start, const uint32_t* tile_end, uint4* items,
+                       uint32_t* n_items, TriRec* recs);
+void launch_fold_stats(hipStream_t s, DevStats* stats, uint32_t* n_items, const unsigned long long* item_stats);
 // the shade kernel of one user kind of a flush (shade_user.h, loaded by trgl_register_shader)
 struct UserShade { hipFunction_t fn; int kind; };
-// item_stats: 4 x uint64 per work item (one partial of the counters per workgroup)
+// item_stats: TRGL_ITEM_STATS_WORDS x uint64 per work item (work_items.h: one partial of the counters per workgroup)
 // builtin_shade: the flush has PHONG / EYE draws (k_shade runs); user[0..n_user): the user kinds it has, shaded behind it
 // user_raster: the raster kernel of a user kind that may discard (raster_user.h), which runs in place of k_raster when the flush
 // holds only draws of that kind; null: k_raster

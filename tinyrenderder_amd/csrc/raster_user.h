@@ -28,27 +28,21 @@ void trgl_raster_user(FrameParams fp, const TriRec* __restrict__ recs, const Tri
     __shared__ unsigned long long s_red[4][3];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // work item of this workgroup: the mapping of k_raster (each group of eight consecutive workgroups, which the dispatcher deals to
-    // the eight XCDs, takes items one eighth of the list apart, so that neighbouring items share an L2; speed only)
-    const uint32_t G = n_items[0];
-    const uint32_t per = (G + 7u) >> 3, xj = blockIdx.x >> 3;
-    const uint32_t g = (blockIdx.x & 7u) * per + xj;
-    if (xj >= per || g >= G) return;                      // (workgroup-uniform: the barrier at the end is safe)
+    uint32_t g;                                           // this workgroup's item: the mapping of k_raster (work_items.h)
+    if (!trgl_item_of_workgroup(blockIdx.x, n_items[0], &g)) return;   // (workgroup-uniform: the barrier at the end is safe)
     const uint4 item4 = items[g];
     const uint32_t item = item4.x;
-    const int t = (int)(item & 0xffffffu);
+    const int t = (int)trgl_item_tile(item);
     const int tile_y = t / fp.tiles_x, tile_x = t - tile_y * fp.tiles_x;
     const int px0 = tile_x << TRGL_TILE_LOG2, py0 = tile_y << TRGL_TILE_LOG2;
-    unsigned long long* my_stats = item_stats + (size_t)g * 4;
+    unsigned long long* my_stats = item_stats + (size_t)g * TRGL_ITEM_STATS_WORDS;
     if (item & TRGL_ITEM_CLEAR) {                         // cleared and empty: the clear values, as k_raster stores them
         const int ya = max(py0 + 8 * w, fp.strip_y0), yb = min(min(py0 + 8 * w + 7, fp.H - 1), fp.strip_y1 - 1);
         if (ya <= yb) trgl_shade::clear_rows(fp, lane, px0, ya, yb);
-        if (threadIdx.x == 0) {
-            my_stats[0] = 0ull; my_stats[1] = ~0ull; my_stats[2] = 0ull; my_stats[3] = 0ull;
-        }
+        if (threadIdx.x == 0) trgl_item_stats_store(my_stats, 0ull, TRGL_ITEM_KMIN_NONE, TRGL_ITEM_KMAX_NONE);
         return;
     }
-    const int brow = (int)((item >> 24) & 3u);
+    const int brow = (int)trgl_item_brow(item);
     const int kblk = 4 * brow + w;                        // this wave's block of the tile: bit 4 cy + cx of the pair masks
     const int X0 = px0 + 8 * w, Y0 = py0 + 8 * brow;
     const int x = X0 + (lane & 7), y = Y0 + (lane >> 3);
@@ -129,7 +123,7 @@ void trgl_raster_user(FrameParams fp, const TriRec* __restrict__ recs, const Tri
         fp.zb[pix] = z;
         if (fp.init_from_clear || frags) trgl_shade::store_pixel(fp, pix, color);
     }
-    // ---- one partial of our_gl.cpp:194-198 per work item, in k_raster's layout: fragments, smallest and largest depth key, 0
+    // ---- one partial of our_gl.cpp:194-198 per work item, in k_raster's layout (work_items.h)
     // (the smallest depth a pixel was written with is its last one: the z-test only lets smaller ones through)
     unsigned long long fr = frags, kmin = zkey(frags ? z : __builtin_inf()), kmax = zkey(zmax);
     for (int o = 32; o; o >>= 1) {
@@ -143,6 +137,6 @@ void trgl_raster_user(FrameParams fp, const TriRec* __restrict__ recs, const Tri
         for (int k = 1; k < 4; ++k) {
             fr += s_red[k][0]; kmin = s_red[k][1] < kmin ? s_red[k][1] : kmin; kmax = s_red[k][2] > kmax ? s_red[k][2] : kmax;
         }
-        my_stats[0] = fr; my_stats[1] = kmin; my_stats[2] = kmax; my_stats[3] = 0ull;
+        trgl_item_stats_store(my_stats, fr, kmin, kmax);
     }
 }

@@ -1,12 +1,10 @@
 // shade_common.h — device code shared by k_raster / k_shade (kernels_raster.hip) and the kernels of user shaders, which hiprtc
 // compiles at run time from shade_user.h and raster_user.h (user_shaders.cpp embeds this file as text).  One copy of the samplers,
-// of the division by u.z, of the per-pixel prologue of deferred shading and of the store of a cleared tile.
+// of the division by u.z, of the per-pixel prologue of deferred shading and of the store of a cleared tile; the work items these
+// kernels take are work_items.h's.
 #pragma once
 #include "trgl_device.h"
-
-// Work items (k_make_items): one per workgroup.
-//   bits 0-23 tile, bits 24-25 row of blocks inside the tile, bit 31: the tile has no triangles and is only cleared
-#define TRGL_ITEM_CLEAR 0x80000000u
+#include "work_items.h"
 
 namespace trgl_shade {
 

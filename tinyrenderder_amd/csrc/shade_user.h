@@ -17,10 +17,10 @@ void trgl_shade_user(FrameParams fp, const TriRec* __restrict__ recs, const TriW
     if (item_idx >= *n_items) return;
     const uint32_t item = items[item_idx].x;
     if (item & TRGL_ITEM_CLEAR) return;                  // no triangles: no owners
-    const int t = (int)(item & 0xffffffu);
+    const int t = (int)trgl_item_tile(item);
     const int tile_y = t / fp.tiles_x, tile_x = t - tile_y * fp.tiles_x;
     const int x = (tile_x << TRGL_TILE_LOG2) + 8 * (int)(threadIdx.x >> 6) + (lane & 7);
-    const int y = (tile_y << TRGL_TILE_LOG2) + 8 * (int)((item >> 24) & 3u) + (lane >> 3);
+    const int y = (tile_y << TRGL_TILE_LOG2) + 8 * (int)trgl_item_brow(item) + (lane >> 3);
     const bool mine = x < fp.W && y < fp.H && y >= fp.strip_y0 && y < fp.strip_y1;
     const size_t idx = (size_t)x + (size_t)y * fp.W;
     const uint32_t dl = mine ? fp.idbuf[idx] : 0xffffffffu;

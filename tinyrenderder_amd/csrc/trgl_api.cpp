@@ -506,7 +506,7 @@ int trgl_flush_end(trgl_ctx* c) {
     // one work item (a workgroup of four block waves) per row of blocks of every owned tile
     const uint32_t max_items = raster_max_items(fp);
     if ((r = c->items.grow(c, (size_t)max_items + 64))) return r;
-    if ((r = c->item_stats.grow(c, ((size_t)max_items + 64) * 4))) return r;
+    if ((r = c->item_stats.grow(c, ((size_t)max_items + 64) * TRGL_ITEM_STATS_WORDS))) return r;
     // k_setup counted the triangles that are not well scaled (it came over with the pair count): without any, the kernel without the literal path
     const bool all_well_scaled = N == 0 || c->stats_pinned->literal_tris == 0;
     fp.zq_cull = (N != 0 && c->stats_pinned->large_tris != 0) ? 1 : 0;      // (k_setup counted them; the count came over with the pair count)
