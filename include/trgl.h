@@ -654,6 +654,67 @@ int trgl_image_modulate(trgl_ctx* ctx, uint8_t* pixels, int w, int h, int bpp, c
  * every row is multiplied, the rows of other ranks as stale afterwards as before. */
 int trgl_framebuffer_modulate(trgl_ctx* ctx, const uint8_t* mask, int mask_mem_kind);
 
+/* ---- occlusion culling of model boxes against resident depths ---------------------------------------------- */
+
+/* New work: the reference decides per model with frustum.intersects(worldAABB) alone (main.cpp:647,680,706).  These calls answer the other
+ * half - is the box hidden behind what is already drawn - from depths that are resident anyway: the z-buffer, or a trgl_zbuffer_snapshot
+ * (a depth pre-pass, the previous frame).  One code byte per box; bit 0 set means "draw it".
+ *
+ * A box is 6 doubles, min.xyz then max.xyz.  M is the caller's row-major matrix (Perspective * ModelView for world-space boxes, main.cpp:623),
+ * V the viewport matrix, the depth image w x h with index x + y * w.  All arithmetic is fp64 without contraction, in this order:
+ *  1. corner k = 0..7, x fastest, then y, then z, as AABB::transform takes them (geometry.h:297-327):
+ *     p = (k&1 ? max.x : min.x, k&2 ? max.y : min.y, k&4 ? max.z : min.z, 1.0); clip[r] = the sum from 0.0 of M[r][c] * p[c], c = 0..3 in
+ *     that order.
+ *  2. any corner with !(clip[3] > 1e-12) (our_gl.cpp:94; a NaN lands here): TRGL_OCCL_UNDECIDED - the box reaches the eye plane and its
+ *     projection bounds nothing.
+ *  3. ndc = clip / clip[3], four true divisions; any of ndc[0..3] not finite: TRGL_OCCL_UNDECIDED (ndc[3] is 1.0 unless clip[3] is +inf;
+ *     our_gl.cpp:109-114 rejects only the faces that hold such a corner, so nothing is concluded for the box).
+ *  4. zmin, zmax = the minimum and maximum of ndc[2] over the corners; zmin > 1.0 || zmax < -1.0: TRGL_OCCL_OUTSIDE (every face is
+ *     rejected at our_gl.cpp:103-106).
+ *  5. s = V * ndc, x and y only, each the sum from 0.0 over c = 0..3, as the setup stage evaluates Viewport * ndc (our_gl.cpp:117-121).
+ *     A NaN among the 16 coordinates: TRGL_OCCL_UNDECIDED, whatever step 4 found.  With (int) the reference's x86-64 cast (NaN or out of range: INT_MIN), the
+ *     rectangle is that of our_gl.cpp:130-133: x0 = max(0, (int)floor(min sx)), x1 = min(w - 1, (int)ceil(max sx)), likewise y0, y1.
+ *     Where ceil(max sx) or ceil(max sy) is >= 2147483648.0 the cast turns a bound far to the right into INT_MIN, while a face that lacks the far
+ *     corner can still own pixels: TRGL_OCCL_UNDECIDED.  Otherwise an empty rectangle (x0 > x1 || y0 > y1): TRGL_OCCL_OUTSIDE.
+ *  6. Z = max(fabs(zmin), fabs(zmax)); zq = zmin - Z * 2^-40 (the scaling is exact, the subtraction rounds once).  our_gl.cpp:156-158
+ *     interpolates a pixel's depth from rounded barycentrics that lie in [0, 1] and sum to 1 within a few ulp, so that depth can fall
+ *     below the smallest vertex depth by a few 2^-53 * Z; 2^-40 * Z covers that with three orders of magnitude to spare.
+ *  7. TRGL_OCCL_VISIBLE if some pixel of the rectangle holds zq < depth[x + y * w], else TRGL_OCCL_HIDDEN.  A NaN depth is never such a
+ *     pixel (nothing passes our_gl.cpp:165 against it); +inf always is.
+ * The guarantee and its limit: for TRGL_OCCL_HIDDEN and TRGL_OCCL_OUTSIDE the 12 faces of the box built from those same 8 clip corners,
+ * in either winding, draw no fragment through rasterize() onto these depths.  A model inside the box inherits that only up to the
+ * rounding of its own vertex transform - its vertices are not the box's corners - and nothing is promised about depths that change
+ * between the query and the draw.
+ *
+ * TRGL_MEM_HOST on the image form: plain C++, ctx may be NULL, no GPU is touched.  TRGL_MEM_DEVICE: needs a context; the work is queued
+ * on the context's stream in order with everything else, nothing is flushed and the call does not wait.  depth and boxes are 8-byte
+ * aligned (16-byte aligned rows of depth are read in 16-byte loads); codes needs no alignment.  On the device a first kernel leaves
+ * two levels over the depths - the maximum of each 8 x 8 and of each 64 x 64 pixel block, a NaN counting as -inf, edge blocks covering
+ * the pixels that exist - and one wavefront per box reads whole blocks inside its rectangle from those levels and only the border
+ * from the depths; a maximum does not depend on the order it is taken in, so the codes equal step 7's scan of every pixel.  The levels
+ * are rebuilt by every call (w * h * 8 bytes read once): batch the boxes.  Scratch memory belongs to the context, grows on demand and
+ * is freed by trgl_destroy.
+ * TRGL_E_INVALID: a null array with n > 0 (depth only for a non-empty image), a null matrix, a negative size, a bad mem_kind or slot,
+ * TRGL_MEM_DEVICE without a context.  TRGL_E_UNSUPPORTED: w * h or n above INT_MAX.  n == 0: TRGL_OK, nothing is read or written.  An
+ * empty image (w * h == 0) with n > 0: depth is not read and step 5 finds every rectangle empty. */
+#define TRGL_OCCL_HIDDEN    0
+#define TRGL_OCCL_VISIBLE   1
+#define TRGL_OCCL_OUTSIDE   2
+#define TRGL_OCCL_UNDECIDED 3
+
+/* The codes of n boxes against a w x h depth image (steps 1-7 above); one mem_kind covers depth, boxes and codes. */
+int trgl_occlusion_boxes_image(trgl_ctx* ctx, const double* depth, int w, int h, const double viewport[16],
+                               const double view_proj[16], const double* boxes, uint64_t n, uint8_t* codes, int mem_kind);
+
+/* The resident form: the depths are the context's z-buffer (snapshot_slot = -1) or those of a snapshot slot, V the context's Viewport.
+ * Completes a begun flush and flushes what is queued (a pending trgl_clear included), as trgl_shadow_mask does, then queues its
+ * kernels; waits only when codes is host memory (the n bytes then cross PCIe once).  Host boxes are first copied to the device by a
+ * copy queued on the context's stream, under the rule written at trgl_framebuffer_modulate for its host mask.  The frame, the depths,
+ * the snapshots and the counters stay untouched.  TRGL_E_STATE for a slot that holds nothing, and on a context with a strip or
+ * interleaved bands set (its depths hold only that rank's rows). */
+int trgl_occlusion_boxes(trgl_ctx* ctx, const double view_proj[16], const double* boxes, uint64_t n, int boxes_mem_kind,
+                         int snapshot_slot, uint8_t* codes, int codes_mem_kind);
+
 /* ---- TGA writer and reader (host only) ------------------------------------- */
 
 /* Replaces: TGAImage::write_tga_file(name, vflip, rle) (tgaimage.cpp:161-242): produces exactly the bytes the

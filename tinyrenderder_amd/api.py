@@ -27,6 +27,7 @@ MAX_Z_SNAPSHOTS = 4           # TRGL_MAX_Z_SNAPSHOTS
 MAX_BLUR_RADIUS = 46340       # TRGL_MAX_BLUR_RADIUS
 MAX_PCF_RADIUS = 4            # TRGL_MAX_PCF_RADIUS
 MAX_CLIP_ATTRS = 24           # TRGL_MAX_CLIP_ATTRS
+OCCL_HIDDEN, OCCL_VISIBLE, OCCL_OUTSIDE, OCCL_UNDECIDED = range(4)     # TRGL_OCCL_*: bit 0 set = draw it
 NEAR_PLANE = (0.0, 0.0, 1.0, 1.0)     # the near plane of the reference's projection in clip space: z + w >= 0
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
 
@@ -48,6 +49,7 @@ SYMBOLS = [
     "trgl_gaussian_kernel", "trgl_image_blur", "trgl_image_scale", "trgl_framebuffer_blur",
     "trgl_shadow_matrix", "trgl_shadow_mask_image", "trgl_shadow_mask", "trgl_image_modulate", "trgl_framebuffer_modulate",
     "trgl_clip_layout", "trgl_clip_stage", "trgl_draw_clipped", "trgl_draw_indexed_vs_clipped",
+    "trgl_occlusion_boxes_image", "trgl_occlusion_boxes",
 ]
 
 
@@ -234,6 +236,8 @@ def load_library(path: str = None):
     L.trgl_draw_clipped.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, cap, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
     L.trgl_draw_indexed_vs_clipped.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Uniforms), dp, dp, cap, C.c_int, C.c_void_p, C.c_int, C.c_uint64,
                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+    L.trgl_occlusion_boxes_image.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, dp, dp, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+    L.trgl_occlusion_boxes.argtypes = [vp, dp, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -494,6 +498,34 @@ def image_modulate(img, mask) -> np.ndarray:
     """trgl_image_modulate for host arrays without a context: a copy of img [h, w, bpp] uint8 with its colour channels multiplied by
     mask [h, w] / 255 (main.cpp:775-781); alpha stays.  Needs no GPU."""
     return _host_image_modulate(load_library(), None, img, mask)
+
+
+def _boxes_count(boxes):
+    if len(boxes.shape) != 2 or boxes.shape[1] != 6:
+        raise ValueError("occlusion: boxes must be [n, 6] (min.xyz, max.xyz)")
+    return int(boxes.shape[0])
+
+
+def _occlusion_boxes_image(L, handle, dptr, depth, viewport, view_proj, bptr, n, optr, device):
+    h, w = _depth_dims(depth, "occlusion_boxes_image: depth")
+    rc = L.trgl_occlusion_boxes_image(handle, dptr, w, h, _dp(_f64(viewport, 16, "viewport")), _dp(_f64(view_proj, 16, "view_proj")),
+                                      bptr, n, optr, MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_occlusion_boxes_image failed ({rc}): {L.trgl_last_error(handle).decode()}")
+
+
+def _host_occlusion_boxes_image(L, handle, depth, viewport, view_proj, boxes):
+    depth, boxes = np.ascontiguousarray(depth, np.float64), np.ascontiguousarray(boxes, np.float64)
+    out = np.empty(_boxes_count(boxes), np.uint8)
+    _occlusion_boxes_image(L, handle, depth.ctypes.data, depth, viewport, view_proj, boxes.ctypes.data, out.size, out.ctypes.data, False)
+    return out
+
+
+def occlusion_boxes_image(depth, viewport, view_proj, boxes) -> np.ndarray:
+    """trgl_occlusion_boxes_image for host arrays without a context: one OCCL_* code (uint8) per box [n, 6] = (min.xyz, max.xyz) against
+    the depths [h, w] under the row-major viewport and view_proj = Perspective * ModelView (the steps are written down in include/trgl.h).
+    Bit 0 of a code set: draw the model.  Needs no GPU."""
+    return _host_occlusion_boxes_image(load_library(), None, depth, viewport, view_proj, boxes)
 
 
 def clip_layout(kind: int):
@@ -961,6 +993,47 @@ class Context:
         if int(np.prod(tuple(mask.shape))) != self.width * self.height:
             raise ValueError("framebuffer_modulate: the mask must hold W * H bytes")
         self._chk(self.L.trgl_framebuffer_modulate(self.h, ptr, MEM_DEVICE if device else MEM_HOST))
+
+    def occlusion_boxes_image(self, depth, viewport, view_proj, boxes, device=False, out=None):
+        """trgl_occlusion_boxes_image; returns the [n] uint8 codes.  Host arrays: no GPU work.  device=True: depth [h, w] and boxes [n, 6] are
+        contiguous float64 device tensors, queried on the context's stream in order with everything else (nothing is flushed, the call
+        does not wait); `out` (uint8 [n], any alignment) is allocated with torch when not given."""
+        if not device:
+            return _host_occlusion_boxes_image(self.L, self.h, depth, viewport, view_proj, boxes)
+        for t, what in ((depth, "depth"), (boxes, "boxes")):
+            if not hasattr(t, "data_ptr") or str(t.dtype) != "torch.float64" or not t.is_contiguous():
+                raise ValueError(f"device=True: {what} must be a contiguous float64 device tensor")
+        n = _boxes_count(boxes)
+        if out is None:
+            import torch
+            out = torch.empty(n, dtype=torch.uint8, device=boxes.device)
+        elif tuple(out.shape) != (n,):
+            raise ValueError("occlusion_boxes_image: out must be [n]")
+        self._keep.append((depth, boxes, out))
+        _occlusion_boxes_image(self.L, self.h, _device_ptr(depth, "depth"), depth, viewport, view_proj, _device_ptr(boxes, "boxes"), n,
+                               _device_image(out, "out"), True)
+        return out
+
+    def occlusion_boxes(self, view_proj, boxes, snapshot=None, device=False):
+        """trgl_occlusion_boxes: one OCCL_* code per box [n, 6] against the resident z-buffer (snapshot=None) or the depths of a snapshot
+        slot, under the context's viewport (flushes what is queued).  Host boxes give a uint8 numpy array (the call waits for it);
+        device=True takes a contiguous float64 device tensor and returns a device tensor without waiting.  Not on a strip / band context."""
+        if not device:
+            boxes = np.ascontiguousarray(boxes, np.float64)
+        n = _boxes_count(boxes)
+        m = _dp(_f64(view_proj, 16, "view_proj"))
+        slot = -1 if snapshot is None else int(snapshot)
+        if device:
+            if str(boxes.dtype) != "torch.float64" or not boxes.is_contiguous():
+                raise ValueError("device=True: boxes must be a contiguous float64 device tensor")
+            import torch
+            out = torch.empty(n, dtype=torch.uint8, device=boxes.device)
+            self._keep.append((boxes, out))
+            self._chk(self.L.trgl_occlusion_boxes(self.h, m, _device_ptr(boxes, "boxes"), n, MEM_DEVICE, slot, _device_ptr(out, "out"), MEM_DEVICE))
+            return out
+        out = np.empty(n, np.uint8)
+        self._chk(self.L.trgl_occlusion_boxes(self.h, m, boxes.ctypes.data, n, MEM_HOST, slot, out.ctypes.data, MEM_HOST))
+        return out
 
     def zbuffer_snapshot(self, slot=0):
         """trgl_zbuffer_snapshot: main.cpp:700 as one device-to-device copy (flushes what is queued, does not wait)."""

@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -145,6 +145,23 @@ uint32_t clip_num_blocks(uint64_t n);
 size_t clip_scratch_words(uint64_t n);       // the block sums and, behind them, the sums of the scan's chunks
 // scratch: clip_scratch_words(n) words; *total receives the number of output triangles.  Four launches, in order on `s`.
 void launch_clip_stage(hipStream_t s, const ClipArgs& a, uint32_t* scratch, unsigned long long* total);
+
+// Occlusion culling of boxes (kernels_occlusion.hip; the test is written down at trgl_occlusion_boxes_image in include/trgl.h, steps 1-6
+// are occlusion_core.h's).  levels: occl_level_doubles(w, h) doubles of scratch - level 1, ceil(w / 8) x ceil(h / 8) maxima of the 8 x 8
+// pixel blocks, then level 2, ceil(w / 64) x ceil(h / 64) maxima of the 64 x 64 blocks; a NaN depth counts as -inf, an edge block covers
+// the pixels that exist.  depth and boxes 8-byte aligned, codes at any address; w * h and n in 0..INT_MAX.
+constexpr int OCCL_L1 = 8, OCCL_L2 = 64;     // pixels along a block's side at the two levels; a workgroup of the build owns one level-2 block
+constexpr int OCCL_QUERY_BOXES = 4;          // boxes of a workgroup of the query, one wavefront each
+size_t occl_level_doubles(int w, int h);
+// one pass over the w * h depths (w * h > 0) that leaves both levels
+void launch_occl_build(hipStream_t s, const double* depth, int w, int h, double* levels);
+// The struct travels as the query kernel's argument.  With w * h == 0 neither depth nor levels is read.
+struct OcclArgs {
+    double M[16]; double V[8];               // view_proj, rows 0 and 1 of the viewport matrix
+    const double* depth; const double* levels; const double* boxes; uint8_t* codes;
+    uint64_t n; int32_t w, h;
+};
+void launch_occl_query(hipStream_t s, const OcclArgs& a);
 
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,

@@ -87,6 +87,9 @@ struct trgl_ctx {
     float* blur_w_pinned = nullptr; size_t blur_w_pinned_cap = 0; hipEvent_t ev_blur_w = nullptr;
     DevBuf<uint32_t> clip_scratch;      // trgl_clip_stage and the clipped draws: the 8-byte count of outputs, then the words of the stage's scan; grows on demand
     DevBuf<uint8_t> shadow_tmp;         // trgl_shadow_mask / trgl_framebuffer_modulate with a host mask: the W * H bytes on their way; grows on demand
+    // trgl_occlusion_boxes(_image): the two levels of block maxima over the depths, rebuilt by every call; host boxes and the codes for a
+    // host array on their way; grow on demand
+    DevBuf<double> occl_levels, occl_boxes; DevBuf<uint8_t> occl_codes;
     DevBuf<uint8_t> pp_out;             // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
     DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
@@ -175,4 +178,7 @@ int host_mesh_attr(bool tangents, double* vertices, int stride, uint64_t n, cons
 // the clip stage over host arrays (outputs with room for 2 n triangles); returns the number of output triangles
 uint64_t host_clip_stage(const double plane[4], const ClipTable& tab, int K, const double* clip, const double* vary, const uint32_t* colors,
                          uint64_t n, double* clip_out, double* vary_out, uint32_t* colors_out);
+// the codes of n boxes against a w x h depth image in host memory (depth is not read when w * h == 0)
+void host_occlusion_boxes(const double* depth, int w, int h, const double viewport[16], const double view_proj[16],
+                          const double* boxes, uint64_t n, uint8_t* codes);
 }  // namespace trgl

@@ -12,6 +12,7 @@
 
 #include "../../include/trgl.h"
 #include "clip_core.h"
+#include "occlusion_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -135,6 +136,28 @@ uint64_t host_clip_stage(const double plane[4], const ClipTable& tab, int K, con
         }
     }
     return o;
+}
+
+// ---- occlusion culling of boxes against a depth image in host memory (include/trgl.h, trgl_occlusion_boxes_image; steps 1-6 are
+// occlusion_core.h's, step 7 a scan of the rectangle) -----------------------------------------------------------------------------------
+void host_occlusion_boxes(const double* depth, int w, int h, const double viewport[16], const double view_proj[16],
+                          const double* boxes, uint64_t n, uint8_t* codes) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const double* box = boxes + 6 * i;
+        OcclFold f = occl_corner(view_proj, viewport, box, 0);
+        for (int k = 1; k < 8; ++k) f = occl_merge(f, occl_corner(view_proj, viewport, box, k));
+        OcclRect r;
+        int code = occl_decide(f, w, h, &r);
+        if (code < 0) {
+            code = TRGL_OCCL_HIDDEN;
+            for (int y = r.y0; y <= r.y1 && code == TRGL_OCCL_HIDDEN; ++y) {
+                const double* row = depth + (size_t)y * (size_t)w;
+                for (int x = r.x0; x <= r.x1; ++x)
+                    if (r.zq < row[x]) { code = TRGL_OCCL_VISIBLE; break; }                          // a NaN never, +inf always
+            }
+        }
+        codes[i] = (uint8_t)code;
+    }
 }
 }  // namespace trgl
 using namespace trgl;

@@ -1,5 +1,5 @@
 // trgl_passes.cpp — the optional passes of include/trgl.h over finished frames and over caller-owned images and meshes: SSAO post-process,
-// z-buffer snapshots, blur and scale, the shadow mask and modulate, mesh bounds and attributes in device memory, the two self-tests.
+// z-buffer snapshots, blur and scale, the shadow mask and modulate, occlusion culling of boxes, mesh bounds and attributes in device memory, the two self-tests.
 // None of them knows the flush pipeline of trgl_api.cpp: each finishes what is pending (end_pending_raster, trgl_flush, flush_sync), then
 // launches on the context's stream.  With TRGL_MEM_HOST the work is done by the host loops (trgl_host.cpp, shim/trgl_image.h).
 #include <climits>
@@ -63,6 +63,24 @@ static ShadowArgs shadow_args(const trgl_shadow_params* p, const double* depth, 
     a.depth = depth; a.map = map; a.mask = mask;
     a.w = w; a.h = h; a.map_w = map_w; a.map_h = map_h; a.radius = p->pcf_radius;
     return a;
+}
+
+// ---- occlusion culling of boxes (include/trgl.h; host loop in trgl_host.cpp, kernels in kernels_occlusion.hip) ------------------------
+// Both kernels over device arrays, queued on the stream: the levels of the depths, then one wavefront per box.  n > 0, w * h <= INT_MAX.
+static int queue_occlusion(trgl_ctx* c, const double* depth, int w, int h, const double* viewport, const double* view_proj,
+                           const double* boxes, uint64_t n, uint8_t* codes) {
+    OcclArgs a;
+    std::memcpy(a.M, view_proj, sizeof(a.M));
+    std::memcpy(a.V, viewport, sizeof(a.V));
+    a.depth = depth; a.levels = nullptr; a.boxes = boxes; a.codes = codes; a.n = n; a.w = w; a.h = h;
+    if (w > 0 && h > 0) {
+        if (int r = c->occl_levels.grow(c, occl_level_doubles(w, h))) return r;
+        launch_occl_build(c->stream, depth, w, h, c->occl_levels.p);
+        a.levels = c->occl_levels.p;
+    }
+    launch_occl_query(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
 }
 
 // ---- Model::generateNormalsIfNeeded (model.cpp:269-316) and Model::computeTangentsIfNeeded (model.cpp:318-388) ----------------------
@@ -322,6 +340,52 @@ int trgl_framebuffer_modulate(trgl_ctx* c, const uint8_t* mask, int mask_mem_kin
     }
     launch_modulate(c->stream, c->fb.p, npx, c->bpp, mask);
     HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_occlusion_boxes_image(trgl_ctx* c, const double* depth, int w, int h, const double viewport[16], const double view_proj[16],
+                               const double* boxes, uint64_t n, uint8_t* codes, int mem_kind) {
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_occlusion_boxes_image: bad mem_kind");
+    if (w < 0 || h < 0) return fail(c, TRGL_E_INVALID, "trgl_occlusion_boxes_image: a negative dimension");
+    if (!viewport || !view_proj) return fail(c, TRGL_E_INVALID, "trgl_occlusion_boxes_image: null matrix");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_occlusion_boxes_image: TRGL_MEM_DEVICE needs a context");
+    if (n == 0) return TRGL_OK;
+    const bool empty = w == 0 || h == 0;
+    if (!boxes || !codes || (!depth && !empty)) return fail(c, TRGL_E_INVALID, "trgl_occlusion_boxes_image: null array");
+    if ((int64_t)w * h > INT_MAX || n > (uint64_t)INT_MAX) return fail(c, TRGL_E_UNSUPPORTED, "trgl_occlusion_boxes_image: w * h or n above INT_MAX");
+    if (mem_kind == TRGL_MEM_HOST) { host_occlusion_boxes(depth, w, h, viewport, view_proj, boxes, n, codes); return TRGL_OK; }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    return queue_occlusion(c, depth, w, h, viewport, view_proj, boxes, n, codes);
+}
+
+int trgl_occlusion_boxes(trgl_ctx* c, const double view_proj[16], const double* boxes, uint64_t n, int boxes_mem_kind, int slot,
+                         uint8_t* codes, int codes_mem_kind) {
+    CHKCTX(c);
+    if (!valid_mem_kind(boxes_mem_kind) || !valid_mem_kind(codes_mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_occlusion_boxes: bad mem_kind");
+    if (slot != -1) { if (int r = zsnap_slot(c, slot, "trgl_occlusion_boxes")) return r; }
+    if (!view_proj) return fail(c, TRGL_E_INVALID, "trgl_occlusion_boxes: view_proj is null");
+    if (n && (!boxes || !codes)) return fail(c, TRGL_E_INVALID, "trgl_occlusion_boxes: null array");
+    if (!owns_whole_frame(c))
+        return fail(c, TRGL_E_STATE, "trgl_occlusion_boxes: the context owns a strip or interleaved bands; its depths hold only this rank's rows (gather with with_z and query on one context)");
+    if (slot >= 0 && !c->zsnap[slot].p) return fail(c, TRGL_E_STATE, "trgl_occlusion_boxes: the slot holds no snapshot");
+    if ((int64_t)c->W * c->H > INT_MAX || n > (uint64_t)INT_MAX) return fail(c, TRGL_E_UNSUPPORTED, "trgl_occlusion_boxes: W * H or n above INT_MAX");
+    if (n == 0) return TRGL_OK;
+    int r = trgl_flush(c); if (r) return r;            // completes a begun flush, draws what is queued, runs a pending clear
+    const double* d_boxes = boxes;
+    if (boxes_mem_kind == TRGL_MEM_HOST) {
+        if ((r = c->occl_boxes.grow(c, 6 * (size_t)n))) return r;
+        // in stream order behind an earlier query that may still read occl_boxes; pinned boxes are read when the stream gets here (include/trgl.h)
+        HIPCHK(c, hipMemcpyAsync(c->occl_boxes.p, boxes, 6 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        d_boxes = c->occl_boxes.p;
+    }
+    uint8_t* d_codes = codes;
+    if (codes_mem_kind == TRGL_MEM_HOST) { if ((r = c->occl_codes.grow(c, (size_t)n))) return r; d_codes = c->occl_codes.p; }
+    if ((r = queue_occlusion(c, slot < 0 ? c->zb.p : c->zsnap[slot].p, c->W, c->H, c->vp, view_proj, d_boxes, n, d_codes))) return r;
+    if (codes_mem_kind == TRGL_MEM_HOST) {
+        HIPCHK(c, hipMemcpyAsync(codes, d_codes, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return TRGL_OK;
 }
 

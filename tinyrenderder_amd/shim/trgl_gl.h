@@ -630,6 +630,37 @@ inline bool gl_modulate(TGAImage& framebuffer, const TGAImage& mask) {
     return TRGL_SHIM_OK(trgl_framebuffer_modulate(s.ctx, image_bytes(mask), TRGL_MEM_HOST)) && ok;
 }
 
+// Occlusion culling of model boxes (include/trgl.h, "occlusion culling of model boxes"; new work - the reference culls with
+// frustum.intersects alone, main.cpp:647,680,706).  gl_occlusion_test asks for every box - world-space boxes with
+// view_proj = Perspective * ModelView, main.cpp:623 - whether it is hidden behind the depths in HBM (snapshot_slot = -1: the z-buffer as it
+// is once the triangles batched so far are drawn; else the depths kept by gl_zbuffer_snapshot) under the current Viewport; the call waits
+// for the codes, one TRGL_OCCL_* byte per box.  gl_occlusion_draw(code) is the other half of `if (frustum.intersects(box))`.  A call
+// that fails (gl_last_error()) answers TRGL_OCCL_UNDECIDED for every box: draw them all.
+inline std::vector<std::uint8_t> gl_occlusion_test(const std::vector<AABB>& boxes, const mat<4, 4>& view_proj, int snapshot_slot = -1) {
+    using namespace trgl_shim;
+    State& s = state();
+    std::vector<std::uint8_t> codes(boxes.size(), std::uint8_t(TRGL_OCCL_UNDECIDED));
+    if (boxes.empty()) return codes;
+    if (!s.ctx) { fail("gl_occlusion_test: nothing has been drawn yet", TRGL_E_STATE, nullptr); return codes; }
+    bool ok = submit_batch();
+    if (s.zbuffer_dirty_on_host && zbuffer.raw().size() == std::size_t(s.w) * s.h) {      // depths the host wrote since the last draw, as bind() uploads them
+        ok = TRGL_SHIM_OK(trgl_write_zbuffer(s.ctx, zbuffer.raw().data())) && ok;
+        s.zbuffer_dirty_on_host = false; s.zbuffer_stale_on_host = false;
+    }
+    double vp[16];                                              // (a batch carries the Viewport it was drawn under; the query takes today's)
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) vp[4 * r + c] = Viewport[r][c];
+    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) && ok;
+    std::vector<double> b(boxes.size() * 6);
+    for (size_t i = 0; i < boxes.size(); ++i)
+        for (int a = 0; a < 3; ++a) { b[6 * i + a] = boxes[i].min[a]; b[6 * i + 3 + a] = boxes[i].max[a]; }
+    double m[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m[4 * r + c] = view_proj[r][c];
+    if (!(TRGL_SHIM_OK(trgl_occlusion_boxes(s.ctx, m, b.data(), b.size() / 6, TRGL_MEM_HOST, snapshot_slot, codes.data(), TRGL_MEM_HOST)) && ok))
+        codes.assign(boxes.size(), std::uint8_t(TRGL_OCCL_UNDECIDED));
+    return codes;
+}
+inline bool gl_occlusion_draw(std::uint8_t code) { return (code & 1) != 0; }
+
 inline void print_render_stats() {                                                // our_gl.cpp:204-210
     trgl_shim::State& s = trgl_shim::state();
     trgl_stats st{};
