@@ -90,6 +90,7 @@ extern "C" {
  *         const double* vary;         this triangle's K varyings (K fixed at registration; null when K = 0)
  *         const trgl_uniforms* u;     the draw's uniform block (texture slots -1 when the draw passed none)
  *         uint32_t color;             this triangle's `colors` entry, 0xffffffff when the draw has none
+ *         uint32_t dst;               0, or with TRGL_SHADER_READS_DEST the pixel under the fragment (below)
  *         ...                         (the texture table, for the sampler)
  *     };
  *     struct trgl_texel { uint32_t bgra; int bytespp; };                          TGAColor
@@ -118,12 +119,40 @@ extern "C" {
  * meet draws of any other kind (invisible in the frame and the counters, as every flush boundary).  TRGL_USER_MAY_DISCARD is
  * defined to 1 ahead of such a source and to 0 ahead of any other, so one source can serve both contracts.  A source written for
  * one contract and compiled under the other is a compile error that names trgl_fragment.
+ *
+ * User shaders that blend: two further flags, each valid only together with TRGL_SHADER_MAY_DISCARD (they need the kernel that
+ * runs a pixel's fragments in order) and free to be combined.  trgl_fragment keeps the discarding contract above.
+ *
+ *   TRGL_SHADER_READS_DEST: trgl_frag_in has a member `uint32_t dst`, and under this flag it is what TGAImage::get(x, y) would
+ *   return for this pixel at the moment of the call in an immediate-mode renderer (tgaimage.cpp:24-30, tgaimage.h:46-50): the
+ *   frame's bpp bytes of the pixel in B,G,R,A order in the low bytes, the remaining bytes ZERO - whoever wrote the pixel last: the
+ *   clear colour, an earlier fragment of the same flush (one that returned alpha 0xAA into a 3-byte frame reads back as alpha 0),
+ *   an earlier flush of any kind, trgl_write_framebuffer, trgl_framebuffer_blur / _modulate.  The member exists under every
+ *   contract; without the flag its value is 0.
+ *
+ *   TRGL_SHADER_NO_DEPTH_WRITE: a fragment that passes the z-test and is not discarded does everything our_gl.cpp:192-198 does -
+ *   the colour, fragments_drawn, min_z / max_z with its depth (first-zero sign rule included) - but not :191: the pixel's depth
+ *   stays, so the z-buffer after the flush holds bit for bit what it held before it (or the clear value), and later fragments
+ *   at the pixel are tested against that depth: several translucent layers in front of one opaque surface all pass.
+ *
+ * TRGL_USER_READS_DEST and TRGL_USER_DEPTH_WRITE are defined to 0 or 1 ahead of every fragment source, as TRGL_USER_MAY_DISCARD is.
+ * The prelude has one blend function, in integers only so that a host restatement is bit-exact:
+ *
+ *     __device__ uint32_t trgl_blend_over(uint32_t src, uint32_t dst);
+ *
+ * source-over with the source's alpha byte a: (s*a + d*(255-a) + 127) / 255 for each of B, G, R and
+ * (255*a + d_a*(255-a) + 127) / 255 for the alpha byte.  Nothing else is fixed-function: additive, multiplicative, premultiplied,
+ * stipple or alpha-test are trgl_fragment bodies over in.dst.  The library keeps submission order and does not sort: draw opaque
+ * geometry first, then translucent geometry back to front.
  */
 #define TRGL_SHADER_USER_FIRST 64
 #define TRGL_MAX_USER_SHADERS  32   /* per context */
 #define TRGL_MAX_USER_VARY     64   /* K */
 /* flags of trgl_shader_compile_ex / trgl_register_shader_ex */
 #define TRGL_SHADER_MAY_DISCARD 1u  /* trgl_fragment returns trgl_frag_out and is called for every z-pass, in order */
+/* (bit value 2 is unassigned) */
+#define TRGL_SHADER_READS_DEST     4u  /* with MAY_DISCARD only: in.dst is the pixel the fragment is drawn over */
+#define TRGL_SHADER_NO_DEPTH_WRITE 8u  /* with MAY_DISCARD only: a drawn fragment leaves the pixel's depth alone */
 
 /*
  * User vertex shaders: the other half of IShader (our_gl.h:36-52), vertex(face, nth), as HIP C++ source compiled at run time for the
@@ -292,7 +321,8 @@ int trgl_shader_compile(const char* source, int n_varyings, char* log, size_t lo
 /* Compile (or take from the cache) and load on the context's device; *kind = TRGL_SHADER_USER_FIRST + i for the i-th
  * registration on this context.  The module belongs to the context and is unloaded by trgl_destroy. */
 int trgl_register_shader(trgl_ctx* ctx, const char* source, int n_varyings, int* kind);
-/* The same with flags (TRGL_SHADER_MAY_DISCARD or 0; any other bit is TRGL_E_INVALID).  The two calls above are these with
+/* The same with flags (0, or TRGL_SHADER_MAY_DISCARD alone or with TRGL_SHADER_READS_DEST and / or TRGL_SHADER_NO_DEPTH_WRITE; any
+ * other bit, and either of those two without MAY_DISCARD, is TRGL_E_INVALID).  The two calls above are these with
  * flags = 0.  Kinds with and without the flag share the numbering and the TRGL_MAX_USER_SHADERS limit. */
 int trgl_shader_compile_ex(const char* source, int n_varyings, uint32_t flags, char* log, size_t log_len);
 int trgl_register_shader_ex(trgl_ctx* ctx, const char* source, int n_varyings, uint32_t flags, int* kind);

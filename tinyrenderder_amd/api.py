@@ -18,6 +18,14 @@ FLAT, GOURAUD, PHONG, EYE, CHECKER = 0, 1, 2, 3, 4
 VARY = {FLAT: 0, GOURAUD: 3, PHONG: 24, EYE: 24, CHECKER: 0}
 SHADER_USER_FIRST, MAX_USER_SHADERS, MAX_USER_VARY = 64, 32, 64      # user shaders: kinds handed out by Context.register_shader
 SHADER_MAY_DISCARD = 1        # TRGL_SHADER_MAY_DISCARD: the user shader's trgl_fragment returns trgl_frag_out (it can discard)
+SHADER_READS_DEST = 4         # TRGL_SHADER_READS_DEST: in.dst is the pixel the fragment is drawn over (with MAY_DISCARD only)
+SHADER_NO_DEPTH_WRITE = 8     # TRGL_SHADER_NO_DEPTH_WRITE: a drawn fragment leaves the depth alone (with MAY_DISCARD only)
+
+
+def shader_flags(may_discard=False, reads_dest=False, depth_write=True) -> int:
+    """The flag word of trgl_shader_compile_ex / trgl_register_shader_ex; which words are valid is the library's decision."""
+    return ((SHADER_MAY_DISCARD if may_discard else 0) | (SHADER_READS_DEST if reads_dest else 0)
+            | (0 if depth_write else SHADER_NO_DEPTH_WRITE))
 MAX_USER_VERTEX_SHADERS = 32  # TRGL_MAX_USER_VERTEX_SHADERS: vertex shaders handed out by Context.register_vertex_shader, from 0
 MEM_HOST, MEM_DEVICE = 0, 1
 PHASE_SETUP, PHASE_BIN, PHASE_RASTER, PHASE_TOTAL, PHASE_RASTER_KERNEL = 0, 1, 2, 3, 4
@@ -271,13 +279,14 @@ def rccl_comm_destroy(comm):
     load_library().trgl_rccl_comm_destroy(comm)
 
 
-def shader_compile(source: str, n_varyings: int, may_discard: bool = False):
+def shader_compile(source: str, n_varyings: int, may_discard: bool = False, *, reads_dest: bool = False, depth_write: bool = True):
     """trgl_shader_compile_ex: compile a user shader (include/trgl.h, "User shaders") without a GPU or a context; may_discard: one
-    whose trgl_fragment returns trgl_frag_out (TRGL_SHADER_MAY_DISCARD).
+    whose trgl_fragment returns trgl_frag_out (TRGL_SHADER_MAY_DISCARD).  reads_dest: in.dst is the pixel under the fragment
+    (TRGL_SHADER_READS_DEST); depth_write=False: TRGL_SHADER_NO_DEPTH_WRITE.  Both need may_discard.
     Returns (ok, compiler log); raises when user shaders are unavailable (no hiprtc)."""
     L = load_library()
     log = C.create_string_buffer(16384)
-    rc = L.trgl_shader_compile_ex(source.encode(), int(n_varyings), SHADER_MAY_DISCARD if may_discard else 0, log, len(log))
+    rc = L.trgl_shader_compile_ex(source.encode(), int(n_varyings), shader_flags(may_discard, reads_dest, depth_write), log, len(log))
     if rc not in (0, -1):
         raise TrglError(f"trgl_shader_compile failed ({rc}): {log.value.decode(errors='replace')}")
     return rc == 0, log.value.decode(errors="replace")
@@ -720,13 +729,15 @@ class Context:
         self._chk(self.L.trgl_gather(self.h, comm, rank, world, int(bool(with_z))))
 
     # ---- submission ----
-    def register_shader(self, source: str, n_varyings: int, may_discard: bool = False) -> int:
+    def register_shader(self, source: str, n_varyings: int, may_discard: bool = False, *, reads_dest: bool = False,
+                        depth_write: bool = True) -> int:
         """trgl_register_shader_ex: compile (or take from the process cache) a user shader and load it on this context; returns its
         kind, for draw() with n x n_varyings varyings.  may_discard: its trgl_fragment returns trgl_frag_out and runs for every
-        z-pass in order (TRGL_SHADER_MAY_DISCARD)."""
+        z-pass in order (TRGL_SHADER_MAY_DISCARD).  With it, reads_dest: in.dst is the pixel the fragment is drawn over
+        (TRGL_SHADER_READS_DEST); depth_write=False: a drawn fragment leaves the depth alone (TRGL_SHADER_NO_DEPTH_WRITE)."""
         kind = C.c_int(-1)
-        self._chk(self.L.trgl_register_shader_ex(self.h, source.encode(), int(n_varyings), SHADER_MAY_DISCARD if may_discard else 0,
-                                                  C.byref(kind)))
+        self._chk(self.L.trgl_register_shader_ex(self.h, source.encode(), int(n_varyings),
+                                                  shader_flags(may_discard, reads_dest, depth_write), C.byref(kind)))
         self._user_vary[kind.value] = int(n_varyings)
         return kind.value
 

@@ -11,6 +11,12 @@
 // perspective-correct barycentrics of :168-185 and then trgl_fragment - called for every fragment that passes the z-test, in
 // submission order per pixel, exactly where our_gl.cpp:187 calls it.  k_raster's accelerations (depth-plane cull, depth bound in
 // the pair, deferred resolves) are left out: they only skip work, and nothing here depends on them.
+//
+// Two further flags of such a kind change this one text in straight lines (include/trgl.h, "User shaders that blend"); with both
+// off the kernel is the one above, instruction for instruction.  TRGL_USER_READS_DEST: `color` is the pixel from the start (the
+// clear colour, or the frame's bytes when the flush does not start from a clear) and its bpp low bytes go to trgl_fragment as
+// in.dst.  TRGL_USER_DEPTH_WRITE 0: a drawn fragment skips our_gl.cpp:191, so `z` stays what the flush found and the smallest
+// depth written is kept in a register of its own, as the largest is.
 #pragma once
 #include "user_prelude.h"
 
@@ -53,8 +59,22 @@ void trgl_raster_user(FrameParams fp, const TriRec* __restrict__ recs, const Tri
     double z = -__builtin_inf();
     if (owned) z = fp.init_from_clear ? fp.clear_z : fp.zb[pix];
     uint32_t color = fp.clear_color;
+#if TRGL_USER_READS_DEST
+    // TGAImage::get (tgaimage.cpp:24-30): the pixel's bpp bytes, the rest of the TGAColor zero.  `color` holds 32 bits of which bpp
+    // bytes are the frame (a fragment's alpha never reaches a 3-byte frame), so in.dst is masked wherever it is formed
+    const uint32_t dst_mask = 0xffffffffu >> (8 * (4 - fp.bpp));
+    if (owned && !fp.init_from_clear) {
+        const uint8_t* src = fp.fb + pix * fp.bpp;
+        if (fp.bpp == 3) color = (uint32_t)src[0] | ((uint32_t)src[1] << 8) | ((uint32_t)src[2] << 16);
+        else if (fp.bpp == 4) color = *reinterpret_cast<const uint32_t*>(src);
+        else color = src[0];
+    }
+#endif
     uint32_t frags = 0;
     double zmax = -__builtin_inf();
+#if !TRGL_USER_DEPTH_WRITE
+    double zmin = __builtin_inf();
+#endif
     const bool zero_locked = stats->zero_locked != 0;
 
     const uint32_t beg = item4.y, end = item4.z;
@@ -103,9 +123,18 @@ void trgl_raster_user(FrameParams fp, const TriRec* __restrict__ recs, const Tri
             in.u = (const trgl_uniforms*)&d.u;
             in.color = r.color;
             in.tex = (const DevTexture*)(CTex*)tex;
+#if TRGL_USER_READS_DEST
+            in.dst = color & dst_mask;
+#else
+            in.dst = 0;
+#endif
             const trgl_frag_out o = trgl_fragment(in);                               // :187
             if (o.discard) continue;                                                 // :188
+#if TRGL_USER_DEPTH_WRITE
             z = zn;                                                                  // :191
+#else
+            asm("v_min_f64 %0, %0, %1" : "+v"(zmin) : "v"(zn));                      // :197, of the depths :191 would have written
+#endif
             color = o.bgra;                                                          // :192 (TGAImage::set at block-out)
             ++frags;                                                                 // :194
             asm("v_max_f64 %0, %0, %1" : "+v"(zmax) : "v"(zn));                      // :198 (the sign of a zero end: below)
@@ -120,12 +149,20 @@ void trgl_raster_user(FrameParams fp, const TriRec* __restrict__ recs, const Tri
 
     // ---- block out: every owned pixel once (the colour only where this flush wrote it, or from the clear) ----------------
     if (owned) {
+#if TRGL_USER_DEPTH_WRITE
         fp.zb[pix] = z;
+#else
+        if (fp.init_from_clear) fp.zb[pix] = z;           // (otherwise the depth is in place already)
+#endif
         if (fp.init_from_clear || frags) trgl_shade::store_pixel(fp, pix, color);
     }
     // ---- one partial of our_gl.cpp:194-198 per work item, in k_raster's layout (work_items.h)
+#if TRGL_USER_DEPTH_WRITE
     // (the smallest depth a pixel was written with is its last one: the z-test only lets smaller ones through)
     unsigned long long fr = frags, kmin = zkey(frags ? z : __builtin_inf()), kmax = zkey(zmax);
+#else
+    unsigned long long fr = frags, kmin = zkey(zmin), kmax = zkey(zmax);
+#endif
     for (int o = 32; o; o >>= 1) {
         fr += __shfl_xor(fr, o);
         const unsigned long long a = __shfl_xor(kmin, o); kmin = a < kmin ? a : kmin;

@@ -43,6 +43,7 @@ void trgl_shade_user(FrameParams fp, const TriRec* __restrict__ recs, const TriW
             in.vary = d.vary ? d.vary + (size_t)local * (uint32_t)d.K : nullptr;
             in.u = (const trgl_uniforms*)&d.u;
             in.tex = (const DevTexture*)(CTex*)tex;
+            in.dst = 0;                                  // (only a kind with TRGL_SHADER_READS_DEST sees the pixel)
             const TriRec& r = recs[d.first + local];
             const TriW& rw = recs_w[d.first + local];
             TRGL_OWNER_BARYCENTRICS(r, rw, x, y, in.bar);

@@ -103,7 +103,7 @@ int trgl::stage_copy(trgl_ctx* c, const void* src, size_t bytes, void** dev) {
 // a registered user kind that may discard (its draws are rasterized by its own kernel, in flushes of their own)
 static bool discarding_kind(const trgl_ctx* c, int kind) {
     const UserKind* uk = user_kind(c, kind);
-    return uk && uk->may_discard;
+    return uk && (uk->flags & TRGL_SHADER_MAY_DISCARD);
 }
 
 int trgl::kind_vary_count(const trgl_ctx* c, int kind) {

@@ -44,8 +44,8 @@ struct PendingRaster { bool active = false; FrameParams fp; int flush_kind = 0; 
 // and the counts that came over from k_setup.  valid: from a complete flush until the next trgl_draw / trgl_clear.
 struct Snapshot { bool valid = false; PendingRaster rp; uint64_t P = 0, literal_tris = 0, large_tris = 0; };
 // a user shader registered on the context (trgl_register_shader_ex): its module and kernel - the shade kernel, or the raster kernel
-// of a kind that may discard (TRGL_SHADER_MAY_DISCARD)
-struct UserKind { hipModule_t mod; hipFunction_t fn; int K; bool may_discard; };
+// of a kind that may discard (TRGL_SHADER_MAY_DISCARD) - and the TRGL_SHADER_* flags it was registered with
+struct UserKind { hipModule_t mod; hipFunction_t fn; int K; uint32_t flags; };
 // a user vertex shader registered on the context (trgl_register_vertex_shader): its module and its vertex-stage kernel (vertex_user.h)
 struct UserVertex { hipModule_t mod; hipFunction_t fn; int K; };
 }  // namespace trgl

@@ -172,7 +172,7 @@ int trgl_register_shader_ex(trgl_ctx* c, const char* source, int n_varyings, uin
     const std::vector<char>* code = nullptr;
     if (int r = user_shader_code(source, n_varyings, flags, &log, &code)) return fail(c, r, "trgl_register_shader: " + log);
     const bool may_discard = (flags & TRGL_SHADER_MAY_DISCARD) != 0;
-    UserKind u{ nullptr, nullptr, n_varyings, may_discard };
+    UserKind u{ nullptr, nullptr, n_varyings, flags };
     HIPCHK(c, hipModuleLoadData(&u.mod, code->data()));
     const hipError_t e = hipModuleGetFunction(&u.fn, u.mod, may_discard ? USER_RASTER_KERNEL : USER_SHADE_KERNEL);
     if (e != hipSuccess) {

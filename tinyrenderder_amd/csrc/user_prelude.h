@@ -10,6 +10,7 @@ struct trgl_frag_in {
     const trgl_uniforms* u;      // the draw's uniform block
     uint32_t color;              // this triangle's `colors` entry, 0xffffffff when the draw has none (k_setup)
     const DevTexture* tex;       // the context's texture table (trgl_sample2D)
+    uint32_t dst;                // with TRGL_SHADER_READS_DEST the pixel as TGAImage::get returns it now: bpp bytes, the rest zero; else 0
 };
 struct trgl_texel { uint32_t bgra; int bytespp; };   // TGAColor (tgaimage.h:29-31), bgra[0] in the low byte
 // what trgl_fragment returns with TRGL_SHADER_MAY_DISCARD: std::pair<bool, TGAColor> of IShader::fragment (our_gl.h:51)
@@ -22,6 +23,15 @@ __device__ __forceinline__ trgl_texel trgl_sample2D(const trgl_frag_in& in, int 
     if (!t) return trgl_texel{ 0xffffffffu, 4 };
     const trgl_shade::Color c = trgl_shade::tex_fetch(t, uv);
     return trgl_texel{ c.bgra, c.bytespp };
+}
+
+// source-over with the source's alpha byte a, in integers (include/trgl.h, "User shaders that blend"): per B, G, R
+// (s a + d (255 - a) + 127) / 255, and for the alpha byte (255 a + d_a (255 - a) + 127) / 255
+__device__ __forceinline__ uint32_t trgl_blend_over(uint32_t src, uint32_t dst) {
+    const uint32_t a = src >> 24, na = 255u - a;
+    uint32_t out = 0;
+    for (int i = 0; i < 24; i += 8) out |= ((((src >> i) & 255u) * a + ((dst >> i) & 255u) * na + 127u) / 255u) << i;
+    return out | (((255u * a + (dst >> 24) * na + 127u) / 255u) << 24);
 }
 
 // ---- user vertex shaders (include/trgl.h, "User vertex shaders"; the kernel behind the source is vertex_user.h) ----

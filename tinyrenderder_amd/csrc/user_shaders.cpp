@@ -139,11 +139,18 @@ static bool source_and_k_ok(const char* source, int K, std::string* log) {
 
 int user_shader_code(const char* source, int K, uint32_t flags, std::string* log, const std::vector<char>** code) {
     if (!source_and_k_ok(source, K, log)) return TRGL_E_INVALID;
-    if (flags & ~uint32_t(TRGL_SHADER_MAY_DISCARD)) { *log = "unknown flag bits " + std::to_string(flags & ~uint32_t(TRGL_SHADER_MAY_DISCARD)); return TRGL_E_INVALID; }
+    const uint32_t known = TRGL_SHADER_MAY_DISCARD | TRGL_SHADER_READS_DEST | TRGL_SHADER_NO_DEPTH_WRITE;
+    if (flags & ~known) { *log = "unknown flag bits " + std::to_string(flags & ~known); return TRGL_E_INVALID; }
     const bool may_discard = (flags & TRGL_SHADER_MAY_DISCARD) != 0;
+    if (!may_discard && flags) {                // (both need the kernel that runs the fragments of a pixel in order)
+        *log = "flag bits " + std::to_string(flags) + ": TRGL_SHADER_READS_DEST and TRGL_SHADER_NO_DEPTH_WRITE are only valid with TRGL_SHADER_MAY_DISCARD";
+        return TRGL_E_INVALID;
+    }
     // the user's lines keep their own numbers in the log (#line)
     const std::string program = "#include \"user_prelude.h\"\n#define TRGL_USER_VARY " + std::to_string(K) +
                                 "\n#define TRGL_USER_MAY_DISCARD " + (may_discard ? "1" : "0") +
+                                "\n#define TRGL_USER_READS_DEST " + ((flags & TRGL_SHADER_READS_DEST) ? "1" : "0") +
+                                "\n#define TRGL_USER_DEPTH_WRITE " + ((flags & TRGL_SHADER_NO_DEPTH_WRITE) ? "0" : "1") +
                                 "\n#line 1 \"user_shader\"\n" + source + "\n#include \"" + (may_discard ? "raster_user.h" : "shade_user.h") + "\"\n";
     return cached_code("flags " + std::to_string(flags), program, log, code);
 }

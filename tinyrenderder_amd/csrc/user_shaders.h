@@ -7,7 +7,7 @@
 namespace trgl {
 // The code object (for the architecture the library is built for) of the kernel of `source` with K varyings and the
 // TRGL_SHADER_* flags `flags` - the shade kernel, or with TRGL_SHADER_MAY_DISCARD the raster kernel - compiled with hiprtc or
-// taken from the process-wide cache.  TRGL_OK, TRGL_E_INVALID (bad K, unknown flags, compile error: the log says why) or
+// taken from the process-wide cache.  TRGL_OK, TRGL_E_INVALID (bad K, unknown flags or a blending flag without MAY_DISCARD, compile error: the log says why) or
 // TRGL_E_UNSUPPORTED (no hiprtc).  *code stays valid for the life of the process; *log is the compiler's log (a cached entry
 // returns the log of its compilation, warnings included).
 int user_shader_code(const char* source, int n_varyings, uint32_t flags, std::string* log, const std::vector<char>** code);

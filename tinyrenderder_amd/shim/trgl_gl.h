@@ -154,7 +154,7 @@ struct State {
     std::vector<double> clip, vary;
     std::vector<std::uint32_t> colors;
     mat<4, 4> viewport_at_batch;
-    struct UserSource { std::string source; int n_varyings; bool may_discard; };
+    struct UserSource { std::string source; int n_varyings; std::uint32_t flags; };   // flags: TRGL_SHADER_*
     std::vector<UserSource> user;         // gl_register_shader(): registered on every context, in order (kind = USER_FIRST + index)
     struct VertexSource { std::string source; int n_varyings; };
     std::vector<VertexSource> vertex;     // gl_register_vertex_shader(): likewise (vertex kind = index)
@@ -191,8 +191,7 @@ inline bool bind(TGAImage& fb) {
         // tries again with a new one)
         for (std::size_t i = 0; i < s.user.size(); ++i) {
             int kind = -1;
-            bool ok = TRGL_SHIM_OK(trgl_register_shader_ex(s.ctx, s.user[i].source.c_str(), s.user[i].n_varyings,
-                                                           s.user[i].may_discard ? TRGL_SHADER_MAY_DISCARD : 0u, &kind));
+            bool ok = TRGL_SHIM_OK(trgl_register_shader_ex(s.ctx, s.user[i].source.c_str(), s.user[i].n_varyings, s.user[i].flags, &kind));
             if (ok && kind != TRGL_SHADER_USER_FIRST + int(i)) ok = fail("gl_register_shader: kinds out of order", TRGL_E_STATE, nullptr);
             if (!ok) { trgl_destroy(s.ctx); s.ctx = nullptr; return false; }
         }
@@ -289,17 +288,20 @@ inline void gl_clip_layout(int kind, const trgl_clip_attr* attrs, int n) {
 // -1 comes back); the kind returned is what UserShader::kind takes, and it stays valid on every context the shim creates.
 // may_discard: the source's trgl_fragment returns trgl_frag_out, the std::pair<bool, TGAColor> of IShader::fragment, and runs for
 // every fragment that passes the z-test, in order (TRGL_SHADER_MAY_DISCARD).
-inline int gl_register_shader(const char* source, int n_varyings, bool may_discard = false) {
+// gl_register_shader_flags: the same with the whole TRGL_SHADER_* flag word, for a fragment() that blends: with
+// TRGL_SHADER_MAY_DISCARD | TRGL_SHADER_READS_DEST its in.dst is what framebuffer.get(x, y) holds when it runs, and with
+// TRGL_SHADER_NO_DEPTH_WRITE it leaves the z-buffer alone.  Submission order is kept, nothing is sorted: opaque geometry first, then
+// translucent geometry back to front.
+inline int gl_register_shader_flags(const char* source, int n_varyings, std::uint32_t flags) {
     trgl_shim::State& s = trgl_shim::state();
     if (s.user.size() >= TRGL_MAX_USER_SHADERS) { trgl_shim::fail("gl_register_shader", TRGL_E_INVALID, nullptr); return -1; }
-    const std::uint32_t flags = may_discard ? TRGL_SHADER_MAY_DISCARD : 0u;
     std::string log(4096, '\0');
     const int rc = trgl_shader_compile_ex(source, n_varyings, flags, &log[0], log.size());
     if (rc != TRGL_OK) {
         if (s.err == TRGL_OK) { s.err = rc; s.err_msg = std::string("gl_register_shader: ") + log.c_str(); }
         return -1;
     }
-    s.user.push_back({ source, n_varyings, may_discard });
+    s.user.push_back({ source, n_varyings, flags });
     const int kind = TRGL_SHADER_USER_FIRST + int(s.user.size()) - 1;
     if (s.ctx) {
         trgl_shim::submit_batch();
@@ -307,6 +309,9 @@ inline int gl_register_shader(const char* source, int n_varyings, bool may_disca
         if (!TRGL_SHIM_OK(trgl_register_shader_ex(s.ctx, source, n_varyings, flags, &k))) { s.user.pop_back(); return -1; }
     }
     return kind;
+}
+inline int gl_register_shader(const char* source, int n_varyings, bool may_discard = false) {
+    return gl_register_shader_flags(source, n_varyings, may_discard ? TRGL_SHADER_MAY_DISCARD : 0u);
 }
 
 // A user vertex shader (include/trgl.h, "User vertex shaders"): HIP C++ source defining trgl_vertex - the body of an
