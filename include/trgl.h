@@ -169,6 +169,10 @@ extern "C" {
  *         int face, nth;              the arguments of IShader::vertex; nth is 0, 1 or 2
  *         const trgl_uniforms* u;     the draw's uniform block (zeros and texture slots -1 when the draw passed NULL)
  *         const double* projection;   the global Perspective: 16 doubles, row-major
+ *         uint32_t instance;          trgl_draw_instanced / trgl_instance_stage: the instance's ORIGINAL number i (not its rank among
+ *                                     the drawn ones); 0 in every other call
+ *         const double* inst;         instances + i * instance_stride, or null when the call passed no instances (and in every other call)
+ *         int inst_stride;            the call's instance_stride; 0 in every other call
  *     };
  *     struct trgl_vert_out {
  *         double clip[4];             the return value of vertex(); (0, 0, 0, 0) until written
@@ -357,6 +361,72 @@ int trgl_draw_indexed_vs(trgl_ctx* ctx, int vs, int shader_kind, const trgl_unif
 int trgl_vertex_stage(trgl_ctx* ctx, int vs, const trgl_uniforms* uniforms, const double projection[16],
                       const double* vertices, int vertex_stride, uint64_t n_vertices,
                       const uint32_t* indices, uint64_t n_faces, double* clip_out, double* vary_out, int mem_kind);
+
+/* ---- instanced draws: one indexed mesh under many transforms, gated by visibility bytes ------------------------ */
+
+/* Replaces: the loop over models of main.cpp:647-736 - `ModelView = ModelView * modelMatrix` (main.cpp:653), then the face loop - for
+ * ONE mesh drawn under n_instances transforms, with a host `if (visible)` around each model.  Mesh, transforms and visibility bytes may
+ * all stay in device memory.
+ *   vertices, vertex_stride, n_vertices, indices, n_faces : the mesh, as for trgl_draw_indexed_vs
+ *   face_colors     : n_faces x uint32, or NULL
+ *   mesh_mem_kind   : covers vertices, indices and face_colors
+ *   instances       : n_instances x instance_stride doubles, or NULL (allowed exactly when instance_stride == 0)
+ *   instance_colors : n_instances x uint32, or NULL
+ *   visible         : n_instances bytes, or NULL
+ *   instance_mem_kind : covers instances, instance_colors and visible (and the three outputs of trgl_instance_stage)
+ * DEFINITION.
+ *   Instance i is drawn when visible == NULL or (visible[i] & 1) != 0.  Bit 0 is the bit trgl_occlusion_boxes sets for "draw it"
+ *   (VISIBLE = 1 and UNDECIDED = 3 have it, HIDDEN = 0 and OUTSIDE = 2 do not), so an array of codes is a valid `visible`; the other
+ *   seven bits are ignored (0xFE skips, 0xFF draws).
+ *   The drawn instances are numbered j = 0 .. n_vis - 1 in ascending i: i_0 < i_1 < ...  (submission order is observable, our_gl.cpp:165).
+ *   Output triangle j * n_faces + f is face f of the mesh under instance i_j:
+ *   vs == -1, the built-in stage: instance_stride >= 16 and instances != NULL; the first 16 doubles of instance i are a row-major
+ *     mat<4,4> M_i, and MV_i = uniforms->model_view * M_i as geometry.h:196-205 computes it: element (r, c) is the sum, started from
+ *     0.0, of model_view[r][k] * M_i[k][c] for k = 0, 1, 2, 3 in this order, each product rounded to fp64 and added without contraction
+ *     (((0.0 + p0) + p1) + p2) + p3.  The clip row (12 doubles) and the varyings row (K = 24) of the triangle are those of
+ *     trgl_vertex_stage(vs = -1) for face f with MV_i in place of uniforms->model_view.  vertex_stride >= 8; shader_kind as for
+ *     trgl_draw_indexed (PHONG, EYE or a user kind with K = 24).
+ *   vs >= 0: trgl_vertex runs once per face-vertex of every drawn instance, with in.face = f, in.nth, in.index, in.vertex as for
+ *     trgl_draw_indexed_vs, in.u the call's uniform block, in.instance = i_j (the original i), in.inst = instances + i_j *
+ *     instance_stride (null when instances is NULL) and in.inst_stride = instance_stride.  instance_stride >= 0.
+ *   Colour of output triangle j * n_faces + f: instance_colors[i_j] if that array is given, else face_colors[f] if given, else the
+ *     draw has no colours.  Giving both arrays is TRGL_E_INVALID.
+ *   Fragment stage: EVERY instance's fragments see the call's ONE uniform block.  PHONG and EYE fragment() read model_view and the
+ *     light directions from it, so an instanced PHONG draw equals the reference's loop only where the shader object was constructed
+ *     once, under the call's ModelView (uniforms->model_view), and not once per model.  A fragment body that needs per-instance values
+ *     gets them from a user vertex shader, which writes them into varyings slots that the fragment reads as per-triangle constants.
+ *   Equivalence: frame bytes, depths and every counter are bit for bit those of calling, for j = 0 .. n_vis - 1 in this order,
+ *     trgl_vertex_stage with the values above and then trgl_draw(shader_kind, uniforms, its rows, colours as above).
+ *     triangles_rasterized grows by n_vis * n_faces; an instance that is not drawn leaves no trace.
+ * MEMORY AND ORDER.  Device arrays are read when the stages run on the context's stream, queued by the call (the rule of
+ * trgl_draw_indexed): codes that trgl_occlusion_boxes left in device memory on this context are ordered in front.  Host arrays are
+ * copied before return.  Alignment of device arrays: instances 8 bytes, colours 4, visible none.
+ * SYNCHRONISATION.  visible == NULL: no wait.  visible in host memory: the list of drawn instances is made on the host; no wait.
+ * visible in device memory: an order-preserving compaction runs on the stream and the call waits for the stream ONCE, for the 8-byte
+ * count n_vis (the draw that is queued needs it on the host - the wait of trgl_draw_clipped).  Nothing is flushed on the call's account;
+ * the 2^24 cut and the flush rules are trgl_draw's.  n_vis == 0 queues nothing.
+ * ERRORS.  TRGL_E_INVALID: a null mesh array or projection, an unknown vs or kind, kinds whose K differ, a bad mem_kind, a stride below
+ * its minimum, instances == NULL with instance_stride != 0 (or the reverse), both colour arrays, a host index out of range.
+ * TRGL_E_UNSUPPORTED: n_instances or n_vis * n_faces above 2^31 - 1.  n_instances == 0 or n_faces == 0: TRGL_OK once the
+ * scalar arguments are checked, and no array is read. */
+int trgl_draw_instanced(trgl_ctx* ctx, int vs, int shader_kind, const trgl_uniforms* uniforms, const double projection[16],
+                        const double* vertices, int vertex_stride, uint64_t n_vertices,
+                        const uint32_t* indices, uint64_t n_faces, const uint32_t* face_colors, int mesh_mem_kind,
+                        const double* instances, int instance_stride, uint64_t n_instances,
+                        const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind);
+/* The stages of trgl_draw_instanced alone (no shader kind, nothing is queued for the rasterizer): clip_out receives n_vis * n_faces x 12
+ * doubles, vary_out n_vis * n_faces x K (may be NULL when K = 0), colors_out n_vis * n_faces x uint32 (written only when a colour array
+ * is given; may be NULL otherwise), each with room for n_instances * n_faces rows, in host or device memory as instance_mem_kind says;
+ * *n_out (host memory) receives n_vis * n_faces, and nothing behind that many rows is written.  Device outputs must be 16-byte
+ * aligned and are complete on the context's stream when the call returns its count (visible in device memory: the one wait above;
+ * otherwise queued, in order with the draws).  Host outputs are complete on return.  The rows are the arrays trgl_draw and
+ * trgl_clip_stage take. */
+int trgl_instance_stage(trgl_ctx* ctx, int vs, const trgl_uniforms* uniforms, const double projection[16],
+                        const double* vertices, int vertex_stride, uint64_t n_vertices,
+                        const uint32_t* indices, uint64_t n_faces, const uint32_t* face_colors, int mesh_mem_kind,
+                        const double* instances, int instance_stride, uint64_t n_instances,
+                        const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind,
+                        double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out);
 
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 

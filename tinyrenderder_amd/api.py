@@ -36,6 +36,9 @@ MAX_BLUR_RADIUS = 46340       # TRGL_MAX_BLUR_RADIUS
 MAX_PCF_RADIUS = 4            # TRGL_MAX_PCF_RADIUS
 MAX_CLIP_ATTRS = 24           # TRGL_MAX_CLIP_ATTRS
 OCCL_HIDDEN, OCCL_VISIBLE, OCCL_OUTSIDE, OCCL_UNDECIDED = range(4)     # TRGL_OCCL_*: bit 0 set = draw it
+# the sizes of the instanced stages (csrc/launch.h): instances per block of the compaction, block counts per block of its scan's lower
+# level, output faces per block of the instanced vertex kernels
+INST_BLOCK, INST_SCAN_CHUNK, INST_VS_FACES = 256, 256, 64
 NEAR_PLANE = (0.0, 0.0, 1.0, 1.0)     # the near plane of the reference's projection in clip space: z + w >= 0
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
 
@@ -58,6 +61,7 @@ SYMBOLS = [
     "trgl_shadow_matrix", "trgl_shadow_mask_image", "trgl_shadow_mask", "trgl_image_modulate", "trgl_framebuffer_modulate",
     "trgl_clip_layout", "trgl_clip_stage", "trgl_draw_clipped", "trgl_draw_indexed_vs_clipped",
     "trgl_occlusion_boxes_image", "trgl_occlusion_boxes",
+    "trgl_draw_instanced", "trgl_instance_stage",
 ]
 
 
@@ -246,6 +250,10 @@ def load_library(path: str = None):
                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
     L.trgl_occlusion_boxes_image.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, dp, dp, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
     L.trgl_occlusion_boxes.argtypes = [vp, dp, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    inst = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int,      # the mesh
+            C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int]                   # the instances
+    L.trgl_draw_instanced.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Uniforms), dp] + inst
+    L.trgl_instance_stage.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp] + inst + [C.c_void_p, C.c_void_p, C.c_void_p, u64p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -879,6 +887,87 @@ class Context:
         self._chk(self.L.trgl_vertex_stage(self.h, vs, None if uniforms is None else C.byref(uniforms), pj.ctypes.data_as(C.POINTER(C.c_double)),
                                            ptrs[0], stride, nv, ptrs[1], nf, optrs[0], optrs[1], MEM_DEVICE if device else MEM_HOST))
         return clip, vary
+
+    def _instance_args(self, vertices, indices, instances, face_colors, instance_colors, visible, device, instances_device):
+        """The mesh and instance arguments of trgl_draw_instanced / trgl_instance_stage as (ctypes arguments, n_faces, n_instances,
+        has_colors, arrays to keep alive).  Host arrays are made contiguous; device arrays are checked by _device_ptr."""
+        vertices, indices, face_colors, mp = self._mesh_ptrs(vertices, indices, face_colors, device)
+        nv, stride = vertices.shape
+        nf = indices.shape[0]
+        if instances is None:
+            inst_stride = 0
+            n_inst = None
+        else:
+            if not instances_device:
+                instances = np.ascontiguousarray(instances, np.float64)
+                if instances.ndim != 2:
+                    instances = instances.reshape(instances.shape[0], -1)
+            n_inst, inst_stride = int(instances.shape[0]), int(instances.shape[1])
+        for a, what in ((instance_colors, "instance_colors"), (visible, "visible")):
+            if a is not None:
+                if n_inst is None:
+                    n_inst = int(a.shape[0])
+                elif int(a.shape[0]) != n_inst:
+                    raise ValueError(f"{what}: one entry per instance expected")
+        if n_inst is None:
+            raise ValueError("the number of instances comes from instances, instance_colors or visible: all three are None")
+        if instances_device:
+            ip = (_device_ptr(instances, "instances"), _device_ptr(instance_colors, "instance_colors"), _device_ptr(visible, "visible"))
+        else:
+            if instance_colors is not None:
+                instance_colors = np.ascontiguousarray(instance_colors, np.uint32)
+            if visible is not None:
+                visible = np.ascontiguousarray(visible, np.uint8)
+            ip = (_ptr(instances), _ptr(instance_colors), _ptr(visible))
+        args = [mp[0], stride, nv, mp[1], nf, mp[2], MEM_DEVICE if device else MEM_HOST,
+                ip[0], inst_stride, n_inst, ip[1], ip[2], MEM_DEVICE if instances_device else MEM_HOST]
+        return args, nf, n_inst, face_colors is not None or instance_colors is not None, (vertices, indices, face_colors, instances, instance_colors, visible)
+
+    def draw_instanced(self, kind, uniforms, projection, vertices, indices, instances=None, vertex_shader=None, face_colors=None,
+                       instance_colors=None, visible=None, device=False, instances_device=False):
+        """trgl_draw_instanced: the mesh (vertices [nv, stride], indices [nf, 3]) once per instance whose `visible` byte has bit 0 set
+        (visible None: every instance), in ascending instance order.  instances [n, stride]: with the built-in stage (vertex_shader None)
+        the first 16 doubles are a row-major model matrix M and the stage runs under uniforms.model_view * M; a user vertex shader
+        reads them as in.inst.  Colours: instance_colors [n] or face_colors [nf], not both.  device: the mesh arrays are device
+        tensors; instances_device: instances, instance_colors and visible are (the codes of occlusion_boxes(device=True) are a valid
+        `visible`; the call then waits once for the count of drawn instances)."""
+        pj = np.ascontiguousarray(projection, np.float64).reshape(16)
+        args, _, _, _, keep = self._instance_args(vertices, indices, instances, face_colors, instance_colors, visible, device, instances_device)
+        if device or instances_device:
+            self._keep.append(keep)
+        self._chk(self.L.trgl_draw_instanced(self.h, -1 if vertex_shader is None else int(vertex_shader), kind,
+                                             None if uniforms is None else C.byref(uniforms), _dp(pj), *args))
+
+    def instance_stage(self, vertex_shader, uniforms, projection, vertices, indices, instances=None, face_colors=None, instance_colors=None,
+                       visible=None, device=False, instances_device=False, out=None):
+        """trgl_instance_stage: the stages of draw_instanced alone; returns (clip, varyings, colors, n_out) with n_out = drawn instances
+        * nf rows written.  vertex_shader: a number from register_vertex_shader, or -1 / None for the built-in stage (K = 24).
+        Host instances: numpy arrays cut to n_out rows (varyings [n_out, K]; colors None when the call has none).  instances_device=True:
+        out = (clip, varyings, colors) are 16-byte aligned device tensors with room for n * nf rows (varyings may be None when K = 0,
+        colors when the call has none); they come back as they are."""
+        vs = -1 if vertex_shader is None else int(vertex_shader)
+        K = VARY[PHONG] if vs < 0 else getattr(self, "_vertex_vary", {}).get(vs, 0)
+        pj = np.ascontiguousarray(projection, np.float64).reshape(16)
+        args, nf, n_inst, has_colors, keep = self._instance_args(vertices, indices, instances, face_colors, instance_colors, visible, device, instances_device)
+        n_out = C.c_uint64(0)
+        if instances_device:
+            clip, vary, col = out
+            optrs = (_device_ptr(clip, "clip"), _device_ptr(vary, "varyings"), _device_ptr(col, "colors"))
+            self._keep.append(keep + (clip, vary, col))
+        else:
+            assert out is None, "out: only with instances_device=True"
+            rows = n_inst * nf
+            clip, vary = np.zeros((rows, 12), np.float64), np.zeros((rows, K), np.float64)
+            col = np.zeros(rows, np.uint32) if has_colors else None
+            optrs = (clip.ctypes.data, vary.ctypes.data if K else None, col.ctypes.data if has_colors else None)
+            if device:
+                self._keep.append(keep)
+        self._chk(self.L.trgl_instance_stage(self.h, vs, None if uniforms is None else C.byref(uniforms), _dp(pj), *args,
+                                             optrs[0], optrs[1], optrs[2], C.byref(n_out)))
+        n = int(n_out.value)
+        if instances_device:
+            return clip, vary, col, n
+        return clip[:n], vary[:n], None if col is None else col[:n], n
 
     def mesh_bounds(self, vertices, device=False):
         """trgl_mesh_bounds: Model::computeAABB (model.cpp:15-40) of vertices [n, stride >= 3]; returns (min[3], max[3]).  device=True:

@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -162,6 +162,26 @@ struct OcclArgs {
     uint64_t n; int32_t w, h;
 };
 void launch_occl_query(hipStream_t s, const OcclArgs& a);
+
+// The stages in front of an instanced draw (kernels_instance.hip; the operation is written down at trgl_draw_instanced in include/trgl.h).
+// Compaction of the visibility bytes: INST_BLOCK instances per block, one per lane; the scan over the block counts has two levels,
+// INST_SCAN_CHUNK block counts per block of the lower one.  The instance list may have any length below 2^31.
+constexpr int INST_BLOCK = 256;
+constexpr int INST_SCAN_CHUNK = 256;
+constexpr int INST_VS_FACES = 64;            // output faces of a block of the instanced vertex stage (three threads each)
+uint32_t inst_num_blocks(uint64_t n);
+size_t inst_scratch_words(uint64_t n);       // 2 words for the 8-byte count, the block counts, the chunk sums
+// list[j] = i_j, the instances with (visible[i] & 1) in ascending order, and *total = n_vis; with mv_out, slot j also receives
+// MV = model_view * M_{i_j} (geometry.h:196-205; M: the first 16 doubles of the instance's record).  scratch: inst_scratch_words(n)
+// words, *total its first two.  Four launches, in order on `s`.  0 < n < 2^31.
+void launch_inst_compact(hipStream_t s, const uint8_t* visible, uint32_t n, uint32_t* scratch, uint32_t* list,
+                         const double model_view[16], const double* instances, int inst_stride, double* mv_out);
+// mv_out[j] = model_view * M_{list[j]} for j < n_vis (list null: M_j) - for a list that was not made by launch_inst_compact
+void launch_inst_mv(hipStream_t s, const uint32_t* list, uint32_t n_vis, const double model_view[16], const double* instances,
+                    int inst_stride, double* mv_out);
+// k_vertex_stage over the flattened faces ip.total = n_vis * nfaces, the model-view matrix of output face g being ip.mv + 16 * (g / nfaces)
+void launch_instance_vertex_stage(hipStream_t s, const InstanceParams& ip, const double proj[16], const double* vertices, int stride,
+                                  const uint32_t* indices, uint32_t nfaces, double* clip, double* vary);
 
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,

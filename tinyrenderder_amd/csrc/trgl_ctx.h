@@ -47,7 +47,8 @@ struct Snapshot { bool valid = false; PendingRaster rp; uint64_t P = 0, literal_
 // of a kind that may discard (TRGL_SHADER_MAY_DISCARD) - and the TRGL_SHADER_* flags it was registered with
 struct UserKind { hipModule_t mod; hipFunction_t fn; int K; uint32_t flags; };
 // a user vertex shader registered on the context (trgl_register_vertex_shader): its module and its vertex-stage kernel (vertex_user.h)
-struct UserVertex { hipModule_t mod; hipFunction_t fn; int K; };
+// (fn_inst: the kernel of the same module that trgl_draw_instanced runs)
+struct UserVertex { hipModule_t mod; hipFunction_t fn; int K; hipFunction_t fn_inst; };
 }  // namespace trgl
 using namespace trgl;
 
@@ -90,7 +91,10 @@ struct trgl_ctx {
     // trgl_occlusion_boxes(_image): the two levels of block maxima over the depths, rebuilt by every call; host boxes and the codes for a
     // host array on their way; grow on demand
     DevBuf<double> occl_levels, occl_boxes; DevBuf<uint8_t> occl_codes;
-    DevBuf<uint8_t> pp_out;             // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
+    // trgl_draw_instanced / trgl_instance_stage: the 8-byte count of drawn instances and the words of the compaction's scan; the list of
+    // drawn instances; model_view * M per drawn instance for the built-in stage.  Read by the stages the call queues; grow on demand
+    DevBuf<uint32_t> inst_scratch, inst_list; DevBuf<double> inst_mv;
+    DevBuf<uint8_t> pp_out;            // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
     DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
     DevBuf<uint32_t> keys[2], vals[2]; DevBuf<uint16_t> bmask[2];     // (tile, triangle, block mask) pairs, ping-pong; grown together

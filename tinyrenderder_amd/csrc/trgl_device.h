@@ -86,6 +86,19 @@ struct VertexUserParams {
     uint32_t        nfaces;       // <= 0xffffffff / 3
     int32_t         stride;
 };
+// What the instanced vertex stages add (trgl_draw_instanced; kernels_instance.hip and the second kernel of vertex_user.h): output face
+// g = slot * nfaces + face of the flattened range 0 .. total, slot j standing for instance list[j] (list null: instance j).
+struct InstanceParams {
+    const uint32_t* list;         // [n_vis] original instance numbers in ascending order, or null
+    const double*   instances;    // [n_instances][inst_stride], or null
+    const double*   mv;           // built-in stage: [n_vis][16], model_view * M of slot j
+    const uint32_t* inst_colors;  // [n_instances] or null
+    const uint32_t* face_colors;  // [nfaces] or null (not both)
+    uint32_t*       colors;       // [total], written when one of the two is given
+    uint32_t        total;        // n_vis * nfaces <= 2^31 - 1
+    int32_t         inst_stride;
+};
+struct VertexUserInstancedParams { VertexUserParams v; InstanceParams i; };     // v.nfaces: faces of the MESH; v.clip / v.vary: [total] rows
 
 // Device-side mirror of the reference's counters (our_gl.cpp:18-22).  z range is kept as
 // order-preserving uint64 keys so atomicMin/atomicMax work on it.

@@ -1,9 +1,11 @@
 // trgl_shader.cpp — run-time shader registration (fragment kinds and vertex shaders, compiled by user_shaders.cpp) and the entry points
 // that run a stage in front of a draw: the vertex stage over an indexed mesh (trgl_draw_indexed, trgl_draw_indexed_vs, trgl_vertex_stage)
-// and the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped).  The draws they make go through trgl_draw
-// (trgl_api.cpp), which owns the queue and its ordering rules.
+// the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and the instanced stages (trgl_draw_instanced,
+// trgl_instance_stage).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <cstring>
+#include <memory>
 #include <new>
+#include <vector>
 
 #include "trgl_ctx.h"
 #include "user_shaders.h"
@@ -162,7 +164,183 @@ static int check_draw_indexed_vs(trgl_ctx* c, int vs, int kind, const trgl_unifo
     return TRGL_OK;
 }
 
+// ---- instanced draws (include/trgl.h: trgl_draw_instanced) ----
+struct InstanceCall {
+    int vs; const trgl_uniforms* u; const double* projection;
+    const double* vertices; int stride; uint64_t n_vertices; const uint32_t* indices; uint64_t n_faces; const uint32_t* face_colors; int mesh_mem;
+    const double* instances; int inst_stride; uint64_t n_inst; const uint32_t* inst_colors; const uint8_t* visible; int inst_mem;
+};
+
+// what trgl_draw_instanced and trgl_instance_stage check alike; K of the stage comes back in *K; *go: there is something to run
+static int check_instance_call(trgl_ctx* c, const char* who, const InstanceCall& a, int* K, bool* go) {
+    *go = false;
+    const std::string w = std::string(who) + ": ";
+    int r;
+    // (with no instances nothing is read: the indices are then not looked at either)
+    if ((r = check_vertex_call(c, who, a.vs, true, a.u, a.projection, a.vertices, a.stride, a.n_vertices, a.indices, a.n_inst ? a.n_faces : 0, a.mesh_mem, K))) return r;
+    if (!valid_mem_kind(a.inst_mem)) return fail(c, TRGL_E_INVALID, w + "bad instance_mem_kind");
+    if (a.inst_stride < (a.vs < 0 ? 16 : 0)) return fail(c, TRGL_E_INVALID, w + (a.vs < 0 ? "instance stride must be >= 16 doubles (a row-major 4x4 matrix)" : "instance stride must be >= 0"));
+    if (a.n_inst && (a.instances == nullptr) != (a.inst_stride == 0)) return fail(c, TRGL_E_INVALID, w + "instances must be null exactly when instance_stride is 0");
+    if (a.inst_colors && a.face_colors) return fail(c, TRGL_E_INVALID, w + "face_colors and instance_colors are both given");
+    if (a.n_inst > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more instances in one call");
+    if (a.inst_mem == TRGL_MEM_DEVICE && (((uintptr_t)a.instances & 7) || ((uintptr_t)a.inst_colors & 3)))
+        return fail(c, TRGL_E_INVALID, w + "device arrays need natural alignment (8 bytes for instances, 4 for colours)");
+    *go = a.n_inst != 0 && a.n_faces != 0;
+    return TRGL_OK;
+}
+
+// The stages of an instanced call, checked (n_inst, n_faces > 0).  draw: the rows go to staged arrays and to trgl_draw(kind), under a
+// StageHold of this call's; else to clip_out / vary_out / colors_out (in a.inst_mem memory) and *n_out receives their number.
+static int run_instanced(trgl_ctx* c, const char* who, const InstanceCall& a, int K, bool draw, int kind,
+                         double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out) {
+    const std::string w = std::string(who) + ": ";
+    int r;
+    // Memory of this call's: the per-flush arena for a draw; for the stage alone buffers that go with the call (nothing is left staged
+    // for a flush that may never come)
+    std::vector<std::unique_ptr<DevBuf<uint8_t>>> own;
+    auto dev_alloc = [&](size_t bytes, void** p) -> int {
+        if (draw) return stage_alloc(c, bytes, p);
+        own.emplace_back(new DevBuf<uint8_t>());
+        if (int e = own.back()->alloc(c, bytes ? bytes : 1)) return e;
+        *p = own.back()->p;
+        return TRGL_OK;
+    };
+    auto dev_copy = [&](const void* src, size_t bytes, void** p) -> int {
+        if (draw) return stage_copy(c, src, bytes, p);
+        if (int e = dev_alloc(bytes, p)) return e;
+        HIPCHK(c, hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice));
+        return TRGL_OK;
+    };
+    void* p = nullptr;
+    const bool builtin = a.vs < 0;
+    const bool has_colors = a.inst_colors || a.face_colors;
+
+    // a. which instances are drawn: list (null: all of them, in order) and n_vis
+    const uint32_t* list = nullptr;
+    uint64_t n_vis = a.n_inst;
+    bool mv_done = false;
+    std::vector<uint32_t> host_list;
+    if (a.visible && a.inst_mem == TRGL_MEM_HOST) {
+        try {
+            for (uint64_t i = 0; i < a.n_inst; ++i) if (a.visible[i] & 1u) host_list.push_back((uint32_t)i);
+        } catch (const std::bad_alloc&) { return fail(c, TRGL_E_NOMEM, w + "out of memory"); }
+        n_vis = host_list.size();
+    } else if (a.visible) {
+        if ((r = c->inst_scratch.grow(c, inst_scratch_words(a.n_inst))) || (r = c->inst_list.grow(c, a.n_inst)) ||
+            (builtin && (r = c->inst_mv.grow(c, 16 * a.n_inst)))) return r;
+        launch_inst_compact(c->stream, a.visible, (uint32_t)a.n_inst, c->inst_scratch.p, c->inst_list.p, builtin ? a.u->model_view : nullptr,
+                            a.instances, a.inst_stride, builtin ? c->inst_mv.p : nullptr);
+        HIPCHK(c, hipGetLastError());
+        unsigned long long count = 0;
+        HIPCHK(c, hipMemcpyAsync(&count, c->inst_scratch.p, sizeof(count), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait of an instanced call: the queue needs the count on the host
+        n_vis = count; list = c->inst_list.p; mv_done = true;
+    }
+    if (n_out) *n_out = 0;
+    if (n_vis == 0) return TRGL_OK;
+    if (n_vis * a.n_faces > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more triangles in one call");
+    const uint64_t total = n_vis * a.n_faces;
+
+    // host arrays on their way
+    const double* dv = a.vertices; const uint32_t* di = a.indices; const uint32_t* dfc = a.face_colors;
+    if (a.mesh_mem == TRGL_MEM_HOST) {
+        if ((r = dev_copy(a.vertices, a.n_vertices * (size_t)a.stride * sizeof(double), &p))) return r;
+        dv = (const double*)p;
+        if ((r = dev_copy(a.indices, 3 * a.n_faces * sizeof(uint32_t), &p))) return r;
+        di = (const uint32_t*)p;
+        if (a.face_colors) { if ((r = dev_copy(a.face_colors, a.n_faces * sizeof(uint32_t), &p))) return r; dfc = (const uint32_t*)p; }
+    }
+    const double* dinst = a.instances; const uint32_t* dic = a.inst_colors;
+    if (a.inst_mem == TRGL_MEM_HOST) {
+        if (a.visible) { if ((r = dev_copy(host_list.data(), n_vis * sizeof(uint32_t), &p))) return r; list = (const uint32_t*)p; }
+        if (a.instances) { if ((r = dev_copy(a.instances, a.n_inst * (size_t)a.inst_stride * sizeof(double), &p))) return r; dinst = (const double*)p; }
+        if (a.inst_colors) { if ((r = dev_copy(a.inst_colors, a.n_inst * sizeof(uint32_t), &p))) return r; dic = (const uint32_t*)p; }
+    }
+    if (builtin && !mv_done) {
+        if ((r = c->inst_mv.grow(c, 16 * n_vis))) return r;
+        launch_inst_mv(c->stream, list, (uint32_t)n_vis, a.u->model_view, dinst, a.inst_stride, c->inst_mv.p);
+        HIPCHK(c, hipGetLastError());
+    }
+
+    // b. the rows
+    const bool host_out = !draw && a.inst_mem == TRGL_MEM_HOST;
+    double* clip = clip_out; double* vary = K ? vary_out : nullptr; uint32_t* col = has_colors ? colors_out : nullptr;
+    if (draw || host_out) {
+        if ((r = dev_alloc(total * 12 * sizeof(double), &p))) return r;
+        clip = (double*)p;
+        if (K) { if ((r = dev_alloc(total * (size_t)K * sizeof(double), &p))) return r; vary = (double*)p; }
+        if (has_colors) { if ((r = dev_alloc(total * sizeof(uint32_t), &p))) return r; col = (uint32_t*)p; }
+    }
+    InstanceParams ip; std::memset(&ip, 0, sizeof(ip));
+    ip.list = list; ip.instances = dinst; ip.mv = builtin ? c->inst_mv.p : nullptr; ip.inst_colors = dic; ip.face_colors = dfc;
+    ip.colors = col; ip.total = (uint32_t)total; ip.inst_stride = a.inst_stride;
+    if (builtin) {
+        launch_instance_vertex_stage(c->stream, ip, a.projection, dv, a.stride, di, (uint32_t)a.n_faces, clip, vary);
+        HIPCHK(c, hipGetLastError());
+    } else {
+        VertexUserInstancedParams q; std::memset(&q, 0, sizeof(q));
+        if (a.u) q.v.u = *a.u; else q.v.u.tex_diffuse = q.v.u.tex_normal = q.v.u.tex_specular = -1;
+        std::memcpy(q.v.proj, a.projection, sizeof(q.v.proj));
+        q.v.vertices = dv; q.v.indices = di; q.v.clip = clip; q.v.vary = vary; q.v.nfaces = (uint32_t)a.n_faces; q.v.stride = a.stride;
+        q.i = ip;
+        void* args[] = { &q };
+        const uint64_t blocks = (total + TRGL_VERTEX_USER_FACES - 1) / TRGL_VERTEX_USER_FACES;
+        HIPCHK(c, hipModuleLaunchKernel(c->vertex[a.vs].fn_inst, (unsigned)blocks, 1, 1, TRGL_VERTEX_USER_FACES * 3, 1, 1, 0, c->stream, args, nullptr));
+    }
+
+    // c. the draw, or the rows back to their caller
+    if (draw) return trgl_draw(c, kind, a.u, clip, vary, col, total, TRGL_MEM_DEVICE);
+    if (host_out) {
+        HIPCHK(c, hipMemcpyAsync(clip_out, clip, total * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (K) HIPCHK(c, hipMemcpyAsync(vary_out, vary, total * (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (has_colors) HIPCHK(c, hipMemcpyAsync(colors_out, col, total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!own.empty()) HIPCHK(c, hipStreamSynchronize(c->stream));       // (they are freed on return)
+    *n_out = total;
+    return TRGL_OK;
+}
+
 extern "C" {
+
+int trgl_draw_instanced(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16],
+                        const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                        const uint32_t* face_colors, int mesh_mem_kind, const double* instances, int instance_stride, uint64_t n_instances,
+                        const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const InstanceCall a{ vs, u, projection, vertices, stride, n_vertices, indices, n_faces, face_colors, mesh_mem_kind,
+                          instances, instance_stride, n_instances, instance_colors, visible, instance_mem_kind };
+    int K = 0; bool go;
+    if ((r = check_instance_call(c, "trgl_draw_instanced", a, &K, &go))) return r;
+    // (what trgl_draw would refuse is refused before anything is queued)
+    const int kind_K = kind_vary_count(c, kind);
+    if (kind_K < 0) return fail(c, TRGL_E_INVALID, "trgl_draw_instanced: unknown shader kind");
+    if (kind_K != K) return fail(c, TRGL_E_INVALID, "trgl_draw_instanced: the shader kind and the vertex stage differ in their number of varyings");
+    if ((r = check_kind_uniforms(c, "trgl_draw_instanced", kind, u)) || !go) return r;
+    StageHold hold(c);
+    return run_instanced(c, "trgl_draw_instanced", a, K, true, kind, nullptr, nullptr, nullptr, nullptr);
+}
+
+int trgl_instance_stage(trgl_ctx* c, int vs, const trgl_uniforms* u, const double projection[16],
+                        const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                        const uint32_t* face_colors, int mesh_mem_kind, const double* instances, int instance_stride, uint64_t n_instances,
+                        const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind,
+                        double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const InstanceCall a{ vs, u, projection, vertices, stride, n_vertices, indices, n_faces, face_colors, mesh_mem_kind,
+                          instances, instance_stride, n_instances, instance_colors, visible, instance_mem_kind };
+    int K = 0; bool go;
+    if ((r = check_instance_call(c, "trgl_instance_stage", a, &K, &go))) return r;
+    if (!n_out) return fail(c, TRGL_E_INVALID, "trgl_instance_stage: n_out is null");
+    *n_out = 0;
+    if (!go) return TRGL_OK;
+    const bool has_colors = instance_colors || face_colors;
+    if (!clip_out || (K && !vary_out) || (has_colors && !colors_out)) return fail(c, TRGL_E_INVALID, "trgl_instance_stage: null output");
+    if (instance_mem_kind == TRGL_MEM_DEVICE && (((uintptr_t)clip_out | (K ? (uintptr_t)vary_out : 0) | (has_colors ? (uintptr_t)colors_out : 0)) & 15))
+        return fail(c, TRGL_E_INVALID, "trgl_instance_stage: device outputs must be 16-byte aligned");
+    return run_instanced(c, "trgl_instance_stage", a, K, false, 0, clip_out, vary_out, colors_out, n_out);
+}
 
 int trgl_register_shader_ex(trgl_ctx* c, const char* source, int n_varyings, uint32_t flags, int* kind) {
     CHKCTX(c);
@@ -195,9 +373,10 @@ int trgl_register_vertex_shader(trgl_ctx* c, const char* source, int n_varyings,
     std::string log;
     const std::vector<char>* code = nullptr;
     if (int r = user_vertex_shader_code(source, n_varyings, &log, &code)) return fail(c, r, "trgl_register_vertex_shader: " + log);
-    UserVertex v{ nullptr, nullptr, n_varyings };
+    UserVertex v{ nullptr, nullptr, n_varyings, nullptr };
     HIPCHK(c, hipModuleLoadData(&v.mod, code->data()));
-    const hipError_t e = hipModuleGetFunction(&v.fn, v.mod, USER_VERTEX_KERNEL);
+    hipError_t e = hipModuleGetFunction(&v.fn, v.mod, USER_VERTEX_KERNEL);
+    if (e == hipSuccess) e = hipModuleGetFunction(&v.fn_inst, v.mod, USER_VERTEX_INSTANCED_KERNEL);
     if (e != hipSuccess) {
         (void)hipModuleUnload(v.mod);
         return fail(c, TRGL_E_HIP, std::string("hipModuleGetFunction: ") + hipGetErrorString(e));

@@ -43,6 +43,9 @@ struct trgl_vert_in {
     int face, nth;               // the arguments of IShader::vertex; nth is 0, 1 or 2
     const trgl_uniforms* u;      // the draw's uniform block (texture slots -1 when the draw passed none)
     const double* projection;    // 16 doubles, row-major
+    uint32_t instance;           // instanced calls: the instance's original number; else 0
+    const double* inst;          // instanced calls: this instance's record (null when the call has none); else null
+    int inst_stride;             // instanced calls: doubles per instance record; else 0
 };
 // what it leaves: its return value and the shader's varying member arrays
 struct trgl_vert_out {

@@ -20,4 +20,5 @@ void set_global_error(const std::string& msg);
 constexpr const char* USER_SHADE_KERNEL = "trgl_shade_user";
 constexpr const char* USER_RASTER_KERNEL = "trgl_raster_user";
 constexpr const char* USER_VERTEX_KERNEL = "trgl_vertex_user";       // vertex_user.h
+constexpr const char* USER_VERTEX_INSTANCED_KERNEL = "trgl_vertex_user_instanced";     // ... its second kernel, in the same code object
 }  // namespace trgl

@@ -46,6 +46,7 @@ void trgl_vertex_user(VertexUserParams p) {
         in.nth = v;
         in.u = &p.u;
         in.projection = p.proj;
+        in.instance = 0u; in.inst = nullptr; in.inst_stride = 0;
         trgl_vert_out out;
         out.clip[0] = out.clip[1] = out.clip[2] = out.clip[3] = 0.0;
         out.vary = TRGL_VS_K ? s_vary + TRGL_VS_K * f : nullptr;
@@ -60,6 +61,70 @@ void trgl_vertex_user(VertexUserParams p) {
         for (uint32_t k = threadIdx.x; k < nf_blk * 6; k += TRGL_VS_THREADS) gc[k] = sc[k];
         if (TRGL_VS_K) {
             const uint32_t nd = nf_blk * TRGL_VS_K;                   // doubles of this block: odd only in a partial last block
+            const double2* sv = reinterpret_cast<const double2*>(s_vary);
+            double2* gv = reinterpret_cast<double2*>(p.vary + (uint64_t)TRGL_VS_K * f0);
+            for (uint32_t k = threadIdx.x; k < nd / 2; k += TRGL_VS_THREADS) gv[k] = sv[k];
+            if ((nd & 1u) && threadIdx.x == 0) p.vary[(uint64_t)TRGL_VS_K * f0 + nd - 1] = s_vary[nd - 1];
+        }
+    }
+}
+
+// The same stage over the flattened faces of an instanced call (include/trgl.h: trgl_draw_instanced): output face g of 0 .. i.total is
+// face g % nfaces of the mesh under slot g / nfaces - one 32-bit division per thread, so a block of 64 output faces spans as many
+// instances as it takes (a 12-face box: six of them).  Rows leave exactly as above; the output triangle's colour is written here too.
+extern "C" __global__ __launch_bounds__(TRGL_VS_THREADS)
+void trgl_vertex_user_instanced(VertexUserInstancedParams q) {
+    __shared__ __attribute__((aligned(16))) double s_clip[TRGL_VS_FACES * 12];
+    __shared__ __attribute__((aligned(16))) double s_vary[TRGL_VS_K ? TRGL_VS_FACES * TRGL_VS_K : 2];
+    const VertexUserParams& p = q.v;
+    const uint32_t f0 = blockIdx.x * TRGL_VS_FACES;                 // (total <= 2^31 - 1: no 32-bit sum here wraps)
+    const int f = threadIdx.x / 3, v = threadIdx.x - 3 * f;
+    const uint32_t g = f0 + (uint32_t)f;
+    const bool live = g < q.i.total;
+    const uint32_t nf_blk = q.i.total - f0 < (uint32_t)TRGL_VS_FACES ? q.i.total - f0 : (uint32_t)TRGL_VS_FACES;
+    uint32_t slot = 0, face = 0, inst = 0, index = 0;
+    if (live) {
+        slot = g / p.nfaces; face = g - slot * p.nfaces;
+        inst = q.i.list ? q.i.list[slot] : slot;
+        index = p.indices[(uint64_t)face * 3 + (uint32_t)v];
+    }
+    {
+        double2* zc = reinterpret_cast<double2*>(s_clip);
+        for (uint32_t k = threadIdx.x; k < TRGL_VS_FACES * 6; k += TRGL_VS_THREADS) zc[k] = make_double2(0.0, 0.0);
+        double2* zv = reinterpret_cast<double2*>(s_vary);
+        for (uint32_t k = threadIdx.x; k < TRGL_VS_FACES * TRGL_VS_K / 2; k += TRGL_VS_THREADS) zv[k] = make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    if (live) {
+        trgl_vert_in in;
+        in.vertex = p.vertices + (size_t)index * (size_t)p.stride;
+        in.stride = p.stride;
+        in.index = index;
+        in.face = (int)face;
+        in.nth = v;
+        in.u = &p.u;
+        in.projection = p.proj;
+        in.instance = inst;
+        in.inst = q.i.instances ? q.i.instances + (size_t)inst * (size_t)q.i.inst_stride : nullptr;
+        in.inst_stride = q.i.inst_stride;
+        trgl_vert_out out;
+        out.clip[0] = out.clip[1] = out.clip[2] = out.clip[3] = 0.0;
+        out.vary = TRGL_VS_K ? s_vary + TRGL_VS_K * f : nullptr;
+        trgl_vertex(in, out);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s_clip[12 * f + 4 * v + r] = out.clip[r];
+        if (v == 0) {
+            if (q.i.inst_colors) q.i.colors[g] = q.i.inst_colors[inst];
+            else if (q.i.face_colors) q.i.colors[g] = q.i.face_colors[face];
+        }
+    }
+    __syncthreads();
+    {
+        const double2* sc = reinterpret_cast<const double2*>(s_clip);
+        double2* gc = reinterpret_cast<double2*>(p.clip + 12 * (uint64_t)f0);
+        for (uint32_t k = threadIdx.x; k < nf_blk * 6; k += TRGL_VS_THREADS) gc[k] = sc[k];
+        if (TRGL_VS_K) {
+            const uint32_t nd = nf_blk * TRGL_VS_K;                   // odd only in a partial last block
             const double2* sv = reinterpret_cast<const double2*>(s_vary);
             double2* gv = reinterpret_cast<double2*>(p.vary + (uint64_t)TRGL_VS_K * f0);
             for (uint32_t k = threadIdx.x; k < nd / 2; k += TRGL_VS_THREADS) gv[k] = sv[k];

@@ -487,6 +487,56 @@ template <class ModelT> inline bool gl_draw_model(const ModelT& model, const ISh
                     model.vertices.size(), model.indices.data(), model.indices.size() / 3, framebuffer);
 }
 
+// The loop over models of main.cpp:647-736 for ONE mesh under many model matrices, in one call (include/trgl.h, trgl_draw_instanced):
+//     for m in models: if (visible(m)) { ModelView = ModelView * m.matrix; <the face loop of gl_draw_indexed> }
+// The shader's describe() is taken ONCE, under the ModelView of the call: the vertex stage of instance i runs under ModelView *
+// model_matrices[i] (geometry.h:196-205), the fragment stage of every instance under the ModelView and lights of that one descriptor -
+// the reference's loop with the shader constructed once, in front of it.  codes: one byte per matrix, drawn when bit 0 is set - what
+// gl_occlusion_test returns plugs in as it is; null: every instance.  A shader with a user vertex shader (vertex_kind >= 0) receives
+// the matrix as in.inst (16 doubles, row-major) and the instance's number as in.instance, and every face gets the descriptor's colour.
+// Clipping (gl_clip_plane) does not apply to instanced draws.
+namespace trgl_shim {
+inline bool draw_instanced(const IShader& shader, const double* vertices, int stride, std::size_t nv, const unsigned int* indices, std::size_t nfaces,
+                           const double* matrices, int matrix_stride, std::size_t n, const std::uint8_t* codes, int instance_mem_kind,
+                           TGAImage& framebuffer) {
+    State& s = state();
+    if (!bind(framebuffer)) return false;
+    bool ok = submit_batch();                                   // earlier rasterize() calls come first
+    trgl_shader_desc d;
+    if (!shader.describe(d)) {
+        std::fprintf(stderr, "trgl: gl_draw_instanced(): needs a shader with a device descriptor\n");
+        std::abort();
+    }
+    if (s.clip_on) return fail("gl_draw_instanced: a clip plane is set, and instanced draws are not clipped", TRGL_E_UNSUPPORTED, nullptr);
+    double vp[16], pj[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { vp[4 * r + c] = Viewport[r][c]; pj[4 * r + c] = Perspective[r][c]; }
+    static_assert(sizeof(unsigned int) == sizeof(std::uint32_t), "indices are 32-bit");
+    const std::vector<std::uint32_t> colors(d.vertex_kind >= 0 ? nfaces : 0, d.color);
+    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
+         TRGL_SHIM_OK(trgl_draw_instanced(s.ctx, d.vertex_kind >= 0 ? d.vertex_kind : -1, d.kind, &d.uniforms, pj, vertices, stride, nv,
+                                          reinterpret_cast<const std::uint32_t*>(indices), nfaces, d.vertex_kind >= 0 ? colors.data() : nullptr, TRGL_MEM_HOST,
+                                          matrices, matrix_stride, n, nullptr, codes, instance_mem_kind)) && ok;
+    s.zbuffer_stale_on_host = true;
+    return ok;
+}
+}  // namespace trgl_shim
+inline bool gl_draw_instanced(const IShader& shader, const double* vertices, int stride, std::size_t nv, const unsigned int* indices, std::size_t nfaces,
+                              const std::vector<mat<4, 4>>& model_matrices, TGAImage& framebuffer, const std::uint8_t* codes = nullptr) {
+    std::vector<double> m(model_matrices.size() * 16);
+    for (std::size_t i = 0; i < model_matrices.size(); ++i)
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m[16 * i + 4 * r + c] = model_matrices[i][r][c];
+    return trgl_shim::draw_instanced(shader, vertices, stride, nv, indices, nfaces, m.data(), 16, model_matrices.size(), codes, TRGL_MEM_HOST, framebuffer);
+}
+// ... with the instances in DEVICE memory: `matrices` (n records of matrix_stride >= 16 doubles, the matrix first, 8-byte aligned) and
+// `codes` (n bytes - as trgl_occlusion_boxes leaves them with TRGL_MEM_DEVICE - or null).  One memory kind covers both arrays in the C
+// ABI, so codes that stay on the device ask for matrices that live there too.  The call waits once, for the count of drawn instances.
+struct gl_device_instances { const double* matrices; int matrix_stride; std::size_t count; const std::uint8_t* codes; };
+inline bool gl_draw_instanced(const IShader& shader, const double* vertices, int stride, std::size_t nv, const unsigned int* indices, std::size_t nfaces,
+                              const gl_device_instances& instances, TGAImage& framebuffer) {
+    return trgl_shim::draw_instanced(shader, vertices, stride, nv, indices, nfaces, instances.matrices, instances.matrix_stride, instances.count,
+                                     instances.codes, TRGL_MEM_DEVICE, framebuffer);
+}
+
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
 // write_tga_file(), main.cpp:743,773).  The depths follow on demand through the `zbuffer` proxy.
 // false: something submitted since the last gl_flush() failed (gl_last_error()); the pixels hold what could be drawn.
