@@ -428,6 +428,73 @@ int trgl_instance_stage(trgl_ctx* ctx, int vs, const trgl_uniforms* uniforms, co
                         const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind,
                         double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out);
 
+/* ---- depth-ordered instanced draws: depths, an order, and the instanced calls under that order ------------------ */
+
+/* New work: the reference draws its models in the order of its command line (main.cpp:647) and sorts nothing.  Translucent kinds
+ * (TRGL_SHADER_READS_DEST, TRGL_SHADER_NO_DEPTH_WRITE) want their instances back to front, a discarding kind runs fewer fragment()
+ * calls front to back; these three calls make such an order and draw under it without the instance arrays leaving device memory.
+ *
+ * trgl_instance_depths: depths_out[i] = the view-space z of `point` (model space) under instance i - element 2 of
+ * (model_view * M_i) * embed<4>(point), summed as geometry.h sums it (operator* of two matrices, :196-205, then dot<4>, :123-127).
+ * With mv = model_view and M_i the first 16 doubles of instance i (row-major; instance_stride >= 16):
+ *     r_c = (((0.0 + mv[2][0]*M_i[0][c]) + mv[2][1]*M_i[1][c]) + mv[2][2]*M_i[2][c]) + mv[2][3]*M_i[3][c]      for c = 0 .. 3
+ *     d_i = (((0.0 + r_0*point[0]) + r_1*point[1]) + r_2*point[2]) + r_3*1.0
+ * Every product is rounded to fp64 and added without contraction (the rule of MV_i above).  mem_kind covers instances and depths_out.
+ * Device memory (8-byte aligned): one thread per instance, queued on the context's stream in order with the draws; the call does not
+ * wait and nothing is flushed.  Host memory: the same expressions in plain C++, complete on return, and ctx may be NULL.
+ * ERRORS.  TRGL_E_INVALID: a bad mem_kind, TRGL_MEM_DEVICE without a context, a null model_view or point, instance_stride < 16, a null
+ * or misaligned array.  TRGL_E_UNSUPPORTED: n_instances above 2^31 - 1.  n_instances == 0: TRGL_OK once the scalar arguments are checked, and no array is read. */
+int trgl_instance_depths(trgl_ctx* ctx, const double model_view[16], const double point[3],
+                         const double* instances, int instance_stride, uint64_t n_instances, int mem_kind, double* depths_out);
+
+/* trgl_depth_order: the order in which n depths - those of trgl_instance_depths, or any doubles of the caller's - are drawn.
+ * DEFINITION.  With b the 64 bits of depths[i],  key(i) = b ^ ((b >> 63) ? 0xFFFFFFFFFFFFFFFF : 0x8000000000000000),  an unsigned
+ * 64-bit integer that ascends as: NaNs with the sign bit set < -inf < ... < -0.0 < +0.0 < ... < +inf < NaNs with the sign bit clear.
+ * -0.0 and +0.0 are different keys; no comparison of doubles takes part.
+ *   TRGL_ORDER_BACK_TO_FRONT: order_out is the permutation of 0 .. n-1 that puts key(i) into non-decreasing order, equal keys in
+ *     ascending i.  camera.h's view matrix looks down -z (camera.h:192-204, zAxis = eye - target: visible points have negative view z), so the
+ *     smallest depth is the farthest instance and this order is farthest first.
+ *   TRGL_ORDER_FRONT_TO_BACK: the same with ~key(i) in place of key(i): nearest first, equal keys STILL in ascending i - it is not
+ *     the other list reversed.
+ * mem_kind covers depths and order_out.  Device memory (depths 8-byte, order_out 4-byte aligned): a key kernel writes the keys and
+ * 0 .. n-1, a stable LSD radix sort over all 64 key bits follows (integers only), out of scratch the context owns; queued on the
+ * context's stream, no wait (n is known on the host), nothing is flushed.  Host memory: std::stable_sort on the same keys, and ctx may
+ * be NULL.
+ * ERRORS.  TRGL_E_INVALID: a bad direction or mem_kind, TRGL_MEM_DEVICE without a context, a null or misaligned array.
+ * TRGL_E_UNSUPPORTED: n above 2^31 - 1.  n == 0: TRGL_OK, and no array is read. */
+#define TRGL_ORDER_BACK_TO_FRONT 0
+#define TRGL_ORDER_FRONT_TO_BACK 1
+int trgl_depth_order(trgl_ctx* ctx, const double* depths, uint64_t n, int direction, int mem_kind, uint32_t* order_out);
+
+/* trgl_draw_instanced / trgl_instance_stage with the instances visited in the order a list names.
+ *   order : n_order x uint32 in order_mem_kind memory (device: 4-byte aligned), or NULL - allowed exactly when n_order == 0, and the call
+ *           then IS trgl_draw_instanced / trgl_instance_stage.
+ * DEFINITION.  Positions p = 0 .. n_order - 1 are visited in ascending p, with i = order[p].  Instance i is drawn at this position when
+ *   i < n_instances and (visible == NULL or (visible[i] & 1) != 0).  The drawn positions are numbered j = 0 .. n_vis - 1 in ascending
+ *   p, and i_j = order[p_j].  From here on every word of the DEFINITION of trgl_draw_instanced holds with these i_j: output triangle
+ *   j * n_faces + f, in.instance = i_j (the original number), instance_colors[i_j], the equivalence with the loop of trgl_vertex_stage +
+ *   trgl_draw over j, the counters.  An instance named twice is drawn twice; one that is not named is not drawn.
+ *   An entry >= n_instances: in a host list TRGL_E_INVALID (nothing is queued); in a device list it is skipped, and it is never used as
+ *   an index.  The outputs of trgl_instance_stage_ordered have room for n_order * n_faces rows.
+ * SYNCHRONISATION.  order in host memory and visible NULL or in host memory: the list of drawn instances is made on the host; no wait.
+ *   Otherwise - a device list, or device visibility bytes - the compaction of trgl_draw_instanced runs on the stream over the positions
+ *   (an array in host memory is copied first) and the call waits ONCE, for the 8-byte count n_vis.
+ * ERRORS.  Those of trgl_draw_instanced, and TRGL_E_INVALID: order == NULL with n_order != 0 (or the reverse), a bad order_mem_kind, a
+ *   misaligned device list, a host entry out of range.  TRGL_E_UNSUPPORTED: n_order or n_vis * n_faces above 2^31 - 1. */
+int trgl_draw_instanced_ordered(trgl_ctx* ctx, int vs, int shader_kind, const trgl_uniforms* uniforms, const double projection[16],
+                                const double* vertices, int vertex_stride, uint64_t n_vertices,
+                                const uint32_t* indices, uint64_t n_faces, const uint32_t* face_colors, int mesh_mem_kind,
+                                const double* instances, int instance_stride, uint64_t n_instances,
+                                const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind,
+                                const uint32_t* order, uint64_t n_order, int order_mem_kind);
+int trgl_instance_stage_ordered(trgl_ctx* ctx, int vs, const trgl_uniforms* uniforms, const double projection[16],
+                                const double* vertices, int vertex_stride, uint64_t n_vertices,
+                                const uint32_t* indices, uint64_t n_faces, const uint32_t* face_colors, int mesh_mem_kind,
+                                const double* instances, int instance_stride, uint64_t n_instances,
+                                const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind,
+                                const uint32_t* order, uint64_t n_order, int order_mem_kind,
+                                double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out);
+
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 
 /* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and

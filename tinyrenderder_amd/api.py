@@ -39,6 +39,7 @@ OCCL_HIDDEN, OCCL_VISIBLE, OCCL_OUTSIDE, OCCL_UNDECIDED = range(4)     # TRGL_OC
 # the sizes of the instanced stages (csrc/launch.h): instances per block of the compaction, block counts per block of its scan's lower
 # level, output faces per block of the instanced vertex kernels
 INST_BLOCK, INST_SCAN_CHUNK, INST_VS_FACES = 256, 256, 64
+ORDER_BACK_TO_FRONT, ORDER_FRONT_TO_BACK = 0, 1     # TRGL_ORDER_*
 NEAR_PLANE = (0.0, 0.0, 1.0, 1.0)     # the near plane of the reference's projection in clip space: z + w >= 0
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
 
@@ -62,6 +63,7 @@ SYMBOLS = [
     "trgl_clip_layout", "trgl_clip_stage", "trgl_draw_clipped", "trgl_draw_indexed_vs_clipped",
     "trgl_occlusion_boxes_image", "trgl_occlusion_boxes",
     "trgl_draw_instanced", "trgl_instance_stage",
+    "trgl_instance_depths", "trgl_depth_order", "trgl_draw_instanced_ordered", "trgl_instance_stage_ordered",
 ]
 
 
@@ -254,6 +256,11 @@ def load_library(path: str = None):
             C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int]                   # the instances
     L.trgl_draw_instanced.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Uniforms), dp] + inst
     L.trgl_instance_stage.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp] + inst + [C.c_void_p, C.c_void_p, C.c_void_p, u64p]
+    order = [C.c_void_p, C.c_uint64, C.c_int]
+    L.trgl_draw_instanced_ordered.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Uniforms), dp] + inst + order
+    L.trgl_instance_stage_ordered.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp] + inst + order + [C.c_void_p, C.c_void_p, C.c_void_p, u64p]
+    L.trgl_instance_depths.argtypes = [vp, dp, dp, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
+    L.trgl_depth_order.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -543,6 +550,58 @@ def occlusion_boxes_image(depth, viewport, view_proj, boxes) -> np.ndarray:
     the depths [h, w] under the row-major viewport and view_proj = Perspective * ModelView (the steps are written down in include/trgl.h).
     Bit 0 of a code set: draw the model.  Needs no GPU."""
     return _host_occlusion_boxes_image(load_library(), None, depth, viewport, view_proj, boxes)
+
+
+def _instance_depths(L, handle, model_view, point, instances, device):
+    mv, pt = _f64(model_view, 16, "model_view"), _f64(point, 3, "point")
+    if device:
+        if not hasattr(instances, "data_ptr") or str(instances.dtype) != "torch.float64" or not instances.is_contiguous() or instances.dim() != 2:
+            raise ValueError("device=True: instances must be a contiguous float64 device tensor [n, stride]")
+        import torch
+        out = torch.empty(int(instances.shape[0]), dtype=torch.float64, device=instances.device)
+        ptrs = (_device_ptr(instances, "instances") if out.numel() else None, out.data_ptr() if out.numel() else None)
+    else:
+        instances = np.ascontiguousarray(instances, np.float64)
+        if instances.ndim != 2:
+            raise ValueError("instances: [n, stride] expected")
+        out = np.empty(instances.shape[0], np.float64)
+        ptrs = (instances.ctypes.data, out.ctypes.data)
+    rc = L.trgl_instance_depths(handle, _dp(mv), _dp(pt), ptrs[0], int(instances.shape[1]), int(instances.shape[0]),
+                                MEM_DEVICE if device else MEM_HOST, ptrs[1])
+    if rc != 0:
+        raise TrglError(f"trgl_instance_depths failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return instances, out
+
+
+def _depth_order(L, handle, depths, front_to_back, device):
+    if device:
+        if not hasattr(depths, "data_ptr") or str(depths.dtype) != "torch.float64" or not depths.is_contiguous() or depths.dim() != 1:
+            raise ValueError("device=True: depths must be a contiguous float64 device tensor [n]")
+        import torch
+        out = torch.empty(int(depths.shape[0]), dtype=torch.int32, device=depths.device)       # (torch has no uint32 arithmetic: the bits are uint32)
+        ptrs = (_device_ptr(depths, "depths") if out.numel() else None, out.data_ptr() if out.numel() else None)
+    else:
+        depths = np.ascontiguousarray(depths, np.float64).reshape(-1)
+        out = np.empty(depths.shape[0], np.uint32)
+        ptrs = (depths.ctypes.data, out.ctypes.data)
+    rc = L.trgl_depth_order(handle, ptrs[0], int(depths.shape[0]), ORDER_FRONT_TO_BACK if front_to_back else ORDER_BACK_TO_FRONT,
+                            MEM_DEVICE if device else MEM_HOST, ptrs[1])
+    if rc != 0:
+        raise TrglError(f"trgl_depth_order failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return depths, out
+
+
+def instance_depths(model_view, point, instances) -> np.ndarray:
+    """trgl_instance_depths for host arrays without a context: the view-space z of `point` (model space) under every instance [n, stride
+    >= 16] - element 2 of (model_view * M_i) * (point, 1), summed as the reference's geometry.h sums it.  Needs no GPU."""
+    return _instance_depths(load_library(), None, model_view, point, instances, False)[1]
+
+
+def depth_order(depths, front_to_back=False) -> np.ndarray:
+    """trgl_depth_order for a host array without a context: the uint32 permutation that draws the depths farthest first (under a view
+    matrix that looks down -z: ascending), or nearest first; ties in ascending number either way.  The order is that of the doubles' bit
+    patterns as include/trgl.h defines it (-0.0 before +0.0, NaNs at the ends by their sign).  Needs no GPU."""
+    return _depth_order(load_library(), None, depths, front_to_back, False)[1]
 
 
 def clip_layout(kind: int):
@@ -923,47 +982,97 @@ class Context:
                 ip[0], inst_stride, n_inst, ip[1], ip[2], MEM_DEVICE if instances_device else MEM_HOST]
         return args, nf, n_inst, face_colors is not None or instance_colors is not None, (vertices, indices, face_colors, instances, instance_colors, visible)
 
+    def _order_args(self, order, order_device):
+        """The three order arguments of the ordered calls as (ctypes arguments, n_order, what to keep alive)."""
+        if order_device:
+            if str(getattr(order, "dtype", "")) not in ("torch.int32", "torch.uint32") or not order.is_contiguous() or order.dim() != 1:
+                raise ValueError("order_device=True: order must be a contiguous 32-bit integer device tensor [n_order]")
+            n = int(order.shape[0])
+            return [_device_ptr(order, "order") if n else None, n, MEM_DEVICE], n, order
+        order = np.ascontiguousarray(order, np.uint32).reshape(-1)
+        return [order.ctypes.data if order.size else None, int(order.size), MEM_HOST], int(order.size), order
+
+    def instance_depths(self, model_view, point, instances, device=False):
+        """trgl_instance_depths: the view-space z of `point` (a point of the mesh in model space) under every instance [n, stride >= 16].
+        Host arrays: a numpy array, no GPU work.  device=True: instances is a contiguous float64 device tensor; the depths come back
+        as a device tensor, queued on the context's stream without waiting."""
+        instances, out = _instance_depths(self.L, self.h, model_view, point, instances, device)
+        if device:
+            self._keep.append((instances, out))
+        return out
+
+    def depth_order(self, depths, front_to_back=False, device=False):
+        """trgl_depth_order: the order in which to draw instances of these depths - farthest first, or with front_to_back nearest first;
+        ties ascend either way.  Host array: a uint32 numpy array.  device=True: depths is a contiguous float64 device tensor; the
+        order comes back as an int32 device tensor (its bits are the uint32 numbers), sorted on the context's stream without waiting.
+        Pass it to draw_instanced / instance_stage as order=..., order_device=True."""
+        depths, out = _depth_order(self.L, self.h, depths, front_to_back, device)
+        if device:
+            self._keep.append((depths, out))
+        return out
+
     def draw_instanced(self, kind, uniforms, projection, vertices, indices, instances=None, vertex_shader=None, face_colors=None,
-                       instance_colors=None, visible=None, device=False, instances_device=False):
+                       instance_colors=None, visible=None, device=False, instances_device=False, order=None, order_device=False):
         """trgl_draw_instanced: the mesh (vertices [nv, stride], indices [nf, 3]) once per instance whose `visible` byte has bit 0 set
         (visible None: every instance), in ascending instance order.  instances [n, stride]: with the built-in stage (vertex_shader None)
         the first 16 doubles are a row-major model matrix M and the stage runs under uniforms.model_view * M; a user vertex shader
         reads them as in.inst.  Colours: instance_colors [n] or face_colors [nf], not both.  device: the mesh arrays are device
         tensors; instances_device: instances, instance_colors and visible are (the codes of occlusion_boxes(device=True) are a valid
-        `visible`; the call then waits once for the count of drawn instances)."""
+        `visible`; the call then waits once for the count of drawn instances).  order (trgl_draw_instanced_ordered): the instances
+        are visited in the order this list of numbers names them - the result of depth_order, or any list; an instance named twice
+        is drawn twice, one that is not named is not drawn, an empty list draws nothing; order_device: the list is a device tensor (entries out of range are
+        skipped, and the call waits once for the count)."""
         pj = np.ascontiguousarray(projection, np.float64).reshape(16)
         args, _, _, _, keep = self._instance_args(vertices, indices, instances, face_colors, instance_colors, visible, device, instances_device)
-        if device or instances_device:
-            self._keep.append(keep)
-        self._chk(self.L.trgl_draw_instanced(self.h, -1 if vertex_shader is None else int(vertex_shader), kind,
-                                             None if uniforms is None else C.byref(uniforms), _dp(pj), *args))
+        vs = -1 if vertex_shader is None else int(vertex_shader)
+        if order is None:
+            if device or instances_device:
+                self._keep.append(keep)
+            self._chk(self.L.trgl_draw_instanced(self.h, vs, kind, None if uniforms is None else C.byref(uniforms), _dp(pj), *args))
+            return
+        oargs, n_order, okeep = self._order_args(order, order_device)
+        if n_order == 0:                     # no position to visit: nothing is drawn (the C call takes a null list for "no list")
+            return
+        if device or instances_device or order_device:
+            self._keep.append(keep + (okeep,))
+        self._chk(self.L.trgl_draw_instanced_ordered(self.h, vs, kind, None if uniforms is None else C.byref(uniforms), _dp(pj), *args, *oargs))
 
     def instance_stage(self, vertex_shader, uniforms, projection, vertices, indices, instances=None, face_colors=None, instance_colors=None,
-                       visible=None, device=False, instances_device=False, out=None):
+                       visible=None, device=False, instances_device=False, out=None, order=None, order_device=False):
         """trgl_instance_stage: the stages of draw_instanced alone; returns (clip, varyings, colors, n_out) with n_out = drawn instances
         * nf rows written.  vertex_shader: a number from register_vertex_shader, or -1 / None for the built-in stage (K = 24).
         Host instances: numpy arrays cut to n_out rows (varyings [n_out, K]; colors None when the call has none).  instances_device=True:
         out = (clip, varyings, colors) are 16-byte aligned device tensors with room for n * nf rows (varyings may be None when K = 0,
-        colors when the call has none); they come back as they are."""
+        colors when the call has none); they come back as they are.  order / order_device: as for draw_instanced
+        (trgl_instance_stage_ordered); the outputs then need room for len(order) * nf rows."""
         vs = -1 if vertex_shader is None else int(vertex_shader)
         K = VARY[PHONG] if vs < 0 else getattr(self, "_vertex_vary", {}).get(vs, 0)
         pj = np.ascontiguousarray(projection, np.float64).reshape(16)
         args, nf, n_inst, has_colors, keep = self._instance_args(vertices, indices, instances, face_colors, instance_colors, visible, device, instances_device)
         n_out = C.c_uint64(0)
+        oargs, n_order, okeep = (None, n_inst, None) if order is None else self._order_args(order, order_device)
+        if order_device:
+            self._keep.append((okeep,))
         if instances_device:
             clip, vary, col = out
             optrs = (_device_ptr(clip, "clip"), _device_ptr(vary, "varyings"), _device_ptr(col, "colors"))
             self._keep.append(keep + (clip, vary, col))
         else:
             assert out is None, "out: only with instances_device=True"
-            rows = n_inst * nf
+            rows = n_order * nf
             clip, vary = np.zeros((rows, 12), np.float64), np.zeros((rows, K), np.float64)
             col = np.zeros(rows, np.uint32) if has_colors else None
             optrs = (clip.ctypes.data, vary.ctypes.data if K else None, col.ctypes.data if has_colors else None)
             if device:
                 self._keep.append(keep)
-        self._chk(self.L.trgl_instance_stage(self.h, vs, None if uniforms is None else C.byref(uniforms), _dp(pj), *args,
-                                             optrs[0], optrs[1], optrs[2], C.byref(n_out)))
+        if order is not None and n_order == 0:
+            pass                             # no position to visit: no rows (the C call takes a null list for "no list")
+        elif order is None:
+            self._chk(self.L.trgl_instance_stage(self.h, vs, None if uniforms is None else C.byref(uniforms), _dp(pj), *args,
+                                                 optrs[0], optrs[1], optrs[2], C.byref(n_out)))
+        else:
+            self._chk(self.L.trgl_instance_stage_ordered(self.h, vs, None if uniforms is None else C.byref(uniforms), _dp(pj), *args, *oargs,
+                                                         optrs[0], optrs[1], optrs[2], C.byref(n_out)))
         n = int(n_out.value)
         if instances_device:
             return clip, vary, col, n

@@ -11,6 +11,10 @@
 //                        instance number and no atomic decides where anything goes.  The lane writes list[slot] and, for the built-in
 //                        vertex stage, MV = model_view * M of its instance (128 bytes): the vertex kernel then reads a finished matrix
 //                        instead of doing the 4x4 product once per face-vertex.
+//   k_inst_count_ordered, k_inst_scatter_ordered : the same two kernels over the POSITIONS of an order list (trgl_draw_instanced_ordered):
+//                        lane p reads i = order[p] and its bit is i < n && (no visibility bytes || visible[i] & 1) - an entry out of range
+//                        is never used as an index - and the scatter writes list[slot] = i and MV of instance i.  The scans between
+//                        them, and everything behind the list, are the unordered call's.
 //   k_inst_mv          : those matrices alone, for a list made elsewhere (on the host) or for a call without visibility bytes.
 //   k_instance_vertex_stage : k_vertex_stage (kernels_post.hip) over the FLATTENED faces 0 .. n_vis * nfaces.  Output face g is face
 //                        g % nfaces of the mesh under slot g / nfaces (one 32-bit division per thread), so a block of 64 output faces spans
@@ -106,6 +110,43 @@ __global__ __launch_bounds__(INST_BLOCK) void k_inst_scatter(const uint8_t* __re
     if (mv_out) write_mv(mvu.m, instances + (size_t)i * (size_t)inst_stride, mv_out + 16 * (size_t)slot);
 }
 
+// the ballot of "drawn at this position" over this lane's wave; *mine: this lane's own bit, *inst: the instance its position names
+__device__ __forceinline__ unsigned long long ordered_ballot(const uint32_t* __restrict__ order, const uint8_t* __restrict__ visible, uint32_t p,
+                                                             uint32_t n_order, uint32_t n, bool* mine, uint32_t* inst) {
+    const uint32_t i = p < n_order ? order[p] : 0xffffffffu;
+    bool m = i < n;                                                       // (n < 2^31: a position past the list fails this too)
+    if (m && visible) m = (visible[i] & 1u) != 0;
+    *mine = m; *inst = i;
+    return __ballot(m);
+}
+
+__global__ __launch_bounds__(INST_BLOCK) void k_inst_count_ordered(const uint32_t* __restrict__ order, uint32_t n_order, const uint8_t* __restrict__ visible,
+                                                                   uint32_t n, uint32_t* __restrict__ blk) {
+    __shared__ uint32_t s_w[4];
+    bool mine; uint32_t i;
+    const unsigned long long b = ordered_ballot(order, visible, blockIdx.x * INST_BLOCK + threadIdx.x, n_order, n, &mine, &i);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ __launch_bounds__(INST_BLOCK) void k_inst_scatter_ordered(const uint32_t* __restrict__ order, uint32_t n_order, const uint8_t* __restrict__ visible,
+                                                                     uint32_t n, const uint32_t* __restrict__ blk, const uint32_t* __restrict__ chunk,
+                                                                     uint32_t* __restrict__ list, Mat4 mvu, const double* __restrict__ instances,
+                                                                     int inst_stride, double* __restrict__ mv_out) {
+    __shared__ uint32_t s_w[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    bool mine; uint32_t i;
+    const unsigned long long b = ordered_ballot(order, visible, blockIdx.x * INST_BLOCK + threadIdx.x, n_order, n, &mine, &i);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (!mine) return;
+    uint32_t slot = chunk[blockIdx.x / INST_SCAN_CHUNK] + blk[blockIdx.x] + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) slot += s_w[w];
+    list[slot] = i;
+    if (mv_out) write_mv(mvu.m, instances + (size_t)i * (size_t)inst_stride, mv_out + 16 * (size_t)slot);
+}
+
 __global__ __launch_bounds__(256) void k_inst_mv(const uint32_t* __restrict__ list, uint32_t n_vis, Mat4 mvu, const double* __restrict__ instances,
                                                  int inst_stride, double* __restrict__ mv_out) {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
@@ -181,6 +222,19 @@ void launch_inst_compact(hipStream_t s, const uint8_t* visible, uint32_t n, uint
     hipLaunchKernelGGL(k_inst_scan_chunks, dim3(nchunks), dim3(INST_SCAN_CHUNK), 0, s, blk, nblk, chunk);
     hipLaunchKernelGGL(k_inst_scan_top, dim3(1), dim3(INST_SCAN_CHUNK), 0, s, chunk, nchunks, total);
     hipLaunchKernelGGL(k_inst_scatter, dim3(nblk), dim3(INST_BLOCK), 0, s, visible, n, blk, chunk, list, mvu, instances, inst_stride, mv_out);
+}
+
+void launch_inst_compact_ordered(hipStream_t s, const uint32_t* order, uint32_t n_order, const uint8_t* visible, uint32_t n, uint32_t* scratch,
+                                 uint32_t* list, const double model_view[16], const double* instances, int inst_stride, double* mv_out) {
+    const uint32_t nblk = inst_num_blocks(n_order), nchunks = (nblk + INST_SCAN_CHUNK - 1) / INST_SCAN_CHUNK;
+    unsigned long long* total = reinterpret_cast<unsigned long long*>(scratch);
+    uint32_t* blk = scratch + 2; uint32_t* chunk = blk + nblk;
+    Mat4 mvu; for (int e = 0; e < 16; ++e) mvu.m[e] = mv_out ? model_view[e] : 0.0;
+    hipLaunchKernelGGL(k_inst_count_ordered, dim3(nblk), dim3(INST_BLOCK), 0, s, order, n_order, visible, n, blk);
+    hipLaunchKernelGGL(k_inst_scan_chunks, dim3(nchunks), dim3(INST_SCAN_CHUNK), 0, s, blk, nblk, chunk);
+    hipLaunchKernelGGL(k_inst_scan_top, dim3(1), dim3(INST_SCAN_CHUNK), 0, s, chunk, nchunks, total);
+    hipLaunchKernelGGL(k_inst_scatter_ordered, dim3(nblk), dim3(INST_BLOCK), 0, s, order, n_order, visible, n, blk, chunk, list, mvu, instances,
+                       inst_stride, mv_out);
 }
 
 void launch_inst_mv(hipStream_t s, const uint32_t* list, uint32_t n_vis, const double model_view[16], const double* instances,

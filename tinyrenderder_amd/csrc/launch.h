@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -176,12 +176,28 @@ size_t inst_scratch_words(uint64_t n);       // 2 words for the 8-byte count, th
 // words, *total its first two.  Four launches, in order on `s`.  0 < n < 2^31.
 void launch_inst_compact(hipStream_t s, const uint8_t* visible, uint32_t n, uint32_t* scratch, uint32_t* list,
                          const double model_view[16], const double* instances, int inst_stride, double* mv_out);
+// The same over the positions of an order list (trgl_draw_instanced_ordered): position p names instance i = order[p] and is drawn when
+// i < n and (visible null or visible[i] & 1); list[j] = i_j in ascending p, *total = n_vis, mv_out as above.  An entry >= n is skipped
+// and never used as an index.  scratch: inst_scratch_words(n_order) words; list (and mv_out) with room for n_order entries.
+// 0 < n_order < 2^31, 0 < n < 2^31.
+void launch_inst_compact_ordered(hipStream_t s, const uint32_t* order, uint32_t n_order, const uint8_t* visible, uint32_t n, uint32_t* scratch,
+                                 uint32_t* list, const double model_view[16], const double* instances, int inst_stride, double* mv_out);
 // mv_out[j] = model_view * M_{list[j]} for j < n_vis (list null: M_j) - for a list that was not made by launch_inst_compact
 void launch_inst_mv(hipStream_t s, const uint32_t* list, uint32_t n_vis, const double model_view[16], const double* instances,
                     int inst_stride, double* mv_out);
 // k_vertex_stage over the flattened faces ip.total = n_vis * nfaces, the model-view matrix of output face g being ip.mv + 16 * (g / nfaces)
 void launch_instance_vertex_stage(hipStream_t s, const InstanceParams& ip, const double proj[16], const double* vertices, int stride,
                                   const uint32_t* indices, uint32_t nfaces, double* clip, double* vary);
+
+// Depths and a depth order for the instances (kernels_order.hip; both are written down at trgl_instance_depths / trgl_depth_order in
+// include/trgl.h).  launch_instance_depths: one thread per instance, 0 < n < 2^31.  launch_depth_order: a key kernel (key or ~key as
+// uint64, and 0 .. n-1), then hipcub's stable radix sort of the pairs over all 64 bits; scratch: depth_order_scratch_bytes(n) bytes,
+// 256-byte aligned.  0 < n < 2^31.
+void launch_instance_depths(hipStream_t s, const double model_view[16], const double point[3], const double* instances, int inst_stride,
+                            uint32_t n, double* depths);
+hipError_t depth_order_scratch_bytes(uint32_t n, size_t* bytes);
+hipError_t launch_depth_order(hipStream_t s, const double* depths, uint32_t n, bool front_to_back, void* scratch, size_t scratch_bytes,
+                              uint32_t* order);
 
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,

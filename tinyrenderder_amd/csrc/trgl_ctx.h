@@ -94,6 +94,7 @@ struct trgl_ctx {
     // trgl_draw_instanced / trgl_instance_stage: the 8-byte count of drawn instances and the words of the compaction's scan; the list of
     // drawn instances; model_view * M per drawn instance for the built-in stage.  Read by the stages the call queues; grow on demand
     DevBuf<uint32_t> inst_scratch, inst_list; DevBuf<double> inst_mv;
+    DevBuf<uint8_t> order_scratch;      // trgl_depth_order: the keys, their sorted copy, the numbers 0 .. n-1, the sort's own space; grows on demand
     DevBuf<uint8_t> pp_out;            // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
     DevBuf<uint32_t> chunk_off;         // pairs before every 16th setup block
@@ -185,4 +186,7 @@ uint64_t host_clip_stage(const double plane[4], const ClipTable& tab, int K, con
 // the codes of n boxes against a w x h depth image in host memory (depth is not read when w * h == 0)
 void host_occlusion_boxes(const double* depth, int w, int h, const double viewport[16], const double view_proj[16],
                           const double* boxes, uint64_t n, uint8_t* codes);
+// trgl_instance_depths and trgl_depth_order over host arrays (host_depth_order: false when it ran out of memory)
+void host_instance_depths(const double model_view[16], const double point[3], const double* instances, int stride, uint64_t n, double* depths);
+bool host_depth_order(const double* depths, uint64_t n, bool front_to_back, uint32_t* order);
 }  // namespace trgl

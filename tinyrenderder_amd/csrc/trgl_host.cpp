@@ -1,6 +1,7 @@
 // trgl_host.cpp — the part of the C ABI in include/trgl.h that runs on the host alone and includes no HIP header: mesh attributes and
 // bounds in host memory, AABB / frustum / shadow-matrix maths, TGA and OBJ files, stats formatting, the global error string.
 // Its arithmetic is pinned bit for bit to the reference (-ffp-contract=off; the sums are chains of `sum += ...`, in the reference's order).
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -158,6 +159,36 @@ void host_occlusion_boxes(const double* depth, int w, int h, const double viewpo
         }
         codes[i] = (uint8_t)code;
     }
+}
+
+// ---- depths of instances and their order in host memory (include/trgl.h, trgl_instance_depths / trgl_depth_order) -------------------
+// dot<4> (geometry.h:122-127) with the four right-hand values apart: summed left to right from 0
+static inline double dot4_from_zero(const double* a, double x, double y, double z, double w) {
+    double sum = 0; sum += a[0] * x; sum += a[1] * y; sum += a[2] * z; sum += a[3] * w; return sum;
+}
+
+void host_instance_depths(const double model_view[16], const double point[3], const double* instances, int stride, uint64_t n, double* depths) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const double* M = instances + i * (uint64_t)stride;
+        double r[4];
+        for (int c = 0; c < 4; ++c) r[c] = dot4_from_zero(model_view + 8, M[c], M[4 + c], M[8 + c], M[12 + c]);      // geometry.h:196-205, row 2
+        depths[i] = dot4_from_zero(r, point[0], point[1], point[2], 1.0);
+    }
+}
+
+// false: out of memory
+bool host_depth_order(const double* depths, uint64_t n, bool front_to_back, uint32_t* order) {
+    try {
+        std::vector<uint64_t> keys(n);
+        const uint64_t flip = front_to_back ? ~0ull : 0ull;
+        for (uint64_t i = 0; i < n; ++i) {
+            uint64_t b; std::memcpy(&b, depths + i, sizeof(b));
+            keys[i] = (b ^ ((b >> 63) ? ~0ull : 1ull << 63)) ^ flip;
+            order[i] = (uint32_t)i;
+        }
+        std::stable_sort(order, order + n, [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+    } catch (const std::bad_alloc&) { return false; }                         // (std::stable_sort falls back to merging in place)
+    return true;
 }
 }  // namespace trgl
 using namespace trgl;

@@ -1,7 +1,7 @@
 // trgl_shader.cpp — run-time shader registration (fragment kinds and vertex shaders, compiled by user_shaders.cpp) and the entry points
 // that run a stage in front of a draw: the vertex stage over an indexed mesh (trgl_draw_indexed, trgl_draw_indexed_vs, trgl_vertex_stage)
 // the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and the instanced stages (trgl_draw_instanced,
-// trgl_instance_stage).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
+// trgl_instance_stage, their ordered forms, and the depths and order those take: trgl_instance_depths, trgl_depth_order).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <cstring>
 #include <memory>
 #include <new>
@@ -169,6 +169,7 @@ struct InstanceCall {
     int vs; const trgl_uniforms* u; const double* projection;
     const double* vertices; int stride; uint64_t n_vertices; const uint32_t* indices; uint64_t n_faces; const uint32_t* face_colors; int mesh_mem;
     const double* instances; int inst_stride; uint64_t n_inst; const uint32_t* inst_colors; const uint8_t* visible; int inst_mem;
+    const uint32_t* order = nullptr; uint64_t n_order = 0; int order_mem = TRGL_MEM_HOST;      // the ordered calls; order null: ascending i
 };
 
 // what trgl_draw_instanced and trgl_instance_stage check alike; K of the stage comes back in *K; *go: there is something to run
@@ -186,6 +187,19 @@ static int check_instance_call(trgl_ctx* c, const char* who, const InstanceCall&
     if (a.inst_mem == TRGL_MEM_DEVICE && (((uintptr_t)a.instances & 7) || ((uintptr_t)a.inst_colors & 3)))
         return fail(c, TRGL_E_INVALID, w + "device arrays need natural alignment (8 bytes for instances, 4 for colours)");
     *go = a.n_inst != 0 && a.n_faces != 0;
+    return TRGL_OK;
+}
+
+// what the ordered calls check of their list on top of that (a list with no entries is no list: the call is the unordered one)
+static int check_instance_order(trgl_ctx* c, const char* who, const InstanceCall& a, bool go) {
+    const std::string w = std::string(who) + ": ";
+    if (!valid_mem_kind(a.order_mem)) return fail(c, TRGL_E_INVALID, w + "bad order_mem_kind");
+    if ((a.order == nullptr) != (a.n_order == 0)) return fail(c, TRGL_E_INVALID, w + "order must be null exactly when n_order is 0");
+    if (a.n_order > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more entries in the order list");
+    if (a.order_mem == TRGL_MEM_DEVICE && ((uintptr_t)a.order & 3)) return fail(c, TRGL_E_INVALID, w + "a device order list must be 4-byte aligned");
+    if (go && a.order_mem == TRGL_MEM_HOST)
+        for (uint64_t p = 0; p < a.n_order; ++p)
+            if (a.order[p] >= a.n_inst) return fail(c, TRGL_E_INVALID, w + "an entry of the order list is not an instance");
     return TRGL_OK;
 }
 
@@ -218,13 +232,33 @@ static int run_instanced(trgl_ctx* c, const char* who, const InstanceCall& a, in
     // a. which instances are drawn: list (null: all of them, in order) and n_vis
     const uint32_t* list = nullptr;
     uint64_t n_vis = a.n_inst;
-    bool mv_done = false;
+    bool mv_done = false, have_host_list = false;
     std::vector<uint32_t> host_list;
-    if (a.visible && a.inst_mem == TRGL_MEM_HOST) {
+    if (a.order && a.order_mem == TRGL_MEM_HOST && (!a.visible || a.inst_mem == TRGL_MEM_HOST)) {
+        try {                                                     // (its entries are checked: all below n_inst)
+            for (uint64_t q = 0; q < a.n_order; ++q) if (!a.visible || (a.visible[a.order[q]] & 1u)) host_list.push_back(a.order[q]);
+        } catch (const std::bad_alloc&) { return fail(c, TRGL_E_NOMEM, w + "out of memory"); }
+        n_vis = host_list.size(); have_host_list = true;
+    } else if (a.order) {
+        // the compaction over the positions: a device list (its entries may be anything), or device bytes behind a host list
+        const uint32_t* dorder = a.order; const uint8_t* dvis = a.visible;
+        if (a.order_mem == TRGL_MEM_HOST) { if ((r = dev_copy(a.order, a.n_order * sizeof(uint32_t), &p))) return r; dorder = (const uint32_t*)p; }
+        if (a.visible && a.inst_mem == TRGL_MEM_HOST) { if ((r = dev_copy(a.visible, a.n_inst, &p))) return r; dvis = (const uint8_t*)p; }
+        const bool mv_here = builtin && a.inst_mem == TRGL_MEM_DEVICE;      // (host matrices are not on the device yet: k_inst_mv, below)
+        if ((r = c->inst_scratch.grow(c, inst_scratch_words(a.n_order))) || (r = c->inst_list.grow(c, a.n_order)) ||
+            (mv_here && (r = c->inst_mv.grow(c, 16 * a.n_order)))) return r;
+        launch_inst_compact_ordered(c->stream, dorder, (uint32_t)a.n_order, dvis, (uint32_t)a.n_inst, c->inst_scratch.p, c->inst_list.p,
+                                    mv_here ? a.u->model_view : nullptr, a.instances, a.inst_stride, mv_here ? c->inst_mv.p : nullptr);
+        HIPCHK(c, hipGetLastError());
+        unsigned long long count = 0;
+        HIPCHK(c, hipMemcpyAsync(&count, c->inst_scratch.p, sizeof(count), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait of an ordered call, as below
+        n_vis = count; list = c->inst_list.p; mv_done = mv_here;
+    } else if (a.visible && a.inst_mem == TRGL_MEM_HOST) {
         try {
             for (uint64_t i = 0; i < a.n_inst; ++i) if (a.visible[i] & 1u) host_list.push_back((uint32_t)i);
         } catch (const std::bad_alloc&) { return fail(c, TRGL_E_NOMEM, w + "out of memory"); }
-        n_vis = host_list.size();
+        n_vis = host_list.size(); have_host_list = true;
     } else if (a.visible) {
         if ((r = c->inst_scratch.grow(c, inst_scratch_words(a.n_inst))) || (r = c->inst_list.grow(c, a.n_inst)) ||
             (builtin && (r = c->inst_mv.grow(c, 16 * a.n_inst)))) return r;
@@ -251,8 +285,8 @@ static int run_instanced(trgl_ctx* c, const char* who, const InstanceCall& a, in
         if (a.face_colors) { if ((r = dev_copy(a.face_colors, a.n_faces * sizeof(uint32_t), &p))) return r; dfc = (const uint32_t*)p; }
     }
     const double* dinst = a.instances; const uint32_t* dic = a.inst_colors;
+    if (have_host_list) { if ((r = dev_copy(host_list.data(), n_vis * sizeof(uint32_t), &p))) return r; list = (const uint32_t*)p; }
     if (a.inst_mem == TRGL_MEM_HOST) {
-        if (a.visible) { if ((r = dev_copy(host_list.data(), n_vis * sizeof(uint32_t), &p))) return r; list = (const uint32_t*)p; }
         if (a.instances) { if ((r = dev_copy(a.instances, a.n_inst * (size_t)a.inst_stride * sizeof(double), &p))) return r; dinst = (const double*)p; }
         if (a.inst_colors) { if ((r = dev_copy(a.inst_colors, a.n_inst * sizeof(uint32_t), &p))) return r; dic = (const uint32_t*)p; }
     }
@@ -300,25 +334,59 @@ static int run_instanced(trgl_ctx* c, const char* who, const InstanceCall& a, in
     return TRGL_OK;
 }
 
+// trgl_draw_instanced (a.order null) and trgl_draw_instanced_ordered
+static int draw_instanced_call(trgl_ctx* c, const char* who, int kind, const InstanceCall& a) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = std::string(who) + ": ";
+    int K = 0; bool go;
+    if ((r = check_instance_call(c, who, a, &K, &go)) || (r = check_instance_order(c, who, a, go))) return r;
+    // (what trgl_draw would refuse is refused before anything is queued)
+    const int kind_K = kind_vary_count(c, kind);
+    if (kind_K < 0) return fail(c, TRGL_E_INVALID, w + "unknown shader kind");
+    if (kind_K != K) return fail(c, TRGL_E_INVALID, w + "the shader kind and the vertex stage differ in their number of varyings");
+    if ((r = check_kind_uniforms(c, who, kind, a.u)) || !go) return r;
+    StageHold hold(c);
+    return run_instanced(c, who, a, K, true, kind, nullptr, nullptr, nullptr, nullptr);
+}
+
+// trgl_instance_stage (a.order null) and trgl_instance_stage_ordered
+static int instance_stage_call(trgl_ctx* c, const char* who, const InstanceCall& a, double* clip_out, double* vary_out, uint32_t* colors_out,
+                               uint64_t* n_out) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = std::string(who) + ": ";
+    int K = 0; bool go;
+    if ((r = check_instance_call(c, who, a, &K, &go)) || (r = check_instance_order(c, who, a, go))) return r;
+    if (!n_out) return fail(c, TRGL_E_INVALID, w + "n_out is null");
+    *n_out = 0;
+    if (!go) return TRGL_OK;
+    const bool has_colors = a.inst_colors || a.face_colors;
+    if (!clip_out || (K && !vary_out) || (has_colors && !colors_out)) return fail(c, TRGL_E_INVALID, w + "null output");
+    if (a.inst_mem == TRGL_MEM_DEVICE && (((uintptr_t)clip_out | (K ? (uintptr_t)vary_out : 0) | (has_colors ? (uintptr_t)colors_out : 0)) & 15))
+        return fail(c, TRGL_E_INVALID, w + "device outputs must be 16-byte aligned");
+    return run_instanced(c, who, a, K, false, 0, clip_out, vary_out, colors_out, n_out);
+}
+
 extern "C" {
 
 int trgl_draw_instanced(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16],
                         const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
                         const uint32_t* face_colors, int mesh_mem_kind, const double* instances, int instance_stride, uint64_t n_instances,
                         const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind) {
-    CHKCTX(c);
-    int r = end_pending_raster(c); if (r) return r;
     const InstanceCall a{ vs, u, projection, vertices, stride, n_vertices, indices, n_faces, face_colors, mesh_mem_kind,
                           instances, instance_stride, n_instances, instance_colors, visible, instance_mem_kind };
-    int K = 0; bool go;
-    if ((r = check_instance_call(c, "trgl_draw_instanced", a, &K, &go))) return r;
-    // (what trgl_draw would refuse is refused before anything is queued)
-    const int kind_K = kind_vary_count(c, kind);
-    if (kind_K < 0) return fail(c, TRGL_E_INVALID, "trgl_draw_instanced: unknown shader kind");
-    if (kind_K != K) return fail(c, TRGL_E_INVALID, "trgl_draw_instanced: the shader kind and the vertex stage differ in their number of varyings");
-    if ((r = check_kind_uniforms(c, "trgl_draw_instanced", kind, u)) || !go) return r;
-    StageHold hold(c);
-    return run_instanced(c, "trgl_draw_instanced", a, K, true, kind, nullptr, nullptr, nullptr, nullptr);
+    return draw_instanced_call(c, "trgl_draw_instanced", kind, a);
+}
+
+int trgl_draw_instanced_ordered(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16],
+                                const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                                const uint32_t* face_colors, int mesh_mem_kind, const double* instances, int instance_stride, uint64_t n_instances,
+                                const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind,
+                                const uint32_t* order, uint64_t n_order, int order_mem_kind) {
+    const InstanceCall a{ vs, u, projection, vertices, stride, n_vertices, indices, n_faces, face_colors, mesh_mem_kind,
+                          instances, instance_stride, n_instances, instance_colors, visible, instance_mem_kind, order, n_order, order_mem_kind };
+    return draw_instanced_call(c, "trgl_draw_instanced_ordered", kind, a);
 }
 
 int trgl_instance_stage(trgl_ctx* c, int vs, const trgl_uniforms* u, const double projection[16],
@@ -326,20 +394,59 @@ int trgl_instance_stage(trgl_ctx* c, int vs, const trgl_uniforms* u, const doubl
                         const uint32_t* face_colors, int mesh_mem_kind, const double* instances, int instance_stride, uint64_t n_instances,
                         const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind,
                         double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out) {
-    CHKCTX(c);
-    int r = end_pending_raster(c); if (r) return r;
     const InstanceCall a{ vs, u, projection, vertices, stride, n_vertices, indices, n_faces, face_colors, mesh_mem_kind,
                           instances, instance_stride, n_instances, instance_colors, visible, instance_mem_kind };
-    int K = 0; bool go;
-    if ((r = check_instance_call(c, "trgl_instance_stage", a, &K, &go))) return r;
-    if (!n_out) return fail(c, TRGL_E_INVALID, "trgl_instance_stage: n_out is null");
-    *n_out = 0;
-    if (!go) return TRGL_OK;
-    const bool has_colors = instance_colors || face_colors;
-    if (!clip_out || (K && !vary_out) || (has_colors && !colors_out)) return fail(c, TRGL_E_INVALID, "trgl_instance_stage: null output");
-    if (instance_mem_kind == TRGL_MEM_DEVICE && (((uintptr_t)clip_out | (K ? (uintptr_t)vary_out : 0) | (has_colors ? (uintptr_t)colors_out : 0)) & 15))
-        return fail(c, TRGL_E_INVALID, "trgl_instance_stage: device outputs must be 16-byte aligned");
-    return run_instanced(c, "trgl_instance_stage", a, K, false, 0, clip_out, vary_out, colors_out, n_out);
+    return instance_stage_call(c, "trgl_instance_stage", a, clip_out, vary_out, colors_out, n_out);
+}
+
+int trgl_instance_stage_ordered(trgl_ctx* c, int vs, const trgl_uniforms* u, const double projection[16],
+                                const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                                const uint32_t* face_colors, int mesh_mem_kind, const double* instances, int instance_stride, uint64_t n_instances,
+                                const uint32_t* instance_colors, const uint8_t* visible, int instance_mem_kind,
+                                const uint32_t* order, uint64_t n_order, int order_mem_kind,
+                                double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out) {
+    const InstanceCall a{ vs, u, projection, vertices, stride, n_vertices, indices, n_faces, face_colors, mesh_mem_kind,
+                          instances, instance_stride, n_instances, instance_colors, visible, instance_mem_kind, order, n_order, order_mem_kind };
+    return instance_stage_call(c, "trgl_instance_stage_ordered", a, clip_out, vary_out, colors_out, n_out);
+}
+
+int trgl_instance_depths(trgl_ctx* c, const double model_view[16], const double point[3], const double* instances, int instance_stride,
+                         uint64_t n_instances, int mem_kind, double* depths_out) {
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_instance_depths: bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_instance_depths: TRGL_MEM_DEVICE needs a context");
+    if (!model_view || !point) return fail(c, TRGL_E_INVALID, "trgl_instance_depths: null model_view or point");
+    if (instance_stride < 16) return fail(c, TRGL_E_INVALID, "trgl_instance_depths: instance stride must be >= 16 doubles (a row-major 4x4 matrix)");
+    if (n_instances > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_instance_depths: 2^31 or more instances in one call");
+    if (n_instances == 0) return TRGL_OK;
+    if (!instances || !depths_out) return fail(c, TRGL_E_INVALID, "trgl_instance_depths: null array");
+    if (mem_kind == TRGL_MEM_HOST) { host_instance_depths(model_view, point, instances, instance_stride, n_instances, depths_out); return TRGL_OK; }
+    CHKCTX(c);
+    if (((uintptr_t)instances | (uintptr_t)depths_out) & 7) return fail(c, TRGL_E_INVALID, "trgl_instance_depths: device arrays must be 8-byte aligned");
+    launch_instance_depths(c->stream, model_view, point, instances, instance_stride, (uint32_t)n_instances, depths_out);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_depth_order(trgl_ctx* c, const double* depths, uint64_t n, int direction, int mem_kind, uint32_t* order_out) {
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_depth_order: bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_depth_order: TRGL_MEM_DEVICE needs a context");
+    if (direction != TRGL_ORDER_BACK_TO_FRONT && direction != TRGL_ORDER_FRONT_TO_BACK) return fail(c, TRGL_E_INVALID, "trgl_depth_order: bad direction");
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_depth_order: 2^31 or more depths in one call");
+    if (n == 0) return TRGL_OK;
+    if (!depths || !order_out) return fail(c, TRGL_E_INVALID, "trgl_depth_order: null array");
+    const bool front_to_back = direction == TRGL_ORDER_FRONT_TO_BACK;
+    if (mem_kind == TRGL_MEM_HOST) {
+        if (!host_depth_order(depths, n, front_to_back, order_out)) return fail(c, TRGL_E_NOMEM, "trgl_depth_order: out of memory");
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    if (((uintptr_t)depths & 7) || ((uintptr_t)order_out & 3))
+        return fail(c, TRGL_E_INVALID, "trgl_depth_order: device arrays need natural alignment (8 bytes for depths, 4 for the order)");
+    size_t bytes = 0;
+    HIPCHK(c, depth_order_scratch_bytes((uint32_t)n, &bytes));
+    if (int r = c->order_scratch.grow(c, bytes)) return r;
+    HIPCHK(c, launch_depth_order(c->stream, depths, (uint32_t)n, front_to_back, c->order_scratch.p, c->order_scratch.cap, order_out));
+    return TRGL_OK;
 }
 
 int trgl_register_shader_ex(trgl_ctx* c, const char* source, int n_varyings, uint32_t flags, int* kind) {

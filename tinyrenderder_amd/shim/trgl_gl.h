@@ -498,7 +498,7 @@ template <class ModelT> inline bool gl_draw_model(const ModelT& model, const ISh
 namespace trgl_shim {
 inline bool draw_instanced(const IShader& shader, const double* vertices, int stride, std::size_t nv, const unsigned int* indices, std::size_t nfaces,
                            const double* matrices, int matrix_stride, std::size_t n, const std::uint8_t* codes, int instance_mem_kind,
-                           TGAImage& framebuffer) {
+                           TGAImage& framebuffer, const std::uint32_t* order = nullptr, std::size_t n_order = 0, int order_mem_kind = TRGL_MEM_HOST) {
     State& s = state();
     if (!bind(framebuffer)) return false;
     bool ok = submit_batch();                                   // earlier rasterize() calls come first
@@ -512,10 +512,16 @@ inline bool draw_instanced(const IShader& shader, const double* vertices, int st
     for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { vp[4 * r + c] = Viewport[r][c]; pj[4 * r + c] = Perspective[r][c]; }
     static_assert(sizeof(unsigned int) == sizeof(std::uint32_t), "indices are 32-bit");
     const std::vector<std::uint32_t> colors(d.vertex_kind >= 0 ? nfaces : 0, d.color);
-    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
-         TRGL_SHIM_OK(trgl_draw_instanced(s.ctx, d.vertex_kind >= 0 ? d.vertex_kind : -1, d.kind, &d.uniforms, pj, vertices, stride, nv,
-                                          reinterpret_cast<const std::uint32_t*>(indices), nfaces, d.vertex_kind >= 0 ? colors.data() : nullptr, TRGL_MEM_HOST,
-                                          matrices, matrix_stride, n, nullptr, codes, instance_mem_kind)) && ok;
+    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) && ok;
+    if (!order)                                                 // (an empty list is no list: the call the shim made before there were lists)
+        ok = TRGL_SHIM_OK(trgl_draw_instanced(s.ctx, d.vertex_kind >= 0 ? d.vertex_kind : -1, d.kind, &d.uniforms, pj, vertices, stride, nv,
+                                              reinterpret_cast<const std::uint32_t*>(indices), nfaces, d.vertex_kind >= 0 ? colors.data() : nullptr, TRGL_MEM_HOST,
+                                              matrices, matrix_stride, n, nullptr, codes, instance_mem_kind)) && ok;
+    else
+        ok = TRGL_SHIM_OK(trgl_draw_instanced_ordered(s.ctx, d.vertex_kind >= 0 ? d.vertex_kind : -1, d.kind, &d.uniforms, pj, vertices, stride, nv,
+                                                      reinterpret_cast<const std::uint32_t*>(indices), nfaces, d.vertex_kind >= 0 ? colors.data() : nullptr,
+                                                      TRGL_MEM_HOST, matrices, matrix_stride, n, nullptr, codes, instance_mem_kind,
+                                                      order, n_order, order_mem_kind)) && ok;
     s.zbuffer_stale_on_host = true;
     return ok;
 }
@@ -535,6 +541,54 @@ inline bool gl_draw_instanced(const IShader& shader, const double* vertices, int
                               const gl_device_instances& instances, TGAImage& framebuffer) {
     return trgl_shim::draw_instanced(shader, vertices, stride, nv, indices, nfaces, instances.matrices, instances.matrix_stride, instances.count,
                                      instances.codes, TRGL_MEM_DEVICE, framebuffer);
+}
+
+// Depth-ordered instanced draws (include/trgl.h, trgl_instance_depths / trgl_depth_order / trgl_draw_instanced_ordered): what a caller
+// of the reference does by sorting its models on the host before the loop of main.cpp:647-736.
+// gl_instance_depths: the view-space z of `point` (a point of the mesh in model space) under ModelView * model_matrices[i], one double per
+// matrix.  gl_depth_order: the order to draw such depths in - farthest first (translucent shaders), or with front_to_back nearest first
+// (fewer fragment() calls of an opaque one); equal depths keep their order either way.  Both run on the host and need no context; a call
+// that fails (gl_last_error()) answers zeros / the order 0 .. n-1.
+inline std::vector<double> gl_instance_depths(const std::vector<mat<4, 4>>& model_matrices, const vec3& point) {
+    std::vector<double> m(model_matrices.size() * 16), depths(model_matrices.size(), 0.0);
+    for (std::size_t i = 0; i < model_matrices.size(); ++i)
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m[16 * i + 4 * r + c] = model_matrices[i][r][c];
+    double mv[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) mv[4 * r + c] = ModelView[r][c];
+    const double p[3] = { point.x, point.y, point.z };
+    const int rc = trgl_instance_depths(nullptr, mv, p, m.data(), 16, m.size() / 16, TRGL_MEM_HOST, depths.data());
+    if (rc != TRGL_OK) trgl_shim::fail("gl_instance_depths", rc, nullptr);
+    return depths;
+}
+inline std::vector<std::uint32_t> gl_depth_order(const std::vector<double>& depths, bool front_to_back = false) {
+    std::vector<std::uint32_t> order(depths.size());
+    for (std::size_t i = 0; i < order.size(); ++i) order[i] = std::uint32_t(i);
+    const int rc = trgl_depth_order(nullptr, depths.data(), depths.size(), front_to_back ? TRGL_ORDER_FRONT_TO_BACK : TRGL_ORDER_BACK_TO_FRONT,
+                                    TRGL_MEM_HOST, order.data());
+    if (rc != TRGL_OK) trgl_shim::fail("gl_depth_order", rc, nullptr);
+    return order;
+}
+// gl_draw_instanced with the matrices visited in the order the list names them: model_matrices[order[0]] first.  A matrix named twice is
+// drawn twice, one that is not named is not drawn; an entry that is no matrix fails the call (TRGL_E_INVALID).  A shader with a user
+// vertex shader still sees the matrix's own number as in.instance.  A set clip plane is TRGL_E_UNSUPPORTED, as for gl_draw_instanced.
+inline bool gl_draw_instanced_ordered(const IShader& shader, const double* vertices, int stride, std::size_t nv, const unsigned int* indices,
+                                      std::size_t nfaces, const std::vector<mat<4, 4>>& model_matrices, const std::vector<std::uint32_t>& order,
+                                      TGAImage& framebuffer, const std::uint8_t* codes = nullptr) {
+    std::vector<double> m(model_matrices.size() * 16);
+    for (std::size_t i = 0; i < model_matrices.size(); ++i)
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m[16 * i + 4 * r + c] = model_matrices[i][r][c];
+    if (order.empty()) return true;                             // (no position to visit: nothing is drawn)
+    return trgl_shim::draw_instanced(shader, vertices, stride, nv, indices, nfaces, m.data(), 16, model_matrices.size(), codes, TRGL_MEM_HOST, framebuffer,
+                                     order.data(), order.size(), TRGL_MEM_HOST);
+}
+// ... with the instances and the list in DEVICE memory (order: n_order uint32, 4-byte aligned - as trgl_depth_order leaves them with
+// TRGL_MEM_DEVICE; entries that are no instance are skipped).  The call waits once, for the count of drawn instances.
+inline bool gl_draw_instanced_ordered(const IShader& shader, const double* vertices, int stride, std::size_t nv, const unsigned int* indices,
+                                      std::size_t nfaces, const gl_device_instances& instances, const std::uint32_t* order, std::size_t n_order,
+                                      TGAImage& framebuffer) {
+    if (n_order == 0) return true;
+    return trgl_shim::draw_instanced(shader, vertices, stride, nv, indices, nfaces, instances.matrices, instances.matrix_stride, instances.count,
+                                     instances.codes, TRGL_MEM_DEVICE, framebuffer, order, n_order, TRGL_MEM_DEVICE);
 }
 
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
