@@ -882,6 +882,53 @@ int trgl_occlusion_boxes_image(trgl_ctx* ctx, const double* depth, int w, int h,
 int trgl_occlusion_boxes(trgl_ctx* ctx, const double view_proj[16], const double* boxes, uint64_t n, int boxes_mem_kind,
                          int snapshot_slot, uint8_t* codes, int codes_mem_kind);
 
+/* ---- world boxes and frustum codes of a crowd of instances, in host memory or in HBM -------------------------- */
+
+/* Replaces: Model::getWorldAABB(modelMatrix) - AABB::transform, geometry.h:297-327 - and the gate frustum.intersects(worldAABB)
+ * (our_gl.cpp:264-280; main.cpp:555-557, 647, 680, 706), each for n models in one call: the single-box calls trgl_aabb_transform and
+ * trgl_frustum_intersects over arrays.  With them the chain in front of trgl_draw_instanced(_ordered) starts at the matrices: boxes,
+ * frustum and occlusion codes, depths and the order are all made where the matrices are.
+ *
+ * trgl_instance_boxes: boxes_out[6*i .. 6*i+5] = min.xyz then max.xyz (the layout trgl_occlusion_boxes takes) of
+ * trgl_aabb_transform(local_i.min, local_i.max, M_i), bit for bit.  M_i: the first 16 doubles of instance i, row-major;
+ * instance_stride >= 16 (as for trgl_instance_depths).
+ *   local_stride == 0 : ONE local box for every instance: local_boxes is 6 doubles, min.xyz then max.xyz, ALWAYS in host memory and read
+ *                       before the call returns - what trgl_mesh_bounds just returned; on the device it travels as a kernel argument.
+ *   local_stride >= 6 : instance i uses the 6 doubles at local_boxes + i * local_stride, in mem_kind memory (a scene of different models).
+ * The arithmetic (geometry.h:297-327), fp64, no contraction:
+ *   corner k = 0 .. 7, x fastest, then y, then z: p = (k&1 ? max.x : min.x, k&2 ? max.y : min.y, k&4 ? max.z : min.z)   (:300-307)
+ *   t[r] = (((0.0 + M[r][0]*p.x) + M[r][1]*p.y) + M[r][2]*p.z) + M[r][3]*1.0 for r = 0 .. 3                              (:314)
+ *   pos = (t[0] / t[3], t[1] / t[3], t[2] / t[3]): three true IEEE divisions, no guard - w = 0 gives +-inf or NaN            (:315)
+ *   lo = pos < lo ? pos : lo from 1e9 and hi = hi < pos ? pos : hi from -1e9, per axis, in corner order                    (:309-310, :317-323)
+ * so a NaN never replaces a bound, of +0.0 and -0.0 the earlier one stays, and an output is never NaN - but it may be +-inf, or the
+ * untouched 1e9 / -1e9 where every corner gave NaN.
+ * mem_kind covers instances, boxes_out and a strided local_boxes.  boxes_out must not overlap an input.
+ *
+ * trgl_frustum_boxes: one code byte per box from Frustum::intersects.  planes: the 24 doubles of trgl_frustum_from_matrix, ALWAYS in
+ * host memory and read before the call returns (a kernel argument on the device).  boxes: n x 6 doubles as above.  With
+ * hit_i = trgl_frustum_intersects(planes, box_i.min, box_i.max):
+ *   TRGL_FRUSTUM_SET   : codes[i] = hit_i ? TRGL_OCCL_VISIBLE : TRGL_OCCL_OUTSIDE
+ *   TRGL_FRUSTUM_MERGE : codes[i] = hit_i ? codes[i] : TRGL_OCCL_OUTSIDE - all eight bits of a kept byte survive; a byte that is
+ *                        overwritten may or may not be read first.  This is how the codes of trgl_occlusion_boxes pick up the
+ *                        reference's own test: a frustum-culled box loses bit 0 whatever the depths said.
+ * mem_kind covers boxes and codes.
+ *
+ * Both.  TRGL_MEM_HOST: plain C++, ctx may be NULL, no GPU is touched, complete on return.  TRGL_MEM_DEVICE: needs a context; one
+ * thread per instance or box, queued on the context's stream in order with everything else (codes that trgl_occlusion_boxes queued
+ * before are complete when MERGE runs, and a trgl_draw_instanced queued after sees the result); the call does not wait and nothing is
+ * flushed.  Device doubles are 8-byte aligned and nothing wider is assumed; codes needs no alignment.
+ * ERRORS.  TRGL_E_INVALID: a bad mem_kind or mode, TRGL_MEM_DEVICE without a context, local_stride other than 0 or >= 6,
+ * instance_stride < 16, null planes, and with n > 0 a null array or a misaligned device array.  TRGL_E_UNSUPPORTED: n above 2^31 - 1.
+ * n == 0: TRGL_OK once the scalar arguments are checked, and no array is read or written. */
+int trgl_instance_boxes(trgl_ctx* ctx, const double* local_boxes, int local_stride,
+                        const double* instances, int instance_stride, uint64_t n_instances,
+                        int mem_kind, double* boxes_out);
+
+#define TRGL_FRUSTUM_SET   0
+#define TRGL_FRUSTUM_MERGE 1
+int trgl_frustum_boxes(trgl_ctx* ctx, const double planes[24], const double* boxes, uint64_t n,
+                       int mode, int mem_kind, uint8_t* codes);
+
 /* ---- TGA writer and reader (host only) ------------------------------------- */
 
 /* Replaces: TGAImage::write_tga_file(name, vflip, rle) (tgaimage.cpp:161-242): produces exactly the bytes the

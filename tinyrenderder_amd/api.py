@@ -40,6 +40,7 @@ OCCL_HIDDEN, OCCL_VISIBLE, OCCL_OUTSIDE, OCCL_UNDECIDED = range(4)     # TRGL_OC
 # level, output faces per block of the instanced vertex kernels
 INST_BLOCK, INST_SCAN_CHUNK, INST_VS_FACES = 256, 256, 64
 ORDER_BACK_TO_FRONT, ORDER_FRONT_TO_BACK = 0, 1     # TRGL_ORDER_*
+FRUSTUM_SET, FRUSTUM_MERGE = 0, 1     # TRGL_FRUSTUM_*: the mode of trgl_frustum_boxes
 NEAR_PLANE = (0.0, 0.0, 1.0, 1.0)     # the near plane of the reference's projection in clip space: z + w >= 0
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
 
@@ -64,6 +65,7 @@ SYMBOLS = [
     "trgl_occlusion_boxes_image", "trgl_occlusion_boxes",
     "trgl_draw_instanced", "trgl_instance_stage",
     "trgl_instance_depths", "trgl_depth_order", "trgl_draw_instanced_ordered", "trgl_instance_stage_ordered",
+    "trgl_instance_boxes", "trgl_frustum_boxes",
 ]
 
 
@@ -261,6 +263,8 @@ def load_library(path: str = None):
     L.trgl_instance_stage_ordered.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp] + inst + order + [C.c_void_p, C.c_void_p, C.c_void_p, u64p]
     L.trgl_instance_depths.argtypes = [vp, dp, dp, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
     L.trgl_depth_order.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
+    L.trgl_instance_boxes.argtypes = [vp, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
+    L.trgl_frustum_boxes.argtypes = [vp, dp, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -602,6 +606,117 @@ def depth_order(depths, front_to_back=False) -> np.ndarray:
     matrix that looks down -z: ascending), or nearest first; ties in ascending number either way.  The order is that of the doubles' bit
     patterns as include/trgl.h defines it (-0.0 before +0.0, NaNs at the ends by their sign).  Needs no GPU."""
     return _depth_order(load_library(), None, depths, front_to_back, False)[1]
+
+
+def _is_device_tensor(a):
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) is True
+
+
+def _device_f64(t, ndim, what):
+    if not _is_device_tensor(t) or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.dim() != ndim:
+        raise ValueError(f"{what} must be a contiguous float64 device tensor with {ndim} dimensions (the other arrays are in device memory)")
+    return t
+
+
+def _instance_boxes(L, handle, local, instances, out):
+    """Returns (arrays to keep alive, boxes [n, 6]).  Device memory when `instances` is a device tensor."""
+    device = _is_device_tensor(instances)
+    one = not _is_device_tensor(local) and np.ndim(local) == 1          # one local box for every instance: always host memory
+    if device:
+        _device_f64(instances, 2, "instance_boxes: instances")
+        if not one:
+            _device_f64(local, 2, "instance_boxes: local")
+    else:
+        instances = np.ascontiguousarray(instances, np.float64)
+        if instances.ndim != 2:
+            raise ValueError("instance_boxes: instances must be [n, stride]")
+        if not one:
+            local = np.ascontiguousarray(local, np.float64)
+    n = int(instances.shape[0])
+    if one:
+        local, local_stride = _f64(local, 6, "instance_boxes: local"), 0
+        lptr = local.ctypes.data
+    else:
+        if len(local.shape) != 2 or int(local.shape[0]) != n:
+            raise ValueError("instance_boxes: local must be [6] (one box for every instance) or [n, stride >= 6]")
+        local_stride = int(local.shape[1])
+        if local_stride == 0:
+            raise ValueError("instance_boxes: a strided local array needs stride >= 6")
+        lptr = _device_ptr(local, "local") if device else local.ctypes.data
+    if out is None:
+        if device:
+            import torch
+            out = torch.empty((n, 6), dtype=torch.float64, device=instances.device)
+        else:
+            out = np.empty((n, 6), np.float64)
+    else:
+        if device:
+            _device_f64(out, 2, "instance_boxes: out")
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous):
+            raise ValueError("instance_boxes: out must be a contiguous float64 numpy array (the other arrays are in host memory)")
+        if tuple(out.shape) != (n, 6):
+            raise ValueError("instance_boxes: out must be [n, 6]")
+    iptr, optr = (_device_ptr(instances, "instances"), _device_ptr(out, "out")) if device else (instances.ctypes.data, out.ctypes.data)
+    if n == 0:
+        iptr = optr = None
+        lptr = lptr if one else None
+    rc = L.trgl_instance_boxes(handle, lptr, local_stride, iptr, int(instances.shape[1]), n, MEM_DEVICE if device else MEM_HOST, optr)
+    if rc != 0:
+        raise TrglError(f"trgl_instance_boxes failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (local, instances, out), out
+
+
+def _frustum_boxes(L, handle, planes, boxes, codes, merge):
+    """Returns (arrays to keep alive, codes [n] uint8).  Device memory when `boxes` is a device tensor."""
+    planes = _f64(planes, 24, "frustum_boxes: planes")
+    device = _is_device_tensor(boxes)
+    if device:
+        _device_f64(boxes, 2, "frustum_boxes: boxes")
+    else:
+        boxes = np.ascontiguousarray(boxes, np.float64)
+    n = _boxes_count(boxes)
+    if codes is None:
+        if merge:
+            raise ValueError("frustum_boxes: merge=True needs the codes to merge into")
+        if device:
+            import torch
+            codes = torch.empty(n, dtype=torch.uint8, device=boxes.device)
+        else:
+            codes = np.empty(n, np.uint8)
+    else:
+        if device:
+            if not _is_device_tensor(codes) or str(codes.dtype) != "torch.uint8" or not codes.is_contiguous():
+                raise ValueError("frustum_boxes: codes must be a contiguous uint8 device tensor (the boxes are in device memory)")
+        elif not (isinstance(codes, np.ndarray) and codes.dtype == np.uint8 and codes.flags.c_contiguous and codes.flags.writeable):
+            raise ValueError("frustum_boxes: codes must be a contiguous writable uint8 numpy array (the boxes are in host memory)")
+        if tuple(codes.shape) != (n,):
+            raise ValueError("frustum_boxes: codes must be [n]")
+    bptr, cptr = (_device_ptr(boxes, "boxes"), _device_ptr(codes, "codes")) if device else (boxes.ctypes.data, codes.ctypes.data)
+    if n == 0:
+        bptr = cptr = None
+    rc = L.trgl_frustum_boxes(handle, _dp(planes), bptr, n, FRUSTUM_MERGE if merge else FRUSTUM_SET, MEM_DEVICE if device else MEM_HOST, cptr)
+    if rc != 0:
+        raise TrglError(f"trgl_frustum_boxes failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (boxes, codes), codes
+
+
+def instance_boxes(local, instances, out=None) -> np.ndarray:
+    """trgl_instance_boxes for host arrays without a context: the world box [n, 6] = (min.xyz, max.xyz) of every instance [n, stride >= 16]
+    - AABB::transform (geometry.h:297-327) of `local` under the instance's row-major matrix, bit for bit trgl_aabb_transform.  local: [6],
+    one box for every instance (mesh_bounds' two halves concatenated), or [n, stride >= 6], one per instance.  Needs no GPU."""
+    if _is_device_tensor(instances):
+        raise TypeError("instance_boxes: device tensors need a context (Context.instance_boxes)")
+    return _instance_boxes(load_library(), None, local, instances, out)[1]
+
+
+def frustum_boxes(planes, boxes, codes=None, merge=False) -> np.ndarray:
+    """trgl_frustum_boxes for host arrays without a context: one code byte per box [n, 6] from Frustum::intersects (our_gl.cpp:264-280)
+    against planes [6, 4] (frustum_from_matrix).  merge=False: OCCL_VISIBLE or OCCL_OUTSIDE, into `codes` or a new array.  merge=True:
+    `codes` (uint8 [n], occlusion codes for instance) is changed in place - OCCL_OUTSIDE where the frustum culls, untouched elsewhere.
+    Needs no GPU."""
+    if _is_device_tensor(boxes):
+        raise TypeError("frustum_boxes: device tensors need a context (Context.frustum_boxes)")
+    return _frustum_boxes(load_library(), None, planes, boxes, codes, merge)[1]
 
 
 def clip_layout(kind: int):
@@ -1010,6 +1125,28 @@ class Context:
         if device:
             self._keep.append((depths, out))
         return out
+
+    def instance_boxes(self, local, instances, out=None):
+        """trgl_instance_boxes: the world box [n, 6] = (min.xyz, max.xyz) of every instance [n, stride >= 16], AABB::transform of `local`
+        under the instance's matrix.  local: [6] in host memory (one box for every instance: mesh_bounds' halves concatenated) or
+        [n, stride >= 6] where the instances are.  numpy instances: a numpy array, no GPU work.  A contiguous float64 device tensor: the
+        boxes come back as a device tensor (`out` when given), queued on the context's stream without waiting - the input of
+        occlusion_boxes(device=True) and frustum_boxes."""
+        keep, out = _instance_boxes(self.L, self.h, local, instances, out)
+        if _is_device_tensor(out):
+            self._keep.append(keep)
+        return out
+
+    def frustum_boxes(self, planes, boxes, codes=None, merge=False):
+        """trgl_frustum_boxes: one code byte per box [n, 6] from Frustum::intersects against planes [6, 4] (host memory).  merge=False
+        writes OCCL_VISIBLE / OCCL_OUTSIDE into `codes` (allocated when None); merge=True writes OCCL_OUTSIDE into the given codes where
+        the frustum culls and leaves every other byte as it is - over the codes of occlusion_boxes that makes the `visible` array of
+        draw_instanced.  numpy boxes: no GPU work.  Device tensors (boxes float64, codes uint8 at any address): queued on the context's
+        stream without waiting."""
+        keep, codes = _frustum_boxes(self.L, self.h, planes, boxes, codes, merge)
+        if _is_device_tensor(codes):
+            self._keep.append(keep)
+        return codes
 
     def draw_instanced(self, kind, uniforms, projection, vertices, indices, instances=None, vertex_shader=None, face_colors=None,
                        instance_colors=None, visible=None, device=False, instances_device=False, order=None, order_device=False):

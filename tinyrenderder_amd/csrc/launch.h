@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -198,6 +198,15 @@ void launch_instance_depths(hipStream_t s, const double model_view[16], const do
 hipError_t depth_order_scratch_bytes(uint32_t n, size_t* bytes);
 hipError_t launch_depth_order(hipStream_t s, const double* depths, uint32_t n, bool front_to_back, void* scratch, size_t scratch_bytes,
                               uint32_t* order);
+
+// World boxes of instances and frustum codes of boxes (kernels_scene.hip; both are written down at trgl_instance_boxes /
+// trgl_frustum_boxes in include/trgl.h, the arithmetic is scene_core.h's).  One thread per instance or box, 0 < n < 2^31; doubles 8-byte
+// aligned, codes at any address.  local_stride == 0: local_boxes is HOST memory, 6 doubles that travel as the kernel's argument; else
+// device memory, instance i's box at local_boxes + i * local_stride.  planes: host memory, the kernel's argument.  merge: only the
+// bytes of culled boxes are written (TRGL_FRUSTUM_MERGE); else every byte (TRGL_FRUSTUM_SET).
+void launch_instance_boxes(hipStream_t s, const double* local_boxes, int local_stride, const double* instances, int inst_stride,
+                           uint32_t n, double* boxes_out);
+void launch_frustum_boxes(hipStream_t s, const double planes[24], const double* boxes, uint32_t n, bool merge, uint8_t* codes);
 
 void launch_selftest_sampler(hipStream_t s, const DevTexture* tex, int slot, const double* uv, unsigned long long n, uint8_t* out);
 void launch_selftest_division(hipStream_t s, unsigned long long n_per_thread, unsigned long long seed,

@@ -14,6 +14,7 @@
 #include "../../include/trgl.h"
 #include "clip_core.h"
 #include "occlusion_core.h"
+#include "scene_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -24,11 +25,7 @@ const char* global_error() { return g_error.c_str(); }
 int fail(trgl_ctx* c, int code, const std::string& msg);       // trgl_api.cpp; called with c == nullptr here
 
 // ---- scene logic around the draws (model.cpp:15-40, geometry.h:264-266,297-327, our_gl.cpp:212-280) ------------------------------
-// std::min(a, b) = (b < a) ? b : a and std::max(a, b) = (a < b) ? b : a with a the running bound: what decides NaNs and signed zeros
-static inline double keep_min(double bound, double p) { return p < bound ? p : bound; }
-static inline double keep_max(double bound, double p) { return bound < p ? p : bound; }
-// dot<n> (geometry.h:122-127): summed left to right from 0
-static inline double dot3_from_zero(const double* a, double x, double y, double z) { double sum = 0; sum += a[0] * x; sum += a[1] * y; sum += a[2] * z; return sum; }
+// keep_min / keep_max (the running std::min / std::max) and dot3_from_zero, AABB::transform and Frustum::intersects: scene_core.h
 
 void host_mesh_bounds(const double* vertices, int stride, uint64_t n, double out_min[3], double out_max[3]) {
     double lo[3] = { 1e9, 1e9, 1e9 }, hi[3] = { -1e9, -1e9, -1e9 };         // model.cpp:21-22
@@ -190,6 +187,20 @@ bool host_depth_order(const double* depths, uint64_t n, bool front_to_back, uint
     } catch (const std::bad_alloc&) { return false; }                         // (std::stable_sort falls back to merging in place)
     return true;
 }
+
+// ---- world boxes of instances and frustum codes of boxes in host memory (include/trgl.h, trgl_instance_boxes / trgl_frustum_boxes;
+// the arithmetic is scene_core.h's) --------------------------------------------------------------------------------------------------
+void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out) {
+    for (uint64_t i = 0; i < n; ++i)
+        aabb_transform_core(local_boxes + i * (uint64_t)local_stride, instances + i * (uint64_t)stride, boxes_out + 6 * i);
+}
+
+void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes) {
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!frustum_intersects_core(planes, boxes + 6 * i)) codes[i] = TRGL_OCCL_OUTSIDE;
+        else if (!merge) codes[i] = TRGL_OCCL_VISIBLE;
+    }
+}
 }  // namespace trgl
 using namespace trgl;
 
@@ -213,22 +224,10 @@ int trgl_format_stats(const trgl_stats* s, char* buf, size_t buflen) {   // our_
 
 int trgl_aabb_transform(const double bmin[3], const double bmax[3], const double m[16], double out_min[3], double out_max[3]) {
     if (!bmin || !bmax || !m || !out_min || !out_max) return TRGL_E_INVALID;
-    double lo[3] = { 1e9, 1e9, 1e9 }, hi[3] = { -1e9, -1e9, -1e9 };             // geometry.h:309-310
-    for (int i = 0; i < 8; ++i) {                                               // :300-307: corner i takes max.x for bit 0, max.y for bit 1, max.z for bit 2
-        const double x = (i & 1) ? bmax[0] : bmin[0], y = (i & 2) ? bmax[1] : bmin[1], z = (i & 4) ? bmax[2] : bmin[2];
-        double t[4];
-        for (int row = 0; row < 4; ++row) {                                     // :314, mat * vec4(corner, 1.0): one dot<4> per row
-            double sum = 0;
-            sum += m[4 * row] * x; sum += m[4 * row + 1] * y; sum += m[4 * row + 2] * z; sum += m[4 * row + 3] * 1.0;
-            t[row] = sum;
-        }
-        for (int a = 0; a < 3; ++a) {
-            const double pos = t[a] / t[3];                                     // :315, no guard
-            lo[a] = keep_min(lo[a], pos);                                       // :317-319
-            hi[a] = keep_max(hi[a], pos);                                       // :321-323
-        }
-    }
-    for (int a = 0; a < 3; ++a) { out_min[a] = lo[a]; out_max[a] = hi[a]; }
+    const double box[6] = { bmin[0], bmin[1], bmin[2], bmax[0], bmax[1], bmax[2] };
+    double out[6];
+    aabb_transform_core(box, m, out);                                           // geometry.h:297-327
+    for (int a = 0; a < 3; ++a) { out_min[a] = out[a]; out_max[a] = out[3 + a]; }
     return TRGL_OK;
 }
 
@@ -250,13 +249,8 @@ int trgl_frustum_from_matrix(const double m[16], double planes[24]) {
 
 int trgl_frustum_intersects(const double planes[24], const double bmin[3], const double bmax[3]) {
     if (!planes || !bmin || !bmax) return TRGL_E_INVALID;
-    for (int i = 0; i < 6; ++i) {                                               // our_gl.cpp:265-278
-        const double* pl = planes + 4 * i;
-        double positive[3] = { bmin[0], bmin[1], bmin[2] };                     // :269
-        for (int a = 0; a < 3; ++a) if (pl[a] >= 0) positive[a] = bmax[a];      // :270-272
-        if (dot3_from_zero(pl, positive[0], positive[1], positive[2]) + pl[3] < 0) return 0;   // :275, Plane::distance
-    }
-    return 1;
+    const double box[6] = { bmin[0], bmin[1], bmin[2], bmax[0], bmax[1], bmax[2] };
+    return frustum_intersects_core(planes, box) ? 1 : 0;                        // our_gl.cpp:264-280
 }
 
 int trgl_clip_layout(int kind, trgl_clip_attr* attrs, int* n_attrs) {

@@ -1,5 +1,5 @@
 // trgl_passes.cpp — the optional passes of include/trgl.h over finished frames and over caller-owned images and meshes: SSAO post-process,
-// z-buffer snapshots, blur and scale, the shadow mask and modulate, occlusion culling of boxes, mesh bounds and attributes in device memory, the two self-tests.
+// z-buffer snapshots, blur and scale, the shadow mask and modulate, occlusion culling of boxes, world boxes and frustum codes of instances, mesh bounds and attributes in device memory, the two self-tests.
 // None of them knows the flush pipeline of trgl_api.cpp: each finishes what is pending (end_pending_raster, trgl_flush, flush_sync), then
 // launches on the context's stream.  With TRGL_MEM_HOST the work is done by the host loops (trgl_host.cpp, shim/trgl_image.h).
 #include <climits>
@@ -386,6 +386,42 @@ int trgl_occlusion_boxes(trgl_ctx* c, const double view_proj[16], const double* 
         HIPCHK(c, hipMemcpyAsync(codes, d_codes, (size_t)n, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return TRGL_OK;
+}
+
+// ---- world boxes of instances and frustum codes of boxes (include/trgl.h; host loops in trgl_host.cpp, kernels in kernels_scene.hip) ----
+int trgl_instance_boxes(trgl_ctx* c, const double* local_boxes, int local_stride, const double* instances, int instance_stride,
+                        uint64_t n_instances, int mem_kind, double* boxes_out) {
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: TRGL_MEM_DEVICE needs a context");
+    if (local_stride != 0 && local_stride < 6) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: local_stride must be 0 (one box for all) or >= 6 doubles");
+    if (instance_stride < 16) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: instance stride must be >= 16 doubles (a row-major 4x4 matrix)");
+    if (n_instances > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_instance_boxes: 2^31 or more instances in one call");
+    if (n_instances == 0) return TRGL_OK;
+    if (!local_boxes || !instances || !boxes_out) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: null array");
+    if (mem_kind == TRGL_MEM_HOST) { host_instance_boxes(local_boxes, local_stride, instances, instance_stride, n_instances, boxes_out); return TRGL_OK; }
+    CHKCTX(c);
+    if ((((uintptr_t)instances | (uintptr_t)boxes_out) & 7) || (local_stride && ((uintptr_t)local_boxes & 7)))
+        return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: device arrays must be 8-byte aligned");
+    launch_instance_boxes(c->stream, local_boxes, local_stride, instances, instance_stride, (uint32_t)n_instances, boxes_out);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_frustum_boxes(trgl_ctx* c, const double planes[24], const double* boxes, uint64_t n, int mode, int mem_kind, uint8_t* codes) {
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: TRGL_MEM_DEVICE needs a context");
+    if (mode != TRGL_FRUSTUM_SET && mode != TRGL_FRUSTUM_MERGE) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: bad mode");
+    if (!planes) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: planes is null");
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_frustum_boxes: 2^31 or more boxes in one call");
+    if (n == 0) return TRGL_OK;
+    if (!boxes || !codes) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: null array");
+    const bool merge = mode == TRGL_FRUSTUM_MERGE;
+    if (mem_kind == TRGL_MEM_HOST) { host_frustum_boxes(planes, boxes, n, merge, codes); return TRGL_OK; }
+    CHKCTX(c);
+    if ((uintptr_t)boxes & 7) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: device boxes must be 8-byte aligned");
+    launch_frustum_boxes(c->stream, planes, boxes, (uint32_t)n, merge, codes);
+    HIPCHK(c, hipGetLastError());
     return TRGL_OK;
 }
 

@@ -33,6 +33,8 @@
 //     gl_zbuffer_snapshot, into a mask and multiply it into the frame in HBM (see below, and include/trgl.h).
 //   * clipping (new; the reference has none): gl_clip_plane(&plane) cuts everything drawn from then on against a plane in clip space
 //     before it is rasterized (include/trgl.h, trgl_clip_stage); gl_clip_plane(nullptr) returns to the reference's behaviour.
+//   * gl_instance_boxes(local, matrices) / gl_frustum_test(frustum, boxes[, codes]) are getWorldAABB and frustum.intersects for a
+//     whole vector of models (trgl_instance_boxes / trgl_frustum_boxes); the codes plug into gl_occlusion_draw and gl_draw_instanced.
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -769,6 +771,47 @@ inline std::vector<std::uint8_t> gl_occlusion_test(const std::vector<AABB>& boxe
     return codes;
 }
 inline bool gl_occlusion_draw(std::uint8_t code) { return (code & 1) != 0; }
+
+// World boxes and frustum codes of many models at once (include/trgl.h, trgl_instance_boxes / trgl_frustum_boxes): the array forms of
+// `model.getWorldAABB(modelMatrix)` and `frustum.intersects(worldAABB)` (main.cpp:555-557, 647).  Both run on the host and need no context.
+// gl_instance_boxes: AABB::transform of `local` (gl_mesh_bounds) under every matrix, bit for bit local.transform(model_matrices[i]).
+// gl_frustum_test(frustum, boxes): one byte per box, TRGL_OCCL_VISIBLE where the frustum intersects it and TRGL_OCCL_OUTSIDE where not.
+// gl_frustum_test(frustum, boxes, codes): merges into the codes gl_occlusion_test returned - a culled box becomes TRGL_OCCL_OUTSIDE, every
+// other byte stays - so that gl_occlusion_draw(codes[i]) answers both tests, and the vector is the `visible` of gl_draw_instanced.
+// A call that fails (gl_last_error()) answers empty boxes at the origin / leaves the codes as they are (SET: UNDECIDED, draw them all).
+inline std::vector<AABB> gl_instance_boxes(const AABB& local, const std::vector<mat<4, 4>>& model_matrices) {
+    const std::size_t n = model_matrices.size();
+    std::vector<double> m(n * 16), b(n * 6, 0.0);
+    for (std::size_t i = 0; i < n; ++i)
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m[16 * i + 4 * r + c] = model_matrices[i][r][c];
+    const double box[6] = { local.min[0], local.min[1], local.min[2], local.max[0], local.max[1], local.max[2] };
+    const int rc = trgl_instance_boxes(nullptr, box, 0, m.data(), 16, n, TRGL_MEM_HOST, b.data());
+    if (rc != TRGL_OK) trgl_shim::fail("gl_instance_boxes", rc, nullptr);
+    std::vector<AABB> boxes(n);
+    for (std::size_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) { boxes[i].min[a] = b[6 * i + a]; boxes[i].max[a] = b[6 * i + 3 + a]; }
+    return boxes;
+}
+namespace trgl_shim {
+inline bool frustum_codes(const Frustum& frustum, const std::vector<AABB>& boxes, int mode, std::uint8_t* codes) {
+    double p[24];
+    for (int i = 0; i < 6; ++i) { for (int a = 0; a < 3; ++a) p[4 * i + a] = frustum.planes[i].normal[a]; p[4 * i + 3] = frustum.planes[i].d; }
+    std::vector<double> b(boxes.size() * 6);
+    for (std::size_t i = 0; i < boxes.size(); ++i)
+        for (int a = 0; a < 3; ++a) { b[6 * i + a] = boxes[i].min[a]; b[6 * i + 3 + a] = boxes[i].max[a]; }
+    const int rc = trgl_frustum_boxes(nullptr, p, b.data(), boxes.size(), mode, TRGL_MEM_HOST, codes);
+    return rc == TRGL_OK || fail(mode == TRGL_FRUSTUM_SET ? "gl_frustum_test" : "gl_frustum_test (merge)", rc, nullptr);
+}
+}  // namespace trgl_shim
+inline std::vector<std::uint8_t> gl_frustum_test(const Frustum& frustum, const std::vector<AABB>& boxes) {
+    std::vector<std::uint8_t> codes(boxes.size(), std::uint8_t(TRGL_OCCL_UNDECIDED));
+    trgl_shim::frustum_codes(frustum, boxes, TRGL_FRUSTUM_SET, codes.data());
+    return codes;
+}
+inline bool gl_frustum_test(const Frustum& frustum, const std::vector<AABB>& boxes, std::vector<std::uint8_t>& codes) {
+    if (codes.size() != boxes.size()) return trgl_shim::fail("gl_frustum_test: one code per box is needed to merge into", TRGL_E_INVALID, nullptr);
+    return trgl_shim::frustum_codes(frustum, boxes, TRGL_FRUSTUM_MERGE, codes.data());
+}
 
 inline void print_render_stats() {                                                // our_gl.cpp:204-210
     trgl_shim::State& s = trgl_shim::state();
