@@ -568,8 +568,14 @@ int trgl_draw_indexed_vs_clipped(trgl_ctx* ctx, int vs, int shader_kind, const t
 int trgl_flush(trgl_ctx* ctx);
 /* The same in two halves, for a caller that overlaps something with the first one: trgl_flush_begin runs per-triangle
  * setup and tile binning (neither reads nor writes the framebuffer / z-buffer), trgl_flush_end the tile raster.  Every
- * other entry point completes a begun flush first.  bench.py: the RCCL gather of the previous frame's strips runs
- * under the next frame's first half. */
+ * other entry point that queues work on the context's stream or reads or changes the context's state completes a begun
+ * flush first, with two exceptions.  The four calls that only queue work over caller-owned device arrays and flush
+ * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths and trgl_depth_order with TRGL_MEM_DEVICE -
+ * leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those four,
+ * trgl_clip_stage, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
+ * computes on the host and returns without touching the context's queue.  A call refused for its arguments or for the
+ * context's state may return before it completes anything.
+ * bench.py: the RCCL gather of the previous frame's strips runs under the next frame's first half. */
 int trgl_flush_begin(trgl_ctx* ctx);
 int trgl_flush_end(trgl_ctx* ctx);
 /* Wait for the context's stream. */
