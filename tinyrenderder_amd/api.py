@@ -200,6 +200,8 @@ def load_library(path: str = None):
         L.trgl_debug_read.argtypes = [vp, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     if hasattr(L, "trgl_debug_binning"):
         L.trgl_debug_binning.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "trgl_debug_radix_blocks"):
+        L.trgl_debug_radix_blocks.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.trgl_selftest_division.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
     L.trgl_selftest_sampler.argtypes = [vp, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.trgl_draw_indexed.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
@@ -1510,6 +1512,16 @@ class Context:
         d, f = C.c_int(), C.c_int()
         self._chk(self.L.trgl_debug_binning(self.h, -1 if mode is None else mode, S, G, C.byref(d), C.byref(f)))
         return dict(direct=bool(d.value), fell_back=bool(f.value))
+
+    def debug_radix_blocks(self, n=None):
+        """Test hook (trgl_debug_radix_blocks).  n caps the grids of the radix scatters of the next flushes (0: automatic, as many
+        blocks as the device holds at once; every block walks its chunks with a stride of the grid); None changes nothing.  Returns
+        the grids of the last binning queued: dict(first=..., last=...)."""
+        if n is not None:
+            self._radix_blocks = int(n)
+        a, b = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.trgl_debug_radix_blocks(self.h, getattr(self, "_radix_blocks", 0), C.byref(a), C.byref(b)))
+        return dict(first=a.value, last=b.value)
 
     def _debug_read(self, what, dtype):
         need = C.c_size_t()

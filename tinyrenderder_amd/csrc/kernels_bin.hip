@@ -10,6 +10,7 @@
 //
 // All integer / fp64 IEEE work; built with -ffp-contract=off so no product is fused into a sum.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include "trgl_device.h"
 #include "launch.h"
 #include "device_util.h"
@@ -477,14 +478,16 @@ __global__ __launch_bounds__(256) void k_expand(FrameParams fp, uint32_t first, 
 // ---------------------------------------------------------------------------------------------
 // stable LSD radix pass on `bits` key bits at `shift`.  A block of RADIX_WAVES waves owns RADIX_CHUNK = RADIX_WAVES x 1024 consecutive
 // pairs; wave w owns the w-th part and walks it in order, 64 pairs a step, ranking equal digits
-// with ballots, so equal keys keep their input order (= triangle submission order).  The chunk is
+// by their lane numbers, so equal keys keep their input order (= triangle submission order).  The chunk is
 // then reordered by digit in LDS and written out linearly, so global stores are contiguous runs
 // (RADIX_CHUNK / 2^bits pairs per digit on average) instead of 64 scattered 4-byte elements per
-// instruction.  hist layout: [digit][block] so one exclusive scan yields every block's base per digit.
+// instruction.  hist layout: [digit][chunk] so one exclusive scan yields every chunk's base per digit.
+// The scatter's grid is what the device holds at once; a block walks the chunks blockIdx.x, blockIdx.x + gridDim.x, ... (a static
+// stride: no work counter, no block waits for another) with the loads of its next chunk in flight behind the current one.
 // A pair is its sort word (k_expand) and its triangle word; WIDE frames also move the 16-bit mask stream.  The last pass writes
 // what k_raster reads - triangle words and masks, no sort words - and the tile bounds (k_radix_scatter).
 // ---------------------------------------------------------------------------------------------
-// A block has RADIX_WAVES waves: 8 (8192 pairs, 74 KB of LDS, two blocks per CU) when the pair buffers hold at least
+// A block has RADIX_WAVES waves: 8 (8192 pairs, 75 KB of LDS, two blocks per CU) when the pair buffers hold at least
 // RADIX_BIG_CAP pairs, else 4 (4096 pairs, four blocks per CU).  8 waves give runs of 64 pairs per digit at 7-bit digits; measured
 // against 4 on the 4096^2 frame (18 M pairs): first pass 94 -> 85 us, last pass 107 -> 101 us, row scans 8 -> 5 us.  On the head frames
 // (C2 / C3, a few hundred thousand pairs: under 100 blocks of 8192 for 256 CUs) 8 waves made the binning 4 us slower.
@@ -610,7 +613,7 @@ __device__ __forceinline__ void rounds_below(uint32_t part, F& f) {
 // blocks: logical pair p of the chunk, in submission order, sits in segment s at p - s_off[s], for the s with s_off[s] <= p < s_off[s + 1].
 // Everything behind the loads - ranks, the reorder, the dense output - is the same code.
 template <int RADIX_WAVES, bool WIDE, bool LAST, bool SEG>
-__global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+__global__ __launch_bounds__(RADIX_WAVES * 64, WIDE ? 2 : 4) void k_radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                                                                  const uint16_t* __restrict__ msk_in,
                                                                  const unsigned long long* __restrict__ pairs_total, uint32_t cap,
                                                                  int shift, int bits, uint32_t nblocks,
@@ -624,29 +627,36 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
     __shared__ uint32_t s_cnt[RADIX_WAVES][1 << RADIX_MAX_BITS];     // per wave: running count, then (after phase 2) local start
     __shared__ uint32_t s_start[1 << RADIX_MAX_BITS];      // first local position of each digit in the chunk
     __shared__ uint32_t s_gbase[1 << RADIX_MAX_BITS];      // global position of the chunk's first pair of each digit
+    __shared__ uint32_t s_tot[1 << RADIX_MAX_BITS];        // pairs of all smaller digits in the whole input
     __shared__ uint32_t s_val[RADIX_CHUNK];
-    __shared__ uint32_t s_key[RADIX_CHUNK];
+    __shared__ __attribute__((aligned(16))) uint32_t s_key[RADIX_CHUNK];
     __shared__ uint16_t s_msk[WIDE ? RADIX_CHUNK : 2];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const unsigned long long P64 = *pairs_total;
     const uint32_t P = (P64 > cap || (!SEG && seg.flag && *seg.flag)) ? 0u : (uint32_t)P64;      // (seg.flag in a dense pass: a later pass of the direct path, k_radix_hist)
-    if (!SEG && (uint64_t)blockIdx.x * RADIX_CHUNK >= P) return;     // the grid covers the capacity of the buffers, not the pairs of this flush
+    // the chunks of this flush: the table has `nblocks` columns (the capacity of the buffers, or the groups), the flush fills the first of them
+    uint32_t nchunks = nblocks;
     if (SEG) {
-        if (*seg.flag || P64 > cap) return;                 // the flush does not fit the segments, or the output buffers: the host bins again
-        const uint32_t b = blockIdx.x * seg.G + lane;
-        if (w == 0) {
-            const uint32_t c = (lane < seg.G && b < seg.nsetup) ? seg.blk_sums[b] : 0u;
-            const uint32_t inc = wave_incl_scan(c);
-            if (lane <= SEG_MAX_GROUP) s_off[lane] = inc - c;     // (lanes from seg.G on hold the total: no pair is looked for behind it)
-        }
+        // the flush does not fit the segments, or the output buffers: the host bins again  (the sizes: k_chunk_spine flags such a flush, never taken)
+        if (*seg.flag || P64 > cap || seg.S > SEG_MAX || seg.G > SEG_MAX_GROUP) return;
+    } else {
+        nchunks = min(nblocks, (uint32_t)(((uint64_t)P + RADIX_CHUNK - 1) / RADIX_CHUNK));
     }
+    uint32_t chunk = blockIdx.x;
+    if (chunk >= nchunks) return;
     const uint32_t nb = 1u << bits, mask = nb - 1;
-    for (uint32_t b = threadIdx.x; b < nb; b += RADIX_THREADS) {
-#pragma unroll
-        for (int ww = 0; ww < RADIX_WAVES; ++ww) s_cnt[ww][b] = 0;
-        s_gbase[b] = base[(size_t)b * nblocks + blockIdx.x];      // pairs of this digit in the blocks before this one (k_radix_scan_rows)
-    }
-    if (w == 0) {       // + the pairs of all smaller digits: exclusive scan of the row totals (nb <= 256: up to 4 digits per lane)
+    // the prefix sums of a group's segment sizes: pairs of the group before segment s
+    auto put_offsets = [&](const uint32_t c) {       // (wave 0; c: blk_sums of the group's lane-th setup block, 0 behind the group)
+        const uint32_t inc = wave_incl_scan(c);
+        if (lane <= SEG_MAX_GROUP) s_off[lane] = inc - c;     // (lanes from seg.G on hold the total: no pair is looked for behind it)
+    };
+    auto group_count = [&](const uint32_t c) {
+        const uint32_t b = c * seg.G + lane;
+        return (lane < seg.G && b < seg.nsetup) ? seg.blk_sums[b] : 0u;
+    };
+    if (w == 0) {
+        if (SEG) put_offsets(group_count(chunk));
+        // the pairs of all smaller digits: exclusive scan of the row totals (nb <= 256: up to 4 digits per lane); the same for every chunk
         uint32_t tot[4], run = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) { const uint32_t d = lane * 4 + q; tot[q] = d < nb ? totals[d] : 0; run += tot[q]; }
@@ -654,61 +664,97 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
         for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if (lane >= o) inc += t; }
         uint32_t ex = inc - run;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { const uint32_t d = lane * 4 + q; if (d < nb) s_start[d] = ex; ex += tot[q]; }
+        for (int q = 0; q < 4; ++q) { const uint32_t d = lane * 4 + q; if (d < nb) s_tot[d] = ex; ex += tot[q]; }
     }
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < nb; b += RADIX_THREADS) s_gbase[b] += s_start[b];
-    __syncthreads();
-    const uint64_t cbeg = SEG ? 0 : (uint64_t)blockIdx.x * RADIX_CHUNK;      // (SEG: positions inside the group)
-    uint64_t cend = cbeg + RADIX_CHUNK; if (cend > P) cend = P;
-    // (SEG: a group rarely fills the chunk, so its pairs are dealt to the waves in equal parts, in order - fewer rounds for every wave
-    // instead of idle last waves; a part is a multiple of 64, and the rounds behind it are skipped)
-    uint32_t wave_part = RADIX_WAVE_CHUNK;
-    if (SEG) {
-        cend = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_off[SEG_MAX_GROUP]);
-        if (cend > (uint64_t)RADIX_CHUNK || seg.S > SEG_MAX || seg.G > SEG_MAX_GROUP) return;      // (k_chunk_spine flags such a flush: never taken; block-uniform)
-        wave_part = (((uint32_t)cend + RADIX_THREADS - 1) / RADIX_THREADS) * 64;
-    }
-    const uint32_t n_chunk = (uint32_t)(cend - cbeg);
-    const uint64_t wbeg = cbeg + (uint64_t)w * wave_part;
+    // The span of a chunk: it holds n pairs, and wave w ranks the `part` of them from w * part on, 64 a round.  Positions are counted
+    // inside the chunk from here on.
+    // (SEG: s_off must hold the group's offsets.  A group rarely fills the chunk, so its pairs are dealt to the waves in equal parts, in
+    // order - fewer rounds for every wave instead of idle last waves; a part is a multiple of 64, and the rounds behind it are skipped)
+    struct Span { uint32_t n, part; };
+    auto span_of = [&](const uint32_t c) {
+        Span sp;
+        if (SEG) {
+            sp.n = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_off[SEG_MAX_GROUP]);
+            sp.part = ((sp.n + RADIX_THREADS - 1) / RADIX_THREADS) * 64;
+        } else {
+            const uint64_t cbeg = (uint64_t)c * RADIX_CHUNK;
+            sp.n = (uint32_t)min((uint64_t)RADIX_CHUNK, (uint64_t)P - cbeg);      // (c < nchunks: cbeg < P)
+            sp.part = RADIX_WAVE_CHUNK;
+        }
+        return sp;
+    };
+    Span cur = span_of(chunk);
+    if (SEG && cur.n > (uint32_t)RADIX_CHUNK) return;      // (k_chunk_spine flags such a flush: never taken; block-uniform)
     const unsigned long long lt = (1ull << lane) - 1ull;
 
-    // ---- phase 1: stable rank of every pair among the equal digits of its wave's part ------------
+    // the wave's match table of phase 1, a 64-bit word per digit: in s_key, which is idle until phase 3 (a wave's share of s_key holds 512)
+    static_assert(RADIX_WAVE_CHUNK * sizeof(uint32_t) >= (sizeof(unsigned long long) << RADIX_MAX_BITS), "a match table per wave in s_key");
+    unsigned long long* const match = reinterpret_cast<unsigned long long*>(s_key) + (size_t)w * (RADIX_WAVE_CHUNK / 2);
     uint32_t k[RADIX_ROUNDS], v[RADIX_ROUNDS], rk[RADIX_ROUNDS];
     uint16_t mk[WIDE ? RADIX_ROUNDS : 1];
-#pragma unroll
-    for (int r = 0; r < RADIX_ROUNDS; ++r) {
-        const uint64_t p = wbeg + (uint64_t)r * 64 + lane;
-        const bool act = p < cend && (!SEG || r * 64 < (int)wave_part);
+    // round r of wave w of chunk c into k[r], v[r] (mk[r]).  The addresses are a base that is the same for the whole block plus a 32-bit
+    // offset, so that the sixteen rounds in flight do not hold sixteen 64-bit addresses in registers.
+    auto load_round = [&](const int r, const uint32_t c, const Span& sp) {
+        const uint32_t q0 = (uint32_t)w * sp.part + lane, q = q0 + (uint32_t)r * 64;
+        // (q < n, written so that the round's part of it is scalar arithmetic; positions are below 2^14)
+        const bool act = (int)q0 < (int)sp.n - r * 64 && (!SEG || (uint32_t)(r * 64) < sp.part);
         if (SEG) {
             // (a binary search over the group's 17 offsets per pair; measured against a table of the segment every 64th pair sits in
             // and a walk from there: 98.6 against 104.5 us on the C4 frame)
-            const uint32_t lp = (uint32_t)p;
             uint32_t sg = 0;
             if (act) {
 #pragma unroll
-                for (uint32_t st = SEG_MAX_GROUP / 2; st; st >>= 1) if (lp >= s_off[sg + st]) sg += st;
+                for (uint32_t st = SEG_MAX_GROUP / 2; st; st >>= 1) if (q >= s_off[sg + st]) sg += st;
             }
-            const size_t a = (size_t)(blockIdx.x * seg.G + sg) * seg.S + (lp - s_off[sg]);
-            k[r] = act ? keys_in[a] : 0; v[r] = act ? vals_in[a] : 0;
+            const size_t group = (size_t)c * seg.G * seg.S;
+            const uint32_t a = sg * seg.S + (q - s_off[sg]);       // (G S <= 16 x 4096)
+            k[r] = act ? (keys_in + group)[a] : 0; v[r] = act ? (vals_in + group)[a] : 0;
         } else {
-            k[r] = act ? keys_in[p] : 0; v[r] = act ? vals_in[p] : 0;
-            if (WIDE) mk[WIDE ? r : 0] = act ? msk_in[p] : (uint16_t)0;
+            const size_t cbeg = (size_t)c * RADIX_CHUNK;
+            k[r] = act ? (keys_in + cbeg)[q] : 0; v[r] = act ? (vals_in + cbeg)[q] : 0;
+            if (WIDE) mk[WIDE ? r : 0] = act ? (msk_in + cbeg)[q] : (uint16_t)0;
         }
-    }
+    };
+#pragma unroll
+    for (int r = 0; r < RADIX_ROUNDS; ++r) load_round(r, chunk, cur);
+
+    // A block takes the chunks blockIdx.x, blockIdx.x + gridDim.x, ... and never waits for another block.  While it reorders and writes
+    // chunk i, the loads of chunk i + 1 are in flight: round r of the next chunk is requested as soon as phase 3 has consumed k[r], v[r]
+    // and rk[r], so the registers of one chunk serve both.  Five block barriers per chunk.  What one chunk's phases share with the
+    // next one's: s_off is written in phase 2 for the NEXT group (its last readers were the loads of phase 3 of the chunk before, so one
+    // copy is enough); s_gbase and s_start are written behind the barrier that follows the ranking; s_key holds the match tables of
+    // the ranking, hence the barrier at the bottom of the loop.
+    for (;;) {
+    const uint32_t next = chunk + gridDim.x;
+    bool more = next < nchunks;
+    const uint32_t wave_part = cur.part, n_chunk = cur.n;
+    const int pos0 = (int)((uint32_t)w * wave_part + lane);      // the lane's pair of round r is pos0 + 64 r, and is there if that is < n_chunk
+    // requested here, used behind the ranking: pairs of each digit in the chunks before this one (k_radix_scan_rows), and the segment
+    // sizes of the next group
+    const uint32_t gb = threadIdx.x < nb ? base[(size_t)threadIdx.x * nblocks + chunk] : 0u;      // (nb <= 256 <= RADIX_THREADS)
+    uint32_t next_count = 0;
+    if (SEG && w == 0 && more) next_count = group_count(next);
+    for (uint32_t d = lane; d < nb; d += 64) { s_cnt[w][d] = 0; match[d] = 0ull; }
+    __builtin_amdgcn_wave_barrier();
+    // ---- phase 1: stable rank of every pair among the equal digits of its wave's part ------------
     auto rank_round = [&](const int r) {
-        const bool act = wbeg + (uint64_t)r * 64 + lane < cend;
+        const bool act = pos0 < (int)n_chunk - r * 64;
         const uint32_t dgt = (k[r] >> shift) & mask;
-        unsigned long long same = __ballot(act);
-        for (int b = 0; b < bits; ++b) {
-            const unsigned long long bal = __ballot((dgt >> b) & 1u);
-            same &= ((dgt >> b) & 1u) ? bal : ~bal;
-        }
+        // the lanes of the round that hold the same digit: every lane ORs its bit into the digit's word of the wave's match table, then
+        // reads the word back (a wave's LDS operations complete in the order they were issued); the first lane of a digit leaves the
+        // word 0 for the next round.  OR does not depend on the order of the lanes and the ranks come from the lane numbers, so
+        // the sort stays stable; lanes past the chunk's end take no part.
+        unsigned long long* const slot = match + dgt;
+        if (act) __hip_atomic_fetch_or(slot, lt + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        __builtin_amdgcn_wave_barrier();
+        const unsigned long long same = act ? __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 0ull;
         const uint32_t cur = act ? s_cnt[w][dgt] : 0;
         __builtin_amdgcn_wave_barrier();
         const uint32_t r_in = __popcll(same & lt);
         rk[r] = cur + r_in;
-        if (act && r_in == 0) s_cnt[w][dgt] = cur + (uint32_t)__popcll(same);
+        asm volatile("" : "+v"(rk[r]));      // (one register per round from here on, not the count and the mask it is made of)
+        if (act && r_in == 0) { s_cnt[w][dgt] = cur + (uint32_t)__popcll(same); *slot = 0ull; }
         __builtin_amdgcn_wave_barrier();
     };
     if constexpr (SEG) {
@@ -719,7 +765,10 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
     }
     __syncthreads();
     // ---- phase 2: local layout: digits ascending, inside a digit waves ascending ------------------------
+    if (threadIdx.x < nb) s_gbase[threadIdx.x] = gb + s_tot[threadIdx.x];
     if (w == 0) {
+        // (the offsets of the next group: the last reader of this group's was phase 3 of the chunk before)
+        if (SEG && more) put_offsets(next_count);
         // exclusive scan over digits of the chunk totals (nb <= 256: up to 4 digits per lane)
         uint32_t tot[4], run = 0;
 #pragma unroll
@@ -745,21 +794,25 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
 #pragma unroll
         for (int ww = 0; ww < RADIX_WAVES; ++ww) { const uint32_t c = s_cnt[ww][d]; s_cnt[ww][d] = run; run += c; }
     }
+    Span nxt = cur;
+    if (more) {
+        nxt = span_of(next);        // (SEG: s_off holds the next group's offsets from here on)
+        if (SEG && nxt.n > (uint32_t)RADIX_CHUNK) more = false;      // (k_chunk_spine flags such a flush: never taken; block-uniform)
+    }
     __syncthreads();
-    // ---- phase 3: reorder in LDS (4-byte words: lanes of one digit write consecutive banks) ---------------------------
+    // ---- phase 3: reorder in LDS (4-byte words: lanes of one digit write consecutive banks), and request the next chunk ----------
     auto place_round = [&](const int r) {
-        if (wbeg + (uint64_t)r * 64 + lane < cend) {
+        if (pos0 < (int)n_chunk - r * 64) {
             const uint32_t dgt = (k[r] >> shift) & mask;
             const uint32_t lp = s_cnt[w][dgt] + rk[r];
             s_key[lp] = k[r]; s_val[lp] = v[r];
             if (WIDE) s_msk[lp] = mk[WIDE ? r : 0];
         }
     };
-    if constexpr (SEG) {
-        rounds_below<0, RADIX_ROUNDS>(wave_part, place_round);
-    } else {
 #pragma unroll
-        for (int r = 0; r < RADIX_ROUNDS; ++r) place_round(r);
+    for (int r = 0; r < RADIX_ROUNDS; ++r) {
+        if (!SEG || (uint32_t)(r * 64) < wave_part) place_round(r);        // (wave-uniform)
+        if (more && (!SEG || (uint32_t)(r * 64) < nxt.part)) load_round(r, next, nxt);
     }
     __syncthreads();
     // ---- phase 4: linear read-out, contiguous global runs per digit ------------------------------------------
@@ -778,6 +831,10 @@ __global__ __launch_bounds__(RADIX_WAVES * 64) void k_radix_scatter(const uint32
             if (i == 0 || (s_key[i - 1] & KEY_MASK) != key) atomicMin(&tile_start[key], dst);
             if (i + 1 == n_chunk || (s_key[i + 1] & KEY_MASK) != key) atomicMax(&tile_end[key], dst + 1);
         }
+    }
+    if (!more) break;
+    chunk = next; cur = nxt;
+    __syncthreads();        // (the match tables of the next chunk's ranking lie in s_key, which the write-out reads)
     }
 }
 
@@ -824,41 +881,64 @@ bool seg_layout_ok(const SegLayout& seg) { return seg.S >= 4 && seg.S <= SEG_MAX
 
 // The pair count of the flush stays on the device (`pairs_total`): grids cover `cap`, the capacity of the pair buffers,
 // and blocks past the last pair do nothing, so the host never has to wait for the count before it can queue these.
+// The scatter's grid: as many blocks as the device holds at once, at most one per chunk (`chunks`: the columns of the table) and at
+// most `max_blocks` (0: no such limit); every block walks its chunks with a stride of the grid.  The blocks per CU of a variant are
+// asked for once per thread and device.
+template <int WAVES, bool WIDE, bool LAST, bool SEG>
+static uint32_t scatter_grid(uint32_t chunks, uint32_t max_blocks) {
+    thread_local int for_dev = -1;
+    thread_local uint32_t resident = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (dev != for_dev) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_radix_scatter<WAVES, WIDE, LAST, SEG>, WAVES * 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+        resident = (uint32_t)per_cu * (uint32_t)cus;
+        for_dev = dev;
+    }
+    uint32_t g = std::min(chunks, resident);
+    if (max_blocks) g = std::min(g, max_blocks);
+    return std::max(g, 1u);
+}
+
 template <int WAVES, bool WIDE, bool LAST>
-static void radix_pass_t(hipStream_t s, const RadixPass& ps, const unsigned long long* pairs_total, uint32_t cap, uint32_t* hist, uint32_t* scan_tmp,
-                         const uint32_t* skip) {
-    const uint32_t nblk = radix_num_workers(cap);
+static uint32_t radix_pass_t(hipStream_t s, const RadixPass& ps, const unsigned long long* pairs_total, uint32_t cap, uint32_t* hist, uint32_t* scan_tmp,
+                             const uint32_t* skip, uint32_t max_blocks) {
+    const uint32_t nblk = radix_num_workers(cap), grid = scatter_grid<WAVES, WIDE, LAST, false>(nblk, max_blocks);
     hipLaunchKernelGGL(k_radix_hist, dim3(nblk), dim3(256), 0, s, ps.keys_in, pairs_total, cap, ps.shift, ps.bits, (uint32_t)(WAVES * RADIX_WAVE_CHUNK),
                        nblk, hist, skip);
     hipLaunchKernelGGL(k_radix_scan_rows, dim3(1u << ps.bits), dim3(ROWSCAN_THREADS), 0, s, hist, nblk, scan_tmp);
-    hipLaunchKernelGGL((k_radix_scatter<WAVES, WIDE, LAST, false>), dim3(nblk), dim3(WAVES * 64), 0, s, ps.keys_in, ps.vals_in, ps.msk_in, pairs_total, cap,
+    hipLaunchKernelGGL((k_radix_scatter<WAVES, WIDE, LAST, false>), dim3(grid), dim3(WAVES * 64), 0, s, ps.keys_in, ps.vals_in, ps.msk_in, pairs_total, cap,
                        ps.shift, ps.bits, nblk, hist, scan_tmp, ps.keys_out, ps.vals_out, ps.msk_out, ps.tile_start, ps.tile_end, SegIn{ nullptr, skip, 0, 0, 0 });
+    return grid;
 }
-// the first pass of the direct path: one block per group of seg.G setup blocks, input from their segments
+// the first pass of the direct path: one chunk per group of seg.G setup blocks, input from their segments
 template <int WAVES, bool LAST>
-static void radix_pass_seg(hipStream_t s, const RadixPass& ps, const SegLayout& sl, const unsigned long long* pairs_total, uint32_t cap, uint32_t* hist,
-                           uint32_t* scan_tmp) {
-    const uint32_t nblk = seg_num_groups(sl);
+static uint32_t radix_pass_seg(hipStream_t s, const RadixPass& ps, const SegLayout& sl, const unsigned long long* pairs_total, uint32_t cap, uint32_t* hist,
+                               uint32_t* scan_tmp, uint32_t max_blocks) {
+    const uint32_t nblk = seg_num_groups(sl), grid = scatter_grid<WAVES, false, LAST, true>(nblk, max_blocks);
     const SegIn seg{ sl.blk_sums, sl.flag, sl.nsetup, sl.S, sl.G };
     hipLaunchKernelGGL(k_radix_hist_seg, dim3(nblk), dim3(256), 0, s, sl.keys, seg, pairs_total, cap, ps.shift, ps.bits, nblk, hist);
     hipLaunchKernelGGL(k_radix_scan_rows, dim3(1u << ps.bits), dim3(ROWSCAN_THREADS), 0, s, hist, nblk, scan_tmp);
-    hipLaunchKernelGGL((k_radix_scatter<WAVES, false, LAST, true>), dim3(nblk), dim3(WAVES * 64), 0, s, sl.keys, sl.vals, ps.msk_in, pairs_total, cap,
+    hipLaunchKernelGGL((k_radix_scatter<WAVES, false, LAST, true>), dim3(grid), dim3(WAVES * 64), 0, s, sl.keys, sl.vals, ps.msk_in, pairs_total, cap,
                        ps.shift, ps.bits, nblk, hist, scan_tmp, ps.keys_out, ps.vals_out, ps.msk_out, ps.tile_start, ps.tile_end, seg);
+    return grid;
 }
 
 template <int WAVES>
-static void radix_pass_w(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
-                         uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg, const uint32_t* skip) {
-    if (seg) { if (last) radix_pass_seg<WAVES, true>(s, ps, *seg, pairs_total, cap, hist, scan_tmp); else radix_pass_seg<WAVES, false>(s, ps, *seg, pairs_total, cap, hist, scan_tmp); }
-    else if (wide) { if (last) radix_pass_t<WAVES, true, true>(s, ps, pairs_total, cap, hist, scan_tmp, skip); else radix_pass_t<WAVES, true, false>(s, ps, pairs_total, cap, hist, scan_tmp, skip); }
-    else { if (last) radix_pass_t<WAVES, false, true>(s, ps, pairs_total, cap, hist, scan_tmp, skip); else radix_pass_t<WAVES, false, false>(s, ps, pairs_total, cap, hist, scan_tmp, skip); }
+static uint32_t radix_pass_w(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
+                             uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg, const uint32_t* skip, uint32_t mb) {
+    if (seg) return last ? radix_pass_seg<WAVES, true>(s, ps, *seg, pairs_total, cap, hist, scan_tmp, mb) : radix_pass_seg<WAVES, false>(s, ps, *seg, pairs_total, cap, hist, scan_tmp, mb);
+    if (wide) return last ? radix_pass_t<WAVES, true, true>(s, ps, pairs_total, cap, hist, scan_tmp, skip, mb) : radix_pass_t<WAVES, true, false>(s, ps, pairs_total, cap, hist, scan_tmp, skip, mb);
+    return last ? radix_pass_t<WAVES, false, true>(s, ps, pairs_total, cap, hist, scan_tmp, skip, mb) : radix_pass_t<WAVES, false, false>(s, ps, pairs_total, cap, hist, scan_tmp, skip, mb);
 }
 
-void launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
-                       uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg, const uint32_t* skip) {
-    if (!cap || (seg && (wide || !seg->nsetup))) return;
-    if (radix_waves(cap) == 8) radix_pass_w<8>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp, seg, skip);
-    else radix_pass_w<4>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp, seg, skip);
+uint32_t launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
+                           uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg, const uint32_t* skip, uint32_t max_blocks) {
+    if (!cap || (seg && (wide || !seg->nsetup))) return 0;
+    if (radix_waves(cap) == 8) return radix_pass_w<8>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp, seg, skip, max_blocks);
+    return radix_pass_w<4>(s, ps, wide, last, pairs_total, cap, hist, scan_tmp, seg, skip, max_blocks);
 }
 
 }  // namespace trgl

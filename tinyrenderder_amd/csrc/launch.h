@@ -54,8 +54,11 @@ struct RadixPass {
 };
 // seg: the pass reads k_setup's segments in place of keys_in / vals_in (the first pass of the direct path; not wide)
 // skip: a later pass of the direct path - it does nothing when *skip (the flag of SegLayout) is set, as the first pass did
-void launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
-                       uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg = nullptr, const uint32_t* skip = nullptr);
+// The scatter of a pass runs as many blocks as the device holds at once (at most one per chunk, and at most max_blocks when that is
+// not 0), each walking its chunks with a stride of the grid; returns that grid (0: nothing was queued).
+uint32_t launch_radix_pass(hipStream_t s, const RadixPass& ps, bool wide, bool last, const unsigned long long* pairs_total, uint32_t cap,
+                           uint32_t* hist, uint32_t* scan_tmp, const SegLayout* seg = nullptr, const uint32_t* skip = nullptr,
+                           uint32_t max_blocks = 0);
 
 uint32_t owned_tiles(const FrameParams& fp);       // tiles of the rows this context owns (strip or interleaved bands)
 uint32_t raster_max_items(const FrameParams& fp);   // work items (workgroups of k_raster) of a flush, at most

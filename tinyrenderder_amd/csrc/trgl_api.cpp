@@ -316,8 +316,10 @@ static int queue_binning(trgl_ctx* c, const FrameParams& fp, uint32_t cap, int* 
     for (int ps = 0; ps < passes; ++ps) {
         const RadixPass rp{ c->keys[cur].p, c->vals[cur].p, c->bmask[cur].p, c->keys[cur ^ 1].p, c->vals[cur ^ 1].p, c->bmask[cur ^ 1].p,
                             c->tile_start.p, c->tile_end(), ps * bits_per, bits_per };
-        launch_radix_pass(s, rp, wide, ps == passes - 1, pairs_dev, cap, c->hist.p, c->scan_tmp.p, ps == 0 ? seg : nullptr,
-                          (seg && ps > 0) ? seg->flag : nullptr);
+        const uint32_t grid = launch_radix_pass(s, rp, wide, ps == passes - 1, pairs_dev, cap, c->hist.p, c->scan_tmp.p, ps == 0 ? seg : nullptr,
+                                                (seg && ps > 0) ? seg->flag : nullptr, c->radix_max_blocks);
+        if (ps == 0) c->radix_used[0] = grid;
+        if (ps == passes - 1) c->radix_used[1] = grid;
         cur ^= 1;
     }
     *cur_out = cur;
@@ -713,6 +715,17 @@ extern "C" int trgl_debug_binning(trgl_ctx* c, int mode, uint32_t S, uint32_t G,
     if (mode >= 0) { c->bin_mode = mode; c->bin_S = mode == 2 ? S : 0; c->bin_G = mode == 2 ? G : 0; c->seg_hold = false; }
     if (last_direct) *last_direct = c->snap.rp.direct;
     if (last_fell_back) *last_fell_back = c->snap.rp.fell_back;
+    return TRGL_OK;
+}
+
+// Test hook beside trgl_debug_binning (not part of include/trgl.h): the radix scatters of the NEXT flushes run at most max_blocks blocks
+// (0: as many as the device holds at once, the default); every block walks its chunks with a stride of the grid, so a small grid makes
+// every block loop.  *used_first / *used_last (may be null): the grids of the first and the last pass of the last binning queued.
+extern "C" int trgl_debug_radix_blocks(trgl_ctx* c, uint32_t max_blocks, uint32_t* used_first, uint32_t* used_last) {
+    CHKCTX(c);
+    c->radix_max_blocks = max_blocks;
+    if (used_first) *used_first = c->radix_used[0];
+    if (used_last) *used_last = c->radix_used[1];
     return TRGL_OK;
 }
 

@@ -107,6 +107,9 @@ struct trgl_ctx {
     uint32_t* seg_flag_pinned = nullptr;
     int bin_mode = 0; uint32_t bin_S = 0, bin_G = 0;
     bool seg_hold = false;
+    // the grids of the radix scatters: at most radix_max_blocks blocks (0: as many as the device holds at once); radix_used: the grids
+    // of the first and the last pass the last flush queued (trgl_debug_radix_blocks)
+    uint32_t radix_max_blocks = 0, radix_used[2] = { 0, 0 };
     uint64_t rule_pairs = 0, rule_nblk = 0;     // pairs and setup blocks of the last flush that had triangles: a, the input of seg_sizes()
     DevBuf<uint32_t> tile_start;        // tile_start[bounds_half()] followed by tile_end[bounds_half()]: set together per flush (in 16-byte words)
     DevBuf<uint4> items; DevBuf<uint32_t> n_items;
