@@ -121,13 +121,15 @@ def zclear_finite_128():
 
 def huge_depths_128():
     """NDC depths up to 1.7e308 on vertices 1 and 2 (vertex 0 stays inside [-1, 1], so our_gl.cpp:103-106 keeps the
-    triangle): the interpolated depth (our_gl.cpp:156-158) overflows to +-inf or lands on huge finite values, and
-    our_gl.cpp:160 drops the non-finite ones.  The screen coordinates stay ordinary ('well scaled')."""
+    triangle): the interpolated depth (our_gl.cpp:156-158) lands on huge finite values of either sign.  (It does not
+    overflow: the computed barycentrics of a covered pixel sum to 1 within a few ulp, and 1.7e308 leaves 5 % of headroom below
+    the largest double, so our_gl.cpp:160 drops nothing here.  At the largest double itself it does: see overflowing_depths_scene
+    in test_user_kind_raster_paths_gpu.py.)  The screen coordinates stay ordinary ('well scaled')."""
     clip, col = scenes.random_triangles(600, 128, 128, seed=23, rmin=4, rmax=48)
     clip = clip.copy()
-    clip[0::5, 6] = 1.7e308;   clip[0::5, 10] = 1.7e308       # sum overflows to +inf
-    clip[1::5, 6] = -1.7e308;  clip[1::5, 10] = -1.7e308      # ... to -inf (would win every z-test if it were written)
-    clip[2::5, 6] = 1.7e308;   clip[2::5, 10] = -1.7e308      # huge cancelling terms: finite or not depending on the pixel
+    clip[0::5, 6] = 1.7e308;   clip[0::5, 10] = 1.7e308       # sums up to 1.7e308
+    clip[1::5, 6] = -1.7e308;  clip[1::5, 10] = -1.7e308      # ... down to -1.7e308 (wins every z-test where covered)
+    clip[2::5, 6] = 1.7e308;   clip[2::5, 10] = -1.7e308      # huge cancelling terms
     clip[3::5, 6] = -1e300                                     # huge but finite: wins where covered
     return make_case(128, 128, [(FLAT, None, clip, None, col)])
 
@@ -532,18 +534,27 @@ def on_device(case, clip_off=0, vary_off=0, col_off=0, producer_sync=True):
     return dict(case, draws=draws)
 
 
-def run_gpu(case, strip=None, interleave=None, split=None, flush_after=None, halves=False, start=None, shaders=None):
+def register_user_kind(ctx, sh):
+    """The user kind of sh = (source, K[, flag word]) on a context: bit 0 of the word (True counts as 1) is TRGL_SHADER_MAY_DISCARD,
+    bit 2 TRGL_SHADER_READS_DEST, bit 3 TRGL_SHADER_NO_DEPTH_WRITE (include/trgl.h)."""
+    flags = int(sh[2]) if len(sh) > 2 else 0
+    return ctx.register_shader(sh[0], sh[1], bool(flags & 1), reads_dest=bool(flags & 4), depth_write=not flags & 8)
+
+
+def run_gpu(case, strip=None, interleave=None, split=None, flush_after=None, halves=False, start=None, shaders=None, inspect=None):
     """Render a case through the C ABI on the GPU; returns (fb, z, stats tuple, stats line).
     strip = (y0, y1): a strip context (set_strip); interleave = (band_rows, rank, world): one rank's bands (set_interleave).
     split = k: each draw in k flushes; flush_after = i: a flush after draw i; halves: the last flush as flush_begin / flush_end.
     start = (fb, z): as for run_oracle, through write_framebuffer / write_zbuffer.
-    shaders: per draw, None or (source, K): the draw uses the user kind the context registers for that source.
+    shaders: per draw, None or (source, K[, flag word]): the draw uses the user kind the context registers for it
+    (register_user_kind).  inspect: f(ctx), called after the last flush has completed and before the read-backs; a run with
+    it ends in an explicit flush() for that, where every other run leaves the last flush to the first read-back.
     A draw whose clip array is a torch CUDA tensor is drawn from device memory (on_device: all of its arrays are); the
     binding refuses a host array in such a draw."""
     from tinyrenderder_amd.api import Context
     shaders = shaders or [None] * len(case["draws"])
     with Context(case["width"], case["height"], case["bpp"]) as ctx:
-        user = {sh: ctx.register_shader(*sh) for sh in dict.fromkeys(sh for sh in shaders if sh)}
+        user = {sh: register_user_kind(ctx, sh) for sh in dict.fromkeys(sh for sh in shaders if sh)}
         ctx.set_viewport(case["viewport"])
         fb0, z0 = start or (None, None)
         if fb0 is None or z0 is None:
@@ -574,6 +585,9 @@ def run_gpu(case, strip=None, interleave=None, split=None, flush_after=None, hal
         if halves:
             ctx.flush_begin()
             ctx.flush_end()
+        if inspect is not None:
+            ctx.flush()
+            inspect(ctx)
         return ctx.read_framebuffer(), ctx.read_zbuffer(), ctx.stats(), ctx.stats_line()
 
 

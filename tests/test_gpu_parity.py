@@ -85,13 +85,8 @@ def test_c4_full_size_equals_the_reference_frame():
     cases.assert_golden(cases.run_gpu(cases.on_device(cases.FULLSIZE_CASES["c4_4096_10m"]())), GOLDEN_FULL["c4_4096_10m"])
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_block_masks_on_adversarial_shapes(seed):
-    """Shapes chosen against the conservative per-block tests of k_raster (edge functions at block corners, depth-plane
-    minimum vs the block's stored maximum): needles with aspect ratios up to 1e7, triangles of area 1e-9..1e-4 px^2 (u.z
-    next to the 1e-12 limit), depth planes as steep as [-1, 1] across a fraction of a pixel, a vertex thousands of pixels
-    off screen, all on top of dense overdraw so that the stored maxima are low and the masks actually drop blocks.  Any
-    block dropped wrongly shows up as a missing fragment: z bits, colours and counters must equal the oracle's."""
+def adversarial_shapes_scene(seed):
+    """The scene of test_block_masks_on_adversarial_shapes (its docstring says what is in it): (W, H, clip, colours)."""
     rng = scenes.SplitMix64(7000 + seed)
     W, H = 160, 96
     n = 12000
@@ -123,6 +118,17 @@ def test_block_masks_on_adversarial_shapes(seed):
         zs = [-1.0, 1.0, -1.0 + 2.0 * u[i, 3]] if kind == 2 else [2.0 * u[i, 3] - 1.0, 2.0 * u[i, 1] - 1.0, 2.0 * u[i, 2] - 1.0]
         for v in range(3):
             clip[i, 4 * v + 0], clip[i, 4 * v + 1], clip[i, 4 * v + 2], clip[i, 4 * v + 3] = p[v][0], p[v][1], zs[v], 1.0
+    return W, H, clip, col
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_block_masks_on_adversarial_shapes(seed):
+    """Shapes chosen against the conservative per-block tests of k_raster (edge functions at block corners, depth-plane
+    minimum vs the block's stored maximum): needles with aspect ratios up to 1e7, triangles of area 1e-9..1e-4 px^2 (u.z
+    next to the 1e-12 limit), depth planes as steep as [-1, 1] across a fraction of a pixel, a vertex thousands of pixels
+    off screen, all on top of dense overdraw so that the stored maxima are low and the masks actually drop blocks.  Any
+    block dropped wrongly shows up as a missing fragment: z bits, colours and counters must equal the oracle's."""
+    W, H, clip, col = adversarial_shapes_scene(seed)
     check(_flat(W, H, clip, col))
 
 

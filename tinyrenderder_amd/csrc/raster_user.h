@@ -6,11 +6,14 @@
 // (kernels_raster.hip) does for a CHECKER flush, in the plainest form: the same work items (k_make_items), the same sorted pair
 // lists, the same item_stats partials for k_fold_stats behind it.  One 256-thread workgroup per work item, one 8x8 block per
 // wave, one pixel per lane; the block's depths and colours stay in registers from the first candidate to the block-out.  Per
-// candidate, in list order: the record's bbox test, barycentric() of our_gl.cpp:77-86 with exactly the operations of the scan
-// (TRGL_OWNER_BARYCENTRICS), the coverage test on the quotients, the depth of :156-158, the finite check and the strict z-test, the
-// perspective-correct barycentrics of :168-185 and then trgl_fragment - called for every fragment that passes the z-test, in
-// submission order per pixel, exactly where our_gl.cpp:187 calls it.  k_raster's accelerations (depth-plane cull, depth bound in
-// the pair, deferred resolves) are left out: they only skip work, and nothing here depends on them.
+// candidate, in list order: the record's bbox test, barycentric() of our_gl.cpp:77-86 with exactly the operations of the scan, the
+// coverage test on the quotients, the depth of :156-158, the finite check and the strict z-test, the perspective-correct
+// barycentrics of :168-185 and then trgl_fragment - called for every fragment that passes the z-test, in submission order per
+// pixel, exactly where our_gl.cpp:187 calls it.  The barycentrics and the correction are written out here, operation for operation
+// the text of TRGL_OWNER_BARYCENTRICS (shade_common.h), not an expansion of it: the coverage test, the depth and the z-test stand
+// between its two halves.  An edit to either copy belongs in both; tests/test_user_kind_raster_paths_gpu.py holds this one to the
+// oracle on the literal and the fallback branch.  k_raster's accelerations (depth-plane cull, depth bound in the pair, deferred
+// resolves) are left out: they only skip work, and nothing here depends on them.
 //
 // Two further flags of such a kind change this one text in straight lines (include/trgl.h, "User shaders that blend"); with both
 // off the kernel is the one above, instruction for instruction.  TRGL_USER_READS_DEST: `color` is the pixel from the start (the
