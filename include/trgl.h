@@ -495,6 +495,79 @@ int trgl_instance_stage_ordered(trgl_ctx* ctx, int vs, const trgl_uniforms* unif
                                 const uint32_t* order, uint64_t n_order, int order_mem_kind,
                                 double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out);
 
+/* ---- depth-ordered triangle draws: a depth per group of triangles, a gather of rows, and trgl_draw under an order list -------- */
+
+/* New work: rasterize() draws triangles as they come (our_gl.cpp:89-201), and trgl_draw sorts nothing.  A translucent mesh or a list of
+ * particle quads wants its TRIANGLES back to front; these three calls make the depths trgl_depth_order sorts and draw under the order
+ * it returns, without the rows of trgl_vertex_stage / trgl_instance_stage / trgl_clip_stage leaving device memory and without a wait.
+ *
+ * GROUPS.  group = g >= 1 consecutive triangles move together (a quad: g = 2).  n must be a multiple of g; there are G = n / g groups,
+ * and group q owns triangles q*g .. q*g + g - 1.
+ *
+ * trgl_triangle_depths: depths_out receives G doubles.  With v = 0 .. 3g - 1 over the vertices of group q in memory order,
+ *     w_v = clip[q*g*12 + 4*v + 3]
+ * (the reference's projection has row 3 = (0, 0, -1, 0), our_gl.cpp:44-56, so clip w = -(view z); the result is negated so that it
+ * ascends as the depths of trgl_instance_depths do: smaller = farther, what TRGL_ORDER_BACK_TO_FRONT expects).
+ *   TRGL_TRI_DEPTH_CENTROID: s = (((0.0 + w_0) + w_1) + ...) + w_{3g-1}, each addition rounded to fp64, in this order; d = s with its
+ *     sign bit flipped.  There is no division: within one call every group has the same 3g.  An addition whose result is a NaN returns,
+ *     bit for bit: the left operand with bit 51 set when the left operand is a NaN; else the right operand with bit 51 set when that is
+ *     one; else (+inf + -inf) 0xFFF8000000000000.
+ *   TRGL_TRI_DEPTH_NEAREST:  m = w_0; for v = 1 .. 3g - 1 in order, m = (w_v < m) ? w_v : m;  d = m with its sign bit flipped.
+ *   TRGL_TRI_DEPTH_FARTHEST: m = w_0; for v = 1 .. 3g - 1 in order, m = (m < w_v) ? w_v : m;  d = m with its sign bit flipped.
+ *   A NaN in w_0 therefore stays, a later NaN never replaces a bound, and of +0.0 and -0.0 the earlier stays.
+ *   "Sign bit flipped" is an integer XOR of bit 63, NaNs included (trgl_depth_order sorts NaNs by their sign): host and device memory
+ *   give the same 64 bits.
+ * mem_kind covers clip and depths_out.  Device memory (8-byte aligned, nothing wider is assumed): one thread per group, queued on the
+ * context's stream in order with the draws; the call does not wait and nothing is flushed.  Host memory: the same expressions in plain
+ * C++, complete on return, and ctx may be NULL.
+ * ERRORS.  TRGL_E_INVALID: a bad mode or mem_kind, TRGL_MEM_DEVICE without a context, group == 0, n not a multiple of group, with n > 0
+ * a null or misaligned array.  TRGL_E_UNSUPPORTED: n above 2^31 - 1.  n == 0: TRGL_OK once the scalar arguments are checked, and no
+ * array is read. */
+#define TRGL_TRI_DEPTH_CENTROID 0
+#define TRGL_TRI_DEPTH_NEAREST  1
+#define TRGL_TRI_DEPTH_FARTHEST 2
+int trgl_triangle_depths(trgl_ctx* ctx, const double* clip, uint64_t n, uint32_t group, int mode,
+                         int mem_kind, double* depths_out);
+
+/* trgl_order_stage: the gather alone.  clip / vary / colors: n triangles as trgl_draw takes them - 12 clip doubles, K varyings
+ * (K in 0 .. TRGL_MAX_USER_VARY; vary and vary_out NULL when K = 0) and one colour each when colors is given (colors_out may be NULL
+ * otherwise).  order: n_order x uint32, each naming a group.
+ * DEFINITION.  For p = 0 .. n_order - 1 and t = 0 .. g - 1, output triangle p*g + t is input triangle order[p]*g + t: every bit of its
+ *   clip row, its varyings row and its colour is copied.  A group named twice is written twice; one that is not named is not written.
+ *   An entry >= G: in a host list TRGL_E_INVALID, and nothing is written.  In a device list the g output triangles are all-zero rows
+ *   (clip +0.0, varyings +0.0, colour 0) and the entry is never used as an index; rasterize() counts such a triangle and drops it at
+ *   our_gl.cpp:94 (w <= 1e-12), so it leaves no other trace.  That rule is why the call needs no count from the device and no wait.
+ *   Exactly n_order * g rows are written.  Inputs and outputs must not overlap.
+ * One mem_kind covers all seven arrays.  Device memory (doubles 8-byte aligned, colours and the list 4-byte): at most one kernel per
+ * array, queued on the context's stream in order with the draws, no wait, nothing is flushed; rows travel 16 bytes at a time where
+ * both pointers are 16-byte aligned and the row length is a multiple of 16, else 8 (colours 4) - the bytes do not depend on it.  It
+ * completes a begun flush, as trgl_clip_stage does.  Host memory: plain C++, complete on return, and ctx may be NULL.
+ * ERRORS.  TRGL_E_INVALID: a bad mem_kind, TRGL_MEM_DEVICE without a context, K outside 0 .. TRGL_MAX_USER_VARY, group == 0, n not a
+ * multiple of group, order == NULL with n_order != 0, a host entry out of range, with n_order > 0 a null or misaligned array.
+ * TRGL_E_UNSUPPORTED: n or n_order * group above 2^31 - 1.  n_order == 0: TRGL_OK once the scalar arguments are checked, and no array
+ * is read or written. */
+int trgl_order_stage(trgl_ctx* ctx, int K, const double* clip, const double* vary, const uint32_t* colors, uint64_t n,
+                     const uint32_t* order, uint64_t n_order, uint32_t group, int mem_kind,
+                     double* clip_out, double* vary_out, uint32_t* colors_out);
+
+/* trgl_draw of the rows trgl_order_stage would produce: frame bytes, depths and every counter are bit for bit those of
+ * trgl_draw(shader_kind, uniforms, clip_out, vary_out, colors_out, n_order * group) over that call's outputs; triangles_rasterized
+ * grows by n_order * group.  Any kind trgl_draw takes, discarding and blending kinds included; the 2^24 cut and the flush rules are
+ * trgl_draw's.
+ *   mem_kind       : covers clip, varyings and colors (n triangles)
+ *   order          : n_order x uint32 in order_mem_kind memory (device: 4-byte aligned), or NULL - allowed exactly when n_order == 0,
+ *                    and the call then IS trgl_draw(ctx, shader_kind, uniforms, clip, varyings, colors, n, mem_kind), the convention
+ *                    of trgl_draw_instanced_ordered.
+ * MEMORY AND SYNCHRONISATION.  No combination waits.  Host rows and a host list: permuted in C++ and drawn as host arrays.  Any other
+ * mix: the host parts are copied to device memory before return, the gather runs on the context's stream into buffers the context
+ * owns until the flush is done, and the result is drawn with TRGL_MEM_DEVICE.  Device inputs are read when the gather runs on the
+ * stream, not at the flush (the rule written for the clip stage): they must be complete on that stream by then, and may be
+ * overwritten once the call has returned and the stream has passed it.
+ * ERRORS.  Those of trgl_draw and of trgl_order_stage, and TRGL_E_INVALID for a bad order_mem_kind. */
+int trgl_draw_ordered(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms,
+                      const double* clip, const double* varyings, const uint32_t* colors, uint64_t n, int mem_kind,
+                      const uint32_t* order, uint64_t n_order, uint32_t group, int order_mem_kind);
+
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 
 /* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and
@@ -569,10 +642,10 @@ int trgl_flush(trgl_ctx* ctx);
 /* The same in two halves, for a caller that overlaps something with the first one: trgl_flush_begin runs per-triangle
  * setup and tile binning (neither reads nor writes the framebuffer / z-buffer), trgl_flush_end the tile raster.  Every
  * other entry point that queues work on the context's stream or reads or changes the context's state completes a begun
- * flush first, with two exceptions.  The four calls that only queue work over caller-owned device arrays and flush
- * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths and trgl_depth_order with TRGL_MEM_DEVICE -
- * leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those four,
- * trgl_clip_stage, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
+ * flush first, with two exceptions.  The five calls that only queue work over caller-owned device arrays and flush
+ * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths, trgl_depth_order and trgl_triangle_depths with
+ * TRGL_MEM_DEVICE - leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those five,
+ * trgl_clip_stage, trgl_order_stage, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
  * computes on the host and returns without touching the context's queue.  A call refused for its arguments or for the
  * context's state may return before it completes anything.
  * bench.py: the RCCL gather of the previous frame's strips runs under the next frame's first half. */

@@ -40,6 +40,8 @@ OCCL_HIDDEN, OCCL_VISIBLE, OCCL_OUTSIDE, OCCL_UNDECIDED = range(4)     # TRGL_OC
 # level, output faces per block of the instanced vertex kernels
 INST_BLOCK, INST_SCAN_CHUNK, INST_VS_FACES = 256, 256, 64
 ORDER_BACK_TO_FRONT, ORDER_FRONT_TO_BACK = 0, 1     # TRGL_ORDER_*
+TRI_DEPTH_CENTROID, TRI_DEPTH_NEAREST, TRI_DEPTH_FARTHEST = 0, 1, 2     # TRGL_TRI_DEPTH_*
+CENTROID, NEAREST, FARTHEST = TRI_DEPTH_CENTROID, TRI_DEPTH_NEAREST, TRI_DEPTH_FARTHEST
 FRUSTUM_SET, FRUSTUM_MERGE = 0, 1     # TRGL_FRUSTUM_*: the mode of trgl_frustum_boxes
 NEAR_PLANE = (0.0, 0.0, 1.0, 1.0)     # the near plane of the reference's projection in clip space: z + w >= 0
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
@@ -66,6 +68,7 @@ SYMBOLS = [
     "trgl_draw_instanced", "trgl_instance_stage",
     "trgl_instance_depths", "trgl_depth_order", "trgl_draw_instanced_ordered", "trgl_instance_stage_ordered",
     "trgl_instance_boxes", "trgl_frustum_boxes",
+    "trgl_triangle_depths", "trgl_order_stage", "trgl_draw_ordered",
 ]
 
 
@@ -267,6 +270,11 @@ def load_library(path: str = None):
     L.trgl_depth_order.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
     L.trgl_instance_boxes.argtypes = [vp, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
     L.trgl_frustum_boxes.argtypes = [vp, dp, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
+    L.trgl_triangle_depths.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_void_p]
+    L.trgl_order_stage.argtypes = [vp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]
+    L.trgl_draw_ordered.argtypes = [vp, C.c_int, C.POINTER(Uniforms), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                                    C.c_void_p, C.c_uint64, C.c_uint32, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -614,6 +622,81 @@ def _is_device_tensor(a):
     return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) is True
 
 
+def _triangle_depths(L, handle, clip, group, mode, device):
+    """Returns (the clip array to keep alive, depths [n / group])."""
+    group = int(group)
+    if device:
+        if not _is_device_tensor(clip) or str(clip.dtype) != "torch.float64" or not clip.is_contiguous() or clip.numel() % 12:
+            raise ValueError("device=True: clip must be a contiguous float64 device tensor [n, 12]")
+        import torch
+        n = clip.numel() // 12
+        out = torch.empty(n // max(group, 1), dtype=torch.float64, device=clip.device)
+        ptrs = (clip.data_ptr() if n else None, out.data_ptr() if out.numel() else None)
+    else:
+        clip = np.ascontiguousarray(clip, np.float64).reshape(-1, 12)
+        n = clip.shape[0]
+        out = np.empty(n // max(group, 1), np.float64)
+        ptrs = (clip.ctypes.data, out.ctypes.data)
+    rc = L.trgl_triangle_depths(handle, ptrs[0], n, group, int(mode), MEM_DEVICE if device else MEM_HOST, ptrs[1])
+    if rc != 0:
+        raise TrglError(f"trgl_triangle_depths failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return clip, out
+
+
+def _order_stage(L, handle, clip, varyings, colors, order, group, device, out):
+    """Returns (arrays to keep alive, (clip_out, varyings_out, colors_out)) - n_order * group rows each."""
+    group = int(group)
+    if device:
+        import torch
+        for a, what in ((clip, "clip"), (varyings, "varyings")):
+            if a is not None and (not _is_device_tensor(a) or str(a.dtype) != "torch.float64" or not a.is_contiguous() or a.dim() != 2):
+                raise ValueError(f"device=True: {what} must be a contiguous float64 device tensor with 2 dimensions")
+        for a, what in ((colors, "colors"), (order, "order")):
+            if a is not None and (not _is_device_tensor(a) or a.element_size() != 4 or not a.is_contiguous() or a.dim() != 1):
+                raise ValueError(f"device=True: {what} must be a contiguous 32-bit device tensor with 1 dimension")
+        n, n_order = int(clip.shape[0]), int(order.shape[0])
+        K = 0 if varyings is None else int(varyings.shape[1])
+        rows = n_order * group
+        if out is None:
+            out = (torch.empty((rows, 12), dtype=torch.float64, device=clip.device),
+                   None if K == 0 else torch.empty((rows, K), dtype=torch.float64, device=clip.device),
+                   None if colors is None else torch.empty(rows, dtype=colors.dtype, device=clip.device))
+        ptrs = (_device_ptr(clip, "clip"), _device_ptr(varyings, "varyings") if K else None, _device_ptr(colors, "colors"), _device_ptr(order, "order"))
+        optrs = (_device_ptr(out[0], "clip_out"), _device_ptr(out[1], "varyings_out") if K else None, _device_ptr(out[2], "colors_out"))
+    else:
+        clip = np.ascontiguousarray(clip, np.float64).reshape(-1, 12)
+        n = clip.shape[0]
+        varyings = None if varyings is None else np.ascontiguousarray(varyings, np.float64).reshape(n, -1)
+        K = 0 if varyings is None else varyings.shape[1]
+        colors = None if colors is None else np.ascontiguousarray(colors, np.uint32).reshape(n)
+        order = np.ascontiguousarray(order, np.uint32).reshape(-1)
+        n_order = order.shape[0]
+        rows = n_order * group
+        if out is None:
+            out = (np.empty((rows, 12), np.float64), None if K == 0 else np.empty((rows, K), np.float64),
+                   None if colors is None else np.empty(rows, np.uint32))
+        ptrs = (_ptr(clip), _ptr(varyings) if K else None, _ptr(colors), _ptr(order))
+        optrs = (_ptr(out[0]), _ptr(out[1]) if K else None, _ptr(out[2]))
+    rc = L.trgl_order_stage(handle, K, ptrs[0], ptrs[1], ptrs[2], n, ptrs[3], n_order, group, MEM_DEVICE if device else MEM_HOST,
+                            optrs[0], optrs[1], optrs[2])
+    if rc != 0:
+        raise TrglError(f"trgl_order_stage failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (clip, varyings, colors, order), out
+
+
+def triangle_depths(clip, group=1, mode=TRI_DEPTH_CENTROID) -> np.ndarray:
+    """trgl_triangle_depths for a host array without a context: one depth per group of `group` consecutive triangles of clip [n, 12],
+    from the clip w of the group's vertices - their sum (CENTROID), their smallest (NEAREST) or their largest (FARTHEST), negated, so
+    that depth_order's default direction draws the farthest group first.  Needs no GPU."""
+    return _triangle_depths(load_library(), None, clip, group, mode, False)[1]
+
+
+def order_stage(clip, varyings=None, colors=None, order=(), group=1):
+    """trgl_order_stage for host arrays without a context: the rows of the groups that `order` names, in that order - output group p is
+    input group order[p].  Returns (clip, varyings, colors) with len(order) * group rows (None where the input is None).  Needs no GPU."""
+    return _order_stage(load_library(), None, clip, varyings, colors, order, group, False, None)[1]
+
+
 def _device_f64(t, ndim, what):
     if not _is_device_tensor(t) or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.dim() != ndim:
         raise ValueError(f"{what} must be a contiguous float64 device tensor with {ndim} dimensions (the other arrays are in device memory)")
@@ -925,8 +1008,12 @@ class Context:
         self._user_vary[kind.value] = int(n_varyings)
         return kind.value
 
-    def draw(self, kind, clip, varyings=None, colors=None, uniforms=None, n=None, device=False, clip_plane=None, clip_attrs=None):
-        """clip_plane: four doubles - the list is cut against that plane first (trgl_draw_clipped; the call waits for the stream once, for
+    def draw(self, kind, clip, varyings=None, colors=None, uniforms=None, n=None, device=False, clip_plane=None, clip_attrs=None,
+             order=None, order_device=False, group=1):
+        """order: a list of groups of `group` consecutive triangles - the groups it names are drawn, in its order (trgl_draw_ordered; no
+        wait).  A numpy array, or with order_device=True a 32-bit integer device tensor such as Context.depth_order(device=True) returns;
+        device arrays of such a draw are read when the call's gather runs on the stream, not at the flush.  Not with clip_plane.
+        clip_plane: four doubles - the list is cut against that plane first (trgl_draw_clipped; the call waits for the stream once, for
         the count of output triangles), with clip_attrs a list of (offset, components) or None for the kind's built-in layout.
         Host arrays (numpy) are copied before return; with device=True pass torch CUDA tensors (or raw
         pointers with n) that stay alive until the flush has completed: every array of such a draw, a host array
@@ -950,6 +1037,14 @@ class Context:
             assert n is not None or hasattr(clip, "shape")
             n = clip.shape[0] if n is None else n
             self._keep.append((clip, varyings, colors))
+        if order is not None:
+            assert clip_plane is None and clip_attrs is None, "order=: not with clip_plane="
+            oargs, _, keep = self._order_args(order, order_device)
+            if order_device:
+                self._keep.append(keep)
+            self._chk(self.L.trgl_draw_ordered(self.h, kind, None if uniforms is None else C.byref(uniforms), ptrs[0], ptrs[1], ptrs[2], int(n),
+                                               MEM_DEVICE if device else MEM_HOST, oargs[0], oargs[1], int(group), oargs[2]))
+            return
         if clip_plane is not None:
             arr, na = _clip_attrs(clip_attrs)
             self._chk(self.L.trgl_draw_clipped(self.h, kind, None if uniforms is None else C.byref(uniforms), _dp(_f64(clip_plane, 4, "clip_plane")),
@@ -1126,6 +1221,26 @@ class Context:
         depths, out = _depth_order(self.L, self.h, depths, front_to_back, device)
         if device:
             self._keep.append((depths, out))
+        return out
+
+    def triangle_depths(self, clip, group=1, mode=TRI_DEPTH_CENTROID, device=False):
+        """trgl_triangle_depths: one depth per group of `group` consecutive triangles of clip [n, 12] (see the module's triangle_depths).
+        Host array: a numpy array, no GPU work.  device=True: clip is a contiguous float64 device tensor; the depths come back as a
+        device tensor, queued on the context's stream without waiting - pass them to depth_order(device=True)."""
+        clip, out = _triangle_depths(self.L, self.h, clip, group, mode, device)
+        if device:
+            self._keep.append((clip, out))
+        return out
+
+    def order_stage(self, clip, varyings=None, colors=None, order=(), group=1, device=False, out=None):
+        """trgl_order_stage: the rows of the groups that `order` names, in that order.  Host arrays: as the module's order_stage.
+        device=True: clip [n, 12] f64, varyings [n, K] f64 or None, colors [n] (32-bit) or None and order [n_order] (32-bit) are device
+        tensors, out = (clip_out, varyings_out, colors_out) device tensors with len(order) * group rows (allocated with torch when not
+        given); the gather is queued on the context's stream without waiting, and an entry of the list that names no group gives
+        all-zero rows.  Returns (clip_out, varyings_out, colors_out)."""
+        keep, out = _order_stage(self.L, self.h, clip, varyings, colors, order, group, device, out)
+        if device:
+            self._keep.append((keep, out))
         return out
 
     def instance_boxes(self, local, instances, out=None):

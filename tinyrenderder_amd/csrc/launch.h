@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -201,6 +201,16 @@ void launch_instance_depths(hipStream_t s, const double model_view[16], const do
 hipError_t depth_order_scratch_bytes(uint32_t n, size_t* bytes);
 hipError_t launch_depth_order(hipStream_t s, const double* depths, uint32_t n, bool front_to_back, void* scratch, size_t scratch_bytes,
                               uint32_t* order);
+
+// A depth per group of triangles and the gather of rows under an order list (kernels_triorder.hip; both are written down at
+// trgl_triangle_depths / trgl_order_stage in include/trgl.h, the depth expressions are triorder_core.h's).
+// launch_triangle_depths: one thread per group; clip holds G * g triangles, depths G doubles, both 8-byte aligned; mode one of
+// TRGL_TRI_DEPTH_*; 0 < G, g >= 1, G * g < 2^31.
+// launch_gather_rows: for p < n_order, the g rows of out group p are those of in group order[p], or zeros when order[p] >= G (the entry
+// is then no index).  Rows of row_bytes bytes (a multiple of 4); in and out aligned to 4 bytes at least, and moved 16 or 8 bytes at a
+// time where they and row_bytes allow it.  0 < n_order, n_order * g < 2^31, G * g < 2^31.
+void launch_triangle_depths(hipStream_t s, const double* clip, uint32_t G, uint32_t g, int mode, double* depths);
+void launch_gather_rows(hipStream_t s, const void* in, void* out, uint32_t row_bytes, const uint32_t* order, uint32_t n_order, uint32_t G, uint32_t g);
 
 // World boxes of instances and frustum codes of boxes (kernels_scene.hip; both are written down at trgl_instance_boxes /
 // trgl_frustum_boxes in include/trgl.h, the arithmetic is scene_core.h's).  One thread per instance or box, 0 < n < 2^31; doubles 8-byte

@@ -192,6 +192,10 @@ void host_occlusion_boxes(const double* depth, int w, int h, const double viewpo
 // trgl_instance_depths and trgl_depth_order over host arrays (host_depth_order: false when it ran out of memory)
 void host_instance_depths(const double model_view[16], const double point[3], const double* instances, int stride, uint64_t n, double* depths);
 bool host_depth_order(const double* depths, uint64_t n, bool front_to_back, uint32_t* order);
+// trgl_triangle_depths over host arrays (G groups of g triangles), and trgl_order_stage (every entry of the list checked: below G)
+void host_triangle_depths(const double* clip, uint64_t G, uint32_t g, int mode, double* depths);
+void host_order_stage(int K, const double* clip, const double* vary, const uint32_t* colors, const uint32_t* order, uint64_t n_order, uint32_t g,
+                      double* clip_out, double* vary_out, uint32_t* colors_out);
 // trgl_instance_boxes and trgl_frustum_boxes over host arrays (local_stride 0: one local box for every instance)
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out);
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);

@@ -15,6 +15,7 @@
 #include "clip_core.h"
 #include "occlusion_core.h"
 #include "scene_core.h"
+#include "triorder_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -186,6 +187,29 @@ bool host_depth_order(const double* depths, uint64_t n, bool front_to_back, uint
         std::stable_sort(order, order + n, [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
     } catch (const std::bad_alloc&) { return false; }                         // (std::stable_sort falls back to merging in place)
     return true;
+}
+
+// ---- a depth per group of triangles and the gather of rows in host memory (include/trgl.h, trgl_triangle_depths / trgl_order_stage;
+// the depth expressions are triorder_core.h's) -------------------------------------------------------------------------------------
+void host_triangle_depths(const double* clip, uint64_t G, uint32_t g, int mode, double* depths) {
+    for (uint64_t q = 0; q < G; ++q) {
+        const double* w = clip + q * (uint64_t)g * 12 + 3;
+        double acc = tri_depth_first(mode, w[0]);
+        for (uint64_t v = 1; v < 3 * (uint64_t)g; ++v) acc = tri_depth_step(mode, acc, w[4 * v]);
+        const uint64_t bits = tri_depth_bits(acc);
+        std::memcpy(depths + q, &bits, sizeof(bits));
+    }
+}
+
+// every entry of the list is below G (checked by the caller)
+void host_order_stage(int K, const double* clip, const double* vary, const uint32_t* colors, const uint32_t* order, uint64_t n_order, uint32_t g,
+                      double* clip_out, double* vary_out, uint32_t* colors_out) {
+    for (uint64_t p = 0; p < n_order; ++p) {
+        const uint64_t src = (uint64_t)order[p] * g, dst = p * g;
+        std::memcpy(clip_out + dst * 12, clip + src * 12, (size_t)g * 12 * sizeof(double));
+        if (K) std::memcpy(vary_out + dst * (uint64_t)K, vary + src * (uint64_t)K, (size_t)g * (size_t)K * sizeof(double));
+        if (colors) std::memcpy(colors_out + dst, colors + src, (size_t)g * sizeof(uint32_t));
+    }
 }
 
 // ---- world boxes of instances and frustum codes of boxes in host memory (include/trgl.h, trgl_instance_boxes / trgl_frustum_boxes;

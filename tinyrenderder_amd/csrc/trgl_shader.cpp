@@ -1,7 +1,7 @@
 // trgl_shader.cpp — run-time shader registration (fragment kinds and vertex shaders, compiled by user_shaders.cpp) and the entry points
 // that run a stage in front of a draw: the vertex stage over an indexed mesh (trgl_draw_indexed, trgl_draw_indexed_vs, trgl_vertex_stage)
 // the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and the instanced stages (trgl_draw_instanced,
-// trgl_instance_stage, their ordered forms, and the depths and order those take: trgl_instance_depths, trgl_depth_order).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
+// trgl_instance_stage, their ordered forms, and the depths and order those take: trgl_instance_depths, trgl_depth_order) and the ordered triangle draw (trgl_triangle_depths, trgl_order_stage, trgl_draw_ordered).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <cstring>
 #include <memory>
 #include <new>
@@ -368,7 +368,132 @@ static int instance_stage_call(trgl_ctx* c, const char* who, const InstanceCall&
     return run_instanced(c, who, a, K, false, 0, clip_out, vary_out, colors_out, n_out);
 }
 
+// ---- depth-ordered triangle draws (include/trgl.h: trgl_triangle_depths, trgl_order_stage, trgl_draw_ordered) ----
+// what the three calls check of n and group alike
+static int check_groups(trgl_ctx* c, const std::string& w, uint64_t n, uint32_t group) {
+    if (group == 0) return fail(c, TRGL_E_INVALID, w + "group is 0");
+    if (n % group) return fail(c, TRGL_E_INVALID, w + "n is not a multiple of group");
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more triangles in one call");
+    return TRGL_OK;
+}
+
+// ... and of the list: n_order * group rows fit, and with host_list every entry names a group
+static int check_order_list(trgl_ctx* c, const std::string& w, const uint32_t* order, uint64_t n_order, uint32_t group, uint64_t G, bool host_list) {
+    if (n_order > 0x7fffffffull / group) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more triangles in the ordered list");
+    if (host_list)
+        for (uint64_t p = 0; p < n_order; ++p)
+            if (order[p] >= G) return fail(c, TRGL_E_INVALID, w + "an entry of the order list is not a group");
+    return TRGL_OK;
+}
+
+static bool order_rows_aligned(const double* clip, const double* vary, const uint32_t* colors) {
+    return !((((uintptr_t)clip | (uintptr_t)vary) & 7) || ((uintptr_t)colors & 3));
+}
+
+// The gather over device arrays, queued on the context's stream: one launch per array (vary null: K = 0; colors null: none)
+static int queue_order_stage(trgl_ctx* c, int K, const double* clip, const double* vary, const uint32_t* colors, uint64_t G, const uint32_t* order,
+                             uint64_t n_order, uint32_t g, double* clip_out, double* vary_out, uint32_t* colors_out) {
+    launch_gather_rows(c->stream, clip, clip_out, 12 * sizeof(double), order, (uint32_t)n_order, (uint32_t)G, g);
+    if (K) launch_gather_rows(c->stream, vary, vary_out, (uint32_t)K * sizeof(double), order, (uint32_t)n_order, (uint32_t)G, g);
+    if (colors) launch_gather_rows(c->stream, colors, colors_out, sizeof(uint32_t), order, (uint32_t)n_order, (uint32_t)G, g);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
 extern "C" {
+
+int trgl_triangle_depths(trgl_ctx* c, const double* clip, uint64_t n, uint32_t group, int mode, int mem_kind, double* depths_out) {
+    const std::string w = "trgl_triangle_depths: ";
+    if (mode != TRGL_TRI_DEPTH_CENTROID && mode != TRGL_TRI_DEPTH_NEAREST && mode != TRGL_TRI_DEPTH_FARTHEST) return fail(c, TRGL_E_INVALID, w + "bad mode");
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, w + "TRGL_MEM_DEVICE needs a context");
+    if (int r = check_groups(c, w, n, group)) return r;
+    if (n == 0) return TRGL_OK;
+    if (!clip || !depths_out) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (mem_kind == TRGL_MEM_HOST) { host_triangle_depths(clip, n / group, group, mode, depths_out); return TRGL_OK; }
+    CHKCTX(c);
+    if (((uintptr_t)clip | (uintptr_t)depths_out) & 7) return fail(c, TRGL_E_INVALID, w + "device arrays must be 8-byte aligned");
+    launch_triangle_depths(c->stream, clip, (uint32_t)(n / group), group, mode, depths_out);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_order_stage(trgl_ctx* c, int K, const double* clip, const double* vary, const uint32_t* colors, uint64_t n,
+                     const uint32_t* order, uint64_t n_order, uint32_t group, int mem_kind,
+                     double* clip_out, double* vary_out, uint32_t* colors_out) {
+    const std::string w = "trgl_order_stage: ";
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, w + "TRGL_MEM_DEVICE needs a context");
+    if (K < 0 || K > TRGL_MAX_USER_VARY) return fail(c, TRGL_E_INVALID, w + "K outside 0..TRGL_MAX_USER_VARY");
+    int r;
+    if ((r = check_groups(c, w, n, group))) return r;
+    if (!order && n_order) return fail(c, TRGL_E_INVALID, w + "order is null");
+    if ((r = check_order_list(c, w, order, n_order, group, n / group, false))) return r;
+    if (n_order == 0) return TRGL_OK;
+    if (!clip_out || (K && !vary_out) || (colors && !colors_out)) return fail(c, TRGL_E_INVALID, w + "null output");
+    if (n && (!clip || (K && !vary))) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (mem_kind == TRGL_MEM_HOST) {
+        if ((r = check_order_list(c, w, order, n_order, group, n / group, true))) return r;
+        host_order_stage(K, clip, vary, colors, order, n_order, group, clip_out, vary_out, colors_out);
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    if (!order_rows_aligned(clip, K ? vary : nullptr, colors) || !order_rows_aligned(clip_out, K ? vary_out : nullptr, colors ? colors_out : nullptr) ||
+        ((uintptr_t)order & 3))
+        return fail(c, TRGL_E_INVALID, w + "device arrays need natural alignment (8 bytes for doubles, 4 for colours and the list)");
+    return queue_order_stage(c, K, clip, K ? vary : nullptr, colors, n / group, order, n_order, group, clip_out, vary_out, colors_out);
+}
+
+int trgl_draw_ordered(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* clip, const double* vary, const uint32_t* colors, uint64_t n,
+                      int mem_kind, const uint32_t* order, uint64_t n_order, uint32_t group, int order_mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_draw_ordered: ";
+    if (!valid_mem_kind(order_mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad order_mem_kind");
+    if ((order == nullptr) != (n_order == 0)) return fail(c, TRGL_E_INVALID, w + "order must be null exactly when n_order is 0");
+    if (!order) return trgl_draw(c, kind, u, clip, vary, colors, n, mem_kind);
+    // (what trgl_draw would refuse is refused before anything is queued)
+    const int K = kind_vary_count(c, kind);
+    if (K < 0) return fail(c, TRGL_E_INVALID, w + "unknown shader kind");
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if ((r = check_groups(c, w, n, group))) return r;
+    if (n && !clip) return fail(c, TRGL_E_INVALID, w + "clip is null");
+    if (n && K && !vary) return fail(c, TRGL_E_INVALID, w + "this shader kind needs varyings");
+    if ((r = check_kind_uniforms(c, "trgl_draw_ordered", kind, u))) return r;
+    const uint64_t G = n / group, rows = n_order * group;
+    const bool host_rows = mem_kind == TRGL_MEM_HOST, host_list = order_mem_kind == TRGL_MEM_HOST;
+    if ((r = check_order_list(c, w, order, n_order, group, G, host_list))) return r;
+    if (!K) vary = nullptr;
+    if (host_rows && host_list) {
+        try {
+            std::vector<double> oclip(rows * 12), ovary(rows * (size_t)K);
+            std::vector<uint32_t> ocol(colors ? rows : 0);
+            host_order_stage(K, clip, vary, colors, order, n_order, group, oclip.data(), ovary.data(), ocol.data());
+            return trgl_draw(c, kind, u, oclip.data(), K ? ovary.data() : nullptr, colors ? ocol.data() : nullptr, rows, TRGL_MEM_HOST);
+        } catch (const std::bad_alloc&) {
+            return fail(c, TRGL_E_NOMEM, w + "out of memory");
+        }
+    }
+    if ((!host_rows && !order_rows_aligned(clip, vary, colors)) || (!host_list && ((uintptr_t)order & 3)))
+        return fail(c, TRGL_E_INVALID, w + "device arrays need natural alignment (8 bytes for doubles, 4 for colours and the list)");
+    StageHold hold(c);
+    void* p = nullptr;
+    if (host_rows && n) {
+        if ((r = stage_copy(c, clip, n * 12 * sizeof(double), &p))) return r;
+        clip = (const double*)p;
+        if (K) { if ((r = stage_copy(c, vary, n * (size_t)K * sizeof(double), &p))) return r; vary = (const double*)p; }
+        if (colors) { if ((r = stage_copy(c, colors, n * sizeof(uint32_t), &p))) return r; colors = (const uint32_t*)p; }
+    }
+    if (host_list) { if ((r = stage_copy(c, order, n_order * sizeof(uint32_t), &p))) return r; order = (const uint32_t*)p; }
+    double* oclip = nullptr; double* ovary = nullptr; uint32_t* ocol = nullptr;
+    if ((r = stage_alloc(c, rows * 12 * sizeof(double), &p))) return r;
+    oclip = (double*)p;
+    if (K) { if ((r = stage_alloc(c, rows * (size_t)K * sizeof(double), &p))) return r; ovary = (double*)p; }
+    if (colors) { if ((r = stage_alloc(c, rows * sizeof(uint32_t), &p))) return r; ocol = (uint32_t*)p; }
+    if ((r = queue_order_stage(c, K, clip, vary, colors, G, order, n_order, group, oclip, ovary, ocol))) return r;
+    return trgl_draw(c, kind, u, oclip, ovary, ocol, rows, TRGL_MEM_DEVICE);
+}
 
 int trgl_draw_instanced(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16],
                         const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,

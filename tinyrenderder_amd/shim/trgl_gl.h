@@ -593,6 +593,53 @@ inline bool gl_draw_instanced_ordered(const IShader& shader, const double* verti
                                      instances.codes, TRGL_MEM_DEVICE, framebuffer, order, n_order, TRGL_MEM_DEVICE);
 }
 
+// Depth-ordered triangle draws (include/trgl.h, trgl_triangle_depths / trgl_draw_ordered): what a caller of the reference does by
+// sorting the triangles of a translucent mesh on the host before its rasterize() loop.
+// gl_triangle_depths: one depth per group of `group` consecutive triangles, from the clip w of the group's vertices (mode: one of
+// TRGL_TRI_DEPTH_*), ascending the way gl_depth_order expects: pass the result to it as it is.  Runs on the host and needs no context;
+// a call that fails (gl_last_error()) answers zeros.
+inline std::vector<double> gl_triangle_depths(const Triangle* clip, std::size_t n, std::uint32_t group = 1, int mode = TRGL_TRI_DEPTH_CENTROID) {
+    static_assert(sizeof(Triangle) == 12 * sizeof(double), "Triangle must be 12 packed doubles");
+    std::vector<double> depths(group ? n / group : 0, 0.0);
+    const int rc = trgl_triangle_depths(nullptr, reinterpret_cast<const double*>(clip), n, group, mode, TRGL_MEM_HOST, depths.data());
+    if (rc != TRGL_OK) trgl_shim::fail("gl_triangle_depths", rc, nullptr);
+    return depths;
+}
+// gl_draw_ordered: `for p in order: for t in 0 .. group-1: rasterize(clip[order[p] * group + t], shader, framebuffer)` over the n triangles
+// at clip (each the Triangle memory image, our_gl.h:55), in one call.  The
+// shader's describe() is taken once: every triangle gets its kind, uniforms, colour and varyings.  A group named twice is drawn twice,
+// one that is not named is not drawn; an entry that is no group fails the call (TRGL_E_INVALID).  A set clip plane is
+// TRGL_E_UNSUPPORTED: ordered draws are not clipped.
+inline bool gl_draw_ordered(const Triangle* clip, std::size_t n, const IShader& shader, const std::vector<std::uint32_t>& order,
+                            TGAImage& framebuffer, std::uint32_t group = 1) {
+    using namespace trgl_shim;
+    State& s = state();
+    if (!bind(framebuffer)) return false;
+    bool ok = submit_batch();                                   // earlier rasterize() calls come first
+    trgl_shader_desc d;
+    if (!shader.describe(d)) {
+        std::fprintf(stderr, "trgl: gl_draw_ordered(): needs a shader with a device descriptor\n");
+        std::abort();
+    }
+    if (s.clip_on) return fail("gl_draw_ordered: a clip plane is set, and ordered draws are not clipped", TRGL_E_UNSUPPORTED, nullptr);
+    if (order.empty()) return ok;                               // (no position to visit: nothing is drawn)
+    const int K = vary_count(d.kind);
+    if (K && !d.varyings) {
+        std::fprintf(stderr, "trgl: gl_draw_ordered(): shader kind %d needs %d doubles of varyings per triangle\n", d.kind, K);
+        std::abort();
+    }
+    std::vector<double> vary;
+    for (std::size_t i = 0; K && i < n; ++i) vary.insert(vary.end(), d.varyings, d.varyings + K);
+    const std::vector<std::uint32_t> colors(n, d.color);
+    double vp[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) vp[4 * r + c] = Viewport[r][c];
+    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) && ok;
+    ok = TRGL_SHIM_OK(trgl_draw_ordered(s.ctx, d.kind, &d.uniforms, reinterpret_cast<const double*>(clip), K ? vary.data() : nullptr, colors.data(), n,
+                                        TRGL_MEM_HOST, order.data(), order.size(), group, TRGL_MEM_HOST)) && ok;
+    s.zbuffer_stale_on_host = true;
+    return ok;
+}
+
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
 // write_tga_file(), main.cpp:743,773).  The depths follow on demand through the `zbuffer` proxy.
 // false: something submitted since the last gl_flush() failed (gl_last_error()); the pixels hold what could be drawn.
