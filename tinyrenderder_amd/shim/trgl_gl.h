@@ -35,6 +35,10 @@
 //     before it is rasterized (include/trgl.h, trgl_clip_stage); gl_clip_plane(nullptr) returns to the reference's behaviour.
 //   * gl_instance_boxes(local, matrices) / gl_frustum_test(frustum, boxes[, codes]) are getWorldAABB and frustum.intersects for a
 //     whole vector of models (trgl_instance_boxes / trgl_frustum_boxes); the codes plug into gl_occlusion_draw and gl_draw_instanced.
+//   * one framebuffer at a time: the frame in HBM is that of the TGAImage last named.  An image of another size or bpp gets a context of
+//     its own - what was pending for the old image is drawn on the old context first, its pixels come back only through gl_flush(old) in
+//     front of the switch, and print_render_stats() counts from zero again; an image of the same size takes the frame over through
+//     gl_flush(A); gl_framebuffer_modified(B); ("One framebuffer at a time").
 //   * errors of the C ABI (out of memory, a flush beyond 2^32 triangle-tile pairs, a HIP error ...) do not end the process: the
 //     call that met one drops its work, gl_flush() / gl_draw_model() / gl_draw_indexed() / gl_postprocess() return false, and
 //     gl_last_error() / gl_last_error_message() tell which (sticky until gl_clear_error()).  Only a programming error - an
@@ -66,6 +70,10 @@
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
+#endif
+// rasterize() hands its batch to the device when it holds this many triangles
+#ifndef TRGL_SHIM_BATCH_TRIS
+#define TRGL_SHIM_BATCH_TRIS (std::size_t(1) << 20)
 #endif
 
 inline mat<4, 4> ModelView = mat<4, 4>::identity();
@@ -184,7 +192,12 @@ inline int device_from_env() { const char* e = std::getenv("TRGL_DEVICE"); retur
 inline bool bind(TGAImage& fb) {
     State& s = state();
     const int fb_bpp = image_bpp(fb);
-    if (s.ctx && (s.w != fb.width() || s.h != fb.height() || s.bpp != fb_bpp)) { trgl_destroy(s.ctx); s.ctx = nullptr; }
+    if (s.ctx && (s.w != fb.width() || s.h != fb.height() || s.bpp != fb_bpp)) {
+        // one framebuffer at a time: what was batched or queued for the old one runs on ITS context, under its own Viewport, and the depths
+        // come to the host copy as the reference's global holds them (the old image's pixels are not fetched: gl_flush(old) does that)
+        (void)static_cast<const trgl_zbuffer_proxy&>(zbuffer).data();
+        trgl_destroy(s.ctx); s.ctx = nullptr;
+    }
     if (!s.ctx) {
         const int rc = trgl_create(device_from_env(), fb.width(), fb.height(), fb_bpp, &s.ctx);
         if (rc != TRGL_OK) { s.ctx = nullptr; return fail("trgl_create", rc, nullptr); }
@@ -390,7 +403,11 @@ inline void gl_zbuffer_modified() {
 }
 inline void gl_framebuffer_modified(TGAImage& fb) {
     trgl_shim::State& s = trgl_shim::state();
-    if (s.ctx) { trgl_shim::submit_batch(); (void)TRGL_SHIM_OK(trgl_write_framebuffer(s.ctx, fb.buffer())); }
+    if (!s.ctx) return;                                         // (the first bind() uploads the image as it is then)
+    // an image of another size or bpp: the context's frame is not its size - bind() makes the context anew from the image's bytes
+    if (s.w != fb.width() || s.h != fb.height() || s.bpp != trgl_shim::image_bpp(fb)) { (void)trgl_shim::bind(fb); return; }
+    trgl_shim::submit_batch();
+    (void)TRGL_SHIM_OK(trgl_write_framebuffer(s.ctx, fb.buffer()));
 }
 
 // Model textures live on the device: TGAImage::buffer() layout, one slot per map (include/trgl.h).
@@ -425,7 +442,7 @@ inline void rasterize(const Triangle& clip, const IShader& shader, TGAImage& fra
     s.clip.insert(s.clip.end(), cp, cp + 12);                   // the Triangle memory image (our_gl.h:55)
     if (K) s.vary.insert(s.vary.end(), d.varyings, d.varyings + K);
     s.colors.push_back(d.color);
-    if (s.clip.size() >= std::size_t(12) << 20) submit_batch();      // bound host memory: 1 Mi triangles per batch
+    if (s.clip.size() >= std::size_t(12) * (TRGL_SHIM_BATCH_TRIS)) submit_batch();   // bound host memory: 1 Mi triangles per batch
 }
 
 // A whole face loop in one call (main.cpp:660-666, 692-698, 715-721):
