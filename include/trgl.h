@@ -827,6 +827,49 @@ int trgl_image_scale(trgl_ctx* ctx, const uint8_t* src, int w, int h, int bpp,
  * would read rows that another rank owns - gather the frame and blur it on one context.  TRGL_E_UNSUPPORTED as for trgl_image_blur. */
 int trgl_framebuffer_blur(trgl_ctx* ctx, int radius);
 
+/* ---- box-filter resolve and frames as textures: supersampling (SSAA) and render-to-texture (RTT) in HBM ---- */
+
+/* New work: the reference samples once per pixel, its TGAImage::scale picks the nearest texel, and its textures come from files, so
+ * nothing here "replaces" a function of it.  The arithmetic is an exact integer box filter over images as above (TGAImage::buffer(),
+ * every channel alike, alpha included, no premultiplication, no gamma).  For a factor f in 1..TRGL_MAX_BOX_FACTOR:
+ *     w2 = w / f, h2 = h / f                                                                     (int division)
+ *     dst(x, y, c) = (sum over j < f, i < f of src(x * f + i, y * f + j, c) + (f * f) / 2) / (f * f)         (unsigned integers)
+ * (f * f) / 2 is an integer division: an exact tie exists only for even f and rounds up.  Source columns >= w2 * f and rows >= h2 * f
+ * have no influence.  f = 1 is the plain copy.  A frame drawn at f W x f H and resolved with f is the W x H frame with f * f samples
+ * a pixel; the same filter puts a finished frame, or any image in device memory, into a texture slot without a byte crossing PCIe. */
+#define TRGL_MAX_BOX_FACTOR 16   /* the largest factor whose sum (256 * 255 = 65280) fits 16 bits: the kernel keeps packed 16-bit partial sums */
+
+/* The box filter of `src` (w x h) into `dst` ((w / factor) x (h / factor)), which must not overlap.  Memory kinds as for
+ * trgl_image_scale: TRGL_MEM_HOST is plain C++, ctx may be NULL, no GPU is touched; TRGL_MEM_DEVICE is queued on the context's stream,
+ * nothing is flushed and the call does not wait; device pointers need no alignment at all, and no byte outside dst is written.
+ * TRGL_E_INVALID: factor outside 1..TRGL_MAX_BOX_FACTOR, w / factor == 0 or h / factor == 0, bpp not in {1, 3, 4}, a null pointer,
+ * overlapping images, a bad mem_kind, TRGL_MEM_DEVICE without a context.  TRGL_E_UNSUPPORTED: w * h * bpp > INT_MAX. */
+int trgl_image_downsample(trgl_ctx* ctx, const uint8_t* src, int w, int h, int bpp, int factor, uint8_t* dst, int mem_kind);
+
+/* The SSAA resolve: completes a begun flush, flushes what is queued (a pending trgl_clear included), as trgl_framebuffer_blur does,
+ * then filters the resident W x H frame into `dst`, (W / factor) x (H / factor) x bpp bytes.  TRGL_MEM_DEVICE: queued on the context's
+ * stream, the call does not wait.  TRGL_MEM_HOST: filtered into scratch memory of the context, copied out, and the call waits - only the
+ * small image crosses PCIe; with factor 1 these are the bytes of trgl_read_framebuffer.  The frame, the z-buffer and the counters stay
+ * as they were.  TRGL_E_STATE on a context with a strip or interleaved bands set, as for trgl_framebuffer_blur; TRGL_E_INVALID for a
+ * factor outside 1..TRGL_MAX_BOX_FACTOR or above W or H, a null dst, a device dst inside the frame, a bad mem_kind;
+ * TRGL_E_UNSUPPORTED: W * H * bpp > INT_MAX. */
+int trgl_framebuffer_resolve(trgl_ctx* ctx, int factor, uint8_t* dst, int mem_kind);
+
+/* Render-to-texture: the filtered image becomes the texture of `slot` (0..TRGL_MAX_TEXTURES-1), as if trgl_upload_texture had been
+ * given it.  trgl_texture_from_framebuffer takes the resident frame, trgl_texture_from_image an image in host or device memory.
+ * Ordering as for trgl_upload_texture: the call completes a begun flush and flushes queued draws, so draws submitted earlier sample what
+ * the slot held before and draws submitted later the new texture.  The texture is a snapshot: later clears, draws or blurs of the frame
+ * do not change it, and a frame may be captured into a slot that the draws of that very frame sampled.
+ * With the resident frame or device memory as the source the call does not wait for the device when the slot is empty or holds a
+ * texture of the same w / factor, h / factor and bpp, whichever call made it: the slot's memory is then reused (one kernel per capture);
+ * an empty slot is entered into the context's texture table in stream order.  A slot that holds another size is released first, and
+ * the call waits for the stream before that.  trgl_upload_texture works on slots these calls filled, and they on slots it filled.
+ * trgl_texture_from_image with TRGL_MEM_HOST is trgl_upload_texture of the host-filtered image.
+ * TRGL_E_INVALID: slot out of range, and the cases of trgl_image_downsample (for the frame: factor above W or H); TRGL_E_STATE:
+ * trgl_texture_from_framebuffer on a context with a strip or interleaved bands set; TRGL_E_UNSUPPORTED: w * h * bpp > INT_MAX. */
+int trgl_texture_from_image(trgl_ctx* ctx, int slot, const uint8_t* src, int w, int h, int bpp, int factor, int mem_kind);
+int trgl_texture_from_framebuffer(trgl_ctx* ctx, int slot, int factor);
+
 /* ---- shadow mapping as a post-pass: a mask from the light's depths, multiplied into an image -------------- */
 
 /* New work: the reference has no shadows, so nothing here "replaces" a function of it.  The arithmetic is borrowed from the lines named

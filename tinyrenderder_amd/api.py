@@ -62,6 +62,7 @@ SYMBOLS = [
     "trgl_zbuffer_snapshot", "trgl_zbuffer_restore", "trgl_zbuffer_snapshot_free",
     "trgl_mesh_normals", "trgl_mesh_tangents",
     "trgl_gaussian_kernel", "trgl_image_blur", "trgl_image_scale", "trgl_framebuffer_blur",
+    "trgl_image_downsample", "trgl_framebuffer_resolve", "trgl_texture_from_image", "trgl_texture_from_framebuffer",
     "trgl_shadow_matrix", "trgl_shadow_mask_image", "trgl_shadow_mask", "trgl_image_modulate", "trgl_framebuffer_modulate",
     "trgl_clip_layout", "trgl_clip_stage", "trgl_draw_clipped", "trgl_draw_indexed_vs_clipped",
     "trgl_occlusion_boxes_image", "trgl_occlusion_boxes",
@@ -245,6 +246,10 @@ def load_library(path: str = None):
     L.trgl_image_blur.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.trgl_image_scale.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.trgl_framebuffer_blur.argtypes = [vp, C.c_int]
+    L.trgl_image_downsample.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.trgl_framebuffer_resolve.argtypes = [vp, C.c_int, C.c_void_p, C.c_int]
+    L.trgl_texture_from_image.argtypes = [vp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.trgl_texture_from_framebuffer.argtypes = [vp, C.c_int, C.c_int]
     L.trgl_shadow_matrix.argtypes = [dp, dp, dp, dp, dp, dp, dp]
     L.trgl_shadow_mask_image.argtypes = [vp, C.POINTER(ShadowParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     L.trgl_shadow_mask.argtypes = [vp, C.POINTER(ShadowParams), C.c_int, C.c_void_p, C.c_int]
@@ -452,6 +457,31 @@ def _image_scale(L, handle, sptr, img, dptr, w2, h2, device):
         raise TrglError(f"trgl_image_scale failed ({rc}): {L.trgl_last_error(handle).decode()}")
 
 
+def _image_downsample(L, handle, sptr, img, factor, dptr, device):
+    h, w, bpp = _image_dims(img, "image_downsample")
+    rc = L.trgl_image_downsample(handle, sptr, w, h, bpp, int(factor), dptr, MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_image_downsample failed ({rc}): {L.trgl_last_error(handle).decode()}")
+
+
+def _box_shape(img, factor):
+    """[h2, w2, bpp] of the box filter's result; zeros where the library will refuse the factor."""
+    f = int(factor)
+    ok = len(img.shape) == 3 and f >= 1
+    return (int(img.shape[0]) // f if ok else 0, int(img.shape[1]) // f if ok else 0, int(img.shape[2]) if len(img.shape) == 3 else 0)
+
+
+def _host_image_downsample(L, handle, img, factor, out=None):
+    src = np.ascontiguousarray(img, np.uint8)
+    shape = _box_shape(src, factor)
+    if out is None:
+        out = np.empty(shape, np.uint8)
+    elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.shape != shape:
+        raise ValueError("image_downsample: out must be a contiguous uint8 array [h // factor, w // factor, bpp]")
+    _image_downsample(L, handle, src.ctypes.data, src, factor, out.ctypes.data, False)
+    return out
+
+
 def _device_image(img, what):
     """The address of a device image: a contiguous uint8 CUDA tensor (its shape says w, h and bpp, so a bare pointer will not do)."""
     if not hasattr(img, "data_ptr"):
@@ -476,6 +506,13 @@ def image_scale(img, w2: int, h2: int) -> np.ndarray:
     out = np.empty((max(int(h2), 0), max(int(w2), 0), src.shape[2] if len(src.shape) == 3 else 0), np.uint8)
     _image_scale(load_library(), None, src.ctypes.data, src, out.ctypes.data, w2, h2, False)
     return out
+
+
+def image_downsample(img, factor: int) -> np.ndarray:
+    """trgl_image_downsample for a host array without a context: the exact box filter (new work, include/trgl.h) of img [h, w, bpp] uint8
+    into a new [h // factor, w // factor, bpp] array: (sum of factor x factor bytes + factor * factor // 2) // (factor * factor) per
+    channel.  Raises for a factor outside 1..16 or above w or h.  Needs no GPU."""
+    return _host_image_downsample(load_library(), None, img, factor)
 
 
 def shadow_matrix(light_mv, light_proj, light_vp, cam_mv, cam_proj, cam_vp) -> np.ndarray:
@@ -1389,6 +1426,70 @@ class Context:
         self._keep.append((img, out))
         _image_scale(self.L, self.h, sptr, img, _device_image(out, "out"), w2, h2, True)
         return out
+
+    def image_downsample(self, img, factor, device=False, out=None):
+        """trgl_image_downsample: the exact box filter of img [h, w, bpp] into [h // factor, w // factor, bpp]; returns the result.
+        Host array: no GPU work.  device=True: contiguous uint8 device tensors at any address, filtered on the context's stream (nothing is
+        flushed, the call does not wait); `out` (must not overlap img) is allocated with torch when not given; both are kept alive until
+        the next sync."""
+        if not device:
+            return _host_image_downsample(self.L, self.h, img, factor, out)
+        sptr = _device_image(img, "img")
+        shape = _box_shape(img, factor)
+        if out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device=img.device)
+        elif tuple(out.shape) != shape:
+            raise ValueError("image_downsample: out must be [h // factor, w // factor, bpp]")
+        self._keep.append((img, out))
+        _image_downsample(self.L, self.h, sptr, img, factor, _device_image(out, "out"), True)
+        return out
+
+    def framebuffer_resolve(self, factor, device=False, out=None):
+        """trgl_framebuffer_resolve: the SSAA resolve - flushes what is queued (a pending clear included), then box-filters the resident
+        frame into [H // factor, W // factor, bpp]; the frame, the z-buffer and the stats stay as they are.  device=False: a numpy array,
+        the call waits for the small image.  device=True: a uint8 tensor on the context's device (allocated with torch when `out` is
+        not given), queued without waiting and kept alive until the next sync.  Not on a strip / band context."""
+        f = int(factor)
+        shape = (self.height // f if f >= 1 else 0, self.width // f if f >= 1 else 0, self.bpp)
+        if not device:
+            if out is None:
+                out = np.empty(shape, np.uint8)
+            elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.shape != shape:
+                raise ValueError("framebuffer_resolve: out must be a contiguous uint8 array [H // factor, W // factor, bpp]")
+            self._chk(self.L.trgl_framebuffer_resolve(self.h, f, out.ctypes.data, MEM_HOST))
+            return out
+        if out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device}")
+        elif tuple(out.shape) != shape:
+            raise ValueError("framebuffer_resolve: out must be [H // factor, W // factor, bpp]")
+        ptr = _device_image(out, "out")
+        self._keep.append((out,))
+        self._chk(self.L.trgl_framebuffer_resolve(self.h, f, ptr, MEM_DEVICE))
+        return out
+
+    def texture_from_image(self, slot, img, factor=1, device=False):
+        """trgl_texture_from_image: the box filter of img [h, w, bpp] (a [h, w] image counts as bpp 1) becomes the texture of `slot`, ordered
+        like upload_texture: draws submitted earlier sample the old texture.  device=True: a contiguous uint8 device tensor, filtered in
+        HBM without a host wait when the slot is empty or holds a texture of the same size; kept alive until the next sync."""
+        if not device:
+            t = np.ascontiguousarray(img, np.uint8)
+            if t.ndim == 2:
+                t = t[..., None]
+            h, w, bpp = _image_dims(t, "texture_from_image")
+            self._chk(self.L.trgl_texture_from_image(self.h, int(slot), t.ctypes.data, w, h, bpp, int(factor), MEM_HOST))
+            return
+        ptr = _device_image(img, "img")
+        h, w, bpp = _image_dims(img, "texture_from_image")
+        self._keep.append((img,))
+        self._chk(self.L.trgl_texture_from_image(self.h, int(slot), ptr, w, h, bpp, int(factor), MEM_DEVICE))
+
+    def texture_from_framebuffer(self, slot, factor=1):
+        """trgl_texture_from_framebuffer: render-to-texture - flushes what is queued, then the box filter of the resident frame becomes the
+        texture of `slot` [H // factor, W // factor, bpp], a snapshot that later clears and draws do not change.  No host wait when the
+        slot is empty or holds a texture of that size.  Not on a strip / band context."""
+        self._chk(self.L.trgl_texture_from_framebuffer(self.h, int(slot), int(factor)))
 
     def framebuffer_blur(self, radius):
         """trgl_framebuffer_blur: framebuffer.gaussian_blur(radius) on the resident frame (flushes what is queued, does not wait); the

@@ -116,6 +116,11 @@ void launch_image_blur(hipStream_t s, uint8_t* pixels, int w, int h, int bpp, in
 // (w2 - 1) * w, (h2 - 1) * h and both byte counts fit an int.
 constexpr int SCALE_BYTES = 256, SCALE_ROWS = 8;             // tile: bytes of an output row (one per thread) x output rows
 void launch_image_scale(hipStream_t s, const uint8_t* src, int w, int h, int bpp, uint8_t* dst, int w2, int h2);
+// The box filter of box_core.h (kernels_resolve.hip): dst (w / f) x (h / f) from src w x h, both bpp bytes a pixel, at any address, not
+// overlapping.  f in 1..TRGL_MAX_BOX_FACTOR with w / f, h / f >= 1, w * h * bpp <= INT_MAX.  f = 1 is queued as a device-to-device copy.
+hipError_t launch_box_filter(hipStream_t s, const uint8_t* src, int w, int h, int bpp, int f, uint8_t* dst);
+// table[slot] = t by a one-thread kernel: an update of the context's texture table that keeps its place in the stream
+hipError_t launch_set_texture(hipStream_t s, DevTexture* table, int slot, const DevTexture& t);
 
 // The shadow post-pass (kernels_shadow.hip; the arithmetic is written down at trgl_shadow_mask_image in include/trgl.h).
 // depth: w * h depths, map: map_w * map_h depths of the light's view, both 8-byte aligned (16-byte aligned arrays are read as 16-byte

@@ -87,6 +87,7 @@ struct trgl_ctx {
     DevBuf<float> blur_weights; DevBuf<uint8_t> blur_tmp; int blur_radius = 0;
     float* blur_w_pinned = nullptr; size_t blur_w_pinned_cap = 0; hipEvent_t ev_blur_w = nullptr;
     DevBuf<uint32_t> clip_scratch;      // trgl_clip_stage and the clipped draws: the 8-byte count of outputs, then the words of the stage's scan; grows on demand
+    DevBuf<uint8_t> resolve_tmp;        // trgl_framebuffer_resolve with a host dst: the filtered image on its way out; grows on demand
     DevBuf<uint8_t> shadow_tmp;         // trgl_shadow_mask / trgl_framebuffer_modulate with a host mask: the W * H bytes on their way; grows on demand
     // trgl_occlusion_boxes(_image): the two levels of block maxima over the depths, rebuilt by every call; host boxes and the codes for a
     // host array on their way; grow on demand
@@ -199,4 +200,6 @@ void host_order_stage(int K, const double* clip, const double* vary, const uint3
 // trgl_instance_boxes and trgl_frustum_boxes over host arrays (local_stride 0: one local box for every instance)
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out);
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);
+// the box filter of box_core.h over host images: dst (w / f) x (h / f) from src w x h; f in 1..TRGL_MAX_BOX_FACTOR, w / f and h / f >= 1
+void host_box_filter(const uint8_t* src, int w, int h, int bpp, int f, uint8_t* dst);
 }  // namespace trgl

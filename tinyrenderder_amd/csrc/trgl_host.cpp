@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/trgl.h"
+#include "box_core.h"
 #include "clip_core.h"
 #include "occlusion_core.h"
 #include "scene_core.h"
@@ -24,6 +25,24 @@ static thread_local std::string g_error;
 void set_global_error(const std::string& msg) { g_error = msg; }
 const char* global_error() { return g_error.c_str(); }
 int fail(trgl_ctx* c, int code, const std::string& msg);       // trgl_api.cpp; called with c == nullptr here
+
+// ---- the box filter (include/trgl.h, trgl_image_downsample; box_core.h) ------------------------------------------------------------
+void host_box_filter(const uint8_t* src, int w, int h, int bpp, int f, uint8_t* dst) {
+    const int w2 = w / f, h2 = h / f;
+    const size_t row = (size_t)w * bpp;
+    if (f == 1) { std::memcpy(dst, src, row * h); return; }
+    const uint32_t half = (uint32_t)(f * f) / 2, magic = box_magic(f);
+    for (int y = 0; y < h2; ++y)
+        for (int x = 0; x < w2; ++x)
+            for (int c = 0; c < bpp; ++c) {
+                uint32_t sum = 0;
+                for (int j = 0; j < f; ++j) {
+                    const uint8_t* p = src + ((size_t)y * f + j) * row + (size_t)x * f * bpp + c;
+                    for (int i = 0; i < f; ++i) sum += p[(size_t)i * bpp];
+                }
+                *dst++ = (uint8_t)box_round(sum, half, magic);
+            }
+}
 
 // ---- scene logic around the draws (model.cpp:15-40, geometry.h:264-266,297-327, our_gl.cpp:212-280) ------------------------------
 // keep_min / keep_max (the running std::min / std::max) and dot3_from_zero, AABB::transform and Frustum::intersects: scene_core.h

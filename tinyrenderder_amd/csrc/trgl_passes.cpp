@@ -1,5 +1,5 @@
 // trgl_passes.cpp — the optional passes of include/trgl.h over finished frames and over caller-owned images and meshes: SSAO post-process,
-// z-buffer snapshots, blur and scale, the shadow mask and modulate, occlusion culling of boxes, world boxes and frustum codes of instances, mesh bounds and attributes in device memory, the two self-tests.
+// z-buffer snapshots, blur and scale, the box-filter resolve and textures from frames, the shadow mask and modulate, occlusion culling of boxes, world boxes and frustum codes of instances, mesh bounds and attributes in device memory, the two self-tests.
 // None of them knows the flush pipeline of trgl_api.cpp: each finishes what is pending (end_pending_raster, trgl_flush, flush_sync), then
 // launches on the context's stream.  With TRGL_MEM_HOST the work is done by the host loops (trgl_host.cpp, shim/trgl_image.h).
 #include <climits>
@@ -42,6 +42,55 @@ static int queue_blur(trgl_ctx* c, uint8_t* pixels, int w, int h, int bpp, int r
     if ((r = c->blur_tmp.grow(c, nbytes))) return r;
     launch_image_blur(c->stream, pixels, w, h, bpp, radius, c->blur_weights.p, c->blur_tmp.p);
     HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+// ---- box-filter resolve and frames as textures (include/trgl.h; host loop in trgl_host.cpp, kernel in kernels_resolve.hip) ------------
+// what trgl_image_downsample checks of an image and a factor, for every call that filters (mem_kind, the pointers and overlap: the caller)
+static int check_box(trgl_ctx* c, const std::string& who, int w, int h, int bpp, int factor) {
+    if (!(bpp == 1 || bpp == 3 || bpp == 4)) return fail(c, TRGL_E_INVALID, who + ": bpp must be 1, 3 or 4");
+    if (factor < 1 || factor > TRGL_MAX_BOX_FACTOR) return fail(c, TRGL_E_INVALID, who + ": factor must be 1.." + std::to_string(TRGL_MAX_BOX_FACTOR));
+    if (w < factor || h < factor) return fail(c, TRGL_E_INVALID, who + ": w / factor or h / factor is 0");
+    if ((int64_t)w * h * bpp > INT_MAX) return fail(c, TRGL_E_UNSUPPORTED, who + ": w * h * bpp above INT_MAX");
+    return TRGL_OK;
+}
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+static int texture_slot(trgl_ctx* c, int slot, const char* who) {
+    if (slot >= 0 && slot < TRGL_MAX_TEXTURES) return TRGL_OK;
+    return fail(c, TRGL_E_INVALID, std::string(who) + ": slot must be 0.." + std::to_string(TRGL_MAX_TEXTURES - 1));
+}
+
+// The box filter of a device image (the resident frame or a caller's) into texture `slot`, all of it in stream order.  A slot that holds
+// a texture of the result's size keeps its memory and its entry in tex_dev; an empty slot gets memory by the sampler's rule (bytes + 8,
+// the tail zeroed: the samplers read each texel as one 4-byte load) and enters the table through a kernel on the stream - never a host
+// write that races a running flush; a slot of another size is released first, behind a wait for the stream.
+static int texture_from_device(trgl_ctx* c, const std::string& who, int slot, const uint8_t* src, int w, int h, int bpp, int factor) {
+    const int w2 = w / factor, h2 = h / factor;
+    const size_t bytes = (size_t)w2 * h2 * bpp;
+    DevTexture& t = c->tex_host[slot];
+    const bool reuse = t.data && t.w == w2 && t.h == h2 && t.bpp == bpp;
+    if (reuse && ranges_overlap(src, (size_t)w * h * bpp, t.data, bytes)) return fail(c, TRGL_E_INVALID, who + ": the source is the slot's own texture");
+    int r = end_pending_raster(c); if (r) return r;
+    if ((r = trgl_flush(c))) return r;                // draws submitted earlier sample what the slot held; a pending clear reaches the frame
+    if (!reuse) {
+        if (t.data) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipFree((void*)t.data));
+            t = DevTexture{ nullptr, 0, 0, 0, 0 };
+        }
+        uint8_t* d = nullptr;
+        if (hipMalloc((void**)&d, bytes + 8) != hipSuccess) {
+            (void)hipGetLastError();
+            HIPCHK(c, launch_set_texture(c->stream, c->tex_dev.p, slot, t));
+            return fail(c, TRGL_E_NOMEM, who + ": out of device memory");
+        }
+        t = DevTexture{ d, w2, h2, bpp, 0 };
+        HIPCHK(c, hipMemsetAsync(d + bytes, 0, 8, c->stream));
+        HIPCHK(c, launch_set_texture(c->stream, c->tex_dev.p, slot, t));
+    }
+    HIPCHK(c, launch_box_filter(c->stream, src, w, h, bpp, factor, const_cast<uint8_t*>(t.data)));
     return TRGL_OK;
 }
 
@@ -264,6 +313,69 @@ int trgl_framebuffer_blur(trgl_ctx* c, int radius) {
     if ((int64_t)c->W * c->H * c->bpp > INT_MAX) return fail(c, TRGL_E_UNSUPPORTED, "trgl_framebuffer_blur: W * H * bpp above INT_MAX (the reference's int byte index overflows)");
     int r = trgl_flush(c); if (r) return r;          // completes a begun flush, draws what is queued, runs a pending clear
     return queue_blur(c, c->fb.p, c->W, c->H, c->bpp, radius, (size_t)c->W * c->H * c->bpp);
+}
+
+int trgl_image_downsample(trgl_ctx* c, const uint8_t* src, int w, int h, int bpp, int factor, uint8_t* dst, int mem_kind) {
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_image_downsample: bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_image_downsample: TRGL_MEM_DEVICE needs a context");
+    if (int r = check_box(c, "trgl_image_downsample", w, h, bpp, factor)) return r;
+    if (!src || !dst) return fail(c, TRGL_E_INVALID, "trgl_image_downsample: null image");
+    if (ranges_overlap(src, (size_t)w * h * bpp, dst, (size_t)(w / factor) * (h / factor) * bpp))
+        return fail(c, TRGL_E_INVALID, "trgl_image_downsample: src and dst overlap");
+    if (mem_kind == TRGL_MEM_HOST) { host_box_filter(src, w, h, bpp, factor, dst); return TRGL_OK; }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    HIPCHK(c, launch_box_filter(c->stream, src, w, h, bpp, factor, dst));
+    return TRGL_OK;
+}
+
+int trgl_framebuffer_resolve(trgl_ctx* c, int factor, uint8_t* dst, int mem_kind) {
+    CHKCTX(c);
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_framebuffer_resolve: bad mem_kind");
+    if (!owns_whole_frame(c))
+        return fail(c, TRGL_E_STATE, "trgl_framebuffer_resolve: the context owns a strip or interleaved bands; its frame holds only this rank's rows (gather the frame and resolve it on one context)");
+    int r = check_box(c, "trgl_framebuffer_resolve", c->W, c->H, c->bpp, factor); if (r) return r;
+    if (!dst) return fail(c, TRGL_E_INVALID, "trgl_framebuffer_resolve: dst is null");
+    const size_t nsrc = (size_t)c->W * c->H * c->bpp, ndst = (size_t)(c->W / factor) * (c->H / factor) * c->bpp;
+    if (mem_kind == TRGL_MEM_DEVICE && ranges_overlap(c->fb.p, nsrc, dst, ndst)) return fail(c, TRGL_E_INVALID, "trgl_framebuffer_resolve: dst lies inside the frame");
+    if ((r = trgl_flush(c))) return r;                // completes a begun flush, draws what is queued, runs a pending clear
+    if (mem_kind == TRGL_MEM_HOST && factor == 1) {   // the bytes of trgl_read_framebuffer
+        HIPCHK(c, hipMemcpyAsync(dst, c->fb.p, nsrc, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return TRGL_OK;
+    }
+    uint8_t* d_dst = dst;
+    if (mem_kind == TRGL_MEM_HOST) { if ((r = c->resolve_tmp.grow(c, ndst))) return r; d_dst = c->resolve_tmp.p; }
+    HIPCHK(c, launch_box_filter(c->stream, c->fb.p, c->W, c->H, c->bpp, factor, d_dst));
+    if (mem_kind == TRGL_MEM_HOST) {
+        HIPCHK(c, hipMemcpyAsync(dst, d_dst, ndst, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return TRGL_OK;
+}
+
+int trgl_texture_from_image(trgl_ctx* c, int slot, const uint8_t* src, int w, int h, int bpp, int factor, int mem_kind) {
+    CHKCTX(c);
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_texture_from_image: bad mem_kind");
+    int r = texture_slot(c, slot, "trgl_texture_from_image"); if (r) return r;
+    if ((r = check_box(c, "trgl_texture_from_image", w, h, bpp, factor))) return r;
+    if (!src) return fail(c, TRGL_E_INVALID, "trgl_texture_from_image: src is null");
+    if (mem_kind == TRGL_MEM_DEVICE) return texture_from_device(c, "trgl_texture_from_image", slot, src, w, h, bpp, factor);
+    if (factor == 1) return trgl_upload_texture(c, slot, src, w, h, bpp);
+    try {
+        std::vector<uint8_t> tmp((size_t)(w / factor) * (h / factor) * bpp);
+        host_box_filter(src, w, h, bpp, factor, tmp.data());
+        return trgl_upload_texture(c, slot, tmp.data(), w / factor, h / factor, bpp);
+    } catch (const std::bad_alloc&) { return fail(c, TRGL_E_NOMEM, "trgl_texture_from_image: out of memory"); }
+}
+
+int trgl_texture_from_framebuffer(trgl_ctx* c, int slot, int factor) {
+    CHKCTX(c);
+    int r = texture_slot(c, slot, "trgl_texture_from_framebuffer"); if (r) return r;
+    if (!owns_whole_frame(c))
+        return fail(c, TRGL_E_STATE, "trgl_texture_from_framebuffer: the context owns a strip or interleaved bands; its frame holds only this rank's rows (gather the frame and capture it on one context)");
+    if ((r = check_box(c, "trgl_texture_from_framebuffer", c->W, c->H, c->bpp, factor))) return r;
+    return texture_from_device(c, "trgl_texture_from_framebuffer", slot, c->fb.p, c->W, c->H, c->bpp, factor);
 }
 
 int trgl_shadow_mask_image(trgl_ctx* c, const trgl_shadow_params* params, const double* depth, int w, int h,

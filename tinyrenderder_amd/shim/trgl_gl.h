@@ -31,6 +31,9 @@
 //     byte; TGAImage::scale / gaussian_blur themselves are host loops in trgl_image.h, as in the reference.
 //   * shadows (new; the reference has none): gl_shadow_matrix / gl_shadow_mask / gl_modulate turn the depths of a light's view, kept with
 //     gl_zbuffer_snapshot, into a mask and multiply it into the frame in HBM (see below, and include/trgl.h).
+//   * supersampling and render-to-texture (new; the reference has neither): gl_resolve(framebuffer, factor, &out) box-filters the frame
+//     in HBM into a small image, gl_texture_from_framebuffer(framebuffer, slot, factor) makes the filtered frame a texture without
+//     leaving HBM, gl_downsample(image, factor, &out) is the same exact filter on the host (see below, and include/trgl.h).
 //   * clipping (new; the reference has none): gl_clip_plane(&plane) cuts everything drawn from then on against a plane in clip space
 //     before it is rasterized (include/trgl.h, trgl_clip_stage); gl_clip_plane(nullptr) returns to the reference's behaviour.
 //   * gl_instance_boxes(local, matrices) / gl_frustum_test(frustum, boxes[, codes]) are getWorldAABB and frustum.intersects for a
@@ -764,6 +767,45 @@ inline bool gl_gaussian_blur(TGAImage& framebuffer, int radius) {
     if (!bind(framebuffer)) return false;
     const bool ok = submit_batch();
     return TRGL_SHIM_OK(trgl_framebuffer_blur(state().ctx, radius)) && ok;
+}
+
+// Supersampling and render-to-texture (include/trgl.h, "box-filter resolve and frames as textures"; new work - the reference samples once
+// per pixel and its textures come from files).  The filter is exact: (sum of factor x factor bytes + factor * factor / 2) /
+// (factor * factor) per channel, factor in 1..TRGL_MAX_BOX_FACTOR.
+//   gl_resolve                   the frame in HBM - drawn at factor times the wanted size - box-filtered into `out`, which becomes a
+//                                (W / factor) x (H / factor) image of the framebuffer's format (trgl_framebuffer_resolve): triangles batched so
+//                                far are drawn first, only the small image crosses PCIe, the call waits for it.  The frame stays as it is.
+//   gl_texture_from_framebuffer  the same filtered frame becomes the texture of `slot` without leaving HBM and without a wait
+//                                (trgl_texture_from_framebuffer): a snapshot that later draws of any frame of this size sample - a mirror,
+//                                a screen in the scene.  Triangles batched so far are drawn first and are part of it.
+//   gl_downsample                the filter for an image that is not the framebuffer: on the host, no GPU is touched
+inline bool gl_resolve(TGAImage& framebuffer, int factor, TGAImage* out) {
+    using namespace trgl_shim;
+    State& s = state();
+    if (!out) return fail("gl_resolve: out is null", TRGL_E_INVALID, nullptr);
+    if (!bind(framebuffer)) return false;
+    const bool ok = submit_batch();
+    if (factor < 1 || factor > TRGL_MAX_BOX_FACTOR || s.w / factor == 0 || s.h / factor == 0)
+        return fail("gl_resolve: factor must be 1..16 and at most the framebuffer's width and height", TRGL_E_INVALID, nullptr);
+    if (out->width() != s.w / factor || out->height() != s.h / factor || image_bpp(*out) != s.bpp) *out = TGAImage(s.w / factor, s.h / factor, s.bpp);
+    return TRGL_SHIM_OK(trgl_framebuffer_resolve(s.ctx, factor, out->buffer(), TRGL_MEM_HOST)) && ok;
+}
+inline bool gl_texture_from_framebuffer(TGAImage& framebuffer, int slot, int factor = 1) {
+    using namespace trgl_shim;
+    if (!bind(framebuffer)) return false;
+    const bool ok = submit_batch();
+    return TRGL_SHIM_OK(trgl_texture_from_framebuffer(state().ctx, slot, factor)) && ok;
+}
+inline bool gl_downsample(const TGAImage& src, int factor, TGAImage* out) {
+    using namespace trgl_shim;
+    if (!out || out == &src) return fail("gl_downsample: out must be another image", TRGL_E_INVALID, nullptr);
+    const int bpp = image_bpp(src);
+    if (factor < 1 || factor > TRGL_MAX_BOX_FACTOR || src.width() / factor == 0 || src.height() / factor == 0)
+        return fail("gl_downsample: factor must be 1..16 and at most the image's width and height", TRGL_E_INVALID, nullptr);
+    if (out->width() != src.width() / factor || out->height() != src.height() / factor || image_bpp(*out) != bpp)
+        *out = TGAImage(src.width() / factor, src.height() / factor, bpp);
+    const int rc = trgl_image_downsample(nullptr, image_bytes(src), src.width(), src.height(), bpp, factor, out->buffer(), TRGL_MEM_HOST);
+    return rc == TRGL_OK ? true : fail("trgl_image_downsample", rc, nullptr);
 }
 
 // Shadow mapping as a post-pass (include/trgl.h, "shadow mapping as a post-pass"; new work, the reference has none).  Draw the light's
