@@ -870,6 +870,90 @@ int trgl_framebuffer_resolve(trgl_ctx* ctx, int factor, uint8_t* dst, int mem_ki
 int trgl_texture_from_image(trgl_ctx* ctx, int slot, const uint8_t* src, int w, int h, int bpp, int factor, int mem_kind);
 int trgl_texture_from_framebuffer(trgl_ctx* ctx, int slot, int factor);
 
+/* ---- mipmapped textures: chain build, filtered samplers for user shaders, and a level-of-detail stage ---------------- */
+
+/* New work: the reference's only sampler is IShader::sample2D, one nearest texel of the full-size image, and the built-in kinds and
+ * trgl_sample2D keep exactly that.  What follows is for user shaders.  All arithmetic is unsigned integer or IEEE fp64 without
+ * contraction, every written operation rounded once in the written order; the host paths and the device paths give the same bits.
+ *
+ * The chain.  Level 0 is the image itself.  Level l + 1 is w' = max(1, w_l / 2) by h' = max(1, h_l / 2) texels (int division); with
+ * fx = (w_l >= 2) ? 2 : 1 and fy = (h_l >= 2) ? 2 : 1,
+ *     level_{l+1}(x, y, c) = (sum over j < fy, i < fx of level_l(x * fx + i, y * fy + j, c) + (fx * fy) / 2) / (fx * fy)
+ * for every channel alike, alpha included.  Where both sides are >= 2 this is trgl_image_downsample with factor 2; the last column or
+ * row of an odd side has no influence; a side of 1 stays 1.  L = 1 + floor(log2(max(w, h))) levels, at most TRGL_MAX_MIP_LEVELS: a side
+ * above 65535 is TRGL_E_UNSUPPORTED. */
+#define TRGL_MAX_MIP_LEVELS 16
+
+/* Host only: the sizes of all L levels (widths[0] = w) and the byte offsets of levels 1 .. L-1 in a packed buffer of *total bytes:
+ * level 1 at offset 0, every level at the next multiple of 16 behind its predecessor (offsets[0] is 0 and names nothing).  Outputs may
+ * be NULL.  TRGL_E_INVALID: w or h < 1, bpp not in {1, 3, 4}; TRGL_E_UNSUPPORTED: a side above 65535 or w * h * bpp > INT_MAX. */
+int trgl_mip_layout(int w, int h, int bpp, int* levels, int widths[TRGL_MAX_MIP_LEVELS], int heights[TRGL_MAX_MIP_LEVELS],
+                    size_t offsets[TRGL_MAX_MIP_LEVELS], size_t* total);
+
+/* Levels 1 .. L-1 of the image `src` into `dst` in that layout.  Nothing outside the levels' bytes is written: the padding between
+ * levels is not touched.  TRGL_MEM_HOST is plain C++ and ctx may be NULL; TRGL_MEM_DEVICE is queued on the context's stream, nothing is
+ * flushed and nothing waits, and src and dst may have any byte alignment.  src and dst must be disjoint.  With L = 1 nothing is
+ * written and dst may be NULL.  Errors as for trgl_mip_layout, and TRGL_E_INVALID for a null pointer, overlap, a bad mem_kind or
+ * TRGL_MEM_DEVICE without a context. */
+int trgl_image_mipmaps(trgl_ctx* ctx, const uint8_t* src, int w, int h, int bpp, uint8_t* dst, int mem_kind);
+
+/* Builds the chain of the texture in `slot`.  Ordering as for the other texture calls: a begun flush is completed and queued draws are
+ * flushed first, so draws submitted earlier see one level and later draws see L levels.  An empty slot is TRGL_E_STATE.  Every call
+ * that replaces a slot's texels (trgl_upload_texture, trgl_texture_from_image, trgl_texture_from_framebuffer) leaves the slot with one
+ * level until this call is made again.  The levels live behind level 0 in the slot's own allocation, and the context remembers its
+ * capacity: a slot that has held a chain and is captured into again at the same size keeps its memory, and the rebuild is kernels on
+ * the stream without a host wait - a per-frame capture plus mipmaps never synchronises.  Only the first build on a slot without room
+ * waits: it allocates, copies level 0 device to device, and releases the old memory behind a wait for the stream. */
+int trgl_texture_mipmaps(trgl_ctx* ctx, int slot);
+
+/* What a user shader's source sees on top of trgl_sample2D (user_prelude.h; every function returns trgl_texel with the channels at and
+ * above bytespp 0; an empty slot samples as opaque white with bytespp 4; a texture without a chain has L = 1 and every function works):
+ *   int trgl_texture_levels(in, slot, int* w, int* h)        L and the size of level 0; 0 for an empty slot
+ *   trgl_sample2D_level(in, slot, uv, int level)              level clamped to 0 .. L-1, then trgl_sample2D's rule on that level:
+ *                                                             clamp(cvttsd2si(uv * size_l), 0, size_l - 1)
+ *   trgl_sample2D_linear(in, slot, uv, int level)             per axis: u = uv[0] * (double)w_l - 0.5; if !(u >= -1.0) u = -1.0 (NaN too);
+ *       if u > (double)w_l u = (double)w_l; fl = floor(u), x0 = (int)fl, fx = (int)((u - fl) * 256.0); xa = clamp(x0, 0, w_l - 1),
+ *       xb = clamp(x0 + 1, 0, w_l - 1); the same for v; per channel
+ *       ((c(xa,ya) * (256 - fx) + c(xb,ya) * fx) * (256 - fy) + (c(xa,yb) * (256 - fx) + c(xb,yb) * fx) * fy + 32768) >> 16
+ *   trgl_sample2D_trilinear(in, slot, uv, double lod)         lam = lod; if !(lam > 0.0) lam = 0.0; if lam > (double)(L - 1) lam = L - 1;
+ *       l0 = (int)lam, t = (int)((lam - (double)l0) * 256.0), l1 = min(l0 + 1, L - 1); a = the linear sample at l0; if t == 0 return a;
+ *       b = the linear sample at l1; per channel (a * (256 - t) + b * t + 128) >> 8
+ *   double trgl_mip_lod(const double bar[3], const double k[4], int tex_w, int tex_h)      the pixel's level of detail from the four
+ *       doubles trgl_lod_stage left in the triangle's varyings: wp = (bar[0] * k[1] + bar[1] * k[2]) + bar[2] * k[3];
+ *       r = (((k[0] * wp) * wp) * wp) * ((double)tex_w * (double)tex_h); if !(r > 1.0) return 0.0 (magnification, zeros, NaN); if r is
+ *       +inf return 64.0; else with e the unbiased exponent of r and m its 52 mantissa bits times 2^-52, return 0.5 * ((double)e + m) -
+ *       the piecewise-linear log2, exact to compute, within 0.05 of 0.5 * log2(r), no libm.
+ * The self-test runs those device functions over n host-side samples (uv: 2 n doubles, lod: n doubles): mode 0 is level, 1 linear,
+ * 2 trilinear; in modes 0 and 1 lod is converted to int as cvttsd2si does (NaN and out of range: INT_MIN, which clamps to level 0).
+ * out receives 5 bytes per sample, as trgl_selftest_sampler gives.  trgl_image_sample is its host twin (no context, no GPU) over an
+ * image and its packed chain of `levels` levels (chain may be NULL when levels is 1; levels is clamped to what w and h allow).
+ * trgl_selftest_mip_lod is the host's compile of trgl_mip_lod over n samples (bar: 3 n doubles, k: 4 n doubles, out: n doubles). */
+int trgl_selftest_sampler_lod(trgl_ctx* ctx, int slot, const double* uv, const double* lod, int mode, uint64_t n, uint8_t* out);
+int trgl_image_sample(const uint8_t* level0, const uint8_t* chain, int w, int h, int bpp, int levels,
+                      const double* uv, const double* lod, int mode, uint64_t n, uint8_t* out);
+int trgl_selftest_mip_lod(const double* bar, const double* k, int tex_w, int tex_h, uint64_t n, double* out);
+
+/* The level-of-detail stage.  A fragment body is called without neighbours and cannot difference uv; for a planar triangle the Jacobian
+ * determinant of (u, v) with respect to screen (x, y) is a per-triangle constant times the cube of the pixel's clip w, and that clip w
+ * is the sum of bar[i] * W_i over the perspective-correct barycentrics.  The stage runs after trgl_clip_stage (or the vertex stage), on
+ * its output rows: for triangle t it reads its clip row and six doubles u0 v0 u1 v1 u2 v2 at vary[t * K + uv_offset ..] (offset 0 in
+ * the PHONG layout) and writes four doubles k = (c, W0, W1, W2) at vary[t * K + out_offset ..]; both ranges lie inside K and do not
+ * overlap, and nothing else of the row is touched.  The four doubles are per-triangle constants: a clip stage must not be told to
+ * interpolate them (do not declare them as clip attributes; run the stage behind the clip).  With (X_i, Y_i, Z_i, W_i) the clip vertices:
+ *     ndc_i = (X_i / W_i, Y_i / W_i, Z_i / W_i, W_i / W_i); s_i.x = sum of viewport[k] * ndc_i[k], s_i.y = sum of viewport[4 + k] * ndc_i[k],
+ *         each sum starting from 0.0 and adding k = 0 .. 3 in order (what rasterize() computes, our_gl.cpp:101,117-121)
+ *     q_i = 1.0 / W_i, U_i = u_i * q_i, V_i = v_i * q_i;  e1 = s1 - s0, e2 = s2 - s0, A = e1x * e2y - e1y * e2x
+ *     for f in U, V, q: d1 = f1 - f0, d2 = f2 - f0, gx = d1 * e2y - d2 * e1y, gy = d2 * e1x - d1 * e2x
+ *     N = (U0 * (gxV * gyq - gyV * gxq) - V0 * (gxU * gyq - gyU * gxq)) + q0 * (gxU * gyV - gyU * gxV);  c = fabs(N) / (A * A)
+ * The four outputs are all +0.0 (the triangle then samples level 0) when any !(W_i > 1e-12), when A == 0, when an ndc or screen value
+ * is not finite, or when c is not finite.  TRGL_MEM_HOST is plain C++ and ctx may be NULL.  TRGL_MEM_DEVICE: arrays 8-byte aligned
+ * (nothing wider is assumed), queued on the context's stream in order with the draws, no wait and no flush; a begun flush is completed
+ * first, as trgl_order_stage does.  TRGL_E_INVALID: a bad mem_kind, a device call without a context, a null viewport, K outside 0..64,
+ * offsets outside K or overlapping, a null or misaligned array with n > 0; TRGL_E_UNSUPPORTED: n above 2^31 - 1.  n == 0 returns
+ * TRGL_OK and no array is read. */
+int trgl_lod_stage(trgl_ctx* ctx, const double viewport[16], const double* clip, double* vary, uint64_t n, int K,
+                   int uv_offset, int out_offset, int mem_kind);
+
 /* ---- shadow mapping as a post-pass: a mask from the light's depths, multiplied into an image -------------- */
 
 /* New work: the reference has no shadows, so nothing here "replaces" a function of it.  The arithmetic is borrowed from the lines named

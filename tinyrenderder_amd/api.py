@@ -70,7 +70,10 @@ SYMBOLS = [
     "trgl_instance_depths", "trgl_depth_order", "trgl_draw_instanced_ordered", "trgl_instance_stage_ordered",
     "trgl_instance_boxes", "trgl_frustum_boxes",
     "trgl_triangle_depths", "trgl_order_stage", "trgl_draw_ordered",
+    "trgl_mip_layout", "trgl_image_mipmaps", "trgl_texture_mipmaps", "trgl_selftest_sampler_lod", "trgl_image_sample", "trgl_lod_stage", "trgl_selftest_mip_lod",
 ]
+MAX_MIP_LEVELS = 16
+SAMPLE_LEVEL, SAMPLE_LINEAR, SAMPLE_TRILINEAR = 0, 1, 2      # the modes of image_sample / selftest_sampler_lod
 
 
 class Uniforms(C.Structure):
@@ -280,6 +283,14 @@ def load_library(path: str = None):
                                    C.c_void_p, C.c_void_p, C.c_void_p]
     L.trgl_draw_ordered.argtypes = [vp, C.c_int, C.POINTER(Uniforms), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
                                     C.c_void_p, C.c_uint64, C.c_uint32, C.c_int]
+    ip = C.POINTER(C.c_int)
+    L.trgl_mip_layout.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.trgl_image_mipmaps.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.trgl_texture_mipmaps.argtypes = [vp, C.c_int]
+    L.trgl_selftest_sampler_lod.argtypes = [vp, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
+    L.trgl_image_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
+    L.trgl_selftest_mip_lod.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p]
+    L.trgl_lod_stage.argtypes = [vp, dp, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -513,6 +524,110 @@ def image_downsample(img, factor: int) -> np.ndarray:
     into a new [h // factor, w // factor, bpp] array: (sum of factor x factor bytes + factor * factor // 2) // (factor * factor) per
     channel.  Raises for a factor outside 1..16 or above w or h.  Needs no GPU."""
     return _host_image_downsample(load_library(), None, img, factor)
+
+
+def mip_layout(w: int, h: int, bpp: int):
+    """trgl_mip_layout: (widths, heights, offsets, total) of the mip chain of a w x h image - the sizes of all L levels, the byte offsets of
+    levels 1 .. L-1 in the packed buffer (offsets[0] is 0 and names nothing) and that buffer's bytes.  Needs no GPU."""
+    L = load_library()
+    n, total = C.c_int(), C.c_size_t()
+    ws, hs, offs = (C.c_int * MAX_MIP_LEVELS)(), (C.c_int * MAX_MIP_LEVELS)(), (C.c_size_t * MAX_MIP_LEVELS)()
+    rc = L.trgl_mip_layout(int(w), int(h), int(bpp), C.byref(n), ws, hs, offs, C.byref(total))
+    if rc != 0:
+        raise TrglError(f"trgl_mip_layout failed ({rc}): {L.trgl_last_error(None).decode()}")
+    return list(ws[:n.value]), list(hs[:n.value]), list(offs[:n.value]), int(total.value)
+
+
+def _image_mipmaps(L, handle, sptr, img, dptr, device):
+    h, w, bpp = _image_dims(img, "image_mipmaps")
+    rc = L.trgl_image_mipmaps(handle, sptr, w, h, bpp, dptr, MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_image_mipmaps failed ({rc}): {L.trgl_last_error(handle).decode()}")
+
+
+def _host_image_mipmaps(L, handle, img, out=None):
+    src = np.ascontiguousarray(img, np.uint8)
+    h, w, bpp = _image_dims(src, "image_mipmaps")
+    total = mip_layout(w, h, bpp)[3]
+    if out is None:
+        out = np.zeros(total, np.uint8)
+    elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.shape != (total,):
+        raise ValueError("image_mipmaps: out must be a contiguous uint8 array of mip_layout(w, h, bpp)[3] bytes")
+    _image_mipmaps(L, handle, src.ctypes.data, src, out.ctypes.data, False)
+    return out
+
+
+def image_mipmaps(img) -> np.ndarray:
+    """trgl_image_mipmaps for a host array without a context: levels 1 .. L-1 of img [h, w, bpp] uint8 as one packed uint8 array in the
+    layout of mip_layout (the padding between levels is zero here: the array is new).  Needs no GPU."""
+    return _host_image_mipmaps(load_library(), None, img)
+
+
+def image_sample(img, chain, uv, lod, mode=SAMPLE_TRILINEAR, levels=None) -> np.ndarray:
+    """trgl_image_sample: the filtered samplers of the user shaders on the host, over img [h, w, bpp] uint8 and its packed chain (None:
+    one level) at uv [n, 2] and lod [n]; mode SAMPLE_LEVEL / SAMPLE_LINEAR (lod converted to int) / SAMPLE_TRILINEAR.  Returns [n, 5]
+    uint8 = bgra[4], bytespp, as selftest_sampler does.  Needs no GPU."""
+    L = load_library()
+    src = np.ascontiguousarray(img, np.uint8)
+    h, w, bpp = _image_dims(src, "image_sample")
+    chain = None if chain is None else np.ascontiguousarray(chain, np.uint8)
+    if levels is None:
+        levels = 1 if chain is None else MAX_MIP_LEVELS
+    if chain is not None and int(levels) > 1 and chain.size < mip_layout(w, h, bpp)[3]:
+        raise ValueError("image_sample: chain is shorter than mip_layout(w, h, bpp)[3] bytes")
+    uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
+    lod = np.ascontiguousarray(np.broadcast_to(np.asarray(lod, np.float64), (uv.shape[0],)))
+    out = np.zeros((uv.shape[0], 5), np.uint8)
+    rc = L.trgl_image_sample(src.ctypes.data, None if chain is None else chain.ctypes.data, w, h, bpp, int(levels),
+                             uv.ctypes.data, lod.ctypes.data, int(mode), uv.shape[0], out.ctypes.data)
+    if rc != 0:
+        raise TrglError(f"trgl_image_sample failed ({rc}): {L.trgl_last_error(None).decode()}")
+    return out
+
+
+def mip_lod(bar, k, tex_w: int, tex_h: int) -> np.ndarray:
+    """trgl_selftest_mip_lod: the host's compile of the user shaders' trgl_mip_lod over bar [n, 3] and k [n, 4]; returns [n] float64 levels
+    of detail for a tex_w x tex_h texture.  Needs no GPU."""
+    L = load_library()
+    bar = np.ascontiguousarray(bar, np.float64).reshape(-1, 3)
+    k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.float64), (bar.shape[0], 4)))
+    out = np.zeros(bar.shape[0], np.float64)
+    rc = L.trgl_selftest_mip_lod(bar.ctypes.data, k.ctypes.data, int(tex_w), int(tex_h), bar.shape[0], out.ctypes.data)
+    if rc != 0:
+        raise TrglError(f"trgl_selftest_mip_lod failed ({rc}): {L.trgl_last_error(None).decode()}")
+    return out
+
+
+def _lod_stage(L, handle, viewport, clip, varyings, uv_offset, out_offset, device):
+    """In place on `varyings`; returns the arrays to keep alive."""
+    vp_m = np.ascontiguousarray(viewport, np.float64).reshape(16)
+    if device:
+        for a, what in ((clip, "clip"), (varyings, "varyings")):
+            if not _is_device_tensor(a) or str(a.dtype) != "torch.float64" or not a.is_contiguous() or a.dim() != 2:
+                raise ValueError(f"device=True: {what} must be a contiguous float64 device tensor with 2 dimensions")
+        n, K = int(clip.shape[0]), int(varyings.shape[1])
+        if int(clip.shape[1]) != 12 or int(varyings.shape[0]) != n:
+            raise ValueError("lod_stage: clip must be [n, 12] and varyings [n, K]")
+        ptrs = (clip.data_ptr() if n else None, varyings.data_ptr() if n else None)
+    else:
+        if not isinstance(varyings, np.ndarray) or varyings.dtype != np.float64 or not varyings.flags.c_contiguous or varyings.ndim != 2:
+            raise ValueError("lod_stage: varyings must be a contiguous float64 array [n, K] (it is rewritten in place)")
+        clip = np.ascontiguousarray(clip, np.float64).reshape(-1, 12)
+        n, K = clip.shape[0], varyings.shape[1]
+        if varyings.shape[0] != n:
+            raise ValueError("lod_stage: clip must be [n, 12] and varyings [n, K]")
+        ptrs = (clip.ctypes.data if n else None, varyings.ctypes.data if n else None)
+    rc = L.trgl_lod_stage(handle, _dp(vp_m), ptrs[0], ptrs[1], n, K, int(uv_offset), int(out_offset), MEM_DEVICE if device else MEM_HOST)
+    if rc != 0:
+        raise TrglError(f"trgl_lod_stage failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return clip, varyings
+
+
+def lod_stage(viewport, clip, varyings, uv_offset=0, out_offset=6):
+    """trgl_lod_stage for host arrays without a context: for every triangle of clip [n, 12] the four level-of-detail doubles
+    (c, W0, W1, W2) from its clip row, the Viewport [4, 4] and its six uv doubles at varyings[:, uv_offset:uv_offset + 6], written in place
+    at varyings[:, out_offset:out_offset + 4] (a contiguous float64 array [n, K]); returns varyings.  Needs no GPU."""
+    return _lod_stage(load_library(), None, viewport, clip, varyings, uv_offset, out_offset, False)[1]
 
 
 def shadow_matrix(light_mv, light_proj, light_vp, cam_mv, cam_proj, cam_vp) -> np.ndarray:
@@ -1491,6 +1606,39 @@ class Context:
         slot is empty or holds a texture of that size.  Not on a strip / band context."""
         self._chk(self.L.trgl_texture_from_framebuffer(self.h, int(slot), int(factor)))
 
+    def texture_mipmaps(self, slot):
+        """trgl_texture_mipmaps: builds the mip chain of the texture in `slot`, ordered like the other texture calls (draws submitted earlier
+        sample one level).  Every call that replaces the slot's texels drops the chain; a rebuild on a slot that has held one of this size
+        is kernels on the stream without a host wait."""
+        self._chk(self.L.trgl_texture_mipmaps(self.h, int(slot)))
+
+    def image_mipmaps(self, img, device=False, out=None):
+        """trgl_image_mipmaps: levels 1 .. L-1 of img [h, w, bpp] as one packed uint8 array (see mip_layout); returns it.  Host array: no
+        GPU work.  device=True: contiguous uint8 device tensors at any address, built on the context's stream (nothing is flushed, the call
+        does not wait); `out` (1-D, mip_layout(w, h, bpp)[3] bytes, not overlapping img; only the levels' bytes are written) is allocated
+        zeroed with torch when not given; both are kept alive until the next sync."""
+        if not device:
+            return _host_image_mipmaps(self.L, self.h, img, out)
+        sptr = _device_image(img, "img")
+        h, w, bpp = _image_dims(img, "image_mipmaps")
+        total = mip_layout(w, h, bpp)[3]
+        if out is None:
+            import torch
+            out = torch.zeros(total, dtype=torch.uint8, device=img.device)
+        elif tuple(out.shape) != (total,):
+            raise ValueError("image_mipmaps: out must be 1-D with mip_layout(w, h, bpp)[3] bytes")
+        self._keep.append((img, out))
+        _image_mipmaps(self.L, self.h, sptr, img, _device_image(out, "out") if total else None, True)
+        return out
+
+    def lod_stage(self, viewport, clip, varyings, uv_offset=0, out_offset=6, device=False):
+        """trgl_lod_stage (see the module's lod_stage): in place on varyings [n, K]; returns it.  device=True: contiguous float64 device
+        tensors, queued on the context's stream in order with the draws (no wait, no flush), kept alive until the next sync."""
+        clip, varyings = _lod_stage(self.L, self.h, viewport, clip, varyings, uv_offset, out_offset, device)
+        if device:
+            self._keep.append((clip, varyings))
+        return varyings
+
     def framebuffer_blur(self, radius):
         """trgl_framebuffer_blur: framebuffer.gaussian_blur(radius) on the resident frame (flushes what is queued, does not wait); the
         z-buffer and the stats stay as they are.  Not on a strip / band context."""
@@ -1714,6 +1862,15 @@ class Context:
         uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
         out = np.zeros((uv.shape[0], 5), np.uint8)
         self._chk(self.L.trgl_selftest_sampler(self.h, slot, uv.ctypes.data, uv.shape[0], out.ctypes.data))
+        return out
+
+    def selftest_sampler_lod(self, slot: int, uv, lod, mode=SAMPLE_TRILINEAR) -> np.ndarray:
+        """The filtered device samplers of the user shaders on texture `slot` at uv [n,2] and lod [n] (mode SAMPLE_LEVEL, SAMPLE_LINEAR:
+        lod converted to int; SAMPLE_TRILINEAR): [n,5] uint8 = bgra[4], bytespp."""
+        uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
+        lod = np.ascontiguousarray(np.broadcast_to(np.asarray(lod, np.float64), (uv.shape[0],)))
+        out = np.zeros((uv.shape[0], 5), np.uint8)
+        self._chk(self.L.trgl_selftest_sampler_lod(self.h, int(slot), uv.ctypes.data, lod.ctypes.data, int(mode), uv.shape[0], out.ctypes.data))
         return out
 
     def last_flush_info(self):

@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -121,6 +121,15 @@ void launch_image_scale(hipStream_t s, const uint8_t* src, int w, int h, int bpp
 hipError_t launch_box_filter(hipStream_t s, const uint8_t* src, int w, int h, int bpp, int f, uint8_t* dst);
 // table[slot] = t by a one-thread kernel: an update of the context's texture table that keeps its place in the stream
 hipError_t launch_set_texture(hipStream_t s, DevTexture* table, int slot, const DevTexture& t);
+// Mip chains, the level-of-detail constants and the self-test of the filtered samplers (kernels_mip.hip; written down under "Mipmapped
+// textures" in include/trgl.h, the arithmetic is mip_core.h's).
+// launch_mip_chain: levels 1 .. L-1 of the w x h image at level0 into `chain`: with slot_layout at mip_slot_offset() from chain (the
+// caller passes level0 itself: a texture slot's allocation), else at mip_packed_offset().  Any byte alignment, level0 and the written
+// levels disjoint, w and h in 1..65535, w * h * bpp <= INT_MAX.  Only the levels' bytes are written.  One launch per MIP_STEP levels.
+// launch_lod_stage: one thread per triangle, 0 < n < 2^31, doubles 8-byte aligned; the offsets lie inside K and do not overlap.
+hipError_t launch_mip_chain(hipStream_t s, const uint8_t* level0, int w, int h, int bpp, uint8_t* chain, bool slot_layout);
+hipError_t launch_lod_stage(hipStream_t s, const double viewport[16], const double* clip, double* vary, uint32_t n, int K, int uv_offset, int out_offset);
+void launch_selftest_sampler_lod(hipStream_t s, const DevTexture* tex, int slot, const double* uv, const double* lod, int mode, unsigned long long n, uint8_t* out);
 
 // The shadow post-pass (kernels_shadow.hip; the arithmetic is written down at trgl_shadow_mask_image in include/trgl.h).
 // depth: w * h depths, map: map_w * map_h depths of the light's view, both 8-byte aligned (16-byte aligned arrays are read as 16-byte

@@ -67,6 +67,7 @@ struct trgl_ctx {
     int il_tiles = 0, il_world = 1, il_rank = 0;     // interleaved bands instead of one strip (trgl_set_interleave)
 
     DevTexture tex_host[TRGL_MAX_TEXTURES];
+    size_t tex_cap[TRGL_MAX_TEXTURES] = {};      // bytes of each slot's allocation: a chain fits when mip_slot_offset(w, h, bpp, L) does
     DevBuf<DevTexture> tex_dev;
 
     std::vector<DrawDesc> draws;
@@ -202,4 +203,7 @@ void host_instance_boxes(const double* local_boxes, int local_stride, const doub
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);
 // the box filter of box_core.h over host images: dst (w / f) x (h / f) from src w x h; f in 1..TRGL_MAX_BOX_FACTOR, w / f and h / f >= 1
 void host_box_filter(const uint8_t* src, int w, int h, int bpp, int f, uint8_t* dst);
+// trgl_image_mipmaps and trgl_lod_stage over host arrays (mip_core.h): levels 1 .. L-1 into the packed layout; the four LOD doubles per row
+void host_mipmaps(const uint8_t* src, int w, int h, int bpp, uint8_t* dst);
+void host_lod_stage(const double viewport[16], const double* clip, double* vary, uint64_t n, int K, int uv_offset, int out_offset);
 }  // namespace trgl

@@ -14,6 +14,7 @@
 #include "../../include/trgl.h"
 #include "box_core.h"
 #include "clip_core.h"
+#include "mip_core.h"
 #include "occlusion_core.h"
 #include "scene_core.h"
 #include "triorder_core.h"
@@ -42,6 +43,38 @@ void host_box_filter(const uint8_t* src, int w, int h, int bpp, int f, uint8_t* 
                 }
                 *dst++ = (uint8_t)box_round(sum, half, magic);
             }
+}
+
+// ---- mip chains, filtered samples and the LOD stage over host arrays (include/trgl.h, "Mipmapped textures"; mip_core.h) ---------------
+// levels 1 .. L-1 of src into dst, in the packed layout; only the levels' bytes are written
+void host_mipmaps(const uint8_t* src, int w, int h, int bpp, uint8_t* dst) {
+    const int L = mip_levels(w, h);
+    const uint8_t* prev = src;
+    for (int l = 1; l < L; ++l) {
+        const int pw = mip_side(w, l - 1), ph = mip_side(h, l - 1), cw = mip_side(w, l), ch = mip_side(h, l);
+        const int fx = pw >= 2 ? 2 : 1, fy = ph >= 2 ? 2 : 1;
+        const size_t prow = (size_t)pw * bpp;
+        uint8_t* out = dst + mip_packed_offset(w, h, bpp, l);
+        uint8_t* o = out;
+        for (int y = 0; y < ch; ++y)
+            for (int x = 0; x < cw; ++x)
+                for (int c = 0; c < bpp; ++c) {
+                    uint32_t sum = 0;
+                    for (int j = 0; j < fy; ++j)
+                        for (int i = 0; i < fx; ++i) sum += prev[((size_t)y * fy + j) * prow + ((size_t)x * fx + i) * bpp + c];
+                    *o++ = (uint8_t)mip_round(sum, (uint32_t)(fx * fy));
+                }
+        prev = out;
+    }
+}
+
+void host_lod_stage(const double viewport[16], const double* clip, double* vary, uint64_t n, int K, int uv_offset, int out_offset) {
+    for (uint64_t t = 0; t < n; ++t) {
+        double* row = vary + t * (uint64_t)K;
+        double out[4];
+        mip_lod_constants(viewport, clip + t * 12, row + uv_offset, out);
+        for (int i = 0; i < 4; ++i) row[out_offset + i] = out[i];
+    }
 }
 
 // ---- scene logic around the draws (model.cpp:15-40, geometry.h:264-266,297-327, our_gl.cpp:212-280) ------------------------------
@@ -309,6 +342,45 @@ int trgl_clip_layout(int kind, trgl_clip_attr* attrs, int* n_attrs) {
     }
     for (int a = 0; attrs && a < n; ++a) attrs[a] = src[a];
     *n_attrs = n;
+    return TRGL_OK;
+}
+
+int trgl_mip_layout(int w, int h, int bpp, int* levels, int widths[TRGL_MAX_MIP_LEVELS], int heights[TRGL_MAX_MIP_LEVELS],
+                    size_t offsets[TRGL_MAX_MIP_LEVELS], size_t* total) {
+    if (w < 1 || h < 1 || !(bpp == 1 || bpp == 3 || bpp == 4)) return fail(nullptr, TRGL_E_INVALID, "trgl_mip_layout: need w, h >= 1 and bpp in {1, 3, 4}");
+    if (w > 65535 || h > 65535) return fail(nullptr, TRGL_E_UNSUPPORTED, "trgl_mip_layout: a side above 65535");
+    if ((int64_t)w * h * bpp > 0x7fffffff) return fail(nullptr, TRGL_E_UNSUPPORTED, "trgl_mip_layout: w * h * bpp above INT_MAX");
+    const int L = mip_levels(w, h);
+    if (levels) *levels = L;
+    for (int l = 0; l < TRGL_MAX_MIP_LEVELS; ++l) {
+        if (widths) widths[l] = l < L ? mip_side(w, l) : 0;
+        if (heights) heights[l] = l < L ? mip_side(h, l) : 0;
+        if (offsets) offsets[l] = (l >= 1 && l < L) ? mip_packed_offset(w, h, bpp, l) : 0;
+    }
+    if (total) *total = mip_packed_offset(w, h, bpp, L);
+    return TRGL_OK;
+}
+
+int trgl_image_sample(const uint8_t* level0, const uint8_t* chain, int w, int h, int bpp, int levels,
+                      const double* uv, const double* lod, int mode, uint64_t n, uint8_t* out) {
+    if (int r = trgl_mip_layout(w, h, bpp, nullptr, nullptr, nullptr, nullptr, nullptr)) return r;
+    if (mode < 0 || mode > 2 || levels < 1) return fail(nullptr, TRGL_E_INVALID, "trgl_image_sample: need mode in 0..2 and levels >= 1");
+    if (n == 0) return TRGL_OK;
+    if (!level0 || !uv || !lod || !out) return fail(nullptr, TRGL_E_INVALID, "trgl_image_sample: null argument");
+    const int L = std::min(levels, mip_levels(w, h));
+    if (L > 1 && !chain) return fail(nullptr, TRGL_E_INVALID, "trgl_image_sample: chain is null");
+    const MipView v{ level0, chain, w, h, bpp, L, false };
+    for (uint64_t i = 0; i < n; ++i) {
+        const MipTexel c = mip_sample_mode(v, uv + 2 * i, lod[i], mode);
+        for (int k = 0; k < 4; ++k) out[5 * i + k] = (uint8_t)(c.bgra >> (8 * k));
+        out[5 * i + 4] = (uint8_t)c.bytespp;
+    }
+    return TRGL_OK;
+}
+
+int trgl_selftest_mip_lod(const double* bar, const double* k, int tex_w, int tex_h, uint64_t n, double* out) {
+    if (n && (!bar || !k || !out)) return fail(nullptr, TRGL_E_INVALID, "trgl_selftest_mip_lod: null argument");
+    for (uint64_t i = 0; i < n; ++i) out[i] = mip_lod(bar + 3 * i, k + 4 * i, tex_w, tex_h);
     return TRGL_OK;
 }
 

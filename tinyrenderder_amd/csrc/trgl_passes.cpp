@@ -1,5 +1,5 @@
 // trgl_passes.cpp — the optional passes of include/trgl.h over finished frames and over caller-owned images and meshes: SSAO post-process,
-// z-buffer snapshots, blur and scale, the box-filter resolve and textures from frames, the shadow mask and modulate, occlusion culling of boxes, world boxes and frustum codes of instances, mesh bounds and attributes in device memory, the two self-tests.
+// z-buffer snapshots, blur and scale, the box-filter resolve and textures from frames, mip chains and the LOD stage, the shadow mask and modulate, occlusion culling of boxes, world boxes and frustum codes of instances, mesh bounds and attributes in device memory, the two self-tests.
 // None of them knows the flush pipeline of trgl_api.cpp: each finishes what is pending (end_pending_raster, trgl_flush, flush_sync), then
 // launches on the context's stream.  With TRGL_MEM_HOST the work is done by the host loops (trgl_host.cpp, shim/trgl_image.h).
 #include <climits>
@@ -8,6 +8,7 @@
 #include <new>
 
 #include "trgl_ctx.h"
+#include "mip_core.h"
 #include "../shim/trgl_image.h"
 
 static int zsnap_slot(trgl_ctx* c, int slot, const char* who) {
@@ -79,6 +80,7 @@ static int texture_from_device(trgl_ctx* c, const std::string& who, int slot, co
             HIPCHK(c, hipStreamSynchronize(c->stream));
             HIPCHK(c, hipFree((void*)t.data));
             t = DevTexture{ nullptr, 0, 0, 0, 0 };
+            c->tex_cap[slot] = 0;
         }
         uint8_t* d = nullptr;
         if (hipMalloc((void**)&d, bytes + 8) != hipSuccess) {
@@ -87,7 +89,11 @@ static int texture_from_device(trgl_ctx* c, const std::string& who, int slot, co
             return fail(c, TRGL_E_NOMEM, who + ": out of device memory");
         }
         t = DevTexture{ d, w2, h2, bpp, 0 };
+        c->tex_cap[slot] = bytes + 8;
         HIPCHK(c, hipMemsetAsync(d + bytes, 0, 8, c->stream));
+        HIPCHK(c, launch_set_texture(c->stream, c->tex_dev.p, slot, t));
+    } else if (t.pad) {      // new texels: one level until trgl_texture_mipmaps is called again (the levels' memory stays with the slot)
+        t.pad = 0;
         HIPCHK(c, launch_set_texture(c->stream, c->tex_dev.p, slot, t));
     }
     HIPCHK(c, launch_box_filter(c->stream, src, w, h, bpp, factor, const_cast<uint8_t*>(t.data)));
@@ -378,6 +384,75 @@ int trgl_texture_from_framebuffer(trgl_ctx* c, int slot, int factor) {
     return texture_from_device(c, "trgl_texture_from_framebuffer", slot, c->fb.p, c->W, c->H, c->bpp, factor);
 }
 
+// ---- mipmapped textures (include/trgl.h; host loops in trgl_host.cpp, kernels in kernels_mip.hip, the arithmetic in mip_core.h) ----------
+int trgl_image_mipmaps(trgl_ctx* c, const uint8_t* src, int w, int h, int bpp, uint8_t* dst, int mem_kind) {
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_image_mipmaps: bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_image_mipmaps: TRGL_MEM_DEVICE needs a context");
+    int L = 0; size_t total = 0;
+    if (int r = trgl_mip_layout(w, h, bpp, &L, nullptr, nullptr, nullptr, &total)) return c ? fail(c, r, std::string("trgl_image_mipmaps: ") + trgl_last_error(nullptr)) : r;
+    if (!src) return fail(c, TRGL_E_INVALID, "trgl_image_mipmaps: src is null");
+    if (L == 1) return TRGL_OK;
+    if (!dst) return fail(c, TRGL_E_INVALID, "trgl_image_mipmaps: dst is null");
+    if (ranges_overlap(src, (size_t)w * h * bpp, dst, total)) return fail(c, TRGL_E_INVALID, "trgl_image_mipmaps: src and dst overlap");
+    if (mem_kind == TRGL_MEM_HOST) { host_mipmaps(src, w, h, bpp, dst); return TRGL_OK; }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    HIPCHK(c, launch_mip_chain(c->stream, src, w, h, bpp, dst, false));
+    return TRGL_OK;
+}
+
+int trgl_texture_mipmaps(trgl_ctx* c, int slot) {
+    CHKCTX(c);
+    int r = texture_slot(c, slot, "trgl_texture_mipmaps"); if (r) return r;
+    DevTexture& t = c->tex_host[slot];
+    if (!t.data || t.w <= 0 || t.h <= 0) return fail(c, TRGL_E_STATE, "trgl_texture_mipmaps: the slot holds no texture");
+    if (t.w > 65535 || t.h > 65535) return fail(c, TRGL_E_UNSUPPORTED, "trgl_texture_mipmaps: a side above 65535");
+    if ((r = end_pending_raster(c))) return r;
+    if ((r = trgl_flush(c))) return r;                // draws submitted earlier sample one level
+    const int L = mip_levels(t.w, t.h);
+    if (L == 1) return TRGL_OK;
+    const size_t bytes0 = (size_t)t.w * t.h * t.bpp, need = mip_slot_offset(t.w, t.h, t.bpp, L);
+    if (c->tex_cap[slot] < need) {
+        // the first build on this slot: room for the levels behind level 0, every byte between and behind them zero (the samplers'
+        // 4-byte loads), level 0 copied over on the stream; the old memory goes behind a wait
+        uint8_t* d = nullptr;
+        if (hipMalloc((void**)&d, need) != hipSuccess) { (void)hipGetLastError(); return fail(c, TRGL_E_NOMEM, "trgl_texture_mipmaps: out of device memory"); }
+        const DevTexture nt{ d, t.w, t.h, t.bpp, 0 };
+        hipError_t e = hipMemsetAsync(d + bytes0, 0, need - bytes0, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d, t.data, bytes0, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = launch_set_texture(c->stream, c->tex_dev.p, slot, nt);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { (void)hipFree(d); HIPCHK(c, e); }
+        HIPCHK(c, hipFree((void*)t.data));
+        t = nt;
+        c->tex_cap[slot] = need;
+    }
+    HIPCHK(c, launch_mip_chain(c->stream, t.data, t.w, t.h, t.bpp, const_cast<uint8_t*>(t.data), true));
+    t.pad = L - 1;
+    HIPCHK(c, launch_set_texture(c->stream, c->tex_dev.p, slot, t));
+    return TRGL_OK;
+}
+
+int trgl_lod_stage(trgl_ctx* c, const double viewport[16], const double* clip, double* vary, uint64_t n, int K,
+                   int uv_offset, int out_offset, int mem_kind) {
+    const std::string w = "trgl_lod_stage: ";
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, w + "TRGL_MEM_DEVICE needs a context");
+    if (!viewport) return fail(c, TRGL_E_INVALID, w + "viewport is null");
+    if (K < 0 || K > TRGL_MAX_USER_VARY) return fail(c, TRGL_E_INVALID, w + "K outside 0..TRGL_MAX_USER_VARY");
+    if (uv_offset < 0 || out_offset < 0 || uv_offset > K - 6 || out_offset > K - 4 || (uv_offset < out_offset + 4 && out_offset < uv_offset + 6))
+        return fail(c, TRGL_E_INVALID, w + "need uv_offset + 6 <= K, out_offset + 4 <= K and ranges that do not overlap");
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more triangles in one call");
+    if (n == 0) return TRGL_OK;
+    if (!clip || !vary) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (((uintptr_t)clip | (uintptr_t)vary) & 7) return fail(c, TRGL_E_INVALID, w + "arrays must be 8-byte aligned");
+    if (mem_kind == TRGL_MEM_HOST) { host_lod_stage(viewport, clip, vary, n, K, uv_offset, out_offset); return TRGL_OK; }
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    HIPCHK(c, launch_lod_stage(c->stream, viewport, clip, vary, (uint32_t)n, K, uv_offset, out_offset));
+    return TRGL_OK;
+}
+
 int trgl_shadow_mask_image(trgl_ctx* c, const trgl_shadow_params* params, const double* depth, int w, int h,
                            const double* map, int map_w, int map_h, uint8_t* mask, int mem_kind) {
     if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_shadow_mask_image: bad mem_kind");
@@ -563,6 +638,23 @@ int trgl_selftest_sampler(trgl_ctx* c, int slot, const double* uv, uint64_t n, u
     if ((r = d_uv.alloc(c, n * 2)) || (r = d_out.alloc(c, n * 5))) return r;
     HIPCHK(c, hipMemcpyAsync(d_uv.p, uv, n * 16, hipMemcpyHostToDevice, c->stream));
     launch_selftest_sampler(c->stream, c->tex_dev.p, slot, d_uv.p, n, d_out.p);
+    HIPCHK(c, hipMemcpyAsync(out, d_out.p, n * 5, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TRGL_OK;
+}
+
+int trgl_selftest_sampler_lod(trgl_ctx* c, int slot, const double* uv, const double* lod, int mode, uint64_t n, uint8_t* out) {
+    CHKCTX(c);
+    if (!uv || !lod || !out) return fail(c, TRGL_E_INVALID, "trgl_selftest_sampler_lod: null argument");
+    if (slot < 0 || slot >= TRGL_MAX_TEXTURES) return fail(c, TRGL_E_INVALID, "trgl_selftest_sampler_lod: bad slot");
+    if (mode < 0 || mode > 2) return fail(c, TRGL_E_INVALID, "trgl_selftest_sampler_lod: mode must be 0, 1 or 2");
+    int r = trgl_flush(c); if (r) return r;
+    if (!n) return TRGL_OK;
+    DevBuf<double> d_uv, d_lod; DevBuf<uint8_t> d_out;
+    if ((r = d_uv.alloc(c, n * 2)) || (r = d_lod.alloc(c, n)) || (r = d_out.alloc(c, n * 5))) return r;
+    HIPCHK(c, hipMemcpyAsync(d_uv.p, uv, n * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_lod.p, lod, n * 8, hipMemcpyHostToDevice, c->stream));
+    launch_selftest_sampler_lod(c->stream, c->tex_dev.p, slot, d_uv.p, d_lod.p, mode, n, d_out.p);
     HIPCHK(c, hipMemcpyAsync(out, d_out.p, n * 5, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return TRGL_OK;

@@ -3,6 +3,7 @@
 // (vertex_user.h).  The sampler is the one k_shade uses (shade_common.h).
 #pragma once
 #include "shade_common.h"
+#include "mip_core.h"
 
 struct trgl_frag_in {
     double bar[3];               // perspective-correct barycentrics (our_gl.cpp:168-185)
@@ -23,6 +24,48 @@ __device__ __forceinline__ trgl_texel trgl_sample2D(const trgl_frag_in& in, int 
     if (!t) return trgl_texel{ 0xffffffffu, 4 };
     const trgl_shade::Color c = trgl_shade::tex_fetch(t, uv);
     return trgl_texel{ c.bgra, c.bytespp };
+}
+
+// ---- mipmapped textures (include/trgl.h, "Mipmapped textures"; the arithmetic is mip_core.h's, which the host compiles too) ----
+// The slot as a mip view: level 0 and, behind it in the slot's own allocation, the levels trgl_texture_mipmaps built (DevTexture::pad
+// holds their number).  false: the slot is empty.
+__device__ __forceinline__ bool trgl_mip_view(const trgl_frag_in& in, int slot, trgl::MipView* v) {
+    const DevTexture* t = trgl_shade::tex_slot(in.tex, slot);
+    if (!t) return false;
+    *v = trgl::MipView{ t->data, t->data, t->w, t->h, t->bpp, 1 + t->pad, true };
+    return true;
+}
+// L and the size of level 0; 0 for an empty slot (w and h are then left alone)
+__device__ __forceinline__ int trgl_texture_levels(const trgl_frag_in& in, int slot, int* w, int* h) {
+    trgl::MipView v;
+    if (!trgl_mip_view(in, slot, &v)) return 0;
+    *w = v.w; *h = v.h;
+    return v.levels;
+}
+// trgl_sample2D's rule on level `level` (clamped to 0..L-1)
+__device__ __forceinline__ trgl_texel trgl_sample2D_level(const trgl_frag_in& in, int slot, const double uv[2], int level) {
+    trgl::MipView v;
+    if (!trgl_mip_view(in, slot, &v)) return trgl_texel{ 0xffffffffu, 4 };
+    const trgl::MipTexel c = trgl::mip_sample_level(v, uv, level);
+    return trgl_texel{ c.bgra, c.bytespp };
+}
+// bilinear on level `level`: weights in 1/256, texel centres at (i + 0.5) / size, clamp at the edges
+__device__ __forceinline__ trgl_texel trgl_sample2D_linear(const trgl_frag_in& in, int slot, const double uv[2], int level) {
+    trgl::MipView v;
+    if (!trgl_mip_view(in, slot, &v)) return trgl_texel{ 0xffffffffu, 4 };
+    const trgl::MipTexel c = trgl::mip_sample_linear(v, uv, level);
+    return trgl_texel{ c.bgra, c.bytespp };
+}
+// trilinear: the bilinear samples of levels floor(lod) and floor(lod) + 1, blended in 1/256
+__device__ __forceinline__ trgl_texel trgl_sample2D_trilinear(const trgl_frag_in& in, int slot, const double uv[2], double lod) {
+    trgl::MipView v;
+    if (!trgl_mip_view(in, slot, &v)) return trgl_texel{ 0xffffffffu, 4 };
+    const trgl::MipTexel c = trgl::mip_sample_trilinear(v, uv, lod);
+    return trgl_texel{ c.bgra, c.bytespp };
+}
+// the level of detail of this pixel from the four per-triangle doubles trgl_lod_stage left in the varyings
+__device__ __forceinline__ double trgl_mip_lod(const double bar[3], const double k[4], int tex_w, int tex_h) {
+    return trgl::mip_lod(bar, k, tex_w, tex_h);
 }
 
 // source-over with the source's alpha byte a, in integers (include/trgl.h, "User shaders that blend"): per B, G, R

@@ -808,6 +808,35 @@ inline bool gl_downsample(const TGAImage& src, int factor, TGAImage* out) {
     return rc == TRGL_OK ? true : fail("trgl_image_downsample", rc, nullptr);
 }
 
+// Mipmapped textures (include/trgl.h, "Mipmapped textures"; new work, the reference has none).
+//   gl_texture_mipmaps   builds the mip chain of the texture in `slot` in HBM (trgl_texture_mipmaps): triangles batched so far are drawn
+//                        first and sample one level; user shaders of later triangles reach the levels through trgl_sample2D_level,
+//                        _linear and _trilinear.  Any call that replaces the slot's texels drops the chain.
+//   gl_lod_stage         the four level-of-detail doubles of n triangles in host arrays, from the global Viewport (trgl_lod_stage on the
+//                        host: no GPU is touched): clip [n][12], vary [n][K], uv at uv_offset, the result at out_offset.  A UserShader
+//                        hands them to its fragment body as four more varyings, which the body passes to trgl_mip_lod.
+//   gl_image_sample      the filtered samplers on the host, over an image and the chain TGAImage-side code built with
+//                        trgl_image::mipmaps (shim/trgl_image.h): out receives 5 bytes a sample (b, g, r, a, bytespp)
+inline bool gl_texture_mipmaps(TGAImage& framebuffer, int slot) {
+    using namespace trgl_shim;
+    if (!bind(framebuffer)) return false;
+    const bool ok = submit_batch();
+    return TRGL_SHIM_OK(trgl_texture_mipmaps(state().ctx, slot)) && ok;
+}
+inline bool gl_lod_stage(const double* clip, double* vary, uint64_t n, int K, int uv_offset, int out_offset) {
+    using namespace trgl_shim;
+    double vp[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) vp[4 * r + c] = Viewport[r][c];
+    const int rc = trgl_lod_stage(nullptr, vp, clip, vary, n, K, uv_offset, out_offset, TRGL_MEM_HOST);
+    return rc == TRGL_OK ? true : fail("trgl_lod_stage", rc, nullptr);
+}
+inline bool gl_image_sample(const TGAImage& img, const std::vector<uint8_t>& chain, const double* uv, const double* lod, int mode, uint64_t n, uint8_t* out) {
+    using namespace trgl_shim;
+    const int rc = trgl_image_sample(image_bytes(img), chain.empty() ? nullptr : chain.data(), img.width(), img.height(), image_bpp(img),
+                                     chain.empty() ? 1 : TRGL_MAX_MIP_LEVELS, uv, lod, mode, n, out);
+    return rc == TRGL_OK ? true : fail("trgl_image_sample", rc, nullptr);
+}
+
 // Shadow mapping as a post-pass (include/trgl.h, "shadow mapping as a post-pass"; new work, the reference has none).  Draw the light's
 // view, gl_zbuffer_snapshot(framebuffer, slot), clear, draw the camera's view, then:
 //   gl_shadow_matrix   the matrix of trgl_shadow_params::screen_to_light from the two views' ModelView / Perspective / Viewport as they

@@ -299,3 +299,20 @@ private:
     std::uint8_t bpp = 0;
     std::vector<std::uint8_t> data;
 };
+
+// The mip chain of an image (include/trgl.h, "Mipmapped textures"; new work, the reference has none): levels 1 .. L-1 in the packed
+// layout of trgl_mip_layout, built by the library's host path - no GPU is touched.  `chain` is empty for a 1 x 1 image.  Programs that
+// call it link the library; the declarations repeat include/trgl.h so that this header still stands alone.
+struct trgl_ctx;
+extern "C" int trgl_mip_layout(int w, int h, int bpp, int* levels, int widths[16], int heights[16], std::size_t offsets[16], std::size_t* total);
+extern "C" int trgl_image_mipmaps(trgl_ctx* ctx, const std::uint8_t* src, int w, int h, int bpp, std::uint8_t* dst, int mem_kind);
+namespace trgl_image {
+inline bool mipmaps(const TGAImage& img, std::vector<std::uint8_t>* chain, int* levels = nullptr) {
+    std::size_t total = 0;
+    int L = 0;
+    if (!chain || trgl_mip_layout(img.width(), img.height(), img.bytespp(), &L, nullptr, nullptr, nullptr, &total) != 0) return false;
+    chain->assign(total, 0);
+    if (levels) *levels = L;
+    return trgl_image_mipmaps(nullptr, img.buffer(), img.width(), img.height(), img.bytespp(), chain->data(), 0 /* TRGL_MEM_HOST */) == 0;
+}
+}  // namespace trgl_image
