@@ -568,6 +568,95 @@ int trgl_draw_ordered(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* unifo
                       const double* clip, const double* varyings, const uint32_t* colors, uint64_t n, int mem_kind,
                       const uint32_t* order, uint64_t n_order, uint32_t group, int order_mem_kind);
 
+/* ---- point sprites and wide lines: one point or one segment becomes the two triangles of a quad -------------------------------- */
+
+/* New work: the reference has neither (rasterize() only knows triangles, and our_gl.cpp:127 drops what is not counter-clockwise on the
+ * screen).  Both are expansion stages in front of rasterize(): ONE input primitive becomes EXACTLY TWO output triangles in the row
+ * format of trgl_draw / trgl_clip_stage / trgl_triangle_depths (group = 2) / trgl_draw_ordered - 12 clip doubles, K varyings, one
+ * colour - so positions that a simulation step left in device memory never visit the host, and there is no count to wait for.
+ *
+ * ARITHMETIC.  fp64, each operation rounded, no contraction or reassociation.  "M * v" is the reference's mat * vec (geometry.h:123-127):
+ * row r gives (((0.0 + M[r][0]*v0) + M[r][1]*v1) + M[r][2]*v2) + M[r][3]*v3.  "a -/+ b" is a - b or a + b as the corner's sign says.
+ * STORED NaNs.  A computed output double (a clip component, ta, tb) that is a NaN is stored as 0x7FF8000000000000: processors differ in
+ * the NaN an operation generates and in the operand whose payload survives, so the 64 bits are fixed here.  The attribute doubles of a
+ * sprite are copies and keep every bit.
+ * THE QUAD.  Both stages make four corners k0 .. k3, counter-clockwise on the screen under the reference's init_perspective /
+ * init_viewport (positive x and y scales).  Output triangle 2i is (k0, k1, k2) and 2i + 1 is (k0, k2, k3), and both get the
+ * primitive's colour.  The first 6 varyings of a row are the three pairs of its vertices in slot order - the memory image of
+ * `vec2 varying_uv[3]`.
+ *
+ * SPRITES.  Point i: position p at +0..2 of its row of point_stride >= 3 doubles; size s = points[i*stride + size_offset], or
+ * params->size when size_offset < 0.
+ *   e = model_view * (p, 1);  h = 0.5 * s.  Corner signs (x, y): k0 (-,-), k1 (+,-), k2 (+,+), k3 (-,+).
+ *   TRGL_SPRITE_VIEW:   corner eye = (e0 -/+ h, e1 -/+ h, e2, e3); clip = projection * corner eye.  The size is in eye-space units.
+ *   TRGL_SPRITE_SCREEN: c = projection * e; hx = (h * scale[0]) * c3; hy = (h * scale[1]) * c3; clip = (c0 -/+ hx, c1 -/+ hy, c2, c3).
+ *                       The size is in units of scale[]: pixels of a w x h viewport with scale = (2.0 / w, 2.0 / h).
+ *   Varyings, K = 6 + n_attr <= TRGL_MAX_USER_VARY: (u, v) = k0 (0,0), k1 (1,0), k2 (1,1), k3 (0,1); then the n_attr doubles at
+ *   +attr_offset of the point's row, bit for bit, in both rows.
+ *   There are no special cases: a NaN, infinite, zero or negative size and a point behind the eye go through the same expressions, and
+ *   rasterize() drops the result at our_gl.cpp:94-127 as it drops any such triangle.  Exactly 2 n rows are written.
+ * vary_out may be NULL when n_attr == 0 (the varyings are then not written: a K = 0 kind reads none); colors_out may be NULL when
+ * colors is, and is not written then.
+ *
+ * LINES.  Segment j: endpoints a = points[indices[2j]], b = points[indices[2j + 1]], or points 2j and 2j + 1 when indices is NULL
+ * (2 n_segments <= n_points then).  Butt caps, no joins: a polyline is its segments, each a quad of its own.
+ *   ca = projection * (model_view * (pa, 1)), cb alike; ta = 0.0, tb = 1.0.
+ *   CUT.  An endpoint is inside when c3 >= w_min (a NaN is not).  Neither inside: the two rows are ALL-ZERO rows - clip +0.0, varyings
+ *     +0.0, colour 0, the convention of trgl_order_stage: rasterize() counts and drops them at our_gl.cpp:94.  Exactly one inside: the
+ *     outside endpoint is replaced, always from the inside one toward it (the clip stage's rule): d = c3 - w_min,
+ *     t = d_in / (d_in - d_out), every clip component and the endpoint's parameter become in + t * (out - in).  A segment and its
+ *     reverse therefore cut at the same bits.
+ *   DIRECTION.  ax = ca0 / ca3, ay = ca1 / ca3, bx, by alike; dx = (bx - ax) * half_extent[0]; dy = (by - ay) * half_extent[1];
+ *     len = sqrt(dx*dx + dy*dy).  Unless len > 0.0 and len is finite: all-zero rows.
+ *   OFFSET.  hw = 0.5 * width; ox = ((-dy / len) * hw) / half_extent[0]; oy = ((dx / len) * hw) / half_extent[1].
+ *   CORNERS.  A-/+ = (ca0 -/+ ox*ca3, ca1 -/+ oy*ca3, ca2, ca3), B-/+ alike with cb; minus is the right-hand side of the direction.
+ *     k0 = A-, k1 = B-, k2 = B+, k3 = A+.
+ *   Varyings, K = 6, per vertex (t, side): A- (ta, 0), B- (tb, 0), B+ (tb, 1), A+ (ta, 1); `side` lets a user kind draw dashes or soft
+ *     edges.  vary_out may be NULL: the varyings are then not written.  colors: one per segment.
+ *   INDICES.  A host index >= n_points: TRGL_E_INVALID, and nothing is written.  A device index >= n_points: all-zero rows, and the
+ *     entry is never used as an address.
+ *
+ * MEMORY AND ORDER.  One mem_kind covers every array of a call.  Host memory: plain C++, ctx may be NULL, complete on return.  Device
+ * memory: doubles 8-byte aligned, colours and indices 4 - nothing wider is assumed; rows leave 16 bytes per lane where the output is
+ * 16-byte aligned and 8 otherwise, and the bytes never depend on it.  One kernel per call, queued on the context's stream in order with
+ * the draws: no wait, nothing is flushed; it completes a begun flush, as trgl_clip_stage does.
+ * trgl_draw_sprites / trgl_draw_lines: trgl_draw of the rows the stage makes - the kind's K must be 6 + n_attr (lines: 6), or 0 with
+ * n_attr == 0.  Host points are expanded in C++ and drawn as host arrays.  Device points are expanded on the stream into buffers the
+ * context owns until the flush is done (the rule of trgl_draw_clipped / trgl_draw_ordered) and drawn with TRGL_MEM_DEVICE; they are read
+ * when the stage runs, not at the flush.  The 2^24 cut and the flush rules are trgl_draw's.
+ * ERRORS.  TRGL_E_INVALID: params NULL, a bad mode or mem_kind, TRGL_MEM_DEVICE without a context, point_stride < 3, size_offset >=
+ * point_stride, n_attr < 0 or its range outside the row, K above TRGL_MAX_USER_VARY, w_min <= 0 or not finite, 2 n_segments > n_points
+ * without indices, a host index out of range, with n > 0 a null or misaligned array or an output that overlaps an input; for the draws
+ * also those of trgl_draw and a kind whose K does not fit.  TRGL_E_UNSUPPORTED: 2 n above 2^31 - 1.  n == 0: TRGL_OK once the scalar
+ * arguments are checked, and no array is read or written. */
+#define TRGL_SPRITE_VIEW   0   /* size in eye-space units: shrinks with distance */
+#define TRGL_SPRITE_SCREEN 1   /* size in units of the caller's scale[]: constant on the screen */
+typedef struct trgl_sprite_params {
+    double  model_view[16], projection[16];   /* row-major, the globals ModelView / Perspective */
+    double  size;            /* used when size_offset < 0 */
+    double  scale[2];        /* SCREEN only: NDC extent per unit of size, x and y (for sizes in pixels of a w x h viewport: 2.0/w, 2.0/h) */
+    int32_t mode;
+    int32_t size_offset;     /* >= 0: the point's size is points[i*stride + size_offset]; < 0: params->size */
+    int32_t attr_offset, n_attr;   /* n_attr doubles of the point's row copied behind the uv pairs of both triangles */
+} trgl_sprite_params;
+int trgl_sprite_stage(trgl_ctx* ctx, const trgl_sprite_params* params, const double* points, int point_stride, const uint32_t* colors,
+                      uint64_t n, int mem_kind, double* clip_out, double* vary_out, uint32_t* colors_out);
+int trgl_draw_sprites(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms, const trgl_sprite_params* params,
+                      const double* points, int point_stride, const uint32_t* colors, uint64_t n, int mem_kind);
+
+typedef struct trgl_line_params {
+    double model_view[16], projection[16];
+    double width;            /* in the units of half_extent: pixels when half_extent = (viewport w / 2, h / 2) */
+    double half_extent[2];
+    double w_min;            /* > 0: the segment is cut where clip w falls below it (the near plane's w = znear) */
+} trgl_line_params;
+int trgl_line_stage(trgl_ctx* ctx, const trgl_line_params* params, const double* points, int point_stride, uint64_t n_points,
+                    const uint32_t* indices, const uint32_t* colors, uint64_t n_segments, int mem_kind,
+                    double* clip_out, double* vary_out, uint32_t* colors_out);
+int trgl_draw_lines(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms, const trgl_line_params* params,
+                    const double* points, int point_stride, uint64_t n_points, const uint32_t* indices, const uint32_t* colors,
+                    uint64_t n_segments, int mem_kind);
+
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 
 /* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and
@@ -645,7 +734,7 @@ int trgl_flush(trgl_ctx* ctx);
  * flush first, with two exceptions.  The five calls that only queue work over caller-owned device arrays and flush
  * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths, trgl_depth_order and trgl_triangle_depths with
  * TRGL_MEM_DEVICE - leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those five,
- * trgl_clip_stage, trgl_order_stage, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
+ * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
  * computes on the host and returns without touching the context's queue.  A call refused for its arguments or for the
  * context's state may return before it completes anything.
  * bench.py: the RCCL gather of the previous frame's strips runs under the next frame's first half. */

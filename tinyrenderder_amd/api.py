@@ -42,6 +42,7 @@ INST_BLOCK, INST_SCAN_CHUNK, INST_VS_FACES = 256, 256, 64
 ORDER_BACK_TO_FRONT, ORDER_FRONT_TO_BACK = 0, 1     # TRGL_ORDER_*
 TRI_DEPTH_CENTROID, TRI_DEPTH_NEAREST, TRI_DEPTH_FARTHEST = 0, 1, 2     # TRGL_TRI_DEPTH_*
 CENTROID, NEAREST, FARTHEST = TRI_DEPTH_CENTROID, TRI_DEPTH_NEAREST, TRI_DEPTH_FARTHEST
+SPRITE_VIEW, SPRITE_SCREEN = 0, 1     # TRGL_SPRITE_*: a sprite's size in eye-space units, or in units of the caller's scale[]
 FRUSTUM_SET, FRUSTUM_MERGE = 0, 1     # TRGL_FRUSTUM_*: the mode of trgl_frustum_boxes
 NEAR_PLANE = (0.0, 0.0, 1.0, 1.0)     # the near plane of the reference's projection in clip space: z + w >= 0
 FRUSTUM_LEFT, FRUSTUM_RIGHT, FRUSTUM_BOTTOM, FRUSTUM_TOP, FRUSTUM_NEAR, FRUSTUM_FAR = range(6)   # Frustum::PlaneIndex (our_gl.h:71-78)
@@ -70,6 +71,7 @@ SYMBOLS = [
     "trgl_instance_depths", "trgl_depth_order", "trgl_draw_instanced_ordered", "trgl_instance_stage_ordered",
     "trgl_instance_boxes", "trgl_frustum_boxes",
     "trgl_triangle_depths", "trgl_order_stage", "trgl_draw_ordered",
+    "trgl_sprite_stage", "trgl_draw_sprites", "trgl_line_stage", "trgl_draw_lines",
     "trgl_mip_layout", "trgl_image_mipmaps", "trgl_texture_mipmaps", "trgl_selftest_sampler_lod", "trgl_image_sample", "trgl_lod_stage", "trgl_selftest_mip_lod",
 ]
 MAX_MIP_LEVELS = 16
@@ -291,6 +293,12 @@ def load_library(path: str = None):
     L.trgl_image_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
     L.trgl_selftest_mip_lod.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p]
     L.trgl_lod_stage.argtypes = [vp, dp, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.trgl_sprite_stage.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.trgl_draw_sprites.argtypes = [vp, C.c_int, C.POINTER(Uniforms), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int]
+    L.trgl_line_stage.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.trgl_draw_lines.argtypes = [vp, C.c_int, C.POINTER(Uniforms), C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                                  C.c_uint64, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -849,6 +857,109 @@ def order_stage(clip, varyings=None, colors=None, order=(), group=1):
     return _order_stage(load_library(), None, clip, varyings, colors, order, group, False, None)[1]
 
 
+class SpriteParams(C.Structure):
+    """trgl_sprite_params"""
+    _fields_ = [("model_view", C.c_double * 16), ("projection", C.c_double * 16), ("size", C.c_double), ("scale", C.c_double * 2),
+                ("mode", C.c_int32), ("size_offset", C.c_int32), ("attr_offset", C.c_int32), ("n_attr", C.c_int32)]
+
+
+class LineParams(C.Structure):
+    """trgl_line_params"""
+    _fields_ = [("model_view", C.c_double * 16), ("projection", C.c_double * 16), ("width", C.c_double), ("half_extent", C.c_double * 2),
+                ("w_min", C.c_double)]
+
+
+def make_sprite_params(model_view, projection, size=1.0, scale=(0.0, 0.0), mode=SPRITE_VIEW, size_offset=-1, attr_offset=0, n_attr=0):
+    """trgl_sprite_params: row-major 4x4 matrices; size is used when size_offset < 0, else the point's size is column size_offset of its
+    row; scale = (2 / w, 2 / h) gives SPRITE_SCREEN sizes in pixels of a w x h viewport; n_attr columns from attr_offset on follow the
+    uv pairs in the varyings of both triangles."""
+    return SpriteParams((C.c_double * 16)(*_f64(model_view, 16, "model_view")), (C.c_double * 16)(*_f64(projection, 16, "projection")),
+                        float(size), (C.c_double * 2)(*_f64(scale, 2, "scale")), int(mode), int(size_offset), int(attr_offset), int(n_attr))
+
+
+def make_line_params(model_view, projection, width, half_extent, w_min):
+    """trgl_line_params: width in the units of half_extent (pixels with half_extent = (w / 2, h / 2) of the viewport); the segment is cut
+    where its clip w falls below w_min > 0."""
+    return LineParams((C.c_double * 16)(*_f64(model_view, 16, "model_view")), (C.c_double * 16)(*_f64(projection, 16, "projection")),
+                      float(width), (C.c_double * 2)(*_f64(half_extent, 2, "half_extent")), float(w_min))
+
+
+def _quad_inputs(points, indices, colors, device):
+    """(points, indices, colors) as the sprite and line calls take them, checked: device tensors with device=True, else numpy arrays."""
+    if device:
+        _device_f64(points, 2, "points")
+        for a, what in ((indices, "indices"), (colors, "colors")):
+            if a is not None and (not _is_device_tensor(a) or a.element_size() != 4 or not a.is_contiguous()):
+                raise ValueError(f"device=True: {what} must be a contiguous 32-bit device tensor")
+        return points, indices, colors
+    points = np.ascontiguousarray(points, np.float64)
+    if points.ndim != 2:
+        raise ValueError("points must have 2 dimensions [n, stride]")
+    return (points, None if indices is None else np.ascontiguousarray(indices, np.uint32).reshape(-1),
+            None if colors is None else np.ascontiguousarray(colors, np.uint32).reshape(-1))
+
+
+def _quad_outputs(points, colors, n, K, device, out):
+    """(clip_out [2 n, 12], varyings_out [2 n, K], colors_out [2 n] or None) for n quads"""
+    if out is not None:
+        return out
+    if device:
+        import torch
+        return (torch.empty((2 * n, 12), dtype=torch.float64, device=points.device), torch.empty((2 * n, K), dtype=torch.float64, device=points.device),
+                None if colors is None else torch.empty(2 * n, dtype=colors.dtype, device=points.device))
+    return np.empty((2 * n, 12), np.float64), np.empty((2 * n, K), np.float64), None if colors is None else np.empty(2 * n, np.uint32)
+
+
+def _sprite_stage(L, handle, params, points, colors, device, out):
+    """Returns (arrays to keep alive, (clip_out, varyings_out, colors_out)) - two rows per point."""
+    points, _, colors = _quad_inputs(points, None, colors, device)
+    n, stride = int(points.shape[0]), int(points.shape[1])
+    if colors is not None and int(colors.shape[0]) != n:
+        raise ValueError("colors: one per point")
+    out = _quad_outputs(points, colors, n, 6 + max(int(params.n_attr), 0), device, out)
+    p = _device_ptr if device else _ptr
+    rc = L.trgl_sprite_stage(handle, C.byref(params), p(points), stride, p(colors), n, MEM_DEVICE if device else MEM_HOST,
+                             p(out[0]), p(out[1]), p(out[2]))
+    if rc != 0:
+        raise TrglError(f"trgl_sprite_stage failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (points, colors), out
+
+
+def _line_segments(points, indices, n_segments):
+    if n_segments is not None:
+        return int(n_segments)
+    return int(points.shape[0]) // 2 if indices is None else int(indices.numel() if hasattr(indices, "numel") else indices.size) // 2
+
+
+def _line_stage(L, handle, params, points, indices, colors, n_segments, device, out):
+    """Returns (arrays to keep alive, (clip_out, varyings_out, colors_out)) - two rows per segment."""
+    points, indices, colors = _quad_inputs(points, indices, colors, device)
+    n_points, stride = int(points.shape[0]), int(points.shape[1])
+    n = _line_segments(points, indices, n_segments)
+    if colors is not None and int(colors.shape[0]) != n:
+        raise ValueError("colors: one per segment")
+    out = _quad_outputs(points, colors, n, 6, device, out)
+    p = _device_ptr if device else _ptr
+    rc = L.trgl_line_stage(handle, C.byref(params), p(points), stride, n_points, p(indices), p(colors), n, MEM_DEVICE if device else MEM_HOST,
+                           p(out[0]), p(out[1]), p(out[2]))
+    if rc != 0:
+        raise TrglError(f"trgl_line_stage failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (points, indices, colors), out
+
+
+def sprite_stage(params, points, colors=None):
+    """trgl_sprite_stage for host arrays without a context: every point [n, stride >= 3] becomes a quad of two triangles that faces the
+    camera (params: make_sprite_params).  Returns (clip [2 n, 12], varyings [2 n, 6 + n_attr], colors [2 n] or None).  Needs no GPU."""
+    return _sprite_stage(load_library(), None, params, points, colors, False, None)[1]
+
+
+def line_stage(params, points, indices=None, colors=None, n_segments=None):
+    """trgl_line_stage for host arrays without a context: every segment - a pair of `indices` into points [n_points, stride >= 3], or
+    points 2 j and 2 j + 1 - becomes a quad of params.width (params: make_line_params), cut at clip w = w_min.  Returns (clip [2 n, 12],
+    varyings [2 n, 6], colors [2 n] or None).  Needs no GPU."""
+    return _line_stage(load_library(), None, params, points, indices, colors, n_segments, False, None)[1]
+
+
 def _device_f64(t, ndim, what):
     if not _is_device_tensor(t) or str(t.dtype) != "torch.float64" or not t.is_contiguous() or t.dim() != ndim:
         raise ValueError(f"{what} must be a contiguous float64 device tensor with {ndim} dimensions (the other arrays are in device memory)")
@@ -1394,6 +1505,45 @@ class Context:
         if device:
             self._keep.append((keep, out))
         return out
+
+    def sprite_stage(self, params, points, colors=None, device=False, out=None):
+        """trgl_sprite_stage: two triangles per point (see the module's sprite_stage).  Host arrays: numpy, no GPU work.  device=True:
+        points [n, stride] f64 and colors [n] (32-bit) or None are device tensors, out = (clip_out, varyings_out, colors_out) device
+        tensors with 2 n rows (allocated with torch when not given); the stage is queued on the context's stream without waiting.
+        Returns (clip_out, varyings_out, colors_out) - what triangle_depths(group=2), order_stage and draw(device=True) take."""
+        keep, out = _sprite_stage(self.L, self.h, params, points, colors, device, out)
+        if device:
+            self._keep.append((keep, out))
+        return out
+
+    def line_stage(self, params, points, indices=None, colors=None, n_segments=None, device=False, out=None):
+        """trgl_line_stage: two triangles per segment (see the module's line_stage).  device=True: points [n_points, stride] f64, indices
+        [2 n] and colors [n] (32-bit) or None are device tensors; an index that names no point gives all-zero rows; queued on the
+        context's stream without waiting.  Returns (clip_out, varyings_out, colors_out)."""
+        keep, out = _line_stage(self.L, self.h, params, points, indices, colors, n_segments, device, out)
+        if device:
+            self._keep.append((keep, out))
+        return out
+
+    def draw_sprites(self, kind, params, points, colors=None, uniforms=None, device=False):
+        """trgl_draw_sprites: draw() of the rows sprite_stage makes; the kind takes 6 + n_attr varyings, or none.  device=True: the
+        points are expanded on the context's stream into buffers of the context's (no wait); they are read then, not at the flush."""
+        points, _, colors = _quad_inputs(points, None, colors, device)
+        p = _device_ptr if device else _ptr
+        if device:
+            self._keep.append((points, colors))
+        self._chk(self.L.trgl_draw_sprites(self.h, kind, None if uniforms is None else C.byref(uniforms), C.byref(params), p(points),
+                                           int(points.shape[1]), p(colors), int(points.shape[0]), MEM_DEVICE if device else MEM_HOST))
+
+    def draw_lines(self, kind, params, points, indices=None, colors=None, n_segments=None, uniforms=None, device=False):
+        """trgl_draw_lines: draw() of the rows line_stage makes; the kind takes 6 varyings - (t, side) per vertex - or none."""
+        points, indices, colors = _quad_inputs(points, indices, colors, device)
+        p = _device_ptr if device else _ptr
+        if device:
+            self._keep.append((points, indices, colors))
+        self._chk(self.L.trgl_draw_lines(self.h, kind, None if uniforms is None else C.byref(uniforms), C.byref(params), p(points),
+                                         int(points.shape[1]), int(points.shape[0]), p(indices), p(colors),
+                                         _line_segments(points, indices, n_segments), MEM_DEVICE if device else MEM_HOST))
 
     def instance_boxes(self, local, instances, out=None):
         """trgl_instance_boxes: the world box [n, 6] = (min.xyz, max.xyz) of every instance [n, stride >= 16], AABB::transform of `local`

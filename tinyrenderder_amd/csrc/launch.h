@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -225,6 +225,27 @@ hipError_t launch_depth_order(hipStream_t s, const double* depths, uint32_t n, b
 // time where they and row_bytes allow it.  0 < n_order, n_order * g < 2^31, G * g < 2^31.
 void launch_triangle_depths(hipStream_t s, const double* clip, uint32_t G, uint32_t g, int mode, double* depths);
 void launch_gather_rows(hipStream_t s, const void* in, void* out, uint32_t row_bytes, const uint32_t* order, uint32_t n_order, uint32_t G, uint32_t g);
+
+// Point sprites and wide lines (kernels_sprite.hip; both are written down at trgl_sprite_stage / trgl_line_stage in include/trgl.h, the
+// arithmetic is sprite_core.h's).  One launch per call: a block computes SPRITE_BLOCK quads, one per lane, and its lanes then store the
+// block's rows as contiguous memory.  points 8-byte aligned, colours and indices 4; clip_out / vary_out 8-byte aligned (moved 16 bytes
+// at a time where 16-byte aligned); vary_out null: no varyings; colors null: colors_out is not written.  0 < n, 2 n < 2^31.  The
+// structs travel as the kernels' arguments.
+constexpr int SPRITE_BLOCK = 256;
+struct SpriteArgs {
+    trgl_sprite_params P;
+    const double* points; const uint32_t* colors;
+    double* clip_out; double* vary_out; uint32_t* colors_out;
+    uint64_t n; int32_t stride;
+};
+struct LineArgs {
+    trgl_line_params P;
+    const double* points; const uint32_t* indices; const uint32_t* colors;      // indices null: segment j = points 2 j, 2 j + 1
+    double* clip_out; double* vary_out; uint32_t* colors_out;
+    uint64_t n_points, n; int32_t stride;
+};
+void launch_sprite_stage(hipStream_t s, const SpriteArgs& a);
+void launch_line_stage(hipStream_t s, const LineArgs& a);
 
 // World boxes of instances and frustum codes of boxes (kernels_scene.hip; both are written down at trgl_instance_boxes /
 // trgl_frustum_boxes in include/trgl.h, the arithmetic is scene_core.h's).  One thread per instance or box, 0 < n < 2^31; doubles 8-byte

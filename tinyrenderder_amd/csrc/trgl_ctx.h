@@ -198,6 +198,12 @@ bool host_depth_order(const double* depths, uint64_t n, bool front_to_back, uint
 void host_triangle_depths(const double* clip, uint64_t G, uint32_t g, int mode, double* depths);
 void host_order_stage(int K, const double* clip, const double* vary, const uint32_t* colors, const uint32_t* order, uint64_t n_order, uint32_t g,
                       double* clip_out, double* vary_out, uint32_t* colors_out);
+// trgl_sprite_stage and trgl_line_stage over host arrays (vary_out null: no varyings; colors null: colors_out is not written; every
+// index of a line list checked: below n_points)
+void host_sprite_stage(const trgl_sprite_params& P, const double* points, int stride, const uint32_t* colors, uint64_t n,
+                       double* clip_out, double* vary_out, uint32_t* colors_out);
+void host_line_stage(const trgl_line_params& P, const double* points, int stride, const uint32_t* indices, const uint32_t* colors, uint64_t n,
+                     double* clip_out, double* vary_out, uint32_t* colors_out);
 // trgl_instance_boxes and trgl_frustum_boxes over host arrays (local_stride 0: one local box for every instance)
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out);
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);

@@ -18,6 +18,7 @@
 #include "occlusion_core.h"
 #include "scene_core.h"
 #include "triorder_core.h"
+#include "sprite_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -261,6 +262,43 @@ void host_order_stage(int K, const double* clip, const double* vary, const uint3
         std::memcpy(clip_out + dst * 12, clip + src * 12, (size_t)g * 12 * sizeof(double));
         if (K) std::memcpy(vary_out + dst * (uint64_t)K, vary + src * (uint64_t)K, (size_t)g * (size_t)K * sizeof(double));
         if (colors) std::memcpy(colors_out + dst, colors + src, (size_t)g * sizeof(uint32_t));
+    }
+}
+
+// ---- point sprites and wide lines in host memory (include/trgl.h, trgl_sprite_stage / trgl_line_stage; the arithmetic and the tables
+// of the two output rows are sprite_core.h's) -------------------------------------------------------------------------------------------
+// rows 2 i and 2 i + 1 of the outputs from quad q; attr: the n_attr doubles behind the pairs (vary_out null: no varyings)
+static void host_quad_rows(const SpriteQuad& q, uint64_t i, uint32_t color, const double* attr, int n_attr,
+                           double* clip_out, double* vary_out, uint32_t* colors_out) {
+    for (int r = 0; r < 24; ++r) clip_out[i * 24 + r] = q.k[quad_clip_index(r)];
+    const uint64_t K = 6 + (uint64_t)n_attr;
+    for (int tri = 0; vary_out && tri < 2; ++tri) {
+        double* row = vary_out + (2 * i + tri) * K;
+        for (int c = 0; c < 6; ++c) row[c] = quad_vary(q.ta, q.tb, q.one, quad_vary_sel(tri, c));
+        if (n_attr) std::memcpy(row + 6, attr, (size_t)n_attr * sizeof(double));
+    }
+    if (colors_out) colors_out[2 * i] = colors_out[2 * i + 1] = color;
+}
+
+void host_sprite_stage(const trgl_sprite_params& P, const double* points, int stride, const uint32_t* colors, uint64_t n,
+                       double* clip_out, double* vary_out, uint32_t* colors_out) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const double* row = points + i * (uint64_t)stride;
+        SpriteQuad q;
+        sprite_quad(P, row[0], row[1], row[2], P.size_offset >= 0 ? row[P.size_offset] : P.size, &q);
+        host_quad_rows(q, i, colors ? colors[i] : 0u, row + P.attr_offset, P.n_attr, clip_out, vary_out, colors ? colors_out : nullptr);
+    }
+}
+
+// every index is below n_points (checked by the caller)
+void host_line_stage(const trgl_line_params& P, const double* points, int stride, const uint32_t* indices, const uint32_t* colors, uint64_t n,
+                     double* clip_out, double* vary_out, uint32_t* colors_out) {
+    for (uint64_t j = 0; j < n; ++j) {
+        const uint64_t ia = indices ? indices[2 * j] : 2 * j, ib = indices ? indices[2 * j + 1] : 2 * j + 1;
+        SpriteQuad q;
+        const double* a = points + ia * (uint64_t)stride; const double* b = points + ib * (uint64_t)stride;
+        line_quad(P, a[0], a[1], a[2], b[0], b[1], b[2], &q);
+        host_quad_rows(q, j, (colors && q.one != 0.0) ? colors[j] : 0u, nullptr, 0, clip_out, vary_out, colors ? colors_out : nullptr);
     }
 }
 

@@ -1,7 +1,7 @@
 // trgl_shader.cpp — run-time shader registration (fragment kinds and vertex shaders, compiled by user_shaders.cpp) and the entry points
 // that run a stage in front of a draw: the vertex stage over an indexed mesh (trgl_draw_indexed, trgl_draw_indexed_vs, trgl_vertex_stage)
 // the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and the instanced stages (trgl_draw_instanced,
-// trgl_instance_stage, their ordered forms, and the depths and order those take: trgl_instance_depths, trgl_depth_order) and the ordered triangle draw (trgl_triangle_depths, trgl_order_stage, trgl_draw_ordered).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
+// trgl_instance_stage, their ordered forms, and the depths and order those take: trgl_instance_depths, trgl_depth_order) the ordered triangle draw (trgl_triangle_depths, trgl_order_stage, trgl_draw_ordered) and the sprite and line stages (trgl_sprite_stage, trgl_draw_sprites, trgl_line_stage, trgl_draw_lines).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <cstring>
 #include <memory>
 #include <new>
@@ -400,7 +400,174 @@ static int queue_order_stage(trgl_ctx* c, int K, const double* clip, const doubl
     return TRGL_OK;
 }
 
+// ---- point sprites and wide lines (include/trgl.h: trgl_sprite_stage, trgl_draw_sprites, trgl_line_stage, trgl_draw_lines) ----
+// The inputs of either stage: n primitives over n_points rows of `stride` doubles (sprites: n_points == n, no indices)
+struct QuadInputs { const double* points; int stride; uint64_t n_points; const uint32_t* indices; const uint32_t* colors; uint64_t n; int mem_kind; };
+
+static bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// what the scalars of a sprite call must satisfy; *K = 6 + n_attr
+static int check_sprite_params(trgl_ctx* c, const std::string& w, const trgl_sprite_params* P, int stride, int mem_kind, uint64_t n, int* K) {
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    if (P->mode != TRGL_SPRITE_VIEW && P->mode != TRGL_SPRITE_SCREEN) return fail(c, TRGL_E_INVALID, w + "bad mode");
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, w + "TRGL_MEM_DEVICE needs a context");
+    if (stride < 3) return fail(c, TRGL_E_INVALID, w + "point stride must be >= 3 doubles");
+    if (P->size_offset >= stride) return fail(c, TRGL_E_INVALID, w + "size_offset is outside the point's row");
+    if (P->n_attr < 0 || (P->n_attr && (P->attr_offset < 0 || (int64_t)P->attr_offset + P->n_attr > stride)))
+        return fail(c, TRGL_E_INVALID, w + "the attribute range is outside the point's row");
+    if (6 + (int64_t)P->n_attr > TRGL_MAX_USER_VARY) return fail(c, TRGL_E_INVALID, w + "6 + n_attr is above TRGL_MAX_USER_VARY");
+    if (n > 0x3fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more triangles in one call");
+    *K = 6 + P->n_attr;
+    return TRGL_OK;
+}
+
+static int check_line_params(trgl_ctx* c, const std::string& w, const trgl_line_params* P, const QuadInputs& in) {
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    if (!valid_mem_kind(in.mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if (in.mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, w + "TRGL_MEM_DEVICE needs a context");
+    if (in.stride < 3) return fail(c, TRGL_E_INVALID, w + "point stride must be >= 3 doubles");
+    if (!(P->w_min > 0.0) || !(P->w_min - P->w_min == 0.0)) return fail(c, TRGL_E_INVALID, w + "w_min must be positive and finite");
+    if (in.n > 0x3fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more triangles in one call");
+    if (!in.indices && 2 * in.n > in.n_points) return fail(c, TRGL_E_INVALID, w + "without indices 2 * n_segments points are needed");
+    return TRGL_OK;
+}
+
+// ... and its arrays (n > 0): present, aligned, outputs apart from inputs; with host memory every index of a line list in range.
+// K: the varyings per row when vary_out is given.
+static int check_quad_arrays(trgl_ctx* c, const std::string& w, const QuadInputs& in, int K, const double* clip_out, const double* vary_out,
+                             const uint32_t* colors_out) {
+    if (!in.points || !clip_out || (in.colors && !colors_out)) return fail(c, TRGL_E_INVALID, w + "null array");
+    if ((((uintptr_t)in.points | (uintptr_t)clip_out | (uintptr_t)vary_out) & 7) ||
+        (((uintptr_t)in.colors | (uintptr_t)in.indices | (in.colors ? (uintptr_t)colors_out : 0)) & 3))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 4 for colours and indices)");
+    const struct { const void* p; uint64_t bytes; } ins[3] = { { in.points, in.n_points * (uint64_t)in.stride * 8 }, { in.colors, in.n * 4 },
+                                                              { in.indices, in.n * 8 } },
+                                                    outs[3] = { { clip_out, in.n * 192 }, { vary_out, in.n * 16 * (uint64_t)K },
+                                                                { in.colors ? colors_out : nullptr, in.n * 8 } };
+    for (const auto& i : ins)
+        for (const auto& o : outs)
+            if (ranges_overlap(i.p, i.bytes, o.p, o.bytes)) return fail(c, TRGL_E_INVALID, w + "an output overlaps an input");
+    for (int x = 0; x < 3; ++x)
+        for (int y = x + 1; y < 3; ++y)
+            if (ranges_overlap(outs[x].p, outs[x].bytes, outs[y].p, outs[y].bytes)) return fail(c, TRGL_E_INVALID, w + "two outputs overlap");
+    if (in.mem_kind == TRGL_MEM_HOST && in.indices)
+        for (uint64_t k = 0; k < 2 * in.n; ++k)
+            if (in.indices[k] >= in.n_points) return fail(c, TRGL_E_INVALID, w + "index out of range");
+    return TRGL_OK;
+}
+
+static int queue_sprite_stage(trgl_ctx* c, const trgl_sprite_params& P, const QuadInputs& in, double* clip_out, double* vary_out, uint32_t* colors_out) {
+    SpriteArgs a; std::memset(&a, 0, sizeof(a));
+    a.P = P; a.points = in.points; a.colors = in.colors; a.clip_out = clip_out; a.vary_out = vary_out; a.colors_out = in.colors ? colors_out : nullptr;
+    a.n = in.n; a.stride = in.stride;
+    launch_sprite_stage(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+static int queue_line_stage(trgl_ctx* c, const trgl_line_params& P, const QuadInputs& in, double* clip_out, double* vary_out, uint32_t* colors_out) {
+    LineArgs a; std::memset(&a, 0, sizeof(a));
+    a.P = P; a.points = in.points; a.indices = in.indices; a.colors = in.colors;
+    a.clip_out = clip_out; a.vary_out = vary_out; a.colors_out = in.colors ? colors_out : nullptr;
+    a.n_points = in.n_points; a.n = in.n; a.stride = in.stride;
+    launch_line_stage(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+// What trgl_sprite_stage (lines null) and trgl_line_stage share once their scalars are checked
+static int quad_stage_call(trgl_ctx* c, const std::string& w, const trgl_sprite_params* sprites, const trgl_line_params* lines, const QuadInputs& in,
+                           int K, double* clip_out, double* vary_out, uint32_t* colors_out) {
+    if (in.n == 0) return TRGL_OK;
+    if (sprites && sprites->n_attr && !vary_out) return fail(c, TRGL_E_INVALID, w + "vary_out is null and n_attr is not 0");
+    int r;
+    if ((r = check_quad_arrays(c, w, in, K, clip_out, vary_out, colors_out))) return r;
+    if (in.mem_kind == TRGL_MEM_HOST) {
+        if (sprites) host_sprite_stage(*sprites, in.points, in.stride, in.colors, in.n, clip_out, vary_out, colors_out);
+        else host_line_stage(*lines, in.points, in.stride, in.indices, in.colors, in.n, clip_out, vary_out, colors_out);
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    return sprites ? queue_sprite_stage(c, *sprites, in, clip_out, vary_out, colors_out) : queue_line_stage(c, *lines, in, clip_out, vary_out, colors_out);
+}
+
+// ... and trgl_draw_sprites / trgl_draw_lines: the scalars are checked, K is the stage's
+static int quad_draw_call(trgl_ctx* c, const std::string& w, const char* who, int kind, const trgl_uniforms* u, const trgl_sprite_params* sprites,
+                          const trgl_line_params* lines, const QuadInputs& in, int K) {
+    // (what trgl_draw would refuse is refused before anything is queued)
+    const int kind_K = kind_vary_count(c, kind);
+    if (kind_K < 0) return fail(c, TRGL_E_INVALID, w + "unknown shader kind");
+    if (kind_K != K && !(kind_K == 0 && K == 6)) return fail(c, TRGL_E_INVALID, w + "the shader kind's number of varyings does not fit the stage's");
+    int r;
+    if ((r = check_kind_uniforms(c, who, kind, u))) return r;
+    if (in.n == 0) return TRGL_OK;
+    const uint64_t rows = 2 * in.n;
+    if (in.mem_kind == TRGL_MEM_HOST) {
+        try {
+            std::vector<double> oclip(rows * 12), ovary(rows * (size_t)kind_K);
+            std::vector<uint32_t> ocol(in.colors ? rows : 0);
+            if ((r = quad_stage_call(c, w, sprites, lines, in, K, oclip.data(), kind_K ? ovary.data() : nullptr, in.colors ? ocol.data() : nullptr))) return r;
+            return trgl_draw(c, kind, u, oclip.data(), kind_K ? ovary.data() : nullptr, in.colors ? ocol.data() : nullptr, rows, TRGL_MEM_HOST);
+        } catch (const std::bad_alloc&) {
+            return fail(c, TRGL_E_NOMEM, w + "out of memory");
+        }
+    }
+    if (!in.points) return fail(c, TRGL_E_INVALID, w + "null array");
+    StageHold hold(c);
+    void* p = nullptr;
+    double* oclip = nullptr; double* ovary = nullptr; uint32_t* ocol = nullptr;
+    if ((r = stage_alloc(c, rows * 12 * sizeof(double), &p))) return r;
+    oclip = (double*)p;
+    if (kind_K) { if ((r = stage_alloc(c, rows * (size_t)kind_K * sizeof(double), &p))) return r; ovary = (double*)p; }
+    if (in.colors) { if ((r = stage_alloc(c, rows * sizeof(uint32_t), &p))) return r; ocol = (uint32_t*)p; }
+    if ((r = quad_stage_call(c, w, sprites, lines, in, K, oclip, ovary, ocol))) return r;
+    return trgl_draw(c, kind, u, oclip, ovary, ocol, rows, TRGL_MEM_DEVICE);
+}
+
 extern "C" {
+
+int trgl_sprite_stage(trgl_ctx* c, const trgl_sprite_params* P, const double* points, int stride, const uint32_t* colors, uint64_t n, int mem_kind,
+                      double* clip_out, double* vary_out, uint32_t* colors_out) {
+    const std::string w = "trgl_sprite_stage: ";
+    int K = 0;
+    if (int r = check_sprite_params(c, w, P, stride, mem_kind, n, &K)) return r;
+    const QuadInputs in{ points, stride, n, nullptr, colors, n, mem_kind };
+    return quad_stage_call(c, w, P, nullptr, in, K, clip_out, vary_out, colors_out);
+}
+
+int trgl_draw_sprites(trgl_ctx* c, int kind, const trgl_uniforms* u, const trgl_sprite_params* P, const double* points, int stride,
+                      const uint32_t* colors, uint64_t n, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_draw_sprites: ";
+    int K = 0;
+    if ((r = check_sprite_params(c, w, P, stride, mem_kind, n, &K))) return r;
+    const QuadInputs in{ points, stride, n, nullptr, colors, n, mem_kind };
+    return quad_draw_call(c, w, "trgl_draw_sprites", kind, u, P, nullptr, in, K);
+}
+
+int trgl_line_stage(trgl_ctx* c, const trgl_line_params* P, const double* points, int stride, uint64_t n_points, const uint32_t* indices,
+                    const uint32_t* colors, uint64_t n_segments, int mem_kind, double* clip_out, double* vary_out, uint32_t* colors_out) {
+    const std::string w = "trgl_line_stage: ";
+    const QuadInputs in{ points, stride, n_points, indices, colors, n_segments, mem_kind };
+    if (int r = check_line_params(c, w, P, in)) return r;
+    return quad_stage_call(c, w, nullptr, P, in, 6, clip_out, vary_out, colors_out);
+}
+
+int trgl_draw_lines(trgl_ctx* c, int kind, const trgl_uniforms* u, const trgl_line_params* P, const double* points, int stride, uint64_t n_points,
+                    const uint32_t* indices, const uint32_t* colors, uint64_t n_segments, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_draw_lines: ";
+    const QuadInputs in{ points, stride, n_points, indices, colors, n_segments, mem_kind };
+    if ((r = check_line_params(c, w, P, in))) return r;
+    return quad_draw_call(c, w, "trgl_draw_lines", kind, u, nullptr, P, in, 6);
+}
 
 int trgl_triangle_depths(trgl_ctx* c, const double* clip, uint64_t n, uint32_t group, int mode, int mem_kind, double* depths_out) {
     const std::string w = "trgl_triangle_depths: ";

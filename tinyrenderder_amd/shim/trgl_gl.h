@@ -660,6 +660,82 @@ inline bool gl_draw_ordered(const Triangle* clip, std::size_t n, const IShader& 
     return ok;
 }
 
+// Point sprites and wide lines (include/trgl.h, trgl_sprite_stage / trgl_line_stage): a point or a segment becomes the two triangles of a
+// quad under the globals ModelView, Perspective and Viewport as they stand at the call - what a caller of the reference would build by
+// hand in front of its rasterize() loop.
+// gl_sprite_params: size in eye-space units (TRGL_SPRITE_VIEW) or in pixels of the global Viewport (TRGL_SPRITE_SCREEN); size_offset >= 0
+// takes each point's size from that column of its row instead.  gl_line_params: width in pixels of the global Viewport; the segment is
+// cut where its clip w falls below w_min (init_perspective's znear).
+inline trgl_sprite_params gl_sprite_params(double size, int mode = TRGL_SPRITE_VIEW, int size_offset = -1, int attr_offset = 0, int n_attr = 0) {
+    trgl_sprite_params p{};
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { p.model_view[4 * r + c] = ModelView[r][c]; p.projection[4 * r + c] = Perspective[r][c]; }
+    p.size = size; p.scale[0] = 1.0 / Viewport[0][0]; p.scale[1] = 1.0 / Viewport[1][1];
+    p.mode = mode; p.size_offset = size_offset; p.attr_offset = attr_offset; p.n_attr = n_attr;
+    return p;
+}
+inline trgl_line_params gl_line_params(double width, double w_min) {
+    trgl_line_params p{};
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { p.model_view[4 * r + c] = ModelView[r][c]; p.projection[4 * r + c] = Perspective[r][c]; }
+    p.width = width; p.half_extent[0] = Viewport[0][0]; p.half_extent[1] = Viewport[1][1]; p.w_min = w_min;
+    return p;
+}
+// The stages alone, on the host, no context needed: clip_out receives 2 n Triangles as 12 doubles each (reinterpret_cast<const Triangle*>
+// (clip_out.data()) is what rasterize() takes), vary_out 2 n rows of 6 + n_attr (lines: 6) varyings; a call that fails (gl_last_error())
+// leaves the vectors empty.
+inline bool gl_sprite_stage(const trgl_sprite_params& params, const double* points, int stride, std::size_t n,
+                            std::vector<double>& clip_out, std::vector<double>& vary_out) {
+    static_assert(sizeof(Triangle) == 12 * sizeof(double), "Triangle must be 12 packed doubles");
+    clip_out.assign(2 * n * 12, 0.0);
+    vary_out.assign(2 * n * std::size_t(6 + (params.n_attr > 0 ? params.n_attr : 0)), 0.0);
+    const int rc = trgl_sprite_stage(nullptr, &params, points, stride, nullptr, n, TRGL_MEM_HOST, clip_out.data(), vary_out.data(), nullptr);
+    if (rc != TRGL_OK) { clip_out.clear(); vary_out.clear(); return trgl_shim::fail("gl_sprite_stage", rc, nullptr); }
+    return true;
+}
+inline bool gl_line_stage(const trgl_line_params& params, const double* points, int stride, std::size_t n_points, const std::uint32_t* indices,
+                          std::size_t n_segments, std::vector<double>& clip_out, std::vector<double>& vary_out) {
+    clip_out.assign(2 * n_segments * 12, 0.0);
+    vary_out.assign(2 * n_segments * 6, 0.0);
+    const int rc = trgl_line_stage(nullptr, &params, points, stride, n_points, indices, nullptr, n_segments, TRGL_MEM_HOST,
+                                   clip_out.data(), vary_out.data(), nullptr);
+    if (rc != TRGL_OK) { clip_out.clear(); vary_out.clear(); return trgl_shim::fail("gl_line_stage", rc, nullptr); }
+    return true;
+}
+// gl_draw_sprites / gl_draw_lines: the stage and `for t in 0 .. 2 n - 1: rasterize(quad triangle t, shader, framebuffer)` in one call.
+// The shader's describe() is taken once: its kind takes no varyings, or the 6 + n_attr (lines: 6) that the stage makes; colors: one per
+// point or segment, or null for the descriptor's colour.  A set clip plane is TRGL_E_UNSUPPORTED: these draws are not clipped.
+namespace trgl_shim {
+inline bool draw_quads(const char* who, const IShader& shader, TGAImage& framebuffer, std::size_t n, const std::uint32_t* colors,
+                       const trgl_sprite_params* sprites, const trgl_line_params* lines, const double* points, int stride, std::size_t n_points,
+                       const std::uint32_t* indices) {
+    State& s = state();
+    if (!bind(framebuffer)) return false;
+    bool ok = submit_batch();                                   // earlier rasterize() calls come first
+    trgl_shader_desc d;
+    if (!shader.describe(d)) {
+        std::fprintf(stderr, "trgl: %s(): needs a shader with a device descriptor\n", who);
+        std::abort();
+    }
+    if (s.clip_on) return fail(who, TRGL_E_UNSUPPORTED, nullptr);
+    std::vector<std::uint32_t> own;
+    if (!colors) { own.assign(n, d.color); colors = own.data(); }
+    double vp[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) vp[4 * r + c] = Viewport[r][c];
+    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) && ok;
+    ok = TRGL_SHIM_OK(sprites ? trgl_draw_sprites(s.ctx, d.kind, &d.uniforms, sprites, points, stride, colors, n, TRGL_MEM_HOST)
+                              : trgl_draw_lines(s.ctx, d.kind, &d.uniforms, lines, points, stride, n_points, indices, colors, n, TRGL_MEM_HOST)) && ok;
+    s.zbuffer_stale_on_host = true;
+    return ok;
+}
+}  // namespace trgl_shim
+inline bool gl_draw_sprites(const trgl_sprite_params& params, const double* points, int stride, std::size_t n, const std::uint32_t* colors,
+                            const IShader& shader, TGAImage& framebuffer) {
+    return trgl_shim::draw_quads("gl_draw_sprites", shader, framebuffer, n, colors, &params, nullptr, points, stride, n, nullptr);
+}
+inline bool gl_draw_lines(const trgl_line_params& params, const double* points, int stride, std::size_t n_points, const std::uint32_t* indices,
+                          std::size_t n_segments, const std::uint32_t* colors, const IShader& shader, TGAImage& framebuffer) {
+    return trgl_shim::draw_quads("gl_draw_lines", shader, framebuffer, n_segments, colors, nullptr, &params, points, stride, n_points, indices);
+}
+
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
 // write_tga_file(), main.cpp:743,773).  The depths follow on demand through the `zbuffer` proxy.
 // false: something submitted since the last gl_flush() failed (gl_last_error()); the pixels hold what could be drawn.
