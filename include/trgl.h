@@ -657,6 +657,79 @@ int trgl_draw_lines(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniform
                     const double* points, int point_stride, uint64_t n_points, const uint32_t* indices, const uint32_t* colors,
                     uint64_t n_segments, int mem_kind);
 
+/* ---- skeletal animation: joint palettes and skinned vertex arrays ------------------------------------------------------------------ */
+
+/* New work: the reference's meshes are rigid (Model::processMesh drops the bones and weights that Assimp delivers, and a vertex is
+ * moved by one matrix only).  trgl_skin_stage makes, from a rest mesh in the reference's Vertex layout (model.h:14-20) and a table of
+ * joint matrices per pose - a PALETTE - one vertex array per pose in the same layout, which trgl_draw_indexed, trgl_draw_indexed_vs,
+ * trgl_draw_instanced, trgl_mesh_bounds, trgl_mesh_normals and trgl_mesh_tangents take as it is.  trgl_pose_palette composes the
+ * palettes from joint hierarchies.  With TRGL_MEM_DEVICE neither the vertices nor the palettes visit the host.
+ *
+ * ARITHMETIC.  fp64, each operation rounded, no contraction or reassociation, IEEE division and square root.
+ * STORED NaNs.  A computed double that is a NaN is stored as 0x7FF8000000000000 (the rule of the sprite stage, for its reason).
+ *
+ * SKINNING.  trgl_skin_params: vertex_stride >= 3 doubles per vertex record; n_influences 1 .. 8 joints per vertex; n_joints
+ * 1 .. 65536 matrices per palette; n_poses >= 1; palette_stride doubles between the palettes of consecutive poses, >= 16 * n_joints,
+ * or 0 when n_poses == 1; flags any of TRGL_SKIN_NORMAL (a direction at +3 of the record), TRGL_SKIN_TANGENT (+8), TRGL_SKIN_BITANGENT
+ * (+11) - each needs a stride that holds its three doubles (6, 11, 14); reserved must be 0.
+ * Vertex v has the joints j_k = joints[v * n_influences + k] and the weights w_k = weights[v * n_influences + k], k = 0 ..
+ * n_influences - 1.  For pose q, M_j is the row-major 4x4 matrix at palette + q * palette_stride + 16 * j.
+ *   BLENDED MATRIX.  B[r][c], r = 0 .. 2, c = 0 .. 3, is the sum, started from +0.0, of w_k * M_{j_k}[r][c] in ascending k: each
+ *     product rounded, then added.  Row 3 of a palette matrix is never read.  Weights are used as given: they are not renormalised
+ *     and a zero weight is not skipped (0 * inf is a NaN here as anywhere).
+ *   POSITION.  out[r] = dot<4>(B[r], (x, y, z, 1.0)) as geometry.h:123-127,187-192 computes it: from 0.0, four products added in order.
+ *   FLAGGED DIRECTIONS.  d' is the same dot with (dx, dy, dz, 0.0); the stored vector is normalized(d') of geometry.h:136-140:
+ *     length = sqrt(dot<3>(d', d')) summed from 0.0; a length of exactly 0 returns d' unchanged, otherwise three true divisions by
+ *     the length.  The matrix is B's 3x3, not its inverse transpose: exact for rotations with uniform scale; a caller who scales
+ *     bones unevenly runs trgl_mesh_normals on the output.
+ *   EVERY OTHER DOUBLE of the record is copied with its 64 bits, NaN payloads included.
+ *   OUTPUT.  Pose q's array begins at out + q * n_vertices * vertex_stride, with the input's stride and layout.  Nothing behind
+ *     n_poses * n_vertices * vertex_stride doubles is written.
+ *   A JOINT NUMBER >= n_joints.  Host memory: TRGL_E_INVALID, and nothing is written.  Device memory: that influence contributes
+ *     nothing (its term is left out of the sum) and the rest of the vertex is computed as defined; the entry is never used as an
+ *     address.  The device list is the caller's responsibility, as everywhere in this header.
+ *
+ * PALETTES.  trgl_pose_palette: parents[j] is -1 for a root, or a joint below j.  For each of n_poses poses, with local_j the matrix at
+ * local + pose * local_stride + 16 * j (local_stride >= 16 * n_joints, or 0 with one pose):
+ *   world_j = local_j for a root, else world_{parents[j]} * local_j;  palette_j = world_j * inverse_bind_j, or world_j when
+ *   inverse_bind is NULL (inverse_bind: n_joints matrices, the same for every pose), stored at palette + pose * palette_stride + 16 * j.
+ * Every product is operator* of mat<4,4> (geometry.h:196-205): element (r, c) summed from 0.0 over ascending k, the product that
+ * trgl_draw_instanced uses for model_view * M_i.  All 16 elements are computed and stored.  A parent that is neither -1 nor below j:
+ * TRGL_E_INVALID with host memory (nothing is written), a root with device memory.
+ *
+ * MEMORY AND ORDER.  One mem_kind covers every array of a call.  Host memory: plain C++, ctx may be NULL, no GPU is touched, complete
+ * on return.  Device memory: vertices, weights, palette, local, inverse_bind and the outputs 8-byte aligned, joints 2, parents 4 -
+ * nothing wider is assumed, and the bytes never depend on the alignment.  One kernel per call, queued on the context's stream in order
+ * with the draws: no wait, nothing is flushed; it completes a begun flush, as trgl_clip_stage does.
+ * ERRORS.  TRGL_E_INVALID: params NULL, a field outside the ranges above, a bad mem_kind, TRGL_MEM_DEVICE without a context, a host
+ * joint or parent out of range, with n_vertices > 0 (n_poses > 0 for the palettes) a null or misaligned array (inverse_bind may be
+ * null), an output that overlaps an input.  TRGL_E_UNSUPPORTED: with device memory a vertex_stride above 5120 doubles, or so many
+ * vertices and poses that the call would need 2^31 blocks or more.  n_vertices == 0 (n_poses == 0): TRGL_OK once the scalars are checked,
+ * and no array is read or written.
+ *
+ * trgl_draw_skinned: trgl_skin_stage with n_poses == 1 into a buffer the context owns until the flush is done (the rule of
+ * trgl_draw_ordered), then trgl_draw_indexed_vs of that buffer with the same vs, shader_kind, uniforms, projection, indices and colors
+ * - or, with vs == -1, trgl_draw_indexed of it (the built-in vertex stage; colors must then be NULL).  Frame bytes, depths and every
+ * counter equal those of the two calls made by hand.  Host arrays are read before the call returns; device arrays follow the rules of
+ * trgl_draw_indexed (the mesh, the joints, the weights and the palette are read when the stages run, not at the flush).  No wait.
+ * Errors: those of the two calls, and n_poses != 1. */
+#define TRGL_SKIN_NORMAL    1u
+#define TRGL_SKIN_TANGENT   2u
+#define TRGL_SKIN_BITANGENT 4u
+typedef struct trgl_skin_params {
+    int32_t  vertex_stride, n_influences;
+    uint32_t n_joints, flags;
+    uint64_t n_poses, palette_stride;
+    uint64_t reserved;
+} trgl_skin_params;
+int trgl_skin_stage(trgl_ctx* ctx, const trgl_skin_params* p, const double* vertices, uint64_t n_vertices, const uint16_t* joints,
+                    const double* weights, const double* palette, int mem_kind, double* out);
+int trgl_pose_palette(trgl_ctx* ctx, const int32_t* parents, const double* inverse_bind, uint32_t n_joints, const double* local,
+                      uint64_t local_stride, uint64_t n_poses, int mem_kind, double* palette, uint64_t palette_stride);
+int trgl_draw_skinned(trgl_ctx* ctx, int vs, int shader_kind, const trgl_uniforms* uniforms, const double projection[16],
+                      const trgl_skin_params* p, const double* vertices, uint64_t n_vertices, const uint16_t* joints, const double* weights,
+                      const double* palette, const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind);
+
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 
 /* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and
@@ -734,7 +807,7 @@ int trgl_flush(trgl_ctx* ctx);
  * flush first, with two exceptions.  The five calls that only queue work over caller-owned device arrays and flush
  * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths, trgl_depth_order and trgl_triangle_depths with
  * TRGL_MEM_DEVICE - leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those five,
- * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
+ * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
  * computes on the host and returns without touching the context's queue.  A call refused for its arguments or for the
  * context's state may return before it completes anything.
  * bench.py: the RCCL gather of the previous frame's strips runs under the next frame's first half. */

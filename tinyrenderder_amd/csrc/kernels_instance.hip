@@ -27,6 +27,7 @@
 #include "trgl_device.h"
 #include "launch.h"
 #include "device_util.h"
+#include "skin_core.h"
 
 namespace {
 
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(INST_SCAN_CHUNK) void k_inst_scan_top(uint32_t* __r
 
 struct Mat4 { double m[16]; };
 
-// out = A * B as geometry.h:196-205 sums it: every element from 0.0, k ascending
+// out = A * B as geometry.h:196-205 sums it: every element from 0.0, k ascending (skin_core.h's statement of it, shared with trgl_pose_palette)
 __device__ __forceinline__ void write_mv(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ out) {
     double b[16];
 #pragma unroll
@@ -87,7 +88,7 @@ __device__ __forceinline__ void write_mv(const double* __restrict__ A, const dou
     for (int r = 0; r < 4; ++r) {
         double row[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) row[c] = dot4(A + 4 * r, b[c], b[4 + c], b[8 + c], b[12 + c]);
+        for (int c = 0; c < 4; ++c) row[c] = trgl::mat4_mul_elem(A, b, r, c);
         double2* o = reinterpret_cast<double2*>(out + 4 * r);             // (mv_out is 16-byte aligned: a device buffer of the context's)
         o[0] = make_double2(row[0], row[1]); o[1] = make_double2(row[2], row[3]);
     }

@@ -1,5 +1,5 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
+// kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_skin.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
 // stages) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -246,6 +246,36 @@ struct LineArgs {
 };
 void launch_sprite_stage(hipStream_t s, const SpriteArgs& a);
 void launch_line_stage(hipStream_t s, const LineArgs& a);
+
+// Skeletal animation (kernels_skin.hip; both are written down at trgl_skin_stage / trgl_pose_palette in include/trgl.h, the
+// arithmetic is skin_core.h's).  launch_skin_stage: one launch per call; a block of SKIN_BLOCK lanes owns `vb` consecutive vertices -
+// vb * stride <= SKIN_TILE_DOUBLES, the LDS tile its records pass through on the way in and out - and SKIN_POSE_GROUP consecutive
+// poses, n_vblocks = ceil(n / vb) blocks per group of poses.  A palette of up to SKIN_LDS_JOINTS joints is staged in LDS, three rows
+// per joint; a larger one is read through the cache.  vertices, weights, palette, out 8-byte aligned, joints 2.  n, n_poses > 0; the
+// number of blocks below 2^31.  LDS is sized per launch: skin_tile_doubles(vb, stride) doubles of tile and 12 per staged joint.
+// launch_pose_palette: POSE_GROUP poses per block of POSE_BLOCK lanes (one wave), 16 lanes per pose; the matrices of up to
+// POSE_LDS_JOINTS joints stay in LDS from load to store, those of more go through the palette in memory.  The structs travel as the
+// kernels' arguments.
+constexpr int SKIN_BLOCK = 256;
+constexpr int SKIN_TILE_DOUBLES = SKIN_BLOCK * 20;      // 40 KiB: 256 records of up to 20 doubles, fewer of wider ones
+constexpr int SKIN_MAX_DEVICE_STRIDE = SKIN_TILE_DOUBLES;
+__host__ __device__ inline uint32_t skin_tile_doubles(uint32_t vb, uint32_t stride) { return (vb * stride + 1u) & ~1u; }      // (16-byte units)
+constexpr int SKIN_LDS_JOINTS = 128;                    // 12 KiB of palette rows
+constexpr int SKIN_POSE_GROUP = 8;
+struct SkinArgs {
+    const double* vertices; const uint16_t* joints; const double* weights; const double* palette; double* out;
+    uint64_t n, n_poses, palette_stride, n_vblocks;
+    uint32_t stride, n_joints, flags, vb;
+};
+void launch_skin_stage(hipStream_t s, const SkinArgs& a, int n_influences);
+constexpr int POSE_GROUP = 4, POSE_BLOCK = 16 * POSE_GROUP;
+constexpr int POSE_LDS_JOINTS = 96;                     // 4 poses x 96 joints x 128 bytes = 48 KiB
+struct PoseArgs {
+    const int32_t* parents; const double* inverse_bind; const double* local; double* palette;      // inverse_bind null: palette = world
+    uint64_t local_stride, n_poses, palette_stride;
+    uint32_t n_joints;
+};
+void launch_pose_palette(hipStream_t s, const PoseArgs& a);
 
 // World boxes of instances and frustum codes of boxes (kernels_scene.hip; both are written down at trgl_instance_boxes /
 // trgl_frustum_boxes in include/trgl.h, the arithmetic is scene_core.h's).  One thread per instance or box, 0 < n < 2^31; doubles 8-byte

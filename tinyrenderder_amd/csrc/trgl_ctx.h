@@ -204,6 +204,11 @@ void host_sprite_stage(const trgl_sprite_params& P, const double* points, int st
                        double* clip_out, double* vary_out, uint32_t* colors_out);
 void host_line_stage(const trgl_line_params& P, const double* points, int stride, const uint32_t* indices, const uint32_t* colors, uint64_t n,
                      double* clip_out, double* vary_out, uint32_t* colors_out);
+// trgl_skin_stage and trgl_pose_palette over host arrays (every joint number and parent checked by the caller)
+void host_skin_stage(const trgl_skin_params& P, const double* vertices, uint64_t n, const uint16_t* joints, const double* weights,
+                     const double* palette, double* out);
+void host_pose_palette(const int32_t* parents, const double* inverse_bind, uint32_t n_joints, const double* local, uint64_t local_stride,
+                       uint64_t n_poses, double* palette, uint64_t palette_stride);
 // trgl_instance_boxes and trgl_frustum_boxes over host arrays (local_stride 0: one local box for every instance)
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out);
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);

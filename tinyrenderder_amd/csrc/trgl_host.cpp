@@ -19,6 +19,7 @@
 #include "scene_core.h"
 #include "triorder_core.h"
 #include "sprite_core.h"
+#include "skin_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -302,6 +303,43 @@ void host_line_stage(const trgl_line_params& P, const double* points, int stride
     }
 }
 
+// ---- skeletal animation in host memory (include/trgl.h, trgl_skin_stage / trgl_pose_palette; the arithmetic is skin_core.h's) ------
+void host_skin_stage(const trgl_skin_params& P, const double* vertices, uint64_t n, const uint16_t* joints, const double* weights,
+                     const double* palette, double* out) {
+    const uint64_t S = (uint64_t)P.vertex_stride, ni = (uint64_t)P.n_influences;
+    for (uint64_t q = 0; q < P.n_poses; ++q) {
+        const double* pal = palette + q * P.palette_stride;
+        for (uint64_t v = 0; v < n; ++v) {
+            const double* in = vertices + v * S;
+            double* o = out + (q * n + v) * S;
+            std::memcpy(o, in, S * sizeof(double));
+            double B[12];
+            skin_blend_zero(B);
+            for (uint64_t k = 0; k < ni; ++k) skin_blend_add(B, weights[v * ni + k], pal + 16 * (uint64_t)joints[v * ni + k]);
+            skin_position(B, in[0], in[1], in[2], o);
+            for (int d = 0; d < 3; ++d)
+                if (P.flags & (1u << d)) { const int at = skin_dir_offset(d); skin_direction(B, in[at], in[at + 1], in[at + 2], o + at); }
+        }
+    }
+}
+
+void host_pose_palette(const int32_t* parents, const double* inverse_bind, uint32_t n_joints, const double* local, uint64_t local_stride,
+                       uint64_t n_poses, double* palette, uint64_t palette_stride) {
+    std::vector<double> world((size_t)n_joints * 16);
+    for (uint64_t q = 0; q < n_poses; ++q) {
+        const double* loc = local + q * local_stride;
+        double* pal = palette + q * palette_stride;
+        for (uint32_t j = 0; j < n_joints; ++j) {
+            double* w = world.data() + 16 * (size_t)j;
+            if (parents[j] < 0) std::memcpy(w, loc + 16 * (size_t)j, 16 * sizeof(double));
+            else mat4_mul(world.data() + 16 * (size_t)parents[j], loc + 16 * (size_t)j, w);
+            double t[16];
+            if (inverse_bind) mat4_mul(w, inverse_bind + 16 * (size_t)j, t); else std::memcpy(t, w, sizeof(t));
+            for (int e = 0; e < 16; ++e) pal[16 * (size_t)j + e] = skin_canon(t[e]);
+        }
+    }
+}
+
 // ---- world boxes of instances and frustum codes of boxes in host memory (include/trgl.h, trgl_instance_boxes / trgl_frustum_boxes;
 // the arithmetic is scene_core.h's) --------------------------------------------------------------------------------------------------
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out) {
@@ -433,14 +471,7 @@ int trgl_shadow_matrix(const double light_mv[16], const double light_proj[16], c
                        const double cam_mv[16], const double cam_proj[16], const double cam_vp[16], double out[16]) {
     if (!light_mv || !light_proj || !light_vp || !cam_mv || !cam_proj || !cam_vp || !out)
         return fail(nullptr, TRGL_E_INVALID, "trgl_shadow_matrix: null matrix");
-    auto mul = [](const double* a, const double* b, double* r) {                     // geometry.h:196-205
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) {
-                double sum = 0;
-                for (int k = 0; k < 4; ++k) sum += a[4 * i + k] * b[4 * k + j];
-                r[4 * i + j] = sum;
-            }
-    };
+    auto mul = [](const double* a, const double* b, double* r) { mat4_mul(a, b, r); };      // geometry.h:196-205 (skin_core.h)
     double t[16], L[16], Cm[16], inv[16];
     mul(light_vp, light_proj, t); mul(t, light_mv, L);                               // Viewport * Perspective * ModelView, left to right
     mul(cam_vp, cam_proj, t); mul(t, cam_mv, Cm);

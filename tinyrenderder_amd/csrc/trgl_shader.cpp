@@ -1,7 +1,8 @@
 // trgl_shader.cpp — run-time shader registration (fragment kinds and vertex shaders, compiled by user_shaders.cpp) and the entry points
 // that run a stage in front of a draw: the vertex stage over an indexed mesh (trgl_draw_indexed, trgl_draw_indexed_vs, trgl_vertex_stage)
 // the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and the instanced stages (trgl_draw_instanced,
-// trgl_instance_stage, their ordered forms, and the depths and order those take: trgl_instance_depths, trgl_depth_order) the ordered triangle draw (trgl_triangle_depths, trgl_order_stage, trgl_draw_ordered) and the sprite and line stages (trgl_sprite_stage, trgl_draw_sprites, trgl_line_stage, trgl_draw_lines).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
+// trgl_instance_stage, their ordered forms, and the depths and order those take: trgl_instance_depths, trgl_depth_order) the ordered triangle draw (trgl_triangle_depths, trgl_order_stage, trgl_draw_ordered) the sprite and line stages (trgl_sprite_stage, trgl_draw_sprites, trgl_line_stage, trgl_draw_lines) and skeletal animation (trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned).  The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -9,6 +10,7 @@
 
 #include "trgl_ctx.h"
 #include "user_shaders.h"
+#include "skin_core.h"
 
 // The vertex stage of `vs` (-1: k_vertex_stage) over an indexed mesh in device memory, queued on the context's stream.  clip and
 // vary (unused when K = 0) are 16-byte aligned; u == nullptr: zeros, texture slots -1.
@@ -529,6 +531,66 @@ static int quad_draw_call(trgl_ctx* c, const std::string& w, const char* who, in
     return trgl_draw(c, kind, u, oclip, ovary, ocol, rows, TRGL_MEM_DEVICE);
 }
 
+// ---- skeletal animation (include/trgl.h: trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned) ----
+static bool mul_fits(uint64_t a, uint64_t b, uint64_t limit) { return a == 0 || b <= limit / a; }
+
+// what the scalars of a skinning call must satisfy
+static int check_skin_params(trgl_ctx* c, const std::string& w, const trgl_skin_params* P, int mem_kind, uint64_t n) {
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, w + "TRGL_MEM_DEVICE needs a context");
+    if (P->vertex_stride < 3) return fail(c, TRGL_E_INVALID, w + "vertex_stride must be >= 3 doubles");
+    if (P->n_influences < 1 || P->n_influences > 8) return fail(c, TRGL_E_INVALID, w + "n_influences must be 1 .. 8");
+    if (P->n_joints < 1 || P->n_joints > 65536) return fail(c, TRGL_E_INVALID, w + "n_joints must be 1 .. 65536");
+    if (P->n_poses < 1) return fail(c, TRGL_E_INVALID, w + "n_poses must be >= 1");
+    if (P->palette_stride < 16ull * P->n_joints && !(P->palette_stride == 0 && P->n_poses == 1))
+        return fail(c, TRGL_E_INVALID, w + "palette_stride must be >= 16 * n_joints (or 0 with one pose)");
+    if (P->reserved) return fail(c, TRGL_E_INVALID, w + "reserved must be 0");
+    if (P->flags & ~(TRGL_SKIN_NORMAL | TRGL_SKIN_TANGENT | TRGL_SKIN_BITANGENT)) return fail(c, TRGL_E_INVALID, w + "unknown flag");
+    if (((P->flags & TRGL_SKIN_NORMAL) && P->vertex_stride < 6) || ((P->flags & TRGL_SKIN_TANGENT) && P->vertex_stride < 11) ||
+        ((P->flags & TRGL_SKIN_BITANGENT) && P->vertex_stride < 14))
+        return fail(c, TRGL_E_INVALID, w + "a flagged direction lies outside the vertex record");
+    // (every byte count of the call fits 64 bits)
+    if (!mul_fits(n, (uint64_t)P->vertex_stride, 1ull << 60) || !mul_fits(n * (uint64_t)P->vertex_stride, P->n_poses, 1ull << 60) ||
+        !mul_fits(P->n_poses, P->palette_stride, 1ull << 60))
+        return fail(c, TRGL_E_UNSUPPORTED, w + "the arrays are too large");
+    return TRGL_OK;
+}
+
+// ... and its arrays (n > 0): present, aligned, the output apart from the inputs; with host memory every joint number in range
+static int check_skin_arrays(trgl_ctx* c, const std::string& w, const trgl_skin_params& P, const double* vertices, uint64_t n, const uint16_t* joints,
+                             const double* weights, const double* palette, int mem_kind, const double* out) {
+    if (!vertices || !joints || !weights || !palette || !out) return fail(c, TRGL_E_INVALID, w + "null array");
+    if ((((uintptr_t)vertices | (uintptr_t)weights | (uintptr_t)palette | (uintptr_t)out) & 7) || ((uintptr_t)joints & 1))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 2 for joints)");
+    const uint64_t ni = (uint64_t)P.n_influences, rec = n * (uint64_t)P.vertex_stride * 8;
+    const struct { const void* p; uint64_t bytes; } ins[4] = { { vertices, rec }, { joints, n * ni * 2 }, { weights, n * ni * 8 },
+                                                              { palette, ((P.n_poses - 1) * P.palette_stride + 16ull * P.n_joints) * 8 } };
+    for (const auto& i : ins)
+        if (ranges_overlap(i.p, i.bytes, out, rec * P.n_poses)) return fail(c, TRGL_E_INVALID, w + "the output overlaps an input");
+    if (mem_kind == TRGL_MEM_HOST)
+        for (uint64_t k = 0; k < n * ni; ++k)
+            if (joints[k] >= P.n_joints) return fail(c, TRGL_E_INVALID, w + "joint number out of range");
+    return TRGL_OK;
+}
+
+// the skin kernel over device arrays (checked), queued on the context's stream
+static int queue_skin_stage(trgl_ctx* c, const std::string& w, const trgl_skin_params& P, const double* vertices, uint64_t n, const uint16_t* joints,
+                            const double* weights, const double* palette, double* out) {
+    if (P.vertex_stride > SKIN_MAX_DEVICE_STRIDE) return fail(c, TRGL_E_UNSUPPORTED, w + "vertex_stride above 5120 doubles with device memory");
+    SkinArgs a; std::memset(&a, 0, sizeof(a));
+    a.vertices = vertices; a.joints = joints; a.weights = weights; a.palette = palette; a.out = out;
+    a.n = n; a.n_poses = P.n_poses; a.palette_stride = P.palette_stride;
+    a.stride = (uint32_t)P.vertex_stride; a.n_joints = P.n_joints; a.flags = P.flags;
+    a.vb = (uint32_t)std::min<int>(SKIN_BLOCK, SKIN_TILE_DOUBLES / P.vertex_stride);
+    a.n_vblocks = (n + a.vb - 1) / a.vb;
+    if (!mul_fits(a.n_vblocks, (P.n_poses + SKIN_POSE_GROUP - 1) / SKIN_POSE_GROUP, 0x7fffffffull))
+        return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more blocks in one call");
+    launch_skin_stage(c->stream, a, P.n_influences);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
 extern "C" {
 
 int trgl_sprite_stage(trgl_ctx* c, const trgl_sprite_params* P, const double* points, int stride, const uint32_t* colors, uint64_t n, int mem_kind,
@@ -567,6 +629,93 @@ int trgl_draw_lines(trgl_ctx* c, int kind, const trgl_uniforms* u, const trgl_li
     const QuadInputs in{ points, stride, n_points, indices, colors, n_segments, mem_kind };
     if ((r = check_line_params(c, w, P, in))) return r;
     return quad_draw_call(c, w, "trgl_draw_lines", kind, u, nullptr, P, in, 6);
+}
+
+int trgl_skin_stage(trgl_ctx* c, const trgl_skin_params* P, const double* vertices, uint64_t n, const uint16_t* joints, const double* weights,
+                    const double* palette, int mem_kind, double* out) {
+    const std::string w = "trgl_skin_stage: ";
+    int r;
+    if ((r = check_skin_params(c, w, P, mem_kind, n))) return r;
+    if (n == 0) return TRGL_OK;
+    if ((r = check_skin_arrays(c, w, *P, vertices, n, joints, weights, palette, mem_kind, out))) return r;
+    if (mem_kind == TRGL_MEM_HOST) { host_skin_stage(*P, vertices, n, joints, weights, palette, out); return TRGL_OK; }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    return queue_skin_stage(c, w, *P, vertices, n, joints, weights, palette, out);
+}
+
+int trgl_pose_palette(trgl_ctx* c, const int32_t* parents, const double* inverse_bind, uint32_t n_joints, const double* local, uint64_t local_stride,
+                      uint64_t n_poses, int mem_kind, double* palette, uint64_t palette_stride) {
+    const std::string w = "trgl_pose_palette: ";
+    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
+    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, w + "TRGL_MEM_DEVICE needs a context");
+    if (n_joints < 1) return fail(c, TRGL_E_INVALID, w + "n_joints must be >= 1");
+    for (const uint64_t stride : { local_stride, palette_stride })
+        if (stride < 16ull * n_joints && !(stride == 0 && n_poses <= 1)) return fail(c, TRGL_E_INVALID, w + "a stride must be >= 16 * n_joints (or 0 with one pose)");
+    if (!mul_fits(n_poses, local_stride, 1ull << 60) || !mul_fits(n_poses, palette_stride, 1ull << 60)) return fail(c, TRGL_E_UNSUPPORTED, w + "the arrays are too large");
+    if (n_poses == 0) return TRGL_OK;
+    if (!parents || !local || !palette) return fail(c, TRGL_E_INVALID, w + "null array");
+    if ((((uintptr_t)inverse_bind | (uintptr_t)local | (uintptr_t)palette) & 7) || ((uintptr_t)parents & 3))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 4 for parents)");
+    const uint64_t mats = 16ull * n_joints * 8, out_bytes = (n_poses - 1) * palette_stride * 8 + mats;
+    if (ranges_overlap(parents, 4ull * n_joints, palette, out_bytes) || ranges_overlap(inverse_bind, mats, palette, out_bytes) ||
+        ranges_overlap(local, (n_poses - 1) * local_stride * 8 + mats, palette, out_bytes))
+        return fail(c, TRGL_E_INVALID, w + "the output overlaps an input");
+    if (mem_kind == TRGL_MEM_HOST) {
+        for (uint32_t j = 0; j < n_joints; ++j)
+            if (parents[j] != -1 && !pose_parent_below(parents[j], j)) return fail(c, TRGL_E_INVALID, w + "a parent must be -1 or a joint below its child");
+        try {
+            host_pose_palette(parents, inverse_bind, n_joints, local, local_stride, n_poses, palette, palette_stride);
+        } catch (const std::bad_alloc&) {
+            return fail(c, TRGL_E_NOMEM, w + "out of memory");
+        }
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    if (int r = end_pending_raster(c)) return r;
+    if ((n_poses + POSE_GROUP - 1) / POSE_GROUP > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more blocks in one call");
+    PoseArgs a; std::memset(&a, 0, sizeof(a));
+    a.parents = parents; a.inverse_bind = inverse_bind; a.local = local; a.palette = palette;
+    a.local_stride = local_stride; a.n_poses = n_poses; a.palette_stride = palette_stride; a.n_joints = n_joints;
+    launch_pose_palette(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_draw_skinned(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16], const trgl_skin_params* P,
+                      const double* vertices, uint64_t n, const uint16_t* joints, const double* weights, const double* palette,
+                      const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_draw_skinned: ";
+    if ((r = check_skin_params(c, w, P, mem_kind, n))) return r;
+    if (P->n_poses != 1) return fail(c, TRGL_E_INVALID, w + "n_poses must be 1");
+    if (vs == -1 && colors) return fail(c, TRGL_E_INVALID, w + "colors: only with a vertex shader");
+    const int stride = P->vertex_stride;
+    int K = TRGL_VARY_PHONG; bool go;
+    // (what the draw would refuse is refused before the skin stage is queued; `vertices` stands in for the skinned array)
+    if (vs == -1) r = check_draw_indexed(c, kind, u, projection, vertices, stride, n, indices, n_faces, mem_kind, &go);
+    else r = check_draw_indexed_vs(c, vs, kind, u, projection, vertices, stride, n, indices, n_faces, mem_kind, &K, &go);
+    if (r || !go) return r;
+    if (n == 0) return fail(c, TRGL_E_INVALID, w + "faces without vertices");
+    if (mem_kind == TRGL_MEM_HOST) {
+        try {
+            std::vector<double> skinned((size_t)n * (size_t)stride);
+            if ((r = check_skin_arrays(c, w, *P, vertices, n, joints, weights, palette, mem_kind, skinned.data()))) return r;
+            host_skin_stage(*P, vertices, n, joints, weights, palette, skinned.data());
+            return vs == -1 ? trgl_draw_indexed(c, kind, u, projection, skinned.data(), stride, n, indices, n_faces, TRGL_MEM_HOST)
+                            : trgl_draw_indexed_vs(c, vs, kind, u, projection, skinned.data(), stride, n, indices, n_faces, colors, TRGL_MEM_HOST);
+        } catch (const std::bad_alloc&) {
+            return fail(c, TRGL_E_NOMEM, w + "out of memory");
+        }
+    }
+    StageHold hold(c);
+    void* p = nullptr;
+    if ((r = stage_alloc(c, (size_t)n * (size_t)stride * sizeof(double), &p))) return r;
+    double* skinned = (double*)p;
+    if ((r = check_skin_arrays(c, w, *P, vertices, n, joints, weights, palette, mem_kind, skinned))) return r;
+    if ((r = queue_skin_stage(c, w, *P, vertices, n, joints, weights, palette, skinned))) return r;
+    return draw_indexed_checked(c, vs, K, kind, u, projection, skinned, stride, n, indices, n_faces, colors, TRGL_MEM_DEVICE);
 }
 
 int trgl_triangle_depths(trgl_ctx* c, const double* clip, uint64_t n, uint32_t group, int mode, int mem_kind, double* depths_out) {

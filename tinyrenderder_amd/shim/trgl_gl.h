@@ -736,6 +736,64 @@ inline bool gl_draw_lines(const trgl_line_params& params, const double* points, 
     return trgl_shim::draw_quads("gl_draw_lines", shader, framebuffer, n_segments, colors, nullptr, &params, points, stride, n_points, indices);
 }
 
+// Skeletal animation (include/trgl.h, trgl_skin_stage / trgl_pose_palette / trgl_draw_skinned): the bones and weights that Assimp
+// delivers and the reference's Model::processMesh drops.  joints / weights: n_influences per vertex; a palette: one mat<4,4> per joint.
+inline trgl_skin_params gl_skin_params(int vertex_stride, int n_influences, std::size_t n_joints, std::uint32_t flags = TRGL_SKIN_NORMAL) {
+    trgl_skin_params p{};
+    p.vertex_stride = vertex_stride; p.n_influences = n_influences; p.n_joints = std::uint32_t(n_joints); p.flags = flags; p.n_poses = 1;
+    return p;
+}
+// palette_j = world_j * inverse_bind_j with world_j = world_parent * local_j (parents[j]: -1, or a joint below j), on the host, no
+// context needed; inverse_bind may be empty (palette = world).  A call that fails (gl_last_error()) leaves `palette` empty.
+inline bool gl_pose_palette(const std::vector<std::int32_t>& parents, const std::vector<mat<4, 4>>& inverse_bind, const std::vector<mat<4, 4>>& local,
+                            std::vector<mat<4, 4>>& palette) {
+    static_assert(sizeof(mat<4, 4>) == 16 * sizeof(double), "mat<4,4> must be 16 packed doubles");
+    palette.assign(parents.size(), mat<4, 4>());
+    const int rc = (local.size() != parents.size() || (!inverse_bind.empty() && inverse_bind.size() != parents.size())) ? TRGL_E_INVALID
+        : trgl_pose_palette(nullptr, parents.data(), inverse_bind.empty() ? nullptr : reinterpret_cast<const double*>(inverse_bind.data()),
+                            std::uint32_t(parents.size()), reinterpret_cast<const double*>(local.data()), 0, 1, TRGL_MEM_HOST,
+                            reinterpret_cast<double*>(palette.data()), 0);
+    if (rc != TRGL_OK) { palette.clear(); return trgl_shim::fail("gl_pose_palette", rc, nullptr); }
+    return true;
+}
+// The skinned copy of `vertices` (nv records of params.vertex_stride doubles) under one palette, on the host, no context needed; a call
+// that fails leaves `out` empty.
+inline bool gl_skin_stage(trgl_skin_params params, const double* vertices, std::size_t nv, const std::uint16_t* joints, const double* weights,
+                          const std::vector<mat<4, 4>>& palette, std::vector<double>& out) {
+    params.n_joints = std::uint32_t(palette.size()); params.n_poses = 1; params.palette_stride = 0;
+    out.assign(nv * std::size_t(params.vertex_stride > 0 ? params.vertex_stride : 0), 0.0);
+    const int rc = trgl_skin_stage(nullptr, &params, vertices, nv, joints, weights, reinterpret_cast<const double*>(palette.data()), TRGL_MEM_HOST, out.data());
+    if (rc != TRGL_OK) { out.clear(); return trgl_shim::fail("gl_skin_stage", rc, nullptr); }
+    return true;
+}
+// gl_skin_stage and gl_draw_indexed of its output in one call (trgl_draw_skinned): the shader's describe() is taken as gl_draw_indexed
+// takes it.  A set clip plane is TRGL_E_UNSUPPORTED: this draw is not clipped.
+inline bool gl_draw_skinned(const IShader& shader, trgl_skin_params params, const double* vertices, std::size_t nv, const std::uint16_t* joints,
+                            const double* weights, const std::vector<mat<4, 4>>& palette, const unsigned int* indices, std::size_t nfaces,
+                            TGAImage& framebuffer) {
+    using namespace trgl_shim;
+    State& s = state();
+    if (!bind(framebuffer)) return false;
+    bool ok = submit_batch();                                   // earlier rasterize() calls come first
+    trgl_shader_desc d;
+    if (!shader.describe(d)) {
+        std::fprintf(stderr, "trgl: gl_draw_skinned(): needs a shader with a device descriptor\n");
+        std::abort();
+    }
+    if (s.clip_on) return fail("gl_draw_skinned", TRGL_E_UNSUPPORTED, nullptr);
+    params.n_joints = std::uint32_t(palette.size()); params.n_poses = 1; params.palette_stride = 0;
+    double vp[16], pj[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { vp[4 * r + c] = Viewport[r][c]; pj[4 * r + c] = Perspective[r][c]; }
+    const bool user_vs = d.vertex_kind >= 0;
+    const std::vector<std::uint32_t> colors(user_vs ? nfaces : 0, d.color);
+    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
+         TRGL_SHIM_OK(trgl_draw_skinned(s.ctx, user_vs ? d.vertex_kind : -1, d.kind, &d.uniforms, pj, &params, vertices, nv, joints, weights,
+                                        reinterpret_cast<const double*>(palette.data()), reinterpret_cast<const std::uint32_t*>(indices), nfaces,
+                                        user_vs ? colors.data() : nullptr, TRGL_MEM_HOST)) && ok;
+    s.zbuffer_stale_on_host = true;
+    return ok;
+}
+
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
 // write_tga_file(), main.cpp:743,773).  The depths follow on demand through the `zbuffer` proxy.
 // false: something submitted since the last gl_flush() failed (gl_last_error()); the pixels hold what could be drawn.
