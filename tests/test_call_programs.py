@@ -9,7 +9,7 @@ latched at the flush) or right behind the previous one (queued draws rendered un
 the final frame must differ, or the occurrence would pin nothing.
 
 Families T, P and I (translucent kinds, passes over the resident frame, instances and clipping) add the rules of csrc/trgl_passes.cpp and
-csrc/trgl_shader.cpp.  Their sensitivity removes a rule in one of five ways: a call is moved in front of the draws it must wait for, or
+the stage entry points (csrc/trgl_stage_*.cpp).  Their sensitivity removes a rule in one of five ways: a call is moved in front of the draws it must wait for, or
 behind the next flush point; a scribble or an overwrite is applied before the call; an order list is reversed; queued draws read the
 arrays of a later draw (the staging arena reset under them).  Where none of the five fits, the rule's own opposite is run: the draws
 queued in front of a refused call do not land, a register is read as it was before the pass that fills it, visibility bytes that draw

@@ -16,7 +16,7 @@ caller's pointers as they are, so every read below is checked from a caller's bu
   f. stream ordering: the context's own stream is hipStreamNonBlocking (init_ctx in trgl_api.cpp) and waits for nobody; on a shared
      stream (trgl_set_stream) producers, flush and overwrites line up without a host sync, as bench.py and shard.StripLoop rely on;
   g. trgl_draw_indexed(TRGL_MEM_DEVICE): k_vertex_stage gathers through the caller's pointers (kernels_post.hip), whole
-     meshes and the block edges of 64 faces (trgl_draw_indexed in trgl_shader.cpp does not stage or check on this path).
+     meshes and the block edges of 64 faces (trgl_draw_indexed in trgl_stage_mesh.cpp does not stage or check on this path).
 
 Bar: the device-memory frame equals the host-memory frame of the same GPU bit for bit - z bits, framebuffer bytes, stats tuple and
 stats line, EYE included (the same kernels on the same numbers) - and the oracle's / the reference's golden within the suite's bar

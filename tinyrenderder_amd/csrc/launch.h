@@ -1,6 +1,8 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
-// kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip, kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_skin.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_shader.cpp (the vertex and clip
-// stages) and trgl_passes.cpp (the rest).
+// kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip,
+// kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_skin.hip,
+// kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
+// trgl_stage_rows.cpp (the stages in front of a draw) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "trgl_device.h"

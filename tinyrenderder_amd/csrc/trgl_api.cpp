@@ -4,7 +4,8 @@
 //   setup (per draw) -> scan(counts) -> expand -> stable radix passes by tile id -> bounds -> raster
 // and is the batched equivalent of the reference's per-face loop of rasterize() calls
 // (main.cpp:660-666): submission order is preserved per tile, so results are identical.
-// Passes, shader entry points, host-only functions and RCCL: trgl_passes.cpp, trgl_shader.cpp, trgl_host.cpp, trgl_rccl.cpp (trgl_ctx.h).
+// Passes, shader registration, the stages in front of a draw, host-only functions and RCCL: trgl_passes.cpp, trgl_shader.cpp,
+// trgl_stage_*.cpp, trgl_host.cpp, trgl_rccl.cpp (trgl_ctx.h).
 #include <algorithm>
 #include <cstring>
 

@@ -1,6 +1,7 @@
 // trgl_ctx.h — the context behind the C ABI and what the library's own translation units share of it (private: neither installed
-// nor embedded).  trgl_api.cpp owns the flush pipeline and its ordering rules; trgl_shader.cpp, trgl_passes.cpp and trgl_rccl.cpp
-// reach the context through the few functions declared at the end; trgl_host.cpp (no HIP) does not include this file.
+// nor embedded).  trgl_api.cpp owns the flush pipeline and its ordering rules; trgl_shader.cpp, the stage entry points
+// (trgl_stage_*.cpp, which share trgl_stage.h on top of this file), trgl_passes.cpp and trgl_rccl.cpp reach the context through
+// the few functions declared at the end; trgl_host.cpp (no HIP) does not include this file.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <new>
 
-#include "trgl_ctx.h"
+#include "trgl_stage.h"
 #include "mip_core.h"
 #include "../shim/trgl_image.h"
 
@@ -322,8 +322,7 @@ int trgl_framebuffer_blur(trgl_ctx* c, int radius) {
 }
 
 int trgl_image_downsample(trgl_ctx* c, const uint8_t* src, int w, int h, int bpp, int factor, uint8_t* dst, int mem_kind) {
-    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_image_downsample: bad mem_kind");
-    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_image_downsample: TRGL_MEM_DEVICE needs a context");
+    if (int r = check_mem(c, "trgl_image_downsample: ", mem_kind)) return r;
     if (int r = check_box(c, "trgl_image_downsample", w, h, bpp, factor)) return r;
     if (!src || !dst) return fail(c, TRGL_E_INVALID, "trgl_image_downsample: null image");
     if (ranges_overlap(src, (size_t)w * h * bpp, dst, (size_t)(w / factor) * (h / factor) * bpp))
@@ -386,8 +385,7 @@ int trgl_texture_from_framebuffer(trgl_ctx* c, int slot, int factor) {
 
 // ---- mipmapped textures (include/trgl.h; host loops in trgl_host.cpp, kernels in kernels_mip.hip, the arithmetic in mip_core.h) ----------
 int trgl_image_mipmaps(trgl_ctx* c, const uint8_t* src, int w, int h, int bpp, uint8_t* dst, int mem_kind) {
-    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_image_mipmaps: bad mem_kind");
-    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_image_mipmaps: TRGL_MEM_DEVICE needs a context");
+    if (int r = check_mem(c, "trgl_image_mipmaps: ", mem_kind)) return r;
     int L = 0; size_t total = 0;
     if (int r = trgl_mip_layout(w, h, bpp, &L, nullptr, nullptr, nullptr, &total)) return c ? fail(c, r, std::string("trgl_image_mipmaps: ") + trgl_last_error(nullptr)) : r;
     if (!src) return fail(c, TRGL_E_INVALID, "trgl_image_mipmaps: src is null");
@@ -436,8 +434,7 @@ int trgl_texture_mipmaps(trgl_ctx* c, int slot) {
 int trgl_lod_stage(trgl_ctx* c, const double viewport[16], const double* clip, double* vary, uint64_t n, int K,
                    int uv_offset, int out_offset, int mem_kind) {
     const std::string w = "trgl_lod_stage: ";
-    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, w + "bad mem_kind");
-    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, w + "TRGL_MEM_DEVICE needs a context");
+    if (int r = check_mem(c, w, mem_kind)) return r;
     if (!viewport) return fail(c, TRGL_E_INVALID, w + "viewport is null");
     if (K < 0 || K > TRGL_MAX_USER_VARY) return fail(c, TRGL_E_INVALID, w + "K outside 0..TRGL_MAX_USER_VARY");
     if (uv_offset < 0 || out_offset < 0 || uv_offset > K - 6 || out_offset > K - 4 || (uv_offset < out_offset + 4 && out_offset < uv_offset + 6))
@@ -579,8 +576,7 @@ int trgl_occlusion_boxes(trgl_ctx* c, const double view_proj[16], const double* 
 // ---- world boxes of instances and frustum codes of boxes (include/trgl.h; host loops in trgl_host.cpp, kernels in kernels_scene.hip) ----
 int trgl_instance_boxes(trgl_ctx* c, const double* local_boxes, int local_stride, const double* instances, int instance_stride,
                         uint64_t n_instances, int mem_kind, double* boxes_out) {
-    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: bad mem_kind");
-    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: TRGL_MEM_DEVICE needs a context");
+    if (int r = check_mem(c, "trgl_instance_boxes: ", mem_kind)) return r;
     if (local_stride != 0 && local_stride < 6) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: local_stride must be 0 (one box for all) or >= 6 doubles");
     if (instance_stride < 16) return fail(c, TRGL_E_INVALID, "trgl_instance_boxes: instance stride must be >= 16 doubles (a row-major 4x4 matrix)");
     if (n_instances > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_instance_boxes: 2^31 or more instances in one call");
@@ -596,8 +592,7 @@ int trgl_instance_boxes(trgl_ctx* c, const double* local_boxes, int local_stride
 }
 
 int trgl_frustum_boxes(trgl_ctx* c, const double planes[24], const double* boxes, uint64_t n, int mode, int mem_kind, uint8_t* codes) {
-    if (!valid_mem_kind(mem_kind)) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: bad mem_kind");
-    if (mem_kind == TRGL_MEM_DEVICE && !c) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: TRGL_MEM_DEVICE needs a context");
+    if (int r = check_mem(c, "trgl_frustum_boxes: ", mem_kind)) return r;
     if (mode != TRGL_FRUSTUM_SET && mode != TRGL_FRUSTUM_MERGE) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: bad mode");
     if (!planes) return fail(c, TRGL_E_INVALID, "trgl_frustum_boxes: planes is null");
     if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "trgl_frustum_boxes: 2^31 or more boxes in one call");

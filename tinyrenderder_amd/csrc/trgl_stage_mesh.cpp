@@ -1,0 +1,389 @@
+// trgl_stage_mesh.cpp — the stages over an indexed mesh and the draws behind them: the vertex stage (trgl_draw_indexed,
+// trgl_draw_indexed_vs, trgl_vertex_stage), the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and
+// skeletal animation (trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned).
+// The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
+#include <algorithm>
+#include <cstring>
+
+#include "trgl_stage.h"
+#include "skin_core.h"
+
+// The vertex stage of `vs` (-1: k_vertex_stage) over an indexed mesh in device memory, queued on the context's stream.  clip and
+// vary (unused when K = 0) are 16-byte aligned; u == nullptr: zeros, texture slots -1.
+static int queue_vertex_stage(trgl_ctx* c, int vs, const trgl_uniforms* u, const double projection[16], const double* dv, int stride,
+                              const uint32_t* di, uint64_t n_faces, double* clip, double* vary) {
+    if (vs < 0) {
+        launch_vertex_stage(c->stream, u->model_view, projection, dv, stride, di, (uint32_t)n_faces, clip, vary);
+        HIPCHK(c, hipGetLastError());
+        return TRGL_OK;
+    }
+    VertexUserParams p; std::memset(&p, 0, sizeof(p));
+    if (u) p.u = *u; else p.u.tex_diffuse = p.u.tex_normal = p.u.tex_specular = -1;
+    std::memcpy(p.proj, projection, sizeof(p.proj));
+    p.vertices = dv; p.indices = di; p.clip = clip; p.vary = vary; p.nfaces = (uint32_t)n_faces; p.stride = stride;
+    void* args[] = { &p };
+    const uint64_t blocks = (n_faces + TRGL_VERTEX_USER_FACES - 1) / TRGL_VERTEX_USER_FACES;
+    HIPCHK(c, hipModuleLaunchKernel(c->vertex[vs].fn, (unsigned)blocks, 1, 1, TRGL_VERTEX_USER_FACES * 3, 1, 1, 0, c->stream, args, nullptr));
+    return TRGL_OK;
+}
+
+int trgl::check_vertex_call(trgl_ctx* c, const std::string& w, int vs, bool builtin_ok, const trgl_uniforms* u, const double* projection,
+                            const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind,
+                            int* K) {
+    if (!((builtin_ok && vs == -1) || (vs >= 0 && vs < (int)c->vertex.size()))) return fail(c, TRGL_E_INVALID, w + "unknown vertex shader");
+    *K = vs < 0 ? TRGL_VARY_PHONG : c->vertex[vs].K;
+    if (!projection || !vertices || !indices) return fail(c, TRGL_E_INVALID, w + "null argument");
+    if (vs < 0 && !u) return fail(c, TRGL_E_INVALID, w + "the built-in vertex stage needs uniforms (model_view)");
+    if (stride < (vs < 0 ? 8 : 1))
+        return fail(c, TRGL_E_INVALID, w + (vs < 0 ? "vertex stride must be >= 8 doubles (pos3, normal3, uv2)" : "vertex stride must be >= 1"));
+    if (int r = check_mem(c, w, mem_kind)) return r;
+    if (n_faces > 0xffffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, w + "too many faces in one call");
+    if (mem_kind == TRGL_MEM_HOST && !all_below(indices, 3 * n_faces, n_vertices)) return fail(c, TRGL_E_INVALID, w + "index out of range");
+    return TRGL_OK;
+}
+
+// A plane and an attribute list as the clipped draws take them (null plane: no clipping), and the table made of them
+struct ClipSpec { const double* plane; const trgl_clip_attr* attrs; int n_attrs; ClipTable tab; };
+
+// spec.tab for a draw of `kind` with K varyings; n_attrs = -1: the kind's built-in layout
+static int clip_spec_table(trgl_ctx* c, const std::string& w, ClipSpec& spec, int kind, int K) {
+    if (!spec.plane) return fail(c, TRGL_E_INVALID, w + "plane is null");
+    trgl_clip_attr builtin[TRGL_MAX_CLIP_ATTRS];
+    const trgl_clip_attr* attrs = spec.attrs; int n_attrs = spec.n_attrs;
+    if (n_attrs == -1) {
+        attrs = builtin; n_attrs = 0;
+        if (kind >= 0 && kind < TRGL_NUM_SHADERS) (void)trgl_clip_layout(kind, builtin, &n_attrs);
+        else if (K > 0) return fail(c, TRGL_E_INVALID, w + "a user kind with varyings has no built-in clip layout: pass its attributes");
+    }
+    if (!clip_table(attrs, n_attrs, K, &spec.tab)) return fail(c, TRGL_E_INVALID, w + "invalid clip attribute list");
+    return TRGL_OK;
+}
+
+// The clip stage over device arrays, queued on the context's stream; *n_out is complete when the stream has been waited for.
+static int queue_clip_stage(trgl_ctx* c, const double plane[4], const ClipTable& tab, int K, const double* clip, const double* vary,
+                            const uint32_t* colors, uint64_t n, const Rows& out, unsigned long long* n_out) {
+    int r;
+    if ((r = c->clip_scratch.grow(c, 2 + clip_scratch_words(n)))) return r;
+    ClipArgs a; std::memset(&a, 0, sizeof(a));
+    std::memcpy(a.plane, plane, sizeof(a.plane));
+    a.clip = clip; a.vary = K ? vary : nullptr; a.colors = colors;
+    a.clip_out = out.clip; a.vary_out = K ? out.vary : nullptr; a.colors_out = colors ? out.colors : nullptr;
+    a.n = n; a.K = K; a.tab = tab;
+    unsigned long long* total = reinterpret_cast<unsigned long long*>(c->clip_scratch.p);
+    launch_clip_stage(c->stream, a, c->clip_scratch.p + 2, total);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(n_out, total, sizeof(*n_out), hipMemcpyDeviceToHost, c->stream));
+    return TRGL_OK;
+}
+
+// trgl_draw of device arrays, through the clip stage when `spec` is given (checked: clip_spec_table).  The arrays are read when the
+// stage runs; its outputs are staged, under the caller's StageHold.
+static int draw_device_clipped(trgl_ctx* c, int kind, int K, const trgl_uniforms* u, const ClipSpec* spec, const double* clip,
+                               const double* vary, const uint32_t* colors, uint64_t n) {
+    if (!spec) return trgl_draw(c, kind, u, clip, vary, colors, n, TRGL_MEM_DEVICE);
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, "clip stage: 2^31 or more triangles in one call");
+    int r; CallMem mem(c, true); Rows o;
+    if ((r = alloc_rows(mem, 2 * n, K, colors != nullptr, &o))) return r;
+    unsigned long long n_out = 0;
+    if ((r = queue_clip_stage(c, spec->plane, spec->tab, K, clip, vary, colors, n, o, &n_out))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait of a clipped draw: the queue needs the count on the host
+    if (n_out == 0) {
+        // nothing is queued; with no draw waiting for a flush either, nobody refers to the staged arrays (the stream has just been waited for)
+        if (c->draws.empty() && c->stage_hold == 1) for (auto& ch : c->stage) ch.used = 0;
+        return TRGL_OK;
+    }
+    return trgl_draw(c, kind, u, o.clip, o.vary, o.colors, n_out, TRGL_MEM_DEVICE);
+}
+
+// What the indexed draws share once their arguments are checked (n_faces > 0): stage a host mesh, run the vertex stage of `vs` (K
+// varyings) into staged clip / vary arrays and hand those to trgl_draw - through the clip stage when `spec` (checked) is given.
+static int draw_indexed_checked(trgl_ctx* c, int vs, int K, int kind, const trgl_uniforms* u, const double projection[16],
+                                const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                                const uint32_t* colors, int mem_kind, const ClipSpec* spec = nullptr) {
+    int r;
+    StageHold hold(c);
+    CallMem mem(c, true); Rows o;
+    if (mem_kind == TRGL_MEM_HOST) {
+        if ((r = mem.copy(vertices, n_vertices * (size_t)stride, &vertices)) || (r = mem.copy(indices, 3 * n_faces, &indices)) ||
+            (colors && (r = mem.copy(colors, n_faces, &colors)))) return r;
+    }
+    if ((r = alloc_rows(mem, n_faces, K, false, &o))) return r;
+    if ((r = queue_vertex_stage(c, vs, u, projection, vertices, stride, indices, n_faces, o.clip, o.vary))) return r;
+    return draw_device_clipped(c, kind, K, u, spec, o.clip, o.vary, colors, n_faces);
+}
+
+// the checks of trgl_draw_indexed; *go: there is something to draw
+static int check_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const double* projection, const double* vertices, int stride,
+                              uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind, bool* go) {
+    *go = false;
+    const std::string w = "trgl_draw_indexed: ";
+    const UserKind* uk = user_kind(c, kind);
+    if (kind != TRGL_SHADER_PHONG && kind != TRGL_SHADER_EYE && !(uk && uk->K == TRGL_VARY_PHONG))     // (a user kind's: the PHONG layout)
+        return fail(c, TRGL_E_INVALID, w + "kind must be PHONG, EYE or a user kind registered with 24 varyings");
+    if (!u || !projection || !vertices || !indices) return fail(c, TRGL_E_INVALID, w + "null argument");
+    if (stride < 8) return fail(c, TRGL_E_INVALID, w + "vertex stride must be >= 8 doubles (pos3, normal3, uv2)");
+    if (int r = check_mem(c, w, mem_kind)) return r;
+    if (n_faces == 0) return TRGL_OK;
+    if (n_faces > 0xffffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, w + "too many faces in one call");
+    if (mem_kind == TRGL_MEM_HOST && !all_below(indices, 3 * n_faces, n_vertices)) return fail(c, TRGL_E_INVALID, w + "index out of range");
+    *go = true;
+    return TRGL_OK;
+}
+
+// the checks of trgl_draw_indexed_vs; K of the stage comes back in *K
+static int check_draw_indexed_vs(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double* projection, const double* vertices,
+                                 int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind, int* K, bool* go) {
+    *go = false;
+    const std::string w = "trgl_draw_indexed_vs: ";
+    int r = check_vertex_call(c, w, vs, false, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, K); if (r) return r;
+    // (what trgl_draw would refuse is refused before the vertex stage is queued)
+    const int kind_K = kind_vary_count(c, kind);
+    if (kind_K < 0) return fail(c, TRGL_E_INVALID, w + "unknown shader kind");
+    if (kind_K != *K) return fail(c, TRGL_E_INVALID, w + "the shader kind and the vertex shader differ in their number of varyings");
+    if ((r = check_kind_uniforms(c, w, kind, u))) return r;
+    *go = n_faces != 0;
+    return TRGL_OK;
+}
+
+// ---- skeletal animation (include/trgl.h: trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned) ----
+// what the scalars of a skinning call must satisfy
+static int check_skin_params(trgl_ctx* c, const std::string& w, const trgl_skin_params* P, int mem_kind, uint64_t n) {
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    if (int r = check_mem(c, w, mem_kind)) return r;
+    if (P->vertex_stride < 3) return fail(c, TRGL_E_INVALID, w + "vertex_stride must be >= 3 doubles");
+    if (P->n_influences < 1 || P->n_influences > 8) return fail(c, TRGL_E_INVALID, w + "n_influences must be 1 .. 8");
+    if (P->n_joints < 1 || P->n_joints > 65536) return fail(c, TRGL_E_INVALID, w + "n_joints must be 1 .. 65536");
+    if (P->n_poses < 1) return fail(c, TRGL_E_INVALID, w + "n_poses must be >= 1");
+    if (P->palette_stride < 16ull * P->n_joints && !(P->palette_stride == 0 && P->n_poses == 1))
+        return fail(c, TRGL_E_INVALID, w + "palette_stride must be >= 16 * n_joints (or 0 with one pose)");
+    if (P->reserved) return fail(c, TRGL_E_INVALID, w + "reserved must be 0");
+    if (P->flags & ~(TRGL_SKIN_NORMAL | TRGL_SKIN_TANGENT | TRGL_SKIN_BITANGENT)) return fail(c, TRGL_E_INVALID, w + "unknown flag");
+    if (((P->flags & TRGL_SKIN_NORMAL) && P->vertex_stride < 6) || ((P->flags & TRGL_SKIN_TANGENT) && P->vertex_stride < 11) ||
+        ((P->flags & TRGL_SKIN_BITANGENT) && P->vertex_stride < 14))
+        return fail(c, TRGL_E_INVALID, w + "a flagged direction lies outside the vertex record");
+    // (every byte count of the call fits 64 bits)
+    if (!mul_fits(n, (uint64_t)P->vertex_stride, 1ull << 60) || !mul_fits(n * (uint64_t)P->vertex_stride, P->n_poses, 1ull << 60) ||
+        !mul_fits(P->n_poses, P->palette_stride, 1ull << 60))
+        return fail(c, TRGL_E_UNSUPPORTED, w + "the arrays are too large");
+    return TRGL_OK;
+}
+
+// ... and its arrays (n > 0): present, aligned, the output apart from the inputs; with host memory every joint number in range
+static int check_skin_arrays(trgl_ctx* c, const std::string& w, const trgl_skin_params& P, const double* vertices, uint64_t n,
+                             const uint16_t* joints, const double* weights, const double* palette, int mem_kind, const double* out) {
+    if (!vertices || !joints || !weights || !palette || !out) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (!aligned({ { vertices, 8 }, { weights, 8 }, { palette, 8 }, { out, 8 }, { joints, 2 } }))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 2 for joints)");
+    const uint64_t ni = (uint64_t)P.n_influences, rec = n * (uint64_t)P.vertex_stride * 8;
+    const struct { const void* p; uint64_t bytes; } ins[4] = { { vertices, rec }, { joints, n * ni * 2 }, { weights, n * ni * 8 },
+                                                              { palette, ((P.n_poses - 1) * P.palette_stride + 16ull * P.n_joints) * 8 } };
+    for (const auto& i : ins)
+        if (arrays_overlap(i.p, i.bytes, out, rec * P.n_poses)) return fail(c, TRGL_E_INVALID, w + "the output overlaps an input");
+    if (mem_kind == TRGL_MEM_HOST && !all_below(joints, n * ni, P.n_joints)) return fail(c, TRGL_E_INVALID, w + "joint number out of range");
+    return TRGL_OK;
+}
+
+// the skin kernel over device arrays (checked), queued on the context's stream
+static int queue_skin_stage(trgl_ctx* c, const std::string& w, const trgl_skin_params& P, const double* vertices, uint64_t n,
+                            const uint16_t* joints, const double* weights, const double* palette, double* out) {
+    if (P.vertex_stride > SKIN_MAX_DEVICE_STRIDE) return fail(c, TRGL_E_UNSUPPORTED, w + "vertex_stride above 5120 doubles with device memory");
+    SkinArgs a; std::memset(&a, 0, sizeof(a));
+    a.vertices = vertices; a.joints = joints; a.weights = weights; a.palette = palette; a.out = out;
+    a.n = n; a.n_poses = P.n_poses; a.palette_stride = P.palette_stride;
+    a.stride = (uint32_t)P.vertex_stride; a.n_joints = P.n_joints; a.flags = P.flags;
+    a.vb = (uint32_t)std::min<int>(SKIN_BLOCK, SKIN_TILE_DOUBLES / P.vertex_stride);
+    a.n_vblocks = (n + a.vb - 1) / a.vb;
+    if (!mul_fits(a.n_vblocks, (P.n_poses + SKIN_POSE_GROUP - 1) / SKIN_POSE_GROUP, 0x7fffffffull))
+        return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more blocks in one call");
+    launch_skin_stage(c->stream, a, P.n_influences);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+extern "C" {
+
+int trgl_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
+                      int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    bool go;
+    if ((r = check_draw_indexed(c, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &go)) || !go) return r;
+    return draw_indexed_checked(c, -1, TRGL_VARY_PHONG, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, nullptr, mem_kind);
+}
+
+int trgl_draw_indexed_vs(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
+                         int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    int K = 0; bool go;
+    if ((r = check_draw_indexed_vs(c, vs, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &K, &go)) || !go) return r;
+    return draw_indexed_checked(c, vs, K, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, colors, mem_kind);
+}
+
+int trgl_draw_indexed_vs_clipped(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16], const double plane[4],
+                                 const trgl_clip_attr* attrs, int n_attrs, const double* vertices, int stride, uint64_t n_vertices,
+                                 const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    int K = TRGL_VARY_PHONG; bool go;
+    if (vs == -1) r = check_draw_indexed(c, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &go);
+    else r = check_draw_indexed_vs(c, vs, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &K, &go);
+    if (r) return r;
+    ClipSpec spec{ plane, attrs, n_attrs, {} };
+    if ((r = clip_spec_table(c, "trgl_draw_indexed_vs_clipped: ", spec, kind, K)) || !go) return r;
+    return draw_indexed_checked(c, vs, K, kind, u, projection, vertices, stride, n_vertices, indices, n_faces, colors, mem_kind, &spec);
+}
+
+int trgl_vertex_stage(trgl_ctx* c, int vs, const trgl_uniforms* u, const double projection[16], const double* vertices, int stride,
+                      uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, double* clip_out, double* vary_out, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_vertex_stage: ";
+    int K = 0;
+    if ((r = check_vertex_call(c, w, vs, true, u, projection, vertices, stride, n_vertices, indices, n_faces, mem_kind, &K))) return r;
+    if (!clip_out || (K && !vary_out)) return fail(c, TRGL_E_INVALID, w + "null output");
+    if (n_faces == 0) return TRGL_OK;
+    if (mem_kind == TRGL_MEM_DEVICE) {
+        if (!aligned({ { clip_out, 16 }, { K ? vary_out : nullptr, 16 } })) return fail(c, TRGL_E_INVALID, w + "device outputs must be 16-byte aligned");
+        return queue_vertex_stage(c, vs, u, projection, vertices, stride, indices, n_faces, clip_out, K ? vary_out : nullptr);
+    }
+    // host memory: through buffers of this call's own, filled in stream order
+    CallMem mem(c, false);
+    double* d_v = nullptr; uint32_t* d_i = nullptr; Rows o;
+    if ((r = mem.alloc(n_vertices * (size_t)stride, &d_v)) || (r = mem.alloc(3 * n_faces, &d_i)) || (r = alloc_rows(mem, n_faces, K, false, &o))) return r;
+    HIPCHK(c, hipMemcpyAsync(d_v, vertices, n_vertices * (size_t)stride * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_i, indices, 3 * n_faces * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if ((r = queue_vertex_stage(c, vs, u, projection, d_v, stride, d_i, n_faces, o.clip, o.vary))) return r;
+    HIPCHK(c, hipMemcpyAsync(clip_out, o.clip, n_faces * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (K) HIPCHK(c, hipMemcpyAsync(vary_out, o.vary, n_faces * (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return mem.done();
+}
+
+int trgl_clip_stage(trgl_ctx* c, const double plane[4], const trgl_clip_attr* attrs, int n_attrs, int K, const double* clip, const double* vary,
+                    const uint32_t* colors, uint64_t n, double* clip_out, double* vary_out, uint32_t* colors_out, uint64_t* n_out, int mem_kind) {
+    const std::string w = "trgl_clip_stage: ";
+    int r = check_mem(c, w, mem_kind); if (r) return r;
+    if (!plane || !n_out) return fail(c, TRGL_E_INVALID, w + "null plane or n_out");
+    ClipTable tab;
+    if (!clip_table(attrs, n_attrs, K, &tab)) return fail(c, TRGL_E_INVALID, w + "invalid clip attribute list (or K outside 0..TRGL_MAX_USER_VARY)");
+    *n_out = 0;
+    if (n == 0) return TRGL_OK;
+    if (!clip || !clip_out || (K && (!vary || !vary_out)) || (colors && !colors_out)) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (mem_kind == TRGL_MEM_HOST) { *n_out = host_clip_stage(plane, tab, K, clip, vary, colors, n, clip_out, vary_out, colors_out); return TRGL_OK; }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more triangles in one call");
+    if (!aligned({ { clip, 8 }, { clip_out, 8 }, { K ? vary : nullptr, 8 }, { K ? vary_out : nullptr, 8 }, { colors, 4 }, { colors ? colors_out : nullptr, 4 } }))
+        return fail(c, TRGL_E_INVALID, w + "device arrays need natural alignment (8 bytes for doubles, 4 for colours)");
+    unsigned long long total = 0;
+    if ((r = queue_clip_stage(c, plane, tab, K, clip, vary, colors, n, Rows{ clip_out, vary_out, colors_out }, &total))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_out = total;
+    return TRGL_OK;
+}
+
+int trgl_draw_clipped(trgl_ctx* c, int kind, const trgl_uniforms* u, const double plane[4], const trgl_clip_attr* attrs, int n_attrs,
+                      const double* clip, const double* vary, const uint32_t* colors, uint64_t n, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_draw_clipped: ";
+    const int K = kind_vary_count(c, kind);
+    if (K < 0) return fail(c, TRGL_E_INVALID, w + "unknown shader kind");
+    ClipSpec spec{ plane, attrs, n_attrs, {} };
+    if ((r = clip_spec_table(c, w, spec, kind, K))) return r;
+    if (n == 0) return TRGL_OK;
+    if (!clip) return fail(c, TRGL_E_INVALID, w + "clip is null");
+    if (K && !vary) return fail(c, TRGL_E_INVALID, w + "this shader kind needs varyings");
+    if ((r = check_kind_uniforms(c, w, kind, u)) || (r = check_mem(c, w, mem_kind))) return r;
+    if (mem_kind == TRGL_MEM_DEVICE) {
+        StageHold hold(c);
+        return draw_device_clipped(c, kind, K, u, &spec, clip, vary, colors, n);
+    }
+    if (n > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more triangles in one call");
+    return no_bad_alloc(c, w, [&] {
+        const HostRows host(2 * n, K, colors != nullptr); const Rows& o = host.o;
+        const uint64_t n_out = host_clip_stage(plane, spec.tab, K, clip, vary, colors, n, o.clip, o.vary, o.colors);
+        return trgl_draw(c, kind, u, o.clip, o.vary, o.colors, n_out, TRGL_MEM_HOST);
+    });
+}
+
+int trgl_skin_stage(trgl_ctx* c, const trgl_skin_params* P, const double* vertices, uint64_t n, const uint16_t* joints, const double* weights,
+                    const double* palette, int mem_kind, double* out) {
+    const std::string w = "trgl_skin_stage: ";
+    int r = check_skin_params(c, w, P, mem_kind, n); if (r) return r;
+    if (n == 0) return TRGL_OK;
+    if ((r = check_skin_arrays(c, w, *P, vertices, n, joints, weights, palette, mem_kind, out))) return r;
+    if (mem_kind == TRGL_MEM_HOST) { host_skin_stage(*P, vertices, n, joints, weights, palette, out); return TRGL_OK; }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    return queue_skin_stage(c, w, *P, vertices, n, joints, weights, palette, out);
+}
+
+int trgl_pose_palette(trgl_ctx* c, const int32_t* parents, const double* inverse_bind, uint32_t n_joints, const double* local,
+                      uint64_t local_stride, uint64_t n_poses, int mem_kind, double* palette, uint64_t palette_stride) {
+    const std::string w = "trgl_pose_palette: ";
+    if (int r = check_mem(c, w, mem_kind)) return r;
+    if (n_joints < 1) return fail(c, TRGL_E_INVALID, w + "n_joints must be >= 1");
+    for (const uint64_t stride : { local_stride, palette_stride })
+        if (stride < 16ull * n_joints && !(stride == 0 && n_poses <= 1)) return fail(c, TRGL_E_INVALID, w + "a stride must be >= 16 * n_joints (or 0 with one pose)");
+    if (!mul_fits(n_poses, local_stride, 1ull << 60) || !mul_fits(n_poses, palette_stride, 1ull << 60))
+        return fail(c, TRGL_E_UNSUPPORTED, w + "the arrays are too large");
+    if (n_poses == 0) return TRGL_OK;
+    if (!parents || !local || !palette) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (!aligned({ { inverse_bind, 8 }, { local, 8 }, { palette, 8 }, { parents, 4 } }))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 4 for parents)");
+    const uint64_t mats = 16ull * n_joints * 8, out_bytes = (n_poses - 1) * palette_stride * 8 + mats;
+    if (arrays_overlap(parents, 4ull * n_joints, palette, out_bytes) || arrays_overlap(inverse_bind, mats, palette, out_bytes) ||
+        arrays_overlap(local, (n_poses - 1) * local_stride * 8 + mats, palette, out_bytes))
+        return fail(c, TRGL_E_INVALID, w + "the output overlaps an input");
+    if (mem_kind == TRGL_MEM_HOST) {
+        for (uint32_t j = 0; j < n_joints; ++j)
+            if (parents[j] != -1 && !pose_parent_below(parents[j], j)) return fail(c, TRGL_E_INVALID, w + "a parent must be -1 or a joint below its child");
+        return no_bad_alloc(c, w, [&] {
+            host_pose_palette(parents, inverse_bind, n_joints, local, local_stride, n_poses, palette, palette_stride);
+            return TRGL_OK;
+        });
+    }
+    CHKCTX(c);
+    if (int r = end_pending_raster(c)) return r;
+    if ((n_poses + POSE_GROUP - 1) / POSE_GROUP > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more blocks in one call");
+    PoseArgs a; std::memset(&a, 0, sizeof(a));
+    a.parents = parents; a.inverse_bind = inverse_bind; a.local = local; a.palette = palette;
+    a.local_stride = local_stride; a.n_poses = n_poses; a.palette_stride = palette_stride; a.n_joints = n_joints;
+    launch_pose_palette(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return TRGL_OK;
+}
+
+int trgl_draw_skinned(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16], const trgl_skin_params* P,
+                      const double* vertices, uint64_t n, const uint16_t* joints, const double* weights, const double* palette,
+                      const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_draw_skinned: ";
+    if ((r = check_skin_params(c, w, P, mem_kind, n))) return r;
+    if (P->n_poses != 1) return fail(c, TRGL_E_INVALID, w + "n_poses must be 1");
+    if (vs == -1 && colors) return fail(c, TRGL_E_INVALID, w + "colors: only with a vertex shader");
+    const int stride = P->vertex_stride;
+    int K = TRGL_VARY_PHONG; bool go;
+    // (what the draw would refuse is refused before the skin stage is queued; `vertices` stands in for the skinned array)
+    if (vs == -1) r = check_draw_indexed(c, kind, u, projection, vertices, stride, n, indices, n_faces, mem_kind, &go);
+    else r = check_draw_indexed_vs(c, vs, kind, u, projection, vertices, stride, n, indices, n_faces, mem_kind, &K, &go);
+    if (r || !go) return r;
+    if (n == 0) return fail(c, TRGL_E_INVALID, w + "faces without vertices");
+    if (mem_kind == TRGL_MEM_HOST) return no_bad_alloc(c, w, [&] {
+        std::vector<double> skinned((size_t)n * (size_t)stride);
+        if (int e = check_skin_arrays(c, w, *P, vertices, n, joints, weights, palette, mem_kind, skinned.data())) return e;
+        host_skin_stage(*P, vertices, n, joints, weights, palette, skinned.data());
+        return vs == -1 ? trgl_draw_indexed(c, kind, u, projection, skinned.data(), stride, n, indices, n_faces, TRGL_MEM_HOST)
+                        : trgl_draw_indexed_vs(c, vs, kind, u, projection, skinned.data(), stride, n, indices, n_faces, colors, TRGL_MEM_HOST);
+    });
+    StageHold hold(c);
+    double* skinned = nullptr;
+    if ((r = CallMem(c, true).alloc((size_t)n * (size_t)stride, &skinned))) return r;
+    if ((r = check_skin_arrays(c, w, *P, vertices, n, joints, weights, palette, mem_kind, skinned))) return r;
+    if ((r = queue_skin_stage(c, w, *P, vertices, n, joints, weights, palette, skinned))) return r;
+    return draw_indexed_checked(c, vs, K, kind, u, projection, skinned, stride, n, indices, n_faces, colors, TRGL_MEM_DEVICE);
+}
+
+}  // extern "C"
