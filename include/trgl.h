@@ -730,6 +730,94 @@ int trgl_draw_skinned(trgl_ctx* ctx, int vs, int shader_kind, const trgl_uniform
                       const trgl_skin_params* p, const double* vertices, uint64_t n_vertices, const uint16_t* joints, const double* weights,
                       const double* palette, const uint32_t* indices, uint64_t n_faces, const uint32_t* colors, int mem_kind);
 
+/* ---- mesh edges: the edge list of an indexed mesh, its classes per view, outlines -------------------------------------------------- */
+
+/* New work: the reference has no edges (it draws faces only).  trgl_mesh_edges makes, once per mesh, the list of its distinct edges
+ * with the two faces on each; trgl_edge_select classifies them per view and per pose - boundary, silhouette, crease - and writes the
+ * selected ones as the index pairs trgl_line_stage takes; trgl_draw_outline draws them.  With TRGL_MEM_DEVICE the mesh, its edges and
+ * the segments stay in device memory: wireframes, toon outlines and hard-edge highlights of a skinned mesh (trgl_skin_stage) need no
+ * per-frame host work.
+ *
+ * EDGES (trgl_mesh_edges).  indices: 3 * n_faces uint32; no vertex array is read.  Half-edge h = 3 f + k (k = 0, 1, 2) joins
+ * a = indices[3 f + k] and b = indices[3 f + (k + 1) % 3].  It makes no edge when a == b.  A host index >= n_vertices:
+ * TRGL_E_INVALID, and nothing is written.  A device index >= n_vertices: that half-edge makes no edge, and the entry is never used as
+ * an address.  An edge is a distinct pair (lo, hi) = (min(a, b), max(a, b)); edges are numbered in ascending (lo, hi), lo first.
+ *   RECORD.  Edge e is the four uint32 {lo, hi, f0, f1} at edges_out + 4 e: f0 = h0 / 3 for the lowest-numbered half-edge h0 on the
+ *   edge, f1 = h1 / 3 for the second lowest, or 0xFFFFFFFF when there is only one (f1 == f0 where one face names the pair twice).
+ *   MORE THAN TWO half-edges on an edge (a fan, duplicated faces): the first two count and the rest are ignored.
+ *   CAPACITY AND FILL.  edges_out has room for 3 * n_faces records.  Every word of the records behind the last edge is 0xFFFFFFFF
+ *   ("no edge"), so a later call may run over the capacity without knowing the count.  Nothing behind the capacity is written.
+ *   COUNT.  n_edges is a host pointer.  NULL: no wait.  Non-NULL with device memory: the call waits for the context's stream once, for
+ *   the 8-byte count (as trgl_draw_instanced does) - at load time, the only wait of this section besides the compacted count below.
+ *   n_faces == 0: TRGL_OK once the scalars are checked, *n_edges = 0, no array is touched.  n_vertices above 2^32 - 1: TRGL_E_INVALID (0xFFFFFFFF names no vertex).
+ *   DEVICE PATH.  A key kernel, a stable radix sort of (key, half-edge) pairs over the bits n_vertices needs, a count of the run heads,
+ *   a scan in two levels and a kernel that writes the records and the fill; no atomic decides a position.  Scratch belongs to the
+ *   context and grows on demand.
+ *
+ * CLASSES (trgl_edge_select).  vertices: positions at +0..2 of records of vertex_stride >= 3 doubles; indices as above; edges:
+ * n_edges records - the count, or any capacity up to 3 * n_faces.  trgl_edge_params: eye[4], homogeneous, in model space (w = 1: a
+ * camera position, w = 0: a direction toward the viewer for orthographic views); crease_cos; select, a mask of the TRGL_EDGE_* bits;
+ * class_color[4], the colour of each bit in ascending order; compact; reserved, which must be 0.
+ *   ARITHMETIC.  fp64, each operation rounded, no contraction or reassociation, IEEE division and square root.
+ *   FACE f with positions p0, p1, p2 in index order:
+ *     n = cross(p1 - p0, p2 - p0) as model.cpp:293-299 computes it (geometry.h:143-149);
+ *     d[a] = eye[a] - eye[3] * p0[a], the product rounded, then subtracted;  s = dot<3>(n, d) summed from 0.0;
+ *     front = s > 0.0 (a NaN, and an eye exactly on the face's plane, are not front);
+ *     u = normalized(n) of geometry.h:136-140: length = sqrt(dot<3>(n, n)); a length of exactly 0 leaves n unchanged.
+ *   CODE BYTE of record e:  TRGL_EDGE_ANY: the record is an edge.  TRGL_EDGE_BOUNDARY: f1 is none.  TRGL_EDGE_SILHOUETTE: f1 exists and
+ *     front(f0) != front(f1).  TRGL_EDGE_CREASE: f1 exists and dot<3>(u0, u1) summed from 0.0 < crease_cos (a NaN is false; equality
+ *     is no crease).  A zero-area face has u = 0, so its edges are creases exactly when 0.0 < crease_cos; a NaN position makes its
+ *     faces not front and their edges no creases.
+ *     A "no edge" record - one whose f0 is 0xFFFFFFFF - gets code 0.  Any other record whose f0 or f1 (where not none) is >= n_faces,
+ *     or whose faces name a vertex >= n_vertices: TRGL_E_INVALID with host memory (nothing is written), code 0 with device memory, and
+ *     the entry is never used as an address.  lo and hi are copied, not checked: trgl_line_stage checks them where they are used.
+ *   SELECTED: code & select is non-zero.
+ *   OUTPUTS, each may be NULL.  codes_out: one byte per record.  segments_out: one uint32 pair per record, (lo, hi) when selected,
+ *     else (0xFFFFFFFF, 0xFFFFFFFF) - the index array of trgl_line_stage, where in device memory such a pair names no point and becomes
+ *     all-zero rows (in host memory trgl_line_stage refuses it as an index out of range: host callers compact).
+ *     colors_out: one per record, class_color of the lowest set bit of code & select, or 0 when not selected.
+ *   COMPACTION.  compact != 0: the selected pairs and their colours move to the front in ascending record number, and the n_edges -
+ *     n_selected entries behind them are the "no edge" pair and colour 0; codes_out stays per record.  n_selected is a host pointer:
+ *     NULL means no wait, non-NULL with device memory one 8-byte wait.  compact == 0: the call never waits; n_selected is written with
+ *     host memory only (the number of selected records) and ignored with device memory.
+ *   The kernel computes both faces of an edge from their six vertices per edge; no per-face scratch is kept between calls.
+ *
+ * trgl_draw_outline: trgl_edge_select with compaction (params->compact is ignored) into buffers the context owns until the flush is
+ * done, then trgl_draw_lines of the selected segments and their colours with the mesh's vertices as points and n_segments set to the
+ * count.  With device memory the call waits once for its 8-byte count (the rule of trgl_draw_clipped); nothing selected queues nothing.
+ * shader_kind takes K = 6 or 0 varyings.  Frame bytes, depths and every counter equal those of the two calls made by hand.
+ * DEPTH.  A line lies in the surface it outlines.  The caller who wants it in front biases the depth in the `projection` of
+ * trgl_line_params (a slightly nearer z row); there is no bias parameter.
+ *
+ * MEMORY AND ORDER.  One mem_kind covers every array of a call.  Host memory: plain C++, ctx may be NULL, no GPU is touched, complete
+ * on return.  Device memory: vertices 8-byte aligned, every uint32 array 4 - nothing wider is assumed - codes at any address; the bytes
+ * never depend on the alignment.  The kernels are queued on the context's stream in order with the draws: nothing is flushed; they
+ * complete a begun flush, as trgl_clip_stage does.  Device inputs are read when the kernels run, not at the flush.
+ * ERRORS.  TRGL_E_INVALID: a bad mem_kind, TRGL_MEM_DEVICE without a context, params NULL, select outside the four bits, reserved not 0,
+ * vertex_stride < 3, n_edges above 3 * n_faces, with n_faces > 0 (n_edges > 0 for the selection) a null input array, a misaligned
+ * array, an output that overlaps an input or another output, a host index or record out of range; for trgl_draw_outline also those of
+ * trgl_draw_lines.  TRGL_E_UNSUPPORTED: 3 * n_faces above 2^31 - 1.  n_edges == 0: TRGL_OK once the scalars are checked,
+ * *n_selected = 0, and no array is read or written. */
+#define TRGL_EDGE_ANY        1u
+#define TRGL_EDGE_BOUNDARY   2u
+#define TRGL_EDGE_SILHOUETTE 4u
+#define TRGL_EDGE_CREASE     8u
+typedef struct trgl_edge_params {
+    double   eye[4];
+    double   crease_cos;
+    uint32_t class_color[4];   /* ANY, BOUNDARY, SILHOUETTE, CREASE */
+    uint32_t select, compact;
+    uint64_t reserved;
+} trgl_edge_params;
+int trgl_mesh_edges(trgl_ctx* ctx, const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, int mem_kind,
+                    uint32_t* edges_out, uint64_t* n_edges);
+int trgl_edge_select(trgl_ctx* ctx, const trgl_edge_params* params, const double* vertices, int vertex_stride, uint64_t n_vertices,
+                     const uint32_t* indices, uint64_t n_faces, const uint32_t* edges, uint64_t n_edges, int mem_kind,
+                     uint8_t* codes_out, uint32_t* segments_out, uint32_t* colors_out, uint64_t* n_selected);
+int trgl_draw_outline(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* uniforms, const trgl_line_params* line_params,
+                      const trgl_edge_params* params, const double* vertices, int vertex_stride, uint64_t n_vertices,
+                      const uint32_t* indices, uint64_t n_faces, const uint32_t* edges, uint64_t n_edges, int mem_kind);
+
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 
 /* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and
@@ -807,7 +895,7 @@ int trgl_flush(trgl_ctx* ctx);
  * flush first, with two exceptions.  The five calls that only queue work over caller-owned device arrays and flush
  * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths, trgl_depth_order and trgl_triangle_depths with
  * TRGL_MEM_DEVICE - leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those five,
- * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
+ * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_edges, trgl_edge_select, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
  * computes on the host and returns without touching the context's queue.  A call refused for its arguments or for the
  * context's state may return before it completes anything.
  * bench.py: the RCCL gather of the previous frame's strips runs under the next frame's first half. */

@@ -43,6 +43,9 @@ ORDER_BACK_TO_FRONT, ORDER_FRONT_TO_BACK = 0, 1     # TRGL_ORDER_*
 TRI_DEPTH_CENTROID, TRI_DEPTH_NEAREST, TRI_DEPTH_FARTHEST = 0, 1, 2     # TRGL_TRI_DEPTH_*
 CENTROID, NEAREST, FARTHEST = TRI_DEPTH_CENTROID, TRI_DEPTH_NEAREST, TRI_DEPTH_FARTHEST
 SKIN_NORMAL, SKIN_TANGENT, SKIN_BITANGENT = 1, 2, 4     # TRGL_SKIN_*: the directions of a vertex record that trgl_skin_stage transforms
+EDGE_ANY, EDGE_BOUNDARY, EDGE_SILHOUETTE, EDGE_CREASE = 1, 2, 4, 8     # TRGL_EDGE_*: the class bits of an edge's code byte
+EDGE_NONE = 0xFFFFFFFF        # every word of a "no edge" record, f1 of a boundary edge, both words of a "no edge" segment
+EDGE_BLOCK = 256              # records per block of the edge kernels (csrc/launch.h); their scan has the levels of INST_SCAN_CHUNK
 SPRITE_VIEW, SPRITE_SCREEN = 0, 1     # TRGL_SPRITE_*: a sprite's size in eye-space units, or in units of the caller's scale[]
 FRUSTUM_SET, FRUSTUM_MERGE = 0, 1     # TRGL_FRUSTUM_*: the mode of trgl_frustum_boxes
 NEAR_PLANE = (0.0, 0.0, 1.0, 1.0)     # the near plane of the reference's projection in clip space: z + w >= 0
@@ -74,6 +77,7 @@ SYMBOLS = [
     "trgl_triangle_depths", "trgl_order_stage", "trgl_draw_ordered",
     "trgl_sprite_stage", "trgl_draw_sprites", "trgl_line_stage", "trgl_draw_lines",
     "trgl_skin_stage", "trgl_pose_palette", "trgl_draw_skinned",
+    "trgl_mesh_edges", "trgl_edge_select", "trgl_draw_outline",
     "trgl_mip_layout", "trgl_image_mipmaps", "trgl_texture_mipmaps", "trgl_selftest_sampler_lod", "trgl_image_sample", "trgl_lod_stage", "trgl_selftest_mip_lod",
 ]
 MAX_MIP_LEVELS = 16
@@ -213,6 +217,8 @@ def load_library(path: str = None):
         L.trgl_debug_binning.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if hasattr(L, "trgl_debug_radix_blocks"):
         L.trgl_debug_radix_blocks.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "trgl_debug_edge_sort"):
+        L.trgl_debug_edge_sort.argtypes = [vp, C.c_uint64, C.c_uint64]
     L.trgl_selftest_division.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
     L.trgl_selftest_sampler.argtypes = [vp, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.trgl_draw_indexed.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
@@ -305,6 +311,11 @@ def load_library(path: str = None):
     L.trgl_pose_palette.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64]
     L.trgl_draw_skinned.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+    L.trgl_mesh_edges.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, u64p]
+    L.trgl_edge_select.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, u64p]
+    L.trgl_draw_outline.argtypes = [vp, C.c_int, C.POINTER(Uniforms), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p,
+                                    C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -964,6 +975,94 @@ def line_stage(params, points, indices=None, colors=None, n_segments=None):
     points 2 j and 2 j + 1 - becomes a quad of params.width (params: make_line_params), cut at clip w = w_min.  Returns (clip [2 n, 12],
     varyings [2 n, 6], colors [2 n] or None).  Needs no GPU."""
     return _line_stage(load_library(), None, params, points, indices, colors, n_segments, False, None)[1]
+
+
+class EdgeParams(C.Structure):
+    """trgl_edge_params"""
+    _fields_ = [("eye", C.c_double * 4), ("crease_cos", C.c_double), ("class_color", C.c_uint32 * 4), ("select", C.c_uint32),
+                ("compact", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+def make_edge_params(eye, crease_cos=-2.0, select=EDGE_ANY, class_color=(0, 0, 0, 0), compact=False):
+    """trgl_edge_params: eye (x, y, z, w) in model space - w = 1 a camera position, w = 0 a direction toward the viewer; an edge is a
+    crease when the dot product of its faces' unit normals is below crease_cos (-2: never); select: a mask of EDGE_ANY, EDGE_BOUNDARY,
+    EDGE_SILHOUETTE, EDGE_CREASE; class_color: the colour of each of the four in that order; compact: selected segments to the front."""
+    return EdgeParams((C.c_double * 4)(*_f64(eye, 4, "eye")), float(crease_cos), (C.c_uint32 * 4)(*[int(x) & 0xFFFFFFFF for x in class_color]),
+                      int(select), 1 if compact else 0, 0)
+
+
+def _words32(a, device, what, cols=None):
+    """A 32-bit array as the edge calls take it: a contiguous device tensor with device=True, else a numpy uint32 array."""
+    if device:
+        if not _is_device_tensor(a) or a.element_size() != 4 or not a.is_contiguous():
+            raise ValueError(f"device=True: {what} must be a contiguous 32-bit device tensor")
+        return a
+    a = np.ascontiguousarray(a, np.uint32)
+    return a if cols is None else a.reshape(-1, cols)
+
+
+def _mesh_edges(L, handle, indices, n_vertices, device, out, count):
+    """Returns (arrays to keep alive, edges [3 n_faces, 4], n_edges or None)."""
+    indices = _words32(indices, device, "indices", 3)
+    nf = int(indices.numel() if device else indices.size) // 3
+    if out is None:
+        if device:
+            import torch
+            out = torch.empty((3 * nf, 4), dtype=torch.int32, device=indices.device)
+        else:
+            out = np.empty((3 * nf, 4), np.uint32)
+    n = C.c_uint64(0)
+    p = _device_ptr if device else _ptr
+    rc = L.trgl_mesh_edges(handle, p(indices) if nf else None, nf, int(n_vertices), MEM_DEVICE if device else MEM_HOST, p(out) if nf else None,
+                           C.byref(n) if count else None)
+    if rc != 0:
+        raise TrglError(f"trgl_mesh_edges failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (indices,), out, (int(n.value) if count else None)
+
+
+def _edge_select(L, handle, params, vertices, indices, edges, n_edges, device, out, count):
+    """Returns (arrays to keep alive, (codes [n], segments [n, 2], colors [n]), n_selected or None); out: three arrays, each may be None
+    (not written) - all three are allocated when out is None."""
+    if device:
+        _device_f64(vertices, 2, "vertices")
+    else:
+        vertices = np.ascontiguousarray(vertices, np.float64)
+        if vertices.ndim != 2:
+            raise ValueError("vertices must have 2 dimensions [n, stride]")
+    indices = _words32(indices, device, "indices", 3)
+    edges = _words32(edges, device, "edges", 4)
+    nf = int(indices.numel() if device else indices.size) // 3
+    n = int(edges.numel() if device else edges.size) // 4 if n_edges is None else int(n_edges)
+    if out is None:
+        if device:
+            import torch
+            out = (torch.empty(n, dtype=torch.uint8, device=vertices.device), torch.empty((n, 2), dtype=torch.int32, device=vertices.device),
+                   torch.empty(n, dtype=torch.int32, device=vertices.device))
+        else:
+            out = (np.empty(n, np.uint8), np.empty((n, 2), np.uint32), np.empty(n, np.uint32))
+    nsel = C.c_uint64(0)
+    p = _device_ptr if device else _ptr
+    rc = L.trgl_edge_select(handle, C.byref(params), p(vertices), int(vertices.shape[1]), int(vertices.shape[0]), p(indices), nf, p(edges), n,
+                            MEM_DEVICE if device else MEM_HOST, p(out[0]), p(out[1]), p(out[2]), C.byref(nsel) if count else None)
+    if rc != 0:
+        raise TrglError(f"trgl_edge_select failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (vertices, indices, edges), out, (int(nsel.value) if count else None)
+
+
+def mesh_edges(indices, n_vertices):
+    """trgl_mesh_edges for host arrays without a context: the distinct edges of the faces indices [n_faces, 3] in ascending (lo, hi).
+    Returns (edges [3 n_faces, 4] uint32 - records {lo, hi, f0, f1}, f1 = EDGE_NONE on a boundary, every word EDGE_NONE behind the last
+    edge - and the number of edges).  Needs no GPU."""
+    _, out, n = _mesh_edges(load_library(), None, indices, n_vertices, False, None, True)
+    return out, n
+
+
+def edge_select(params, vertices, indices, edges, n_edges=None):
+    """trgl_edge_select for host arrays without a context: the code byte of every edge record under params (make_edge_params), the
+    index pair of every selected one - what line_stage takes as indices - and its colour.  Returns (codes [n], segments [n, 2],
+    colors [n], n_selected); with params.compact the selected pairs and colours come first.  Needs no GPU."""
+    _, out, n = _edge_select(load_library(), None, params, vertices, indices, edges, n_edges, False, None, True)
+    return out[0], out[1], out[2], n
 
 
 class SkinParams(C.Structure):
@@ -1657,6 +1756,47 @@ class Context:
         self._chk(self.L.trgl_draw_lines(self.h, kind, None if uniforms is None else C.byref(uniforms), C.byref(params), p(points),
                                          int(points.shape[1]), int(points.shape[0]), p(indices), p(colors),
                                          _line_segments(points, indices, n_segments), MEM_DEVICE if device else MEM_HOST))
+
+    def mesh_edges(self, indices, n_vertices, device=False, out=None, count=True):
+        """trgl_mesh_edges (see the module's mesh_edges).  device=True: indices [n_faces, 3] is a 32-bit device tensor and the records
+        come back as a device tensor [3 n_faces, 4] (`out` when given); an index >= n_vertices makes no edge.  count=True waits once for
+        the 8-byte count; count=False queues the kernels without waiting and returns None for it.  Returns (edges, n_edges)."""
+        keep, out, n = _mesh_edges(self.L, self.h, indices, n_vertices, device, out, count)
+        if device:
+            self._keep.append((keep, out))
+        return out, n
+
+    def edge_select(self, params, vertices, indices, edges, n_edges=None, device=False, out=None, count=None):
+        """trgl_edge_select (see the module's edge_select).  device=True: vertices [n, stride] f64, indices and edges (32-bit) are device
+        tensors - vertices may be one pose of skin_stage's output -, out = (codes uint8, segments, colors) device tensors, each may be
+        None (allocated with torch when out is None); queued on the context's stream.  count (default: params.compact): wait once for
+        the 8-byte count of selected records.  Returns (codes, segments, colors, n_selected or None): segments and colors are what
+        draw_lines takes as indices and colors."""
+        if count is None:
+            count = bool(params.compact) or not device
+        keep, out, n = _edge_select(self.L, self.h, params, vertices, indices, edges, n_edges, device, out, count)
+        if device:
+            self._keep.append((keep, out))
+        return out[0], out[1], out[2], n
+
+    def draw_outline(self, kind, line_params, edge_params, vertices, indices, edges, n_edges=None, uniforms=None, device=False):
+        """trgl_draw_outline: edge_select with compaction into buffers of the context's, then draw_lines of the selected segments in
+        their class colours with the mesh's vertices as points; the kind takes 6 varyings or none.  device=True: every array is a
+        device tensor, and the call waits once for the count.  A line lies in the surface: bias the depth in line_params.projection."""
+        if device:
+            _device_f64(vertices, 2, "vertices")
+        else:
+            vertices = np.ascontiguousarray(vertices, np.float64)
+        indices = _words32(indices, device, "indices", 3)
+        edges = _words32(edges, device, "edges", 4)
+        nf = int(indices.numel() if device else indices.size) // 3
+        n = int(edges.numel() if device else edges.size) // 4 if n_edges is None else int(n_edges)
+        p = _device_ptr if device else _ptr
+        if device:
+            self._keep.append((vertices, indices, edges))
+        self._chk(self.L.trgl_draw_outline(self.h, kind, None if uniforms is None else C.byref(uniforms), C.byref(line_params),
+                                           C.byref(edge_params), p(vertices), int(vertices.shape[1]), int(vertices.shape[0]), p(indices), nf,
+                                           p(edges), n, MEM_DEVICE if device else MEM_HOST))
 
     def skin_stage(self, vertices, joints, weights, palette, flags=0, device=False, out=None):
         """trgl_skin_stage (see the module's skin_stage).  Host arrays: numpy, no GPU work.  device=True: vertices [n, stride] f64,

@@ -211,29 +211,33 @@ namespace trgl {
 uint32_t inst_num_blocks(uint64_t n) { return (uint32_t)((n + INST_BLOCK - 1) / INST_BLOCK); }
 size_t inst_scratch_words(uint64_t n) { const size_t nblk = inst_num_blocks(n); return 2 + nblk + (nblk + INST_SCAN_CHUNK - 1) / INST_SCAN_CHUNK; }
 
+void launch_block_count_scan(hipStream_t s, uint32_t* blk, uint32_t nblk, uint32_t* chunk, unsigned long long* total) {
+    const uint32_t nchunks = (nblk + INST_SCAN_CHUNK - 1) / INST_SCAN_CHUNK;
+    hipLaunchKernelGGL(k_inst_scan_chunks, dim3(nchunks), dim3(INST_SCAN_CHUNK), 0, s, blk, nblk, chunk);
+    hipLaunchKernelGGL(k_inst_scan_top, dim3(1), dim3(INST_SCAN_CHUNK), 0, s, chunk, nchunks, total);
+}
+
 static Mat4 mat4_of(const double m[16]) { Mat4 r; for (int e = 0; e < 16; ++e) r.m[e] = m[e]; return r; }
 
 void launch_inst_compact(hipStream_t s, const uint8_t* visible, uint32_t n, uint32_t* scratch, uint32_t* list,
                          const double model_view[16], const double* instances, int inst_stride, double* mv_out) {
-    const uint32_t nblk = inst_num_blocks(n), nchunks = (nblk + INST_SCAN_CHUNK - 1) / INST_SCAN_CHUNK;
+    const uint32_t nblk = inst_num_blocks(n);
     unsigned long long* total = reinterpret_cast<unsigned long long*>(scratch);
     uint32_t* blk = scratch + 2; uint32_t* chunk = blk + nblk;
     Mat4 mvu; for (int e = 0; e < 16; ++e) mvu.m[e] = mv_out ? model_view[e] : 0.0;
     hipLaunchKernelGGL(k_inst_count, dim3(nblk), dim3(INST_BLOCK), 0, s, visible, n, blk);
-    hipLaunchKernelGGL(k_inst_scan_chunks, dim3(nchunks), dim3(INST_SCAN_CHUNK), 0, s, blk, nblk, chunk);
-    hipLaunchKernelGGL(k_inst_scan_top, dim3(1), dim3(INST_SCAN_CHUNK), 0, s, chunk, nchunks, total);
+    launch_block_count_scan(s, blk, nblk, chunk, total);
     hipLaunchKernelGGL(k_inst_scatter, dim3(nblk), dim3(INST_BLOCK), 0, s, visible, n, blk, chunk, list, mvu, instances, inst_stride, mv_out);
 }
 
 void launch_inst_compact_ordered(hipStream_t s, const uint32_t* order, uint32_t n_order, const uint8_t* visible, uint32_t n, uint32_t* scratch,
                                  uint32_t* list, const double model_view[16], const double* instances, int inst_stride, double* mv_out) {
-    const uint32_t nblk = inst_num_blocks(n_order), nchunks = (nblk + INST_SCAN_CHUNK - 1) / INST_SCAN_CHUNK;
+    const uint32_t nblk = inst_num_blocks(n_order);
     unsigned long long* total = reinterpret_cast<unsigned long long*>(scratch);
     uint32_t* blk = scratch + 2; uint32_t* chunk = blk + nblk;
     Mat4 mvu; for (int e = 0; e < 16; ++e) mvu.m[e] = mv_out ? model_view[e] : 0.0;
     hipLaunchKernelGGL(k_inst_count_ordered, dim3(nblk), dim3(INST_BLOCK), 0, s, order, n_order, visible, n, blk);
-    hipLaunchKernelGGL(k_inst_scan_chunks, dim3(nchunks), dim3(INST_SCAN_CHUNK), 0, s, blk, nblk, chunk);
-    hipLaunchKernelGGL(k_inst_scan_top, dim3(1), dim3(INST_SCAN_CHUNK), 0, s, chunk, nchunks, total);
+    launch_block_count_scan(s, blk, nblk, chunk, total);
     hipLaunchKernelGGL(k_inst_scatter_ordered, dim3(nblk), dim3(INST_BLOCK), 0, s, order, n_order, visible, n, blk, chunk, list, mvu, instances,
                        inst_stride, mv_out);
 }

@@ -1,7 +1,7 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
 // kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip,
 // kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_skin.hip,
-// kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
+// kernels_edge.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
 // trgl_stage_rows.cpp (the stages in front of a draw) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -190,6 +190,10 @@ constexpr int INST_SCAN_CHUNK = 256;
 constexpr int INST_VS_FACES = 64;            // output faces of a block of the instanced vertex stage (three threads each)
 uint32_t inst_num_blocks(uint64_t n);
 size_t inst_scratch_words(uint64_t n);       // 2 words for the 8-byte count, the block counts, the chunk sums
+// The scan of that compaction alone, for any kernel pair that counts per block of INST_BLOCK lanes (kernels_edge.hip): blk[0 .. nblk)
+// become their exclusive prefix sums within chunks of INST_SCAN_CHUNK, chunk[c] the sum of the chunks before c, *total the sum of all.
+// An entry's position is chunk[b / INST_SCAN_CHUNK] + blk[b] + its rank within block b.  Two launches; nblk > 0, the sum below 2^32.
+void launch_block_count_scan(hipStream_t s, uint32_t* blk, uint32_t nblk, uint32_t* chunk, unsigned long long* total);
 // list[j] = i_j, the instances with (visible[i] & 1) in ascending order, and *total = n_vis; with mv_out, slot j also receives
 // MV = model_view * M_{i_j} (geometry.h:196-205; M: the first 16 doubles of the instance's record).  scratch: inst_scratch_words(n)
 // words, *total its first two.  Four launches, in order on `s`.  0 < n < 2^31.
@@ -278,6 +282,30 @@ struct PoseArgs {
     uint32_t n_joints;
 };
 void launch_pose_palette(hipStream_t s, const PoseArgs& a);
+
+// Mesh edges (kernels_edge.hip; written down under "mesh edges" in include/trgl.h, the key and the arithmetic are edge_core.h's).
+// Every kernel runs EDGE_BLOCK lanes a block, one half-edge or one record per lane; the counts of the blocks go through
+// launch_block_count_scan, so its two levels (INST_SCAN_CHUNK block counts per block of the lower one) are this stage's too.
+// launch_mesh_edges: nh = 3 * n_faces half-edges, 0 < nh < 2^31; indices and edges_out (room for nh records) 4-byte aligned, written 16
+// bytes per record where 16-byte aligned.  scratch: mesh_edges_scratch_bytes() bytes, 256-byte aligned; *total then points at the 8-byte
+// count of edges in it.  A key kernel, the sort, a count, the scan's two launches and a write kernel, in order on `s`.
+// launch_edge_select: 0 < n_edges < 2^31; vertices 8-byte aligned, indices / edges / segments / colors 4, codes any; a null output is not
+// written.  P.compact: scratch of edge_select_scratch_bytes(n_edges) bytes, *total the 8-byte count of selected records in it (four
+// launches); else scratch is unused and *total null (one launch).  The struct travels as the kernels' argument.
+constexpr int EDGE_BLOCK = 256;
+hipError_t mesh_edges_scratch_bytes(uint32_t nh, uint64_t n_vertices, size_t* bytes);
+hipError_t launch_mesh_edges(hipStream_t s, const uint32_t* indices, uint32_t nh, uint64_t n_vertices, void* scratch, size_t scratch_bytes,
+                             uint32_t* edges_out, const unsigned long long** total);
+// the sort of launch_mesh_edges alone, over the keys that call left in the same scratch (a measurement's floor: profiles/outline_probe.py)
+hipError_t launch_mesh_edges_sort(hipStream_t s, uint32_t nh, uint64_t n_vertices, void* scratch, size_t scratch_bytes);
+struct EdgeSelectArgs {
+    trgl_edge_params P;
+    const double* vertices; const uint32_t* indices; const uint32_t* edges;
+    uint8_t* codes; uint32_t* segments; uint32_t* colors;
+    uint64_t n_vertices; uint32_t n_faces, n_edges; int32_t stride;
+};
+size_t edge_select_scratch_bytes(uint32_t n_edges);
+hipError_t launch_edge_select(hipStream_t s, const EdgeSelectArgs& a, void* scratch, const unsigned long long** total);
 
 // World boxes of instances and frustum codes of boxes (kernels_scene.hip; both are written down at trgl_instance_boxes /
 // trgl_frustum_boxes in include/trgl.h, the arithmetic is scene_core.h's).  One thread per instance or box, 0 < n < 2^31; doubles 8-byte

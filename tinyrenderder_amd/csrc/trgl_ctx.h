@@ -97,6 +97,9 @@ struct trgl_ctx {
     // trgl_draw_instanced / trgl_instance_stage: the 8-byte count of drawn instances and the words of the compaction's scan; the list of
     // drawn instances; model_view * M per drawn instance for the built-in stage.  Read by the stages the call queues; grow on demand
     DevBuf<uint32_t> inst_scratch, inst_list; DevBuf<double> inst_mv;
+    // trgl_mesh_edges: the 8-byte count, keys and half-edge numbers with their sorted copies, the scan's words, the sort's own space;
+    // trgl_edge_select with compaction: the 8-byte count, a byte per record, the scan's words.  Grows on demand
+    DevBuf<uint8_t> edge_scratch;
     DevBuf<uint8_t> order_scratch;      // trgl_depth_order: the keys, their sorted copy, the numbers 0 .. n-1, the sort's own space; grows on demand
     DevBuf<uint8_t> pp_out;            // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
@@ -210,6 +213,11 @@ void host_skin_stage(const trgl_skin_params& P, const double* vertices, uint64_t
                      const double* palette, double* out);
 void host_pose_palette(const int32_t* parents, const double* inverse_bind, uint32_t n_joints, const double* local, uint64_t local_stride,
                        uint64_t n_poses, double* palette, uint64_t palette_stride);
+// trgl_mesh_edges over host arrays (every index checked by the caller: below n_vertices; returns the count) and trgl_edge_select (false,
+// and nothing written, for a record out of range; *n_selected may be null).  Both may throw std::bad_alloc.
+uint64_t host_mesh_edges(const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, uint32_t* edges_out);
+bool host_edge_select(const trgl_edge_params& P, const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                      const uint32_t* edges, uint64_t n_edges, uint8_t* codes_out, uint32_t* segments_out, uint32_t* colors_out, uint64_t* n_selected);
 // trgl_instance_boxes and trgl_frustum_boxes over host arrays (local_stride 0: one local box for every instance)
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out);
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);

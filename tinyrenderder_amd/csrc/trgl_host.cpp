@@ -20,6 +20,7 @@
 #include "triorder_core.h"
 #include "sprite_core.h"
 #include "skin_core.h"
+#include "edge_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -338,6 +339,67 @@ void host_pose_palette(const int32_t* parents, const double* inverse_bind, uint3
             for (int e = 0; e < 16; ++e) pal[16 * (size_t)j + e] = skin_canon(t[e]);
         }
     }
+}
+
+// ---- mesh edges in host memory (include/trgl.h, trgl_mesh_edges / trgl_edge_select; the key and the arithmetic are edge_core.h's) ----
+// every index is below n_vertices (checked by the caller); returns the number of edges
+uint64_t host_mesh_edges(const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, uint32_t* edges_out) {
+    const int bits = edge_index_bits(n_vertices);
+    const uint64_t none = edge_key_none(bits), nh = 3 * n_faces;
+    std::vector<std::pair<uint64_t, uint32_t>> he;      // (key, half-edge): pairs are distinct, so their order is the stable sort's by key
+    he.reserve((size_t)nh);
+    for (uint64_t h = 0; h < nh; ++h) {
+        const uint64_t f = h / 3, k = h - 3 * f;
+        const uint64_t key = edge_key(indices[h], indices[3 * f + (k == 2 ? 0 : k + 1)], n_vertices, bits);
+        if (key != none) he.emplace_back(key, (uint32_t)h);
+    }
+    std::sort(he.begin(), he.end());
+    uint64_t e = 0;
+    for (size_t i = 0; i < he.size(); ++i) {
+        if (i && he[i - 1].first == he[i].first) continue;
+        uint32_t* rec = edges_out + 4 * e++;
+        rec[0] = edge_key_lo(he[i].first, bits); rec[1] = edge_key_hi(he[i].first, bits); rec[2] = he[i].second / 3;
+        rec[3] = (i + 1 < he.size() && he[i + 1].first == he[i].first) ? he[i + 1].second / 3 : EDGE_NONE;
+    }
+    for (uint64_t w = 4 * e; w < 4 * nh; ++w) edges_out[w] = EDGE_NONE;
+    return e;
+}
+
+// false, and nothing written, when a record names a face >= n_faces or a face of it a vertex >= n_vertices
+bool host_edge_select(const trgl_edge_params& P, const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                      const uint32_t* edges, uint64_t n_edges, uint8_t* codes_out, uint32_t* segments_out, uint32_t* colors_out, uint64_t* n_selected) {
+    std::vector<uint8_t> codes((size_t)n_edges);
+    const auto face = [&](uint32_t f, EdgeFace* out) {
+        const uint32_t* ix = indices + 3 * (uint64_t)f;
+        if (f >= n_faces || ix[0] >= n_vertices || ix[1] >= n_vertices || ix[2] >= n_vertices) return false;
+        *out = edge_face(vertices + ix[0] * (uint64_t)stride, vertices + ix[1] * (uint64_t)stride, vertices + ix[2] * (uint64_t)stride, P.eye);
+        return true;
+    };
+    for (uint64_t i = 0; i < n_edges; ++i) {
+        const uint32_t f0 = edges[4 * i + 2], f1 = edges[4 * i + 3];
+        if (f0 == EDGE_NONE) { codes[i] = 0; continue; }
+        EdgeFace A, B{};
+        const bool has1 = f1 != EDGE_NONE;
+        if (!face(f0, &A) || (has1 && !face(f1, &B))) return false;
+        codes[i] = edge_code(A, has1, B, P.crease_cos);
+    }
+    uint64_t slot = 0;
+    for (uint64_t i = 0; i < n_edges; ++i) {
+        const uint32_t sel = codes[i] & P.select;
+        if (codes_out) codes_out[i] = codes[i];
+        if (P.compact && !sel) continue;
+        const uint64_t at = P.compact ? slot : i;
+        if (sel) ++slot;
+        if (segments_out) { segments_out[2 * at] = sel ? edges[4 * i] : EDGE_NONE; segments_out[2 * at + 1] = sel ? edges[4 * i + 1] : EDGE_NONE; }
+        if (colors_out) colors_out[at] = sel ? edge_color(P.class_color, sel) : 0u;
+    }
+    if (P.compact)
+        for (uint64_t at = slot; at < n_edges; ++at) {
+            if (segments_out) { segments_out[2 * at] = EDGE_NONE; segments_out[2 * at + 1] = EDGE_NONE; }
+            if (colors_out) colors_out[at] = 0u;
+        }
+    if (n_selected) *n_selected = slot;
+    return true;
 }
 
 // ---- world boxes of instances and frustum codes of boxes in host memory (include/trgl.h, trgl_instance_boxes / trgl_frustum_boxes;

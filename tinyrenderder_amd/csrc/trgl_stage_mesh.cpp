@@ -1,12 +1,14 @@
 // trgl_stage_mesh.cpp — the stages over an indexed mesh and the draws behind them: the vertex stage (trgl_draw_indexed,
 // trgl_draw_indexed_vs, trgl_vertex_stage), the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and
-// skeletal animation (trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned).
+// skeletal animation (trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned) and mesh edges (trgl_mesh_edges, trgl_edge_select,
+// trgl_draw_outline).
 // The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <algorithm>
 #include <cstring>
 
 #include "trgl_stage.h"
 #include "skin_core.h"
+#include "edge_core.h"
 
 // The vertex stage of `vs` (-1: k_vertex_stage) over an indexed mesh in device memory, queued on the context's stream.  clip and
 // vary (unused when K = 0) are 16-byte aligned; u == nullptr: zeros, texture slots -1.
@@ -200,6 +202,55 @@ static int queue_skin_stage(trgl_ctx* c, const std::string& w, const trgl_skin_p
     return TRGL_OK;
 }
 
+// ---- mesh edges (include/trgl.h: trgl_mesh_edges, trgl_edge_select, trgl_draw_outline) ----
+// The arrays of a selection call: the mesh, its edge records and the three outputs (each may be null)
+struct EdgeArrays { const double* vertices; int stride; uint64_t n_vertices; const uint32_t* indices; uint64_t n_faces; const uint32_t* edges;
+                    uint64_t n_edges; uint8_t* codes; uint32_t* segments; uint32_t* colors; };
+
+// what the scalars of a selection call must satisfy
+static int check_edge_params(trgl_ctx* c, const std::string& w, const trgl_edge_params* P, const EdgeArrays& a, int mem_kind) {
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    if (int r = check_mem(c, w, mem_kind)) return r;
+    if (P->select & ~(TRGL_EDGE_ANY | TRGL_EDGE_BOUNDARY | TRGL_EDGE_SILHOUETTE | TRGL_EDGE_CREASE)) return fail(c, TRGL_E_INVALID, w + "unknown bit in select");
+    if (P->reserved) return fail(c, TRGL_E_INVALID, w + "reserved must be 0");
+    if (a.stride < 3) return fail(c, TRGL_E_INVALID, w + "vertex_stride must be >= 3 doubles");
+    if (a.n_vertices > 0xffffffffull) return fail(c, TRGL_E_INVALID, w + "n_vertices above 2^32 - 1");
+    if (a.n_faces > 0x7fffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, w + "3 * n_faces above 2^31 - 1");
+    if (a.n_edges > 3 * a.n_faces) return fail(c, TRGL_E_INVALID, w + "n_edges above 3 * n_faces");
+    return TRGL_OK;
+}
+
+// ... and its arrays (n_edges > 0): present, aligned, outputs apart from inputs and from one another
+static int check_edge_arrays(trgl_ctx* c, const std::string& w, const EdgeArrays& a) {
+    if (!a.vertices || !a.indices || !a.edges) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (!aligned({ { a.vertices, 8 }, { a.indices, 4 }, { a.edges, 4 }, { a.segments, 4 }, { a.colors, 4 } }))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for vertices, 4 for 32-bit words)");
+    struct Range { const void* p; uint64_t bytes; };
+    const Range ins[3] = { { a.vertices, a.n_vertices * (uint64_t)a.stride * 8 }, { a.indices, a.n_faces * 12 }, { a.edges, a.n_edges * 16 } };
+    const Range outs[3] = { { a.codes, a.n_edges }, { a.segments, a.n_edges * 8 }, { a.colors, a.n_edges * 4 } };
+    for (const Range& i : ins)
+        for (const Range& o : outs)
+            if (arrays_overlap(i.p, i.bytes, o.p, o.bytes)) return fail(c, TRGL_E_INVALID, w + "an output overlaps an input");
+    for (int x = 0; x < 3; ++x)
+        for (int y = x + 1; y < 3; ++y)
+            if (arrays_overlap(outs[x].p, outs[x].bytes, outs[y].p, outs[y].bytes)) return fail(c, TRGL_E_INVALID, w + "two outputs overlap");
+    return TRGL_OK;
+}
+
+// The selection over device arrays (checked, n_edges > 0), queued on the context's stream; with P.compact, *count is complete when the
+// stream has been waited for (count null: it is not fetched)
+static int queue_edge_select(trgl_ctx* c, const trgl_edge_params& P, const EdgeArrays& a, unsigned long long* count) {
+    int r;
+    if (P.compact && (r = c->edge_scratch.grow(c, edge_select_scratch_bytes((uint32_t)a.n_edges)))) return r;
+    EdgeSelectArgs k; std::memset(&k, 0, sizeof(k));
+    k.P = P; k.vertices = a.vertices; k.indices = a.indices; k.edges = a.edges; k.codes = a.codes; k.segments = a.segments; k.colors = a.colors;
+    k.n_vertices = a.n_vertices; k.n_faces = (uint32_t)a.n_faces; k.n_edges = (uint32_t)a.n_edges; k.stride = a.stride;
+    const unsigned long long* total = nullptr;
+    HIPCHK(c, launch_edge_select(c->stream, k, c->edge_scratch.p, &total));
+    if (total && count) HIPCHK(c, hipMemcpyAsync(count, total, sizeof(*count), hipMemcpyDeviceToHost, c->stream));
+    return TRGL_OK;
+}
+
 extern "C" {
 
 int trgl_draw_indexed(trgl_ctx* c, int kind, const trgl_uniforms* u, const double projection[16], const double* vertices,
@@ -384,6 +435,112 @@ int trgl_draw_skinned(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, con
     if ((r = check_skin_arrays(c, w, *P, vertices, n, joints, weights, palette, mem_kind, skinned))) return r;
     if ((r = queue_skin_stage(c, w, *P, vertices, n, joints, weights, palette, skinned))) return r;
     return draw_indexed_checked(c, vs, K, kind, u, projection, skinned, stride, n, indices, n_faces, colors, TRGL_MEM_DEVICE);
+}
+
+int trgl_mesh_edges(trgl_ctx* c, const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, int mem_kind, uint32_t* edges_out, uint64_t* n_edges) {
+    const std::string w = "trgl_mesh_edges: ";
+    int r = check_mem(c, w, mem_kind); if (r) return r;
+    if (n_vertices > 0xffffffffull) return fail(c, TRGL_E_INVALID, w + "n_vertices above 2^32 - 1");
+    if (n_faces > 0x7fffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, w + "3 * n_faces above 2^31 - 1");
+    if (n_faces == 0) { if (n_edges) *n_edges = 0; return TRGL_OK; }
+    if (!indices || !edges_out) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (!aligned({ { indices, 4 }, { edges_out, 4 } })) return fail(c, TRGL_E_INVALID, w + "arrays must be 4-byte aligned");
+    if (arrays_overlap(indices, n_faces * 12, edges_out, n_faces * 48)) return fail(c, TRGL_E_INVALID, w + "the output overlaps the input");
+    if (mem_kind == TRGL_MEM_HOST) {
+        if (!all_below(indices, 3 * n_faces, n_vertices)) return fail(c, TRGL_E_INVALID, w + "index out of range");
+        return no_bad_alloc(c, w, [&] {
+            const uint64_t e = host_mesh_edges(indices, n_faces, n_vertices, edges_out);
+            if (n_edges) *n_edges = e;
+            return TRGL_OK;
+        });
+    }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    const uint32_t nh = (uint32_t)(3 * n_faces);
+    size_t bytes = 0;
+    HIPCHK(c, mesh_edges_scratch_bytes(nh, n_vertices, &bytes));
+    if ((r = c->edge_scratch.grow(c, bytes))) return r;
+    const unsigned long long* total = nullptr;
+    HIPCHK(c, launch_mesh_edges(c->stream, indices, nh, n_vertices, c->edge_scratch.p, c->edge_scratch.cap, edges_out, &total));
+    if (n_edges) {
+        unsigned long long count = 0;
+        HIPCHK(c, hipMemcpyAsync(&count, total, sizeof(count), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait, at load time
+        *n_edges = count;
+    }
+    return TRGL_OK;
+}
+
+// Diagnostic, not part of include/trgl.h (profiles/outline_probe.py): the radix sort of the last trgl_mesh_edges call with these counts
+// again, over the keys it left in the context's scratch - the floor that call is measured against.  Queued, no wait.
+int trgl_debug_edge_sort(trgl_ctx* c, uint64_t n_faces, uint64_t n_vertices) {
+    CHKCTX(c);
+    if (n_faces == 0 || n_faces > 0x7fffffffull / 3 || n_vertices > 0xffffffffull) return fail(c, TRGL_E_INVALID, "trgl_debug_edge_sort: bad counts");
+    size_t bytes = 0;
+    HIPCHK(c, mesh_edges_scratch_bytes((uint32_t)(3 * n_faces), n_vertices, &bytes));
+    if (c->edge_scratch.cap < bytes) return fail(c, TRGL_E_STATE, "trgl_debug_edge_sort: no trgl_mesh_edges call of this size came before");
+    HIPCHK(c, launch_mesh_edges_sort(c->stream, (uint32_t)(3 * n_faces), n_vertices, c->edge_scratch.p, c->edge_scratch.cap));
+    return TRGL_OK;
+}
+
+int trgl_edge_select(trgl_ctx* c, const trgl_edge_params* P, const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices,
+                     uint64_t n_faces, const uint32_t* edges, uint64_t n_edges, int mem_kind, uint8_t* codes_out, uint32_t* segments_out,
+                     uint32_t* colors_out, uint64_t* n_selected) {
+    const std::string w = "trgl_edge_select: ";
+    const EdgeArrays a{ vertices, stride, n_vertices, indices, n_faces, edges, n_edges, codes_out, segments_out, colors_out };
+    int r = check_edge_params(c, w, P, a, mem_kind); if (r) return r;
+    const bool wants_count = n_selected && (P->compact || mem_kind == TRGL_MEM_HOST);
+    if (n_edges == 0) { if (wants_count) *n_selected = 0; return TRGL_OK; }
+    if ((r = check_edge_arrays(c, w, a))) return r;
+    if (mem_kind == TRGL_MEM_HOST) return no_bad_alloc(c, w, [&] {
+        if (!host_edge_select(*P, vertices, stride, n_vertices, indices, n_faces, edges, n_edges, codes_out, segments_out, colors_out, n_selected))
+            return fail(c, TRGL_E_INVALID, w + "a record names a face or a vertex out of range");
+        return (int)TRGL_OK;
+    });
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    unsigned long long count = 0;
+    if ((r = queue_edge_select(c, *P, a, wants_count ? &count : nullptr))) return r;
+    if (wants_count) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        *n_selected = count;
+    }
+    return TRGL_OK;
+}
+
+int trgl_draw_outline(trgl_ctx* c, int kind, const trgl_uniforms* u, const trgl_line_params* LP, const trgl_edge_params* P, const double* vertices,
+                      int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces, const uint32_t* edges, uint64_t n_edges,
+                      int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_draw_outline: ";
+    EdgeArrays a{ vertices, stride, n_vertices, indices, n_faces, edges, n_edges, nullptr, nullptr, nullptr };
+    if ((r = check_edge_params(c, w, P, a, mem_kind))) return r;
+    // (what trgl_draw_lines would refuse of its scalars is refused before anything is queued: a draw of no segments checks them all)
+    static const uint32_t no_index = 0;
+    if ((r = trgl_draw_lines(c, kind, u, LP, vertices, stride, n_vertices, &no_index, nullptr, 0, mem_kind))) return r;
+    if (n_edges == 0) return TRGL_OK;
+    if ((r = check_edge_arrays(c, w, a))) return r;
+    trgl_edge_params Q = *P; Q.compact = 1;
+    if (mem_kind == TRGL_MEM_HOST) return no_bad_alloc(c, w, [&] {
+        std::vector<uint32_t> segments(2 * (size_t)n_edges), colors((size_t)n_edges);
+        uint64_t n = 0;
+        if (!host_edge_select(Q, vertices, stride, n_vertices, indices, n_faces, edges, n_edges, nullptr, segments.data(), colors.data(), &n))
+            return fail(c, TRGL_E_INVALID, w + "a record names a face or a vertex out of range");
+        return trgl_draw_lines(c, kind, u, LP, vertices, stride, n_vertices, segments.data(), colors.data(), n, TRGL_MEM_HOST);
+    });
+    StageHold hold(c);
+    CallMem mem(c, true);
+    if ((r = mem.alloc(2 * (size_t)n_edges, &a.segments)) || (r = mem.alloc((size_t)n_edges, &a.colors))) return r;
+    unsigned long long count = 0;
+    if ((r = queue_edge_select(c, Q, a, &count))) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait of an outline draw: trgl_draw_lines needs the count on the host
+    if (count == 0) {
+        // nothing is queued; with no draw waiting for a flush either, nobody refers to the staged arrays (the stream has just been waited for)
+        if (c->draws.empty() && c->stage_hold == 1) for (auto& ch : c->stage) ch.used = 0;
+        return TRGL_OK;
+    }
+    return trgl_draw_lines(c, kind, u, LP, vertices, stride, n_vertices, a.segments, a.colors, count, TRGL_MEM_DEVICE);
 }
 
 }  // extern "C"

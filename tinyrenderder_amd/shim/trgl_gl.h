@@ -794,6 +794,67 @@ inline bool gl_draw_skinned(const IShader& shader, trgl_skin_params params, cons
     return ok;
 }
 
+// Mesh edges (include/trgl.h, trgl_mesh_edges / trgl_edge_select / trgl_draw_outline): the distinct edges of an indexed mesh, their
+// classes under an eye in model space - boundary, silhouette, crease - and the selected ones as wide lines.
+// gl_edge_params: eye (x, y, z, w) in model space, w = 1 a camera position, w = 0 a direction; class_color: ANY, BOUNDARY, SILHOUETTE, CREASE.
+inline trgl_edge_params gl_edge_params(const double eye[4], double crease_cos, std::uint32_t select, const std::uint32_t class_color[4]) {
+    trgl_edge_params p{};
+    for (int a = 0; a < 4; ++a) { p.eye[a] = eye[a]; p.class_color[a] = class_color[a]; }
+    p.crease_cos = crease_cos; p.select = select;
+    return p;
+}
+// The edge records {lo, hi, f0, f1} of nfaces faces, on the host, no context needed: `edges` receives exactly the edges, four words
+// each (once per mesh; the records do not depend on the vertices).  A call that fails (gl_last_error()) leaves it empty.
+inline bool gl_mesh_edges(const unsigned int* indices, std::size_t nfaces, std::size_t nvertices, std::vector<std::uint32_t>& edges) {
+    edges.assign(12 * nfaces, 0u);
+    std::uint64_t n = 0;
+    const int rc = trgl_mesh_edges(nullptr, reinterpret_cast<const std::uint32_t*>(indices), nfaces, nvertices, TRGL_MEM_HOST, edges.data(), &n);
+    if (rc != TRGL_OK) { edges.clear(); return trgl_shim::fail("gl_mesh_edges", rc, nullptr); }
+    edges.resize(4 * std::size_t(n));
+    return true;
+}
+// The classes of those edges under `params`: codes one byte per edge; segments (index pairs into the vertices) and colors hold the
+// selected edges only, in edge order - what gl_draw_lines takes.  A call that fails leaves the vectors empty.
+inline bool gl_edge_select(trgl_edge_params params, const double* vertices, int stride, std::size_t nvertices, const unsigned int* indices,
+                           std::size_t nfaces, const std::vector<std::uint32_t>& edges, std::vector<std::uint8_t>& codes,
+                           std::vector<std::uint32_t>& segments, std::vector<std::uint32_t>& colors) {
+    const std::size_t n = edges.size() / 4;
+    codes.assign(n, 0); segments.assign(2 * n, 0u); colors.assign(n, 0u);
+    params.compact = 1;
+    std::uint64_t selected = 0;
+    const int rc = trgl_edge_select(nullptr, &params, vertices, stride, nvertices, reinterpret_cast<const std::uint32_t*>(indices), nfaces, edges.data(), n,
+                                    TRGL_MEM_HOST, codes.data(), segments.data(), colors.data(), &selected);
+    if (rc != TRGL_OK) { codes.clear(); segments.clear(); colors.clear(); return trgl_shim::fail("gl_edge_select", rc, nullptr); }
+    segments.resize(2 * std::size_t(selected)); colors.resize(std::size_t(selected));
+    return true;
+}
+// gl_edge_select and gl_draw_lines of the selected edges in their class colours in one call (trgl_draw_outline), under the globals
+// ModelView, Perspective and Viewport; width in pixels, w_min as for gl_line_params.  The lines lie in the surface they outline: a
+// caller who wants them in front draws under a Perspective whose depth row is slightly nearer.  The shader's kind takes no varyings
+// or the line stage's 6.  A set clip plane is TRGL_E_UNSUPPORTED: this draw is not clipped.
+inline bool gl_draw_outline(const trgl_edge_params& params, double width, double w_min, const double* vertices, int stride, std::size_t nvertices,
+                            const unsigned int* indices, std::size_t nfaces, const std::vector<std::uint32_t>& edges, const IShader& shader,
+                            TGAImage& framebuffer) {
+    using namespace trgl_shim;
+    State& s = state();
+    if (!bind(framebuffer)) return false;
+    bool ok = submit_batch();                                   // earlier rasterize() calls come first
+    trgl_shader_desc d;
+    if (!shader.describe(d)) {
+        std::fprintf(stderr, "trgl: gl_draw_outline(): needs a shader with a device descriptor\n");
+        std::abort();
+    }
+    if (s.clip_on) return fail("gl_draw_outline", TRGL_E_UNSUPPORTED, nullptr);
+    const trgl_line_params lines = gl_line_params(width, w_min);
+    double vp[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) vp[4 * r + c] = Viewport[r][c];
+    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
+         TRGL_SHIM_OK(trgl_draw_outline(s.ctx, d.kind, &d.uniforms, &lines, &params, vertices, stride, nvertices,
+                                        reinterpret_cast<const std::uint32_t*>(indices), nfaces, edges.data(), edges.size() / 4, TRGL_MEM_HOST)) && ok;
+    s.zbuffer_stale_on_host = true;
+    return ok;
+}
+
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
 // write_tga_file(), main.cpp:743,773).  The depths follow on demand through the `zbuffer` proxy.
 // false: something submitted since the last gl_flush() failed (gl_last_error()); the pixels hold what could be drawn.
