@@ -818,6 +818,106 @@ int trgl_draw_outline(trgl_ctx* ctx, int shader_kind, const trgl_uniforms* unifo
                       const trgl_edge_params* params, const double* vertices, int vertex_stride, uint64_t n_vertices,
                       const uint32_t* indices, uint64_t n_faces, const uint32_t* edges, uint64_t n_edges, int mem_kind);
 
+/* ---- mesh subdivision: one level of Loop or linear refinement of an indexed mesh ---------------------------------------------------- */
+
+/* New work: the reference draws the mesh it loaded.  Every stage above keeps the vertex and face count it was given; these calls make,
+ * from a mesh and the edge records trgl_mesh_edges left for it, the mesh with a vertex on every edge and four faces per face.
+ * trgl_subdiv_topology runs once per mesh, from the indices alone; trgl_subdiv_vertices runs per pose over a vertex array - one pose of
+ * trgl_skin_stage's output, say - and trgl_draw_subdivided draws its result.  With TRGL_MEM_DEVICE nothing visits the host.
+ * NONE is 0xFFFFFFFF.  V = n_vertices, E = n_edges AS PASSED, F = n_faces.
+ *
+ * INPUTS OF THE TOPOLOGY.  indices: 3 F uint32.  edges, n_edges: what trgl_mesh_edges made for these indices and this n_vertices -
+ * n_edges is the count, or any capacity up to 3 F, so that no count has to come back to the host.  A "no edge" record is one whose f0
+ * is NONE.  Records ascend in (lo, hi), "no edge" records behind every edge.
+ *
+ * REFINED MESH.  Refined vertex v < V is old vertex v (an EVEN vertex); refined vertex V + e belongs to edge record e (an ODD vertex).
+ * For face f = (a, b, c) let m_ab = V + e(a, b), with e(a, b) the number of the record whose (lo, hi) is (min, max) of the pair.
+ * Face f becomes the four faces at indices_out + 12 f, in this order: (a, m_ab, m_ca), (b, m_bc, m_ab), (c, m_ca, m_bc),
+ * (m_ab, m_bc, m_ca) - orientation is kept.  The lookup uses the pair, not f0 / f1: the third and later faces on a fan edge get the same
+ * odd vertex, and the refinement is watertight wherever the input was.
+ *   THE LOOKUP is stated: with key(lo, hi) = lo * 2^32 + hi, first = 0 and last = E; while first < last: mid = (first + last) / 2,
+ *   first = mid + 1 when key(record mid) < key(pair), else last = mid.  Record `first` names the pair when first < E, its (lo, hi) is the
+ *   pair's and its odd stencil (below) is an edge's.  Over records that ascend this finds the one record of a pair; over others it
+ *   finds what the halving reaches.
+ *   A face with a half-edge that makes no edge (a == b) becomes four faces (0, 0, 0).  Device memory: a face with an index >= V, or
+ *   with a pair that no record names, becomes four faces (0, 0, 0) as well, and no such entry is ever used as an address.  Host memory:
+ *   both are TRGL_E_INVALID, and nothing is written.
+ *
+ * STENCILS.  stencils_out: trgl_subdiv_stencil_words(V, E) = 6 E + 4 V uint32 - the odd records at +0, the even records at +4 E, the
+ * ring at +4 E + 4 V.
+ *   ODD RECORD e at +4 e: {lo, hi, o0, o1}.  o0 is the corner of face f0 opposite the edge: indices[3 f0 + (k + 2) % 3] for the lowest k
+ *   whose half-edge joins lo and hi; o1 the same for f1.  When f1 is none, or f1 == f0, both are NONE (the boundary rule).  A "no edge"
+ *   record gives four NONE words.  INCONSISTENT records - lo >= hi, hi >= V, f0 or (where not none) f1 >= F, a face that does not hold
+ *   the pair or that names a vertex >= V - are TRGL_E_INVALID with host memory (nothing is written) and "no edge" with device memory.
+ *   EVEN RECORD v at +4 E + 4 v: {begin, count, b0, b1}.  count: the number of odd records that are edges with v as an endpoint.  begin:
+ *   the position in the ring of the first of them - the sum of the counts of all lower vertices -, or 0 when count == 0.  When none of
+ *   v's edges is a boundary edge (o0 == NONE), (b0, b1) = (NONE, NONE): the interior rule.  When exactly two are, b0 and b1 are their
+ *   other endpoints in ring order: the boundary rule.  For any other number (b0, b1) = (v, v): a corner, which is copied.
+ *   RING, 2 E words: for each vertex the other endpoints of its edges in ascending edge number - which is ascending neighbour number -,
+ *   vertex after vertex; the words behind the last used one are NONE.
+ *
+ * VERTICES (trgl_subdiv_vertices).  trgl_subdiv_params: vertex_stride >= 1 doubles per record; mode TRGL_SUBDIV_LINEAR or
+ * TRGL_SUBDIV_LOOP; smooth 0 .. vertex_stride: with LOOP the first `smooth` doubles of a record get the Loop weights and the rest the
+ * linear rule (with LINEAR smooth is ignored); reserved32 and reserved must be 0.  stencils, n_edges: the table and the E it was made
+ * with.  vertices_out: V + E records, record r of refined vertex r.
+ *   ARITHMETIC.  fp64, each operation rounded, no contraction or reassociation.  A computed double that is a NaN is stored as
+ *   0x7FF8000000000000 (the rule of the skin stage); a copied double keeps its 64 bits.  Per double x of a record:
+ *   MIDPOINT - LINEAR, LOOP doubles at or behind `smooth`, and LOOP odd vertices whose o0 and o1 are NONE: 0.5 * (x_lo + x_hi).
+ *   LOOP ODD, INTERIOR: s = x_lo + x_hi; t = x_o0 + x_o1; out = 0.375 * s + 0.125 * t - the two products rounded, then added.
+ *   LOOP EVEN, INTERIOR: S from +0.0 plus x of each ring entry in ring order; beta = 0.1875 when count <= 3, else
+ *   3.0 / (8.0 * (double)count) (Warren's weights, IEEE division); a = 1.0 - (double)count * beta; out = a * x_v + beta * S, the two
+ *   products rounded, then added.  count == 0: the vertex is copied.
+ *   LOOP EVEN, BOUNDARY: out = 0.75 * x_v + 0.125 * (x_b0 + x_b1).
+ *   A corner is copied.  In LINEAR, and for doubles at or behind `smooth`, every even vertex is copied.
+ *   The record of a "no edge" stencil (four NONE words) is all +0.0.
+ *   A STENCIL WORD THAT NAMES NO VERTEX - lo or hi >= V; o0 and o1 neither both NONE nor both < V; begin + count > 2 E; b0 and b1
+ *   neither both NONE nor both < V; a ring entry >= V of a vertex under the interior rule - is TRGL_E_INVALID in host memory (nothing is
+ *   written, whatever the mode).  In device memory that record is all +0.0 for an odd vertex and copied for an even one, and the word
+ *   is never used as an address.
+ *   NORMALS are not part of the rule: use smooth = 3 and trgl_mesh_normals on the output - or smooth six doubles and accept
+ *   unnormalised directions.
+ *   A SECOND LEVEL is trgl_mesh_edges plus trgl_subdiv_topology on the refined mesh (V + E vertices, 4 F faces).  Passing capacities
+ *   instead of counts keeps a chain of levels free of waits, at the price of unreferenced zero records.
+ *
+ * trgl_draw_subdivided: trgl_subdiv_vertices into a buffer the context owns until the flush is done (the rule of trgl_draw_skinned),
+ * then trgl_draw_indexed_vs of that buffer - V + E vertices of vertex_stride doubles - with refined_indices, n_refined_faces and colors;
+ * or, with vs == -1, trgl_draw_indexed of it (colors must then be NULL).  Frame bytes, depths and every counter equal those of the two
+ * calls made by hand.  No wait.  Errors: those of the two calls.
+ *
+ * MEMORY AND ORDER.  One mem_kind covers every array of a call.  Host memory: plain C++, ctx may be NULL, no GPU is touched, complete
+ * on return.  Device memory: doubles 8-byte aligned, every uint32 array 4 - nothing wider is assumed -; the bytes never depend on the
+ * alignment, and nothing behind the stated sizes is written.  The kernels are queued on the context's stream in order with the draws:
+ * no call of this section ever waits, nothing is flushed; they complete a begun flush, as trgl_clip_stage does.  Device inputs are
+ * read when the kernels run, not at the flush.  Outputs may not overlap inputs or each other.
+ * DEVICE PATH.  Topology: a kernel for the odd stencils, a stable radix sort of two (vertex, entry) pairs per record over the bits of
+ * n_vertices - after which a vertex's entries lie in ascending edge number at `begin` -, a ring, an even-record and an index kernel;
+ * scratch belongs to the context and grows on demand.  Vertices: one kernel, any vertex_stride.  No atomic decides a position or a sum.
+ * ERRORS.  TRGL_E_INVALID: a bad mem_kind, TRGL_MEM_DEVICE without a context, params NULL or a field outside the ranges above,
+ * n_vertices above 2^32 - 1, n_edges above 3 * n_faces (topology), n_vertices + n_edges above 2^32 - 1, a null or misaligned array, an
+ * output that overlaps an input or the other output, a host entry out of range as listed above.  TRGL_E_UNSUPPORTED: 3 * n_faces above
+ * 2^31 - 1; with device memory so many doubles that the vertex call would need 2^31 blocks or more.  n_faces == 0 or n_vertices == 0:
+ * TRGL_OK once the scalars are checked, and no array is read or written. */
+#define TRGL_SUBDIV_LINEAR 0u
+#define TRGL_SUBDIV_LOOP   1u
+typedef struct trgl_subdiv_params {
+    int32_t  vertex_stride;   /* doubles per vertex record, >= 1 */
+    int32_t  smooth;          /* LOOP: the first `smooth` doubles of a record get the Loop weights, 0 .. vertex_stride; the rest the linear rule */
+    uint32_t mode;            /* TRGL_SUBDIV_LINEAR (smooth is ignored) or TRGL_SUBDIV_LOOP */
+    uint32_t reserved32;      /* must be 0 */
+    uint64_t reserved;        /* must be 0 */
+} trgl_subdiv_params;
+uint64_t trgl_subdiv_stencil_words(uint64_t n_vertices, uint64_t n_edges);   /* 6 * n_edges + 4 * n_vertices */
+int trgl_subdiv_topology(trgl_ctx* ctx, const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices,
+                         const uint32_t* edges, uint64_t n_edges, int mem_kind,
+                         uint32_t* indices_out /* 12 * n_faces */, uint32_t* stencils_out /* trgl_subdiv_stencil_words() */);
+int trgl_subdiv_vertices(trgl_ctx* ctx, const trgl_subdiv_params* params, const double* vertices, uint64_t n_vertices,
+                         const uint32_t* stencils, uint64_t n_edges, int mem_kind,
+                         double* vertices_out /* (n_vertices + n_edges) * vertex_stride */);
+int trgl_draw_subdivided(trgl_ctx* ctx, int vs, int shader_kind, const trgl_uniforms* uniforms, const double projection[16],
+                         const trgl_subdiv_params* params, const double* vertices, uint64_t n_vertices,
+                         const uint32_t* stencils, uint64_t n_edges, const uint32_t* refined_indices, uint64_t n_refined_faces,
+                         const uint32_t* colors, int mem_kind);
+
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 
 /* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and
@@ -895,7 +995,7 @@ int trgl_flush(trgl_ctx* ctx);
  * flush first, with two exceptions.  The five calls that only queue work over caller-owned device arrays and flush
  * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths, trgl_depth_order and trgl_triangle_depths with
  * TRGL_MEM_DEVICE - leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those five,
- * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_edges, trgl_edge_select, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
+ * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_edges, trgl_edge_select, trgl_subdiv_topology, trgl_subdiv_vertices, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
  * computes on the host and returns without touching the context's queue.  A call refused for its arguments or for the
  * context's state may return before it completes anything.
  * bench.py: the RCCL gather of the previous frame's strips runs under the next frame's first half. */

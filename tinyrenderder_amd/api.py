@@ -45,6 +45,8 @@ CENTROID, NEAREST, FARTHEST = TRI_DEPTH_CENTROID, TRI_DEPTH_NEAREST, TRI_DEPTH_F
 SKIN_NORMAL, SKIN_TANGENT, SKIN_BITANGENT = 1, 2, 4     # TRGL_SKIN_*: the directions of a vertex record that trgl_skin_stage transforms
 EDGE_ANY, EDGE_BOUNDARY, EDGE_SILHOUETTE, EDGE_CREASE = 1, 2, 4, 8     # TRGL_EDGE_*: the class bits of an edge's code byte
 EDGE_NONE = 0xFFFFFFFF        # every word of a "no edge" record, f1 of a boundary edge, both words of a "no edge" segment
+SUBDIV_LINEAR, SUBDIV_LOOP = 0, 1   # TRGL_SUBDIV_*: the modes of subdiv_vertices
+SUBDIV_BLOCK, SUBDIV_ITEMS = 256, 4   # lanes per block of the subdivision kernels and doubles per lane of the vertex kernel (csrc/launch.h)
 EDGE_BLOCK = 256              # records per block of the edge kernels (csrc/launch.h); their scan has the levels of INST_SCAN_CHUNK
 SPRITE_VIEW, SPRITE_SCREEN = 0, 1     # TRGL_SPRITE_*: a sprite's size in eye-space units, or in units of the caller's scale[]
 FRUSTUM_SET, FRUSTUM_MERGE = 0, 1     # TRGL_FRUSTUM_*: the mode of trgl_frustum_boxes
@@ -78,6 +80,7 @@ SYMBOLS = [
     "trgl_sprite_stage", "trgl_draw_sprites", "trgl_line_stage", "trgl_draw_lines",
     "trgl_skin_stage", "trgl_pose_palette", "trgl_draw_skinned",
     "trgl_mesh_edges", "trgl_edge_select", "trgl_draw_outline",
+    "trgl_subdiv_stencil_words", "trgl_subdiv_topology", "trgl_subdiv_vertices", "trgl_draw_subdivided",
     "trgl_mip_layout", "trgl_image_mipmaps", "trgl_texture_mipmaps", "trgl_selftest_sampler_lod", "trgl_image_sample", "trgl_lod_stage", "trgl_selftest_mip_lod",
 ]
 MAX_MIP_LEVELS = 16
@@ -219,6 +222,8 @@ def load_library(path: str = None):
         L.trgl_debug_radix_blocks.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(L, "trgl_debug_edge_sort"):
         L.trgl_debug_edge_sort.argtypes = [vp, C.c_uint64, C.c_uint64]
+    if hasattr(L, "trgl_debug_subdiv_sort"):
+        L.trgl_debug_subdiv_sort.argtypes = [vp, C.c_uint64, C.c_uint64]
     L.trgl_selftest_division.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
     L.trgl_selftest_sampler.argtypes = [vp, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.trgl_draw_indexed.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
@@ -316,6 +321,12 @@ def load_library(path: str = None):
                                    C.c_void_p, C.c_void_p, C.c_void_p, u64p]
     L.trgl_draw_outline.argtypes = [vp, C.c_int, C.POINTER(Uniforms), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p,
                                     C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
+    L.trgl_subdiv_stencil_words.argtypes = [C.c_uint64, C.c_uint64]
+    L.trgl_subdiv_stencil_words.restype = C.c_uint64
+    L.trgl_subdiv_topology.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+    L.trgl_subdiv_vertices.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+    L.trgl_draw_subdivided.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("trgl_last_error",):
@@ -1065,6 +1076,92 @@ def edge_select(params, vertices, indices, edges, n_edges=None):
     return out[0], out[1], out[2], n
 
 
+class SubdivParams(C.Structure):
+    """trgl_subdiv_params"""
+    _fields_ = [("vertex_stride", C.c_int32), ("smooth", C.c_int32), ("mode", C.c_uint32), ("reserved32", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+def make_subdiv_params(vertex_stride, mode=SUBDIV_LOOP, smooth=3):
+    """trgl_subdiv_params: records of vertex_stride doubles; mode SUBDIV_LOOP - the first `smooth` doubles of a record get the Loop
+    weights, the rest midpoints and copies - or SUBDIV_LINEAR (midpoints and copies throughout; smooth is ignored)."""
+    return SubdivParams(int(vertex_stride), int(smooth), int(mode), 0, 0)
+
+
+def subdiv_stencil_words(n_vertices, n_edges):
+    """trgl_subdiv_stencil_words: 6 * n_edges + 4 * n_vertices, the uint32 words of a stencil array"""
+    return 6 * int(n_edges) + 4 * int(n_vertices)
+
+
+def _subdiv_topology(L, handle, indices, n_vertices, edges, n_edges, device, out):
+    """Returns (arrays to keep alive, refined indices [4 n_faces, 3], stencils [subdiv_stencil_words]); out: the two, or None."""
+    indices = _words32(indices, device, "indices", 3)
+    edges = _words32(edges, device, "edges", 4)
+    nf = int(indices.numel() if device else indices.size) // 3
+    n = int(edges.numel() if device else edges.size) // 4 if n_edges is None else int(n_edges)
+    words = subdiv_stencil_words(n_vertices, n)
+    if out is None:
+        if device:
+            import torch
+            out = (torch.empty((4 * nf, 3), dtype=torch.int32, device=indices.device), torch.empty(words, dtype=torch.int32, device=indices.device))
+        else:
+            out = (np.empty((4 * nf, 3), np.uint32), np.empty(words, np.uint32))
+    p = _device_ptr if device else _ptr
+    rc = L.trgl_subdiv_topology(handle, p(indices) if nf else None, nf, int(n_vertices), p(edges) if n else None, n,
+                                MEM_DEVICE if device else MEM_HOST, p(out[0]) if nf else None, p(out[1]) if words else None)
+    if rc != 0:
+        raise TrglError(f"trgl_subdiv_topology failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (indices, edges), out[0], out[1]
+
+
+def _subdiv_inputs(vertices, stencils, n_edges, device):
+    """(vertices [n, stride], stencils, n_edges): n_edges from the stencil array's size when not given"""
+    if device:
+        _device_f64(vertices, 2, "vertices")
+    else:
+        vertices = np.ascontiguousarray(vertices, np.float64)
+        if vertices.ndim != 2:
+            raise ValueError("vertices must have 2 dimensions [n, stride]")
+    stencils = _words32(stencils, device, "stencils")
+    if n_edges is None:
+        words = int(stencils.numel() if device else stencils.size) - 4 * int(vertices.shape[0])
+        if words < 0 or words % 6:
+            raise ValueError("stencils must hold 6 * n_edges + 4 * n_vertices words")
+        n_edges = words // 6
+    return vertices, stencils, int(n_edges)
+
+
+def _subdiv_vertices(L, handle, params, vertices, stencils, n_edges, device, out):
+    """Returns (arrays to keep alive, refined vertices [n_vertices + n_edges, stride])."""
+    vertices, stencils, n_edges = _subdiv_inputs(vertices, stencils, n_edges, device)
+    nv, stride = int(vertices.shape[0]), int(vertices.shape[1])
+    if out is None:
+        if device:
+            import torch
+            out = torch.empty((nv + n_edges, stride), dtype=torch.float64, device=vertices.device)
+        else:
+            out = np.empty((nv + n_edges, stride), np.float64)
+    p = _device_ptr if device else _ptr
+    rc = L.trgl_subdiv_vertices(handle, C.byref(params), p(vertices), nv, p(stencils), n_edges, MEM_DEVICE if device else MEM_HOST, p(out))
+    if rc != 0:
+        raise TrglError(f"trgl_subdiv_vertices failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (vertices, stencils), out
+
+
+def subdiv_topology(indices, n_vertices, edges, n_edges=None):
+    """trgl_subdiv_topology for host arrays without a context: from the faces indices [n_faces, 3] and the records mesh_edges made for
+    them - n_edges the count, or None for the whole capacity - the refined faces [4 n_faces, 3] over the vertices 0 .. n_vertices - 1
+    (even) and n_vertices + e (odd, one per record), and the stencil array subdiv_vertices takes.  Needs no GPU."""
+    _, refined, stencils = _subdiv_topology(load_library(), None, indices, n_vertices, edges, n_edges, False, None)
+    return refined, stencils
+
+
+def subdiv_vertices(params, vertices, stencils, n_edges=None):
+    """trgl_subdiv_vertices for host arrays without a context: the refined vertices [n_vertices + n_edges, stride] of vertices
+    [n_vertices, stride] under params (make_subdiv_params) and the stencils of subdiv_topology.  Normals are not part of the rule:
+    smooth = 3 and mesh_normals on the result.  Needs no GPU."""
+    return _subdiv_vertices(load_library(), None, params, vertices, stencils, n_edges, False, None)[1]
+
+
 class SkinParams(C.Structure):
     """trgl_skin_params"""
     _fields_ = [("vertex_stride", C.c_int32), ("n_influences", C.c_int32), ("n_joints", C.c_uint32), ("flags", C.c_uint32),
@@ -1797,6 +1894,40 @@ class Context:
         self._chk(self.L.trgl_draw_outline(self.h, kind, None if uniforms is None else C.byref(uniforms), C.byref(line_params),
                                            C.byref(edge_params), p(vertices), int(vertices.shape[1]), int(vertices.shape[0]), p(indices), nf,
                                            p(edges), n, MEM_DEVICE if device else MEM_HOST))
+
+    def subdiv_topology(self, indices, n_vertices, edges, n_edges=None, device=False, out=None):
+        """trgl_subdiv_topology (see the module's subdiv_topology).  device=True: indices and edges are 32-bit device tensors - edges as
+        mesh_edges(device=True) left them; n_edges=None passes the capacity, so no count has to visit the host -, out = (refined indices
+        [4 n_faces, 3], stencils [subdiv_stencil_words]) device tensors (allocated with torch when None); queued on the context's
+        stream without waiting.  Returns (refined indices, stencils)."""
+        keep, refined, stencils = _subdiv_topology(self.L, self.h, indices, n_vertices, edges, n_edges, device, out)
+        if device:
+            self._keep.append((keep, refined, stencils))
+        return refined, stencils
+
+    def subdiv_vertices(self, params, vertices, stencils, n_edges=None, device=False, out=None):
+        """trgl_subdiv_vertices (see the module's subdiv_vertices).  device=True: vertices [n, stride] f64 - one pose of skin_stage's
+        output, say - and stencils are device tensors, out [n + n_edges, stride] a device tensor (allocated with torch when None); one
+        kernel queued on the context's stream without waiting.  n_edges: the E the stencils were made with (None: from their size)."""
+        keep, out = _subdiv_vertices(self.L, self.h, params, vertices, stencils, n_edges, device, out)
+        if device:
+            self._keep.append((keep, out))
+        return out
+
+    def draw_subdivided(self, kind, uniforms, projection, params, vertices, stencils, refined_indices, n_edges=None, device=False,
+                        vertex_shader=None, colors=None):
+        """trgl_draw_subdivided: subdiv_vertices into a buffer of the context's, then draw_indexed of it with the refined indices
+        (vertex_shader= and colors= - one per refined face - as there).  device=True: every array is a device tensor; no wait."""
+        pj = np.ascontiguousarray(projection, np.float64).reshape(16)
+        vertices, stencils, n_edges = _subdiv_inputs(vertices, stencils, n_edges, device)
+        _, refined_indices, colors, ptrs = self._mesh_ptrs(vertices, refined_indices, colors, device)
+        p = _device_ptr if device else _ptr
+        if device:
+            self._keep.append((vertices, stencils, refined_indices, colors))
+        self._chk(self.L.trgl_draw_subdivided(self.h, -1 if vertex_shader is None else int(vertex_shader), kind,
+                                              None if uniforms is None else C.byref(uniforms), _dp(pj), C.byref(params), p(vertices),
+                                              int(vertices.shape[0]), p(stencils), n_edges, ptrs[1], int(refined_indices.shape[0]), ptrs[2],
+                                              MEM_DEVICE if device else MEM_HOST))
 
     def skin_stage(self, vertices, joints, weights, palette, flags=0, device=False, out=None):
         """trgl_skin_stage (see the module's skin_stage).  Host arrays: numpy, no GPU work.  device=True: vertices [n, stride] f64,

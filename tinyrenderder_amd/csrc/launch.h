@@ -1,7 +1,7 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
 // kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip,
 // kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_skin.hip,
-// kernels_edge.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
+// kernels_edge.hip, kernels_subdiv.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
 // trgl_stage_rows.cpp (the stages in front of a draw) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -306,6 +306,27 @@ struct EdgeSelectArgs {
 };
 size_t edge_select_scratch_bytes(uint32_t n_edges);
 hipError_t launch_edge_select(hipStream_t s, const EdgeSelectArgs& a, void* scratch, const unsigned long long** total);
+
+// Mesh subdivision (kernels_subdiv.hip; written down under "mesh subdivision" in include/trgl.h, the rules are subdiv_core.h's).
+// launch_subdiv_topology: 0 < n_faces, 3 * n_faces < 2^31, 0 < n_vertices, n_edges <= 3 * n_faces (0: no record), n_vertices + n_edges
+// < 2^32; every array 4-byte aligned, written 16 bytes at a time where 16-byte aligned.  scratch: subdiv_topology_scratch_bytes() bytes,
+// 256-byte aligned.  A stencil kernel, the sort, a ring, an even-record and an index kernel, in order on `s`.
+// launch_subdiv_vertices: one launch of SUBDIV_BLOCK lanes a block, SUBDIV_ITEMS doubles of the output per lane; vertices and out 8-byte
+// aligned, stencils 4; (n_vertices + n_edges) * stride below 2^31 * SUBDIV_BLOCK * SUBDIV_ITEMS.  smooth: 0 for the linear mode.  The
+// struct travels as the kernel's argument (step_q and step_r are filled in by the launch).
+constexpr int SUBDIV_BLOCK = 256;
+constexpr int SUBDIV_ITEMS = 4;
+hipError_t subdiv_topology_scratch_bytes(uint64_t n_edges, uint64_t n_vertices, size_t* bytes);
+hipError_t launch_subdiv_topology(hipStream_t s, const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, const uint32_t* edges,
+                                  uint64_t n_edges, void* scratch, size_t scratch_bytes, uint32_t* indices_out, uint32_t* stencils_out);
+// the sort of launch_subdiv_topology alone, over the entries that call left in the same scratch (a measurement's floor: profiles/subdiv_probe.py)
+hipError_t launch_subdiv_topology_sort(hipStream_t s, uint64_t n_edges, uint64_t n_vertices, void* scratch, size_t scratch_bytes);
+struct SubdivVertexArgs {
+    const double* vertices; const uint32_t* stencils; double* out;
+    uint64_t n_vertices, n_edges;
+    uint32_t stride, smooth, step_q, step_r;
+};
+hipError_t launch_subdiv_vertices(hipStream_t s, SubdivVertexArgs a);
 
 // World boxes of instances and frustum codes of boxes (kernels_scene.hip; both are written down at trgl_instance_boxes /
 // trgl_frustum_boxes in include/trgl.h, the arithmetic is scene_core.h's).  One thread per instance or box, 0 < n < 2^31; doubles 8-byte

@@ -100,6 +100,8 @@ struct trgl_ctx {
     // trgl_mesh_edges: the 8-byte count, keys and half-edge numbers with their sorted copies, the scan's words, the sort's own space;
     // trgl_edge_select with compaction: the 8-byte count, a byte per record, the scan's words.  Grows on demand
     DevBuf<uint8_t> edge_scratch;
+    // trgl_subdiv_topology: two sort entries per edge record with their sorted copies and the sort's own space.  Grows on demand
+    DevBuf<uint8_t> subdiv_scratch;
     DevBuf<uint8_t> order_scratch;      // trgl_depth_order: the keys, their sorted copy, the numbers 0 .. n-1, the sort's own space; grows on demand
     DevBuf<uint8_t> pp_out;            // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
@@ -218,6 +220,12 @@ void host_pose_palette(const int32_t* parents, const double* inverse_bind, uint3
 uint64_t host_mesh_edges(const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, uint32_t* edges_out);
 bool host_edge_select(const trgl_edge_params& P, const double* vertices, int stride, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
                       const uint32_t* edges, uint64_t n_edges, uint8_t* codes_out, uint32_t* segments_out, uint32_t* colors_out, uint64_t* n_selected);
+// trgl_subdiv_topology and trgl_subdiv_vertices over host arrays: false, and nothing written, for an entry the header refuses in host
+// memory (an index, a record or a stencil word out of range, a pair that no record names).  The first may throw std::bad_alloc.
+bool host_subdiv_topology(const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, const uint32_t* edges, uint64_t n_edges,
+                          uint32_t* indices_out, uint32_t* stencils_out);
+bool host_subdiv_vertices(const trgl_subdiv_params& P, const double* vertices, uint64_t n_vertices, const uint32_t* stencils, uint64_t n_edges,
+                          double* out);
 // trgl_instance_boxes and trgl_frustum_boxes over host arrays (local_stride 0: one local box for every instance)
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out);
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);

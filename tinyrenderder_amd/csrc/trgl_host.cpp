@@ -21,6 +21,7 @@
 #include "sprite_core.h"
 #include "skin_core.h"
 #include "edge_core.h"
+#include "subdiv_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -399,6 +400,102 @@ bool host_edge_select(const trgl_edge_params& P, const double* vertices, int str
             if (colors_out) colors_out[at] = 0u;
         }
     if (n_selected) *n_selected = slot;
+    return true;
+}
+
+// ---- mesh subdivision in host memory (include/trgl.h, trgl_subdiv_topology / trgl_subdiv_vertices; the rules are subdiv_core.h's) ----
+// false, and nothing written, for an index or a record out of range, an inconsistent record or a pair that no record names
+bool host_subdiv_topology(const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, const uint32_t* edges, uint64_t n_edges,
+                          uint32_t* indices_out, uint32_t* stencils_out) {
+    const uint64_t E = n_edges, V = n_vertices;
+    std::vector<uint32_t> st((size_t)(6 * E + 4 * V), SUBDIV_NONE), refined((size_t)(12 * n_faces), 0u);
+    uint32_t* odd = st.data();
+    uint32_t* even = st.data() + 4 * E;
+    uint32_t* ring = even + 4 * V;
+    for (uint64_t k = 0; k < 3 * n_faces; ++k) if (indices[k] >= V) return false;
+    std::vector<uint32_t> count((size_t)V, 0u), begin((size_t)V, 0u), fill((size_t)V, 0u);
+    for (uint64_t e = 0; e < E; ++e) {
+        const int kind = subdiv_odd_stencil(indices, n_faces, V, edges + 4 * e, odd + 4 * e);
+        if (kind == SUBDIV_REC_BAD) return false;
+        if (kind == SUBDIV_REC_EDGE) { ++count[odd[4 * e]]; ++count[odd[4 * e + 1]]; }
+    }
+    uint32_t at = 0;
+    for (uint64_t v = 0; v < V; ++v) { begin[v] = count[v] ? at : 0u; at += count[v]; }
+    for (uint64_t e = 0; e < E; ++e) {      // ascending e: every vertex's entries in ascending edge number
+        const uint32_t lo = odd[4 * e], hi = odd[4 * e + 1];
+        if (lo == SUBDIV_NONE) continue;
+        ring[begin[lo] + fill[lo]++] = hi;
+        ring[begin[hi] + fill[hi]++] = lo;
+    }
+    // (which ring entry belongs to a boundary edge: the edges again, in the same order)
+    std::vector<uint32_t> nb((size_t)V, 0u), first((size_t)V, 0u), second((size_t)V, 0u);
+    for (uint64_t e = 0; e < E; ++e) {
+        const uint32_t ends[2] = { odd[4 * e], odd[4 * e + 1] };
+        if (ends[0] == SUBDIV_NONE || odd[4 * e + 2] != SUBDIV_NONE) continue;
+        for (int s = 0; s < 2; ++s) {
+            const uint32_t v = ends[s], other = ends[1 - s];
+            if (nb[v] == 0) first[v] = other; else if (nb[v] == 1) second[v] = other;
+            ++nb[v];
+        }
+    }
+    for (uint64_t v = 0; v < V; ++v) {
+        uint32_t* rec = even + 4 * v;
+        rec[0] = begin[v]; rec[1] = count[v];
+        subdiv_boundary_pair((uint32_t)v, nb[v], first[v], second[v], rec + 2, rec + 3);
+    }
+    for (uint64_t f = 0; f < n_faces; ++f) {
+        const uint32_t a = indices[3 * f], b = indices[3 * f + 1], c = indices[3 * f + 2];
+        if (a == b || b == c || c == a) continue;      // a half-edge that makes no edge: four faces (0, 0, 0)
+        const uint64_t ab = subdiv_find_edge(edges, E, a, b), bc = subdiv_find_edge(edges, E, b, c), ca = subdiv_find_edge(edges, E, c, a);
+        if (ab >= E || bc >= E || ca >= E || odd[4 * ab] == SUBDIV_NONE || odd[4 * bc] == SUBDIV_NONE || odd[4 * ca] == SUBDIV_NONE) return false;
+        const uint32_t m_ab = (uint32_t)(V + ab), m_bc = (uint32_t)(V + bc), m_ca = (uint32_t)(V + ca);
+        const uint32_t four[12] = { a, m_ab, m_ca, b, m_bc, m_ab, c, m_ca, m_bc, m_ab, m_bc, m_ca };
+        std::memcpy(refined.data() + 12 * f, four, sizeof(four));
+    }
+    if (!refined.empty()) std::memcpy(indices_out, refined.data(), refined.size() * sizeof(uint32_t));
+    if (!st.empty()) std::memcpy(stencils_out, st.data(), st.size() * sizeof(uint32_t));
+    return true;
+}
+
+// false, and nothing written, for a stencil word that names no vertex
+bool host_subdiv_vertices(const trgl_subdiv_params& P, const double* vertices, uint64_t n_vertices, const uint32_t* stencils, uint64_t n_edges,
+                          double* out) {
+    const uint64_t E = n_edges, V = n_vertices, S = (uint64_t)P.vertex_stride;
+    const uint64_t smooth = P.mode == TRGL_SUBDIV_LOOP ? (uint64_t)P.smooth : 0;
+    const uint32_t* odd = stencils;
+    const uint32_t* even = stencils + 4 * E;
+    const uint32_t* ring = even + 4 * V;
+    for (uint64_t e = 0; e < E; ++e) if (subdiv_odd_class(odd + 4 * e, V) == SUBDIV_ODD_BAD) return false;
+    for (uint64_t v = 0; v < V; ++v) {
+        const int kind = subdiv_even_class(even + 4 * v, (uint32_t)v, V, E);
+        if (kind == SUBDIV_EVEN_BAD) return false;
+        if (kind == SUBDIV_EVEN_RING)
+            for (uint64_t k = 0; k < even[4 * v + 1]; ++k) if (ring[even[4 * v] + k] >= V) return false;
+    }
+    for (uint64_t v = 0; v < V; ++v) {
+        const uint32_t* st = even + 4 * v;
+        const int kind = subdiv_even_class(st, (uint32_t)v, V, E);
+        const double* x = vertices + v * S;
+        double* o = out + v * S;
+        for (uint64_t d = 0; d < S; ++d) {
+            if (d >= smooth || kind == SUBDIV_EVEN_COPY) { o[d] = x[d]; continue; }
+            if (kind == SUBDIV_EVEN_EDGE) { o[d] = subdiv_even_boundary(x[d], vertices[st[2] * S + d], vertices[st[3] * S + d]); continue; }
+            double sum = 0.0;
+            for (uint64_t k = 0; k < st[1]; ++k) sum += vertices[ring[st[0] + k] * S + d];
+            o[d] = subdiv_even_interior(st[1], x[d], sum);
+        }
+    }
+    for (uint64_t e = 0; e < E; ++e) {
+        const uint32_t* st = odd + 4 * e;
+        const int kind = subdiv_odd_class(st, V);
+        double* o = out + (V + e) * S;
+        for (uint64_t d = 0; d < S; ++d) {
+            if (kind == SUBDIV_ODD_ZERO) { o[d] = 0.0; continue; }
+            const double xl = vertices[st[0] * S + d], xh = vertices[st[1] * S + d];
+            o[d] = (kind == SUBDIV_ODD_FULL && d < smooth) ? subdiv_odd_interior(xl, xh, vertices[st[2] * S + d], vertices[st[3] * S + d])
+                                                           : subdiv_midpoint(xl, xh);
+        }
+    }
     return true;
 }
 

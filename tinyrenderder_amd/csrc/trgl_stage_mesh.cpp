@@ -1,7 +1,7 @@
 // trgl_stage_mesh.cpp — the stages over an indexed mesh and the draws behind them: the vertex stage (trgl_draw_indexed,
 // trgl_draw_indexed_vs, trgl_vertex_stage), the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and
-// skeletal animation (trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned) and mesh edges (trgl_mesh_edges, trgl_edge_select,
-// trgl_draw_outline).
+// skeletal animation (trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned), mesh edges (trgl_mesh_edges, trgl_edge_select,
+// trgl_draw_outline) and mesh subdivision (trgl_subdiv_topology, trgl_subdiv_vertices, trgl_draw_subdivided).
 // The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <algorithm>
 #include <cstring>
@@ -9,6 +9,7 @@
 #include "trgl_stage.h"
 #include "skin_core.h"
 #include "edge_core.h"
+#include "subdiv_core.h"
 
 // The vertex stage of `vs` (-1: k_vertex_stage) over an indexed mesh in device memory, queued on the context's stream.  clip and
 // vary (unused when K = 0) are 16-byte aligned; u == nullptr: zeros, texture slots -1.
@@ -248,6 +249,45 @@ static int queue_edge_select(trgl_ctx* c, const trgl_edge_params& P, const EdgeA
     const unsigned long long* total = nullptr;
     HIPCHK(c, launch_edge_select(c->stream, k, c->edge_scratch.p, &total));
     if (total && count) HIPCHK(c, hipMemcpyAsync(count, total, sizeof(*count), hipMemcpyDeviceToHost, c->stream));
+    return TRGL_OK;
+}
+
+// ---- mesh subdivision (include/trgl.h: trgl_subdiv_topology, trgl_subdiv_vertices, trgl_draw_subdivided) ----
+// what the scalars of a vertex call must satisfy
+static int check_subdiv_params(trgl_ctx* c, const std::string& w, const trgl_subdiv_params* P, uint64_t n_vertices, uint64_t n_edges, int mem_kind) {
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    if (int r = check_mem(c, w, mem_kind)) return r;
+    if (P->vertex_stride < 1) return fail(c, TRGL_E_INVALID, w + "vertex_stride must be >= 1");
+    if (P->mode != TRGL_SUBDIV_LINEAR && P->mode != TRGL_SUBDIV_LOOP) return fail(c, TRGL_E_INVALID, w + "unknown mode");
+    if (P->mode == TRGL_SUBDIV_LOOP && (P->smooth < 0 || P->smooth > P->vertex_stride)) return fail(c, TRGL_E_INVALID, w + "smooth must be 0 .. vertex_stride");
+    if (P->reserved32 || P->reserved) return fail(c, TRGL_E_INVALID, w + "reserved must be 0");
+    if (n_vertices > 0xffffffffull) return fail(c, TRGL_E_INVALID, w + "n_vertices above 2^32 - 1");
+    if (n_edges > 0xffffffffull - n_vertices) return fail(c, TRGL_E_INVALID, w + "n_vertices + n_edges above 2^32 - 1");
+    return TRGL_OK;
+}
+
+// ... and its arrays (n_vertices > 0): present, aligned, the output apart from the inputs
+static int check_subdiv_arrays(trgl_ctx* c, const std::string& w, const trgl_subdiv_params& P, const double* vertices, uint64_t n_vertices,
+                               const uint32_t* stencils, uint64_t n_edges, const double* out) {
+    if (!vertices || !stencils || !out) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (!aligned({ { vertices, 8 }, { out, 8 }, { stencils, 4 } }))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 4 for stencils)");
+    const uint64_t rec = (uint64_t)P.vertex_stride * 8;
+    if (arrays_overlap(vertices, n_vertices * rec, out, (n_vertices + n_edges) * rec) ||
+        arrays_overlap(stencils, trgl_subdiv_stencil_words(n_vertices, n_edges) * 4, out, (n_vertices + n_edges) * rec))
+        return fail(c, TRGL_E_INVALID, w + "the output overlaps an input");
+    return TRGL_OK;
+}
+
+// the vertex kernel over device arrays (checked, n_vertices > 0), queued on the context's stream
+static int queue_subdiv_vertices(trgl_ctx* c, const std::string& w, const trgl_subdiv_params& P, const double* vertices, uint64_t n_vertices,
+                                 const uint32_t* stencils, uint64_t n_edges, double* out) {
+    if (!mul_fits(n_vertices + n_edges, (uint64_t)P.vertex_stride, 0x7fffffffull * SUBDIV_BLOCK * SUBDIV_ITEMS))
+        return fail(c, TRGL_E_UNSUPPORTED, w + "2^31 or more blocks in one call");
+    SubdivVertexArgs a; std::memset(&a, 0, sizeof(a));
+    a.vertices = vertices; a.stencils = stencils; a.out = out; a.n_vertices = n_vertices; a.n_edges = n_edges;
+    a.stride = (uint32_t)P.vertex_stride; a.smooth = P.mode == TRGL_SUBDIV_LOOP ? (uint32_t)P.smooth : 0u;
+    HIPCHK(c, launch_subdiv_vertices(c->stream, a));
     return TRGL_OK;
 }
 
@@ -541,6 +581,100 @@ int trgl_draw_outline(trgl_ctx* c, int kind, const trgl_uniforms* u, const trgl_
         return TRGL_OK;
     }
     return trgl_draw_lines(c, kind, u, LP, vertices, stride, n_vertices, a.segments, a.colors, count, TRGL_MEM_DEVICE);
+}
+
+uint64_t trgl_subdiv_stencil_words(uint64_t n_vertices, uint64_t n_edges) { return 6 * n_edges + 4 * n_vertices; }
+
+int trgl_subdiv_topology(trgl_ctx* c, const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, const uint32_t* edges, uint64_t n_edges,
+                         int mem_kind, uint32_t* indices_out, uint32_t* stencils_out) {
+    const std::string w = "trgl_subdiv_topology: ";
+    int r = check_mem(c, w, mem_kind); if (r) return r;
+    if (n_vertices > 0xffffffffull) return fail(c, TRGL_E_INVALID, w + "n_vertices above 2^32 - 1");
+    if (n_faces > 0x7fffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, w + "3 * n_faces above 2^31 - 1");
+    if (n_edges > 3 * n_faces) return fail(c, TRGL_E_INVALID, w + "n_edges above 3 * n_faces");
+    if (n_edges > 0xffffffffull - n_vertices) return fail(c, TRGL_E_INVALID, w + "n_vertices + n_edges above 2^32 - 1");
+    if (n_faces == 0 || n_vertices == 0) return TRGL_OK;
+    if (!indices || (n_edges && !edges) || !indices_out || !stencils_out) return fail(c, TRGL_E_INVALID, w + "null array");
+    if (!aligned({ { indices, 4 }, { edges, 4 }, { indices_out, 4 }, { stencils_out, 4 } })) return fail(c, TRGL_E_INVALID, w + "arrays must be 4-byte aligned");
+    struct Range { const void* p; uint64_t bytes; };
+    const Range ins[2] = { { indices, n_faces * 12 }, { edges, n_edges * 16 } };
+    const Range outs[2] = { { indices_out, n_faces * 48 }, { stencils_out, trgl_subdiv_stencil_words(n_vertices, n_edges) * 4 } };
+    for (const Range& i : ins)
+        for (const Range& o : outs)
+            if (arrays_overlap(i.p, i.bytes, o.p, o.bytes)) return fail(c, TRGL_E_INVALID, w + "an output overlaps an input");
+    if (arrays_overlap(outs[0].p, outs[0].bytes, outs[1].p, outs[1].bytes)) return fail(c, TRGL_E_INVALID, w + "the two outputs overlap");
+    if (mem_kind == TRGL_MEM_HOST) return no_bad_alloc(c, w, [&] {
+        if (!host_subdiv_topology(indices, n_faces, n_vertices, edges, n_edges, indices_out, stencils_out))
+            return fail(c, TRGL_E_INVALID, w + "an index or a record out of range, an inconsistent record, or a pair that no record names");
+        return (int)TRGL_OK;
+    });
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    size_t bytes = 0;
+    HIPCHK(c, subdiv_topology_scratch_bytes(n_edges, n_vertices, &bytes));
+    if ((r = c->subdiv_scratch.grow(c, bytes))) return r;
+    HIPCHK(c, launch_subdiv_topology(c->stream, indices, n_faces, n_vertices, edges, n_edges, c->subdiv_scratch.p, c->subdiv_scratch.cap,
+                                     indices_out, stencils_out));
+    return TRGL_OK;
+}
+
+// Diagnostic, not part of include/trgl.h (profiles/subdiv_probe.py): the radix sort of the last trgl_subdiv_topology call with these
+// counts again, over the entries it left in the context's scratch - the floor that call is measured against.  Queued, no wait.
+int trgl_debug_subdiv_sort(trgl_ctx* c, uint64_t n_edges, uint64_t n_vertices) {
+    CHKCTX(c);
+    if (n_edges == 0 || n_edges > 0x7fffffffull || n_vertices == 0 || n_vertices > 0xffffffffull - n_edges)
+        return fail(c, TRGL_E_INVALID, "trgl_debug_subdiv_sort: bad counts");
+    size_t bytes = 0;
+    HIPCHK(c, subdiv_topology_scratch_bytes(n_edges, n_vertices, &bytes));
+    if (c->subdiv_scratch.cap < bytes) return fail(c, TRGL_E_STATE, "trgl_debug_subdiv_sort: no trgl_subdiv_topology call of this size came before");
+    HIPCHK(c, launch_subdiv_topology_sort(c->stream, n_edges, n_vertices, c->subdiv_scratch.p, c->subdiv_scratch.cap));
+    return TRGL_OK;
+}
+
+int trgl_subdiv_vertices(trgl_ctx* c, const trgl_subdiv_params* P, const double* vertices, uint64_t n_vertices, const uint32_t* stencils,
+                         uint64_t n_edges, int mem_kind, double* out) {
+    const std::string w = "trgl_subdiv_vertices: ";
+    int r = check_subdiv_params(c, w, P, n_vertices, n_edges, mem_kind); if (r) return r;
+    if (n_vertices == 0) return TRGL_OK;
+    if ((r = check_subdiv_arrays(c, w, *P, vertices, n_vertices, stencils, n_edges, out))) return r;
+    if (mem_kind == TRGL_MEM_HOST) {
+        if (!host_subdiv_vertices(*P, vertices, n_vertices, stencils, n_edges, out)) return fail(c, TRGL_E_INVALID, w + "a stencil word names no vertex");
+        return TRGL_OK;
+    }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    return queue_subdiv_vertices(c, w, *P, vertices, n_vertices, stencils, n_edges, out);
+}
+
+int trgl_draw_subdivided(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, const double projection[16], const trgl_subdiv_params* P,
+                         const double* vertices, uint64_t n_vertices, const uint32_t* stencils, uint64_t n_edges, const uint32_t* refined_indices,
+                         uint64_t n_refined_faces, const uint32_t* colors, int mem_kind) {
+    CHKCTX(c);
+    int r = end_pending_raster(c); if (r) return r;
+    const std::string w = "trgl_draw_subdivided: ";
+    if ((r = check_subdiv_params(c, w, P, n_vertices, n_edges, mem_kind))) return r;
+    if (vs == -1 && colors) return fail(c, TRGL_E_INVALID, w + "colors: only with a vertex shader");
+    const int stride = P->vertex_stride;
+    const uint64_t n = n_vertices + n_edges;
+    int K = TRGL_VARY_PHONG; bool go;
+    // (what the draw would refuse is refused before the vertex kernel is queued; `vertices` stands in for the refined array)
+    if (vs == -1) r = check_draw_indexed(c, kind, u, projection, vertices, stride, n, refined_indices, n_refined_faces, mem_kind, &go);
+    else r = check_draw_indexed_vs(c, vs, kind, u, projection, vertices, stride, n, refined_indices, n_refined_faces, mem_kind, &K, &go);
+    if (r || !go) return r;
+    if (n_vertices == 0) return fail(c, TRGL_E_INVALID, w + "faces without vertices");
+    if (mem_kind == TRGL_MEM_HOST) return no_bad_alloc(c, w, [&] {
+        std::vector<double> refined((size_t)n * (size_t)stride);
+        if (int e = check_subdiv_arrays(c, w, *P, vertices, n_vertices, stencils, n_edges, refined.data())) return e;
+        if (!host_subdiv_vertices(*P, vertices, n_vertices, stencils, n_edges, refined.data())) return fail(c, TRGL_E_INVALID, w + "a stencil word names no vertex");
+        return vs == -1 ? trgl_draw_indexed(c, kind, u, projection, refined.data(), stride, n, refined_indices, n_refined_faces, TRGL_MEM_HOST)
+                        : trgl_draw_indexed_vs(c, vs, kind, u, projection, refined.data(), stride, n, refined_indices, n_refined_faces, colors, TRGL_MEM_HOST);
+    });
+    StageHold hold(c);
+    double* refined = nullptr;
+    if ((r = CallMem(c, true).alloc((size_t)n * (size_t)stride, &refined))) return r;
+    if ((r = check_subdiv_arrays(c, w, *P, vertices, n_vertices, stencils, n_edges, refined))) return r;
+    if ((r = queue_subdiv_vertices(c, w, *P, vertices, n_vertices, stencils, n_edges, refined))) return r;
+    return draw_indexed_checked(c, vs, K, kind, u, projection, refined, stride, n, refined_indices, n_refined_faces, colors, TRGL_MEM_DEVICE);
 }
 
 }  // extern "C"

@@ -855,6 +855,62 @@ inline bool gl_draw_outline(const trgl_edge_params& params, double width, double
     return ok;
 }
 
+// Mesh subdivision (include/trgl.h, trgl_subdiv_topology / trgl_subdiv_vertices / trgl_draw_subdivided): one level of Loop or linear
+// refinement of an indexed mesh, on the host, no context needed.  Where Model keeps `vertices` (records of `stride` doubles) and
+// `indices`: gl_mesh_edges(indices) once, gl_subdiv_topology once - refined_indices replaces the index vector, 4 faces per face -, then
+// gl_subdiv_vertices per pose, whose output replaces the vertex vector: nvertices + edges.size() / 4 records of the same stride.
+// A second level is the same three calls on the refined mesh.  Normals are not part of the rule: smooth = 3 and the mesh-normal call.
+inline trgl_subdiv_params gl_subdiv_params(int vertex_stride, std::uint32_t mode = TRGL_SUBDIV_LOOP, int smooth = 3) {
+    trgl_subdiv_params p{};
+    p.vertex_stride = vertex_stride; p.smooth = smooth; p.mode = mode;
+    return p;
+}
+// `edges`: what gl_mesh_edges left for these indices.  A call that fails (gl_last_error()) leaves the vectors empty.
+inline bool gl_subdiv_topology(const unsigned int* indices, std::size_t nfaces, std::size_t nvertices, const std::vector<std::uint32_t>& edges,
+                               std::vector<unsigned int>& refined_indices, std::vector<std::uint32_t>& stencils) {
+    static_assert(sizeof(unsigned int) == sizeof(std::uint32_t), "indices are 32-bit");
+    const std::size_t n = edges.size() / 4;
+    refined_indices.assign(12 * nfaces, 0u); stencils.assign(std::size_t(trgl_subdiv_stencil_words(nvertices, n)), 0u);
+    const int rc = trgl_subdiv_topology(nullptr, reinterpret_cast<const std::uint32_t*>(indices), nfaces, nvertices, edges.data(), n, TRGL_MEM_HOST,
+                                        reinterpret_cast<std::uint32_t*>(refined_indices.data()), stencils.data());
+    if (rc != TRGL_OK) { refined_indices.clear(); stencils.clear(); return trgl_shim::fail("gl_subdiv_topology", rc, nullptr); }
+    return true;
+}
+// nedges: edges.size() / 4 of the gl_subdiv_topology call that made `stencils`
+inline bool gl_subdiv_vertices(const trgl_subdiv_params& params, const double* vertices, std::size_t nvertices, const std::vector<std::uint32_t>& stencils,
+                               std::size_t nedges, std::vector<double>& out) {
+    out.assign((nvertices + nedges) * std::size_t(params.vertex_stride > 0 ? params.vertex_stride : 0), 0.0);
+    const int rc = trgl_subdiv_vertices(nullptr, &params, vertices, nvertices, stencils.data(), nedges, TRGL_MEM_HOST, out.data());
+    if (rc != TRGL_OK) { out.clear(); return trgl_shim::fail("gl_subdiv_vertices", rc, nullptr); }
+    return true;
+}
+// gl_subdiv_vertices and gl_draw_indexed of its output with the refined indices in one call (trgl_draw_subdivided): the shader's
+// describe() is taken as gl_draw_indexed takes it.  A set clip plane is TRGL_E_UNSUPPORTED: this draw is not clipped.
+inline bool gl_draw_subdivided(const IShader& shader, const trgl_subdiv_params& params, const double* vertices, std::size_t nvertices,
+                               const std::vector<std::uint32_t>& stencils, std::size_t nedges, const unsigned int* refined_indices,
+                               std::size_t nrefined, TGAImage& framebuffer) {
+    using namespace trgl_shim;
+    State& s = state();
+    if (!bind(framebuffer)) return false;
+    bool ok = submit_batch();                                   // earlier rasterize() calls come first
+    trgl_shader_desc d;
+    if (!shader.describe(d)) {
+        std::fprintf(stderr, "trgl: gl_draw_subdivided(): needs a shader with a device descriptor\n");
+        std::abort();
+    }
+    if (s.clip_on) return fail("gl_draw_subdivided", TRGL_E_UNSUPPORTED, nullptr);
+    double vp[16], pj[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { vp[4 * r + c] = Viewport[r][c]; pj[4 * r + c] = Perspective[r][c]; }
+    const bool user_vs = d.vertex_kind >= 0;
+    const std::vector<std::uint32_t> colors(user_vs ? nrefined : 0, d.color);
+    ok = TRGL_SHIM_OK(trgl_set_viewport(s.ctx, vp)) &&
+         TRGL_SHIM_OK(trgl_draw_subdivided(s.ctx, user_vs ? d.vertex_kind : -1, d.kind, &d.uniforms, pj, &params, vertices, nvertices, stencils.data(),
+                                           nedges, reinterpret_cast<const std::uint32_t*>(refined_indices), nrefined,
+                                           user_vs ? colors.data() : nullptr, TRGL_MEM_HOST)) && ok;
+    s.zbuffer_stale_on_host = true;
+    return ok;
+}
+
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
 // write_tga_file(), main.cpp:743,773).  The depths follow on demand through the `zbuffer` proxy.
 // false: something submitted since the last gl_flush() failed (gl_last_error()); the pixels hold what could be drawn.
