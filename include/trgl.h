@@ -918,6 +918,65 @@ int trgl_draw_subdivided(trgl_ctx* ctx, int vs, int shader_kind, const trgl_unif
                          const uint32_t* stencils, uint64_t n_edges, const uint32_t* refined_indices, uint64_t n_refined_faces,
                          const uint32_t* colors, int mem_kind);
 
+/* ---- mesh welding: identical vertices joined, the index array every mesh stage above reads -------------------------------------------- */
+
+/* New work: the reference gets shared indices from Assimp (aiProcess_JoinIdenticalVertices, model.cpp:96), which is not part of this
+ * library; its comparison is not reproduced.  trgl_mesh_edges, trgl_edge_select, the subdivision calls and trgl_mesh_normals take two
+ * corners for one vertex only when they carry one index.  trgl_mesh_weld makes such indices: from a vertex array split along UV and
+ * normal seams (trgl_obj_load), or from a triangle soup, the array of distinct vertices and the map from old numbers to new ones.  With
+ * TRGL_MEM_DEVICE nothing visits the host.  NONE is 0xFFFFFFFF.
+ *
+ * KEY.  trgl_weld_params: vertex_stride >= 1 doubles per record; the key is the key_count >= 1 doubles from key_offset on, key_offset
+ * >= 0 and key_offset + key_count <= vertex_stride; cell; reserved32 and reserved must be 0.  Component a of vertex v is
+ * x = vertices[v * vertex_stride + key_offset + a].  cell == 0.0: the compared value is q = x.  cell > 0 (finite): q = floor(x / cell +
+ * 0.5) - fp64, an IEEE division, the sum rounded once, floor exact; no reciprocal, no contraction, no reassociation.
+ * IDENTICAL.  u and v are identical when q_u[a] == q_v[a] under IEEE == for every a: -0.0 equals +0.0, infinities of one sign are equal,
+ * and a key that holds a NaN equals nothing, not even itself (in cell mode q is a NaN for a NaN x, for inf / inf ... as IEEE gives it).
+ *   Cell mode is a GRID weld, not a distance weld: q names a cell of width `cell` centred on a multiple of it, and two values however
+ *   close on either side of a cell's border do not join.
+ * REPRESENTATIVE.  rep(v) is the lowest-numbered u identical to v; v itself when there is none (the NaN case).
+ * NUMBERING.  The representatives - the v with rep(v) == v - are numbered 0 .. n_unique - 1 in ascending old number, so a mesh without
+ * duplicates maps to itself.  remap_out[v] (n_vertices uint32) is the new number of rep(v).
+ * OUTPUTS, each may be NULL.
+ *   firsts_out, n_vertices uint32: firsts_out[j], j < n_unique, is the old number of new vertex j; every word behind that is NONE.  It
+ *     gathers what lives beside the records - the joints and weights of trgl_skin_stage, colours.
+ *   vertices_out, n_vertices records: record j < n_unique is the whole record of vertex firsts_out[j], copied bit for bit, the key's own
+ *     bytes included (-0.0 stays -0.0); every byte of the records behind n_unique is 0.
+ *   indices_out, 3 * n_faces uint32: indices_out[i] = remap[indices[i]].  It needs `indices`; indices == NULL is allowed without it (for
+ *     a soup remap_out IS the index array).
+ *   Nothing behind these capacities is written.  Faces are neither removed nor reordered: a face that welding made degenerate stays
+ *   (trgl_mesh_edges makes no edge from a == b, rasterize() drops zero area).
+ * AN INDEX >= n_vertices.  Host memory: TRGL_E_INVALID, nothing is written.  Device memory: indices_out[i] = NONE - what
+ * trgl_mesh_edges takes for "no vertex" -, and the entry is never used as an address.
+ * COUNT.  n_unique is a host pointer.  NULL: no wait.  Non-NULL with device memory: the call waits for the context's stream once, for
+ * the 8-byte count (the rule of trgl_mesh_edges).  Because of the fills a later call may take the capacity n_vertices instead: a
+ * load-time chain - weld, edges, topology - queues without a number coming back.
+ * MEMORY AND ORDER.  One mem_kind covers every array of a call.  Host memory: plain C++, ctx may be NULL, no GPU is touched, complete
+ * on return.  Device memory: doubles 8-byte aligned, every uint32 array 4 - nothing wider is assumed -; the bytes never depend on the
+ * alignment.  The kernels are queued on the context's stream in order with the draws: nothing is flushed; they complete a begun flush,
+ * as trgl_clip_stage does.  Device inputs are read when the kernels run.
+ * DEVICE PATH.  A 64-bit hash of the key per vertex (zeros hashed as +0.0, q in cell mode), a stable radix sort of (hash, vertex) pairs,
+ * a kernel in which every entry compares its key with the head of its run of equal hashes - and, on a collision, walks the run -, a
+ * scan in two levels over the representatives in old order, and kernels that write the outputs and the fills.  No atomic decides a
+ * number or a position.  Scratch belongs to the context and grows on demand.
+ * ERRORS.  TRGL_E_INVALID: a bad mem_kind, TRGL_MEM_DEVICE without a context, params NULL, a reserved field not 0, vertex_stride < 1,
+ * key_offset < 0, key_count < 1, key_offset + key_count > vertex_stride, cell negative, NaN or infinite, a null `vertices` with
+ * n_vertices > 0, indices_out without indices, a misaligned array, an output that overlaps an input or another output, n_faces > 0
+ * with n_vertices == 0, a host index out of range.  TRGL_E_UNSUPPORTED: n_vertices or 3 * n_faces above 2^31 - 1, or n_vertices *
+ * vertex_stride * 8 bytes that do not fit 2^60.  n_vertices == 0 (and n_faces == 0): TRGL_OK once the scalars are checked,
+ * *n_unique = 0, no array is touched. */
+typedef struct trgl_weld_params {
+    int32_t  vertex_stride;   /* doubles per record, >= 1 */
+    int32_t  key_offset;      /* first double of the key within a record */
+    int32_t  key_count;       /* >= 1, key_offset + key_count <= vertex_stride */
+    int32_t  reserved32;      /* 0 */
+    double   cell;            /* 0.0: compare the values themselves; finite > 0: compare grid cells */
+    uint64_t reserved;        /* 0 */
+} trgl_weld_params;
+int trgl_mesh_weld(trgl_ctx* ctx, const trgl_weld_params* params, const double* vertices, uint64_t n_vertices,
+                   const uint32_t* indices, uint64_t n_faces, int mem_kind,
+                   uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out, uint64_t* n_unique);
+
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 
 /* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and
@@ -995,7 +1054,7 @@ int trgl_flush(trgl_ctx* ctx);
  * flush first, with two exceptions.  The five calls that only queue work over caller-owned device arrays and flush
  * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths, trgl_depth_order and trgl_triangle_depths with
  * TRGL_MEM_DEVICE - leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those five,
- * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_edges, trgl_edge_select, trgl_subdiv_topology, trgl_subdiv_vertices, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
+ * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_edges, trgl_edge_select, trgl_subdiv_topology, trgl_subdiv_vertices, trgl_mesh_weld, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
  * computes on the host and returns without touching the context's queue.  A call refused for its arguments or for the
  * context's state may return before it completes anything.
  * bench.py: the RCCL gather of the previous frame's strips runs under the next frame's first half. */

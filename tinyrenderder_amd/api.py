@@ -81,6 +81,7 @@ SYMBOLS = [
     "trgl_skin_stage", "trgl_pose_palette", "trgl_draw_skinned",
     "trgl_mesh_edges", "trgl_edge_select", "trgl_draw_outline",
     "trgl_subdiv_stencil_words", "trgl_subdiv_topology", "trgl_subdiv_vertices", "trgl_draw_subdivided",
+    "trgl_mesh_weld",
     "trgl_mip_layout", "trgl_image_mipmaps", "trgl_texture_mipmaps", "trgl_selftest_sampler_lod", "trgl_image_sample", "trgl_lod_stage", "trgl_selftest_mip_lod",
 ]
 MAX_MIP_LEVELS = 16
@@ -224,6 +225,10 @@ def load_library(path: str = None):
         L.trgl_debug_edge_sort.argtypes = [vp, C.c_uint64, C.c_uint64]
     if hasattr(L, "trgl_debug_subdiv_sort"):
         L.trgl_debug_subdiv_sort.argtypes = [vp, C.c_uint64, C.c_uint64]
+    if hasattr(L, "trgl_debug_weld_hash_bits"):
+        L.trgl_debug_weld_hash_bits.argtypes = [vp, C.c_int]
+        L.trgl_debug_weld_sort.argtypes = [vp, C.c_uint64]
+        L.trgl_debug_weld_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.trgl_selftest_division.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
     L.trgl_selftest_sampler.argtypes = [vp, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     L.trgl_draw_indexed.argtypes = [vp, C.c_int, C.POINTER(Uniforms), dp, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
@@ -321,6 +326,8 @@ def load_library(path: str = None):
                                    C.c_void_p, C.c_void_p, C.c_void_p, u64p]
     L.trgl_draw_outline.argtypes = [vp, C.c_int, C.POINTER(Uniforms), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p,
                                     C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]
+    L.trgl_mesh_weld.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, u64p]
     L.trgl_subdiv_stencil_words.argtypes = [C.c_uint64, C.c_uint64]
     L.trgl_subdiv_stencil_words.restype = C.c_uint64
     L.trgl_subdiv_topology.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
@@ -1162,6 +1169,84 @@ def subdiv_vertices(params, vertices, stencils, n_edges=None):
     return _subdiv_vertices(load_library(), None, params, vertices, stencils, n_edges, False, None)[1]
 
 
+class WeldParams(C.Structure):
+    """trgl_weld_params"""
+    _fields_ = [("vertex_stride", C.c_int32), ("key_offset", C.c_int32), ("key_count", C.c_int32), ("reserved32", C.c_int32), ("cell", C.c_double),
+                ("reserved", C.c_uint64)]
+
+
+def make_weld_params(vertex_stride, key_offset=0, key_count=3, cell=0.0):
+    """trgl_weld_params: records of vertex_stride doubles, compared by the key_count doubles from key_offset on - the values themselves
+    (cell = 0.0: IEEE ==, so -0.0 joins +0.0 and a NaN joins nothing), or their grid cells floor(x / cell + 0.5) (a grid weld: two values
+    on either side of a cell border do not join)."""
+    return WeldParams(int(vertex_stride), int(key_offset), int(key_count), 0, float(cell), 0)
+
+
+WELD_OUTPUTS = ("remap", "firsts", "vertices", "indices")
+
+
+def _mesh_weld(L, handle, params, vertices, indices, device, out, count):
+    """Returns (arrays to keep alive, dict(remap [n], firsts [n], vertices [n, stride], indices [n_faces, 3] or None), n_unique or
+    None).  out: None - every output is allocated (indices only with `indices`) - or a dict naming the outputs to write, each an array
+    or None to allocate it; an output that is not named is not written (NULL)."""
+    if device:
+        _device_f64(vertices, 2, "vertices")
+    else:
+        vertices = np.ascontiguousarray(vertices, np.float64)
+        if vertices.ndim != 2:
+            raise ValueError("vertices must have 2 dimensions [n, stride]")
+    nv, stride = int(vertices.shape[0]), int(vertices.shape[1])
+    nf = 0
+    if indices is not None:
+        indices = _words32(indices, device, "indices", 3)
+        nf = int(indices.numel() if device else indices.size) // 3
+    if out is None:
+        out = {k: None for k in WELD_OUTPUTS if k != "indices" or indices is not None}
+    unknown = set(out) - set(WELD_OUTPUTS)
+    if unknown:
+        raise ValueError(f"mesh_weld: unknown outputs {sorted(unknown)}")
+    shapes = dict(remap=(nv,), firsts=(nv,), vertices=(nv, stride), indices=(nf, 3))
+    res = {}
+    for k in WELD_OUTPUTS:
+        if k not in out:
+            res[k] = None
+        elif out[k] is not None:
+            res[k] = out[k]
+        elif device:
+            import torch
+            res[k] = torch.empty(shapes[k], dtype=torch.float64 if k == "vertices" else torch.int32, device=vertices.device)
+        else:
+            res[k] = np.empty(shapes[k], np.float64 if k == "vertices" else np.uint32)
+    n = C.c_uint64(0)
+    p = _device_ptr if device else _ptr
+    rc = L.trgl_mesh_weld(handle, C.byref(params), p(vertices) if nv else None, nv, p(indices) if nf else None, nf,
+                          MEM_DEVICE if device else MEM_HOST, p(res["remap"]), p(res["firsts"]), p(res["vertices"]),
+                          p(res["indices"]) if nf or indices is None else None, C.byref(n) if count else None)
+    if rc != 0:
+        raise TrglError(f"trgl_mesh_weld failed ({rc}): {L.trgl_last_error(handle).decode()}")
+    return (vertices, indices), res, (int(n.value) if count else None)
+
+
+def mesh_weld(params, vertices, indices=None):
+    """trgl_mesh_weld for host arrays without a context: the vertices [n, stride] whose keys (params: make_weld_params) are identical
+    joined.  Returns (dict(remap [n] - the new number of every old vertex -, firsts [n] - the old number of every new vertex, EDGE_NONE
+    behind the last -, vertices [n, stride] - the kept records, zeros behind the last -, indices [n_faces, 3] - `indices` renumbered, or
+    None without them), n_unique).  For a triangle soup remap.reshape(-1, 3) is the index array.  Needs no GPU."""
+    _, out, n = _mesh_weld(load_library(), None, params, vertices, indices, False, None, True)
+    return out, n
+
+
+def weld_hashes(params, vertices):
+    """Test hook (trgl_debug_weld_hash): the 64-bit hash the device path of mesh_weld sorts by, per vertex of a host array."""
+    L = load_library()
+    vertices = np.ascontiguousarray(vertices, np.float64)
+    out = np.empty(vertices.shape[0], np.uint64)
+    rc = L.trgl_debug_weld_hash(C.addressof(params), _ptr(vertices), int(vertices.shape[0]), _ptr(out))
+    if rc != 0:
+        raise TrglError(f"trgl_debug_weld_hash failed ({rc}): {L.trgl_last_error(None).decode()}")
+    return out
+
+
 class SkinParams(C.Structure):
     """trgl_skin_params"""
     _fields_ = [("vertex_stride", C.c_int32), ("n_influences", C.c_int32), ("n_joints", C.c_uint32), ("flags", C.c_uint32),
@@ -1894,6 +1979,25 @@ class Context:
         self._chk(self.L.trgl_draw_outline(self.h, kind, None if uniforms is None else C.byref(uniforms), C.byref(line_params),
                                            C.byref(edge_params), p(vertices), int(vertices.shape[1]), int(vertices.shape[0]), p(indices), nf,
                                            p(edges), n, MEM_DEVICE if device else MEM_HOST))
+
+    def mesh_weld(self, params, vertices, indices=None, device=False, out=None, count=True):
+        """trgl_mesh_weld (see the module's mesh_weld).  device=True: vertices [n, stride] f64 and indices [n_faces, 3] (32-bit, or None)
+        are device tensors and so are the outputs; out: None for all of them, or a dict naming those to write - "remap", "firsts",
+        "vertices", "indices", each a device tensor or None to allocate it.  count=True waits once for the 8-byte count; count=False
+        queues the kernels without waiting and returns None for it: later calls take the capacity n.  Returns (dict, n_unique)."""
+        keep, out, n = _mesh_weld(self.L, self.h, params, vertices, indices, device, out, count)
+        if device:
+            self._keep.append((keep, out))
+        return out, n
+
+    def debug_weld_hash_bits(self, bits=64):
+        """Test hook (trgl_debug_weld_hash_bits): later device welds keep the low `bits` bits of the hash (0 .. 64) and sort over them.
+        Small values force the walk through colliding keys; 0 is one run.  The outputs do not change with it."""
+        self._chk(self.L.trgl_debug_weld_hash_bits(self.h, int(bits)))
+
+    def debug_weld_sort(self, n_vertices):
+        """Diagnostic (trgl_debug_weld_sort): the sort of the last device weld of n_vertices again, over the pairs it left; no wait."""
+        self._chk(self.L.trgl_debug_weld_sort(self.h, int(n_vertices)))
 
     def subdiv_topology(self, indices, n_vertices, edges, n_edges=None, device=False, out=None):
         """trgl_subdiv_topology (see the module's subdiv_topology).  device=True: indices and edges are 32-bit device tensors - edges as

@@ -1,7 +1,7 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
 // kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip,
 // kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_skin.hip,
-// kernels_edge.hip, kernels_subdiv.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
+// kernels_edge.hip, kernels_subdiv.hip, kernels_weld.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
 // trgl_stage_rows.cpp (the stages in front of a draw) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -327,6 +327,24 @@ struct SubdivVertexArgs {
     uint32_t stride, smooth, step_q, step_r;
 };
 hipError_t launch_subdiv_vertices(hipStream_t s, SubdivVertexArgs a);
+
+// Mesh welding (kernels_weld.hip; written down under "mesh welding" in include/trgl.h, the key, the comparison and the hash are
+// weld_core.h's).  Every kernel runs WELD_BLOCK lanes a block, one vertex, sorted entry or index per lane; the counts of the blocks go
+// through launch_block_count_scan.  0 < n < 2^31 vertices, n_idx < 2^31 indices (0: none); vertices and vertices_out 8-byte aligned, the
+// uint32 arrays 4; a null output is not written (indices_out needs indices).  hash_bits 0 .. 64: the low bits of the hash the sort runs
+// over (0: no sort, one run).  scratch: mesh_weld_scratch_bytes() bytes, 256-byte aligned; *total then points at the 8-byte count of
+// distinct vertices in it.  The struct travels as the kernels' argument.
+constexpr int WELD_BLOCK = 256;
+struct WeldArgs {
+    trgl_weld_params P;
+    const double* vertices; const uint32_t* indices;
+    uint32_t* remap_out; uint32_t* firsts_out; double* vertices_out; uint32_t* indices_out;
+    uint32_t n, n_idx; int32_t hash_bits;
+};
+hipError_t mesh_weld_scratch_bytes(uint32_t n, int hash_bits, size_t* bytes);
+hipError_t launch_mesh_weld(hipStream_t s, const WeldArgs& a, void* scratch, size_t scratch_bytes, const unsigned long long** total);
+// the sort of launch_mesh_weld alone, over the pairs that call left in the same scratch (a measurement's floor: profiles/weld_probe.py)
+hipError_t launch_mesh_weld_sort(hipStream_t s, uint32_t n, int hash_bits, void* scratch, size_t scratch_bytes);
 
 // World boxes of instances and frustum codes of boxes (kernels_scene.hip; both are written down at trgl_instance_boxes /
 // trgl_frustum_boxes in include/trgl.h, the arithmetic is scene_core.h's).  One thread per instance or box, 0 < n < 2^31; doubles 8-byte

@@ -102,6 +102,10 @@ struct trgl_ctx {
     DevBuf<uint8_t> edge_scratch;
     // trgl_subdiv_topology: two sort entries per edge record with their sorted copies and the sort's own space.  Grows on demand
     DevBuf<uint8_t> subdiv_scratch;
+    // trgl_mesh_weld: the 8-byte count, hashes and vertex numbers with their sorted copies, representatives, new numbers, the map, the
+    // scan's words, the sort's own space.  Grows on demand.  weld_hash_bits: the low bits of the hash in use (trgl_debug_weld_hash_bits)
+    DevBuf<uint8_t> weld_scratch;
+    int weld_hash_bits = 64;
     DevBuf<uint8_t> order_scratch;      // trgl_depth_order: the keys, their sorted copy, the numbers 0 .. n-1, the sort's own space; grows on demand
     DevBuf<uint8_t> pp_out;            // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
@@ -226,6 +230,10 @@ bool host_subdiv_topology(const uint32_t* indices, uint64_t n_faces, uint64_t n_
                           uint32_t* indices_out, uint32_t* stencils_out);
 bool host_subdiv_vertices(const trgl_subdiv_params& P, const double* vertices, uint64_t n_vertices, const uint32_t* stencils, uint64_t n_edges,
                           double* out);
+// trgl_mesh_weld over host arrays (every index checked by the caller: below n_vertices; 0 < n_vertices < 2^31; null outputs are not
+// written; returns the count).  May throw std::bad_alloc.
+uint64_t host_mesh_weld(const trgl_weld_params& P, const double* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                        uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out);
 // trgl_instance_boxes and trgl_frustum_boxes over host arrays (local_stride 0: one local box for every instance)
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out);
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);

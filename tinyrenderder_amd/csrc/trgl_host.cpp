@@ -22,6 +22,7 @@
 #include "skin_core.h"
 #include "edge_core.h"
 #include "subdiv_core.h"
+#include "weld_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -401,6 +402,44 @@ bool host_edge_select(const trgl_edge_params& P, const double* vertices, int str
         }
     if (n_selected) *n_selected = slot;
     return true;
+}
+
+// ---- mesh welding in host memory (include/trgl.h, trgl_mesh_weld; the key, the comparison and the hash are weld_core.h's) ----
+// Every index is below n_vertices (checked by the caller), 0 < n_vertices < 2^31; returns the number of distinct vertices.  A table of
+// representatives with open addressing: vertex v, in ascending v, probes from its hash for the first representative identical to it and
+// takes an empty slot when there is none - a key with a NaN is identical to nothing, itself included, and is never entered.
+uint64_t host_mesh_weld(const trgl_weld_params& P, const double* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                        uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out) {
+    const uint64_t S = (uint64_t)P.vertex_stride;
+    uint64_t slots = 16;
+    while (slots < 2 * n_vertices) slots *= 2;
+    std::vector<uint32_t> table(slots, WELD_NONE), remap((size_t)n_vertices), firsts;
+    for (uint64_t v = 0; v < n_vertices; ++v) {
+        const double* r = vertices + v * S;
+        bool has_nan = false;
+        for (int a = 0; a < P.key_count; ++a) { const double q = weld_q(r[P.key_offset + a], P.cell); has_nan = has_nan || q != q; }
+        uint32_t rep = (uint32_t)v;
+        if (!has_nan) {
+            uint64_t at = weld_hash(r, P.key_offset, P.key_count, P.cell) & (slots - 1);
+            while (table[at] != WELD_NONE && !weld_identical(vertices + table[at] * S, r, P.key_offset, P.key_count, P.cell)) at = (at + 1) & (slots - 1);
+            if (table[at] == WELD_NONE) table[at] = (uint32_t)v;
+            rep = table[at];
+        }
+        if (rep == v) { remap[v] = (uint32_t)firsts.size(); firsts.push_back((uint32_t)v); }
+        else remap[v] = remap[rep];
+    }
+    const uint64_t U = firsts.size();
+    if (remap_out) std::memcpy(remap_out, remap.data(), n_vertices * sizeof(uint32_t));
+    if (firsts_out) {
+        std::memcpy(firsts_out, firsts.data(), U * sizeof(uint32_t));
+        for (uint64_t j = U; j < n_vertices; ++j) firsts_out[j] = WELD_NONE;
+    }
+    if (vertices_out) {
+        for (uint64_t j = 0; j < U; ++j) std::memcpy(vertices_out + j * S, vertices + firsts[j] * S, S * sizeof(double));
+        std::memset(vertices_out + U * S, 0, (n_vertices - U) * S * sizeof(double));
+    }
+    if (indices_out) for (uint64_t i = 0; i < 3 * n_faces; ++i) indices_out[i] = remap[indices[i]];
+    return U;
 }
 
 // ---- mesh subdivision in host memory (include/trgl.h, trgl_subdiv_topology / trgl_subdiv_vertices; the rules are subdiv_core.h's) ----

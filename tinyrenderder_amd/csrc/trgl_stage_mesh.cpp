@@ -1,15 +1,17 @@
 // trgl_stage_mesh.cpp — the stages over an indexed mesh and the draws behind them: the vertex stage (trgl_draw_indexed,
 // trgl_draw_indexed_vs, trgl_vertex_stage), the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and
 // skeletal animation (trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned), mesh edges (trgl_mesh_edges, trgl_edge_select,
-// trgl_draw_outline) and mesh subdivision (trgl_subdiv_topology, trgl_subdiv_vertices, trgl_draw_subdivided).
+// trgl_draw_outline), mesh subdivision (trgl_subdiv_topology, trgl_subdiv_vertices, trgl_draw_subdivided) and mesh welding (trgl_mesh_weld).
 // The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "trgl_stage.h"
 #include "skin_core.h"
 #include "edge_core.h"
 #include "subdiv_core.h"
+#include "weld_core.h"
 
 // The vertex stage of `vs` (-1: k_vertex_stage) over an indexed mesh in device memory, queued on the context's stream.  clip and
 // vary (unused when K = 0) are 16-byte aligned; u == nullptr: zeros, texture slots -1.
@@ -288,6 +290,45 @@ static int queue_subdiv_vertices(trgl_ctx* c, const std::string& w, const trgl_s
     a.vertices = vertices; a.stencils = stencils; a.out = out; a.n_vertices = n_vertices; a.n_edges = n_edges;
     a.stride = (uint32_t)P.vertex_stride; a.smooth = P.mode == TRGL_SUBDIV_LOOP ? (uint32_t)P.smooth : 0u;
     HIPCHK(c, launch_subdiv_vertices(c->stream, a));
+    return TRGL_OK;
+}
+
+// ---- mesh welding (include/trgl.h: trgl_mesh_weld) ----
+// The arrays of a weld: the records, the indices (may be null) and the four outputs (each may be null)
+struct WeldArrays { const double* vertices; uint64_t n_vertices; const uint32_t* indices; uint64_t n_faces; uint32_t* remap; uint32_t* firsts;
+                    double* vertices_out; uint32_t* indices_out; };
+
+// what the scalars of a weld must satisfy
+static int check_weld_params(trgl_ctx* c, const std::string& w, const trgl_weld_params* P, uint64_t n_vertices, uint64_t n_faces, int mem_kind) {
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    if (int r = check_mem(c, w, mem_kind)) return r;
+    if (P->reserved32 || P->reserved) return fail(c, TRGL_E_INVALID, w + "reserved must be 0");
+    if (P->vertex_stride < 1) return fail(c, TRGL_E_INVALID, w + "vertex_stride must be >= 1");
+    if (P->key_offset < 0 || P->key_count < 1 || (int64_t)P->key_offset + P->key_count > P->vertex_stride)
+        return fail(c, TRGL_E_INVALID, w + "the key must lie inside the record (key_offset >= 0, key_count >= 1)");
+    if (!(P->cell >= 0.0) || std::isinf(P->cell)) return fail(c, TRGL_E_INVALID, w + "cell must be 0 or a finite positive width");
+    if (n_vertices > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "n_vertices above 2^31 - 1");
+    if (n_faces > 0x7fffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, w + "3 * n_faces above 2^31 - 1");
+    if (!mul_fits(n_vertices, (uint64_t)P->vertex_stride * 8, 1ull << 60)) return fail(c, TRGL_E_UNSUPPORTED, w + "the vertex array is too large");
+    return TRGL_OK;
+}
+
+// ... and its arrays (n_vertices > 0): present, aligned, outputs apart from inputs and from one another
+static int check_weld_arrays(trgl_ctx* c, const std::string& w, const trgl_weld_params& P, const WeldArrays& a) {
+    if (!a.vertices) return fail(c, TRGL_E_INVALID, w + "vertices is null");
+    if (a.indices_out && !a.indices) return fail(c, TRGL_E_INVALID, w + "indices_out needs indices");
+    if (!aligned({ { a.vertices, 8 }, { a.vertices_out, 8 }, { a.indices, 4 }, { a.remap, 4 }, { a.firsts, 4 }, { a.indices_out, 4 } }))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 4 for 32-bit words)");
+    struct Range { const void* p; uint64_t bytes; };
+    const uint64_t rec = a.n_vertices * (uint64_t)P.vertex_stride * 8;
+    const Range ins[2] = { { a.vertices, rec }, { a.indices, a.n_faces * 12 } };
+    const Range outs[4] = { { a.remap, a.n_vertices * 4 }, { a.firsts, a.n_vertices * 4 }, { a.vertices_out, rec }, { a.indices_out, a.n_faces * 12 } };
+    for (const Range& i : ins)
+        for (const Range& o : outs)
+            if (arrays_overlap(i.p, i.bytes, o.p, o.bytes)) return fail(c, TRGL_E_INVALID, w + "an output overlaps an input");
+    for (int x = 0; x < 4; ++x)
+        for (int y = x + 1; y < 4; ++y)
+            if (arrays_overlap(outs[x].p, outs[x].bytes, outs[y].p, outs[y].bytes)) return fail(c, TRGL_E_INVALID, w + "two outputs overlap");
     return TRGL_OK;
 }
 
@@ -675,6 +716,76 @@ int trgl_draw_subdivided(trgl_ctx* c, int vs, int kind, const trgl_uniforms* u, 
     if ((r = check_subdiv_arrays(c, w, *P, vertices, n_vertices, stencils, n_edges, refined))) return r;
     if ((r = queue_subdiv_vertices(c, w, *P, vertices, n_vertices, stencils, n_edges, refined))) return r;
     return draw_indexed_checked(c, vs, K, kind, u, projection, refined, stride, n, refined_indices, n_refined_faces, colors, TRGL_MEM_DEVICE);
+}
+
+int trgl_mesh_weld(trgl_ctx* c, const trgl_weld_params* P, const double* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                   int mem_kind, uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out, uint64_t* n_unique) {
+    const std::string w = "trgl_mesh_weld: ";
+    int r = check_weld_params(c, w, P, n_vertices, n_faces, mem_kind); if (r) return r;
+    if (n_vertices == 0) {
+        if (n_faces) return fail(c, TRGL_E_INVALID, w + "faces without vertices");
+        if (n_unique) *n_unique = 0;
+        return TRGL_OK;
+    }
+    const WeldArrays a{ vertices, n_vertices, indices, n_faces, remap_out, firsts_out, vertices_out, indices_out };
+    if ((r = check_weld_arrays(c, w, *P, a))) return r;
+    if (mem_kind == TRGL_MEM_HOST) {
+        if (indices && !all_below(indices, 3 * n_faces, n_vertices)) return fail(c, TRGL_E_INVALID, w + "index out of range");
+        return no_bad_alloc(c, w, [&] {
+            const uint64_t u = host_mesh_weld(*P, vertices, n_vertices, indices, n_faces, remap_out, firsts_out, vertices_out, indices_out);
+            if (n_unique) *n_unique = u;
+            return TRGL_OK;
+        });
+    }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    size_t bytes = 0;
+    HIPCHK(c, mesh_weld_scratch_bytes((uint32_t)n_vertices, c->weld_hash_bits, &bytes));
+    if ((r = c->weld_scratch.grow(c, bytes))) return r;
+    WeldArgs k; std::memset(&k, 0, sizeof(k));
+    k.P = *P; k.vertices = vertices; k.indices = indices_out ? indices : nullptr;
+    k.remap_out = remap_out; k.firsts_out = firsts_out; k.vertices_out = vertices_out; k.indices_out = indices_out;
+    k.n = (uint32_t)n_vertices; k.n_idx = indices_out ? (uint32_t)(3 * n_faces) : 0u; k.hash_bits = c->weld_hash_bits;
+    const unsigned long long* total = nullptr;
+    HIPCHK(c, launch_mesh_weld(c->stream, k, c->weld_scratch.p, c->weld_scratch.cap, &total));
+    if (n_unique) {
+        unsigned long long count = 0;
+        HIPCHK(c, hipMemcpyAsync(&count, total, sizeof(count), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait, at load time
+        *n_unique = count;
+    }
+    return TRGL_OK;
+}
+
+// Test hook, not part of include/trgl.h (tests/test_weld_gpu.py): later device welds of this context keep only the low `bits` bits of
+// the hash (0 .. 64; 64 is the default) and sort over that many - small values force the walk through a run of colliding keys, 0 puts
+// every vertex in one run.  The outputs do not change with it.
+int trgl_debug_weld_hash_bits(trgl_ctx* c, int bits) {
+    CHKCTX(c);
+    if (bits < 0 || bits > 64) return fail(c, TRGL_E_INVALID, "trgl_debug_weld_hash_bits: bits must be 0 .. 64");
+    c->weld_hash_bits = bits;
+    return TRGL_OK;
+}
+
+// Diagnostic, not part of include/trgl.h (profiles/weld_probe.py): the radix sort of the last trgl_mesh_weld call with this count again,
+// over the pairs it left in the context's scratch - the floor that call is measured against.  Queued, no wait.
+int trgl_debug_weld_sort(trgl_ctx* c, uint64_t n_vertices) {
+    CHKCTX(c);
+    if (n_vertices == 0 || n_vertices > 0x7fffffffull || c->weld_hash_bits < 1) return fail(c, TRGL_E_INVALID, "trgl_debug_weld_sort: bad count, or no hash bits to sort");
+    size_t bytes = 0;
+    HIPCHK(c, mesh_weld_scratch_bytes((uint32_t)n_vertices, c->weld_hash_bits, &bytes));
+    if (c->weld_scratch.cap < bytes) return fail(c, TRGL_E_STATE, "trgl_debug_weld_sort: no trgl_mesh_weld call of this size came before");
+    HIPCHK(c, launch_mesh_weld_sort(c->stream, (uint32_t)n_vertices, c->weld_hash_bits, c->weld_scratch.p, c->weld_scratch.cap));
+    return TRGL_OK;
+}
+
+// Test hook, not part of include/trgl.h (tests/test_weld.py): weld_core.h's hash of the key of every vertex of a host array
+int trgl_debug_weld_hash(const trgl_weld_params* P, const double* vertices, uint64_t n_vertices, uint64_t* hashes_out) {
+    const std::string w = "trgl_debug_weld_hash: ";
+    if (int r = check_weld_params(nullptr, w, P, n_vertices, 0, TRGL_MEM_HOST)) return r;
+    if (n_vertices && (!vertices || !hashes_out)) return fail(nullptr, TRGL_E_INVALID, w + "null array");
+    for (uint64_t v = 0; v < n_vertices; ++v) hashes_out[v] = weld_hash(vertices + v * (uint64_t)P->vertex_stride, P->key_offset, P->key_count, P->cell);
+    return TRGL_OK;
 }
 
 }  // extern "C"

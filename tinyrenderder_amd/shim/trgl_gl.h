@@ -911,6 +911,32 @@ inline bool gl_draw_subdivided(const IShader& shader, const trgl_subdiv_params& 
     return ok;
 }
 
+// Mesh welding (include/trgl.h, trgl_mesh_weld): what stands where Model asked Assimp for aiProcess_JoinIdenticalVertices - on the host,
+// no context needed.  The vertices (records of `stride` doubles) whose key - key_count doubles from key_offset on; cell > 0: their grid
+// cells - is identical become one: `vertices` shrinks to the distinct records in their first order, every entry of `indices` (3 per
+// face; may be empty for a soup) is renumbered, and remap[v] is the new number of old vertex v - what gathers arrays kept beside the
+// records.  Faces are kept, degenerate ones included.  A call that fails (gl_last_error()) leaves the three vectors as they were.
+inline trgl_weld_params gl_weld_params(int vertex_stride, int key_offset = 0, int key_count = 3, double cell = 0.0) {
+    trgl_weld_params p{};
+    p.vertex_stride = vertex_stride; p.key_offset = key_offset; p.key_count = key_count; p.cell = cell;
+    return p;
+}
+inline bool gl_mesh_weld(const trgl_weld_params& params, std::vector<double>& vertices, std::vector<unsigned int>& indices, std::vector<std::uint32_t>& remap) {
+    static_assert(sizeof(unsigned int) == sizeof(std::uint32_t), "indices are 32-bit");
+    const std::size_t stride = std::size_t(params.vertex_stride > 0 ? params.vertex_stride : 1), n = vertices.size() / stride;
+    std::vector<double> welded(vertices.size());
+    std::vector<unsigned int> renumbered(indices.size());
+    std::vector<std::uint32_t> map(n);
+    std::uint64_t unique = 0;
+    const int rc = trgl_mesh_weld(nullptr, &params, vertices.data(), n, indices.empty() ? nullptr : reinterpret_cast<const std::uint32_t*>(indices.data()),
+                                  indices.size() / 3, TRGL_MEM_HOST, map.data(), nullptr, welded.data(),
+                                  indices.empty() ? nullptr : reinterpret_cast<std::uint32_t*>(renumbered.data()), &unique);
+    if (rc != TRGL_OK) return trgl_shim::fail("gl_mesh_weld", rc, nullptr);
+    welded.resize(std::size_t(unique) * stride);
+    vertices.swap(welded); indices.swap(renumbered); remap.swap(map);
+    return true;
+}
+
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
 // write_tga_file(), main.cpp:743,773).  The depths follow on demand through the `zbuffer` proxy.
 // false: something submitted since the last gl_flush() failed (gl_last_error()); the pixels hold what could be drawn.
