@@ -977,6 +977,101 @@ int trgl_mesh_weld(trgl_ctx* ctx, const trgl_weld_params* params, const double* 
                    const uint32_t* indices, uint64_t n_faces, int mem_kind,
                    uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out, uint64_t* n_unique);
 
+/* ---- mesh levels of detail: faces that draw nothing removed, one level of vertex clustering ------------------------------------------- */
+
+/* New work: the reference draws every mesh at the detail Assimp delivered (its aiProcess_FindDegenerates / aiProcess_OptimizeMeshes-style
+ * steps are not part of this library and are not reproduced).  Every mesh call above refines a mesh or leaves its size alone;
+ * trgl_mesh_weld says of itself that a face welding made degenerate stays.  These two calls make a mesh smaller.  With TRGL_MEM_DEVICE
+ * nothing visits the host.  NONE is 0xFFFFFFFF.  One mem_kind covers every array of a call.
+ *
+ * trgl_mesh_clean: DROP THE FACES THAT DRAW NOTHING, THEN THE VERTICES NOBODY NAMES.
+ * FACES.  With V = n_vertices, face f (indices[3 f .. 3 f + 2]) is
+ *   invalid    when one of its indices is >= V.  Host memory: TRGL_E_INVALID, nothing is written.  Device memory: the face is dropped,
+ *              and the index is never used as an address;
+ *   degenerate when two of its three indices are equal;
+ *   duplicate  - only with TRGL_CLEAN_DUPLICATES - when some g < f that is neither invalid nor degenerate has the same canonical triple:
+ *              the rotation of the three indices that puts the smallest first, orientation kept.  A mirrored face is no duplicate:
+ *              both sides of a collapsed sheet stay.  (g need not be kept itself: it is then a duplicate of a kept face in front.)
+ *   Everything else is KEPT.  Kept faces keep their relative order and are numbered 0 .. Fk - 1.
+ * FACE OUTPUTS, each may be NULL.
+ *   indices_out, 3 * n_faces uint32: face j < Fk is the three indices of kept face j in their original rotation; every word behind
+ *     3 * Fk is the fill: TRGL_CLEAN_FILL_NONE writes NONE - what trgl_mesh_edges, trgl_mesh_weld and these two calls take for "no
+ *     vertex" -, TRGL_CLEAN_FILL_ZERO writes 0 - a face (0, 0, 0), which rasterize() drops, so trgl_draw_indexed may run over the
+ *     capacity n_faces without a count.
+ *   face_firsts_out, n_faces uint32: the old number of kept face j, NONE behind Fk.
+ * VERTICES.  Without TRGL_CLEAN_VERTICES the indices keep their old numbers, vremap_out, vfirsts_out and vertices_out must be NULL,
+ * `vertices` may be NULL and counts[1] = V.  With it a vertex is referenced when a kept face names it; the referenced vertices are
+ * numbered 0 .. Vk - 1 in ascending old number; vremap_out[v] (n_vertices uint32) is that new number, or NONE; indices_out carries new
+ * numbers; vfirsts_out (n_vertices uint32) and vertices_out (n_vertices records of vertex_stride doubles) are what firsts_out and
+ * vertices_out are to trgl_mesh_weld: vfirsts_out[j] the old number of new vertex j, NONE behind Vk; record j the whole record of that
+ * vertex bit for bit, every byte behind Vk records 0.  vertex_stride is read only with TRGL_CLEAN_VERTICES and vertices_out, which
+ * needs `vertices`.
+ * COUNTS.  counts (host, may be NULL) = { Fk, Vk }.  NULL: no wait.  Non-NULL with device memory: one wait for the 16 bytes.
+ * ERRORS.  TRGL_E_INVALID: a bad mem_kind, TRGL_MEM_DEVICE without a context, params NULL, a reserved field not 0, unknown flags, an
+ * unknown fill, vertex_stride < 1 where it is read, a vertex output without TRGL_CLEAN_VERTICES, vertices_out without vertices, a null
+ * `indices` with n_faces > 0, a misaligned array, an output that overlaps an input or another output, n_faces > 0 with n_vertices ==
+ * 0, a host index out of range.  TRGL_E_UNSUPPORTED: n_vertices or 3 * n_faces above 2^31 - 1, or records that do not fit 2^60 bytes.
+ * n_faces == 0: TRGL_OK; with TRGL_CLEAN_VERTICES every vertex is unreferenced (NONE and zero records everywhere), counts = { 0, 0 }.
+ *
+ * trgl_mesh_simplify: ONE LEVEL OF VERTEX CLUSTERING (Rossignac-Borrel), defined as a COMPOSITION of the calls above:
+ *   (a) WELD.  trgl_mesh_weld with key_offset 0, key_count 3 and this cell over `vertices` and `indices`: the same q = floor(x / cell +
+ *       0.5), the same IEEE ==, the same representative (the lowest number).  A NaN position clusters with nothing.
+ *   (b) MEAN, when mean_count > 0.  An input vertex is referenced when some word of `indices` equals its number.  For every cluster and
+ *       every a < mean_count: s = double a of the cluster's lowest-numbered referenced member; the other referenced members' doubles a
+ *       are added in ascending old number, every sum rounded, no contraction, no reassociation; the result is s / (double)count, an
+ *       IEEE division.  A cluster with one referenced member keeps that member's bits; one with none keeps the representative's record.
+ *       The doubles at or behind mean_count are the representative's: normals, uv and the rest are not blended.  Referenced-only is
+ *       deliberate: the zero records behind a count all lie in the origin's cell and must not pull its mean when a second level runs
+ *       over the capacity.
+ *   (c) CLEAN.  trgl_mesh_clean with TRGL_CLEAN_DUPLICATES | TRGL_CLEAN_VERTICES and this fill over (b)'s records and (a)'s indices.
+ * OUTPUTS, each may be NULL.  vertices_out, indices_out, face_firsts_out and counts are (c)'s.  remap_out[v] (n_vertices uint32) is
+ * (c)'s vremap at (a)'s remap[v]: NONE for a vertex whose cluster left.  firsts_out[j] is (a)'s firsts at (c)'s vfirsts[j]: the lowest-
+ * numbered input vertex of the cluster that became new vertex j, NONE behind the count.
+ * THE CHAIN.  A second level queues over the CAPACITIES n_vertices and n_faces of the first, run with TRGL_CLEAN_FILL_NONE: the first
+ * level's fill faces are invalid, so the second level drops them, and its fill records are unreferenced, so they enter no mean and
+ * leave with (c).  Below the final counts the words equal those of a chain that passed the real counts; no number visits the host
+ * unless counts is given.
+ * ERRORS.  Those of trgl_mesh_weld and trgl_mesh_clean, with vertex_stride < 3 and mean_count outside 0 .. vertex_stride.
+ *
+ * MEMORY AND ORDER, both calls, as trgl_mesh_weld.  Host memory: plain C++, ctx may be NULL, no GPU is touched.  Device memory: doubles
+ * 8-byte aligned, every uint32 array 4 - nothing wider is assumed -; the bytes never depend on the alignment.  The kernels are queued on
+ * the context's stream in order with the draws: nothing is flushed; they complete a begun flush, as trgl_clip_stage does.
+ * DEVICE PATH.  Duplicate faces are found the way the weld finds duplicate vertices: a 64-bit hash of the canonical triple per face, a
+ * stable radix sort of (hash, face) pairs, every entry compared with the head of its run of equal hashes - and, on a collision, a walk
+ * of the run; a dropped face is identical to nothing.  Referenced flags are plain stores of one word by every face that names the
+ * vertex; numbers come from ballots and a scan in two levels; kept triples and records leave as contiguous pieces.  The mean is one
+ * thread per cluster, walking the cluster's run of the weld's sorted pairs in ascending vertex number: a mesh collapsed into a few cells
+ * makes that walk long and serial (README: the measured worst case).  The intermediate arrays of trgl_mesh_simplify live in scratch the
+ * context owns.  No atomic decides a number or a position. */
+#define TRGL_CLEAN_DUPLICATES 1u
+#define TRGL_CLEAN_VERTICES   2u
+#define TRGL_CLEAN_FILL_NONE  0u
+#define TRGL_CLEAN_FILL_ZERO  1u
+typedef struct trgl_clean_params {
+    int32_t  vertex_stride;   /* doubles per record; only read with TRGL_CLEAN_VERTICES and vertices_out */
+    uint32_t flags;           /* TRGL_CLEAN_DUPLICATES | TRGL_CLEAN_VERTICES */
+    uint32_t fill;            /* TRGL_CLEAN_FILL_NONE or TRGL_CLEAN_FILL_ZERO */
+    uint32_t reserved32;      /* 0 */
+    uint64_t reserved;        /* 0 */
+} trgl_clean_params;
+int trgl_mesh_clean(trgl_ctx* ctx, const trgl_clean_params* params, const uint32_t* indices, uint64_t n_faces,
+                    const double* vertices, uint64_t n_vertices, int mem_kind,
+                    uint32_t* indices_out, uint32_t* face_firsts_out,
+                    uint32_t* vremap_out, uint32_t* vfirsts_out, double* vertices_out,
+                    uint64_t counts[2] /* host; may be NULL */);
+typedef struct trgl_simplify_params {
+    int32_t  vertex_stride;   /* >= 3; the position is the first 3 doubles of a record */
+    int32_t  mean_count;      /* 0 .. vertex_stride: the first mean_count doubles of a kept record become the cell's mean */
+    uint32_t fill;            /* as trgl_clean_params.fill */
+    uint32_t reserved32;      /* 0 */
+    double   cell;            /* finite, >= 0; 0 compares the positions themselves */
+    uint64_t reserved;        /* 0 */
+} trgl_simplify_params;
+int trgl_mesh_simplify(trgl_ctx* ctx, const trgl_simplify_params* params, const double* vertices, uint64_t n_vertices,
+                       const uint32_t* indices, uint64_t n_faces, int mem_kind,
+                       uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out,
+                       uint32_t* indices_out, uint32_t* face_firsts_out, uint64_t counts[2] /* host; may be NULL */);
+
 /* ---- clipping against a plane in clip space, between the vertex stage and rasterize() ------------------------ */
 
 /* New work: the reference does not clip.  rasterize() drops a whole triangle as soon as one vertex has w <= 1e-12 (our_gl.cpp:94) and
@@ -1054,7 +1149,7 @@ int trgl_flush(trgl_ctx* ctx);
  * flush first, with two exceptions.  The five calls that only queue work over caller-owned device arrays and flush
  * nothing - trgl_instance_boxes, trgl_frustum_boxes, trgl_instance_depths, trgl_depth_order and trgl_triangle_depths with
  * TRGL_MEM_DEVICE - leave a begun flush begun.  And a call whose arrays are all in host memory and that does no GPU work (those five,
- * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_edges, trgl_edge_select, trgl_subdiv_topology, trgl_subdiv_vertices, trgl_mesh_weld, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
+ * trgl_clip_stage, trgl_order_stage, trgl_sprite_stage, trgl_line_stage, trgl_skin_stage, trgl_pose_palette, trgl_mesh_edges, trgl_edge_select, trgl_subdiv_topology, trgl_subdiv_vertices, trgl_mesh_weld, trgl_mesh_clean, trgl_mesh_simplify, trgl_mesh_bounds, the trgl_mesh_* attributes and the *_image / trgl_image_* forms with TRGL_MEM_HOST)
  * computes on the host and returns without touching the context's queue.  A call refused for its arguments or for the
  * context's state may return before it completes anything.
  * bench.py: the RCCL gather of the previous frame's strips runs under the next frame's first half. */

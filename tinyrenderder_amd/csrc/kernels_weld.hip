@@ -21,28 +21,18 @@
 // No atomic decides a number or a position.  Records move as 64-bit words: every bit is kept.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include "compact_device.h"
 #include "launch.h"
 #include "weld_core.h"
 
 namespace {
 
 using namespace trgl;
+using namespace trgl_dev;            // block_rank, store_run, move_kept_records (compact_device.h)
 
-static_assert(WELD_BLOCK == 256 && WELD_BLOCK == INST_BLOCK, "four waves per block, and the scan of kernels_instance.hip over the block counts");
+static_assert(WELD_BLOCK == 256 && WELD_BLOCK == INST_BLOCK && WELD_BLOCK == COMPACT_BLOCK, "four waves per block, and the scan of kernels_instance.hip over the block counts");
 
 typedef unsigned long long u64;
-
-// The rank of this lane among the lanes of its block with `mine` set, and the block's count of them (every lane).  s_w: 4 words of LDS.
-__device__ __forceinline__ uint32_t block_rank(bool mine, uint32_t* s_w, uint32_t* count) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 b = __ballot(mine);
-    if (lane == 0) s_w[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t rank = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) rank += s_w[w];
-    *count = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    return rank;
-}
 
 __global__ __launch_bounds__(WELD_BLOCK) void k_weld_keys(WeldArgs a, u64* __restrict__ hashes, uint32_t* __restrict__ numbers) {
     const uint32_t v = blockIdx.x * WELD_BLOCK + threadIdx.x;
@@ -82,18 +72,6 @@ __global__ __launch_bounds__(WELD_BLOCK) void k_weld_count(const uint32_t* __res
     if (threadIdx.x == 0) blk[blockIdx.x] = count;
 }
 
-// nd 64-bit words to g (8-byte aligned) as contiguous memory, word d = f(d): 16 bytes per lane, 8 at a head or tail
-template <class F> __device__ __forceinline__ void store_run(u64* g, u64 nd, F f) {
-    const u64 head = (((uintptr_t)g & 15) != 0 && nd) ? 1u : 0u;
-    if (head && threadIdx.x == 0) g[0] = f((u64)0);
-    const u64 pairs = (nd - head) >> 1;
-    for (u64 p = threadIdx.x; p < pairs; p += WELD_BLOCK) {
-        const u64 d = head + 2 * p;
-        *reinterpret_cast<ulonglong2*>(g + d) = make_ulonglong2(f(d), f(d + 1));
-    }
-    if (((nd - head) & 1u) && threadIdx.x == WELD_BLOCK - 1) g[nd - 1] = f(nd - 1);
-}
-
 __global__ __launch_bounds__(WELD_BLOCK) void k_weld_write(WeldArgs a, const uint32_t* __restrict__ rep, const uint32_t* __restrict__ blk,
                                                            const uint32_t* __restrict__ chunk, const u64* __restrict__ total,
                                                            uint32_t* __restrict__ newnum) {
@@ -113,22 +91,8 @@ __global__ __launch_bounds__(WELD_BLOCK) void k_weld_write(WeldArgs a, const uin
     if (v < a.n && (u64)v >= U && a.firsts_out) a.firsts_out[v] = WELD_NONE;
     if (!a.vertices_out) return;
     __syncthreads();
-    const u64 S = (u64)a.P.vertex_stride;
-    const u64* src = reinterpret_cast<const u64*>(a.vertices) + (u64)v0 * S;
-    u64* out = reinterpret_cast<u64*>(a.vertices_out);
-    if (count) {
-        const u64 nd = (u64)count * S;
-        if (nd <= 0xFFFFFFFFull) {
-            const uint32_t S32 = (uint32_t)S;
-            store_run(out + (u64)base * S, nd, [&](u64 d) { const uint32_t r = (uint32_t)d / S32; return src[(u64)s_src[r] * S + ((uint32_t)d - r * S32)]; });
-        } else {
-            store_run(out + (u64)base * S, nd, [&](u64 d) { const u64 r = d / S; return src[(u64)s_src[r] * S + (d - r * S)]; });
-        }
-    }
-    // the zero records of the block's vertices at or above *total
-    const u64 end = (u64)v0 + WELD_BLOCK < (u64)a.n ? (u64)v0 + WELD_BLOCK : (u64)a.n;
-    const u64 z0 = U > (u64)v0 ? U : (u64)v0;
-    if (z0 < end) store_run(out + z0 * S, (end - z0) * S, [](u64) { return (u64)0; });
+    move_kept_records(reinterpret_cast<const u64*>(a.vertices), reinterpret_cast<u64*>(a.vertices_out), (u64)a.P.vertex_stride, s_src, count, base,
+                      v0, a.n, U);
 }
 
 __global__ __launch_bounds__(WELD_BLOCK) void k_weld_remap(const uint32_t* __restrict__ rep, const uint32_t* __restrict__ newnum, uint32_t n,
@@ -145,7 +109,6 @@ __global__ __launch_bounds__(WELD_BLOCK) void k_weld_indices(const uint32_t* __r
     indices_out[i] = idx < n ? remap[idx] : WELD_NONE;
 }
 
-size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 uint32_t num_blocks(uint32_t n) { return (n + WELD_BLOCK - 1) / WELD_BLOCK; }
 uint32_t num_chunks(uint32_t nblk) { return (nblk + INST_SCAN_CHUNK - 1) / INST_SCAN_CHUNK; }
 
@@ -157,15 +120,15 @@ Carve carve(void* scratch, uint32_t n) {
     Carve c;
     size_t off = 0;
     c.total = (u64*)(p + off); off += 256;
-    c.hashes = (u64*)(p + off); off += align256((size_t)n * sizeof(u64));
-    c.sorted_hashes = (u64*)(p + off); off += align256((size_t)n * sizeof(u64));
-    c.numbers = (uint32_t*)(p + off); off += align256((size_t)n * sizeof(uint32_t));
-    c.sorted_numbers = (uint32_t*)(p + off); off += align256((size_t)n * sizeof(uint32_t));
-    c.rep = (uint32_t*)(p + off); off += align256((size_t)n * sizeof(uint32_t));
-    c.newnum = (uint32_t*)(p + off); off += align256((size_t)n * sizeof(uint32_t));
-    c.remap = (uint32_t*)(p + off); off += align256((size_t)n * sizeof(uint32_t));
-    c.blk = (uint32_t*)(p + off); off += align256((size_t)nblk * sizeof(uint32_t));
-    c.chunk = (uint32_t*)(p + off); off += align256((size_t)num_chunks(nblk) * sizeof(uint32_t));
+    c.hashes = (u64*)(p + off); off += scratch_align256((size_t)n * sizeof(u64));
+    c.sorted_hashes = (u64*)(p + off); off += scratch_align256((size_t)n * sizeof(u64));
+    c.numbers = (uint32_t*)(p + off); off += scratch_align256((size_t)n * sizeof(uint32_t));
+    c.sorted_numbers = (uint32_t*)(p + off); off += scratch_align256((size_t)n * sizeof(uint32_t));
+    c.rep = (uint32_t*)(p + off); off += scratch_align256((size_t)n * sizeof(uint32_t));
+    c.newnum = (uint32_t*)(p + off); off += scratch_align256((size_t)n * sizeof(uint32_t));
+    c.remap = (uint32_t*)(p + off); off += scratch_align256((size_t)n * sizeof(uint32_t));
+    c.blk = (uint32_t*)(p + off); off += scratch_align256((size_t)nblk * sizeof(uint32_t));
+    c.chunk = (uint32_t*)(p + off); off += scratch_align256((size_t)num_chunks(nblk) * sizeof(uint32_t));
     c.sort_off = off;
     return c;
 }
@@ -187,7 +150,7 @@ hipError_t mesh_weld_scratch_bytes(uint32_t n, int hash_bits, size_t* bytes) {
         const hipError_t e = sort_pairs(nullptr, tmp, c, n, hash_bits, nullptr);
         if (e != hipSuccess) return e;
     }
-    *bytes = c.sort_off + align256(tmp);
+    *bytes = c.sort_off + scratch_align256(tmp);
     return hipSuccess;
 }
 
@@ -216,6 +179,11 @@ hipError_t launch_mesh_weld(hipStream_t s, const WeldArgs& a, void* scratch, siz
             hipLaunchKernelGGL(k_weld_indices, dim3(num_blocks(a.n_idx)), dim3(WELD_BLOCK), 0, s, a.indices, a.n_idx, remap, a.n, a.indices_out);
     }
     return hipGetLastError();
+}
+
+WeldPairs mesh_weld_pairs(const void* scratch, uint32_t n, int hash_bits) {
+    const Carve c = carve(const_cast<void*>(scratch), n);
+    return hash_bits > 0 ? WeldPairs{ c.sorted_hashes, c.sorted_numbers, c.rep, c.newnum } : WeldPairs{ c.hashes, c.numbers, c.rep, c.newnum };
 }
 
 hipError_t launch_mesh_weld_sort(hipStream_t s, uint32_t n, int hash_bits, void* scratch, size_t scratch_bytes) {

@@ -1,7 +1,7 @@
 // launch.h — host-callable launchers of the gfx950 kernels (kernels_bin.hip, kernels_items.hip, kernels_raster.hip, kernels_post.hip,
 // kernels_mesh.hip, kernels_image.hip, kernels_resolve.hip, kernels_mip.hip, kernels_shadow.hip, kernels_clip.hip,
 // kernels_occlusion.hip, kernels_instance.hip, kernels_order.hip, kernels_triorder.hip, kernels_sprite.hip, kernels_skin.hip,
-// kernels_edge.hip, kernels_subdiv.hip, kernels_weld.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
+// kernels_edge.hip, kernels_subdiv.hip, kernels_weld.hip, kernels_lod.hip, kernels_scene.hip, kernels_selftest.hip), called by trgl_api.cpp (the flush), trgl_stage_mesh.cpp, trgl_stage_instance.cpp and
 // trgl_stage_rows.cpp (the stages in front of a draw) and trgl_passes.cpp (the rest).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -335,6 +335,8 @@ hipError_t launch_subdiv_vertices(hipStream_t s, SubdivVertexArgs a);
 // over (0: no sort, one run).  scratch: mesh_weld_scratch_bytes() bytes, 256-byte aligned; *total then points at the 8-byte count of
 // distinct vertices in it.  The struct travels as the kernels' argument.
 constexpr int WELD_BLOCK = 256;
+// the pieces of a scratch buffer start on 256-byte boundaries (kernels_weld.hip, kernels_lod.hip, trgl_stage_mesh.cpp)
+inline size_t scratch_align256(size_t n) { return (n + 255) & ~size_t(255); }
 struct WeldArgs {
     trgl_weld_params P;
     const double* vertices; const uint32_t* indices;
@@ -345,6 +347,41 @@ hipError_t mesh_weld_scratch_bytes(uint32_t n, int hash_bits, size_t* bytes);
 hipError_t launch_mesh_weld(hipStream_t s, const WeldArgs& a, void* scratch, size_t scratch_bytes, const unsigned long long** total);
 // the sort of launch_mesh_weld alone, over the pairs that call left in the same scratch (a measurement's floor: profiles/weld_probe.py)
 hipError_t launch_mesh_weld_sort(hipStream_t s, uint32_t n, int hash_bits, void* scratch, size_t scratch_bytes);
+
+// What launch_mesh_weld leaves in its scratch for a kernel queued behind it (kernels_lod.hip, the mean of a cell): the (hash, vertex)
+// pairs as sorted - a run of equal hashes ascends in vertex number; hash_bits == 0: one run -, rep[v] the representative of vertex v and
+// newnum[v] the new number of a representative v (other entries are not written).  n and hash_bits as passed to launch_mesh_weld.
+struct WeldPairs { const unsigned long long* hashes; const uint32_t* numbers; const uint32_t* rep; const uint32_t* newnum; };
+WeldPairs mesh_weld_pairs(const void* scratch, uint32_t n, int hash_bits);
+
+// Mesh levels of detail (kernels_lod.hip; written down under "mesh levels of detail" in include/trgl.h, the class of a face, the
+// canonical triple, its hash and the mean's arithmetic are lod_core.h's).  Every kernel runs LOD_BLOCK lanes a block, one face, sorted
+// entry or vertex per lane; the counts of the blocks go through launch_block_count_scan.
+// launch_mesh_clean: n_faces < 2^31 / 3, 0 < n_vertices < 2^31 (n_faces == 0 needs CLEAN_VERTICES); indices 4-byte aligned, vertices
+// and vertices_out 8; a null output is not written; the vertex outputs need TRGL_CLEAN_VERTICES in P.flags.  hash_bits 0 .. 64: the low
+// bits of the face hash the sort runs over (0: no sort, one run).  scratch: mesh_clean_scratch_bytes() bytes, 256-byte aligned; *totals
+// then points at the two 8-byte counts { kept faces, kept vertices } in it (the second is only written with TRGL_CLEAN_VERTICES).
+constexpr int LOD_BLOCK = 256;
+struct CleanArgs {
+    trgl_clean_params P;
+    const uint32_t* indices; const double* vertices;
+    uint32_t* indices_out; uint32_t* face_firsts_out; uint32_t* vremap_out; uint32_t* vfirsts_out; double* vertices_out;
+    uint32_t n_faces, n_vertices; int32_t hash_bits;
+};
+hipError_t mesh_clean_scratch_bytes(uint32_t n_faces, uint32_t n_vertices, int hash_bits, size_t* bytes);
+hipError_t launch_mesh_clean(hipStream_t s, const CleanArgs& a, void* scratch, size_t scratch_bytes, const unsigned long long** totals);
+// the sort of launch_mesh_clean alone, over the pairs that call left in the same scratch (a measurement's floor: profiles/lod_probe.py)
+hipError_t launch_mesh_clean_sort(hipStream_t s, uint32_t n_faces, uint32_t n_vertices, int hash_bits, void* scratch, size_t scratch_bytes);
+// The pieces of trgl_mesh_simplify between its weld and its clean, and behind the clean.
+// launch_lod_mean: queued behind launch_mesh_weld(n vertices, hash_bits) whose scratch is weld_scratch and whose vertices_out is
+// `records`: the first mean_count doubles of every kept record become the mean of the cluster's members that some word of
+// indices[0 .. n_idx) names.  referenced: n words of scratch.
+hipError_t launch_lod_mean(hipStream_t s, const double* vertices, int stride, int mean_count, uint32_t n, const uint32_t* indices, uint32_t n_idx,
+                           const void* weld_scratch, int hash_bits, uint32_t* referenced, double* records);
+// launch_lod_compose: remap_out[v] = vremap[weld_remap[v]] and firsts_out[j] = weld_firsts[vfirsts[j]], NONE where vfirsts[j] is (either
+// output may be null)
+hipError_t launch_lod_compose(hipStream_t s, uint32_t n, const uint32_t* weld_remap, const uint32_t* vremap, uint32_t* remap_out,
+                              const uint32_t* weld_firsts, const uint32_t* vfirsts, uint32_t* firsts_out);
 
 // World boxes of instances and frustum codes of boxes (kernels_scene.hip; both are written down at trgl_instance_boxes /
 // trgl_frustum_boxes in include/trgl.h, the arithmetic is scene_core.h's).  One thread per instance or box, 0 < n < 2^31; doubles 8-byte

@@ -106,6 +106,12 @@ struct trgl_ctx {
     // scan's words, the sort's own space.  Grows on demand.  weld_hash_bits: the low bits of the hash in use (trgl_debug_weld_hash_bits)
     DevBuf<uint8_t> weld_scratch;
     int weld_hash_bits = 64;
+    // trgl_mesh_clean: the two 8-byte counts, face hashes and numbers with their sorted copies, keep bytes, referenced words, the vertex map,
+    // the two scans' words, the sort's own space.  lod_work: the arrays between the weld, the mean and the clean of trgl_mesh_simplify.
+    // Both grow on demand.  lod_hash_bits: the low bits of the face hash in use (trgl_debug_lod_hash_bits)
+    DevBuf<uint8_t> lod_scratch;
+    DevBuf<uint8_t> lod_work;
+    int lod_hash_bits = 64;
     DevBuf<uint8_t> order_scratch;      // trgl_depth_order: the keys, their sorted copy, the numbers 0 .. n-1, the sort's own space; grows on demand
     DevBuf<uint8_t> pp_out;            // trgl_postprocess: three [H][W][3] images + two 64-bit z-range keys, kept between calls
     DevBuf<uint32_t> blk_sums;          // pairs per setup block of 256 triangles
@@ -234,6 +240,15 @@ bool host_subdiv_vertices(const trgl_subdiv_params& P, const double* vertices, u
 // written; returns the count).  May throw std::bad_alloc.
 uint64_t host_mesh_weld(const trgl_weld_params& P, const double* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
                         uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out);
+// trgl_mesh_clean over host arrays (every index checked by the caller: below n_vertices; null outputs are not written; the vertex
+// outputs only with TRGL_CLEAN_VERTICES); counts = { kept faces, kept vertices }.  May throw std::bad_alloc.
+void host_mesh_clean(const trgl_clean_params& P, const uint32_t* indices, uint64_t n_faces, const double* vertices, uint64_t n_vertices,
+                     uint32_t* indices_out, uint32_t* face_firsts_out, uint32_t* vremap_out, uint32_t* vfirsts_out, double* vertices_out,
+                     uint64_t counts[2]);
+// trgl_mesh_simplify over host arrays (as above; n_vertices > 0): host_mesh_weld, the means, host_mesh_clean.  May throw std::bad_alloc.
+void host_mesh_simplify(const trgl_simplify_params& P, const double* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                        uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out, uint32_t* face_firsts_out,
+                        uint64_t counts[2]);
 // trgl_instance_boxes and trgl_frustum_boxes over host arrays (local_stride 0: one local box for every instance)
 void host_instance_boxes(const double* local_boxes, int local_stride, const double* instances, int stride, uint64_t n, double* boxes_out);
 void host_frustum_boxes(const double planes[24], const double* boxes, uint64_t n, bool merge, uint8_t* codes);

@@ -23,6 +23,7 @@
 #include "edge_core.h"
 #include "subdiv_core.h"
 #include "weld_core.h"
+#include "lod_core.h"
 #include "../shim/trgl_image.h"
 #include "../shim/trgl_obj.h"
 
@@ -440,6 +441,101 @@ uint64_t host_mesh_weld(const trgl_weld_params& P, const double* vertices, uint6
     }
     if (indices_out) for (uint64_t i = 0; i < 3 * n_faces; ++i) indices_out[i] = remap[indices[i]];
     return U;
+}
+
+// ---- mesh levels of detail in host memory (include/trgl.h, trgl_mesh_clean / trgl_mesh_simplify; the definitions are lod_core.h's) ----
+// Every index is below n_vertices (checked by the caller).  Duplicates: a table of canonical triples with open addressing, faces entered
+// in ascending number - a face that finds its triple is a duplicate of an earlier candidate.
+void host_mesh_clean(const trgl_clean_params& P, const uint32_t* indices, uint64_t n_faces, const double* vertices, uint64_t n_vertices,
+                     uint32_t* indices_out, uint32_t* face_firsts_out, uint32_t* vremap_out, uint32_t* vfirsts_out, double* vertices_out,
+                     uint64_t counts[2]) {
+    const bool duplicates = (P.flags & TRGL_CLEAN_DUPLICATES) != 0, with_vertices = (P.flags & TRGL_CLEAN_VERTICES) != 0;
+    std::vector<uint32_t> kept;
+    uint64_t slots = 16;
+    while (duplicates && slots < 2 * n_faces) slots *= 2;
+    std::vector<uint32_t> table(duplicates ? slots : 0, LOD_NONE);
+    for (uint64_t f = 0; f < n_faces; ++f) {
+        const uint32_t a = indices[3 * f], b = indices[3 * f + 1], c = indices[3 * f + 2];
+        if (lod_face_class(a, b, c, (uint32_t)n_vertices) != LOD_FACE_CANDIDATE) continue;
+        if (duplicates) {
+            const LodTriple t = lod_canonical(a, b, c);
+            uint64_t at = lod_face_hash(t) & (slots - 1);
+            for (; table[at] != LOD_NONE; at = (at + 1) & (slots - 1)) {
+                const uint32_t* g = indices + 3 * (uint64_t)table[at];
+                if (lod_same_triple(lod_canonical(g[0], g[1], g[2]), t)) break;
+            }
+            if (table[at] != LOD_NONE) continue;
+            table[at] = (uint32_t)f;
+        }
+        kept.push_back((uint32_t)f);
+    }
+    const uint64_t K = kept.size();
+    std::vector<uint32_t> vremap;
+    uint64_t U = n_vertices;
+    if (with_vertices) {
+        vremap.assign((size_t)n_vertices, 0u);
+        for (uint32_t f : kept) for (int k = 0; k < 3; ++k) vremap[indices[3 * (uint64_t)f + k]] = 1u;
+        U = 0;
+        for (uint64_t v = 0; v < n_vertices; ++v) {
+            if (!vremap[v]) { vremap[v] = LOD_NONE; continue; }
+            if (vfirsts_out) vfirsts_out[U] = (uint32_t)v;
+            if (vertices_out) std::memcpy(vertices_out + U * (uint64_t)P.vertex_stride, vertices + v * (uint64_t)P.vertex_stride, (size_t)P.vertex_stride * sizeof(double));
+            vremap[v] = (uint32_t)U++;
+        }
+        if (vfirsts_out) for (uint64_t j = U; j < n_vertices; ++j) vfirsts_out[j] = LOD_NONE;
+        if (vertices_out) std::memset(vertices_out + U * (uint64_t)P.vertex_stride, 0, (size_t)((n_vertices - U) * (uint64_t)P.vertex_stride) * sizeof(double));
+        if (vremap_out) std::memcpy(vremap_out, vremap.data(), (size_t)n_vertices * sizeof(uint32_t));
+    }
+    const uint32_t fill = P.fill == TRGL_CLEAN_FILL_ZERO ? 0u : LOD_NONE;
+    if (indices_out) {
+        for (uint64_t j = 0; j < K; ++j)
+            for (int k = 0; k < 3; ++k) { const uint32_t i = indices[3 * (uint64_t)kept[j] + k]; indices_out[3 * j + k] = with_vertices ? vremap[i] : i; }
+        for (uint64_t i = 3 * K; i < 3 * n_faces; ++i) indices_out[i] = fill;
+    }
+    if (face_firsts_out) {
+        for (uint64_t j = 0; j < K; ++j) face_firsts_out[j] = kept[j];
+        for (uint64_t j = K; j < n_faces; ++j) face_firsts_out[j] = LOD_NONE;
+    }
+    counts[0] = K; counts[1] = U;
+}
+
+// The composition the header writes down: (a) the weld by position, (b) the means of the referenced members in ascending old number,
+// (c) the clean with both flags; then the two maps put together.
+void host_mesh_simplify(const trgl_simplify_params& P, const double* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                        uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out, uint32_t* face_firsts_out,
+                        uint64_t counts[2]) {
+    const uint64_t S = (uint64_t)P.vertex_stride, M = (uint64_t)P.mean_count;
+    trgl_weld_params W{};
+    W.vertex_stride = P.vertex_stride; W.key_offset = 0; W.key_count = 3; W.cell = P.cell;
+    std::vector<uint32_t> remap((size_t)n_vertices), firsts((size_t)n_vertices), welded_indices((size_t)(3 * n_faces));
+    std::vector<double> records(vertices_out ? (size_t)(n_vertices * S) : 0);
+    const uint64_t U = host_mesh_weld(W, vertices, n_vertices, n_faces ? indices : nullptr, n_faces, remap.data(), firsts.data(),
+                                      vertices_out ? records.data() : nullptr, n_faces ? welded_indices.data() : nullptr);
+    if (M && vertices_out) {
+        std::vector<uint8_t> referenced((size_t)n_vertices, 0);
+        for (uint64_t i = 0; i < 3 * n_faces; ++i) referenced[indices[i]] = 1;
+        std::vector<uint32_t> count((size_t)U, 0u), first((size_t)U, 0u);
+        std::vector<double> sum((size_t)(U * M));
+        for (uint64_t v = 0; v < n_vertices; ++v) {                      // ascending old number
+            if (!referenced[v]) continue;
+            const uint64_t j = remap[v];
+            const double* r = vertices + v * S;
+            if (count[j] == 0) { first[j] = (uint32_t)v; for (uint64_t a = 0; a < M; ++a) sum[j * M + a] = r[a]; }
+            else for (uint64_t a = 0; a < M; ++a) sum[j * M + a] = lod_mean_add(sum[j * M + a], r[a]);
+            ++count[j];
+        }
+        for (uint64_t j = 0; j < U; ++j) {
+            if (count[j] == 1) std::memcpy(records.data() + j * S, vertices + (uint64_t)first[j] * S, (size_t)M * sizeof(double));
+            else if (count[j] > 1) for (uint64_t a = 0; a < M; ++a) records[j * S + a] = lod_mean_div(sum[j * M + a], count[j]);
+        }
+    }
+    trgl_clean_params C{};
+    C.vertex_stride = P.vertex_stride; C.flags = TRGL_CLEAN_DUPLICATES | TRGL_CLEAN_VERTICES; C.fill = P.fill;
+    std::vector<uint32_t> vremap(remap_out ? (size_t)n_vertices : 0), vfirsts(firsts_out ? (size_t)n_vertices : 0);
+    host_mesh_clean(C, welded_indices.data(), n_faces, records.data(), n_vertices, indices_out, face_firsts_out, remap_out ? vremap.data() : nullptr,
+                    firsts_out ? vfirsts.data() : nullptr, vertices_out, counts);
+    if (remap_out) for (uint64_t v = 0; v < n_vertices; ++v) remap_out[v] = vremap[remap[v]];
+    if (firsts_out) for (uint64_t j = 0; j < n_vertices; ++j) firsts_out[j] = vfirsts[j] == LOD_NONE ? LOD_NONE : firsts[vfirsts[j]];
 }
 
 // ---- mesh subdivision in host memory (include/trgl.h, trgl_subdiv_topology / trgl_subdiv_vertices; the rules are subdiv_core.h's) ----

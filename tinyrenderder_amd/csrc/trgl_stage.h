@@ -46,6 +46,18 @@ inline bool aligned(std::initializer_list<AlignedTo> list) {
     return true;
 }
 
+// a byte range of a call, and the rule that every output lies apart from every input and from every other output
+struct ByteRange { const void* p; uint64_t bytes; };
+inline int check_apart(trgl_ctx* c, const std::string& w, std::initializer_list<ByteRange> ins, std::initializer_list<ByteRange> outs) {
+    for (const ByteRange& i : ins)
+        for (const ByteRange& o : outs)
+            if (arrays_overlap(i.p, i.bytes, o.p, o.bytes)) return fail(c, TRGL_E_INVALID, w + "an output overlaps an input");
+    for (const ByteRange* x = outs.begin(); x != outs.end(); ++x)
+        for (const ByteRange* y = x + 1; y != outs.end(); ++y)
+            if (arrays_overlap(x->p, x->bytes, y->p, y->bytes)) return fail(c, TRGL_E_INVALID, w + "two outputs overlap");
+    return TRGL_OK;
+}
+
 // The device memory of one call.  arena: the per-flush arena - a draw's, which must hold a StageHold until trgl_draw has its arrays.
 // Else buffers of the call's own that go with this object (a stage-only call: nothing is left staged for a flush that may never come);
 // work queued on them is waited for first: done() on the way out of a call that succeeded.

@@ -1,7 +1,8 @@
 // trgl_stage_mesh.cpp — the stages over an indexed mesh and the draws behind them: the vertex stage (trgl_draw_indexed,
 // trgl_draw_indexed_vs, trgl_vertex_stage), the clip stage (trgl_clip_stage, trgl_draw_clipped, trgl_draw_indexed_vs_clipped) and
 // skeletal animation (trgl_skin_stage, trgl_pose_palette, trgl_draw_skinned), mesh edges (trgl_mesh_edges, trgl_edge_select,
-// trgl_draw_outline), mesh subdivision (trgl_subdiv_topology, trgl_subdiv_vertices, trgl_draw_subdivided) and mesh welding (trgl_mesh_weld).
+// trgl_draw_outline), mesh subdivision (trgl_subdiv_topology, trgl_subdiv_vertices, trgl_draw_subdivided) mesh welding (trgl_mesh_weld)
+// and mesh levels of detail (trgl_mesh_clean, trgl_mesh_simplify).
 // The draws they make go through trgl_draw (trgl_api.cpp), which owns the queue and its ordering rules.
 #include <algorithm>
 #include <cmath>
@@ -12,6 +13,7 @@
 #include "edge_core.h"
 #include "subdiv_core.h"
 #include "weld_core.h"
+#include "lod_core.h"
 
 // The vertex stage of `vs` (-1: k_vertex_stage) over an indexed mesh in device memory, queued on the context's stream.  clip and
 // vary (unused when K = 0) are 16-byte aligned; u == nullptr: zeros, texture slots -1.
@@ -319,16 +321,16 @@ static int check_weld_arrays(trgl_ctx* c, const std::string& w, const trgl_weld_
     if (a.indices_out && !a.indices) return fail(c, TRGL_E_INVALID, w + "indices_out needs indices");
     if (!aligned({ { a.vertices, 8 }, { a.vertices_out, 8 }, { a.indices, 4 }, { a.remap, 4 }, { a.firsts, 4 }, { a.indices_out, 4 } }))
         return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 4 for 32-bit words)");
-    struct Range { const void* p; uint64_t bytes; };
     const uint64_t rec = a.n_vertices * (uint64_t)P.vertex_stride * 8;
-    const Range ins[2] = { { a.vertices, rec }, { a.indices, a.n_faces * 12 } };
-    const Range outs[4] = { { a.remap, a.n_vertices * 4 }, { a.firsts, a.n_vertices * 4 }, { a.vertices_out, rec }, { a.indices_out, a.n_faces * 12 } };
-    for (const Range& i : ins)
-        for (const Range& o : outs)
-            if (arrays_overlap(i.p, i.bytes, o.p, o.bytes)) return fail(c, TRGL_E_INVALID, w + "an output overlaps an input");
-    for (int x = 0; x < 4; ++x)
-        for (int y = x + 1; y < 4; ++y)
-            if (arrays_overlap(outs[x].p, outs[x].bytes, outs[y].p, outs[y].bytes)) return fail(c, TRGL_E_INVALID, w + "two outputs overlap");
+    return check_apart(c, w, { { a.vertices, rec }, { a.indices, a.n_faces * 12 } },
+                       { { a.remap, a.n_vertices * 4 }, { a.firsts, a.n_vertices * 4 }, { a.vertices_out, rec }, { a.indices_out, a.n_faces * 12 } });
+}
+
+// ---- mesh levels of detail (include/trgl.h: trgl_mesh_clean, trgl_mesh_simplify) ----
+// the counts of a mesh that both calls accept
+static int check_lod_counts(trgl_ctx* c, const std::string& w, uint64_t n_vertices, uint64_t n_faces) {
+    if (n_vertices > 0x7fffffffull) return fail(c, TRGL_E_UNSUPPORTED, w + "n_vertices above 2^31 - 1");
+    if (n_faces > 0x7fffffffull / 3) return fail(c, TRGL_E_UNSUPPORTED, w + "3 * n_faces above 2^31 - 1");
     return TRGL_OK;
 }
 
@@ -785,6 +787,181 @@ int trgl_debug_weld_hash(const trgl_weld_params* P, const double* vertices, uint
     if (int r = check_weld_params(nullptr, w, P, n_vertices, 0, TRGL_MEM_HOST)) return r;
     if (n_vertices && (!vertices || !hashes_out)) return fail(nullptr, TRGL_E_INVALID, w + "null array");
     for (uint64_t v = 0; v < n_vertices; ++v) hashes_out[v] = weld_hash(vertices + v * (uint64_t)P->vertex_stride, P->key_offset, P->key_count, P->cell);
+    return TRGL_OK;
+}
+
+int trgl_mesh_clean(trgl_ctx* c, const trgl_clean_params* P, const uint32_t* indices, uint64_t n_faces, const double* vertices, uint64_t n_vertices,
+                    int mem_kind, uint32_t* indices_out, uint32_t* face_firsts_out, uint32_t* vremap_out, uint32_t* vfirsts_out, double* vertices_out,
+                    uint64_t* counts) {
+    const std::string w = "trgl_mesh_clean: ";
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    int r = check_mem(c, w, mem_kind); if (r) return r;
+    if (P->reserved32 || P->reserved) return fail(c, TRGL_E_INVALID, w + "reserved must be 0");
+    if (P->flags & ~(TRGL_CLEAN_DUPLICATES | TRGL_CLEAN_VERTICES)) return fail(c, TRGL_E_INVALID, w + "unknown flags");
+    if (P->fill != TRGL_CLEAN_FILL_NONE && P->fill != TRGL_CLEAN_FILL_ZERO) return fail(c, TRGL_E_INVALID, w + "unknown fill");
+    const bool with_vertices = (P->flags & TRGL_CLEAN_VERTICES) != 0;
+    if (!with_vertices && (vremap_out || vfirsts_out || vertices_out))
+        return fail(c, TRGL_E_INVALID, w + "vremap_out, vfirsts_out and vertices_out need TRGL_CLEAN_VERTICES");
+    if (vertices_out && P->vertex_stride < 1) return fail(c, TRGL_E_INVALID, w + "vertex_stride must be >= 1");
+    if ((r = check_lod_counts(c, w, n_vertices, n_faces))) return r;
+    const uint64_t rec = vertices_out ? (uint64_t)P->vertex_stride * 8 : 0;
+    if (!mul_fits(n_vertices, rec, 1ull << 60)) return fail(c, TRGL_E_UNSUPPORTED, w + "the vertex array is too large");
+    if (n_vertices == 0) {
+        if (n_faces) return fail(c, TRGL_E_INVALID, w + "faces without vertices");
+        if (counts) counts[0] = counts[1] = 0;
+        return TRGL_OK;
+    }
+    if (n_faces && !indices) return fail(c, TRGL_E_INVALID, w + "indices is null");
+    if (vertices_out && !vertices) return fail(c, TRGL_E_INVALID, w + "vertices_out needs vertices");
+    if (!aligned({ { vertices, 8 }, { vertices_out, 8 }, { indices, 4 }, { indices_out, 4 }, { face_firsts_out, 4 }, { vremap_out, 4 }, { vfirsts_out, 4 } }))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 4 for 32-bit words)");
+    if ((r = check_apart(c, w, { { indices, n_faces * 12 }, { vertices_out ? vertices : nullptr, n_vertices * rec } },
+                             { { indices_out, n_faces * 12 }, { face_firsts_out, n_faces * 4 }, { vremap_out, n_vertices * 4 }, { vfirsts_out, n_vertices * 4 },
+                               { vertices_out, n_vertices * rec } }))) return r;
+    if (mem_kind == TRGL_MEM_HOST) {
+        if (!all_below(indices, 3 * n_faces, n_vertices)) return fail(c, TRGL_E_INVALID, w + "index out of range");
+        return no_bad_alloc(c, w, [&] {
+            uint64_t k[2];
+            host_mesh_clean(*P, indices, n_faces, vertices, n_vertices, indices_out, face_firsts_out, vremap_out, vfirsts_out, vertices_out, k);
+            if (counts) { counts[0] = k[0]; counts[1] = k[1]; }
+            return TRGL_OK;
+        });
+    }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    if (n_faces == 0 && !with_vertices) {
+        if (counts) { counts[0] = 0; counts[1] = n_vertices; }
+        return TRGL_OK;
+    }
+    size_t bytes = 0;
+    HIPCHK(c, mesh_clean_scratch_bytes((uint32_t)n_faces, (uint32_t)n_vertices, c->lod_hash_bits, &bytes));
+    if ((r = c->lod_scratch.grow(c, bytes))) return r;
+    CleanArgs k; std::memset(&k, 0, sizeof(k));
+    k.P = *P; k.indices = indices; k.vertices = vertices;
+    k.indices_out = indices_out; k.face_firsts_out = face_firsts_out; k.vremap_out = vremap_out; k.vfirsts_out = vfirsts_out; k.vertices_out = vertices_out;
+    k.n_faces = (uint32_t)n_faces; k.n_vertices = (uint32_t)n_vertices; k.hash_bits = c->lod_hash_bits;
+    const unsigned long long* totals = nullptr;
+    HIPCHK(c, launch_mesh_clean(c->stream, k, c->lod_scratch.p, c->lod_scratch.cap, &totals));
+    if (counts) {
+        unsigned long long got[2] = { 0, 0 };
+        HIPCHK(c, hipMemcpyAsync(got, totals, sizeof(got), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait, at load time
+        counts[0] = got[0]; counts[1] = with_vertices ? got[1] : n_vertices;
+    }
+    return TRGL_OK;
+}
+
+int trgl_mesh_simplify(trgl_ctx* c, const trgl_simplify_params* P, const double* vertices, uint64_t n_vertices, const uint32_t* indices, uint64_t n_faces,
+                       int mem_kind, uint32_t* remap_out, uint32_t* firsts_out, double* vertices_out, uint32_t* indices_out, uint32_t* face_firsts_out,
+                       uint64_t* counts) {
+    const std::string w = "trgl_mesh_simplify: ";
+    if (!P) return fail(c, TRGL_E_INVALID, w + "params is null");
+    int r = check_mem(c, w, mem_kind); if (r) return r;
+    if (P->reserved32 || P->reserved) return fail(c, TRGL_E_INVALID, w + "reserved must be 0");
+    if (P->fill != TRGL_CLEAN_FILL_NONE && P->fill != TRGL_CLEAN_FILL_ZERO) return fail(c, TRGL_E_INVALID, w + "unknown fill");
+    if (P->vertex_stride < 3) return fail(c, TRGL_E_INVALID, w + "vertex_stride must be >= 3");
+    if (P->mean_count < 0 || P->mean_count > P->vertex_stride) return fail(c, TRGL_E_INVALID, w + "mean_count must be 0 .. vertex_stride");
+    if (!(P->cell >= 0.0) || std::isinf(P->cell)) return fail(c, TRGL_E_INVALID, w + "cell must be 0 or a finite positive width");
+    if ((r = check_lod_counts(c, w, n_vertices, n_faces))) return r;
+    const uint64_t rec = (uint64_t)P->vertex_stride * 8;
+    if (!mul_fits(n_vertices, rec, 1ull << 60)) return fail(c, TRGL_E_UNSUPPORTED, w + "the vertex array is too large");
+    if (n_vertices == 0) {
+        if (n_faces) return fail(c, TRGL_E_INVALID, w + "faces without vertices");
+        if (counts) counts[0] = counts[1] = 0;
+        return TRGL_OK;
+    }
+    if (!vertices) return fail(c, TRGL_E_INVALID, w + "vertices is null");
+    if (n_faces && !indices) return fail(c, TRGL_E_INVALID, w + "indices is null");
+    if (!aligned({ { vertices, 8 }, { vertices_out, 8 }, { indices, 4 }, { remap_out, 4 }, { firsts_out, 4 }, { indices_out, 4 }, { face_firsts_out, 4 } }))
+        return fail(c, TRGL_E_INVALID, w + "arrays need natural alignment (8 bytes for doubles, 4 for 32-bit words)");
+    if ((r = check_apart(c, w, { { vertices, n_vertices * rec }, { indices, n_faces * 12 } },
+                             { { remap_out, n_vertices * 4 }, { firsts_out, n_vertices * 4 }, { vertices_out, n_vertices * rec }, { indices_out, n_faces * 12 },
+                               { face_firsts_out, n_faces * 4 } }))) return r;
+    if (mem_kind == TRGL_MEM_HOST) {
+        if (!all_below(indices, 3 * n_faces, n_vertices)) return fail(c, TRGL_E_INVALID, w + "index out of range");
+        return no_bad_alloc(c, w, [&] {
+            uint64_t k[2];
+            host_mesh_simplify(*P, vertices, n_vertices, indices, n_faces, remap_out, firsts_out, vertices_out, indices_out, face_firsts_out, k);
+            if (counts) { counts[0] = k[0]; counts[1] = k[1]; }
+            return TRGL_OK;
+        });
+    }
+    CHKCTX(c);
+    if ((r = end_pending_raster(c))) return r;
+    // the arrays between the weld, the mean and the clean: the weld's map, first occurrences, indices and records, the clean's two maps,
+    // the referenced words of the mean
+    const uint32_t n = (uint32_t)n_vertices, F = (uint32_t)n_faces;
+    const size_t words = scratch_align256((size_t)n * 4), rec_bytes = vertices_out ? scratch_align256((size_t)(n_vertices * rec)) : 0;
+    size_t weld_bytes = 0, clean_bytes = 0;
+    HIPCHK(c, mesh_weld_scratch_bytes(n, c->weld_hash_bits, &weld_bytes));
+    HIPCHK(c, mesh_clean_scratch_bytes(F, n, c->lod_hash_bits, &clean_bytes));
+    if ((r = c->weld_scratch.grow(c, weld_bytes)) || (r = c->lod_scratch.grow(c, clean_bytes)) ||
+        (r = c->lod_work.grow(c, 5 * words + scratch_align256((size_t)F * 12) + rec_bytes))) return r;
+    uint8_t* p = c->lod_work.p;
+    uint32_t* weld_remap = (uint32_t*)p; uint32_t* weld_firsts = (uint32_t*)(p + words); uint32_t* vremap = (uint32_t*)(p + 2 * words);
+    uint32_t* vfirsts = (uint32_t*)(p + 3 * words); uint32_t* referenced = (uint32_t*)(p + 4 * words);
+    uint32_t* weld_indices = (uint32_t*)(p + 5 * words);
+    double* records = vertices_out ? (double*)(p + 5 * words + scratch_align256((size_t)F * 12)) : nullptr;
+    WeldArgs k; std::memset(&k, 0, sizeof(k));
+    k.P.vertex_stride = P->vertex_stride; k.P.key_offset = 0; k.P.key_count = 3; k.P.cell = P->cell;
+    k.vertices = vertices; k.indices = F ? indices : nullptr;
+    k.remap_out = weld_remap; k.firsts_out = weld_firsts; k.vertices_out = records; k.indices_out = F ? weld_indices : nullptr;
+    k.n = n; k.n_idx = 3 * F; k.hash_bits = c->weld_hash_bits;
+    const unsigned long long* unused = nullptr;
+    HIPCHK(c, launch_mesh_weld(c->stream, k, c->weld_scratch.p, c->weld_scratch.cap, &unused));
+    if (P->mean_count > 0 && records)
+        HIPCHK(c, launch_lod_mean(c->stream, vertices, P->vertex_stride, P->mean_count, n, indices, 3 * F, c->weld_scratch.p, c->weld_hash_bits, referenced,
+                                  records));
+    CleanArgs q; std::memset(&q, 0, sizeof(q));
+    q.P.vertex_stride = P->vertex_stride; q.P.flags = TRGL_CLEAN_DUPLICATES | TRGL_CLEAN_VERTICES; q.P.fill = P->fill;
+    q.indices = weld_indices; q.vertices = records;
+    q.indices_out = indices_out; q.face_firsts_out = face_firsts_out; q.vremap_out = vremap; q.vfirsts_out = vfirsts; q.vertices_out = vertices_out;
+    q.n_faces = F; q.n_vertices = n; q.hash_bits = c->lod_hash_bits;
+    const unsigned long long* totals = nullptr;
+    HIPCHK(c, launch_mesh_clean(c->stream, q, c->lod_scratch.p, c->lod_scratch.cap, &totals));
+    HIPCHK(c, launch_lod_compose(c->stream, n, weld_remap, vremap, remap_out, weld_firsts, vfirsts, firsts_out));
+    if (counts) {
+        unsigned long long got[2] = { 0, 0 };
+        HIPCHK(c, hipMemcpyAsync(got, totals, sizeof(got), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));       // the one wait, at load time
+        counts[0] = got[0]; counts[1] = got[1];
+    }
+    return TRGL_OK;
+}
+
+// Test hook, not part of include/trgl.h (tests/test_lod_gpu.py): later device cleans and simplifies of this context keep only the low
+// `bits` bits of the face hash (0 .. 64; 64 is the default) and sort over that many - small values force the walk through a run of
+// colliding triples, 0 puts every face in one run.  The outputs do not change with it.
+int trgl_debug_lod_hash_bits(trgl_ctx* c, int bits) {
+    CHKCTX(c);
+    if (bits < 0 || bits > 64) return fail(c, TRGL_E_INVALID, "trgl_debug_lod_hash_bits: bits must be 0 .. 64");
+    c->lod_hash_bits = bits;
+    return TRGL_OK;
+}
+
+// Diagnostic, not part of include/trgl.h (profiles/lod_probe.py): the radix sort of the last trgl_mesh_clean call with these counts again,
+// over the pairs it left in the context's scratch - the floor that call is measured against.  Queued, no wait.
+int trgl_debug_lod_sort(trgl_ctx* c, uint64_t n_faces, uint64_t n_vertices) {
+    CHKCTX(c);
+    if (n_faces == 0 || n_faces > 0x7fffffffull / 3 || n_vertices == 0 || n_vertices > 0x7fffffffull || c->lod_hash_bits < 1)
+        return fail(c, TRGL_E_INVALID, "trgl_debug_lod_sort: bad counts, or no hash bits to sort");
+    size_t bytes = 0;
+    HIPCHK(c, mesh_clean_scratch_bytes((uint32_t)n_faces, (uint32_t)n_vertices, c->lod_hash_bits, &bytes));
+    if (c->lod_scratch.cap < bytes) return fail(c, TRGL_E_STATE, "trgl_debug_lod_sort: no trgl_mesh_clean call of this size came before");
+    HIPCHK(c, launch_mesh_clean_sort(c->stream, (uint32_t)n_faces, (uint32_t)n_vertices, c->lod_hash_bits, c->lod_scratch.p, c->lod_scratch.cap));
+    return TRGL_OK;
+}
+
+// Test hook, not part of include/trgl.h (tests/lod_cases.py): what the device path sorts face f of a host array by - lod_core.h's hash of
+// its canonical triple, or of its own number when it is invalid or degenerate
+int trgl_debug_lod_face_hash(const uint32_t* indices, uint64_t n_faces, uint64_t n_vertices, uint64_t* hashes_out) {
+    const std::string w = "trgl_debug_lod_face_hash: ";
+    if (int r = check_lod_counts(nullptr, w, n_vertices, n_faces)) return r;
+    if (n_faces && (!indices || !hashes_out)) return fail(nullptr, TRGL_E_INVALID, w + "null array");
+    for (uint64_t f = 0; f < n_faces; ++f) {
+        const uint32_t a = indices[3 * f], b = indices[3 * f + 1], d = indices[3 * f + 2];
+        hashes_out[f] = lod_face_class(a, b, d, (uint32_t)n_vertices) == LOD_FACE_CANDIDATE ? lod_face_hash(lod_canonical(a, b, d)) : lod_dropped_hash((uint32_t)f);
+    }
     return TRGL_OK;
 }
 

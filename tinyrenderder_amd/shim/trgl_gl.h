@@ -937,6 +937,51 @@ inline bool gl_mesh_weld(const trgl_weld_params& params, std::vector<double>& ve
     return true;
 }
 
+// Mesh levels of detail (include/trgl.h, trgl_mesh_clean / trgl_mesh_simplify): what stands where Model would have asked Assimp for
+// aiProcess_FindDegenerates- and aiProcess_OptimizeMeshes-style steps - on the host, no context needed.
+// gl_mesh_clean: the faces of `indices` (3 per face) with two equal indices are dropped, and with `duplicates` those whose three indices,
+// rotated, an earlier face has (a mirrored face stays); then the vertices (records of `stride` doubles) that no kept face names:
+// both vectors shrink, the kept faces and vertices stay in their order, and remap[v] is the new number of old vertex v or 0xFFFFFFFF.
+// gl_mesh_simplify: one level of vertex clustering - the vertices whose positions (the first 3 doubles) share a cell of the grid of width
+// `cell` become one, the first mean_count doubles of its record the mean of the cell's vertices that a face names, the rest the lowest-
+// numbered one's; then gl_mesh_clean.  A call that fails (gl_last_error()) leaves the three vectors as they were.
+inline bool gl_mesh_clean(int stride, std::vector<double>& vertices, std::vector<unsigned int>& indices, std::vector<std::uint32_t>& remap,
+                          bool duplicates = true) {
+    static_assert(sizeof(unsigned int) == sizeof(std::uint32_t), "indices are 32-bit");
+    trgl_clean_params p{};
+    p.vertex_stride = stride; p.flags = TRGL_CLEAN_VERTICES | (duplicates ? TRGL_CLEAN_DUPLICATES : 0u); p.fill = TRGL_CLEAN_FILL_NONE;
+    const std::size_t n = vertices.size() / std::size_t(stride > 0 ? stride : 1);
+    std::vector<double> kept(vertices.size());
+    std::vector<unsigned int> faces(indices.size());
+    std::vector<std::uint32_t> map(n);
+    std::uint64_t counts[2] = { 0, 0 };
+    const int rc = trgl_mesh_clean(nullptr, &p, indices.empty() ? nullptr : reinterpret_cast<const std::uint32_t*>(indices.data()), indices.size() / 3,
+                                   vertices.data(), n, TRGL_MEM_HOST, indices.empty() ? nullptr : reinterpret_cast<std::uint32_t*>(faces.data()), nullptr,
+                                   map.data(), nullptr, kept.data(), counts);
+    if (rc != TRGL_OK) return trgl_shim::fail("gl_mesh_clean", rc, nullptr);
+    faces.resize(std::size_t(counts[0]) * 3); kept.resize(std::size_t(counts[1]) * std::size_t(stride));
+    vertices.swap(kept); indices.swap(faces); remap.swap(map);
+    return true;
+}
+inline bool gl_mesh_simplify(int stride, double cell, int mean_count, std::vector<double>& vertices, std::vector<unsigned int>& indices,
+                             std::vector<std::uint32_t>& remap) {
+    static_assert(sizeof(unsigned int) == sizeof(std::uint32_t), "indices are 32-bit");
+    trgl_simplify_params p{};
+    p.vertex_stride = stride; p.mean_count = mean_count; p.fill = TRGL_CLEAN_FILL_NONE; p.cell = cell;
+    const std::size_t n = vertices.size() / std::size_t(stride > 0 ? stride : 1);
+    std::vector<double> kept(vertices.size());
+    std::vector<unsigned int> faces(indices.size());
+    std::vector<std::uint32_t> map(n);
+    std::uint64_t counts[2] = { 0, 0 };
+    const int rc = trgl_mesh_simplify(nullptr, &p, vertices.data(), n, indices.empty() ? nullptr : reinterpret_cast<const std::uint32_t*>(indices.data()),
+                                      indices.size() / 3, TRGL_MEM_HOST, map.data(), nullptr, kept.data(),
+                                      indices.empty() ? nullptr : reinterpret_cast<std::uint32_t*>(faces.data()), nullptr, counts);
+    if (rc != TRGL_OK) return trgl_shim::fail("gl_mesh_simplify", rc, nullptr);
+    faces.resize(std::size_t(counts[0]) * 3); kept.resize(std::size_t(counts[1]) * std::size_t(stride));
+    vertices.swap(kept); indices.swap(faces); remap.swap(map);
+    return true;
+}
+
 // Run everything submitted so far and bring the pixels back into the caller's TGAImage (before framebuffer.get(),
 // write_tga_file(), main.cpp:743,773).  The depths follow on demand through the `zbuffer` proxy.
 // false: something submitted since the last gl_flush() failed (gl_last_error()); the pixels hold what could be drawn.
